@@ -10,11 +10,19 @@ A "step" = one episode batch through the hot path: `--episodes` (default 8 x --g
 tuples to rank 0 THROUGH THE C ABI (az_comm_init + az_gather_samples on the engine's stream: the product's collective, not a
 torch.distributed stand-in).  Weak scaling: per-GPU work is fixed; `value` = all ranks' games / max-over-ranks time.
 
-Two passes, both named in `config.passes`: the TIMED region runs with the engine's HIP-event brackets off (its search loop replays
-hipGraphs, as any embedding host's would); a separate profiled pass of the same call afterwards (brackets on every
-`--profile-every`th simulation step) gives the live per-kernel times behind "roofline" (the dominant kernel, conv3 on the matrix
-cores) and "kernels".  "cpu_baseline" = the CPU oracle driving the same search with the same f32 net on torch-CPU, bounded
-sample, rank 0 at N=1 only.
+A plain run (`--steps N --warmup W`) sets up, warms up, times the N steps, writes the last timed step's outputs if
+`--dump-outputs DIR` is given, and prints the result line.  The TIMED region runs with the engine's HIP-event brackets off (its
+search loop replays hipGraphs, as any embedding host's would).  Everything else the benchmark measures runs only with `--full`,
+after the timed region: a separate profiled pass of the same call (brackets on every `--profile-every`th simulation step; named in
+`config.passes`) gives "per_call" and the live per-kernel times behind "roofline" (the dominant kernel, conv3 on the matrix cores),
+"kernels", "conv2_table" and "tree_hbm"; "cpu_baseline" = the CPU oracle driving the same search with the same f32 net on
+torch-CPU, bounded sample, rank 0 at N=1 only; "nnet_train", "no_dedup", "mfma_conv2", "arena" and "config1_dropin" are the
+auxiliary probes.  The `--no-*` switches drop single parts of `--full`.
+
+--dump-outputs DIR: what the last timed step handed its caller (rank 0's), as DIR/<name>.npy in float32 / float64:
+states (the u64 bitboard pairs, exact in float64), pis, zs -- a seeded sample of DUMP_TUPLES tuples when the step emitted more,
+their row numbers in `tuple_rows` -- and game_len, moves per episode (a seeded sample of DUMP_EPISODES episodes when there are
+more, their indices in `episode_rows`).  Same arguments, same inputs: two builds can be compared array for array.
 """
 import argparse
 import json
@@ -33,6 +41,8 @@ HBM_PEAK_GBS = 8000.0
 FLOP_PER_LEAF = 328_986_624  # the net as dense arithmetic
 # with conv1 and conv2 as table lookups (az_set_option "conv2_table", the default) those two layers' flops are never executed
 FLOP_PER_LEAF_TABLES = FLOP_PER_LEAF - 2 * 42 * 18 * 512 - 2 * 42 * 512 * 4608
+DUMP_TUPLES = 1 << 18        # --dump-outputs caps: at most ~27 MB in all
+DUMP_EPISODES = 1 << 16
 
 
 def cpu_baseline(params, channels, sims, mean_plies=None, budget_s=20.0, seed=1):
@@ -160,6 +170,30 @@ def committed_pmc():
         return None, None
 
 
+def dump_outputs(d, r, n):
+    """--dump-outputs: the last timed step's result `r` (n tuples) as float32 / float64 .npy files under d; larger outputs as
+    a fixed, seeded sample of rows (module docstring)."""
+    import torch
+
+    def sample(total, cap, seed):
+        if total <= cap:
+            return np.arange(total)
+        return np.sort(np.random.default_rng(seed).choice(total, cap, replace=False))
+    rows = sample(n, DUMP_TUPLES, 0)
+    eps = sample(r["game_len"].shape[0], DUMP_EPISODES, 1)
+    idx = torch.from_numpy(rows).to(r["states"].device)
+    states = r["states"][idx].cpu().numpy()
+    if states.size and (states.min() < 0 or states.max() >= 2**53):
+        raise RuntimeError("--dump-outputs: a state does not fit a float64 exactly")
+    arrays = {"states": states.astype(np.float64), "pis": r["pis"][idx].cpu().numpy().astype(np.float32),
+              "zs": r["zs"][idx].cpu().numpy().astype(np.float32), "tuple_rows": rows.astype(np.float64),
+              "game_len": r["game_len"][eps].astype(np.float32), "moves": r["moves"][eps].astype(np.float32),
+              "episode_rows": eps.astype(np.float64)}
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def self_launch(n):
     """`python3 bench.py --gpus N` without torchrun: start N ranks (one per GPU) under torch.distributed.run as a CHILD
     process -- never an exec, and before anything in this process has initialised the GPU -- and pass its output through.
@@ -227,6 +261,11 @@ def main():
     ap.add_argument("--sims", type=int, default=100)
     ap.add_argument("--net", default="conv", choices=["conv", "stub"])
     ap.add_argument("--channels", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled pass, the CPU baseline, the NNet::train probe and the auxiliary "
+                         "measurements (off: the result line carries the timed region's figures only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64; see the module docstring)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event brackets (roofline = null)")
     ap.add_argument("--profile-every", type=int, default=64, help="bracket every n-th simulation step with HIP events (each bracket idles the GPU a little)")
@@ -241,6 +280,9 @@ def main():
                     help="rehearse the N-rank launcher + gather on CPU over gloo with synthetic tuples (no engine, no GPU; value = 0)")
     args = ap.parse_args()
     episodes = args.episodes or 8 * args.games
+    if not args.full:
+        # a plain run does only what the headline figure needs: the profiled pass, the CPU baseline and the probes come with --full
+        args.no_profile = args.no_cpu_baseline = args.no_train_probe = args.no_aux = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python3 bench.py --gpus N`: this parent never touches the GPU (no torch import, no engine); it starts the
@@ -337,8 +379,10 @@ def main():
             _gs, _gp, gz, counts = e.gather_samples(out["states"][:n], out["pis"][:n], out["zs"][:n], dst=0, is_dst=rank == 0, out=gathered)
             if rank == 0 and int(counts.sum()) != gz.shape[0]:
                 raise RuntimeError("az_gather_samples: count mismatch")
+        last[0] = r
         return n, int(r["game_len"].sum())
 
+    last = [None]
     for i in range(args.warmup):
         step(i)
     e.reset_stats()
@@ -354,6 +398,9 @@ def main():
     st_timed = e.stats()
     if session:
         e.selfplay_end()
+    if args.dump_outputs and rank == 0 and last[0] is not None:
+        # before anything below reuses `out`
+        dump_outputs(args.dump_outputs, last[0], last[0]["count"])
     # the profiled pass (outside the timed region): the same call with the HIP-event brackets on
     prof_s = None
     if not args.no_profile:

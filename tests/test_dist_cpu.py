@@ -141,3 +141,48 @@ def test_sharded_cpp_example_builds_and_rejects_bad_wiring(tmp_path):
                            "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
     assert subprocess.run([exe], capture_output=True).returncode == 2
     assert subprocess.run([exe, "3", "2", os.path.join(tmp_path, "id"), os.path.join(tmp_path, "ck")], capture_output=True).returncode == 2
+
+
+def test_bench_dump_outputs_sampled_and_bounded(tmp_path):
+    """--dump-outputs writes the step's caller-visible arrays in float32 / float64, exactly (bitboards included), as the same
+    seeded sample of rows every time, and stays under 64 MB for a step larger than the caps."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n_eps = bench.DUMP_EPISODES + 7
+    st, pi, z = _fake_samples(0, 160000)
+    n = st.shape[0]
+    assert n > bench.DUMP_TUPLES
+    r = {"states": torch.from_numpy(st), "pis": torch.from_numpy(pi), "zs": torch.from_numpy(z),
+         "game_len": np.arange(n_eps, dtype=np.int32) % 43, "moves": (np.arange(n_eps * 42) % 7).astype(np.uint8).reshape(n_eps, 42)}
+    for d in ("a", "b"):
+        bench.dump_outputs(os.path.join(tmp_path, d), r, n)
+    names = sorted(f for f in os.listdir(os.path.join(tmp_path, "a")))
+    assert names == sorted(k + ".npy" for k in ("states", "pis", "zs", "tuple_rows", "game_len", "moves", "episode_rows"))
+    total = 0
+    for f in names:
+        a, b = np.load(os.path.join(tmp_path, "a", f)), np.load(os.path.join(tmp_path, "b", f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += os.path.getsize(os.path.join(tmp_path, "a", f))
+    assert total <= 64 << 20
+    rows = np.load(os.path.join(tmp_path, "a", "tuple_rows.npy")).astype(np.int64)
+    assert rows.shape == (bench.DUMP_TUPLES,) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(os.path.join(tmp_path, "a", "states.npy")).astype(np.int64), st[rows])
+    assert np.array_equal(np.load(os.path.join(tmp_path, "a", "pis.npy")), pi[rows])
+    assert np.array_equal(np.load(os.path.join(tmp_path, "a", "zs.npy")), z[rows])
+    eps = np.load(os.path.join(tmp_path, "a", "episode_rows.npy")).astype(np.int64)
+    assert eps.shape == (bench.DUMP_EPISODES,)
+    assert np.array_equal(np.load(os.path.join(tmp_path, "a", "moves.npy")), r["moves"][eps].astype(np.float32))
+    assert np.array_equal(np.load(os.path.join(tmp_path, "a", "game_len.npy")), r["game_len"][eps].astype(np.float32))
+
+
+def test_bench_plain_run_defers_the_extras_to_full():
+    """A plain bench.py run measures the timed steps only: the profiled pass, the CPU baseline, the train probe and the
+    auxiliary measurements are switched off unless --full is given."""
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    main = src[src.index("def main():"):]
+    gate = main[main.index("if not args.full:"):main.index("import torch")]
+    for flag in ("args.no_profile", "args.no_cpu_baseline", "args.no_train_probe", "args.no_aux"):
+        assert flag in gate, flag
+    assert '"--full"' in main and '"--dump-outputs"' in main
