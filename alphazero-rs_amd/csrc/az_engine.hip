@@ -8,6 +8,7 @@
 #include <rccl/rccl.h>      // types only: the library is dlopen'ed by az_comm_* (a host that never shards never loads it)
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "az_combine.h"
 #include "az_net.h"
 #include "az_train.h"
 #include "az_tree.h"
@@ -245,6 +247,39 @@ uint32_t hash_entries(int num_sims, int calls) {
     return next_pow2(2ull * ((uint64_t)calls * ((uint64_t)num_sims + 1) + 2));
 }
 
+// ---- shared tree batch (az_tree_share) ----
+// One caller's get_action_prob on its slot.  The follower thread only fills this in and sleeps; the leader reads the state, runs
+// the batch and writes the answer (caller buffers in device memory included), so followers never make a HIP call.
+struct SlotCall {
+    const uint64_t* state;
+    float temp;
+    uint64_t seed, game_id;
+    float* pi;
+    uint16_t* counts;
+    float* q;
+    az_status status;
+};
+struct SlotRunner {
+    az_tree* t;
+    void operator()(CombineBatch<SlotCall>& b) const;
+};
+constexpr size_t SLOT_ERR_LEN = 256;
+struct SharedTrees {
+    SlotCombiner<SlotCall, SlotRunner> comb;
+    DeviceMem mem;
+    SlotReq* d_req = nullptr;        // [G] the batch's request block
+    uint8_t* d_reset = nullptr;      // [G] launch_reset_trees flags
+    void* h_io = nullptr;            // pinned: SlotReq [G] (uploaded with one copy) + SlotOut [G] (written by k_slot_root_policy)
+    SlotReq* h_req = nullptr;
+    SlotOut* h_out = nullptr;
+    // message of each slot's last failed call (az_tree_slot_error); written by the leader of the batch before the owner wakes
+    std::vector<std::array<char, SLOT_ERR_LEN>> err;
+    SharedTrees(int G, az_tree* t) : comb(G, SlotRunner{t}), err((size_t)G) {
+        for (auto& m : err) m[0] = 0;
+    }
+    ~SharedTrees() { if (h_io) (void)hipHostFree(h_io); }
+};
+
 }  // namespace
 
 struct az_engine {
@@ -349,6 +384,7 @@ struct az_tree {
     float* h_pi = nullptr;
     float* h_q = nullptr;
     uint16_t* h_counts = nullptr;
+    std::unique_ptr<SharedTrees> shared;     // az_tree_share: slots driven by many host threads
     ~az_tree() { if (h_io) (void)hipHostFree(h_io); }
 };
 
@@ -720,6 +756,88 @@ struct ScopedTimer {
         e->stats.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 };
+
+void set_slot_error(SharedTrees& sh, int slot, const std::string& msg) {
+    std::snprintf(sh.err[(size_t)slot].data(), SLOT_ERR_LEN, "%s", msg.c_str());
+}
+
+// The leader's batch: every requested slot searches its own tree in ONE run_search over the tree batch (the others are inactive and
+// untouched), then each request gets its own policy, RNG stream and status.  Runs with the combiner unlocked, one leader at a time:
+// this is the only place a shared tree makes HIP calls, and the only place it writes e->err / e->stats.
+void SlotRunner::operator()(CombineBatch<SlotCall>& b) const {
+    az_engine* e = t->e;
+    SharedTrees& sh = *t->shared;
+    const int n = (int)b.slots.size();
+    auto fail_all = [&](az_status st, const std::string& msg) {
+        for (int i = 0; i < n; ++i) { b.reqs[i]->status = st; set_slot_error(sh, b.slots[i], msg); }
+    };
+    NetModel* net;
+    if (az_status st = find_net(e, t->model_id, &net)) { fail_all(st, e->err); return; }
+    TreeDev& d = t->th.d;
+    const int G = d.G;
+    if (az_status st = check_batch(e, *net, G * d.T)) { fail_all(st, e->err); return; }
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        bool any_reset = false;
+        for (int i = 0; i < n; ++i) {
+            const SlotCall& c = *b.reqs[i];
+            SlotReq& r = sh.h_req[i];
+            if (on_device(c.state)) HIPCHK(hipMemcpy(&r.state, c.state, 16, hipMemcpyDeviceToHost));
+            else std::memcpy(&r.state, c.state, 16);
+            r.seed = c.seed; r.game_id = c.game_id; r.temp = c.temp;
+            r.slot = b.slots[i]; r.reset = b.reset[i]; r.pad = 0;
+            any_reset = any_reset || b.reset[i];
+        }
+        HIPCHK(hipMemcpyAsync(sh.d_req, sh.h_req, (size_t)n * sizeof(SlotReq), hipMemcpyHostToDevice, s));
+        launch_slot_arm(d, sh.d_req, n, t->d_root_states, sh.d_reset, s);
+        if (any_reset) launch_reset_trees(d, sh.d_reset, s);      // AsyncMcts::default for the slots acquired since their last batch
+        SearchParams sp{(uint32_t)t->max_depth, (float)t->cpuct};
+        // sized by the whole batch, not by this batch's requests: every batch replays the same captured graph
+        prepare_cache(e, dedup_applies(e, *net), (uint64_t)G * ((uint64_t)t->num_sims + 1), s);
+        run_search(e, t->th, t->d_root_states, t->num_sims, sp, *net, G);
+        launch_slot_root_policy(d, sh.d_req, n, sh.h_out, s);
+        launch_harvest(d, t->th.d_totals, t->th.d_counts, s);
+        launch_call_readback(t->th.d_totals, e->cache.stat, d.err, t->h_rb, s);
+        HIPCHK(hipStreamSynchronize(s));
+        resolve_profile(e);
+        fold_dedup(e, t->h_rb->dd);
+        fold_tree_totals(e, t->h_rb->totals, dedup_applies(e, *net));
+        e->stats.moves += (uint64_t)n;
+        // a capacity error no request could be blamed for (transposition table, node_path) fails the whole batch
+        const uint32_t* err = t->h_rb->err;
+        bool blamed = false;
+        for (int i = 0; i < n; ++i) blamed = blamed || (sh.h_out[i].status & (1u << ERR_CAPACITY));
+        const bool unblamed = !blamed && (err[ERR_CAPACITY] || err[ERR_HASH_FULL] || err[ERR_PATH]);
+        auto copy_out = [&](void* dst, const void* src, size_t bytes) {
+            if (on_device(dst)) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+            else std::memcpy(dst, src, bytes);
+        };
+        for (int i = 0; i < n; ++i) {
+            SlotCall& c = *b.reqs[i];
+            const SlotOut& o = sh.h_out[i];
+            if (unblamed || (o.status & (1u << ERR_CAPACITY))) {
+                c.status = AZ_ERR_CAPACITY;
+                set_slot_error(sh, b.slots[i], err[ERR_HASH_FULL] ? "transposition table full" : err[ERR_PATH] ? "node_path overflow"
+                                                   : "node arena exhausted (reserve too small; src/node.rs:237)");
+                continue;
+            }
+            if (o.status & (1u << ERR_TERMINAL_ROOT)) {
+                c.status = AZ_ERR_TERMINAL_ROOT;
+                set_slot_error(sh, b.slots[i], "get_action_prob on a finished game (src/async_mcts.rs:85)");
+                continue;
+            }
+            copy_out(c.pi, o.pi, 7 * sizeof(float));
+            if (c.counts) copy_out(c.counts, o.counts, 7 * sizeof(uint16_t));
+            if (c.q) copy_out(c.q, o.q, 7 * sizeof(float));
+            c.status = AZ_OK;
+        }
+    } catch (const HipFail& f) {
+        fail_hip(e, f);
+        fail_all(AZ_ERR_HIP, e->err);
+    }
+}
 
 }  // namespace
 
@@ -1272,6 +1390,7 @@ void az_tree_destroy(az_tree* t) {
 az_status az_tree_reset(az_tree* t, const uint64_t* root_states) {
     if (!t) return AZ_ERR_BAD_ARGUMENT;
     az_engine* e = t->e;
+    if (t->shared) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tree_reset on a shared tree batch (its slots belong to their threads)");
     try {
         HIPCHK(hipSetDevice(e->device));
         const ulonglong2* roots = nullptr;
@@ -1289,6 +1408,7 @@ az_status az_tree_reset(az_tree* t, const uint64_t* root_states) {
 
 az_status az_tree_record_evals(az_tree* t, int32_t cap) {
     if (!t || cap < 0) return AZ_ERR_BAD_ARGUMENT;
+    if (t->shared) return fail(t->e, AZ_ERR_BAD_ARGUMENT, "az_tree_record_evals on a shared tree batch (it would rebuild held slots' trees)");
     try {
         HIPCHK(hipSetDevice(t->e->device));
         TreeDev& d = t->th.d;
@@ -1339,6 +1459,7 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
                                   float* pi, uint16_t* counts, float* q) {
     if (!t || !states || !pi) return AZ_ERR_BAD_ARGUMENT;
     az_engine* e = t->e;
+    if (t->shared) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tree_get_action_prob on a shared tree batch: use az_tree_slot_get_action_prob");
     NetModel* net;
     az_status st = find_net(e, t->model_id, &net);
     if (st) return st;
@@ -1380,6 +1501,72 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
         if (q) copy_out(q, t->h_q, (size_t)G * 7 * sizeof(float));
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// ---- shared tree batch: many host threads, one slot (one AsyncMcts) each ---------------------------------------------------
+az_status az_tree_share(az_tree* t, int32_t window_us) {
+    if (!t || window_us < 0) return AZ_ERR_BAD_ARGUMENT;
+    if (t->shared) {                        // already shared: only the window changes
+        t->shared->comb.set_window_us(window_us);
+        return AZ_OK;
+    }
+    az_engine* e = t->e;
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        const int G = t->th.d.G;
+        std::unique_ptr<SharedTrees> sh(new SharedTrees(G, t));
+        sh->d_req = sh->mem.alloc<SlotReq>((size_t)G);
+        sh->d_reset = sh->mem.alloc<uint8_t>((size_t)G);
+        HIPCHK(hipMemset(sh->d_reset, 0, (size_t)G));
+        HIPCHK(hipHostMalloc(&sh->h_io, (size_t)G * (sizeof(SlotReq) + sizeof(SlotOut)), hipHostMallocDefault));
+        sh->h_req = (SlotReq*)sh->h_io;
+        sh->h_out = (SlotOut*)(sh->h_req + G);
+        sh->comb.set_window_us(window_us);
+        HIPCHK(hipStreamSynchronize(e->stream));
+        t->shared = std::move(sh);
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// The slot calls below run on many host threads at once: they touch no engine-wide state (az_last_error included) and make no
+// HIP call except as the batch's leader (SlotRunner).
+az_status az_tree_slot_acquire(az_tree* t, int32_t* slot) {
+    if (!t || !slot || !t->shared) return AZ_ERR_BAD_ARGUMENT;
+    const int s = t->shared->comb.acquire();
+    if (s < 0) return AZ_ERR_CAPACITY;
+    t->shared->err[(size_t)s][0] = 0;
+    *slot = s;
+    return AZ_OK;
+}
+
+az_status az_tree_slot_release(az_tree* t, int32_t slot) {
+    if (!t || !t->shared) return AZ_ERR_BAD_ARGUMENT;
+    return t->shared->comb.release(slot) ? AZ_OK : AZ_ERR_BAD_ARGUMENT;
+}
+
+az_status az_tree_slot_get_action_prob(az_tree* t, int32_t slot, const uint64_t* state, float temp, uint64_t seed, uint64_t game_id,
+                                       float* pi, uint16_t* counts, float* q) {
+    if (!t || !t->shared) return AZ_ERR_BAD_ARGUMENT;
+    SharedTrees& sh = *t->shared;
+    if (!state || !pi) {
+        if (sh.comb.holds(slot)) set_slot_error(sh, slot, "az_tree_slot_get_action_prob: state and pi are required");
+        return AZ_ERR_BAD_ARGUMENT;
+    }
+    SlotCall c{state, temp, seed, game_id, pi, counts, q, AZ_ERR_HIP};
+    if (!sh.comb.submit(slot, &c)) return AZ_ERR_BAD_ARGUMENT;      // out of range, not held, or a call already in flight
+    return c.status;
+}
+
+const char* az_tree_slot_error(const az_tree* t, int32_t slot) {
+    if (!t || !t->shared || slot < 0 || slot >= t->th.d.G) return "";
+    return t->shared->err[(size_t)slot].data();
+}
+
+az_status az_tree_share_stats(az_tree* t, uint64_t* out) {
+    if (!t || !out || !t->shared) return AZ_ERR_BAD_ARGUMENT;
+    const CombineStats cs = t->shared->comb.stats();
+    out[0] = cs.batches; out[1] = cs.requests; out[2] = cs.largest; out[3] = cs.by_window;
+    return AZ_OK;
 }
 
 // ---- Coach::execute_episode x many -----------------------------------------------------------

@@ -201,6 +201,33 @@ void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, Sear
                            hipStream_t s);
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,
                         uint16_t* counts, float* q, hipStream_t s);
+// ---- shared tree batch (az_tree_share): per-request arming and root policy around the unchanged search -----------------------
+// One request of a batch, as the leader uploads it (one copy of the compact block per batch).
+struct SlotReq {
+    ulonglong2 state;     // canonical root of this get_action_prob
+    uint64_t seed;        // tie-break RNG stream (seed, game_id, ply = stones)
+    uint64_t game_id;
+    float temp;
+    int32_t slot;         // tree of the batch
+    uint32_t reset;       // 1: the slot was (re)acquired since its last batch -- rebuild its tree at the initial board first
+    uint32_t pad;
+};
+static_assert(sizeof(SlotReq) == 48, "48-byte request records");
+// One answer, compacted by request, written into pinned host memory.  status = bit mask of ErrIdx blamed on THIS request.
+struct SlotOut {
+    float pi[7];
+    float q[7];
+    uint16_t counts[7];
+    uint16_t pad;
+    uint32_t status;
+    uint32_t pad2;
+};
+static_assert(sizeof(SlotOut) == 80, "80-byte answer records");
+// head.active = 1 for the requested slots and 0 for all others, their root states into roots[slot], reset_flags[slot] = the
+// request's reset bit (0 elsewhere), t.err cleared; slots outside [0, G) are skipped
+void launch_slot_arm(const TreeDev& t, const SlotReq* req, int n, ulonglong2* roots, uint8_t* reset_flags, hipStream_t s);
+// get_action_prob's epilogue for each request with its own temperature and RNG stream (root_policy), plus its status word
+void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s);
 // what one get_action_prob call hands back besides pi / counts / q: written into PINNED host memory by k_call_readback
 struct CallReadback {
     unsigned long long totals[ST_TOTALS];

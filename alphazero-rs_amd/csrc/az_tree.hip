@@ -866,6 +866,61 @@ __global__ __launch_bounds__(64) void k_root_policy(TreeDev t, float temp, uint6
     }
 }
 
+// ---- shared tree batch (az_tree_share) ----------------------------------------------------------------------------------------
+// One workgroup: first every slot goes inactive (and loses its reset flag), then -- after the barrier, so the two phases' stores to
+// one head never race -- the requested slots are armed.  A batch of any size leaves every other tree exactly as it was.
+__global__ __launch_bounds__(1024) void k_slot_arm(TreeDev t, const SlotReq* __restrict__ req, int n, ulonglong2* roots, uint8_t* reset_flags) {
+    for (int g = threadIdx.x; g < t.G; g += blockDim.x) {
+        t.head[g].head.active = 0u;
+        reset_flags[g] = 0;
+    }
+    if (threadIdx.x < ERR_COUNT) t.err[threadIdx.x] = 0u;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const SlotReq r = req[i];
+        if (r.slot < 0 || r.slot >= t.G) continue;
+        t.head[r.slot].head.active = 1u;
+        roots[r.slot] = r.state;
+        reset_flags[r.slot] = r.reset ? 1 : 0;
+    }
+}
+
+// k_root_policy per REQUEST: request i's tree is req[i].slot, its temperature and RNG stream are its own, its answer goes to out[i].
+// status: a failed root (the search left the tree inactive: arena exhausted at the root) or a terminal root is this request's own
+// error; a capacity error raised during the search (t.err) is blamed on every tree of the batch that is that close to full (a tree
+// whose push failed always is: node_upgrade refuses exactly when len + 8 > R or count + 8 > reserve could be exceeded).
+template <class G>
+__global__ __launch_bounds__(64) void k_slot_root_policy(TreeDev t, const SlotReq* __restrict__ req, int n, SlotOut* out) {
+    constexpr int GW = G::GROUP;
+    constexpr int NA = G::ACTIONS;
+    const int tid = blockIdx.x * 64 + threadIdx.x;
+    const int i = tid / GW, sub = tid % GW;
+    if (i >= n) return;
+    const SlotReq r = req[i];
+    if (r.slot < 0 || r.slot >= t.G) return;
+    const int g = r.slot;
+    const size_t base = (size_t)g * t.R;
+    const TreeHead h = head_load(t, g);
+    uint32_t status = 0u;
+    RootPolicy rp{0.0f, 0u, 0.0f};
+    if (!h.active) {
+        status = 1u << ERR_CAPACITY;
+    } else {
+        const uint32_t ecd = (node_load(node_ptr(t, base, h.root)).meta >> META_ECODE_SHIFT) & 3u;
+        const bool full_err = (t.err[ERR_CAPACITY] | t.err[ERR_HASH_FULL]) != 0u;
+        if (ecd != E_NONE) status = 1u << ERR_TERMINAL_ROOT;
+        else if (full_err && (h.len + BLOCK_SLOTS > t.R || h.count + BLOCK_SLOTS > t.reserve_nodes)) status = 1u << ERR_CAPACITY;
+        const typename G::State s = G::unpack(node_key(t, base, h.root));
+        rp = root_policy<G>(t, h.root, g, sub, r.temp, r.seed, r.game_id, (uint64_t)G::stones(s));
+    }
+    if (sub < NA) {
+        out[i].pi[sub] = rp.pi;
+        out[i].q[sub] = rp.q;
+        out[i].counts[sub] = (uint16_t)rp.count;
+    }
+    if (sub == 0) out[i].status = status;
+}
+
 // sums the per-tree counters into totals (one atomicAdd per counter per wave) and clears them
 __global__ __launch_bounds__(256) void k_harvest(TreeDev t, unsigned long long* totals, uint32_t* node_counts) {
     const int g = blockIdx.x * 256 + threadIdx.x;
@@ -1238,6 +1293,13 @@ void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, Sear
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,
                         uint16_t* counts, float* q, hipStream_t s) {
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_root_policy<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, temp, seed, first_game_id, pi, counts, q));
+}
+void launch_slot_arm(const TreeDev& t, const SlotReq* req, int n, ulonglong2* roots, uint8_t* reset_flags, hipStream_t s) {
+    hipLaunchKernelGGL(k_slot_arm, dim3(1), dim3(1024), 0, s, t, req, n, roots, reset_flags);
+}
+void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s) {
+    if (n <= 0) return;
+    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_slot_root_policy<TG>, dim3(group_blocks(n)), dim3(64), 0, s, t, req, n, out));
 }
 void launch_harvest(const TreeDev& t, unsigned long long* totals, uint32_t* node_counts, hipStream_t s) {
     hipLaunchKernelGGL(k_harvest, dim3((t.G + 255) / 256), dim3(256), 0, s, t, totals, node_counts);

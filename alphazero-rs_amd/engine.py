@@ -83,7 +83,8 @@ EXPORTS = [
     "az_net_get_params", "az_net_predict", "az_net_predict_states", "az_net_train", "az_net_train_history",
     "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
-    "az_tree_node_counts", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
+    "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
+    "az_tree_slot_error", "az_tree_share_stats", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
     "az_comm_unique_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
 COMM_ID_BYTES = 128
@@ -125,6 +126,12 @@ def load_library(path=LIB_PATH):
         "az_tree_record_evals": (i32, [vp, i32]),
         "az_tree_get_evals": (i32, [vp, vp, vp, vp, vp]),
         "az_tree_node_counts": (i32, [vp, vp]),
+        "az_tree_share": (i32, [vp, i32]),
+        "az_tree_slot_acquire": (i32, [vp, C.POINTER(i32)]),
+        "az_tree_slot_release": (i32, [vp, i32]),
+        "az_tree_slot_get_action_prob": (i32, [vp, i32, vp, f32, u64, u64, vp, vp, vp]),
+        "az_tree_slot_error": (C.c_char_p, [vp, i32]),
+        "az_tree_share_stats": (i32, [vp, vp]),
         "az_selfplay": (i32, [vp, C.POINTER(az_selfplay_params), C.POINTER(az_samples)]),
         "az_selfplay_begin": (i32, [vp, C.POINTER(az_selfplay_params)]),
         "az_selfplay_next": (i32, [vp, C.c_int32, C.POINTER(az_samples)]),
@@ -502,6 +509,47 @@ class TreeBatch:
         out = np.zeros(self.n_games, np.uint32)
         self.engine._check(self.engine._lib.az_tree_node_counts(self._h, _ptr(out)))
         return out
+
+    # ---- shared tree batch (az_tree_share): one slot per host thread, the threads' calls coalesced into batched searches ----
+    def share(self, window_us=0):
+        """Turn the batch into a shared one; from now on only the slot_* calls drive it.  ctypes releases the GIL during a
+        call, so threading.Threads calling slot_get_action_prob really wait for (and run) batches concurrently."""
+        self.engine._check(self.engine._lib.az_tree_share(self._h, window_us))
+
+    def slot_acquire(self):
+        """AsyncMcts::default on a free slot (its tree starts at the initial board); raises AzError(AZ_ERR_CAPACITY) when all are held."""
+        slot = C.c_int32(-1)
+        st = self.engine._lib.az_tree_slot_acquire(self._h, C.byref(slot))
+        if st != AZ_OK:
+            raise AzError(st, "az_tree_slot_acquire")
+        return slot.value
+
+    def slot_release(self, slot):
+        st = self.engine._lib.az_tree_slot_release(self._h, slot)
+        if st != AZ_OK:
+            raise AzError(st, "az_tree_slot_release: slot out of range or not held")
+
+    def slot_get_action_prob(self, slot, state, temp, seed=0, game_id=0):
+        """get_action_prob on one held slot: state (mine, theirs) canonical -> (pi [7] f32, counts [7] u16, q [7] f32).
+        Blocks until the batch that carries the request has run."""
+        s = np.ascontiguousarray(state, dtype=np.uint64).reshape(2)
+        pi = np.empty(ACTIONS, np.float32)
+        counts = np.empty(ACTIONS, np.uint16)
+        q = np.empty(ACTIONS, np.float32)
+        st = self.engine._lib.az_tree_slot_get_action_prob(self._h, slot, _ptr(s), temp, seed, game_id, _ptr(pi), _ptr(counts), _ptr(q))
+        if st != AZ_OK:
+            raise AzError(st, self.slot_error(slot))
+        return pi, counts, q
+
+    def slot_error(self, slot):
+        msg = self.engine._lib.az_tree_slot_error(self._h, slot)
+        return msg.decode() if msg else ""
+
+    def share_stats(self):
+        """{batches, requests, largest, by_window} since share()."""
+        out = np.zeros(4, np.uint64)
+        self.engine._check(self.engine._lib.az_tree_share_stats(self._h, _ptr(out)))
+        return dict(zip(("batches", "requests", "largest", "by_window"), (int(x) for x in out)))
 
 
 # ---- host-side helpers on canonical bitboards (mirror of the Game trait for Connect Four) ----

@@ -15,7 +15,11 @@
  *   - Every call returns an az_status (0 = ok).  The reference panics instead
  *     (unwrap/assert!); the panic sites map onto the status codes below.
  *   - A handle is used by one host thread at a time; calls are synchronous on
- *     return.  One HIP stream per engine.  Engines on different devices may be
+ *     return.  The one exception is a SHARED tree batch (az_tree_share): its
+ *     slot calls (az_tree_slot_*) are made by many host threads at once, one
+ *     thread per held slot; while any of them is in flight no other call may be
+ *     made on the same engine (or on any of its trees), and az_tree_destroy comes
+ *     only after every slot has been released.  One HIP stream per engine.  Engines on different devices may be
  *     driven from different host threads freely.  Two engines on the SAME device
  *     driven from two threads at once need "search_graph" 0 on both: while one
  *     thread captures its search loop as a hipGraph, HIP refuses the blocking
@@ -261,6 +265,34 @@ az_status az_tree_reset(az_tree* t, const uint64_t* root_states);
  * RNG (temp == 0 tie-break) = stream (seed, first_game_id + g, ply = stones on board). */
 az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp, uint64_t seed,
                                   uint64_t first_game_id, float* pi, uint16_t* counts, float* q);
+/* ---- a SHARED tree batch: many host threads, one AsyncMcts (slot) each, one batched search ----
+ * The reference's inference_thread (src/async_mcts.rs:117-189) answers the leaf boards of every episode thread with one predict
+ * once batch_size of them are waiting.  Here a host that keeps Coach::execute_episode per thread (src/coach.rs:202-205, :241-272)
+ * gives each thread one slot of a G-tree batch; each thread's blocking az_tree_slot_get_action_prob waits until the batch starts,
+ * and one waiting caller (the leader; there is no library-owned thread) runs the whole batch as one search over the requested
+ * slots and hands every caller its own result.  A caller's result is bit-identical to what a 1-game az_tree returns for the same
+ * calls: it does not depend on which requests shared its batch, on timing or on the thread count.
+ * az_tree_share turns the batch into a shared one (no slot held):
+ *   window_us = 0: a batch starts when every held slot has a request waiting (the reference's batch_size rule);
+ *   window_us > 0: also when the oldest waiting request is that old.  Calling it again only changes the window.
+ * Afterwards az_tree_get_action_prob, az_tree_reset and az_tree_record_evals are refused (AZ_ERR_BAD_ARGUMENT).
+ * "eval_cache_persist" applies per batch (0: every batch starts from an empty cache).  Slot calls do not set az_last_error. */
+az_status az_tree_share(az_tree* t, int32_t window_us);
+/* AsyncMcts::default for one slot: the lowest free slot, its tree rebuilt at the initial board before its next search.
+ * AZ_ERR_CAPACITY when all G slots are held. */
+az_status az_tree_slot_acquire(az_tree* t, int32_t* slot);
+/* The thread leaves: batches stop waiting for the slot.  AZ_ERR_BAD_ARGUMENT when the slot is out of range or not held. */
+az_status az_tree_slot_release(az_tree* t, int32_t slot);
+/* get_action_prob(&self, s, temp, episode_id, rng) for one held slot (src/async_mcts.rs:74-115); blocks until its batch has run.
+ * state [2] canonical; pi [7], counts [7] / q [7] may be NULL.  temp, seed and game_id are the request's own: tie-break RNG stream
+ * = (seed, game_id, ply = stones), the stream of az_tree_get_action_prob with first_game_id = game_id.  A terminal root
+ * (AZ_ERR_TERMINAL_ROOT) or a full tree (AZ_ERR_CAPACITY) fails only its own request; the message is az_tree_slot_error's. */
+az_status az_tree_slot_get_action_prob(az_tree* t, int32_t slot, const uint64_t* state, float temp, uint64_t seed,
+                                       uint64_t game_id, float* pi, uint16_t* counts, float* q);
+/* Message of the slot's last failed az_tree_slot_get_action_prob ("" if none); valid until the slot's next call. */
+const char* az_tree_slot_error(const az_tree* t, int32_t slot);
+/* out[4] = {batches, requests, largest batch, batches started by the window} since az_tree_share. */
+az_status az_tree_share_stats(az_tree* t, uint64_t* out);
 /* Record every NNet::predict the search issues, per tree, in order (replay parity). cap = records per tree. */
 az_status az_tree_record_evals(az_tree* t, int32_t cap);
 /* Copy out the record log: rec_count [G]; states [G,cap,2], pis [G,cap,7], vs [G,cap] (any may be NULL). */

@@ -6,6 +6,7 @@
 //   Game trait            src/game.rs:10-28           -> ConnectFourGame (connect_four_game.rs:81-238)
 //   NNet trait            src/nnet.rs:35-45           -> NNet, Mi355xNNet (az_net_* entry points)
 //   AsyncMcts<G>          src/async_mcts.rs:14-115    -> AsyncMcts (az_tree_* entry points, one tree)
+//   inference_thread      src/async_mcts.rs:117-189   -> SharedMcts (az_tree_share: one slot per host thread, batched searches)
 //   arena::play_game(s)   src/arena.rs:7-99           -> play_game, play_games (closures, Heap's order)
 //   Coach::execute_episode src/coach.rs:104-157       -> execute_episode
 //   Coach::setup / learn  src/coach.rs:38-103, :169-396 -> Coach (az_selfplay, az_net_train, az_arena; one call each)
@@ -134,7 +135,41 @@ class Mi355xNNet : public NNet {
     Engine& e_;
 };
 
-// ---- AsyncMcts: one tree behind az_tree_* ----------------------------------------------------------------------
+class AsyncMcts;
+
+// ---- SharedMcts: one shared az_tree whose slots many host threads use at once (az_tree_share) -------------------------
+// The reference's episode threads (src/coach.rs:202-205, :241-272) share one inference_thread (src/async_mcts.rs:117-189); here
+// each thread builds its AsyncMcts on a slot of one G-tree batch (SharedMcts::mcts), keeps execute_episode as written, and the
+// engine coalesces the threads' get_action_prob calls into batched searches.  Destroy the SharedMcts after every AsyncMcts on it.
+class SharedMcts {
+  public:
+    SharedMcts(Engine& e, size_t slots, size_t reserve_space, size_t num_sims, size_t num_threads, size_t max_depth, size_t model_id,
+               int32_t cpuct, int32_t window_us = 0) : e_(e) {
+        if (num_threads == 0 || num_sims % num_threads != 0)
+            throw Panic("assertion failed: self.num_sims % self.num_threads == 0");   // src/async_mcts.rs:192
+        e_.check(az_tree_create(e.raw(), (int)slots, reserve_space, (int)num_sims, (int)num_threads, (int)max_depth, (int)model_id, cpuct, &t_));
+        const int rc = az_tree_share(t_, window_us);
+        if (rc != AZ_OK) { az_tree_destroy(t_); t_ = nullptr; e_.check(rc); }
+    }
+    ~SharedMcts() { if (t_) az_tree_destroy(t_); }
+    SharedMcts(const SharedMcts&) = delete;
+    SharedMcts& operator=(const SharedMcts&) = delete;
+    // AsyncMcts::default(..) on a free slot (the tree starts at the initial board); the slot is released when the AsyncMcts dies
+    inline AsyncMcts mcts();
+    // {batches, requests, largest batch, batches started by the window}
+    std::array<uint64_t, 4> stats() const {
+        std::array<uint64_t, 4> s{};
+        if (az_tree_share_stats(t_, s.data()) != AZ_OK) throw Panic("az_tree_share_stats failed");
+        return s;
+    }
+    az_tree* raw() const { return t_; }
+
+  private:
+    Engine& e_;
+    az_tree* t_ = nullptr;
+};
+
+// ---- AsyncMcts: one tree behind az_tree_* (its own 1-game az_tree, or one slot of a SharedMcts) -------------------------------
 class AsyncMcts {
   public:
     // AsyncMcts::default(reserve_space, num_sims, num_threads, max_depth, model_id, cpuct, ..), src/async_mcts.rs:27-48
@@ -145,25 +180,47 @@ class AsyncMcts {
             throw Panic("assertion failed: self.num_sims % self.num_threads == 0");   // src/async_mcts.rs:192
         return AsyncMcts(e, reserve_space, num_sims, num_threads, max_depth, model_id, cpuct);
     }
-    AsyncMcts(AsyncMcts&& o) noexcept : e_(o.e_), t_(o.t_) { o.t_ = nullptr; }
-    ~AsyncMcts() { if (t_) az_tree_destroy(t_); }
+    AsyncMcts(AsyncMcts&& o) noexcept : e_(o.e_), t_(o.t_), slot_(o.slot_) { o.t_ = nullptr; }
+    ~AsyncMcts() {
+        if (!t_) return;
+        if (slot_ >= 0) az_tree_slot_release(t_, slot_);
+        else az_tree_destroy(t_);
+    }
     // get_action_prob(&self, s, temp, episode_id, rng): `s` canonical; rng = (seed, episode_id) stream (B7)
     Policy get_action_prob(const ConnectFourGame& s, float temp, size_t episode_id, uint64_t seed,
                            std::array<uint16_t, 7>* counts = nullptr, std::array<float, 7>* q = nullptr) const {
         const uint64_t st[2] = {s.plus, s.minus};
         Policy pi(7);
+        if (slot_ >= 0) {           // a slot of a SharedMcts: errors are the slot's own (az_last_error belongs to the whole engine)
+            const int rc = az_tree_slot_get_action_prob(t_, slot_, st, temp, seed, (uint64_t)episode_id, pi.data(),
+                                                        counts ? counts->data() : nullptr, q ? q->data() : nullptr);
+            if (rc != AZ_OK) throw Panic(std::string(az_tree_slot_error(t_, slot_)));
+            return pi;
+        }
         e_.check(az_tree_get_action_prob(t_, st, temp, seed, (uint64_t)episode_id, pi.data(),
                                          counts ? counts->data() : nullptr, q ? q->data() : nullptr));
         return pi;
     }
+    int slot() const { return slot_; }
 
   private:
+    friend class SharedMcts;
+    AsyncMcts(Engine& e, az_tree* shared, int slot) : e_(e), t_(shared), slot_(slot) {}
     AsyncMcts(Engine& e, size_t reserve, size_t sims, size_t threads, size_t max_depth, size_t model_id, int32_t cpuct) : e_(e) {
         e_.check(az_tree_create(e.raw(), 1, reserve, (int)sims, (int)threads, (int)max_depth, (int)model_id, cpuct, &t_));
     }
     Engine& e_;
     az_tree* t_ = nullptr;
+    int slot_ = -1;           // >= 0: slot of a shared tree batch (t_ is the SharedMcts's, not ours)
 };
+
+inline AsyncMcts SharedMcts::mcts() {
+    int32_t slot = -1;
+    const int rc = az_tree_slot_acquire(t_, &slot);
+    if (rc == AZ_ERR_CAPACITY) throw Panic("SharedMcts: every slot is held");
+    if (rc != AZ_OK) throw Panic("az_tree_slot_acquire failed");
+    return AsyncMcts(e_, t_, slot);
+}
 
 // ---- arena (src/arena.rs:7-99) ------------------------------------------------------------------------------------
 using PlayerAction = std::function<uint8_t(const ConnectFourGame&)>;

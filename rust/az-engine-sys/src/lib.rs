@@ -1,7 +1,7 @@
 //! Raw bindings of include/az_engine.h (EVERY exported entry point, checked against the header by
 //! tests/test_abi_cpu.py) plus a safe `Mi355xNNet` with the reference's `NNet` trait surface (src/nnet.rs:35-45:
 //! `new`, `predict`, `train`), an `Mi355xMcts` with `AsyncMcts`'s (`default`, `from_state`, `get_action_prob`,
-//! src/async_mcts.rs:27-115), and helpers that replace the self-play fan-out (src/coach.rs:241-272) and the arena gate
+//! src/async_mcts.rs:27-115), a `SharedMcts` whose slots many episode threads search on at once (az_tree_share), and helpers that replace the self-play fan-out (src/coach.rs:241-272) and the arena gate
 //! (src/coach.rs:333-390) with one engine call each.  NOT compiled in this repository (no Rust toolchain here).
 #![allow(non_camel_case_types)]
 use std::ffi::{CStr, CString};
@@ -83,6 +83,13 @@ extern "C" {
     pub fn az_tree_record_evals(t: *mut az_tree, cap: i32) -> c_int;
     pub fn az_tree_get_evals(t: *mut az_tree, rec_count: *mut i32, states: *mut u64, pis: *mut f32, vs: *mut f32) -> c_int;
     pub fn az_tree_node_counts(t: *mut az_tree, out: *mut u32) -> c_int;
+    pub fn az_tree_share(t: *mut az_tree, window_us: i32) -> c_int;
+    pub fn az_tree_slot_acquire(t: *mut az_tree, slot: *mut i32) -> c_int;
+    pub fn az_tree_slot_release(t: *mut az_tree, slot: i32) -> c_int;
+    pub fn az_tree_slot_get_action_prob(t: *mut az_tree, slot: i32, state: *const u64, temp: f32, seed: u64, game_id: u64,
+                                        pi: *mut f32, counts: *mut u16, q: *mut f32) -> c_int;
+    pub fn az_tree_slot_error(t: *const az_tree, slot: i32) -> *const c_char;
+    pub fn az_tree_share_stats(t: *mut az_tree, out: *mut u64) -> c_int;
     // ---- Coach::execute_episode x many, src/coach.rs:104-157; arena::play_games, src/arena.rs:62-99
     pub fn az_selfplay(e: *mut az_engine, p: *const az_selfplay_params, out: *mut az_samples) -> c_int;
     // the same as a session: the slots stay full across the calls that fetch the episodes (no drain per chunk)
@@ -171,6 +178,60 @@ impl Mi355xMcts {
     }
 }
 impl Drop for Mi355xMcts { fn drop(&mut self) { unsafe { az_tree_destroy(self.t) } } }
+
+/// One shared tree batch for many episode threads (az_tree_share): the rayon pool of src/coach.rs:202-205, :241-272 keeps
+/// `execute_episode`, each thread takes a slot (`mcts()`, one `AsyncMcts::default` per episode), and the engine coalesces the
+/// threads' `get_action_prob` calls into batched searches -- the role of `inference_thread` (src/async_mcts.rs:117-189).
+/// While slots are in use, make no other call on the engine; drop every `SharedSlot` before the `SharedMcts`.
+pub struct SharedMcts { pub t: *mut az_tree }
+// The slot calls are made from many threads at once by design (include/az_engine.h threading contract).
+unsafe impl Send for SharedMcts {}
+unsafe impl Sync for SharedMcts {}
+
+impl SharedMcts {
+    /// `slots` trees of AsyncMcts::default(reserve_space, num_sims, num_threads, max_depth, model_id, cpuct, ..);
+    /// window_us = 0: a batch starts when every held slot waits, > 0: also when the oldest request is that old
+    pub fn new(e: *mut az_engine, slots: usize, reserve_space: usize, num_sims: usize, num_threads: usize, max_depth: usize, model_id: usize,
+               cpuct: i32, window_us: i32) -> Self {
+        let mut t = std::ptr::null_mut();
+        check(e, unsafe { az_tree_create(e, slots as i32, reserve_space as u64, num_sims as i32, num_threads as i32, max_depth as i32, model_id as i32, cpuct, &mut t) });
+        check(e, unsafe { az_tree_share(t, window_us) });
+        SharedMcts { t }
+    }
+    /// AsyncMcts::default on a free slot; the slot goes back when the guard drops
+    pub fn mcts(&self) -> SharedSlot<'_> {
+        let mut slot = -1i32;
+        let rc = unsafe { az_tree_slot_acquire(self.t, &mut slot) };
+        assert_eq!(rc, 0, "az_tree_slot_acquire: every slot is held (status {})", rc);
+        SharedSlot { owner: self, slot }
+    }
+    /// [batches, requests, largest batch, batches started by the window]
+    pub fn stats(&self) -> [u64; 4] {
+        let mut s = [0u64; 4];
+        assert_eq!(unsafe { az_tree_share_stats(self.t, s.as_mut_ptr()) }, 0);
+        s
+    }
+}
+impl Drop for SharedMcts { fn drop(&mut self) { unsafe { az_tree_destroy(self.t) } } }
+
+/// One thread's `AsyncMcts` on a slot of a `SharedMcts`.
+pub struct SharedSlot<'a> { owner: &'a SharedMcts, slot: i32 }
+
+impl SharedSlot<'_> {
+    /// get_action_prob(&self, s, temp, episode_id, rng), src/async_mcts.rs:74-115, for this slot's tree: blocks until its batch ran;
+    /// `state` = canonical bitboards [2]; tie-break stream (seed, episode_id, ply = stones)
+    pub fn get_action_prob(&self, state: &[u64; 2], temp: f32, episode_id: u64, seed: u64) -> [f32; 7] {
+        let mut pi = [0f32; 7];
+        let rc = unsafe { az_tree_slot_get_action_prob(self.owner.t, self.slot, state.as_ptr(), temp, seed, episode_id, pi.as_mut_ptr(),
+                                                       std::ptr::null_mut(), std::ptr::null_mut()) };
+        if rc != 0 {
+            let msg = unsafe { CStr::from_ptr(az_tree_slot_error(self.owner.t, self.slot)) }.to_string_lossy().into_owned();
+            panic!("az_engine status {}: {}", rc, msg);
+        }
+        pi
+    }
+}
+impl Drop for SharedSlot<'_> { fn drop(&mut self) { unsafe { az_tree_slot_release(self.owner.t, self.slot); } } }
 
 /// Counters since az_create / the last reset (SURVEY.md 8b "Introspection").
 pub fn stats(e: *mut az_engine) -> az_stats {
