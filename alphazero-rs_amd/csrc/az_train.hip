@@ -330,6 +330,10 @@ void launch_splitk_reduce(const float* partial, int splits, int M, int N, float*
 // forward on the f32 kernel; since round 4 conv2..conv4 run it as f16 x 3 (split_f16 below: 2^-22, the f32 kernel's own grade, with
 // the operands scaled into half's NORMAL range -- the matrix cores treat half subnormals as zero).  conv1 (K = 18) and the FC layers
 // (64 rows) stay on the f32 kernel.  Measured error of a step's gradients against float64 autograd: DESIGN.md section 8.
+// Range contract of the f16 x 3 forward: the weights enter as 256 W (|W| < 128 keeps 256 W finite), the activations a[l] as s_l a[l],
+// where s_l <= 64 is a power of two chosen on the device each step from the BatchNorm parameters so that s_l times the bound
+// |gamma| sqrt(M - 1) + max(beta, 0) on a[l] stays below 2^15 (act_scales_body).  Any finite activation a training-mode BatchNorm can
+// produce therefore stays finite in half precision; only the low halves of the smallest activations lose bits when s_l < 64.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 AZ_D uint16_t bf16_rne(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
@@ -393,6 +397,7 @@ struct Gemm3 {
     int xcd_rows;                   // workgroup id -> tile mapping (k_gemm3)
     float out_scale;                // the accumulators times this (a power of two: the f16 forward's weights are stored times 256), then + bias
     ImplicitA ia;                   // k_gemm3_ring only
+    const float* out_scale_dev;     // not nullptr: out_scale read from here instead (the f16 forward: 1 / (256 s_l), chosen on the device)
 };
 
 // One stage = the four operand tiles of one 32-deep K-step -- A_hi, A_lo, W_hi, W_lo, 128 rows x 64 B each = 32 KiB -- shared by the step's
@@ -495,6 +500,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(const Gemm3 g) {
     }
 #undef AZ_G3DMA
     // f32 epilogue: a lane holds 4 consecutive columns of one row
+    const float osc = g.out_scale_dev ? *g.out_scale_dev : g.out_scale;
     float* obase = g.splits > 1 ? g.out + (size_t)blockIdx.y * g.M * g.N : g.out;
     const int ldo = g.splits > 1 ? g.N : g.ldo;
 #pragma unroll
@@ -507,8 +513,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(const Gemm3 g) {
             const int m = m0 + wr * (G3_BM / 2) + mt * 16 + frow;
             if (m >= g.M) continue;
             *(float4*)(obase + (size_t)m * ldo + n) =
-                make_float4(acc[mt][nt][0] * g.out_scale + bv.x, acc[mt][nt][1] * g.out_scale + bv.y, acc[mt][nt][2] * g.out_scale + bv.z,
-                            acc[mt][nt][3] * g.out_scale + bv.w);
+                make_float4(acc[mt][nt][0] * osc + bv.x, acc[mt][nt][1] * osc + bv.y, acc[mt][nt][2] * osc + bv.z, acc[mt][nt][3] * osc + bv.w);
         }
     }
 }
@@ -640,6 +645,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm3_ring(const Gemm3 g) {
         buf = buf == 2 ? 0 : buf + 1;
     }
 #undef AZ_G3RDMA
+    const float osc = g.out_scale_dev ? *g.out_scale_dev : g.out_scale;
     float* obase = g.splits > 1 ? g.out + (size_t)split * g.M * g.N : g.out;
     const int ldo = g.splits > 1 ? g.N : g.ldo;
 #pragma unroll
@@ -652,8 +658,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm3_ring(const Gemm3 g) {
             const int m = m0 + wr * 64 + mt * 16 + frow;
             if (m >= g.M) continue;
             *(float4*)(obase + (size_t)m * ldo + n) =
-                make_float4(acc[mt][nt][0] * g.out_scale + bv.x, acc[mt][nt][1] * g.out_scale + bv.y, acc[mt][nt][2] * g.out_scale + bv.z,
-                            acc[mt][nt][3] * g.out_scale + bv.w);
+                make_float4(acc[mt][nt][0] * osc + bv.x, acc[mt][nt][1] * osc + bv.y, acc[mt][nt][2] * osc + bv.z, acc[mt][nt][3] * osc + bv.w);
         }
     }
 }
@@ -899,15 +904,56 @@ __global__ __launch_bounds__(256) void k_transpose_split(const TransposeJob j0, 
     __shared__ float tile[64][65];
     transpose_split_body<F16>(j0, j1, j2, R, Rp, scale, blockIdx.x, blockIdx.y, tile);
 }
+// The range of the f16 x 3 forward.  a[l] (l = 0..2, the output of conv l+1's BatchNorm and ReLU) enters conv l+2's GEMM as s_l a[l] in
+// half pairs, and the epilogue multiplies by 1 / (256 s_l).  Training-mode BatchNorm bounds its output: |xhat| <= sqrt(M - 1) over M rows
+// (Samuelson's inequality; eps only shrinks it), so a[l] <= B_l = max_c |gamma_c| sqrt(M_l - 1) + max(beta_c, 0).  s_l is the largest
+// power of two <= 64 with s_l B_l < 2^15: a factor of two below half's largest finite value, so hi never rounds to infinity (with a fixed
+// 64, one activation above 65504 / 64 made the step's loss NaN).  64 keeps the low halves of activations down to 1/512 out of the
+// subnormals the matrix cores flush; a smaller s_l loses the low halves of proportionally larger ones (2^-11 of such an element).
+// Powers of two scale exactly.  The bound needs the parameters only, so it is computed before the forward, on the device (the values are
+// read by k_im2col, k_bn_apply and the GEMM epilogue: nothing of it is baked into a captured graph).
+struct ActScaleJob {
+    int64_t bn[3];          // offsets of conv1..conv3's BatchNorm parameters (gamma [C], beta [C], ...)
+    float sqrt_m1[3];       // sqrt(M_l - 1), M_l = the layer's rows
+    int C;
+};
+// one block of 256 threads; out[l] = s_l, out[4 + l] = 1 / (256 s_l)
+AZ_D void act_scales_body(const float* __restrict__ P, const ActScaleJob& j, float* __restrict__ out) {
+    __shared__ float red[256];
+    for (int l = 0; l < 3; ++l) {
+        float bmax = 0.0f;
+        for (int c = threadIdx.x; c < j.C; c += blockDim.x)
+            bmax = fmaxf(bmax, fabsf(P[j.bn[l] + c]) * j.sqrt_m1[l] + fmaxf(P[j.bn[l] + j.C + c], 0.0f));
+        red[threadIdx.x] = bmax;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            float sc = 64.0f;
+            while (sc > 0x1p-24f && !(sc * red[0] < 32768.0f)) sc *= 0.5f;
+            out[l] = sc;
+            out[4 + l] = 1.0f / (256.0f * sc);
+        }
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(256) void k_act_scales(const float* __restrict__ P, const ActScaleJob j, float* __restrict__ out) {
+    act_scales_body(P, j, out);
+}
+
 // One launch for everything a step derives from the parameters: blocks [0, tx * ty) transpose conv2..conv4's matrices into the f16 x 3
-// forward's operand ((256 W)^T as half pairs), the rest split the five matrices for dgrad (bf16 pairs, conv2's rows permuted).
+// forward's operand ((256 W)^T as half pairs), the next 5 sgx split the five matrices for dgrad (bf16 pairs, conv2's rows permuted), the
+// last one computes the activation scales (act_scales_body).
 __global__ __launch_bounds__(256) void k_weight_prep(const TransposeJob j0, const TransposeJob j1, const TransposeJob j2, int R, int Rp, float scale,
                                                      int tgx, int tgy, const float* __restrict__ P, const SplitWeights sw, uint16_t* __restrict__ w_hi,
-                                                     uint16_t* __restrict__ w_lo, int sgx) {
+                                                     uint16_t* __restrict__ w_lo, int sgx, const ActScaleJob aj, float* __restrict__ act_scale) {
     __shared__ float tile[64][65];
     const int id = blockIdx.x;
     if (id < tgx * tgy) { transpose_split_body<true>(j0, j1, j2, R, Rp, scale, id % tgx, id / tgx, tile); return; }
     const int r = id - tgx * tgy;
+    if (r == 5 * sgx) { act_scales_body(P, aj, act_scale); return; }
     split_weights_body(P, sw, w_hi, w_lo, r % sgx, r / sgx, sgx);
 }
 
@@ -959,10 +1005,12 @@ __global__ void k_boards_col1(const float* __restrict__ boards, float* __restric
 struct Im2colOut {
     float* col;
     uint16_t *col_hi, *col_lo, *col_bhi, *col_blo;
+    const float* hi_scale;      // with col_hi: s_l (act_scales_body), the factor of the half pairs
 };
 __global__ void k_im2col(const float* __restrict__ in, const Im2colOut out, int b, int H, int W, int C, int pad) {
     const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2, c4n = C / 4;
     const int64_t total = (int64_t)b * Ho * Wo * 9 * c4n;
+    const float sc = out.col_hi ? *out.hi_scale : 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int c4 = (int)(i % c4n);
         const int tap = (int)((i / c4n) % 9);
@@ -975,8 +1023,9 @@ __global__ void k_im2col(const float* __restrict__ in, const Im2colOut out, int 
         if (out.col) *(float4*)(out.col + o) = v;
         if (out.col_hi) {
             uint16_t h0, h1, h2, h3, l0, l1, l2, l3;
-            // times 64: a half below 2^-14 is subnormal, and the low halves of activations under 1/8 would be; scaled, that is under 1/512
-            split_f16(v.x * 64.0f, h0, l0); split_f16(v.y * 64.0f, h1, l1); split_f16(v.z * 64.0f, h2, l2); split_f16(v.w * 64.0f, h3, l3);
+            // times s_l (64 unless the layer's range needs less): a half below 2^-14 is subnormal, and the low halves of activations under
+            // 1/8 would be; times 64, that is under 1/512
+            split_f16(v.x * sc, h0, l0); split_f16(v.y * sc, h1, l1); split_f16(v.z * sc, h2, l2); split_f16(v.w * sc, h3, l3);
             *(uint2*)(out.col_hi + o) = make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2 | ((uint32_t)h3 << 16));
             *(uint2*)(out.col_lo + o) = make_uint2((uint32_t)l0 | ((uint32_t)l1 << 16), (uint32_t)l2 | ((uint32_t)l3 << 16));
         }
@@ -1049,9 +1098,10 @@ struct BnLayer {
     uint32_t keep_thresh;
     float drop_scale;
     uint16_t *out_hi, *out_lo;   // k_bn_bwd_apply, not nullptr: dz also as hi / lo bf16 (the dgrad operand), same [M][N] layout
-    // k_bn_apply, not nullptr: the activations also as 64 x a in half-precision hi / lo (the next layer's f16 x 3 forward operand) and as
+    // k_bn_apply, not nullptr: the activations also as s_l x a in half-precision hi / lo (the next layer's f16 x 3 forward operand) and as
     // bf16 hi / lo (its wgrad operand), same [M][N] layout -- what k_im2col writes 9 x of when the GEMMs do not gather (ImplicitA)
     uint16_t *act_hi, *act_lo, *act_bhi, *act_blo;
+    const float* act_scale;      // with act_hi: s_l (act_scales_body) in place of the 64
 };
 
 
@@ -1178,6 +1228,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(const BnLayer L, const double*
     const float4 mean = *(const float4*)(s_mean + tx * 4), inv = *(const float4*)(s_inv + tx * 4);
     const float4 gamma = *(const float4*)(L.gamma + c), beta = *(const float4*)(L.beta + c);
     const uint64_t mask_seed = L.keep_thresh ? st->mask_seed : 0;
+    const float asc = L.act_hi ? *L.act_scale : 0.0f;
     auto row = [&](int r, const float4 z) {
         const size_t i = (size_t)r * L.N + c;
         float4 y = make_float4(fmaxf(gamma.x * ((z.x - mean.x) * inv.x) + beta.x, 0.0f), fmaxf(gamma.y * ((z.y - mean.y) * inv.y) + beta.y, 0.0f),
@@ -1191,7 +1242,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(const BnLayer L, const double*
         *(float4*)(L.out + i) = y;
         if (L.act_hi) {
             uint16_t h0, h1, h2, h3, l0, l1, l2, l3;
-            split_f16(y.x * 64.0f, h0, l0); split_f16(y.y * 64.0f, h1, l1); split_f16(y.z * 64.0f, h2, l2); split_f16(y.w * 64.0f, h3, l3);
+            split_f16(y.x * asc, h0, l0); split_f16(y.y * asc, h1, l1); split_f16(y.z * asc, h2, l2); split_f16(y.w * asc, h3, l3);
             *(uint2*)(L.act_hi + i) = make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2 | ((uint32_t)h3 << 16));
             *(uint2*)(L.act_lo + i) = make_uint2((uint32_t)l0 | ((uint32_t)l1 << 16), (uint32_t)l2 | ((uint32_t)l3 << 16));
         }
@@ -1532,6 +1583,7 @@ struct Trainer {
     // forward conv2..conv4 as f16 x 3 (fwd_x3): the im2col matrices and the transposed weights (times 256) as half-precision hi / lo pairs
     bool fwd_x3 = true;
     uint16_t *col_hi[4] = {nullptr}, *col_lo[4] = {nullptr}, *wt_hi[4] = {nullptr}, *wt_lo[4] = {nullptr};
+    float* act_scale = nullptr;        // [8]: s_l of a[0..2] at [l], the epilogue's 1 / (256 s_l) at [4 + l] (act_scales_body)
     // wgrad of conv2..conv4 on k_wgrad3_tr (transposed LDS reads, no k_transpose_split): the im2col matrices as bf16 hi / lo
     bool wgrad_tr = true;
     uint16_t *col_bhi[4] = {nullptr}, *col_blo[4] = {nullptr};
@@ -1595,6 +1647,7 @@ Trainer* trainer_create(int channels, const char** err) {
     ok &= (t->step_state = t->dalloc<StepState>(1)) != nullptr;
     ok &= hipHostMalloc((void**)&t->host_state, HOST_STATE_RING * sizeof(StepState), hipHostMallocDefault) == hipSuccess;
     ok &= (t->counters = t->dalloc<EpochCounters>(1)) != nullptr;
+    ok &= (t->act_scale = t->dalloc<float>(8)) != nullptr;
     {
         const size_t NM = std::max<size_t>(C, 1024), Mp = (B * 42 + 63) / 64 * 64;
         for (uint16_t** q : {&t->w_hi, &t->w_lo}) ok &= (*q = t->dalloc<uint16_t>(T)) != nullptr;
@@ -1741,7 +1794,7 @@ int red_parts(int M) { return std::max(1, std::min(RED_PARTS, (M + 63) / 64)); }
 // Kc.  Split-K so that about two workgroups per CU exist (a workgroup walks at least 8 K-steps); the slices are summed in slice order.
 void launch_gemm3(const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* out, int ldo,
                   const float* bias, int M, int N, int Kc, float* ws, size_t ws_floats, hipStream_t s, bool ring = false, bool f16 = false,
-                  float out_scale = 1.0f, const ImplicitA* ia = nullptr) {
+                  float out_scale = 1.0f, const ImplicitA* ia = nullptr, const float* out_scale_dev = nullptr) {
     const int steps = Kc / 32;
     const int mt_r = (M + G3R_BM - 1) / G3R_BM;
     // at most a tenth of the row tiles' rows beyond M, and a contraction long enough to fill and drain the ring (conv4's wgrad has 12
@@ -1754,7 +1807,8 @@ void launch_gemm3(const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uin
         while (splits > 1 && (size_t)splits * M * N > ws_floats) --splits;
         const int sps = (steps + splits - 1) / splits;
         splits = (steps + sps - 1) / sps;
-        Gemm3 g{a_hi, a_lo, w_hi, w_lo, splits > 1 ? ws : out, bias, M, N, Kc, lda, ldw, ldo, sps, splits, 0, out_scale, ia ? *ia : ImplicitA{}};
+        Gemm3 g{a_hi, a_lo, w_hi, w_lo, splits > 1 ? ws : out, bias, M, N, Kc, lda, ldw, ldo, sps, splits, 0, out_scale, ia ? *ia : ImplicitA{},
+                out_scale_dev};
         if (f16) hipLaunchKernelGGL((k_gemm3_ring<true>), dim3((unsigned)((tiles * splits + 7) / 8 * 8)), dim3(512), 0, s, g);
         else hipLaunchKernelGGL((k_gemm3_ring<false>), dim3((unsigned)((tiles * splits + 7) / 8 * 8)), dim3(512), 0, s, g);
         if (splits > 1)
@@ -1767,7 +1821,7 @@ void launch_gemm3(const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uin
     const int sps = (steps + splits - 1) / splits;
     splits = (steps + sps - 1) / sps;
     const int xcd_rows = mt >= 8 ? 1 : 0;
-    Gemm3 g{a_hi, a_lo, w_hi, w_lo, splits > 1 ? ws : out, bias, M, N, Kc, lda, ldw, ldo, sps, splits, xcd_rows, out_scale, ImplicitA{}};
+    Gemm3 g{a_hi, a_lo, w_hi, w_lo, splits > 1 ? ws : out, bias, M, N, Kc, lda, ldw, ldo, sps, splits, xcd_rows, out_scale, ImplicitA{}, out_scale_dev};
     const dim3 grid((unsigned)((xcd_rows ? (mt + 7) / 8 * 8 : mt) * NT), (unsigned)splits);
     if (f16) hipLaunchKernelGGL((k_gemm3<true>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((k_gemm3<false>), grid, dim3(256), 0, s, g);
@@ -1870,16 +1924,20 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
     // k_wgrad3_tr's shape constraints (a batch of 64 meets them at every width that is a multiple of 256 / 9 ... i.e. 9 C % 256 == 0)
     auto tr_ok = [&](int l) { return x3 && t->wgrad_tr && l >= 1 && l <= 3 && ld[l].M % 32 == 0 && ld[l].K % 256 == 0 && ld[l].N % 128 == 0; };
     const bool prep_one = fx3 && !fork;      // both weight preparations in one launch, ahead of the forward pass
-    if (fx3) {          // W [9C][C] of conv2..conv4 -> (256 W)^T as half hi / lo [C][9C]
+    if (fx3) {          // W [9C][C] of conv2..conv4 -> (256 W)^T as half hi / lo [C][9C]; the activations' scales s_l
         TransposeJob j[3];
         for (int l = 1; l <= 3; ++l) j[l - 1] = TransposeJob{P + ld[l].w, t->wt_hi[l], t->wt_lo[l], C, C / 64, C};
         const int tgx = 3 * (C / 64), tgy = 9 * C / 64;
+        ActScaleJob aj{};
+        for (int l = 0; l < 3; ++l) { aj.bn[l] = ld[l].bn; aj.sqrt_m1[l] = (float)std::sqrt((double)(rows[l] - 1)); }
+        aj.C = C;
         if (prep_one) {
             const SplitWeights sw = split_desc();
-            hipLaunchKernelGGL(k_weight_prep, dim3((unsigned)(tgx * tgy + 256 * 5)), dim3(256), 0, s, j[0], j[1], j[2], 9 * C, 9 * C, 256.0f, tgx, tgy,
-                               (const float*)P, sw, t->w_hi, t->w_lo, 256);
+            hipLaunchKernelGGL(k_weight_prep, dim3((unsigned)(tgx * tgy + 256 * 5 + 1)), dim3(256), 0, s, j[0], j[1], j[2], 9 * C, 9 * C, 256.0f, tgx,
+                               tgy, (const float*)P, sw, t->w_hi, t->w_lo, 256, aj, t->act_scale);
         } else {
             hipLaunchKernelGGL((k_transpose_split<true>), dim3((unsigned)tgx, (unsigned)tgy), dim3(256), 0, s, j[0], j[1], j[2], 9 * C, 9 * C, 256.0f);
+            hipLaunchKernelGGL(k_act_scales, dim3(1), dim3(256), 0, s, (const float*)P, aj, t->act_scale);
         }
     }
     for (int l = 0; l < 6; ++l) {
@@ -1887,14 +1945,17 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
         if (impl && l >= 1 && l <= 3) {
             const ImplicitA ia = gather(l, false);
             launch_gemm3(t->act_hi[l - 1], t->act_lo[l - 1], 0, t->wt_hi[l], t->wt_lo[l], 9 * C, t->z[l], d.N, P + d.bias, d.M, d.N, d.K, t->splitk,
-                         t->splitk_floats, s, true, true, 1.0f / (256.0f * 64.0f), &ia);
+                         t->splitk_floats, s, true, true, 1.0f, &ia, t->act_scale + 4 + (l - 1));
         } else if (fx3 && l >= 1 && l <= 3)
             launch_gemm3(t->col_hi[l], t->col_lo[l], 9 * C, t->wt_hi[l], t->wt_lo[l], 9 * C, t->z[l], d.N, P + d.bias, d.M, d.N, d.K, t->splitk,
-                         t->splitk_floats, s, t->gemm3_ring, true, 1.0f / (256.0f * 64.0f));
+                         t->splitk_floats, s, t->gemm3_ring, true, 1.0f, nullptr, t->act_scale + 4 + (l - 1));
         else
             gemm_nn(d.A, d.lda, P + d.w, t->z[l], P + d.bias, d.M, d.N, d.K, t->splitk, t->splitk_floats, s, t->fwd_dma);
         BnLayer bn = bn_desc(l, t->a[l], nullptr);
-        if (impl && l <= 2) { bn.act_hi = t->act_hi[l]; bn.act_lo = t->act_lo[l]; bn.act_bhi = t->act_bhi[l]; bn.act_blo = t->act_blo[l]; }
+        if (impl && l <= 2) {
+            bn.act_hi = t->act_hi[l]; bn.act_lo = t->act_lo[l]; bn.act_bhi = t->act_bhi[l]; bn.act_blo = t->act_blo[l];
+            bn.act_scale = t->act_scale + l;
+        }
         if ((l == 3 || l == 4) && fc_tr(l + 1)) { bn.act_bhi = t->act_bhi[l]; bn.act_blo = t->act_blo[l]; }
         const int parts = red_parts(d.M), rpb = (d.M + parts - 1) / parts;
         if (d.M <= BN_SMALL_ROWS) {
@@ -1907,7 +1968,7 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
         if (l <= 2 && !impl) {
             const int ln = l + 1;                // the layer this matrix feeds
             Im2colOut io{};
-            if (fx3) { io.col_hi = t->col_hi[ln]; io.col_lo = t->col_lo[ln]; }
+            if (fx3) { io.col_hi = t->col_hi[ln]; io.col_lo = t->col_lo[ln]; io.hi_scale = t->act_scale + l; }
             if (tr_ok(ln)) { io.col_bhi = t->col_bhi[ln]; io.col_blo = t->col_blo[ln]; }
             if (!fx3 || !tr_ok(ln)) io.col = t->col[ln];
             const int H = l == 2 ? 4 : 6, W = l == 2 ? 5 : 7, pad = l == 0 ? 1 : 0;
