@@ -5,19 +5,23 @@
 #include "../../include/az_engine.h"
 
 #include <dlfcn.h>
+#include <unistd.h>
 #include <rccl/rccl.h>      // types only: the library is dlopen'ed by az_comm_* (a host that never shards never loads it)
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "az_combine.h"
+#include "az_local_comm.h"
 #include "az_net.h"
 #include "az_train.h"
 #include "az_tree.h"
@@ -52,7 +56,7 @@ struct NetModel {
     uint64_t cache_tag = 0;     // evaluation-cache tag of the current weights (0 = none yet); new tag per upload
     uint64_t generation = 0;    // bumped by every weight upload / kind change of any model of the process: part of a search graph's key
 };
-uint64_t g_model_generation = 0;
+std::atomic<uint64_t> g_model_generation{0};     // engines of one process run concurrently (one host thread each)
 
 // timed regions (profile mode): event pairs recorded on the engine stream, resolved at sync points
 enum Region { RG_TREE = 0, RG_NET = 1, RG_COUNT };   // RG_NET brackets the whole predict (kept for stub nets)
@@ -87,8 +91,10 @@ struct Profiler {
 };
 
 // RCCL entry points, resolved at the first az_comm_* call.  Not a link-time dependency: a process that also hosts another copy
-// of RCCL (PyTorch bundles one) must not have two sets of ncclXxx symbols bound into one namespace.
+// of RCCL (PyTorch bundles one) must not have two sets of ncclXxx symbols bound into one namespace.  load() may race between the
+// engines of one process (one host thread each): it runs under a mutex, and the table is only read once load() has returned true.
 struct Rccl {
+    std::mutex mu;
     void* lib = nullptr;
     ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
     ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
@@ -101,6 +107,7 @@ struct Rccl {
     ncclResult_t (*GroupEnd)() = nullptr;
     const char* (*GetErrorString)(ncclResult_t) = nullptr;
     bool load(std::string* why) {
+        std::lock_guard<std::mutex> lk(mu);
         if (lib) return true;
         for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
             lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
@@ -124,6 +131,8 @@ struct Rccl {
     }
 };
 Rccl g_rccl;      // function table only (no per-engine state)
+// the in-process ids of az_comm_local_id (csrc/az_local_comm.h): engines of this process that form a world without RCCL
+LocalCommRegistry g_local_comms{(int64_t)getpid()};
 
 // (s, pi, z) as one 48-byte tuple: the unit of the episode-batch gather (symmetries are regenerated at the destination)
 struct PackedSample { unsigned long long s0, s1; float pi[7]; float z; };
@@ -350,9 +359,12 @@ struct az_engine {
     // no hipMalloc / hipFree per call); at most three are kept (self-play + the arena's pair)
     std::vector<std::unique_ptr<TreeHost>> tree_pool;
     uint64_t tree_pool_allocs = 0;  // arenas created (a second call of the same shape must not add to it)
-    // communicator of the sharded Coach loop (az_comm_init): RCCL on the engine's stream
+    // communicator of the sharded Coach loop (az_comm_init): RCCL on the engine's stream, or an in-process group
+    // (az_comm_local_id; csrc/az_local_comm.h) -- at most one of the two is set
     ncclComm_t comm = nullptr;
+    std::shared_ptr<LocalGroup> local;
     int comm_rank = 0, comm_world = 1;
+    bool has_comm() const { return comm || local; }
     // staging of the collectives (az_gather_samples, az_allreduce_u64): one device allocation that only grows
     struct Scratch {
         void* p = nullptr;
@@ -877,6 +889,7 @@ void az_destroy(az_engine* e) {
     if (e->cache_keys) (void)hipFree(e->cache_keys);
     if (e->cache_pv) (void)hipFree(e->cache_pv);
     if (e->comm && g_rccl.CommDestroy) { (void)g_rccl.CommDestroy(e->comm); e->comm = nullptr; }
+    if (e->local) { e->local->leave(e->comm_rank); e->local.reset(); }       // the peers' collectives fail from now on
     e->tree_pool.clear();
     trainer_destroy(e->trainer);
     { double ms[RG_COUNT] = {0, 0}; e->prof.resolve(ms); }
@@ -1897,7 +1910,7 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
     const int first = sharded ? p->first_game : 0;
     out_wld[0] = out_wld[1] = out_wld[2] = 0;
     // a host that asks for the whole arena's tally but never bound a communicator would gate the model on its own shard's count
-    if (p->allreduce_wld && (!sharded || !e->comm))
+    if (p->allreduce_wld && (!sharded || !e->has_comm()))
         return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: allreduce_wld needs a sharded call (total_games > 0) on an engine with a communicator (az_comm_init)");
     if (G == 0) {      // an empty shard still takes part in the tally's all-reduce
         if (p->allreduce_wld) return az_allreduce_u64(e, out_wld, 3);
@@ -2086,6 +2099,9 @@ az_status az_arena_get_evals(az_engine* e, int32_t which, int32_t* rec_count, ui
 }
 
 // ---- the collective of the sharded Coach loop ---------------------------------------------------------------------------------
+// Two backends, chosen by the id alone: RCCL (az_comm_unique_id) or an in-process group (az_comm_local_id, csrc/az_local_comm.h).
+// The collectives below are shared code -- argument checks, the hello verdict, packing, offsets, unpacking -- on top of the only
+// three things that differ: comm_allgather_hello, comm_sum_u64 and comm_exchange.
 #define NCCLCHK(expr) do { ncclResult_t _r = (expr); if (_r != ncclSuccess) return fail(e, AZ_ERR_HIP, std::string("RCCL: ") + g_rccl.GetErrorString(_r) + " at " #expr); } while (0)
 
 az_status az_comm_unique_id(az_engine* e, uint8_t id[AZ_COMM_ID_BYTES]) {
@@ -2099,9 +2115,41 @@ az_status az_comm_unique_id(az_engine* e, uint8_t id[AZ_COMM_ID_BYTES]) {
     return AZ_OK;
 }
 
+az_status az_comm_local_id(az_engine* e, int32_t world, uint8_t id[AZ_COMM_ID_BYTES]) {
+    if (!e || !id) return AZ_ERR_BAD_ARGUMENT;
+    static_assert(LOCAL_ID_BYTES == AZ_COMM_ID_BYTES, "one id size for both backends");
+    const std::string why = g_local_comms.create(world, id);
+    return why.empty() ? AZ_OK : fail(e, AZ_ERR_BAD_ARGUMENT, why);
+}
+
+// an in-process id: join the group (returns once every rank has joined), then enable peer access towards the other members'
+// devices where the hardware allows it ("already enabled" by another engine of the process is fine)
+static az_status comm_init_local(az_engine* e, int32_t rank, int32_t world, const LocalId& lid) {
+    try { HIPCHK(hipSetDevice(e->device)); } catch (const HipFail& f) { return fail_hip(e, f); }
+    std::shared_ptr<LocalGroup> g;
+    const std::string why = g_local_comms.join(lid, rank, world, e->device, &g);
+    if (!why.empty()) return fail(e, AZ_ERR_BAD_ARGUMENT, why);
+    std::vector<int> devs = g->devices();
+    std::sort(devs.begin(), devs.end());
+    devs.erase(std::unique(devs.begin(), devs.end()), devs.end());
+    for (int d : devs) {
+        int can = 0;
+        if (d == e->device || hipDeviceCanAccessPeer(&can, e->device, d) != hipSuccess || !can) continue;
+        // anything but success / already enabled leaves the copies to the runtime's staged path: still correct, so not an error
+        (void)hipDeviceEnablePeerAccess(d, 0);
+        (void)hipGetLastError();
+    }
+    e->local = std::move(g);
+    e->comm_rank = rank;
+    e->comm_world = world;
+    return AZ_OK;
+}
+
 az_status az_comm_init(az_engine* e, int32_t rank, int32_t world, const uint8_t id[AZ_COMM_ID_BYTES]) {
     if (!e || !id || world < 1 || rank < 0 || rank >= world) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_comm_init: bad rank / world");
-    if (e->comm) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_comm_init: the engine already has a communicator (az_comm_destroy first)");
+    if (e->has_comm()) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_comm_init: the engine already has a communicator (az_comm_destroy first)");
+    LocalId lid;
+    if (local_id_decode(id, &lid)) return comm_init_local(e, rank, world, lid);
     std::string why;
     if (!g_rccl.load(&why)) return fail(e, AZ_ERR_UNSUPPORTED, why);
     try { HIPCHK(hipSetDevice(e->device)); } catch (const HipFail& f) { return fail_hip(e, f); }
@@ -2115,6 +2163,11 @@ az_status az_comm_init(az_engine* e, int32_t rank, int32_t world, const uint8_t 
 
 az_status az_comm_destroy(az_engine* e) {
     if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (e->local) {          // every copy of a collective was synchronised before it returned: nothing of this engine is in flight
+        e->local->leave(e->comm_rank);
+        e->local.reset();
+        e->comm_rank = 0; e->comm_world = 1;
+    }
     if (e->comm) {
         (void)hipSetDevice(e->device);
         (void)hipStreamSynchronize(e->stream);
@@ -2125,10 +2178,25 @@ az_status az_comm_destroy(az_engine* e) {
     return AZ_OK;
 }
 
-az_status az_allreduce_u64(az_engine* e, uint64_t* values, int32_t n) {
-    if (!e || !values || n < 0 || n > 64) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_allreduce_u64: bad argument");
-    if (!e->comm) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_allreduce_u64: no communicator (az_comm_init)");
-    if (n == 0) return AZ_OK;
+// primitive 2: in-place sum of n u64 counters over the ranks.  In-process: one round of [ok, 64 values] records summed in rank order
+// (wrapping, as RCCL's ncclUint64 sum); a rank with bad arguments still takes part, so every rank returns the same error.
+static az_status comm_sum_u64(az_engine* e, uint64_t* values, int32_t n, bool args_ok) {
+    if (e->local) {
+        uint64_t rec[1 + 64] = {args_ok ? 1ull : 0ull};
+        if (args_ok && n > 0) std::memcpy(rec + 1, values, (size_t)n * 8);
+        std::vector<unsigned char> all;
+        const std::string err = e->local->all_gather(e->comm_rank, LOCAL_OP_ALLREDUCE, n, rec, sizeof rec, &all);
+        if (!err.empty()) return fail(e, AZ_ERR_BAD_ARGUMENT, err);
+        std::vector<uint64_t> q((size_t)e->comm_world * (1 + 64));
+        std::memcpy(q.data(), all.data(), q.size() * 8);
+        for (int r = 0; r < e->comm_world; ++r)
+            if (!q[(size_t)r * 65]) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_allreduce_u64: bad argument on rank " + std::to_string(r) + " (values NULL or n outside 0..64)");
+        uint64_t sum[64] = {};
+        for (int r = 0; r < e->comm_world; ++r)
+            for (int i = 0; i < n; ++i) sum[i] += q[(size_t)r * 65 + 1 + (size_t)i];
+        if (n > 0) std::memcpy(values, sum, (size_t)n * 8);
+        return AZ_OK;
+    }
     try {
         HIPCHK(hipSetDevice(e->device));
         unsigned long long* d = (unsigned long long*)e->comm_scratch.ensure((size_t)n * 8, e->stream);
@@ -2140,42 +2208,130 @@ az_status az_allreduce_u64(az_engine* e, uint64_t* values, int32_t n) {
     } catch (const HipFail& f) { return fail_hip(e, f); }
 }
 
+az_status az_allreduce_u64(az_engine* e, uint64_t* values, int32_t n) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    const bool args_ok = values && n >= 0 && n <= 64;
+    if (!e->local && !args_ok) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_allreduce_u64: bad argument");
+    if (!e->has_comm()) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_allreduce_u64: no communicator (az_comm_init)");
+    if (n == 0 && !e->local) return AZ_OK;      // in-process, n = 0 still meets the peers: a rank that passed another n must hear of it
+    return comm_sum_u64(e, values, n, args_ok);
+}
+
+struct CommHello { long long n, cap, dst, pad; };
+
+// primitive 1: all-gather of the per-rank hello records.  RCCL: through d_stage (world + 1 records of device memory) on the engine's
+// stream; in-process: one round of host records.
+static az_status comm_allgather_hello(az_engine* e, const CommHello& mine, CommHello* d_stage, std::vector<CommHello>& hello) {
+    const int world = e->comm_world;
+    hello.resize((size_t)world);
+    if (e->local) {
+        std::vector<unsigned char> all;
+        const std::string err = e->local->all_gather(e->comm_rank, LOCAL_OP_GATHER_HELLO, 0, &mine, sizeof mine, &all);
+        if (!err.empty()) return fail(e, AZ_ERR_BAD_ARGUMENT, err);
+        std::memcpy(hello.data(), all.data(), all.size());
+        return AZ_OK;
+    }
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemcpyAsync(d_stage + world, &mine, sizeof mine, hipMemcpyHostToDevice, s));
+    NCCLCHK(g_rccl.AllGather(d_stage + world, d_stage, sizeof(CommHello), ncclUint8, e->comm, s));
+    HIPCHK(hipMemcpyAsync(hello.data(), d_stage, (size_t)world * sizeof(CommHello), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return AZ_OK;
+}
+
+// primitive 3: the exchange of the packed tuples.  off[r] = rank r's first tuple in rank order (off[world] = total); d_all = the
+// receive area of a receiving rank.  RCCL: ONE grouped gatherv (a receiving rank posts a receive per peer, a sending rank one send
+// per receiver).  In-process, host-synchronous (no stream ever waits on another engine's event): every rank publishes its packed
+// block (device pointer, count) at barrier A, a receiving rank copies every rank's block into d_all on its own stream and
+// synchronises it, and barrier B keeps every sender's block alive (comm_scratch may move it) until every copy is done.  pack_ok =
+// false (in-process only): this rank's packing failed; it still meets its peers, and every rank returns the same error.
+static az_status comm_exchange(az_engine* e, const PackedSample* d_mine, bool pack_ok, const std::vector<long long>& off, int dst_rank,
+                               bool receiver, PackedSample* d_all) {
+    const int world = e->comm_world, rank = e->comm_rank;
+    hipStream_t s = e->stream;
+    const long long n = off[(size_t)rank + 1] - off[(size_t)rank];
+    if (e->local) {
+        struct Post { unsigned long long ptr; long long n; int32_t ok, pad; };
+        bool ok = pack_ok;
+        if (ok && hipStreamSynchronize(s) != hipSuccess) ok = false;          // 1. packed and synchronised
+        const Post mine{(unsigned long long)(uintptr_t)d_mine, n, ok ? 1 : 0, 0};
+        std::vector<unsigned char> all;
+        std::string err = e->local->all_gather(rank, LOCAL_OP_GATHER_POST, 0, &mine, sizeof mine, &all);     // 2. barrier A
+        if (!err.empty()) return fail(e, AZ_ERR_BAD_ARGUMENT, err);
+        std::vector<Post> post((size_t)world);
+        std::memcpy(post.data(), all.data(), all.size());
+        for (int r = 0; r < world; ++r)
+            if (!post[(size_t)r].ok) return fail(e, AZ_ERR_HIP, "az_gather_samples: rank " + std::to_string(r) + " could not stage its tuples (HIP error); nothing was exchanged");
+        int32_t copied = 1;                                                    // 3. the receivers' copies, on their own streams
+        if (receiver) {
+            for (int r = 0; r < world && copied; ++r) {
+                const long long cr = off[(size_t)r + 1] - off[(size_t)r];
+                if (cr > 0 && hipMemcpyAsync(d_all + off[(size_t)r], (const void*)(uintptr_t)post[(size_t)r].ptr, (size_t)cr * sizeof(PackedSample),
+                                             hipMemcpyDefault, s) != hipSuccess) copied = 0;
+            }
+            if (hipStreamSynchronize(s) != hipSuccess) copied = 0;
+        }
+        err = e->local->all_gather(rank, LOCAL_OP_GATHER_DONE, 0, &copied, sizeof copied, &all);          // 4. barrier B
+        if (!err.empty()) return fail(e, AZ_ERR_BAD_ARGUMENT, err);
+        for (int r = 0; r < world; ++r) {
+            int32_t c;
+            std::memcpy(&c, all.data() + (size_t)r * sizeof c, sizeof c);
+            if (!c) return fail(e, AZ_ERR_HIP, "az_gather_samples: rank " + std::to_string(r) + "'s copies of the exchange failed (HIP error)");
+        }
+        return AZ_OK;
+    }
+    struct GroupGuard {          // an error between GroupStart and GroupEnd must not leave the group open
+        bool open = false;
+        ~GroupGuard() { if (open) (void)g_rccl.GroupEnd(); }
+    } group;
+    NCCLCHK(g_rccl.GroupStart());
+    group.open = true;
+    for (int r = 0; r < world; ++r) {
+        const long long cr = off[(size_t)r + 1] - off[(size_t)r];
+        if (receiver) {
+            if (r != rank && cr > 0) NCCLCHK(g_rccl.Recv(d_all + off[(size_t)r], (size_t)cr * sizeof(PackedSample), ncclUint8, r, e->comm, s));
+            if (r == rank && n > 0) HIPCHK(hipMemcpyAsync(d_all + off[(size_t)r], d_mine, (size_t)n * sizeof(PackedSample), hipMemcpyDeviceToDevice, s));
+        }
+        if (r != rank && n > 0 && (dst_rank < 0 || r == dst_rank)) NCCLCHK(g_rccl.Send(d_mine, (size_t)n * sizeof(PackedSample), ncclUint8, r, e->comm, s));
+    }
+    group.open = false;
+    NCCLCHK(g_rccl.GroupEnd());
+    return AZ_OK;
+}
+
 // The episode-batch exchange.  EVERY decision that could make one rank leave early is taken from data every rank holds: the first
 // collective carries, per rank, its tuple count (or -1: its local buffers are unusable), the capacity it can receive into (-1: not a
-// receiver, -2: receive buffers unusable) and its dst_rank -- so either every rank posts its part of the grouped exchange or every rank
+// receiver, -2: receive buffers unusable) and its dst_rank -- so either every rank posts its part of the exchange or every rank
 // returns the same error without posting anything.  (Round 3's version returned on the receiving rank alone and left its peers
 // waiting in ncclGroupEnd.)
 az_status az_gather_samples(az_engine* e, const az_samples* local, int32_t dst_rank, az_samples* gathered, int64_t* counts_out) {
     if (!e || !local) return AZ_ERR_BAD_ARGUMENT;
-    if (!e->comm) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_gather_samples: no communicator (az_comm_init)");
+    if (!e->has_comm()) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_gather_samples: no communicator (az_comm_init)");
     const int world = e->comm_world, rank = e->comm_rank;
     long long n = local->count;
     const bool dst_ok = dst_rank >= -1 && dst_rank < world;
     const bool receiver = dst_ok && (dst_rank < 0 || rank == dst_rank);         // dst_rank = -1: every rank receives (all-gather)
     const bool local_ok = dst_ok && n >= 0 && (n == 0 || (local->states && local->pis && local->zs));
     const bool recv_ok = !receiver || (gathered && gathered->states && gathered->pis && gathered->zs && gathered->capacity >= 0);
-    struct Hello { long long n, cap, dst, pad; };
-    const Hello mine{local_ok ? n : -1, !receiver ? -1 : (recv_ok ? gathered->capacity : -2), dst_rank, 0};
+    const CommHello mine{local_ok ? n : -1, !receiver ? -1 : (recv_ok ? gathered->capacity : -2), dst_rank, 0};
     if (!local_ok) n = 0;
-    struct GroupGuard {          // an error between GroupStart and GroupEnd must not leave the group open
-        bool open = false;
-        ~GroupGuard() { if (open) (void)g_rccl.GroupEnd(); }
-    } group;
     try {
         HIPCHK(hipSetDevice(e->device));
         hipStream_t s = e->stream;
         // one allocation, kept by the engine and grown on demand (it was five to nine hipMalloc / hipFree pairs per call):
         // [hello x (world + 1)] [st | pi | z | packed] of the local tuples; the receive side is carved once the total is known
-        const size_t hello_b = ((size_t)world + 1) * sizeof(Hello);
+        const size_t hello_b = ((size_t)world + 1) * sizeof(CommHello);
         const size_t local_b = (size_t)n * (16 + 28 + 4 + sizeof(PackedSample));
-        char* base = (char*)e->comm_scratch.ensure(hello_b + local_b + 256, s);
-        Hello* d_hello = (Hello*)base;
+        char* base = nullptr;
+        try {
+            base = (char*)e->comm_scratch.ensure(hello_b + local_b + 256, s);
+        } catch (const HipFail&) {      // in-process the hello needs no device memory: the failure is met again (and published) at step 2
+            if (!e->local) throw;
+        }
         // 1. all-gather of the per-rank hello records (count, receive capacity, dst_rank)
-        HIPCHK(hipMemcpyAsync(d_hello + world, &mine, sizeof mine, hipMemcpyHostToDevice, s));
-        NCCLCHK(g_rccl.AllGather(d_hello + world, d_hello, sizeof(Hello), ncclUint8, e->comm, s));
-        std::vector<Hello> hello((size_t)world);
-        HIPCHK(hipMemcpyAsync(hello.data(), d_hello, (size_t)world * sizeof(Hello), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        std::vector<CommHello> hello;
+        az_status st = comm_allgather_hello(e, mine, (CommHello*)base, hello);
+        if (st) return st;
         long long total = 0;
         int bad_local = -1, bad_recv = -1, bad_dst = -1;
         for (int r = 0; r < world; ++r) {
@@ -2190,37 +2346,37 @@ az_status az_gather_samples(az_engine* e, const az_samples* local, int32_t dst_r
         if (bad_dst >= 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_gather_samples: dst_rank outside the communicator or not the same on every rank (rank " + std::to_string(bad_dst) + ")");
         if (bad_local >= 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_gather_samples: rank " + std::to_string(bad_local) + "'s local tuples need states, pis and zs");
         if (bad_recv >= 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_gather_samples: rank " + std::to_string(bad_recv) + "'s gathered buffers are missing or too small for " + std::to_string(total) + " tuples");
-        // 2. pack this rank's tuples (inputs may be host or device memory)
+        std::vector<long long> off((size_t)world + 1, 0);           // rank r's tuples start at off[r] of the rank-order result
+        for (int r = 0; r < world; ++r) off[(size_t)r + 1] = off[(size_t)r] + hello[r].n;
+        // 2. pack this rank's tuples (inputs may be host or device memory).  In-process, a failure here is published at the exchange
+        // (the peers are about to wait for this rank there); over RCCL it returns before anything is posted, as it always did.
         const size_t recv_b = receiver ? (size_t)total * (sizeof(PackedSample) + 16 + 28 + 4) : 0;
-        base = (char*)e->comm_scratch.ensure(hello_b + local_b + recv_b + 512, s);      // may move: nothing of step 1 is needed any more
-        char* cur = base + hello_b;
+        char* cur = nullptr;
         auto carve = [&](size_t bytes) { char* q = cur; cur += (bytes + 63) / 64 * 64; return q; };
-        ulonglong2* d_st = (ulonglong2*)carve((size_t)n * 16);
-        float* d_pi = (float*)carve((size_t)n * 28);
-        float* d_z = (float*)carve((size_t)n * 4);
-        PackedSample* d_mine = (PackedSample*)carve((size_t)n * sizeof(PackedSample));
-        if (n > 0) {
-            HIPCHK(hipMemcpyAsync(d_st, local->states, (size_t)n * 16, hipMemcpyDefault, s));
-            HIPCHK(hipMemcpyAsync(d_pi, local->pis, (size_t)n * 28, hipMemcpyDefault, s));
-            HIPCHK(hipMemcpyAsync(d_z, local->zs, (size_t)n * 4, hipMemcpyDefault, s));
-            hipLaunchKernelGGL(k_pack_samples, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_st, d_pi, d_z, d_mine, n);
-        }
-        // 3. ONE exchange (a grouped gatherv): a receiving rank posts a receive per peer, a sending rank one send per receiver
-        PackedSample* d_all = receiver ? (PackedSample*)carve((size_t)total * sizeof(PackedSample)) : nullptr;
-        NCCLCHK(g_rccl.GroupStart());
-        group.open = true;
-        long long off = 0;
-        for (int r = 0; r < world; ++r) {
-            const long long cr = hello[r].n;
-            if (receiver) {
-                if (r != rank && cr > 0) NCCLCHK(g_rccl.Recv(d_all + off, (size_t)cr * sizeof(PackedSample), ncclUint8, r, e->comm, s));
-                if (r == rank && n > 0) HIPCHK(hipMemcpyAsync(d_all + off, d_mine, (size_t)n * sizeof(PackedSample), hipMemcpyDeviceToDevice, s));
+        PackedSample* d_mine = nullptr;
+        bool pack_ok = true;
+        try {
+            base = (char*)e->comm_scratch.ensure(hello_b + local_b + recv_b + 512, s);      // may move: nothing of step 1 is needed any more
+            cur = base + hello_b;
+            ulonglong2* d_st = (ulonglong2*)carve((size_t)n * 16);
+            float* d_pi = (float*)carve((size_t)n * 28);
+            float* d_z = (float*)carve((size_t)n * 4);
+            d_mine = (PackedSample*)carve((size_t)n * sizeof(PackedSample));
+            if (n > 0) {
+                HIPCHK(hipMemcpyAsync(d_st, local->states, (size_t)n * 16, hipMemcpyDefault, s));
+                HIPCHK(hipMemcpyAsync(d_pi, local->pis, (size_t)n * 28, hipMemcpyDefault, s));
+                HIPCHK(hipMemcpyAsync(d_z, local->zs, (size_t)n * 4, hipMemcpyDefault, s));
+                hipLaunchKernelGGL(k_pack_samples, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_st, d_pi, d_z, d_mine, n);
             }
-            if (r != rank && n > 0 && (dst_rank < 0 || r == dst_rank)) NCCLCHK(g_rccl.Send(d_mine, (size_t)n * sizeof(PackedSample), ncclUint8, r, e->comm, s));
-            off += cr;
+        } catch (const HipFail&) {
+            if (!e->local) throw;
+            pack_ok = false;
         }
-        group.open = false;
-        NCCLCHK(g_rccl.GroupEnd());
+        // 3. ONE exchange
+        PackedSample* d_all = receiver && pack_ok ? (PackedSample*)carve((size_t)total * sizeof(PackedSample)) : nullptr;
+        st = comm_exchange(e, d_mine, pack_ok, off, dst_rank, receiver, d_all);
+        if (st) return st;
+        // 4. unpack into the caller's buffers
         if (receiver) {
             ulonglong2* o_st = (ulonglong2*)carve((size_t)total * 16);
             float* o_pi = (float*)carve((size_t)total * 28);

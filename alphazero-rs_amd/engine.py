@@ -85,7 +85,7 @@ EXPORTS = [
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
     "az_tree_slot_error", "az_tree_share_stats", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
-    "az_comm_unique_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
+    "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
 COMM_ID_BYTES = 128
 
@@ -141,6 +141,7 @@ def load_library(path=LIB_PATH):
         "az_arena_get_evals": (i32, [vp, i32, vp, vp, vp, vp]),
         "az_arena_get_moves": (i32, [vp, vp, vp]),
         "az_comm_unique_id": (i32, [vp, vp]),
+        "az_comm_local_id": (i32, [vp, i32, vp]),
         "az_comm_init": (i32, [vp, i32, i32, vp]),
         "az_comm_destroy": (i32, [vp]),
         "az_gather_samples": (i32, [vp, C.POINTER(az_samples), i32, C.POINTER(az_samples), vp]),
@@ -415,6 +416,14 @@ class Engine:
     def comm_unique_id(self):
         buf = np.zeros(COMM_ID_BYTES, np.uint8)
         self._check(self._lib.az_comm_unique_id(self._h, _ptr(buf)))
+        return buf
+
+    def comm_local_id(self, world):
+        """The 128-byte id of an IN-PROCESS communicator of `world` ranks: engines of this process that comm_init with it form one
+        world without RCCL.  Each rank's collectives block until every rank has called them, so drive each engine from its own
+        thread (ctypes releases the GIL during the call)."""
+        buf = np.zeros(COMM_ID_BYTES, np.uint8)
+        self._check(self._lib.az_comm_local_id(self._h, int(world), _ptr(buf)))
         return buf
 
     def comm_init(self, rank, world, unique_id):

@@ -25,6 +25,11 @@
  *     thread captures its search loop as a hipGraph, HIP refuses the blocking
  *     copies of the other thread (hipErrorStreamCaptureImplicit, reported as
  *     AZ_ERR_HIP).  Measured gain of that arrangement: none (profiles/README.md).
+ *     The same holds for training's captured step: such engines set "train_graph" 0 as well.
+ *     A COLLECTIVE (az_comm_init with a local or an RCCL id, az_gather_samples, az_allreduce_u64, az_arena with
+ *     allreduce_wld) blocks until every rank of the communicator has called it, so the ranks of an in-process
+ *     communicator (az_comm_local_id) are driven by one host thread each; a rank that never arrives is waited for
+ *     (there is no timeout, as with RCCL).
  *     az_arena overlaps its two models' searches on two HIP streams; streams share the device's few hardware queues, so a
  *     process that keeps many other streams alive can make the two share one (measured: 2755 -> 1860 games/s with one extra
  *     idle stream).
@@ -367,7 +372,7 @@ typedef struct az_arena_params {
      * initial board (None). */
     int32_t use_start_board;
     /* sharded call (total_games > 0) on an engine with a communicator (az_comm_init): != 0 sums out_wld over the ranks
-     * (one 3-counter all-reduce over RCCL), so every rank returns the whole arena's tally */
+     * (one 3-counter all-reduce over the communicator), so every rank returns the whole arena's tally */
     int32_t allreduce_wld;
     uint64_t start_board[2];
 } az_arena_params;
@@ -386,9 +391,22 @@ az_status az_arena_get_moves(az_engine* e, int32_t* game_len, uint8_t* moves);
  * src/coach.rs:241-272 fans episodes out over a rayon pool; here one process per GPU plays a shard of the global
  * episode ids and the (s, pi, z) tuples meet once per episode batch) --------------------------------------------------
  * RCCL over xGMI on the engine's own stream.  az_comm_unique_id is called on ONE rank; the host ships the 128 bytes to the
- * others by its own means (a file, MPI, torch.distributed ...) and every rank calls az_comm_init with them. */
+ * others by its own means (a file, MPI, torch.distributed ...) and every rank calls az_comm_init with them.
+ * The id alone decides the backend: an id of az_comm_local_id makes the same collectives run between engines of this process,
+ * without RCCL (below). */
 #define AZ_COMM_ID_BYTES 128
 az_status az_comm_unique_id(az_engine* e, uint8_t id[AZ_COMM_ID_BYTES]);
+/* An id for an IN-PROCESS communicator of `world` ranks: engines of this process (same or different devices) that
+ * call az_comm_init(e, rank, world, id) with it form a world without RCCL.  The id is a magic prefix, a process-unique serial and
+ * `world`; it serves one world.  az_comm_init with it returns once all `world` ranks have joined; refused at once
+ * (AZ_ERR_BAD_ARGUMENT): a world that differs from the id's, a rank already taken, an id whose world is already complete, an
+ * unknown serial or another process's id, an engine that already has a communicator.  Peer access between the members' devices
+ * is enabled where the hardware allows it.  The collectives return what the RCCL backend returns, bit for bit, with the same
+ * verdicts; the data moves host-synchronously (each rank packs and synchronises its stream, the receivers copy every rank's block
+ * on their own streams, two barriers; no stream waits on another engine's event).  Also AZ_ERR_BAD_ARGUMENT on every rank, with
+ * one message naming the ranks, never a hang: ranks in different collectives or passing different n to az_allreduce_u64; a
+ * rank that left (az_comm_destroy or az_destroy): the other ranks' pending and later collectives fail, a blocked one is woken. */
+az_status az_comm_local_id(az_engine* e, int32_t world, uint8_t id[AZ_COMM_ID_BYTES]);
 az_status az_comm_init(az_engine* e, int32_t rank, int32_t world, const uint8_t id[AZ_COMM_ID_BYTES]);
 az_status az_comm_destroy(az_engine* e);
 /* One gather of the packed tuples of `local` (count tuples: states [count,2], pis [count,7], zs [count]; host or device)

@@ -408,7 +408,8 @@ class Coach {
     // One process per GPU: rank r of `world` plays the episode ids shard_range(num_eps, r, world) of every
     // iteration and the arena games shard_range(num_arena_games, r, world); the tuples meet in ONE az_gather_samples (every
     // rank receives: the trainer is replicated) and the arena tally in one 3-counter all-reduce.  world > 1 needs a
-    // communicator on the engine (az_comm_unique_id on one rank, the 128 bytes shipped by the host, az_comm_init on all).
+    // communicator on the engine (az_comm_unique_id on one rank, the 128 bytes shipped by the host, az_comm_init on all; or, for the
+    // engines of ONE process driven by one thread each, az_comm_local_id: examples/connect_four_threads.cpp).
     void shard(int rank, int world) {
         if (world < 1 || rank < 0 || rank >= world) throw Panic("shard: rank outside the world");
         rank_ = rank; world_ = world;

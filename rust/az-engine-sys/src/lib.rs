@@ -102,6 +102,8 @@ extern "C" {
     pub fn az_arena_get_moves(e: *mut az_engine, game_len: *mut i32, moves: *mut u8) -> c_int;
     // ---- the collective of the sharded Coach loop (one process per GPU; RCCL on the engine's stream)
     pub fn az_comm_unique_id(e: *mut az_engine, id: *mut u8) -> c_int;
+    // an in-process communicator: engines of this process, one host thread each, form one world without RCCL
+    pub fn az_comm_local_id(e: *mut az_engine, world: i32, id: *mut u8) -> c_int;
     pub fn az_comm_init(e: *mut az_engine, rank: i32, world: i32, id: *const u8) -> c_int;
     pub fn az_comm_destroy(e: *mut az_engine) -> c_int;
     pub fn az_gather_samples(e: *mut az_engine, local: *const az_samples, dst_rank: i32, gathered: *mut az_samples, counts_out: *mut i64) -> c_int;
@@ -250,6 +252,14 @@ pub fn self_play(e: *mut az_engine, p: &az_selfplay_params) -> (Vec<f32>, Vec<f3
     let n = out.count as usize;
     boards.truncate(n * 84); pis.truncate(n * 7); zs.truncate(n);
     (boards, pis, zs)
+}
+
+/// The id of an in-process communicator of `world` ranks (az_comm_local_id): hand the same 128 bytes to the `world` engines of
+/// this process, each on its own thread, and call `az_comm_init(e, rank, world, id)` on every one of them.
+pub fn comm_local_id(e: *mut az_engine, world: i32) -> [u8; 128] {
+    let mut id = [0u8; 128];
+    check(e, unsafe { az_comm_local_id(e, world, id.as_mut_ptr()) });
+    id
 }
 
 /// The ONE exchange of a sharded episode batch (each rank played `p.first_game_id ..` of the global episode ids): this rank's
