@@ -908,6 +908,7 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     if (is("conv3_tail") && (value == 0 || value == 1)) { e->netopt.conv3_tail = (int)value; return AZ_OK; }
     if (is("ring_packed") && (value == 0 || value == 1)) { e->netopt.ring_packed = (int)value; return AZ_OK; }
     if (is("conv3_planes") && (value == 0 || value == 1)) { e->netopt.conv3_planes = (int)value; return AZ_OK; }
+    if (is("conv3_wreg") && (value == 0 || value == 1)) { e->netopt.conv3_wreg = (int)value; return AZ_OK; }
     if (is("narrow_rows") && value >= 0 && value <= 65536) { e->netopt.narrow_rows = (int)value; return AZ_OK; }
     if (is("tree_block4") && (value == 0 || value == 1)) { e->tree_block4 = (int)value; return AZ_OK; }
     if (is("dedup_stats") && (value == 0 || value == 1)) { e->dedup_stats = (int)value; return AZ_OK; }
@@ -952,7 +953,7 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     if (is("ring_tile") && value >= 0 && value < 60000) { const int l = (int)(value / 10000); if (l >= 3 && l <= 5) o.ring_tile[l] = (int)(value % 10000); return AZ_OK; }
     if (is("conv3_ring") && value >= 0 && value <= 3) { o.conv3_ring = (int)value; return AZ_OK; }
     if (is("conv2_pipe") && (value == 0 || value == 1)) { o.conv2_pipe = (int)value; return AZ_OK; }
-    if (is("conv3_pipe") && ((value >= 0 && value <= 3) || (value >= 9 && value <= 15))) { o.conv3_pipe = (int)value; return AZ_OK; }
+    if (is("conv3_pipe") && ((value >= 0 && value <= 3) || (value >= 9 && value <= 16))) { o.conv3_pipe = (int)value; return AZ_OK; }
     if (is("conv3_pp") && (value == 0 || value == 1 || (value >= 16 && value <= 40))) { o.conv3_pp = (int)value; return AZ_OK; }
     if (is("conv1_table") && (value == 0 || value == 1)) { o.conv1_table = (int)value; return AZ_OK; }
     if (is("conv4_big") && value >= 0 && value <= 2) { o.conv4_big = (int)value; return AZ_OK; }
@@ -2398,6 +2399,12 @@ az_status az_gather_samples(az_engine* e, const az_samples* local, int32_t dst_r
 }
 
 #ifdef AZ_DIAG
+// Diagnostic library only (not part of the ABI): conv3's output of the last forward on the engine's first stream, `rows` boards of
+// [4][5][C] bf16, copied to `out`.  Returns the number of bytes, or -1.
+long long az_diag_read_conv3_out(az_engine* e, int rows, void* out) {
+    if (!e || !out || rows <= 0 || hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;
+    return netws_read_conv3_out(e->ws[0], rows, out);
+}
 // Diagnostic library only (not part of the ABI): the children of the node reached from tree g's current root by following `path`
 // (child indices, not actions).  out rows of 8 u64: slot, a, ctr (resolved through a link), prior bits, link, meta, own ctr, key.
 // Returns the number of children, or -1.

@@ -76,6 +76,8 @@ struct NetOptions {
     int ring_packed = 1;    // the LDS-DMA ring reads its weight stages from the model's packed copy (one stage = 16 KiB of consecutive bytes instead of
                             // 128 rows K * 2 bytes apart; conv4 -3 %; bit-identical); 0 = from the [N][K] weights
     int conv3_tail = 1;     // conv3: a short last round of workgroups is cut into half tiles (k_conv3_auto); 0 = full tiles only (bit-identical)
+    int conv3_wreg = 1;     // conv3: the weight operand straight from global memory into registers in MFMA fragment order (k_conv3_auto_wreg; no
+                            // weight tile in LDS, no barrier in the K loop; needs conv3_planes); 0 = the weight tile through LDS (k_conv3_auto; bit-identical)
     int narrow_rows = 32;   // conv3 / conv4 / fc1 / fc2 of a batch of at most this many rows (x 2 for conv4, x 4 for the FCs) run as the register-fed
                             // skinny GEMM (k_gemm_skinny), decided on the device from the exact row count; 0 = never (bit-identical)
     // ---- diagnostic library only ----
@@ -87,7 +89,7 @@ struct NetOptions {
     int conv1_table = 1;    // conv2 as a GEMM gathers its image from the conv1 table (1) / runs k_conv1 into act1 (0)
     int conv2_pipe = 1;     // conv2 as a GEMM: k_conv_same_pipe (1) / round 1's k_conv_img2 (0)
     int conv3_pipe = 1;     // conv3: 1 k_conv_valid_pipe with interleaved fragment reads; 2 without; 0 round 1's kernel; 3 clock stamps;
-                            // 9-15 its timing ladder (WRONG results)
+                            // 9-15 its timing ladder, 16 the bound of a register-fed weight operand (WRONG results)
     int conv3_ring = 0;     // force conv3 onto the ring (1 / 2: 128-row tiles with 2 / 4 stages, 3: device-picked tile)
     int conv4_big = 0;      // conv4 on the 256x256 kernel (1 always, 2 from 4096 rows)
     int fc_ring = 1;        // 1 ring with the tile picked on the device; 2 picked on the host; 3 plain 128-row ring; 0 register-staged tiles
@@ -95,6 +97,8 @@ struct NetOptions {
 };
 // diagnostic variant 13 only: per-block {shader cycles, 100 MHz ticks} of the conv2 K loop
 bool netws_read_clock_stamps(NetWorkspace* ws, unsigned long long* out2048);
+// diagnostic library's reader: conv3's output of the workspace's last forward, rows x [4][5][C] bf16 -> out; returns the bytes copied or -1
+long long netws_read_conv3_out(NetWorkspace* ws, int rows, void* out);
 // allocate what a forward under `opt` may need later (conv1's haloed image for the kernel sets that run conv1 as a kernel), so that
 // convnet_forward never allocates -- it may run inside a stream capture
 bool convnet_prepare(NetWorkspace* ws, const NetOptions& opt);

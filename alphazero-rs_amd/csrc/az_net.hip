@@ -281,6 +281,7 @@ struct GemmDesc {
     const uint16_t* Wp;        // k_conv3_pp: the layer's weights packed as LDS stage images (ConvNet::wp3), nullptr = not available
     const uint16_t* Wr;        // gemm_ring_body: the layer's weights as the ring's LDS stage images [N / 128][K / 64][128 rows][128 B] in K-step order
                                // (ConvNet::wr: one stage = 16 KiB of CONSECUTIVE global bytes instead of 128 rows K * 2 bytes apart), nullptr = read W
+    const uint16_t* Wf;        // conv_valid_tile<.., WREG>: conv3's weights in MFMA fragment order (ConvNet::wf3), nullptr = not available
 };
 
 constexpr int GBM = 128, GBN = 128, GBK = 64;
@@ -833,6 +834,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_same_pipe(const GemmDesc d) {
 constexpr int C3_PLANE_BYTES = 32768;         // one chunk-parity plane: 512 cells of 64 B
 constexpr int C3_TAB_INV = 512;               // uint16 per LDS row cell: source image row | swizzle << 10
 constexpr int C3_TAB_RD = 9 * 2 * 16 * 8;     // uint16 per (tap, wave row, fragment row, row tile): the cell's byte offset in its plane
+constexpr int WF3_STEP = 4096;                // bf16 per (64-channel group, K-step) of ConvNet::wf3 (conv_valid_tile<.., WREG>): 8 KiB
+constexpr int WF3_PAD = 1;                    // K-steps of padding: the kernel requests one step past the last and never uses it
 constexpr int C3_NB = 12;     // (conv4 as <L, 19, 4, 5, 4> is bit-identical too and was measured neutral: it stays on k_gemm256)
 
 // ---- the same tile with the LDS-DMA issued from inline asm and a software-pipelined K-step ---------------------------
@@ -847,7 +850,7 @@ constexpr int C3_NB = 12;     // (conv4 as <L, 19, 4, 5, 4> is bit-identical too
 //   reads fbX, faX(ks0) of step k+1 | MFMA fbY x faY(ks1)
 // Same K order per accumulator as k_conv_valid_img2 (and every other conv3 kernel): bit-identical.
 
-template <int LAYER, int NB, int IH, int IW, bool STAMP = false, int ABLATE = 0, bool IL = false>   // IL: fragment reads interleaved into the MFMA clusters (sched_group_barrier); STAMP: diagnostic build, per-segment s_memtime sums of wave 0 into d.dbg; ABLATE (timing only, WRONG results): 1 no image switch, 2 + no wait for the weight DMA
+template <int LAYER, int NB, int IH, int IW, bool STAMP = false, int ABLATE = 0, bool IL = false>   // IL: fragment reads interleaved into the MFMA clusters (sched_group_barrier); STAMP: diagnostic build, per-segment s_memtime sums of wave 0 into d.dbg; ABLATE (timing only, WRONG results): 1 no image switch, 2 + no wait for the weight DMA, 3 + no weight DMA, 4 + no barriers, 5 + no fragment reads; 6 the bound of a register-fed weight operand: MFMAs, the 16 image fragment reads and the image switch, no weight tile at all (no DMA, no per-step barrier, weight fragments loop-invariant)
 __global__ __launch_bounds__(256, 2) void k_conv_valid_pipe(const GemmDesc d) {
     constexpr int OH = IH - 2, OW = IW - 2, OUT_PER = OH * OW, IN_PER = IH * IW;
     constexpr int OUT_ROWS = NB * OUT_PER, IMG_R = NB * IN_PER;
@@ -909,7 +912,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_valid_pipe(const GemmDesc d) {
     const int b_row0 = IMG_BYTES + (wc * 64 + frow) * 128;
     const int coffB0 = ((0 + fq) ^ fsw) << 4, coffB1 = ((4 + fq) ^ fsw) << 4;
 #define AZ_PLDA(dst_, mt0_, ks_, dt_)                                                                        \
-    if constexpr (ABLATE < 5) _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                       \
+    if constexpr (ABLATE < 5 || ABLATE == 6) _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                       \
         const int r_ = rbase[(mt0_) + i_] + (dt_);                                                           \
         dst_[i_] = *(const bf16x8*)(smem + r_ * 128 + ((((ks_) * 4 + fq) ^ (r_ & 7)) << 4));                 \
     }
@@ -983,7 +986,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_valid_pipe(const GemmDesc d) {
         if constexpr (ABLATE < 4) __builtin_amdgcn_s_barrier();
         AZ_PSB;
         AZ_PSTAMP(5);
-        if (ABLATE <= 0 && sw && ncbi < ncb) {                                  // single image buffer: the switch is covered by the CU's other workgroup
+        if ((ABLATE <= 0 || ABLATE == 6) && sw && ncbi < ncb) {                 // single image buffer: the switch is covered by the CU's other workgroup
+            if constexpr (ABLATE == 6) __builtin_amdgcn_s_barrier();            // no per-step barrier: every wave is past its last read of the old slice
             AZ_PDMA_IMG(ncbi);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -1062,23 +1066,26 @@ __global__ __launch_bounds__(256, 2) void k_conv_valid_pipe(const GemmDesc d) {
 //                                               run alone (k_conv3_auto)
 //   (conv4 as NB 20, 4x5, MT 4, NTW 4 -- 120 of 128 rows x 128 channels, 50 + 16 KiB -- was built and measured in round 3: bit-identical and
 //    slower than the ring at every batch size, 64 against 59 us at 2300 rows, 258 against 197 at 8192: profiles/README.md; removed)
-template <int NB, int IH, int IW, int MT, int NTW, bool PLANES = false>
+//   WREG = 1: the WEIGHT operand does not pass through LDS at all.  A wave loads its weight fragments straight from a fragment-ordered
+//   copy of the layer's weights (ConvNet::wf3) into two register slots of half a K-step each, half a K-step ahead; LDS holds
+//   the image only, and the K loop has NO barrier except around the image switch.  See the WREG branch of conv_valid_tile.
+template <int NB, int IH, int IW, int MT, int NTW, bool PLANES = false, int WREG = 0>
 struct ConvTile {
     static constexpr int OH = IH - 2, OW = IW - 2, OUT_PER = OH * OW, IN_PER = IH * IW;
     static constexpr int OUT_ROWS = NB * OUT_PER, IMG_R = NB * IN_PER;
     static constexpr int NCOL = 32 * NTW, WROWS = 16 * MT;
     static constexpr int IMG_BYTES = PLANES ? 2 * C3_PLANE_BYTES : (IMG_R * 128 + 1023) / 1024 * 1024;
-    static constexpr int LDS_BYTES = IMG_BYTES + NCOL * 128;
+    static constexpr int LDS_BYTES = IMG_BYTES + (WREG ? 0 : NCOL * 128);
     static constexpr int EP_STRIDE = NCOL * 2 + 16;
     static_assert(OUT_ROWS <= 2 * WROWS && IMG_R % 8 == 0 && MT % 2 == 0, "tile");
     static_assert(LDS_BYTES <= 81920, "two workgroups must fit a CU's 160 KiB");
     static_assert(OUT_ROWS * EP_STRIDE <= LDS_BYTES, "the output tile must fit the dead buffers");
 };
 
-template <int NB, int IH, int IW, int MT, int NTW, bool PLANES = false>
+template <int NB, int IH, int IW, int MT, int NTW, bool PLANES = false, int WREG = 0>
 __device__ __forceinline__ void conv_valid_tile(const GemmDesc& d, unsigned char* smem, const int b0 /*first board*/, const int n0 /*first column*/,
                                                 const int n_boards) {
-    using T = ConvTile<NB, IH, IW, MT, NTW, PLANES>;
+    using T = ConvTile<NB, IH, IW, MT, NTW, PLANES, WREG>;
     static_assert(!PLANES || (NB == C3_NB && IH == 6 && IW == 7 && MT == 8), "the cell maps are conv3's");
     constexpr int OUT_PER = T::OUT_PER, IN_PER = T::IN_PER, OUT_ROWS = T::OUT_ROWS, IMG_R = T::IMG_R, NCOL = T::NCOL, OW = T::OW;
     constexpr int IMG_BYTES = T::IMG_BYTES;
@@ -1177,16 +1184,18 @@ __device__ __forceinline__ void conv_valid_tile(const GemmDesc& d, unsigned char
         if (NM - nmf_ * (nr_) > 0) __builtin_amdgcn_sched_group_barrier(0x008, NM - nmf_ * (nr_), 0);        \
     }
     static_assert(NM >= NTW + MH, "a cluster must hold at least one MFMA per read of its region");
+    bf16x8 faX[MH], faY[MH];
+    const int ncb = C / 64;
+    const int nk = ncb * 9;
+    int cb = 0, tap = 0, dt = 0;
+    if constexpr (WREG == 0) {
     AZ_TDMA_W(0);
     AZ_TDMA_IMG(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    bf16x8 fbX[NTW], fbY[NTW], faX[MH], faY[MH];
+    bf16x8 fbX[NTW], fbY[NTW];
     AZ_TLDB(fbX, coffB0);
     AZ_TLDA(faX, 0, 0, 0, tq);
-    const int ncb = C / 64;
-    const int nk = ncb * 9;
-    int cb = 0, tap = 0, dt = 0;
     for (int kt = 0; kt < nk; ++kt) {
         const bool sw = tap == 8;
         const int ntap = sw ? 0 : tap + 1, ncbi = sw ? cb + 1 : cb;
@@ -1227,6 +1236,83 @@ __device__ __forceinline__ void conv_valid_tile(const GemmDesc& d, unsigned char
         AZ_TSB;
         tap = ntap; cb = ncbi; dt = ndt;
         if constexpr (PLANES) { tq[0] = ntq[0]; tq[1] = ntq[1]; tq[2] = ntq[2]; tq[3] = ntq[3]; }
+    }
+    } else {
+        // ---- WREG: the weight operand straight from global memory into registers ------------------------------------------------------
+        // ConvNet::wf3 holds the layer's weights as [N / 64][K-step in this loop's order][16-channel tile of the 64][k half][lane] x 16 B:
+        // the 8 bf16 W[n][tap * C + cb * 64 + ks * 32 + fq * 8 ..] of channel n = tile * 16 + frow are exactly what AZ_TLDB hands lane
+        // (fq, frow) from the LDS tile.  One fragment of a wave is 1 KiB of consecutive bytes (one buffer_load_dwordx4), the 2 * NTW
+        // fragments of a K-step are consecutive too, and the next K-step's follow 8 KiB on: one offset, advanced once per step.
+        // Two register slots of half a K-step each (NTW fragments): fwX (k half 0: clusters 1 and 2) is requested for step kt + 1 as soon
+        // as cluster 2 has left it, fwY (k half 1: clusters 3 and 4) behind cluster 4 -- every fragment is half a K-step (2 * NM MFMAs) in
+        // flight before its first use, and the loop needs no unrolling: a slot is a fixed set of registers.  Measured against deeper
+        // rings (profiles/README.md, "conv3 weights from registers"): a third slot (a full step ahead) written out over a tap triple
+        // makes the register allocator rename the 128 accumulators and spill; with register moves instead it is spill-free and
+        // 2.5 % (one slot moved) / 4 % (both) slower than this one -- the loads' latency is covered, what is left is their issue.
+        // Waits: the compiler sees these loads and its vmcnt waits for them are COUNTED.  The image DMA is issued from inline asm and the
+        // compiler does not count it: the kernel DRAINS at the image switch -- the switch's own vmcnt(0) waits for the DMA and for the
+        // weight loads in flight alike -- and between switches no DMA is in flight.  Even if one were, an uncounted older or younger
+        // request can only make a counted wait longer, never shorter (loads return in order).
+        // No barrier: a wave's weights are its own registers; the image is read-only between two switches.  At a switch: every wave past
+        // its last read of the old slice (barrier) -> DMA -> landed (vmcnt(0), barrier), as before.  (A barrier per K-step to keep the two
+        // waves that fetch the same fragments in step was measured too: 2 % slower.)
+        // Same K order per accumulator (channel block outer, tap inner, k half 0 then 1): bit-identical.
+        static_assert(PLANES && WREG == 1, "the ring needs the 64 KiB PLANES image (the epilogue's tile must fit it)");
+        static_assert(NTW == 4 || NTW == 2, "a wave's columns are one 64-channel group of the packed copy, or half of one");
+        // Buffer loads: the copy's descriptor and the wave's byte offset into it live in SGPRs (the offset advances by scalar adds), the
+        // only VGPR of the address is one loop-invariant lane offset (as flat global loads the compiler kept several 64-bit lane
+        // addresses).  A request past the copy (there is none: WF3_PAD) would read zeros, not fault.
+        const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)d.Wf, 0, (d.K * d.N + WF3_PAD * WF3_STEP) * 2, 0x00020000);
+        uint32_t wfo = (uint32_t)(((n0 >> 6) + (NTW == 4 ? wc : 0)) * nk) * 8192u + (uint32_t)(NTW == 4 ? 0 : wc * 2) * 2048u;
+        const uint32_t wlane = (uint32_t)lane * 16u;
+        bf16x8 fwX[NTW], fwY[NTW];
+#define AZ_TLDW(dst_, off_)                                                                                  \
+    _Pragma("unroll") for (int j_ = 0; j_ < NTW; ++j_)                                                       \
+        dst_[j_] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, wlane, wfo + (uint32_t)((off_) + j_ * 2048), 0));
+        AZ_TDMA_IMG(0);
+        AZ_TLDW(fwX, 0);
+        AZ_TLDW(fwY, 1024);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        AZ_TLDA(faX, 0, 0, 0, tq);
+        for (int kt = 0; kt < nk; ++kt) {
+            const bool sw = tap == 8;
+            const int ntap = sw ? 0 : tap + 1, ncbi = sw ? cb + 1 : cb;
+            const int nky = ntap / 3, ndt = nky * IW + (ntap - nky * 3);
+            { const uint4 v = rdtab[ntap * 32]; ntq[0] = v.x; ntq[1] = v.y; ntq[2] = v.z; ntq[3] = v.w; }
+            AZ_TLDA(faY, MH, 0, dt, tq);
+            AZ_TMMA(0, fwX, faX);
+            AZ_TMIX(MH);
+            AZ_TSB;
+            AZ_TLDA(faX, 0, 1, dt, tq);
+            AZ_TMMA(MH, fwX, faY);
+            AZ_TMIX(MH);
+            AZ_TSB;
+            AZ_TLDW(fwX, 8192);                                  // step kt + 1, k half 0, into the registers clusters 1 and 2 have just left
+            AZ_TLDA(faY, MH, 1, dt, tq);
+            AZ_TMMA(0, fwY, faX);
+            __builtin_amdgcn_sched_group_barrier(0x020, NTW, 0); // the global loads first: not behind the cluster's reads
+            AZ_TMIX(MH);
+            AZ_TSB;
+            if (sw && ncbi < ncb) {                              // single image buffer: the switch is covered by the CU's other workgroup
+                __builtin_amdgcn_s_waitcnt(0xC07F);
+                __builtin_amdgcn_s_barrier();                    // every wave is past its last read of the old slice
+                AZ_TDMA_IMG(ncbi);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the drain: the new slice AND the weight loads in flight
+                __builtin_amdgcn_s_barrier();
+            }
+            AZ_TSB;
+            AZ_TLDA(faX, 0, 0, ndt, ntq);                        // next step's first fragments, under this step's last cluster
+            AZ_TMMA(MH, fwY, faY);
+            AZ_TMIX(MH);
+            AZ_TSB;
+            AZ_TLDW(fwY, 8192 + 1024);                           // step kt + 1, k half 1 (past the last step: the copy's padding, unused)
+            wfo += 8192u;
+            AZ_TSB;
+            tap = ntap; cb = ncbi; dt = ndt;
+            tq[0] = ntq[0]; tq[1] = ntq[1]; tq[2] = ntq[2]; tq[3] = ntq[3];
+        }
+#undef AZ_TLDW
     }
 #undef AZ_TDMA_W
 #undef AZ_TDMA_IMG
@@ -1280,10 +1366,8 @@ __device__ __forceinline__ void conv_valid_tile(const GemmDesc& d, unsigned char
 // and is slower than the uncut round (2300 rows: 160 -> 170 us) -- a workgroup alone on its CU is not the 76-us level round 2's notes
 // priced it at, so those rounds stay uncut.
 constexpr int C3_TAIL = 128;
-template <int LAYER, bool PLANES>
-__global__ __launch_bounds__(256, 2) void k_conv3_auto(const GemmDesc d, const int full_grid, const int tail_wgs /* C3_TAIL, or 0: no tile is cut */) {
-    using TF = ConvTile<C3_NB, 6, 7, 8, 4, PLANES>;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[TF::LDS_BYTES];
+template <bool PLANES, int WREG>      // the weight operand: 0 through LDS, 1 straight into registers
+__device__ __forceinline__ void conv3_auto_body(const GemmDesc& d, unsigned char* smem, const int full_grid, const int tail_wgs) {
     const int n_boards = (int)(*d.n_dev);
     if (n_boards * d.rows_per_sample <= d.m_min) return;      // the small-batch kernel launched beside this one takes the batch
     if (blockIdx.x == 0 && threadIdx.x == 0 && d.acct && n_boards > 0) { atomicAdd(&d.acct[0], (unsigned long long)n_boards); atomicAdd(&d.acct[1], 1ull); }
@@ -1304,8 +1388,20 @@ __global__ __launch_bounds__(256, 2) void k_conv3_auto(const GemmDesc d, const i
     const int ntile = j % NT, mtile = (j / NT) * 8 + xcd;
     const int b0 = mtile * C3_NB, n0 = ntile * 128;
     if (b0 >= n_boards) return;
-    if (half < 0) conv_valid_tile<C3_NB, 6, 7, 8, 4, PLANES>(d, smem, b0, n0, n_boards);
-    else conv_valid_tile<C3_NB, 6, 7, 8, 2, PLANES>(d, smem, b0, n0 + half * 64, n_boards);
+    if (half < 0) conv_valid_tile<C3_NB, 6, 7, 8, 4, PLANES, WREG>(d, smem, b0, n0, n_boards);
+    else conv_valid_tile<C3_NB, 6, 7, 8, 2, PLANES, WREG>(d, smem, b0, n0 + half * 64, n_boards);
+}
+template <int LAYER, bool PLANES>
+__global__ __launch_bounds__(256, 2) void k_conv3_auto(const GemmDesc d, const int full_grid, const int tail_wgs /* C3_TAIL, or 0: no tile is cut */) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[ConvTile<C3_NB, 6, 7, 8, 4, PLANES>::LDS_BYTES];
+    conv3_auto_body<PLANES, 0>(d, smem, full_grid, tail_wgs);
+}
+// The same kernel with the weight operand straight from global memory in registers (conv_valid_tile<.., WREG>; "conv3_wreg"): a symbol of its own, so a
+// profile tells the two apart.
+template <int LAYER>
+__global__ __launch_bounds__(256, 2) void k_conv3_auto_wreg(const GemmDesc d, const int full_grid, const int tail_wgs) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[ConvTile<C3_NB, 6, 7, 8, 4, true, 1>::LDS_BYTES];
+    conv3_auto_body<true, 1>(d, smem, full_grid, tail_wgs);
 }
 
 #ifdef AZ_DIAG
@@ -1757,6 +1853,8 @@ struct ConvNet {                      // the WEIGHTS of one model id (21 MB bf16
     uint16_t* wg[5] = {nullptr};                       // conv2,3,4, fc1, fc2 folded bf16 [N][K]
     uint16_t* wr[5] = {nullptr};                       // conv2,3,4, fc1, fc2 as the ring's stage images (GemmDesc::Wr)
     uint16_t* wp3 = nullptr;                           // conv3's weights as k_conv3_pp's LDS stage images [N / 256][C / 64 * 18][256][32] (C % 256 == 0)
+    uint16_t* wf3 = nullptr;                           // conv3's weights in MFMA fragment order (k_conv3_auto_wreg) [C / 64][C / 64 * 9 K-steps][4][2][64 lanes][8]
+                                                       // + WF3_PAD K-steps of padding
     float* bg[5] = {nullptr};                          // folded bias f32 [N]
     float *wh = nullptr, *bh = nullptr;              // heads f32 [8][512], [8]
     template <class T> T* dalloc(size_t n) {
@@ -1861,6 +1959,8 @@ ConvNet* convnet_create(int channels, const char** err) {
     }
     ok &= (n->wh = n->dalloc<float>(8 * 512)) != nullptr;
     ok &= (n->bh = n->dalloc<float>(8)) != nullptr;
+    ok &= (n->wf3 = n->dalloc<uint16_t>(9 * (size_t)C * C + (size_t)WF3_PAD * WF3_STEP)) != nullptr;
+    if (n->wf3) ok &= hipMemset(n->wf3 + 9 * (size_t)C * C, 0, (size_t)WF3_PAD * WF3_STEP * sizeof(uint16_t)) == hipSuccess;
 #ifdef AZ_DIAG
     if (C % PP_NCOL == 0) ok &= (n->wp3 = n->dalloc<uint16_t>(9 * (size_t)C * C)) != nullptr;
 #endif
@@ -1990,6 +2090,23 @@ bool convnet_set_params(ConvNet* net, const float* p, int64_t count) {
                 }
             ok &= hipMemcpy(net->wr[l], wr.data(), wr.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
         }
+        if (l == 1 && net->wf3) {   // conv3: the same bf16 values in MFMA fragment order (conv_valid_tile<.., WREG>): K-steps in the kernel's order
+            std::vector<uint16_t> wf((size_t)9 * C * C);
+            const int nk = C / 64 * 9;
+            for (int g = 0; g < C / 64; ++g)
+                for (int kt = 0; kt < nk; ++kt) {
+                    const int cb = kt / 9, tap = kt - cb * 9;
+                    uint16_t* st = &wf[((size_t)g * nk + kt) * WF3_STEP];
+                    for (int j = 0; j < 4; ++j)
+                        for (int ks = 0; ks < 2; ++ks)
+                            for (int ln = 0; ln < 64; ++ln) {
+                                const int frow = ln & 15, fq = ln >> 4;
+                                std::memcpy(st + ((j * 2 + ks) * 64 + ln) * 8,
+                                            &w[(size_t)(g * 64 + j * 16 + frow) * K[1] + (size_t)tap * C + cb * 64 + ks * 32 + fq * 8], 16);
+                            }
+                }
+            ok &= hipMemcpy(net->wf3, wf.data(), wf.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+        }
 #ifdef AZ_DIAG
         if (l == 1 && net->wp3) {   // conv3: the same bf16 values as k_conv3_pp's stage images (stage = channel block, tap, k half)
             std::vector<uint16_t> wp((size_t)9 * C * C);
@@ -2091,7 +2208,7 @@ static void launch_conv2_gemm(const GemmDesc& d, int rows_hint, hipStream_t s) {
     const int t8 = (tiles + 7) / 8 * 8;
     hipLaunchKernelGGL((k_conv_same_pipe<1, TABLE>), dim3(t8 * (d.N / HBN2_)), dim3(256), 0, s, d);
 }
-static void launch_conv3_image(const GemmDesc& d, int rows_hint, hipStream_t s, bool tail, bool planes, int pp) {
+static void launch_conv3_image(const GemmDesc& d, int rows_hint, hipStream_t s, bool tail, bool planes, int pp, bool wreg) {
 #ifdef AZ_DIAG
     if (pp && d.Wp && d.N % PP_NCOL == 0) {
         const int t8 = ((rows_hint + PP_NB - 1) / PP_NB + 7) / 8 * 8;
@@ -2126,7 +2243,10 @@ static void launch_conv3_image(const GemmDesc& d, int rows_hint, hipStream_t s, 
     const int tiles = (rows_hint + C3_NB - 1) / C3_NB;
     const int t8 = (tiles + 7) / 8 * 8;
     const int full_grid = t8 * (d.N / 128);
-    if (planes) hipLaunchKernelGGL((k_conv3_auto<2, true>), dim3(full_grid + (tail ? C3_TAIL : 0)), dim3(256), 0, s, d, full_grid, tail ? C3_TAIL : 0);
+    // the register-fed weight operand needs the fragment-ordered copy and the PLANES image (64 KiB: the epilogue's tile fits it)
+    if (wreg && planes && d.Wf)
+        hipLaunchKernelGGL((k_conv3_auto_wreg<2>), dim3(full_grid + (tail ? C3_TAIL : 0)), dim3(256), 0, s, d, full_grid, tail ? C3_TAIL : 0);
+    else if (planes) hipLaunchKernelGGL((k_conv3_auto<2, true>), dim3(full_grid + (tail ? C3_TAIL : 0)), dim3(256), 0, s, d, full_grid, tail ? C3_TAIL : 0);
     else if (tail) hipLaunchKernelGGL((k_conv3_auto<2, false>), dim3(full_grid + C3_TAIL), dim3(256), 0, s, d, full_grid, C3_TAIL);
     else hipLaunchKernelGGL((k_conv_valid_pipe<2, C3_NB, 6, 7, false, 0, true>), dim3(full_grid), dim3(256), 0, s, d);
 }
@@ -2202,6 +2322,7 @@ static bool launch_gemm_diag(const GemmDesc& d, int rows_hint, int rows_typ, hip
             case 13: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 3, true>), g3, b3, 0, s, d); break;
             case 14: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 4, true>), g3, b3, 0, s, d); break;
             case 15: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 5, true>), g3, b3, 0, s, d); break;
+            case 16: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 6, true>), g3, b3, 0, s, d); break;
             default: hipLaunchKernelGGL((k_conv_valid_img2<LAYER, C3_NB, 6, 7, 2>), g3, b3, 0, s, d); break;
         }
         return true;
@@ -2302,7 +2423,7 @@ static void launch_gemm(const GemmDesc& d, int rows_hint, int rows_typ, hipStrea
     }
     if constexpr (LAYER == 2) {
         if (o.conv3_small && conv3_is_small(d2, rows_hint, rows_typ)) launch_ring_auto<LAYER>(d2, rows_hint, rows_typ, s, true);
-        else launch_conv3_image(d2, rows_hint, s, o.conv3_tail != 0, o.conv3_planes != 0, o.conv3_pp);
+        else launch_conv3_image(d2, rows_hint, s, o.conv3_tail != 0, o.conv3_planes != 0, o.conv3_pp, o.conv3_wreg != 0);
         return;
     }
 
@@ -2367,6 +2488,12 @@ bool netws_read_clock_stamps(NetWorkspace* n, unsigned long long* out2048) {
     return n && hipMemcpy(out2048, n->dbg, 2048 * 8, hipMemcpyDeviceToHost) == hipSuccess;
 }
 
+long long netws_read_conv3_out(NetWorkspace* n, int rows, void* out) {
+    if (!n || rows <= 0 || rows > n->max_batch) return -1;
+    const size_t bytes = (size_t)rows * 20 * n->C * sizeof(uint16_t);
+    return hipMemcpy(out, n->act3, bytes, hipMemcpyDeviceToHost) == hipSuccess ? (long long)bytes : -1;
+}
+
 void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows_hint, int rows_typ, hipStream_t s, NetProfile* prof,
                      const NetOptions& o) {
     const int C = n->C;
@@ -2428,8 +2555,10 @@ void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows
     d.rows_per_sample = 20; d.out_w = 5; d.in_h = 6; d.in_w = 7;
     d.Wr = o.ring_packed ? n->wr[1] : nullptr;
     d.Wp = n->wp3;
+    d.Wf = n->wf3;
     launch_gemm<2>(d, rows_hint, rows_typ, s, o);
     d.Wp = nullptr;
+    d.Wf = nullptr;
     if (timed) (void)hipEventRecord(rec.e2b, s);
     // conv4: 3x3 valid [4][5][C] -> [2][3][C]
     d.A = ws->act3; d.W = n->wg[2]; d.bias = n->bg[2]; d.out = ws->act4;
