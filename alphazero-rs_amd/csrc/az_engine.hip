@@ -430,6 +430,14 @@ void net_forward(az_engine* e, const NetModel& net, const EvalBatch& eb, int row
     }
 }
 
+// "net_fp8": the model's fp8 weight copies and scales follow its parameters -- built when the option is switched on and at every upload
+// while it is on, never by a forward (which may run inside a stream capture)
+az_status fp8_sync_model(az_engine* e, NetModel& m) {
+    if (!e->netopt.net_fp8 || m.kind != AZ_NET_CONV || !m.conv) return AZ_OK;
+    if (!convnet_build_fp8(m.conv, workspace_for(e, e->stream), e->stream)) return fail(e, AZ_ERR_HIP, "net_fp8: building the model's fp8 copies failed");
+    return AZ_OK;
+}
+
 bool dedup_applies(const az_engine* e, const NetModel& net) {
     return e->eval_dedup == 2 || (e->eval_dedup == 1 && net.kind == AZ_NET_CONV);
 }
@@ -903,7 +911,29 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     if (!e || !key) return AZ_ERR_BAD_ARGUMENT;
     auto is = [&](const char* k) { return std::strcmp(key, k) == 0; };
     // ---- options of the shipped library: every one of them lives in THIS engine ----
-    if (is("conv2_table") && (value == 0 || value == 1)) { e->netopt.conv2_table = (int)value; return AZ_OK; }
+    if (is("conv2_table") && (value == 0 || value == 1)) {
+        if (value == 0 && e->netopt.net_fp8) return fail(e, AZ_ERR_BAD_ARGUMENT, "conv2_table = 0 is not available while net_fp8 is 1 (the fp8 class takes conv2 from the table kernel)");
+        e->netopt.conv2_table = (int)value;
+        return AZ_OK;
+    }
+    if (is("net_fp8") && (value == 0 || value == 1)) {
+        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "net_fp8 cannot change while a self-play session is open");
+        if (value == 1 && e->netopt.conv2_table != 1) return fail(e, AZ_ERR_BAD_ARGUMENT, "net_fp8 needs conv2_table = 1");
+        if ((int)value == e->netopt.net_fp8) return AZ_OK;
+        try {
+            HIPCHK(hipSetDevice(e->device));
+            e->netopt.net_fp8 = (int)value;
+            for (auto& kv : e->nets) {
+                NetModel& m = kv.second;
+                if (m.kind != AZ_NET_CONV) continue;
+                const az_status st = fp8_sync_model(e, m);
+                if (st) { e->netopt.net_fp8 = 0; return st; }
+                m.cache_tag = 0;                                  // the other class's cached rows and captured graphs are never used again
+                m.generation = ++g_model_generation;
+            }
+            return AZ_OK;
+        } catch (const HipFail& f) { e->netopt.net_fp8 = 0; return fail_hip(e, f); }
+    }
     if (is("conv3_small") && (value == 0 || value == 1)) { e->netopt.conv3_small = (int)value; return AZ_OK; }
     if (is("conv3_tail") && (value == 0 || value == 1)) { e->netopt.conv3_tail = (int)value; return AZ_OK; }
     if (is("ring_packed") && (value == 0 || value == 1)) { e->netopt.ring_packed = (int)value; return AZ_OK; }
@@ -1120,7 +1150,7 @@ az_status az_net_init_random(az_engine* e, int32_t model_id, uint64_t seed) {
         m->kind = AZ_NET_CONV;
         m->cache_tag = 0;
         m->generation = ++g_model_generation;
-        return AZ_OK;
+        return fp8_sync_model(e, *m);
     } catch (const HipFail& f) { return fail_hip(e, f); }
 }
 
@@ -1138,7 +1168,7 @@ az_status az_net_set_params(az_engine* e, int32_t model_id, const float* params,
         m->kind = AZ_NET_CONV;
         m->cache_tag = 0;
         m->generation = ++g_model_generation;
-        return AZ_OK;
+        return fp8_sync_model(e, *m);
     } catch (const HipFail& f) { return fail_hip(e, f); }
 }
 
@@ -2404,6 +2434,20 @@ az_status az_gather_samples(az_engine* e, const az_samples* local, int32_t dst_r
 long long az_diag_read_conv3_out(az_engine* e, int rows, void* out) {
     if (!e || !out || rows <= 0 || hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;
     return netws_read_conv3_out(e->ws[0], rows, out);
+}
+// Diagnostic library only: the same for a "net_fp8" engine -- `rows` boards of [4][5][C] e4m3 codes; and a model's (sa2, sa3)
+long long az_diag_read_conv3_out_fp8(az_engine* e, int rows, void* out) {
+    if (!e || !out || rows <= 0 || hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;
+    return netws_read_conv3_out_fp8(e->ws[0], rows, out);
+}
+long long az_diag_read_conv2_out_fp8(az_engine* e, int rows, void* out) {        // conv2's: `rows` boards of [6][7][C] e4m3 codes
+    if (!e || !out || rows <= 0 || hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;
+    return netws_read_conv2_out_fp8(e->ws[0], rows, out);
+}
+int az_diag_fp8_scales(az_engine* e, int32_t model_id, float* out2) {
+    if (!e || !out2) return -1;
+    auto it = e->nets.find(model_id);
+    return it != e->nets.end() && it->second.conv && convnet_fp8_scales(it->second.conv, out2) ? 0 : -1;
 }
 // Diagnostic library only (not part of the ABI): the children of the node reached from tree g's current root by following `path`
 // (child indices, not actions).  out rows of 8 u64: slot, a, ctr (resolved through a link), prior bits, link, meta, own ctr, key.

@@ -11,6 +11,7 @@
 // 64 input channels of one filter tap is one contiguous 128-byte row segment; conv1 (K = 18) reads the
 // bitboards directly (to_features fused, connect_four_game.rs:219-237) on the VALU.
 #include "az_net.h"
+#include "az_fp8.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,6 +24,8 @@ constexpr int ACTIONS = ConnectFour::ACTIONS;      // the net is Connect Four's 
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 // ---- fixtures ------------------------------------------------------------------------------------
 // DumbConnectFourNnet (examples/connect_four.rs:34-41, S9): pi = 1/width, v = +1; or the hash fixture.
@@ -58,6 +61,15 @@ static inline uint16_t f32_to_bf16_host(float f) {
 AZ_D uint32_t pack_bf16x2(float lo, float hi) {
     __bf16 a = (__bf16)lo, b = (__bf16)hi;       // v_cvt_pk_bf16_f32 (round to nearest even)
     return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
+}
+
+// four f32 -> four e4m3fn codes ("net_fp8"): x * scale (a power of two), clamped to +-448 so that nothing converts to NaN, then
+// v_cvt_pk_fp8_f32 (round to nearest even; OCP codes on gfx950)
+AZ_D uint32_t pack_fp8x4(float a, float b, float c, float d, float scale) {
+    auto q = [&](float x) { return fminf(fmaxf(x * scale, -FP8_MAX), FP8_MAX); };
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(q(a), q(b), 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(q(c), q(d), w, true);
+    return (uint32_t)w;
 }
 
 AZ_D uint32_t pack_f16x2(float lo, float hi) {
@@ -195,9 +207,9 @@ __global__ __launch_bounds__(64) void k_conv1_table(const float* __restrict__ w 
 // (a stone never floats over an empty cell: ~4000 of the 19683 patterns) are ~4.6 MB, about one L2.  One wave per (board, slice):
 // lanes 0..41 compute the board's 42 patterns once, then six passes of one board row each, lane = (x, 16-byte chunk); the nine
 // neighbour patterns come from the owning lanes by ds_bpermute.  Same per-channel summation order as k_conv2_table: bit-identical.
-__global__ __launch_bounds__(256, 4) void k_conv2_table_x(const EvalBatch eb, const uint16_t* __restrict__ U /*[19683 + 1][9][C] f16, last row 0*/,
-                                                       const float* __restrict__ bias /*[C]*/, uint16_t* __restrict__ out /*[n][42][C] bf16*/,
-                                                       int C) {
+template <bool F8>   // F8 ("net_fp8"): the same gather and sums, the row stored as e4m3 codes of relu(acc + b) * sa2 into [n][42][C] BYTES
+__device__ __forceinline__ void conv2_table_x_body(const EvalBatch& eb, const uint16_t* __restrict__ U, const float* __restrict__ bias,
+                                                   uint16_t* __restrict__ out, int C, float sa2) {
     const int nsl = C / 64;                                   // channel slices (8 at C = 512: one per XCD)
     const int slice = blockIdx.x % nsl;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -238,7 +250,14 @@ __global__ __launch_bounds__(256, 4) void k_conv2_table_x(const EvalBatch eb, co
                     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(acc[2 * i + 1]) : "v"(w[i]), "s"(one));
                 }
             }
-            if (lane < 56) {
+            if constexpr (F8) {
+                if (lane < 56) {
+                    uint2 o;
+                    o.x = pack_fp8x4(fmaxf(acc[0] + b0.x, 0.f), fmaxf(acc[1] + b0.y, 0.f), fmaxf(acc[2] + b0.z, 0.f), fmaxf(acc[3] + b0.w, 0.f), sa2);
+                    o.y = pack_fp8x4(fmaxf(acc[4] + b1.x, 0.f), fmaxf(acc[5] + b1.y, 0.f), fmaxf(acc[6] + b1.z, 0.f), fmaxf(acc[7] + b1.w, 0.f), sa2);
+                    *(uint2*)((unsigned char*)out + ((size_t)b * 42 + (size_t)(y * 7 + x)) * C + coff) = o;
+                }
+            } else if (lane < 56) {
                 uint4 o;
                 o.x = pack_bf16x2(fmaxf(acc[0] + b0.x, 0.f), fmaxf(acc[1] + b0.y, 0.f));
                 o.y = pack_bf16x2(fmaxf(acc[2] + b0.z, 0.f), fmaxf(acc[3] + b0.w, 0.f));
@@ -248,6 +267,15 @@ __global__ __launch_bounds__(256, 4) void k_conv2_table_x(const EvalBatch eb, co
             }
         }
     }
+}
+__global__ __launch_bounds__(256, 4) void k_conv2_table_x(const EvalBatch eb, const uint16_t* __restrict__ U /*[19683 + 1][9][C] f16, last row 0*/,
+                                                       const float* __restrict__ bias /*[C]*/, uint16_t* __restrict__ out /*[n][42][C] bf16*/,
+                                                       int C) {
+    conv2_table_x_body<false>(eb, U, bias, out, C, 1.0f);
+}
+__global__ __launch_bounds__(256, 4) void k_conv2_table_x8(const EvalBatch eb, const uint16_t* __restrict__ U, const float* __restrict__ bias,
+                                                        uint16_t* __restrict__ out /*[n][42][C] e4m3*/, int C, float sa2) {
+    conv2_table_x_body<true>(eb, U, bias, out, C, sa2);
 }
 
 // ---- implicit GEMM on MFMA: out[M,N] = relu(A_gather[M,K] * W[N,K]^T + bias) ---------------------------
@@ -282,6 +310,8 @@ struct GemmDesc {
     const uint16_t* Wr;        // gemm_ring_body: the layer's weights as the ring's LDS stage images [N / 128][K / 64][128 rows][128 B] in K-step order
                                // (ConvNet::wr: one stage = 16 KiB of CONSECUTIVE global bytes instead of 128 rows K * 2 bytes apart), nullptr = read W
     const uint16_t* Wf;        // conv_valid_tile<.., WREG>: conv3's weights in MFMA fragment order (ConvNet::wf3), nullptr = not available
+    const float* dq;           // gemm_ring_body<.., F8>: per output channel 1 / (sw[n] * sa_in), the power of two that undoes both operand scales
+    float out_scale;           // gemm_ring_body<.., 1>: the scale of the e4m3 output tensor (sa3)
 };
 
 constexpr int GBM = 128, GBN = 128, GBK = 64;
@@ -418,9 +448,15 @@ __device__ __forceinline__ void lds_dma16(const void* sbase /*uniform*/, uint32_
 // BM = 64 .. 192 rows per tile (k_gemm_ring_auto picks it on the device): a CU fetches its tiles L2 -> LDS at a bounded rate
 // (~19-27 B/clk) whatever else it does, so idle CUs are idle fetch bandwidth and a second, nearly empty round of workgroups is a
 // whole round of time -- the tile is the smallest whose grid still fits whole rounds of workgroup slots.
-template <int NS, int BM>
+// F8 ("net_fp8", conv3 and conv4 only): both operands are e4m3 bytes, so the same 128-byte row segment is one tap x 128 channels and
+// a K-step is ONE v_mfma_f32_16x16x128_f8f6f4 per accumulator (a lane's 32 bytes = the 16-byte chunks fq and 4 + fq the two bf16
+// MFMAs of a step read): same stages, same DMA maps, same LDS addresses, half the K-steps.  The weights always come from the packed
+// copy (ConvNet::w8, az_fp8.h); the epilogue is acc * dq[n] + bias, ReLU, then F8 == 1: * out_scale -> e4m3 (conv3), F8 == 2: bf16 (conv4).
+template <int NS, int BM, int F8 = 0>
 __device__ __forceinline__ void gemm_ring_body(const GemmDesc& d, unsigned char* smem /*NS * (BM * 128 + 16384) bytes of LDS*/, const int M) {
     static_assert(BM % 32 == 0 && BM >= 64 && BM <= 192 && NS * (BM * 128 + 16384) <= 163840 && 2 * (BM / 32 + 4) <= 63, "tile");
+    constexpr int ES = F8 ? 1 : 2;                    // bytes per operand element
+    constexpr int KB = 128 / ES;                      // channels of a K-step: one 128-byte row segment
     constexpr int MT = BM / 32;                       // 16-row tiles per wave (2 x 2 waves) = A pieces per wave
     constexpr int STAGE = BM * 128 + 16384;           // [A BM x 128 B | W 128 x 128 B]
     constexpr int NDMA = MT + 4;                      // DMA instructions per wave per stage
@@ -444,13 +480,13 @@ __device__ __forceinline__ void gemm_ring_body(const GemmDesc& d, unsigned char*
         m = m < M ? m : M - 1;
         const int b = m / d.rows_per_sample, r = m - b * d.rows_per_sample;
         const int y = r / d.out_w, x = r - y * d.out_w;
-        a_ob[q] = (uint32_t)(((b * d.in_h + y) * d.in_w + x) * d.in_c + chunk * 8) * 2u;
+        a_ob[q] = (uint32_t)(((b * d.in_h + y) * d.in_w + x) * d.in_c + chunk * (16 / ES)) * (uint32_t)ES;
     }
-    const bool packed = d.Wr != nullptr;
+    const bool packed = F8 || d.Wr != nullptr;
     const uint32_t b_ob = packed ? (uint32_t)(wave * 1024 + lane * 16)
                                  : (uint32_t)((n0 + wave * 8 + lrow) * d.K + chunk * 8) * 2u;      // W piece q: + q * w_stride on the SGPR base
     const size_t w_stride = packed ? (size_t)4096 : (size_t)64 * d.K;
-    const char* wr_tile = (const char*)d.Wr + (size_t)ntile * (size_t)(d.K / GBK) * 16384;
+    const char* wr_tile = (const char*)d.Wr + (size_t)ntile * (size_t)(d.K / KB) * 16384;
     int ks_idx = 0;
     typedef __attribute__((address_space(3))) void* lds_ptr;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr)(smem + wave * 1024);
@@ -459,7 +495,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmDesc& d, unsigned char*
     uint32_t ks_c0 = 0, ks_toff = 0, ks_kk = 0;
 #define AZ_RDMA(buf_)                                                                                   \
     {                                                                                                   \
-        const char* abase = (const char*)(d.A + ks_toff);                                               \
+        const char* abase = (const char*)d.A + (size_t)ks_toff * ES;                                    \
         const char* wbase = packed ? wr_tile + (size_t)ks_idx * 16384 : (const char*)(d.W + ks_kk);     \
         ++ks_idx;                                                                                       \
         const uint32_t la = lds0 + (buf_) * STAGE;                                                      \
@@ -467,14 +503,14 @@ __device__ __forceinline__ void gemm_ring_body(const GemmDesc& d, unsigned char*
         _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) lds_dma16(wbase + q_ * w_stride, b_ob, la + BM * 128 + q_ * 4096); \
         ++ks_tap; ++ks_kx; ks_toff += (uint32_t)d.in_c; ks_kk += (uint32_t)d.cin;                       \
         if (ks_kx == d.tap_w) { ks_kx = 0; ks_toff += (uint32_t)((d.in_w - d.tap_w) * d.in_c); }        \
-        if (ks_tap == ntaps) { ks_tap = 0; ks_kx = 0; ks_c0 += GBK; ks_toff = ks_c0; ks_kk = ks_c0; }   \
+        if (ks_tap == ntaps) { ks_tap = 0; ks_kx = 0; ks_c0 += KB; ks_toff = ks_c0; ks_kk = ks_c0; }    \
     }
     f32x4 acc[MT][4];
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int jn = 0; jn < 4; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int nk = d.K / GBK;
+    const int nk = d.K / KB;
     const int frow = lane & 15, fq = lane >> 4, fsw = lane & 7;
 #pragma unroll
     for (int st = 0; st < NS - 1; ++st)
@@ -492,6 +528,27 @@ __device__ __forceinline__ void gemm_ring_body(const GemmDesc& d, unsigned char*
         const unsigned char* sB = sA + BM * 128;
         // both 32-deep halves' fragments are requested up front: the second half's reads sit between the first half's MFMAs
         const int coff0 = ((0 + fq) ^ fsw) << 4, coff1 = ((4 + fq) ^ fsw) << 4;
+        if constexpr (F8) {
+            i32x8 fa[MT], fb[4];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const unsigned char* row = sB + (wc * 64 + nt * 16 + frow) * 128;
+                fb[nt] = __builtin_shufflevector(*(const i32x4*)(row + coff0), *(const i32x4*)(row + coff1), 0, 1, 2, 3, 4, 5, 6, 7);
+            }
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const unsigned char* row = sA + (wr * (BM / 2) + mt * 16 + frow) * 128;
+                fa[mt] = __builtin_shufflevector(*(const i32x4*)(row + coff0), *(const i32x4*)(row + coff1), 0, 1, 2, 3, 4, 5, 6, 7);
+            }
+            // formats 0 / 0 = e4m3 x e4m3, no block scales: the compiler selects the unscaled v_mfma_f32_16x16x128_f8f6f4
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[nt], fa[mt], acc[mt][nt], 0, 0, 0, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            continue;                                    // the bf16 step below is not part of an F8 instantiation's loop
+        }
         bf16x8 fa0[MT], fb0[4], fa1[MT], fb1[4];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) fa0[mt] = *(const bf16x8*)(sA + (wr * (BM / 2) + mt * 16 + frow) * 128 + coff0);
@@ -522,8 +579,10 @@ __device__ __forceinline__ void gemm_ring_body(const GemmDesc& d, unsigned char*
     }
 #undef AZ_RDMA
     // epilogue through LDS (the ring is dead): + bias, ReLU, bf16 as [BM rows][128 channels] with a 272-byte row stride, then whole
-    // 256-byte row segments, 16 bytes per lane (instead of 8-byte stores in 32-byte pieces of 16 different rows)
-    constexpr int EP_STRIDE = 272;
+    // 256-byte row segments, 16 bytes per lane (instead of 8-byte stores in 32-byte pieces of 16 different rows).  F8: the accumulator
+    // first loses both operand scales (dq[n], an exact power of two); F8 == 1 stores e4m3 codes of the result * out_scale, 144-byte rows
+    constexpr bool OUT8 = F8 == 1;
+    constexpr int EP_STRIDE = OUT8 ? 144 : 272;
     static_assert(BM * EP_STRIDE <= NS * STAGE, "the output tile must fit the ring");
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_s_barrier();
@@ -531,26 +590,34 @@ __device__ __forceinline__ void gemm_ring_body(const GemmDesc& d, unsigned char*
     for (int nt = 0; nt < 4; ++nt) {
         const int nl = wc * 64 + nt * 16 + fq * 4;
         const float4 bv = *(const float4*)(d.bias + n0 + nl);
+        float4 qv = make_float4(1.f, 1.f, 1.f, 1.f);
+        if constexpr (F8 != 0) qv = *(const float4*)(d.dq + n0 + nl);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int ml = wr * (BM / 2) + mt * 16 + frow;
-            float r0 = acc[mt][nt][0] + bv.x, r1 = acc[mt][nt][1] + bv.y, r2 = acc[mt][nt][2] + bv.z,
-                  r3 = acc[mt][nt][3] + bv.w;
+            float r0 = acc[mt][nt][0], r1 = acc[mt][nt][1], r2 = acc[mt][nt][2], r3 = acc[mt][nt][3];
+            if constexpr (F8 != 0) { r0 *= qv.x; r1 *= qv.y; r2 *= qv.z; r3 *= qv.w; }
+            r0 += bv.x; r1 += bv.y; r2 += bv.z; r3 += bv.w;
             if (d.relu) { r0 = fmaxf(r0, 0.f); r1 = fmaxf(r1, 0.f); r2 = fmaxf(r2, 0.f); r3 = fmaxf(r3, 0.f); }
-            uint2 o;
-            o.x = pack_bf16x2(r0, r1);
-            o.y = pack_bf16x2(r2, r3);
-            *(uint2*)(smem + ml * EP_STRIDE + nl * 2) = o;
+            if constexpr (OUT8) {
+                *(uint32_t*)(smem + ml * EP_STRIDE + nl) = pack_fp8x4(r0, r1, r2, r3, d.out_scale);
+            } else {
+                uint2 o;
+                o.x = pack_bf16x2(r0, r1);
+                o.y = pack_bf16x2(r2, r3);
+                *(uint2*)(smem + ml * EP_STRIDE + nl * 2) = o;
+            }
         }
     }
     __syncthreads();
+    constexpr int ROW16 = OUT8 ? 8 : 16;              // 16-byte pieces of a tile row
 #pragma unroll
-    for (int it = 0; it < BM * 16 / 256; ++it) {
+    for (int it = 0; it < BM * ROW16 / 256; ++it) {
         const int idx = it * 256 + tid;
-        const int ml = idx >> 4, c = idx & 15;
+        const int ml = idx / ROW16, c = idx % ROW16;
         const int m = m0 + ml;
         if (m >= M) continue;
-        *(uint4*)(d.out + (size_t)m * d.N + n0 + c * 8) = *(const uint4*)(smem + ml * EP_STRIDE + c * 16);
+        *(uint4*)((unsigned char*)d.out + ((size_t)m * d.N + n0) * (OUT8 ? 1 : 2) + c * 16) = *(const uint4*)(smem + ml * EP_STRIDE + c * 16);
     }
 }
 
@@ -590,6 +657,26 @@ __global__ __launch_bounds__(256, (NS <= 2 ? 2 : 1)) void k_gemm_ring_auto(const
         if (bm == 64) gemm_ring_body<4, 64>(d, smem, M);
         else if (bm == 96) gemm_ring_body<4, 96>(d, smem, M);
         else gemm_ring_body<4, 128>(d, smem, M);
+    }
+}
+
+// "net_fp8": conv3 (F8 = 1, e4m3 -> e4m3) and conv4 (F8 = 2, e4m3 -> bf16) on the ring at EVERY batch size -- one kernel family per layer,
+// the tile picked on the device as above; a row's K order does not depend on the tile, so every tile gives the same bits.
+template <int LAYER, int NS, int F8>
+__global__ __launch_bounds__(256, (NS <= 2 ? 2 : 1)) void k_gemm_ring_f8(const GemmDesc d) {
+    constexpr int BMAX = NS == 2 ? 192 : 128;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[NS * (BMAX * 128 + 16384)];
+    const int M = (int)(*d.n_dev) * d.rows_per_sample;
+    const int bm = __builtin_amdgcn_readfirstlane(ring_pick_bm(M, d.N / GBN, NS, true));
+    if constexpr (NS == 2) {
+        if (bm == 96) gemm_ring_body<2, 96, F8>(d, smem, M);
+        else if (bm == 160) gemm_ring_body<2, 160, F8>(d, smem, M);
+        else if (bm == 192) gemm_ring_body<2, 192, F8>(d, smem, M);
+        else gemm_ring_body<2, 128, F8>(d, smem, M);
+    } else {
+        if (bm == 64) gemm_ring_body<4, 64, F8>(d, smem, M);
+        else if (bm == 96) gemm_ring_body<4, 96, F8>(d, smem, M);
+        else gemm_ring_body<4, 128, F8>(d, smem, M);
     }
 }
 
@@ -1857,6 +1944,12 @@ struct ConvNet {                      // the WEIGHTS of one model id (21 MB bf16
                                                        // + WF3_PAD K-steps of padding
     float* bg[5] = {nullptr};                          // folded bias f32 [N]
     float *wh = nullptr, *bh = nullptr;              // heads f32 [8][512], [8]
+    // "net_fp8" (built by convnet_build_fp8, never by a forward): conv3's and conv4's folded f32 weights as e4m3 codes of w' * sw[n] in
+    // the ring's stage-image order (az_fp8.h), the per-channel factors 1 / (sw[n] * sa_in) and the two activation scales
+    unsigned char* w8[2] = {nullptr, nullptr};
+    float* dq8[2] = {nullptr, nullptr};
+    float sa2 = 0.f, sa3 = 0.f;
+    bool fp8_ready = false;                            // the copies belong to the current parameters
     template <class T> T* dalloc(size_t n) {
         void* p = nullptr;
         if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr;
@@ -2046,6 +2139,7 @@ bool convnet_set_params(ConvNet* net, const float* p, int64_t count) {
     const Layout L(net->C);
     if (count != L.total) return false;
     net->params.assign(p, p + count);
+    net->fp8_ready = false;
     const int C = net->C;
     bool ok = true;
     {   // conv1: f32 [18][C], k = (ky*3+kx)*2 + ci
@@ -2254,7 +2348,7 @@ static void launch_conv3_image(const GemmDesc& d, int rows_hint, hipStream_t s, 
 // The LDS-DMA ring with the tile rows picked on the device.  The host picks the FAMILY from its estimate (NS = 4: one workgroup per CU,
 // for grids of at most 256 tiles; the estimate + 15 %: a batch over the limit would pay a whole second round), the kernel picks the
 // tile rows from the exact count (measured: tools/ring_tiles.py, profiles/README.md).
-template <int LAYER>
+template <int LAYER, int F8 = 0>      // F8: the "net_fp8" kernels of conv3 (1) / conv4 (2), same family rule
 static void launch_ring_auto(const GemmDesc& d, int rows_hint, int rows_typ, hipStream_t s, bool force_one_per_cu = false) {
     const int m_est = (int)((rows_typ > 0 ? (long long)rows_typ * 115 / 100 : (long long)rows_hint) * d.rows_per_sample), ncol = d.N / GBN;
     const bool conv = d.tap_w > 1;
@@ -2264,7 +2358,10 @@ static void launch_ring_auto(const GemmDesc& d, int rows_hint, int rows_typ, hip
     auto launch = [&](bool one_per_cu, const GemmDesc& dd, int m_cover) {
         const int bmin = one_per_cu ? 64 : 96;                               // the grid covers the smallest tile of the family
         const int mtb = ((m_cover + bmin - 1) / bmin + 7) / 8 * 8;
-        if (one_per_cu) hipLaunchKernelGGL((k_gemm_ring_auto<LAYER, 4>), dim3(mtb * ncol), dim3(256), 0, s, dd);
+        if constexpr (F8 != 0) {
+            if (one_per_cu) hipLaunchKernelGGL((k_gemm_ring_f8<LAYER, 4, F8>), dim3(mtb * ncol), dim3(256), 0, s, dd);
+            else hipLaunchKernelGGL((k_gemm_ring_f8<LAYER, 2, F8>), dim3(mtb * ncol), dim3(256), 0, s, dd);
+        } else if (one_per_cu) hipLaunchKernelGGL((k_gemm_ring_auto<LAYER, 4>), dim3(mtb * ncol), dim3(256), 0, s, dd);
         else hipLaunchKernelGGL((k_gemm_ring_auto<LAYER, 2>), dim3(mtb * ncol), dim3(256), 0, s, dd);
     };
     // The estimate (the previous move's largest batch) cannot tell the families apart near the line: a batch just under it on the two-per-CU
@@ -2494,11 +2591,153 @@ long long netws_read_conv3_out(NetWorkspace* n, int rows, void* out) {
     return hipMemcpy(out, n->act3, bytes, hipMemcpyDeviceToHost) == hipSuccess ? (long long)bytes : -1;
 }
 
+long long netws_read_conv3_out_fp8(NetWorkspace* n, int rows, void* out) {
+    if (!n || rows <= 0 || rows > n->max_batch) return -1;
+    const size_t bytes = (size_t)rows * 20 * n->C;
+    return hipMemcpy(out, n->act3, bytes, hipMemcpyDeviceToHost) == hipSuccess ? (long long)bytes : -1;
+}
+
+long long netws_read_conv2_out_fp8(NetWorkspace* n, int rows, void* out) {
+    if (!n || rows <= 0 || rows > n->max_batch) return -1;
+    const size_t bytes = (size_t)rows * 42 * n->C;
+    return hipMemcpy(out, n->act2, bytes, hipMemcpyDeviceToHost) == hipSuccess ? (long long)bytes : -1;
+}
+
+bool convnet_fp8_scales(const ConvNet* n, float out[2]) {
+    if (!n || !n->fp8_ready) return false;
+    out[0] = n->sa2; out[1] = n->sa3;
+    return true;
+}
+
+// ---- "net_fp8": calibration and the packed copies ---------------------------------------------------------------------------------------
+// max over a bf16 tensor of non-negative values (a ReLU output): the bit patterns order like the values
+__global__ __launch_bounds__(256) void k_amax_relu_bf16(const uint16_t* __restrict__ x, const uint32_t* __restrict__ n_dev, size_t per_row, uint32_t* out) {
+    const size_t n = (size_t)*n_dev * per_row / 8;
+    uint32_t m = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint4 v = ((const uint4*)x)[i];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { m = max(m, w[j] & 0xFFFFu); m = max(m, w[j] >> 16); }
+    }
+    atomicMax(out, m);
+}
+
+// The calibration set: FP8_CALIB_POSITIONS legal, unfinished positions, game g played with uniformly random legal moves to ply g % 42 (or
+// to the last position before the game ends), every draw from the counter RNG under a purpose of its own: a constant of the library.
+constexpr uint64_t RNG_FP8_CALIB = 5;
+static std::vector<ulonglong2> fp8_calibration_set() {
+    std::vector<ulonglong2> set((size_t)FP8_CALIB_POSITIONS);
+    for (int g = 0; g < FP8_CALIB_POSITIONS; ++g) {
+        ConnectFour::State st = ConnectFour::init();
+        for (int ply = 0; ply < g % 42; ++ply) {
+            const uint32_t valid = ConnectFour::valid_mask(st);
+            int acts[7], na = 0;
+            for (int a = 0; a < 7; ++a) if (valid >> a & 1u) acts[na++] = a;
+            if (na == 0) break;
+            const ConnectFour::State nx = ConnectFour::play(st, acts[rng_choose(rng_draw(FP8_CALIB_SEED, (uint64_t)g, (uint64_t)ply, RNG_FP8_CALIB), (uint32_t)na)]);
+            if (ConnectFour::ended_code(nx) != E_NONE) break;
+            st = nx;
+        }
+        set[(size_t)g] = st;
+    }
+    return set;
+}
+
+// amax of conv2's and conv3's outputs over the calibration set on the bf16 path (tables + the shipped conv3 kernels: every bf16 kernel
+// of a layer gives the same bits, so the result is a function of the weights alone), in chunks of at most the workspace's max_batch
+static bool fp8_calibrate(ConvNet* n, NetWorkspace* ws, hipStream_t s, float amax[2]) {
+    const std::vector<ulonglong2> set = fp8_calibration_set();
+    const int C = n->C, chunk = std::min(ws->max_batch, FP8_CALIB_POSITIONS);
+    ulonglong2* d_state = nullptr;
+    uint32_t* d_u = nullptr;                 // {n, amax2 bits, amax3 bits}
+    bool ok = hipMalloc((void**)&d_state, (size_t)chunk * sizeof(ulonglong2)) == hipSuccess && hipMalloc((void**)&d_u, 3 * sizeof(uint32_t)) == hipSuccess;
+    ok = ok && hipMemsetAsync(d_u, 0, 3 * sizeof(uint32_t), s) == hipSuccess;
+    const NetOptions o{};
+    for (int b0 = 0; ok && b0 < FP8_CALIB_POSITIONS; b0 += chunk) {
+        const uint32_t nb = (uint32_t)std::min(chunk, FP8_CALIB_POSITIONS - b0);
+        ok = ok && hipMemcpyAsync(d_u, &nb, sizeof nb, hipMemcpyHostToDevice, s) == hipSuccess;
+        ok = ok && hipMemcpyAsync(d_state, set.data() + b0, (size_t)nb * sizeof(ulonglong2), hipMemcpyHostToDevice, s) == hipSuccess;
+        if (!ok) break;
+        EvalBatch eb{};
+        eb.cap = chunk; eb.n = d_u; eb.state = d_state;
+        const size_t nsl = (size_t)C / 64;
+        const size_t blocks = std::min<size_t>(((size_t)nb + 3) / 4, 256) * nsl;
+        hipLaunchKernelGGL(k_conv2_table_x, dim3((unsigned)blocks), dim3(256), 0, s, eb, n->u2, n->bg[0], ws->act2, C);
+        hipLaunchKernelGGL(k_amax_relu_bf16, dim3(256), dim3(256), 0, s, ws->act2, d_u, (size_t)42 * C, d_u + 1);
+        GemmDesc d{};
+        d.n_dev = d_u; d.relu = 1; d.dbg = ws->dbg; d.c3tab = ws->c3tab; d.acct = ws->acct;
+        d.A = ws->act2; d.W = n->wg[1]; d.bias = n->bg[1]; d.out = ws->act3;
+        d.rows_per_sample = 20; d.out_w = 5; d.in_h = 6; d.in_w = 7; d.in_c = C; d.tap_w = 3; d.cin = C; d.K = 9 * C; d.N = C;
+        d.Wr = n->wr[1]; d.Wf = n->wf3;
+        launch_gemm<2>(d, (int)nb, (int)nb, s, o);
+        hipLaunchKernelGGL(k_amax_relu_bf16, dim3(256), dim3(256), 0, s, ws->act3, d_u, (size_t)20 * C, d_u + 2);
+        ok = hipStreamSynchronize(s) == hipSuccess;       // the next chunk overwrites the states
+    }
+    uint32_t h[3] = {0, 0, 0};
+    ok = ok && hipMemcpy(h, d_u, sizeof h, hipMemcpyDeviceToHost) == hipSuccess;
+    if (d_state) (void)hipFree(d_state);
+    if (d_u) (void)hipFree(d_u);
+    for (int i = 0; i < 2; ++i) {
+        const uint32_t bits = h[1 + i] << 16;
+        std::memcpy(&amax[i], &bits, 4);
+    }
+    return ok;
+}
+
+bool convnet_build_fp8(ConvNet* net, NetWorkspace* ws, hipStream_t s) {
+    if (!net || !ws || net->params.empty()) return false;
+    if (net->fp8_ready) return true;
+    const int C = net->C;
+    const Layout L(C);
+    const float* p = net->params.data();
+    for (int i = 0; i < 2; ++i) {
+        if (!net->w8[i]) net->w8[i] = net->dalloc<unsigned char>((size_t)9 * C * C);
+        if (!net->dq8[i]) net->dq8[i] = net->dalloc<float>((size_t)C);
+        if (!net->w8[i] || !net->dq8[i]) return false;
+    }
+    // conv3's k_conv3_auto counts its rows into the workspace's accounting: the calibration pass is not part of any call's statistics
+    unsigned long long acct[2] = {0, 0};
+    bool ok = hipStreamSynchronize(s) == hipSuccess && hipMemcpy(acct, ws->acct, sizeof acct, hipMemcpyDeviceToHost) == hipSuccess;
+    float amax[2] = {0.f, 0.f};
+    ok = ok && fp8_calibrate(net, ws, s, amax);
+    ok = ok && hipMemcpy(ws->acct, acct, sizeof acct, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) return false;
+    net->sa2 = fp8_act_scale(amax[0]);
+    net->sa3 = fp8_act_scale(amax[1]);
+    const float sa_in[2] = {net->sa2, net->sa3};
+    std::vector<float> wrow((size_t)9 * C), dq((size_t)C);
+    std::vector<unsigned char> w8((size_t)9 * C * C);
+    for (int i = 0; i < 2; ++i) {
+        const int l = 2 + i;                            // conv3, conv4 of the parameter layout
+        for (int nn = 0; nn < C; ++nn) {
+            float sc, sh;
+            fold_scale(p + L.conv_bn[l], C, nn, &sc, &sh);
+            float amax_w = 0.f;
+            for (int k = 0; k < 9 * C; ++k) {
+                wrow[(size_t)k] = p[L.conv_w[l] + (int64_t)k * C + nn] * sc;        // the fold of convnet_set_params, kept in f32
+                amax_w = std::max(amax_w, std::fabs(wrow[(size_t)k]));
+            }
+            const float sw = fp8_weight_scale(amax_w);
+            dq[(size_t)nn] = 1.0f / (sw * sa_in[i]);
+            for (int tap = 0; tap < 9; ++tap)
+                for (int c = 0; c < C; ++c)
+                    w8[(size_t)fp8_ring_offset(C, nn, tap, c)] = fp8_e4m3_from_f32(wrow[(size_t)tap * C + c] * sw);
+        }
+        ok &= hipMemcpy(net->w8[i], w8.data(), w8.size(), hipMemcpyHostToDevice) == hipSuccess;
+        ok &= hipMemcpy(net->dq8[i], dq.data(), dq.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    net->fp8_ready = ok;
+    return ok;
+}
+
 void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows_hint, int rows_typ, hipStream_t s, NetProfile* prof,
                      const NetOptions& o) {
     const int C = n->C;
     if (rows_hint > ws->max_batch) rows_hint = ws->max_batch;
     if (rows_hint <= 0) return;
+    const bool fp8 = o.net_fp8 != 0;
+    if (fp8 && !n->fp8_ready) return;          // the engine builds the copies with the option / at every upload: nothing to fall back to
     if (rows_typ <= 0 || rows_typ > rows_hint) rows_typ = rows_hint;
     NetWorkspace::Rec rec{};
     uint32_t* n_log = nullptr;
@@ -2543,7 +2782,8 @@ void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows
         {
             const size_t nsl = (size_t)C / 64;                                                  // one wave per (board, 64-channel slice)
             const size_t blocks = std::min<size_t>(((size_t)rows_hint + 3) / 4, 256) * nsl;
-            hipLaunchKernelGGL(k_conv2_table_x, dim3((unsigned)blocks), dim3(256), 0, s, eb, n->u2, n->bg[0], ws->act2, C);
+            if (fp8) hipLaunchKernelGGL(k_conv2_table_x8, dim3((unsigned)blocks), dim3(256), 0, s, eb, n->u2, n->bg[0], ws->act2, C, n->sa2);
+            else hipLaunchKernelGGL(k_conv2_table_x, dim3((unsigned)blocks), dim3(256), 0, s, eb, n->u2, n->bg[0], ws->act2, C);
         }
     } else {
         launch_gemm<1>(d, rows_hint, rows_typ, s, o);
@@ -2556,6 +2796,11 @@ void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows
     d.Wr = o.ring_packed ? n->wr[1] : nullptr;
     d.Wp = n->wp3;
     d.Wf = n->wf3;
+    if (fp8) {           // e4m3 act2 -> e4m3 act3 (the first half of the allocation), the ring at every batch size
+        GemmDesc d8 = d;
+        d8.Wr = (const uint16_t*)n->w8[0]; d8.dq = n->dq8[0]; d8.out_scale = n->sa3; d8.Wp = nullptr; d8.Wf = nullptr;
+        launch_ring_auto<2, 1>(d8, rows_hint, rows_typ, s);
+    } else
     launch_gemm<2>(d, rows_hint, rows_typ, s, o);
     d.Wp = nullptr;
     d.Wf = nullptr;
@@ -2564,6 +2809,11 @@ void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows
     d.A = ws->act3; d.W = n->wg[2]; d.bias = n->bg[2]; d.out = ws->act4;
     d.Wr = o.ring_packed ? n->wr[2] : nullptr;
     d.rows_per_sample = 6; d.out_w = 3; d.in_h = 4; d.in_w = 5;
+    if (fp8) {           // e4m3 act3 -> bf16 act4
+        GemmDesc d8 = d;
+        d8.Wr = (const uint16_t*)n->w8[1]; d8.dq = n->dq8[1];
+        launch_ring_auto<3, 2>(d8, rows_hint, rows_typ, s);
+    } else
     launch_gemm<3>(d, rows_hint, rows_typ, s, o);
     if (timed) (void)hipEventRecord(rec.e2c, s);
     // fc1: [6C] -> 1024

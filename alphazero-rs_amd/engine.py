@@ -287,6 +287,8 @@ class Engine:
         self._check(self._lib.az_net_train_end(self._h, model_id))
 
     def set_option(self, key, value):
+        """az_set_option on this engine (keys: include/az_engine.h), e.g. set_option("net_fp8", 1): conv3 and conv4 of this engine's
+        conv-net forwards on the FP8 (e4m3) matrix path -- a numerics class of its own, default off."""
         self._check(self._lib.az_set_option(self._h, key.encode(), int(value)))
 
     # ---- stats ----

@@ -157,6 +157,34 @@ const char* az_last_error(const az_engine* e);
  *                           copy of the model (16 KiB of consecutive bytes per stage); 0: from the [N][K] weights.  Bit-identical
  *            "narrow_rows"  n (default 32, 0 = off): batches of at most n boards (conv3; 2n for conv4, 4n for the FCs) run the
  *                           register-fed skinny GEMM; the hand-over is decided on the device from the exact row count.  Bit-identical
+ *            "net_fp8"      0 (default) / 1: conv3 and conv4 of every conv-net forward of this engine (search, self-play, arena,
+ *                           az_net_predict*, shared tree batches) on the FP8 matrix path.  A NUMERICS CLASS of its own, not
+ *                           bit-identical to bf16.  Nothing else changes: conv1 / conv2 stay table lookups, fc1 / fc2 / heads stay
+ *                           bf16 / f32, the trainer and the weights file are untouched.  The contract:
+ *                             format      OCP e4m3fn (not fnuz, not e5m2), round to nearest even, saturating at +-448
+ *                             weights     BatchNorm folded in f32 as for bf16; per output channel n the scale
+ *                                         sw[n] = 2^floor(log2(448 / max_k |w'[n][k]|)) (1 for an all-zero channel), q = e4m3(w' * sw[n])
+ *                             activations one power-of-two scale per tensor, sa2 (conv2's output) and sa3 (conv3's output):
+ *                                         s = 2^floor(log2(448 / (4 * amax))), amax = the tensor's maximum over the library's built-in
+ *                                         calibration set (1024 legal positions at all plies from the counter RNG, a constant of the
+ *                                         library) on the engine's own bf16 path, in chunks of at most max_batch -- a function of the
+ *                                         weights alone, the same on every engine, rank and run; values are clamped to +-448 before the
+ *                                         conversion, so a larger one saturates and never becomes NaN
+ *                             arithmetic  products of two e4m3 values are exact; f32 accumulation inside v_mfma_f32_16x16x128_f8f6f4,
+ *                                         K walked 128-channel block outer, tap inner; epilogue acc * (1 / (sw[n] * sa_in)) + bias[n]
+ *                                         (the factor is an exact power of two), ReLU; conv3 then * sa3 -> clamp -> e4m3, conv4 -> bf16
+ *                             invariants  a row's (pi, v) depends on its state alone (not on the batch size, its place in the batch or
+ *                                         the tile the device picked), so de-duplication and the cache stay bit-exact; "conv3_small",
+ *                                         "conv3_tail", "conv3_planes", "conv3_wreg", "narrow_rows" and "ring_packed" never change an fp8
+ *                                         result (an fp8 engine runs conv3 and conv4 on the LDS-DMA ring at every batch size)
+ *                           Measured error (torch emulation, random nets, 200 legal positions, C = 512): max |dpi| 6.1e-3, |dv| 2.6e-2
+ *                           against the textbook f32 net, ten times bf16's 5.9e-4 / 2.7e-3; insensitive to the activation scale (scales
+ *                           64 x smaller move the result by 5e-4 / 5e-3).  The fp8 copies and scales are built when the option is
+ *                           switched on and at every later weight upload (init, load, set_params, train end), never by a forward.
+ *                           Changing the value gives every conv model a new evaluation-cache tag and generation: a persistent cache never
+ *                           serves a row of the other class and no captured search graph of the other class is replayed.  Refused
+ *                           (AZ_ERR_BAD_ARGUMENT) while a self-play session is open and while "conv2_table" is 0; "conv2_table" = 0 is
+ *                           refused while "net_fp8" is 1
  *   search   "search_graph" n (default 20, even, 0 = off): n simulation steps per captured hipGraph replay (conv nets) ...
  *            "search_graph_rows" n (default 1024): ... for searches whose expected leaf batch has at most n rows (the arena, the drain
  *                           of a self-play call, single trees: there the host's launch calls set the pace; on big batches the kernels do)

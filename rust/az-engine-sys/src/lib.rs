@@ -53,6 +53,8 @@ extern "C" {
     pub fn az_create(cfg: *const az_config, out: *mut *mut az_engine) -> c_int;
     pub fn az_destroy(e: *mut az_engine);
     pub fn az_last_error(e: *const az_engine) -> *const c_char;
+    /// Keys: include/az_engine.h.  "net_fp8" = 1 (default 0) runs conv3 and conv4 of this engine's conv-net forwards on the FP8
+    /// (OCP e4m3) matrix path: a numerics class of its own, no new export.
     pub fn az_set_option(e: *mut az_engine, key: *const c_char, value: i64) -> c_int;
     pub fn az_get_stats(e: *mut az_engine, out: *mut az_stats) -> c_int;
     pub fn az_reset_stats(e: *mut az_engine) -> c_int;
