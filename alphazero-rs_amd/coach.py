@@ -52,6 +52,9 @@ class Coach:
         self.num_episode_threads = num_episode_threads    # = concurrent game slots on the GPU (rayon pool size, :202-205)
         self.num_arena_games, self.num_iters, self.num_eps, self.num_sims = num_arena_games, num_iters, num_eps, num_sims
         self.max_depth, self.cpuct = max_depth, cpuct
+        # NET_CLASS_FP8 (engine.py): every iteration pins the playing model to fp8 before az_selfplay and both arena models to bf16
+        # before az_arena; training is untouched.  NET_CLASS_ENGINE (-1, the default): no class call at all
+        self.selfplay_class = -1
         self.history = collections.deque()
         self.start_iteration = 0
         os.makedirs(self.dir, exist_ok=True)
@@ -136,6 +139,8 @@ class Coach:
             boards, pis, vs = np.zeros((0, 2, 6, 7), np.float32), np.zeros((0, 7), np.float32), np.zeros(0, np.float32)
             if not skip_first_play or iteration > self.start_iteration:
                 t0 = time.perf_counter()
+                if self.selfplay_class != -1:
+                    self.engine.net_set_class(model_id, self.selfplay_class)
                 boards, pis, vs = self.execute_episodes(model_id, iteration, seed)
                 t_play = time.perf_counter() - t0
                 if vs.shape[0] > self.max_queue_length:                 # :275-277: keep the newest max_queue_length
@@ -168,6 +173,9 @@ class Coach:
             # the W/L/D tally is one 3-counter all-reduce
             total = 2 * (self.num_arena_games // 2)
             a_seed = seed + 7919 * (iteration + 1)
+            if self.selfplay_class != -1:                               # the gate is judged in bf16 whatever the episodes were played in
+                self.engine.net_set_class(model_id + 1, 0)
+                self.engine.net_set_class(model_id, 0)
             if world > 1 and total > 0:
                 from . import dist as azdist
                 import torch

@@ -55,6 +55,7 @@ struct NetModel {
     ConvNet* conv = nullptr;
     uint64_t cache_tag = 0;     // evaluation-cache tag of the current weights (0 = none yet); new tag per upload
     uint64_t generation = 0;    // bumped by every weight upload / kind change of any model of the process: part of a search graph's key
+    int klass = AZ_NET_CLASS_ENGINE;   // az_net_set_class: state of the id (survives uploads, dropped by az_net_free)
 };
 std::atomic<uint64_t> g_model_generation{0};     // engines of one process run concurrently (one host thread each)
 
@@ -422,18 +423,27 @@ NetWorkspace* workspace_for(az_engine* e, hipStream_t s) {
     return e->ws[i];
 }
 
+// The numerics class a model's forwards run in: its own (az_net_set_class) or, by default, the engine's "net_fp8" option ...
+int effective_class(const az_engine* e, const NetModel& m) { return m.klass == AZ_NET_CLASS_ENGINE ? (e->netopt.net_fp8 ? 1 : 0) : m.klass; }
+// ... resolved here, once per forward: the kernels only ever see NetOptions::net_fp8
+NetOptions netopt_for(const az_engine* e, const NetModel& m) {
+    NetOptions o = e->netopt;
+    o.net_fp8 = effective_class(e, m);
+    return o;
+}
+
 void net_forward(az_engine* e, const NetModel& net, const EvalBatch& eb, int rows_hint, hipStream_t s, int rows_typ = 0, bool timed = true) {
     if (net.kind == AZ_NET_CONV) {
-        convnet_forward(net.conv, workspace_for(e, s), eb, rows_hint, rows_typ, s, (e->prof.on && timed) ? &e->netprof : nullptr, e->netopt);
+        convnet_forward(net.conv, workspace_for(e, s), eb, rows_hint, rows_typ, s, (e->prof.on && timed) ? &e->netprof : nullptr, netopt_for(e, net));
     } else {
         launch_net_fixture(eb, net.kind, net.salt, s);
     }
 }
 
-// "net_fp8": the model's fp8 weight copies and scales follow its parameters -- built when the option is switched on and at every upload
-// while it is on, never by a forward (which may run inside a stream capture)
+// "net_fp8": the model's fp8 weight copies and scales follow its parameters -- built when its effective class becomes fp8 and at every
+// upload while it is, never by a forward (which may run inside a stream capture)
 az_status fp8_sync_model(az_engine* e, NetModel& m) {
-    if (!e->netopt.net_fp8 || m.kind != AZ_NET_CONV || !m.conv) return AZ_OK;
+    if (m.kind != AZ_NET_CONV || !m.conv || !effective_class(e, m)) return AZ_OK;
     if (!convnet_build_fp8(m.conv, workspace_for(e, e->stream), e->stream)) return fail(e, AZ_ERR_HIP, "net_fp8: building the model's fp8 copies failed");
     return AZ_OK;
 }
@@ -647,13 +657,13 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
         k.max_rows = d_max_rows; k.ec_key = ec.key; k.ec_stat = ec.stat; k.log_state = th.d.log_state; k.log_row = th.d.log_row;
         k.ec_tag = ec.tag; k.salt = net.salt; k.kind = net.kind; k.rows_hint = rows_hint; k.rows_typ = rows_typ; k.S = S; k.dedup = dedup ? 1 : 0;
         k.block4 = th.d.block4; k.log_cap = th.d.log_cap; k.ec_bmask = ec.bmask; k.ec_stones = ec.max_stones; k.max_depth = sp.max_depth; k.cpuct = sp.cpuct_f;
-        k.opt = e->netopt;
+        k.opt = netopt_for(e, net);
         k.reserve_nodes = th.d.reserve_nodes;      // TreeDev travels by value into the captured launches: the capacity threshold is baked in
         k.model_gen = net.generation;              // a freed and re-created model may reuse the ConvNet's address: its weights' identity is the generation
         TreeHost::StepGraph& sg = th.step_graph;
         if (!sg.exec || sg.key.size() != sizeof k || std::memcmp(sg.key.data(), &k, sizeof k) != 0) {
             if (sg.exec) { HIPCHK(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(sg.exec); sg.exec = nullptr; }
-            if (net.kind == AZ_NET_CONV) convnet_prepare(workspace_for(e, s), e->netopt);      // nothing may allocate while the stream is capturing
+            if (net.kind == AZ_NET_CONV) convnet_prepare(workspace_for(e, s), k.opt);      // nothing may allocate while the stream is capturing
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
             try {
@@ -913,6 +923,10 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     // ---- options of the shipped library: every one of them lives in THIS engine ----
     if (is("conv2_table") && (value == 0 || value == 1)) {
         if (value == 0 && e->netopt.net_fp8) return fail(e, AZ_ERR_BAD_ARGUMENT, "conv2_table = 0 is not available while net_fp8 is 1 (the fp8 class takes conv2 from the table kernel)");
+        if (value == 0)
+            for (const auto& kv : e->nets)
+                if (kv.second.kind == AZ_NET_CONV && effective_class(e, kv.second))
+                    return fail(e, AZ_ERR_BAD_ARGUMENT, "conv2_table = 0 is not available while model " + std::to_string(kv.first) + " is of the fp8 class (it takes conv2 from the table kernel)");
         e->netopt.conv2_table = (int)value;
         return AZ_OK;
     }
@@ -925,7 +939,7 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
             e->netopt.net_fp8 = (int)value;
             for (auto& kv : e->nets) {
                 NetModel& m = kv.second;
-                if (m.kind != AZ_NET_CONV) continue;
+                if (m.kind != AZ_NET_CONV || m.klass != AZ_NET_CLASS_ENGINE) continue;      // a pinned model keeps its class, its tag and its graphs
                 const az_status st = fp8_sync_model(e, m);
                 if (st) { e->netopt.net_fp8 = 0; return st; }
                 m.cache_tag = 0;                                  // the other class's cached rows and captured graphs are never used again
@@ -1136,6 +1150,39 @@ az_status az_net_free(az_engine* e, int32_t model_id) {
     (void)hipStreamSynchronize(e->stream);
     if (it->second.conv) convnet_destroy(it->second.conv);
     e->nets.erase(it);          // its evaluation-cache entries die with its tag
+    return AZ_OK;
+}
+
+az_status az_net_set_class(az_engine* e, int32_t model_id, int32_t c) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (c != AZ_NET_CLASS_ENGINE && c != AZ_NET_CLASS_BF16 && c != AZ_NET_CLASS_FP8) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_set_class: the class must be ENGINE, BF16 or FP8");
+    auto it = e->nets.find(model_id);
+    if (it == e->nets.end()) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_set_class: model id not initialised");
+    NetModel& m = it->second;
+    if (m.kind != AZ_NET_CONV || !m.conv) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_set_class: the stub / hash nets have no numerics class");
+    if ((int)c == m.klass) return AZ_OK;
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_set_class: a model's class cannot change while a self-play session is open");
+    if (c == AZ_NET_CLASS_FP8 && e->netopt.conv2_table != 1) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_set_class: the fp8 class needs conv2_table = 1");
+    const int before = effective_class(e, m), stored = m.klass;
+    m.klass = (int)c;
+    if (effective_class(e, m) == before) return AZ_OK;          // the same kernels as before: the tag and the captured graphs stay good
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        const az_status st = fp8_sync_model(e, m);
+        if (st) { m.klass = stored; return st; }
+        m.cache_tag = 0;                                          // the other class's cached rows and captured graphs are never used again
+        m.generation = ++g_model_generation;
+        return AZ_OK;
+    } catch (const HipFail& f) { m.klass = stored; return fail_hip(e, f); }
+}
+
+az_status az_net_get_class(az_engine* e, int32_t model_id, int32_t* stored, int32_t* effective) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    auto it = e->nets.find(model_id);
+    if (it == e->nets.end()) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_get_class: model id not initialised");
+    if (it->second.kind != AZ_NET_CONV) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_get_class: the stub / hash nets have no numerics class");
+    if (stored) *stored = it->second.klass;
+    if (effective) *effective = effective_class(e, it->second);
     return AZ_OK;
 }
 
@@ -2448,6 +2495,14 @@ int az_diag_fp8_scales(az_engine* e, int32_t model_id, float* out2) {
     if (!e || !out2) return -1;
     auto it = e->nets.find(model_id);
     return it != e->nets.end() && it->second.conv && convnet_fp8_scales(it->second.conv, out2) ? 0 : -1;
+}
+// Diagnostic library only: k_gemm_skinny_f8 launches the engine has issued since az_create (both streams' workspaces; a launch
+// captured into a search graph counts once, at the capture)
+long long az_diag_fp8_skinny_launches(az_engine* e) {
+    if (!e) return -1;
+    long long n = 0;
+    for (NetWorkspace* w : e->ws) n += (long long)netws_fp8_skinny_launches(w);
+    return n;
 }
 // Diagnostic library only (not part of the ABI): the children of the node reached from tree g's current root by following `path`
 // (child indices, not actions).  out rows of 8 u64: slot, a, ctr (resolved through a link), prior bits, link, meta, own ctr, key.

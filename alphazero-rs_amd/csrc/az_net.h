@@ -79,7 +79,8 @@ struct NetOptions {
     int conv3_wreg = 1;     // conv3: the weight operand straight from global memory into registers in MFMA fragment order (k_conv3_auto_wreg; no
                             // weight tile in LDS, no barrier in the K loop; needs conv3_planes); 0 = the weight tile through LDS (k_conv3_auto; bit-identical)
     int net_fp8 = 0;        // 1: conv3 and conv4 on the fp8 (OCP e4m3) matrix path, a numerics class of its own (include/az_engine.h):
-                            // conv2's table kernel writes e4m3, both convs run the LDS-DMA ring on v_mfma_f32_16x16x128_f8f6f4 at every batch size;
+                            // conv2's table kernel writes e4m3, both convs run v_mfma_f32_16x16x128_f8f6f4 on the LDS-DMA ring or, for small batches
+                            // ("narrow_rows"), on the register-fed skinny GEMM, bit-identically;
                             // needs conv2_table = 1 and the model's fp8 copies (convnet_build_fp8)
     int narrow_rows = 32;   // conv3 / conv4 / fc1 / fc2 of a batch of at most this many rows (x 2 for conv4, x 4 for the FCs) run as the register-fed
                             // skinny GEMM (k_gemm_skinny), decided on the device from the exact row count; 0 = never (bit-identical)
@@ -106,6 +107,8 @@ long long netws_read_conv3_out(NetWorkspace* ws, int rows, void* out);
 long long netws_read_conv3_out_fp8(NetWorkspace* ws, int rows, void* out);
 // ... and its e4m3 conv2 output, rows x [6][7][C] bytes
 long long netws_read_conv2_out_fp8(NetWorkspace* ws, int rows, void* out);
+// "net_fp8": k_gemm_skinny_f8 launches issued on the workspace since it was created (diagnostic library's reader)
+unsigned long long netws_fp8_skinny_launches(const NetWorkspace* ws);
 // "net_fp8": build the model's fp8 weight copies and scales for its current parameters (no-op when they are current): runs the
 // calibration set through the bf16 conv2 / conv3 on stream s in workspace ws, synchronises, allocates on first use.  Never called
 // by a forward.

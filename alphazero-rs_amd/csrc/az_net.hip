@@ -667,6 +667,7 @@ __global__ __launch_bounds__(256, (NS <= 2 ? 2 : 1)) void k_gemm_ring_f8(const G
     constexpr int BMAX = NS == 2 ? 192 : 128;
     __shared__ __attribute__((aligned(16))) unsigned char smem[NS * (BMAX * 128 + 16384)];
     const int M = (int)(*d.n_dev) * d.rows_per_sample;
+    if (M <= d.m_min) return;                  // the skinny kernel launched beside this one takes the batch
     const int bm = __builtin_amdgcn_readfirstlane(ring_pick_bm(M, d.N / GBN, NS, true));
     if constexpr (NS == 2) {
         if (bm == 96) gemm_ring_body<2, 96, F8>(d, smem, M);
@@ -1849,6 +1850,97 @@ __device__ __forceinline__ void gemm_skinny_tile(const GemmDesc& d, const int M,
         }
     }
 }
+// The same wave tile for the "net_fp8" layers (F8 = 1: conv3, e4m3 -> e4m3 * out_scale; F8 = 2: conv4, e4m3 -> bf16).  A K-step is one
+// tap x 128 channels = one 128-byte segment of an activation row and of a weight row, ONE v_mfma_f32_16x16x128_f8f6f4 per accumulator;
+// lane l supplies, for row l & 15, the 16-byte chunks fq and 4 + fq (fq = l >> 4) of the segment -- the 32 bytes gemm_ring_body<.., F8>
+// reads from LDS -- with the operands in the ring's order (weights, activations, acc) and the K-steps in its order (channel block outer,
+// tap inner), then the ring's epilogue arithmetic: every accumulator sees the same operations in the same order, bit-identical.
+// The weights come from the ring's own packed copy (ConvNet::w8: stage s of column tile t at (t * steps + s) * 16 KiB, chunk c of row r
+// at slot c ^ (r & 7)): two 16-byte loads per lane and step, the stage offset a scalar.
+template <int MR, int NR, int D, int F8>
+__device__ __forceinline__ void gemm_skinny_tile_f8(const GemmDesc& d, const int M, const int mtile, const int ntile, const int lane) {
+    const int m0 = mtile * (16 * MR), n0 = ntile * (16 * NR);
+    const int frow = lane & 15, fq = lane >> 4;
+    const int ntaps = d.K / d.cin;
+    const int nk = d.K / 128;
+    const unsigned char* a_ptr[MR];
+    const unsigned char* w_ptr0[NR];
+    const unsigned char* w_ptr1[NR];
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+        int m = m0 + i * 16 + frow;
+        m = m < M ? m : M - 1;
+        const int b = m / d.rows_per_sample, r = m - b * d.rows_per_sample;
+        const int y = r / d.out_w, x = r - y * d.out_w;
+        a_ptr[i] = (const unsigned char*)d.A + (size_t)((b * d.in_h + y) * d.in_w + x) * d.in_c + fq * 16;
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        const int n = n0 + j * 16 + frow, r = n & 127;
+        const unsigned char* row = (const unsigned char*)d.Wr + ((size_t)(n >> 7) * nk * 128 + r) * 128;
+        w_ptr0[j] = row + ((fq ^ (r & 7)) << 4);
+        w_ptr1[j] = row + (((4 + fq) ^ (r & 7)) << 4);
+    }
+    // K-step walker (channel block outer, tap inner), scalars only
+    int ks_tap = 0, ks_kx = 0;
+    uint32_t ks_c0 = 0, ks_toff = 0, ks_w = 0;
+    i32x8 fa[D][MR], fb[D][NR];
+#define AZ_SLOAD8(s_)                                                                                   \
+    {                                                                                                   \
+        _Pragma("unroll") for (int i_ = 0; i_ < MR; ++i_)                                               \
+            fa[s_][i_] = __builtin_shufflevector(*(const i32x4*)(a_ptr[i_] + ks_toff), *(const i32x4*)(a_ptr[i_] + ks_toff + 64), 0, 1, 2, 3, 4, 5, 6, 7); \
+        _Pragma("unroll") for (int j_ = 0; j_ < NR; ++j_)                                               \
+            fb[s_][j_] = __builtin_shufflevector(*(const i32x4*)(w_ptr0[j_] + ks_w), *(const i32x4*)(w_ptr1[j_] + ks_w), 0, 1, 2, 3, 4, 5, 6, 7); \
+        ++ks_tap; ++ks_kx; ks_toff += (uint32_t)d.in_c; ks_w += 16384u;                                 \
+        if (ks_kx == d.tap_w) { ks_kx = 0; ks_toff += (uint32_t)((d.in_w - d.tap_w) * d.in_c); }        \
+        if (ks_tap == ntaps) { ks_tap = 0; ks_kx = 0; ks_c0 += 128; ks_toff = ks_c0; }                  \
+    }
+    // formats 0 / 0 = e4m3 x e4m3, no block scales: the compiler selects the unscaled v_mfma_f32_16x16x128_f8f6f4
+#define AZ_SMMA8(s_)                                                                                    \
+    _Pragma("unroll") for (int i_ = 0; i_ < MR; ++i_)                                                   \
+        _Pragma("unroll") for (int j_ = 0; j_ < NR; ++j_)                                               \
+            acc[i_][j_] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[s_][j_], fa[s_][i_], acc[i_][j_], 0, 0, 0, 0, 0, 0);
+    f32x4 acc[MR][NR];
+#pragma unroll
+    for (int i = 0; i < MR; ++i)
+#pragma unroll
+        for (int j = 0; j < NR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int st = 0; st < D; ++st) AZ_SLOAD8(st);
+    // steady state: straight-line body (every slot is used, then refilled D steps ahead), so the waits stay counted
+    for (int kt = D; kt < nk; kt += D) {
+#pragma unroll
+        for (int st = 0; st < D; ++st) { AZ_SMMA8(st); AZ_SLOAD8(st); }
+    }
+#pragma unroll
+    for (int st = 0; st < D; ++st) AZ_SMMA8(st);         // the last D steps: nothing left to fetch
+#undef AZ_SLOAD8
+#undef AZ_SMMA8
+    // the ring's F8 epilogue, operation for operation; a lane holds 4 consecutive output channels of one row and stores them itself
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+        const int mo = m0 + i * 16 + frow;
+        if (mo >= M) continue;
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const int n = n0 + j * 16 + fq * 4;
+            const float4 bv = *(const float4*)(d.bias + n);
+            const float4 qv = *(const float4*)(d.dq + n);
+            float r0 = acc[i][j][0], r1 = acc[i][j][1], r2 = acc[i][j][2], r3 = acc[i][j][3];
+            r0 *= qv.x; r1 *= qv.y; r2 *= qv.z; r3 *= qv.w;
+            r0 += bv.x; r1 += bv.y; r2 += bv.z; r3 += bv.w;
+            if (d.relu) { r0 = fmaxf(r0, 0.f); r1 = fmaxf(r1, 0.f); r2 = fmaxf(r2, 0.f); r3 = fmaxf(r3, 0.f); }
+            if constexpr (F8 == 1) {
+                *(uint32_t*)((unsigned char*)d.out + (size_t)mo * d.N + n) = pack_fp8x4(r0, r1, r2, r3, d.out_scale);
+            } else {
+                uint2 o;
+                o.x = pack_bf16x2(r0, r1);
+                o.y = pack_bf16x2(r2, r3);
+                *(uint2*)(d.out + (size_t)mo * d.N + n) = o;
+            }
+        }
+    }
+}
 constexpr int SK_SMALL_WAVES = 256;         // 1 x 1 tiles while they make at most this many waves, 2 x 2 beyond
 static inline int skinny_waves_max(int M, int N) {     // a grid that covers either tiling of any batch of up to M output rows
     const int w1 = (std::min(M, SK_SMALL_WAVES * 16 * 16 / N) + 15) / 16 * (N / 16), w2 = (M + 31) / 32 * (N / 32);
@@ -1873,6 +1965,25 @@ __global__ __launch_bounds__(64) void k_gemm_skinny(const GemmDesc d) {
         const int ntile = blockIdx.x % NT, mtile = blockIdx.x / NT;
         if (mtile * 32 >= M) return;
         gemm_skinny_tile<2, 2, (D1 >= 4 ? D1 / 2 : D1)>(d, M, mtile, ntile, lane);
+    }
+}
+// "net_fp8": the same kernel on e4m3 operands.  D1 / D2 (ring depths of the 1 x 1 / 2 x 2 tiles) divide the K / 128 steps: 36 at
+// C = 512, 18 at 256 (9 and 6), 9 at 128 (9 and 3)
+template <int LAYER, int F8, int D1, int D2>
+__global__ __launch_bounds__(64) void k_gemm_skinny_f8(const GemmDesc d) {
+    const int M = (int)(*d.n_dev) * d.rows_per_sample;
+    if (M > d.m_max || M <= 0) return;
+    const int lane = threadIdx.x;
+    if ((M + 15) / 16 * (d.N / 16) <= SK_SMALL_WAVES) {
+        const int NT = d.N / 16;
+        const int ntile = blockIdx.x % NT, mtile = blockIdx.x / NT;
+        if (mtile * 16 >= M) return;
+        gemm_skinny_tile_f8<1, 1, D1, F8>(d, M, mtile, ntile, lane);
+    } else {
+        const int NT = d.N / 32;
+        const int ntile = blockIdx.x % NT, mtile = blockIdx.x / NT;
+        if (mtile * 32 >= M) return;
+        gemm_skinny_tile_f8<2, 2, D2, F8>(d, M, mtile, ntile, lane);
     }
 }
 
@@ -2019,6 +2130,7 @@ struct NetWorkspace {
     unsigned long long* dbg = nullptr;     // [2048] clock stamps of the diagnostic variant
     uint16_t* c3tab = nullptr;             // Conv3Tables (the PLANES layout of conv3's LDS image)
     unsigned long long* acct = nullptr;    // [2] k_conv3_auto's rows and working launches
+    unsigned long long fp8_skinny_launches = 0;   // k_gemm_skinny_f8 launches issued on this workspace (host count; the diagnostic library's reader)
     template <class T> T* dalloc(size_t n) {
         void* p = nullptr;
         if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr;
@@ -2527,6 +2639,32 @@ static void launch_gemm(const GemmDesc& d, int rows_hint, int rows_typ, hipStrea
     launch_ring_auto<LAYER>(d2, rows_hint, rows_typ, s);
 }
 
+// "net_fp8": conv3 (LAYER 2, F8 1) / conv4 (LAYER 3, F8 2).  The hand-over rule of launch_gemm: batches of at most "narrow_rows" boards
+// (2 x for conv4) run k_gemm_skinny_f8, decided on the device from the exact row count; everything else, and everything with
+// "narrow_rows" = 0, runs the ring.  Both compute the same bits.
+template <int LAYER, int F8>
+static void launch_gemm_f8(const GemmDesc& d, int rows_hint, int rows_typ, hipStream_t s, const NetOptions& o, NetWorkspace* ws) {
+    GemmDesc dd = d;
+    if (o.narrow_rows > 0 && d.N % 32 == 0 && d.cin % 128 == 0) {
+        const int lim = o.narrow_rows * (LAYER == 2 ? 1 : 2);
+        const int est = rows_typ > 0 ? rows_typ : rows_hint;
+        if (est <= 16 * lim) {
+            dd.m_max = lim * d.rows_per_sample;
+            const int rows_cov = rows_hint < lim ? rows_hint : lim;
+            const dim3 grid((unsigned)skinny_waves_max(rows_cov * d.rows_per_sample, d.N)), block(64);
+            const int nk = d.K / 128;
+            if (nk % 18 == 0) hipLaunchKernelGGL((k_gemm_skinny_f8<LAYER, F8, 9, 6>), grid, block, 0, s, dd);
+            else hipLaunchKernelGGL((k_gemm_skinny_f8<LAYER, F8, 9, 3>), grid, block, 0, s, dd);
+            ++ws->fp8_skinny_launches;
+            if (rows_hint <= lim) return;                 // the bound itself is small: nothing else can be needed
+            dd.m_min = dd.m_max;
+        }
+    }
+    launch_ring_auto<LAYER, F8>(dd, rows_hint, rows_typ, s);
+}
+
+unsigned long long netws_fp8_skinny_launches(const NetWorkspace* n) { return n ? n->fp8_skinny_launches : 0; }
+
 static hipEvent_t net_event(NetWorkspace* n) {
     if (!n->ev_pool.empty()) { hipEvent_t e = n->ev_pool.back(); n->ev_pool.pop_back(); return e; }
     hipEvent_t e = nullptr;
@@ -2796,10 +2934,10 @@ void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows
     d.Wr = o.ring_packed ? n->wr[1] : nullptr;
     d.Wp = n->wp3;
     d.Wf = n->wf3;
-    if (fp8) {           // e4m3 act2 -> e4m3 act3 (the first half of the allocation), the ring at every batch size
+    if (fp8) {           // e4m3 act2 -> e4m3 act3 (the first half of the allocation): the ring, or for small batches the skinny GEMM
         GemmDesc d8 = d;
         d8.Wr = (const uint16_t*)n->w8[0]; d8.dq = n->dq8[0]; d8.out_scale = n->sa3; d8.Wp = nullptr; d8.Wf = nullptr;
-        launch_ring_auto<2, 1>(d8, rows_hint, rows_typ, s);
+        launch_gemm_f8<2, 1>(d8, rows_hint, rows_typ, s, o, ws);
     } else
     launch_gemm<2>(d, rows_hint, rows_typ, s, o);
     d.Wp = nullptr;
@@ -2812,7 +2950,7 @@ void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows
     if (fp8) {           // e4m3 act3 -> bf16 act4
         GemmDesc d8 = d;
         d8.Wr = (const uint16_t*)n->w8[1]; d8.dq = n->dq8[1];
-        launch_ring_auto<3, 2>(d8, rows_hint, rows_typ, s);
+        launch_gemm_f8<3, 2>(d8, rows_hint, rows_typ, s, o, ws);
     } else
     launch_gemm<3>(d, rows_hint, rows_typ, s, o);
     if (timed) (void)hipEventRecord(rec.e2c, s);

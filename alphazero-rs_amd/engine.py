@@ -31,6 +31,7 @@ STATUS_NAMES = {
 }
 NET_STUB, NET_HASH, NET_CONV = 0, 1, 2
 GAME_CONNECT_FOUR, GAME_CONNECT_THREE = 0, 1
+NET_CLASS_ENGINE, NET_CLASS_BF16, NET_CLASS_FP8 = -1, 0, 1      # az_net_class
 
 
 class AzError(RuntimeError):
@@ -79,6 +80,7 @@ class az_arena_params(C.Structure):
 # every symbol include/az_engine.h declares (tests check the library exports all of them)
 EXPORTS = [
     "az_create", "az_destroy", "az_last_error", "az_set_option", "az_get_stats", "az_reset_stats", "az_net_set_kind", "az_net_free",
+    "az_net_set_class", "az_net_get_class",
     "az_net_init_random", "az_net_load", "az_net_save", "az_net_param_count", "az_net_set_params",
     "az_net_get_params", "az_net_predict", "az_net_predict_states", "az_net_train", "az_net_train_history",
     "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_tree_create",
@@ -107,6 +109,8 @@ def load_library(path=LIB_PATH):
         "az_net_set_kind": (i32, [vp, i32, i32, u64]),
         "az_net_init_random": (i32, [vp, i32, u64]),
         "az_net_free": (i32, [vp, i32]),
+        "az_net_set_class": (i32, [vp, i32, i32]),
+        "az_net_get_class": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
         "az_net_load": (i32, [vp, i32, C.c_char_p]),
         "az_net_save": (i32, [vp, i32, C.c_char_p]),
         "az_net_param_count": (i64, [vp]),
@@ -218,6 +222,17 @@ class Engine:
     def net_free(self, model_id):
         """Drop a model id (weights + conv1 table); the per-stream activation workspace stays."""
         self._check(self._lib.az_net_free(self._h, model_id))
+
+    def net_set_class(self, model_id, net_class):
+        """az_net_set_class: pin ONE conv model to NET_CLASS_BF16 / NET_CLASS_FP8, or hand it back to the engine's "net_fp8" option
+        (NET_CLASS_ENGINE, the default).  State of the id: it survives weight uploads, net_free drops it."""
+        self._check(self._lib.az_net_set_class(self._h, model_id, int(net_class)))
+
+    def net_class(self, model_id):
+        """az_net_get_class -> (stored az_net_class, effective: 0 bf16 / 1 fp8)."""
+        stored, effective = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.az_net_get_class(self._h, model_id, C.byref(stored), C.byref(effective)))
+        return stored.value, effective.value
 
     def net_init_random(self, model_id, seed):
         self._check(self._lib.az_net_init_random(self._h, model_id, seed))

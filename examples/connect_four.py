@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--trainer", default="engine", choices=["engine", "torch"])   # NNet::train: az_net_train or autograd
     ap.add_argument("--epochs", type=int, default=10)        # connect_four_net.py:13
+    ap.add_argument("--selfplay-fp8", action="store_true")   # episodes in the fp8 class, the arena gate in bf16 (Coach.selfplay_class)
     a = ap.parse_args()
     e = azeng.Engine(device=0, max_batch=max(a.slots, a.arena, 128), net_channels=a.channels)
     e.net_init_random(0, a.seed)
@@ -46,6 +47,8 @@ def main():
                         1000,      # max_depth
                         1,         # cpuct
                         trainer=Trainer(channels=a.channels, epochs=a.epochs) if a.trainer == "torch" else None)
+    if a.selfplay_fp8:
+        coach.selfplay_class = azeng.NET_CLASS_FP8
     for r in coach.learn(skip_first_play=False, seed=a.seed):
         print(r["iteration"], "samples", r["samples"], "new/prev/draw", r["nwins"], r["pwins"], r["draws"],
               "accepted" if r["accepted"] else "rejected", "loss", r["losses"][-1],

@@ -73,6 +73,9 @@ typedef enum az_net_kind {
     AZ_NET_CONV = 2    /* policy+value conv net, connect_four_net.py:20-95, bf16 MFMA */
 } az_net_kind;
 
+/* The numerics class of a conv model (az_net_set_class): the engine's "net_fp8" option decides (default), or the model is pinned. */
+typedef enum { AZ_NET_CLASS_ENGINE = -1, AZ_NET_CLASS_BF16 = 0, AZ_NET_CLASS_FP8 = 1 } az_net_class;
+
 typedef struct az_engine az_engine;
 typedef struct az_tree az_tree;
 
@@ -176,7 +179,8 @@ const char* az_last_error(const az_engine* e);
  *                             invariants  a row's (pi, v) depends on its state alone (not on the batch size, its place in the batch or
  *                                         the tile the device picked), so de-duplication and the cache stay bit-exact; "conv3_small",
  *                                         "conv3_tail", "conv3_planes", "conv3_wreg", "narrow_rows" and "ring_packed" never change an fp8
- *                                         result (an fp8 engine runs conv3 and conv4 on the LDS-DMA ring at every batch size)
+ *                                         result (an fp8 model runs conv3 and conv4 on the LDS-DMA ring, or for small batches on the
+ *                                         register-fed skinny GEMM, bit-identically)
  *                           Measured error (torch emulation, random nets, 200 legal positions, C = 512): max |dpi| 6.1e-3, |dv| 2.6e-2
  *                           against the textbook f32 net, ten times bf16's 5.9e-4 / 2.7e-3; insensitive to the activation scale (scales
  *                           64 x smaller move the result by 5e-4 / 5e-3).  The fp8 copies and scales are built when the option is
@@ -184,7 +188,8 @@ const char* az_last_error(const az_engine* e);
  *                           Changing the value gives every conv model a new evaluation-cache tag and generation: a persistent cache never
  *                           serves a row of the other class and no captured search graph of the other class is replayed.  Refused
  *                           (AZ_ERR_BAD_ARGUMENT) while a self-play session is open and while "conv2_table" is 0; "conv2_table" = 0 is
- *                           refused while "net_fp8" is 1
+ *                           refused while "net_fp8" is 1 or any model's effective class is fp8.  The option is the class of every model
+ *                           that az_net_set_class has not pinned
  *   search   "search_graph" n (default 20, even, 0 = off): n simulation steps per captured hipGraph replay (conv nets) ...
  *            "search_graph_rows" n (default 1024): ... for searches whose expected leaf batch has at most n rows (the arena, the drain
  *                           of a self-play call, single trees: there the host's launch calls set the pace; on big batches the kernels do)
@@ -249,6 +254,18 @@ az_status az_net_init_random(az_engine* e, int32_t model_id, uint64_t seed);
 /* NNet::new(checkpoint) / save: flat f32 file, layout in DESIGN.md "weights file". */
 az_status az_net_load(az_engine* e, int32_t model_id, const char* path);
 az_status az_net_save(az_engine* e, int32_t model_id, const char* path);
+/* The numerics class of ONE model.  AZ_NET_CLASS_ENGINE (every id's default) follows the engine's "net_fp8" option; BF16 and FP8 pin
+ * the model whatever the option says, so one engine can seat a net against its own fp8 copy in az_arena, or play self-play in fp8
+ * and the gate in bf16.  The class is state of the model id: it survives weight uploads into the id (az_net_init_random, _load,
+ * _set_params, az_net_train* ending in it), az_net_free drops it, a fresh id starts at ENGINE.  Every forward of the model (search,
+ * self-play, arena, az_net_predict*, shared tree batches) runs in its EFFECTIVE class (0 bf16 / 1 fp8).  A call that changes the
+ * effective class gives this model, and no other, a new evaluation-cache tag and generation (no cached row and no captured search
+ * graph of the other class is used again) and, towards fp8, builds its fp8 copies and scales -- never a forward does; a call
+ * that leaves the effective class as it is keeps the tag.  AZ_ERR_BAD_ARGUMENT: an unknown id, a stub / hash model, FP8 while
+ * "conv2_table" is 0, any change while a self-play session is open. */
+az_status az_net_set_class(az_engine* e, int32_t model_id, int32_t net_class /* an az_net_class */);
+/* stored = what was set (an az_net_class), effective = 0 (bf16) or 1 (fp8); either may be NULL. */
+az_status az_net_get_class(az_engine* e, int32_t model_id, int32_t* stored, int32_t* effective);
 /* Raw f32 parameter exchange (same order as the weights file); count from az_net_param_count. */
 int64_t az_net_param_count(const az_engine* e);
 az_status az_net_set_params(az_engine* e, int32_t model_id, const float* params, int64_t n);

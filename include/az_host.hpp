@@ -110,6 +110,13 @@ class Engine {
     Engine& operator=(const Engine&) = delete;
     az_engine* raw() const { return e_; }
     void check(int rc) const { if (rc != AZ_OK) throw Panic(std::string(az_last_error(e_))); }
+    // az_net_set_class / az_net_get_class: the numerics class of ONE conv model (ENGINE = the engine's "net_fp8" option decides)
+    void net_set_class(size_t model_id, az_net_class c) { check(az_net_set_class(e_, (int32_t)model_id, (int32_t)c)); }
+    std::pair<int32_t, int32_t> net_class(size_t model_id) const {     // (stored az_net_class, effective: 0 bf16 / 1 fp8)
+        int32_t stored = 0, effective = 0;
+        check(az_net_get_class(e_, (int32_t)model_id, &stored, &effective));
+        return {stored, effective};
+    }
 
   private:
     az_engine* e_ = nullptr;
@@ -494,6 +501,7 @@ class Coach {
         for (size_t iteration = start_iteration; iteration < start_iteration + num_iters; ++iteration) {
             HistoryEntry h;
             if (!skip_first_play || iteration > start_iteration) {
+                if (selfplay_class != AZ_NET_CLASS_ENGINE) e_.net_set_class(model_id, selfplay_class);
                 h = execute_episodes(model_id, iteration, seed);
                 if (h.len() > max_queue_length) {                   // keep the newest max_queue_length (:275-277)
                     const size_t drop = h.len() - max_queue_length;
@@ -538,6 +546,10 @@ class Coach {
                 a.first_game = (int32_t)alo; a.num_games = (int32_t)(ahi - alo); a.total_games = (int32_t)total; a.allreduce_wld = 1;
                 if (total == 0) { a.total_games = 0; a.first_game = 0; a.num_games = 0; a.allreduce_wld = 0; }
             }
+            if (selfplay_class != AZ_NET_CLASS_ENGINE) {            // the gate is judged in bf16 whatever the episodes were played in
+                e_.net_set_class(model_id + 1, AZ_NET_CLASS_BF16);
+                e_.net_set_class(model_id, AZ_NET_CLASS_BF16);
+            }
             uint64_t wld[3] = {0, 0, 0};
             e_.check(az_arena(e_.raw(), &a, wld, nullptr));
             r.nwins = (size_t)wld[0]; r.pwins = (size_t)wld[1]; r.draws = (size_t)wld[2];
@@ -566,6 +578,9 @@ class Coach {
     size_t mcts_reserve_size = 0, temp_threshold = 0, max_history_length = 0, max_queue_length = 0, num_episode_threads = 0,
            num_arena_games = 0, num_iters = 0, num_eps = 0, num_sims = 0, max_depth = 0, num_sim_threads = 1;
     bool use_comm_at_world_1 = false;     // tests: run the gather / all-reduce path at world size 1
+    // AZ_NET_CLASS_FP8: every iteration pins the playing model to fp8 before az_selfplay and both arena models to bf16 before
+    // az_arena (the superseded id's class goes with az_net_free); training is untouched.  ENGINE (default): no class call at all
+    az_net_class selfplay_class = AZ_NET_CLASS_ENGINE;
     float update_threshold = 0.f;
     int32_t cpuct = 1;
 

@@ -61,6 +61,9 @@ extern "C" {
     // ---- NNet trait, src/nnet.rs:35-45
     pub fn az_net_set_kind(e: *mut az_engine, model_id: i32, kind: c_int, salt: u64) -> c_int;
     pub fn az_net_free(e: *mut az_engine, model_id: i32) -> c_int;
+    /// net_class: AZ_NET_CLASS_ENGINE (-1, follow "net_fp8"), AZ_NET_CLASS_BF16 (0) or AZ_NET_CLASS_FP8 (1); state of the model id
+    pub fn az_net_set_class(e: *mut az_engine, model_id: i32, net_class: i32) -> c_int;
+    pub fn az_net_get_class(e: *mut az_engine, model_id: i32, stored: *mut i32, effective: *mut i32) -> c_int;
     pub fn az_net_init_random(e: *mut az_engine, model_id: i32, seed: u64) -> c_int;
     pub fn az_net_load(e: *mut az_engine, model_id: i32, path: *const c_char) -> c_int;
     pub fn az_net_save(e: *mut az_engine, model_id: i32, path: *const c_char) -> c_int;
@@ -147,6 +150,14 @@ impl Mi355xNNet {
     }
     /// Drop a superseded model id (Coach::learn moves to model_id + 1 per accepted iteration, src/coach.rs:383-390).
     pub fn free(&mut self, model_id: usize) { check(self.e, unsafe { az_net_free(self.e, model_id as i32) }); }
+    /// Pin one model's numerics class (AZ_NET_CLASS_*); -1 hands it back to the engine's "net_fp8" option.
+    pub fn set_class(&mut self, model_id: usize, net_class: i32) { check(self.e, unsafe { az_net_set_class(self.e, model_id as i32, net_class) }); }
+    /// (stored class, effective class: 0 bf16 / 1 fp8)
+    pub fn class(&self, model_id: usize) -> (i32, i32) {
+        let (mut s, mut f) = (0i32, 0i32);
+        check(self.e, unsafe { az_net_get_class(self.e, model_id as i32, &mut s, &mut f) });
+        (s, f)
+    }
 }
 impl Drop for Mi355xNNet { fn drop(&mut self) { unsafe { az_destroy(self.e) } } }
 
