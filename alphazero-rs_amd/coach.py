@@ -25,6 +25,7 @@ panicking; when coach.state names a model whose .aznet exists it is loaded into 
 restarted run is byte-identical to an uninterrupted one.
 """
 import collections
+import contextlib
 import os
 import time
 
@@ -55,6 +56,9 @@ class Coach:
         # NET_CLASS_FP8 (engine.py): every iteration pins the playing model to fp8 before az_selfplay and both arena models to bf16
         # before az_arena; training is untouched.  NET_CLASS_ENGINE (-1, the default): no class call at all
         self.selfplay_class = -1
+        # Dirichlet root noise of the episodes (Engine.set_root_noise): switched on before every az_selfplay and off again behind it, so
+        # nothing else the engine is used for sees it (the arena never does anyway).  eps 0 (the default): the engine is never asked
+        self.root_noise_eps, self.root_noise_alpha = 0.0, 1.0
         self.history = collections.deque()
         self.start_iteration = 0
         os.makedirs(self.dir, exist_ok=True)
@@ -85,6 +89,16 @@ class Coach:
         save_examples(path, self.history)
         return path
 
+    @contextlib.contextmanager
+    def _selfplay_root_noise(self):
+        if self.root_noise_eps > 0:
+            self.engine.set_root_noise(self.root_noise_eps, self.root_noise_alpha)
+        try:
+            yield
+        finally:
+            if self.root_noise_eps > 0:
+                self.engine.set_root_noise(0.0, self.root_noise_alpha)
+
     def execute_episodes(self, model_id, iteration, seed):
         """The self-play fan-out of src/coach.rs:241-272: num_eps x execute_episode, sharded by global game id."""
         from . import dist as azdist
@@ -92,11 +106,12 @@ class Coach:
         lo, hi = azdist.shard_range(self.num_eps, rank, world)
         first = iteration * self.num_eps
         if hi > lo:
-            r = self.engine.selfplay(n_games=hi - lo, num_sims=self.num_sims, model_id=model_id, seed=seed,
-                                     first_game_id=first + lo, concurrent=min(self.num_episode_threads, hi - lo),
-                                     temp_threshold=self.temp_threshold, max_depth=self.max_depth, cpuct=self.cpuct,
-                                     reserve=self.mcts_reserve_size, symmetries=False, want_boards=False,
-                                     num_sim_threads=self.num_sim_threads)
+            with self._selfplay_root_noise():
+                r = self.engine.selfplay(n_games=hi - lo, num_sims=self.num_sims, model_id=model_id, seed=seed,
+                                         first_game_id=first + lo, concurrent=min(self.num_episode_threads, hi - lo),
+                                         temp_threshold=self.temp_threshold, max_depth=self.max_depth, cpuct=self.cpuct,
+                                         reserve=self.mcts_reserve_size, symmetries=False, want_boards=False,
+                                         num_sim_threads=self.num_sim_threads)
             states, pis, zs = r["states"], r["pis"], r["zs"]
         else:
             states, pis, zs = np.zeros((0, 2), np.uint64), np.zeros((0, 7), np.float32), np.zeros(0, np.float32)

@@ -185,6 +185,7 @@ struct TreeHost {
     // make a kept arena look freshly created (the trees themselves are rebuilt by launch_reset_trees)
     void recycle(uint64_t reserve_nodes, hipStream_t s) {
         d.reserve_nodes = (uint32_t)reserve_nodes;
+        d.noise = RootNoise{};                    // root noise belongs to the call that sets it (the arena never does)
         HIPCHK(hipMemsetAsync(d.err, 0, ERR_COUNT * sizeof(uint32_t), s));
         HIPCHK(hipMemsetAsync(d_totals, 0, ST_TOTALS * sizeof(unsigned long long), s));
         HIPCHK(hipMemsetAsync(eb.n, 0, sizeof(uint32_t), s));
@@ -303,6 +304,8 @@ struct az_engine {
     NetProfile netprof;
     NetOptions netopt;              // kernel-set switches of the conv net: this engine's, passed down with every forward
     int tree_block4 = 1;            // "tree_block4": k_backup_select as 4-wave workgroups
+    // Dirichlet root noise of self-play and the tree calls, never of the arena ("root_noise_eps_e6" 0 = off, "root_noise_alpha_e6")
+    int64_t root_noise_eps_e6 = 0, root_noise_alpha_e6 = 1000000;
     // activation workspaces of the conv net: [0] the engine stream, [1] a second concurrent stream (az_arena's old-model
     // search); created on first use, shared by every model id
     NetWorkspace* ws[2] = {nullptr, nullptr};
@@ -389,6 +392,7 @@ struct az_tree {
     DeviceMem mem;
     int num_sims = 0, max_depth = 0, model_id = 0, cpuct = 0;
     ulonglong2* d_root_states = nullptr;
+    ulonglong2* d_noise_streams = nullptr;     // [G] (seed, game_id) of each tree's current call: the root-noise streams
     // pinned host block of one get_action_prob call: the roots go up from it and k_root_policy / k_call_readback write the
     // results and counters straight into it, so a call costs one stream synchronisation instead of eight blocking copies
     void* h_io = nullptr;
@@ -411,6 +415,16 @@ az_status fail_hip(az_engine* e, const HipFail& f) {
     char buf[512];
     std::snprintf(buf, sizeof buf, "HIP error %d (%s) at %s", (int)f.code, hipGetErrorString(f.code), f.what);
     return fail(e, AZ_ERR_HIP, buf);
+}
+
+// "root_noise_eps_e6" / "root_noise_alpha_e6" as the kernels take them: the division in double, rounded once to f32.  eps == 0 (off) gives
+// the all-zero record whatever alpha is, so noise-free searches share their captured graphs.
+RootNoise root_noise_for(const az_engine* e) {
+    RootNoise rn{};
+    if (e->root_noise_eps_e6 == 0) return rn;
+    rn.eps = (float)((double)e->root_noise_eps_e6 / 1e6);
+    rn.alpha = (float)((double)e->root_noise_alpha_e6 / 1e6);
+    return rn;
 }
 
 NetWorkspace* workspace_for(az_engine* e, hipStream_t s) {
@@ -651,6 +665,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
             uint64_t model_gen;
             float cpuct;
             NetOptions opt;
+            RootNoise noise;                           // TreeDev travels by value: a graph captured with other noise arguments is never replayed
         } k;
         std::memset(&k, 0, sizeof k);
         k.th = &th; k.conv = net.conv; k.ws = net.kind == AZ_NET_CONV ? workspace_for(e, s) : nullptr; k.stream = s; k.root_states = d_root_states;
@@ -658,6 +673,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
         k.ec_tag = ec.tag; k.salt = net.salt; k.kind = net.kind; k.rows_hint = rows_hint; k.rows_typ = rows_typ; k.S = S; k.dedup = dedup ? 1 : 0;
         k.block4 = th.d.block4; k.log_cap = th.d.log_cap; k.ec_bmask = ec.bmask; k.ec_stones = ec.max_stones; k.max_depth = sp.max_depth; k.cpuct = sp.cpuct_f;
         k.opt = netopt_for(e, net);
+        k.noise = th.d.noise;
         k.reserve_nodes = th.d.reserve_nodes;      // TreeDev travels by value into the captured launches: the capacity threshold is baked in
         k.model_gen = net.generation;              // a freed and re-created model may reuse the ConvNet's address: its weights' identity is the generation
         TreeHost::StepGraph& sg = th.step_graph;
@@ -821,7 +837,9 @@ void SlotRunner::operator()(CombineBatch<SlotCall>& b) const {
             any_reset = any_reset || b.reset[i];
         }
         HIPCHK(hipMemcpyAsync(sh.d_req, sh.h_req, (size_t)n * sizeof(SlotReq), hipMemcpyHostToDevice, s));
-        launch_slot_arm(d, sh.d_req, n, t->d_root_states, sh.d_reset, s);
+        d.noise = root_noise_for(e);
+        if (d.noise.eps != 0.0f) d.noise.stream = t->d_noise_streams;         // each request's own (seed, game_id)
+        launch_slot_arm(d, sh.d_req, n, t->d_root_states, sh.d_reset, s, d.noise.stream ? t->d_noise_streams : nullptr);
         if (any_reset) launch_reset_trees(d, sh.d_reset, s);      // AsyncMcts::default for the slots acquired since their last batch
         SearchParams sp{(uint32_t)t->max_depth, (float)t->cpuct};
         // sized by the whole batch, not by this batch's requests: every batch replays the same captured graph
@@ -947,6 +965,14 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
             }
             return AZ_OK;
         } catch (const HipFail& f) { e->netopt.net_fp8 = 0; return fail_hip(e, f); }
+    }
+    if (is("root_noise_eps_e6") || is("root_noise_alpha_e6")) {
+        const bool eps = is("root_noise_eps_e6");
+        if (eps ? (value < 0 || value > 1000000) : (value < 50000 || value > 100000000))
+            return fail(e, AZ_ERR_BAD_ARGUMENT, eps ? "root_noise_eps_e6 must be in 0 .. 1000000" : "root_noise_alpha_e6 must be in 50000 .. 100000000");
+        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "root noise cannot change while a self-play session is open");
+        (eps ? e->root_noise_eps_e6 : e->root_noise_alpha_e6) = value;
+        return AZ_OK;
     }
     if (is("conv3_small") && (value == 0 || value == 1)) { e->netopt.conv3_small = (int)value; return AZ_OK; }
     if (is("conv3_tail") && (value == 0 || value == 1)) { e->netopt.conv3_tail = (int)value; return AZ_OK; }
@@ -1454,6 +1480,7 @@ az_status az_tree_create(az_engine* e, int32_t n_games, uint64_t reserve, int32_
         if (az_status cs = check_tree_slots(e, reachable_blocks(num_sims, AZ_MAX_PLIES, nodes))) return cs;
         t->th.create(n_games, reachable_blocks(num_sims, AZ_MAX_PLIES, nodes), nodes, hash_entries(num_sims, AZ_MAX_PLIES), num_threads, e->cfg.game);
         t->d_root_states = t->mem.alloc<ulonglong2>(n_games);
+        t->d_noise_streams = t->mem.alloc<ulonglong2>(n_games);
         {
             const size_t G = (size_t)n_games, head = (sizeof(CallReadback) + 63) / 64 * 64;
             HIPCHK(hipHostMalloc(&t->h_io, head + G * 16 + G * 7 * 4 * 2 + G * 7 * 2, hipHostMallocDefault));
@@ -1570,6 +1597,11 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
             HIPCHK(hipMemcpyAsync(t->d_root_states, t->h_states, (size_t)G * 16, hipMemcpyHostToDevice, e->stream));
         }
         launch_set_active(d, 1u, e->stream);
+        d.noise = root_noise_for(e);
+        if (d.noise.eps != 0.0f) {                 // tree g's stream: (seed, first_game_id + g), from device memory so the search graph survives the call's seed
+            launch_noise_streams(t->d_noise_streams, G, seed, first_game_id, e->stream);
+            d.noise.stream = t->d_noise_streams;
+        }
         SearchParams sp{(uint32_t)t->max_depth, (float)t->cpuct};
         prepare_cache(e, dedup_applies(e, *net), (uint64_t)G * ((uint64_t)t->num_sims + 1), e->stream);
         run_search(e, t->th, t->d_root_states, t->num_sims, sp, *net, G);
@@ -1590,6 +1622,26 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
         copy_out(pi, t->h_pi, (size_t)G * 7 * sizeof(float));
         if (counts) copy_out(counts, t->h_counts, (size_t)G * 7 * sizeof(uint16_t));
         if (q) copy_out(q, t->h_q, (size_t)G * 7 * sizeof(float));
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// The device sampler alone (csrc/az_noise.h as the search kernels run it) for n roots at the engine's current alpha.
+az_status az_root_noise_eta(az_engine* e, int32_t n, uint64_t seed, const uint64_t* game_ids, const uint64_t* states, float* eta_out) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (n < 0 || (n > 0 && (!game_ids || !states || !eta_out))) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_root_noise_eta: bad argument");
+    if (n == 0) return AZ_OK;
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        DeviceMem mem;
+        uint64_t* d_ids = mem.alloc<uint64_t>((size_t)n);
+        ulonglong2* d_states = mem.alloc<ulonglong2>((size_t)n);
+        float* d_eta = mem.alloc<float>((size_t)n * 7);
+        HIPCHK(hipMemcpyAsync(d_ids, game_ids, (size_t)n * 8, hipMemcpyDefault, e->stream));
+        HIPCHK(hipMemcpyAsync(d_states, states, (size_t)n * 16, hipMemcpyDefault, e->stream));
+        launch_root_noise_eta(e->cfg.game, n, seed, d_ids, d_states, (float)((double)e->root_noise_alpha_e6 / 1e6), d_eta, e->stream);
+        HIPCHK(hipMemcpyAsync(eta_out, d_eta, (size_t)n * 7 * sizeof(float), hipMemcpyDefault, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
 }
@@ -1688,7 +1740,7 @@ struct SelfplaySession {
     EvalCache ec{};
     int fill = 0;
     long long step = 0;
-    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); }
+    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); if (lease.th) lease.th->d.noise = RootNoise{}; }
 };
 
 static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, std::unique_ptr<SelfplaySession>& out) {
@@ -1752,6 +1804,8 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
         HIPCHK(hipMemcpy(gd.counters, ctr, sizeof ctr, hipMemcpyHostToDevice));
     }
     launch_reset_trees(th.d, nullptr, s);
+    th.d.noise = root_noise_for(e);               // the session's root noise: stream (seed, first_game_id + the slot's episode, ply)
+    if (th.d.noise.eps != 0.0f) { th.d.noise.seed = p->seed; th.d.noise.first_game_id = p->first_game_id; th.d.noise.row = gd.gid; }
     prepare_cache(e, dedup_applies(e, *net), (uint64_t)n_games * AZ_MAX_PLIES * ((uint64_t)p->num_sims + 1), s);
     ss->sp = SearchParams{(uint32_t)p->max_depth, (float)p->cpuct};
     ss->mp = SelfplayMoveParams{p->seed, p->first_game_id, p->temp_threshold, C < n_games ? 1 : 0, 0, 0};

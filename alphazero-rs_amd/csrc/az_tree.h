@@ -57,6 +57,17 @@ struct TreeLine {
 };
 static_assert(sizeof(TreeLine) == 128, "head + inline path = one 128-byte line");
 
+// Dirichlet root noise ("root_noise_eps_e6" / "root_noise_alpha_e6", include/az_engine.h; the sampler: az_noise.h).  eps == 0 is OFF: the
+// launchers then pick the kernels' noise-free instantiations, which contain none of this.  Tree g's stream is (seed, game_id, ply = stones
+// on the root board) with (seed, game_id) = stream[g] when stream is set (the tree calls: one pair per tree / per slot request), else
+// (seed, first_game_id + (row ? row[g] : g)) (self-play: row = the slot's current episode).
+struct RootNoise {
+    float eps, alpha;
+    uint64_t seed, first_game_id;
+    const int32_t* row;          // [G] or nullptr
+    const ulonglong2* stream;    // [G] (seed, game_id) or nullptr
+};
+
 struct TreeDev {
     int32_t G;               // trees
     uint32_t R;              // slots per tree (a multiple of BLOCK_SLOTS)
@@ -81,6 +92,7 @@ struct TreeDev {
     float* log_pi;           // [G*log_cap*7]
     float* log_v;            // [G*log_cap]
     const int32_t* log_row;  // [G] or nullptr: log row of tree g (az_selfplay: the slot's current episode, so a log survives slot refills); nullptr = g
+    RootNoise noise;         // set by the entry point around its searches; zero for the arena
 };
 
 // Leaf batch handed to the net (src/async_mcts.rs:117-189 restated as lanes): the DISTINCT states the trees of one
@@ -225,7 +237,13 @@ struct SlotOut {
 static_assert(sizeof(SlotOut) == 80, "80-byte answer records");
 // head.active = 1 for the requested slots and 0 for all others, their root states into roots[slot], reset_flags[slot] = the
 // request's reset bit (0 elsewhere), t.err cleared; slots outside [0, G) are skipped
-void launch_slot_arm(const TreeDev& t, const SlotReq* req, int n, ulonglong2* roots, uint8_t* reset_flags, hipStream_t s);
+// streams (may be nullptr): streams[slot] = the request's (seed, game_id), the root-noise stream of its tree
+void launch_slot_arm(const TreeDev& t, const SlotReq* req, int n, ulonglong2* roots, uint8_t* reset_flags, hipStream_t s, ulonglong2* streams = nullptr);
+// streams[g] = (seed, first_game_id + g): the root-noise streams of az_tree_get_action_prob
+void launch_noise_streams(ulonglong2* streams, int n, uint64_t seed, uint64_t first_game_id, hipStream_t s);
+// eta_out[i][0..7) = the Dirichlet(alpha) noise of root states[i] on the stream (seed, game_ids[i], stones(states[i])): what a search with root
+// noise mixes into that root's priors (all device pointers)
+void launch_root_noise_eta(int game, int n, uint64_t seed, const uint64_t* game_ids, const ulonglong2* states, float alpha, float* eta_out, hipStream_t s);
 // get_action_prob's epilogue for each request with its own temperature and RNG stream (root_policy), plus its status word
 void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s);
 // what one get_action_prob call hands back besides pi / counts / q: written into PINNED host memory by k_call_readback

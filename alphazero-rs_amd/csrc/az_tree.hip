@@ -8,8 +8,10 @@
 // Reference restated: src/async_mcts.rs:74-115, :219-371; src/node.rs:272-370;
 // src/coach.rs:104-157; with the repairs of SURVEY.md section 0.2 (tagged S#/B#).
 #include "az_tree.h"
+#include "az_noise.h"
 
 namespace az {
+static_assert(NOISE_PURPOSE == RNG_NOISE, "az_noise.h restates the purpose word of az_common.h");
 
 // ---- lane-group primitives (GW = Game::GROUP lanes per tree) ------------------------------------------------------
 template <int GW> AZ_D uint32_t gshfl(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src, GW); }
@@ -287,8 +289,36 @@ AZ_D uint32_t leaf_request(const EvalBatch& eb, const EvalCache& ec, bool want, 
     return src;
 }
 
-// ---- get_action_prob prologue: root lookup (src/async_mcts.rs:81) + S10 + S1 -------------
+// ---- Dirichlet root noise (az_noise.h; only the NZ instantiations of the kernels contain it) ---------------------------------------
+// The root's 8 lanes together: lane sub < nchild draws the Gamma variate of its own child's action `myact` (an action's draws are a
+// sub-stream of their own, so the lanes' rejection counts do not matter), the sum runs over the children in slot order = ascending
+// action order (group shuffles), and the lane gets its child's eta.
 template <class G>
+AZ_D float root_noise_eta_lane(uint64_t stream, float alpha, uint32_t nchild, uint32_t myact, int sub) {
+    constexpr int GW = G::GROUP;
+    const float gm = (uint32_t)sub < nchild ? noise_gamma(stream, myact, alpha) : 0.0f;
+    float sum = 0.0f;
+#pragma unroll
+    for (int j = 0; j < G::ACTIONS; ++j) {
+        const float gj = gshflf<GW>(gm, j);
+        if ((uint32_t)j < nchild) sum = __fadd_rn(sum, gj);
+    }
+    return noise_normalise(gm, sum, nchild);
+}
+// the prior of lane sub's root child after the mix: (1 - eps) * prior + eps * eta[myact]; s = the root's state
+template <class G>
+AZ_D float root_noise_mix(const TreeDev& t, int g, typename G::State s, uint32_t nchild, uint32_t myact, float prior, int sub) {
+    uint64_t seed = t.noise.seed, game_id;
+    if (t.noise.stream) { const ulonglong2 st = t.noise.stream[g]; seed = st.x; game_id = st.y; }
+    else game_id = t.noise.first_game_id + (uint64_t)(t.noise.row ? t.noise.row[g] : g);
+    const uint64_t stream = noise_stream(seed, game_id, (uint64_t)G::stones(s));
+    return noise_mix(t.noise.eps, prior, root_noise_eta_lane<G>(stream, t.noise.alpha, nchild, myact, sub));
+}
+
+// ---- get_action_prob prologue: root lookup (src/async_mcts.rs:81) + S10 + S1 -------------
+// NZ: root noise is on.  A root that already has its prior gets the noise here; one that is evaluated first (LEAF_ROOT) gets it in its
+// backup, right after the prior is stored -- once per get_action_prob either way, before the call's first selection.
+template <class G, bool NZ = false>
 AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ulonglong2* root_states, int g, int sub) {
     const bool act = h.active != 0;
     size_t base = (size_t)g * t.R;
@@ -319,6 +349,13 @@ AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ul
                 if (sub == 0) atomicOr(&t.err[ERR_TERMINAL_ROOT], 1u);
             } else if (!(meta & META_HAS_PRIOR)) {
                 kind = LEAF_ROOT;  // S1 (A1): evaluate the root once so best_child has a prior (not a simulation: nothing is backed up)
+            } else if constexpr (NZ) {
+                const NodeRec rr = node_load(node_ptr(t, base, root));
+                const uint32_t nchild = (rr.meta >> META_NCHILD_SHIFT) & 7u;
+                uint4* cp = node_ptr(t, base, rr.child_base + ((uint32_t)sub < nchild ? (uint32_t)sub : 0u));
+                const NodeRec cr = node_load(cp);
+                const float mixed = root_noise_mix<G>(t, g, s, nchild, cr.meta & META_A_MASK, __uint_as_float(cr.prior), sub);
+                if ((uint32_t)sub < nchild) node_set_prior(cp, __float_as_uint(mixed));
             }
         }
         h.root = (root == NONE) ? 0u : root;
@@ -331,14 +368,14 @@ AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ul
     return s;
 }
 
-template <class G>
+template <class G, bool NZ>
 __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, EvalCache ec, const ulonglong2* root_states) {
     constexpr int GW = G::GROUP;
     int tid = blockIdx.x * 64 + threadIdx.x;
     int g = tid / GW, sub = tid % GW;
     if (g >= t.G) return;
     TreeHead h = head_load(t, g);
-    const typename G::State s = root_prepare_body<G>(t, h, root_states, g, sub);
+    const typename G::State s = root_prepare_body<G, NZ>(t, h, root_states, g, sub);
     const uint32_t src = leaf_request<G>(eb, ec, h.leaf_kind == LEAF_ROOT, s, sub);
     if (h.leaf_kind == LEAF_ROOT) h.src = src;
     if (sub == 0) head_store(t, g, h);
@@ -537,7 +574,7 @@ AZ_D void cache_claim_finish(const EvalCache& ec, CacheClaim c, float pv, int su
 // ---- mask/renormalise/store the prior (src/async_mcts.rs:317-353) + backup (:361-370) ----
 // INLINE_PV: the leaf's (pi, v) row is handed over in a register (pv_in: lane a < ACTIONS holds pi[a], lane ACTIONS holds v)
 // instead of being read through TreeHead.src -- the fused search of the fixture nets.
-template <class G, bool INLINE_PV = false>
+template <class G, bool INLINE_PV = false, bool NZ = false>
 AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const EvalBatch& eb, const EvalCache& ec, int g,
                       int sub, const uint32_t* path, float pv_in = 0.0f) {
     constexpr int GW = G::GROUP;
@@ -594,7 +631,8 @@ AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const 
         }
         const uint32_t nchild = (lr.meta >> META_NCHILD_SHIFT) & 7u, cb = lr.child_base;
         const uint32_t myact = (uint32_t)sub < nchild ? nth_set_bit<NA>(vm, (uint32_t)sub) : 0u;
-        const float pa = gshflf<GW>(p, (int)myact);
+        float pa = gshflf<GW>(p, (int)myact);
+        if constexpr (NZ) { if (apply_only) pa = root_noise_mix<G>(t, g, s, nchild, myact, pa, sub); }      // the root's own evaluation: mix the noise in
         if ((uint32_t)sub < nchild) node_set_prior(node_ptr(t, base, cb + sub), __float_as_uint(pa));   // set_policy, :348
         if (sub == 0) node_set_word(lp, (lr.meta | META_HAS_PRIOR) & ~META_LOCKED, lr.link, lr.child_base);      // set_policy + unlock, :348-351
         h.stat[ST_LEAF_EVALS] += 1;
@@ -676,7 +714,7 @@ AZ_D void clear_election_keys(const EvalBatch& eb) {
     const uint32_t total = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= eb.tmask; i += total) eb.tkey[i] = 0ull;
 }
-template <class G>
+template <class G, bool NZ>
 __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCache ec) {
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * 64 + threadIdx.x;
@@ -686,7 +724,7 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
     if (g >= t.G) return;
     TreeHead h = head_load(t, g);
     const PathRegs pth = path_load(t, g, sub);
-    backup_body<G>(t, h, pth, eb, ec, g, sub, t.path + (size_t)g * PATH_CAP);
+    backup_body<G, false, NZ>(t, h, pth, eb, ec, g, sub, t.path + (size_t)g * PATH_CAP);
     h.leaf_kind = LEAF_NONE;
     if (sub == 0) head_store(t, g, h);
 }
@@ -694,7 +732,7 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
 // backup of simulation i and select of simulation i+1 in one launch: both belong to the same 8 lanes of the same tree and
 // nothing else touches that tree in between.  The leaf of i+1 goes into the OTHER eval batch (eb_next; its count was
 // zeroed by the previous launch, this one zeroes eb_prev's), so the two ping-pong.
-template <class G, bool STAMP = false>      // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
+template <class G, bool STAMP, bool NZ>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
 __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec,
                                                        SearchParams sp, unsigned long long* dbg) {
     constexpr int GW = G::GROUP;
@@ -709,7 +747,7 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     TreeHead h = head_load(t, g);
     PathRegs pth = path_load(t, g, sub);
     AZ_TSTAMP(1);
-    backup_body<G>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * PATH_CAP);
+    backup_body<G, false, NZ>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * PATH_CAP);
     AZ_TSTAMP(2);
     // the counters this tree's other lanes just wrote are read by the selection below
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -750,7 +788,7 @@ AZ_D void group_memory_sync() {
 struct ThreadRegs { uint32_t leaf, leaf_kind; float leaf_val; uint32_t src, path_len; };
 AZ_D void thread_to_head(TreeHead& h, const ThreadRegs& r) { h.leaf = r.leaf; h.leaf_kind = r.leaf_kind; h.leaf_val = r.leaf_val; h.src = r.src; h.path_len = r.path_len; }
 AZ_D ThreadRegs head_to_thread(const TreeHead& h) { return ThreadRegs{h.leaf, h.leaf_kind, h.leaf_val, h.src, h.path_len}; }
-template <class G>
+template <class G, bool NZ>
 __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp, int first, int last) {
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * 64 + threadIdx.x;
@@ -761,7 +799,18 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
     TreeHead h = head_load(t, g);
     const ThreadRegs root_req = head_to_thread(h);          // first: k_root_prepare left the root's evaluation request in the head (S1)
     const int T = t.T;
-    for (int tt = 0; tt < T; ++tt) {                        // backups in thread order
+    int tt0 = 0;
+    if constexpr (NZ) {
+        // the root's own evaluation (the only backup of a first step) is where the noise goes in: peeled out of the thread loop, which
+        // then runs the noise-free body
+        if (first) {
+            PathRegs pth{0u, 0u};
+            thread_to_head(h, root_req);
+            backup_body<G, false, true>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * T * PATH_CAP);
+            tt0 = T;
+        }
+    }
+    for (int tt = tt0; tt < T; ++tt) {                      // backups in thread order
         TreeLine* tl = t.thr + (size_t)g * T + tt;
         ThreadRegs r{0u, LEAF_NONE, 0.0f, 0u, 0u};
         PathRegs pth{0u, 0u};
@@ -822,7 +871,7 @@ AZ_D float fixture_row(typename G::State s, int kind, uint64_t salt, int sub) {
     for (int a = 0; a < G::ACTIONS; ++a) out = sub == a ? pi[a] : out;
     return out;
 }
-template <class G>
+template <class G, bool NZ>
 __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind,
                                                        uint64_t salt) {
     constexpr int GW = G::GROUP;
@@ -833,12 +882,12 @@ __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglon
     const EvalCache no_ec{};
     TreeHead h = head_load(t, g);
     PathRegs pth{0u, 0u};
-    typename G::State ls = root_prepare_body<G>(t, h, root_states, g, sub);
+    typename G::State ls = root_prepare_body<G, NZ>(t, h, root_states, g, sub);
     for (int i = 0; i <= num_sims; ++i) {
         group_memory_sync();
         // backup of the previous leaf (i == 0: the root's priors only, S1), then the next selection
         const float pv = (h.leaf_kind == LEAF_EVAL || h.leaf_kind == LEAF_ROOT) ? fixture_row<G>(ls, kind, salt, sub) : 0.0f;
-        backup_body<G, true>(t, h, pth, no_eb, no_ec, g, sub, t.path + (size_t)g * PATH_CAP, pv);
+        backup_body<G, true, NZ>(t, h, pth, no_eb, no_ec, g, sub, t.path + (size_t)g * PATH_CAP, pv);
         if (i == num_sims) break;
         group_memory_sync();
         ls = select_body<G>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP);
@@ -869,7 +918,8 @@ __global__ __launch_bounds__(64) void k_root_policy(TreeDev t, float temp, uint6
 // ---- shared tree batch (az_tree_share) ----------------------------------------------------------------------------------------
 // One workgroup: first every slot goes inactive (and loses its reset flag), then -- after the barrier, so the two phases' stores to
 // one head never race -- the requested slots are armed.  A batch of any size leaves every other tree exactly as it was.
-__global__ __launch_bounds__(1024) void k_slot_arm(TreeDev t, const SlotReq* __restrict__ req, int n, ulonglong2* roots, uint8_t* reset_flags) {
+__global__ __launch_bounds__(1024) void k_slot_arm(TreeDev t, const SlotReq* __restrict__ req, int n, ulonglong2* roots, uint8_t* reset_flags,
+                                                   ulonglong2* streams) {
     for (int g = threadIdx.x; g < t.G; g += blockDim.x) {
         t.head[g].head.active = 0u;
         reset_flags[g] = 0;
@@ -882,7 +932,35 @@ __global__ __launch_bounds__(1024) void k_slot_arm(TreeDev t, const SlotReq* __r
         t.head[r.slot].head.active = 1u;
         roots[r.slot] = r.state;
         reset_flags[r.slot] = r.reset ? 1 : 0;
+        if (streams) streams[r.slot] = make_ulonglong2(r.seed, r.game_id);      // the slot's root-noise stream
     }
+}
+__global__ void k_noise_streams(ulonglong2* streams, int n, uint64_t seed, uint64_t first_game_id) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n) streams[g] = make_ulonglong2(seed, first_game_id + (uint64_t)g);
+}
+// az_root_noise_eta: the sampler alone, 8 lanes per root exactly as a search runs it (the root's children = its valid moves in ascending
+// order); lane a then holds eta[a] (0 for an invalid action)
+template <class G>
+__global__ __launch_bounds__(64) void k_root_noise_eta(int n, uint64_t seed, const uint64_t* __restrict__ game_ids, const ulonglong2* __restrict__ states,
+                                                       float alpha, float* __restrict__ eta_out) {
+    constexpr int GW = G::GROUP;
+    constexpr int NA = G::ACTIONS;
+    const int tid = blockIdx.x * 64 + threadIdx.x;
+    const int i = tid / GW, sub = tid % GW;
+    if (i >= n) return;
+    const typename G::State s = states[i];
+    const uint32_t vm = G::valid_mask(s) & ((1u << NA) - 1u), nchild = (uint32_t)__popc(vm);
+    const uint32_t myact = (uint32_t)sub < nchild ? nth_set_bit<NA>(vm, (uint32_t)sub) : 0u;
+    const float eta = root_noise_eta_lane<G>(noise_stream(seed, game_ids[i], (uint64_t)G::stones(s)), alpha, nchild, myact, sub);
+    float mine = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        const float ej = gshflf<GW>(eta, j);
+        const uint32_t aj = gshfl<GW>(myact, j);
+        if ((uint32_t)j < nchild && aj == (uint32_t)sub) mine = ej;
+    }
+    if (sub < NA) eta_out[(size_t)i * NA + sub] = mine;
 }
 
 // k_root_policy per REQUEST: request i's tree is req[i].slot, its temperature and RNG stream are its own, its answer goes to out[i].
@@ -1066,7 +1144,7 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
 // net's rows alone -- the schedule decides when a row is evaluated, never what it is.
 //   gd.sims[g]   simulations of the current move done so far; -1 = the move's root is not prepared yet
 //   first        the first launch behind a forward: eb_prev holds that forward's rows (parked trees back up; its table is cleared)
-template <class G>
+template <class G, bool NZ>
 __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp,
                                                     SelfplayMoveParams mp, int num_sims, int first, int max_iters) {
     constexpr int GW = G::GROUP;
@@ -1091,14 +1169,14 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
             if (h.leaf_kind != LEAF_NONE) {                                    // the pending leaf: store its prior, back its value up
                 const bool was_sim = h.leaf_kind != LEAF_ROOT;
                 group_memory_sync();
-                backup_body<G>(t, h, pth, eb_prev, ec, g, sub, path);
+                backup_body<G, false, NZ>(t, h, pth, eb_prev, ec, g, sub, path);
                 h.leaf_kind = LEAF_NONE;
                 if (was_sim) ++sims;
                 continue;
             }
             group_memory_sync();
             if (sims < 0) {                                                    // get_action_prob's prologue for the slot's position (S10, S1)
-                leaf_s = root_prepare_body<G>(t, h, gd.state, g, sub);
+                leaf_s = root_prepare_body<G, NZ>(t, h, gd.state, g, sub);
                 sims = 0;
                 if (!h.active) break;                                          // a failed root (error flag set): the call ends with an error
                 if (h.leaf_kind == LEAF_ROOT) { want = true; break; }
@@ -1219,6 +1297,12 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
         if ((game_) == 1) { using TG = ConnectThree; __VA_ARGS__; } \
         else { using TG = ConnectFour; __VA_ARGS__; }               \
     } while (0)
+// ... and per root-noise setting: NZ = true only when the tree batch carries a non-zero eps
+#define AZ_FOR_GAME_NZ(t_, ...)                                                          \
+    do {                                                                                 \
+        if ((t_).noise.eps != 0.0f) { constexpr bool NZ = true; AZ_FOR_GAME((t_).game, __VA_ARGS__); } \
+        else { constexpr bool NZ = false; AZ_FOR_GAME((t_).game, __VA_ARGS__); }         \
+    } while (0)
 static inline int group_blocks(int G) { return (G * BLOCK_SLOTS + 63) / 64; }
 #ifdef AZ_DIAG
 // diagnostic library only: the PUCT term of best_child (src/node.rs:352-356) for n (child counter, prior bits, parent N) triples, as the
@@ -1264,10 +1348,10 @@ void launch_reset_trees(const TreeDev& t, const uint8_t* flags, hipStream_t s, c
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_reset_trees<TG>, dim3(t.G), dim3(256), 0, s, t, flags, const_cast<uint8_t*>(flags), roots));
 }
 void launch_root_prepare(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, const ulonglong2* root_states, hipStream_t s) {
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_root_prepare<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec, root_states));
+    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_root_prepare<TG, NZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec, root_states));
 }
 void launch_backup(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, hipStream_t s) {
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_backup<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec));
+    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_backup<TG, NZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec));
 }
 void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                           hipStream_t s) {
@@ -1275,27 +1359,34 @@ void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const Eval
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
 #ifdef AZ_DIAG
     if (g_tree_dbg && t.G * 8 / 64 <= TREE_DBG_WAVES) {
-        AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_backup_select<TG, true>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg));
+        AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_backup_select<TG, true, NZ>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg));
         return;
     }
 #endif
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_backup_select<TG, false>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr));
+    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_backup_select<TG, false, NZ>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr));
 }
 void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                     int first, int last, hipStream_t s) {
     // one wave per workgroup: leaf_request is called T times per launch and its one-atomic-per-workgroup path keeps state in LDS
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_step_mt<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last));
+    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_step_mt<TG, NZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last));
 }
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s) {
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_search_fixture<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt));
+    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt));
 }
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,
                         uint16_t* counts, float* q, hipStream_t s) {
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_root_policy<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, temp, seed, first_game_id, pi, counts, q));
 }
-void launch_slot_arm(const TreeDev& t, const SlotReq* req, int n, ulonglong2* roots, uint8_t* reset_flags, hipStream_t s) {
-    hipLaunchKernelGGL(k_slot_arm, dim3(1), dim3(1024), 0, s, t, req, n, roots, reset_flags);
+void launch_slot_arm(const TreeDev& t, const SlotReq* req, int n, ulonglong2* roots, uint8_t* reset_flags, hipStream_t s, ulonglong2* streams) {
+    hipLaunchKernelGGL(k_slot_arm, dim3(1), dim3(1024), 0, s, t, req, n, roots, reset_flags, streams);
+}
+void launch_noise_streams(ulonglong2* streams, int n, uint64_t seed, uint64_t first_game_id, hipStream_t s) {
+    hipLaunchKernelGGL(k_noise_streams, dim3((n + 255) / 256), dim3(256), 0, s, streams, n, seed, first_game_id);
+}
+void launch_root_noise_eta(int game, int n, uint64_t seed, const uint64_t* game_ids, const ulonglong2* states, float alpha, float* eta_out, hipStream_t s) {
+    if (n <= 0) return;
+    AZ_FOR_GAME(game, hipLaunchKernelGGL(k_root_noise_eta<TG>, dim3(group_blocks(n)), dim3(64), 0, s, n, seed, game_ids, states, alpha, eta_out));
 }
 void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s) {
     if (n <= 0) return;
@@ -1315,7 +1406,7 @@ void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s) {
     const bool four = t.block4 && (t.G * 8) % 256 == 0;
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_async_step<TG>, grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters));
+    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_async_step<TG, NZ>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters));
 }
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s) {
     hipLaunchKernelGGL(k_sync_active, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gd);

@@ -86,7 +86,7 @@ EXPORTS = [
     "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
-    "az_tree_slot_error", "az_tree_share_stats", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
+    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
     "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
 COMM_ID_BYTES = 128
@@ -136,6 +136,7 @@ def load_library(path=LIB_PATH):
         "az_tree_slot_get_action_prob": (i32, [vp, i32, vp, f32, u64, u64, vp, vp, vp]),
         "az_tree_slot_error": (C.c_char_p, [vp, i32]),
         "az_tree_share_stats": (i32, [vp, vp]),
+        "az_root_noise_eta": (i32, [vp, i32, u64, vp, vp, vp]),
         "az_selfplay": (i32, [vp, C.POINTER(az_selfplay_params), C.POINTER(az_samples)]),
         "az_selfplay_begin": (i32, [vp, C.POINTER(az_selfplay_params)]),
         "az_selfplay_next": (i32, [vp, C.c_int32, C.POINTER(az_samples)]),
@@ -305,6 +306,23 @@ class Engine:
         """az_set_option on this engine (keys: include/az_engine.h), e.g. set_option("net_fp8", 1): conv3 and conv4 of this engine's
         conv-net forwards on the FP8 (e4m3) matrix path -- a numerics class of its own, default off."""
         self._check(self._lib.az_set_option(self._h, key.encode(), int(value)))
+
+    def set_root_noise(self, eps, alpha=1.0):
+        """Dirichlet root noise of self-play and the tree calls (never the arena): prior <- (1 - eps) * prior + eps * eta,
+        eta ~ Dirichlet(alpha) over the root's valid moves, once per get_action_prob.  eps = 0 switches it off (the default);
+        the values travel as "root_noise_eps_e6" / "root_noise_alpha_e6" (include/az_engine.h)."""
+        self.set_option("root_noise_alpha_e6", int(round(float(alpha) * 1e6)))
+        self.set_option("root_noise_eps_e6", int(round(float(eps) * 1e6)))
+
+    def root_noise_eta(self, states, game_ids, seed=0):
+        """az_root_noise_eta: eta [n,7] the device sampler draws for root states [n,2] on the streams (seed, game_ids[i], stones),
+        at the engine's current alpha."""
+        s = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, 2)
+        g = np.ascontiguousarray(game_ids, dtype=np.uint64).reshape(-1)
+        assert g.shape[0] == s.shape[0]
+        eta = np.empty((s.shape[0], ACTIONS), np.float32)
+        self._check(self._lib.az_root_noise_eta(self._h, s.shape[0], seed, _ptr(g), _ptr(s), _ptr(eta)))
+        return eta
 
     # ---- stats ----
     def stats(self):

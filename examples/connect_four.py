@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--trainer", default="engine", choices=["engine", "torch"])   # NNet::train: az_net_train or autograd
     ap.add_argument("--epochs", type=int, default=10)        # connect_four_net.py:13
     ap.add_argument("--selfplay-fp8", action="store_true")   # episodes in the fp8 class, the arena gate in bf16 (Coach.selfplay_class)
+    ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
     a = ap.parse_args()
     e = azeng.Engine(device=0, max_batch=max(a.slots, a.arena, 128), net_channels=a.channels)
     e.net_init_random(0, a.seed)
@@ -49,6 +50,9 @@ def main():
                         trainer=Trainer(channels=a.channels, epochs=a.epochs) if a.trainer == "torch" else None)
     if a.selfplay_fp8:
         coach.selfplay_class = azeng.NET_CLASS_FP8
+    if a.root_noise:
+        eps, _, alpha = a.root_noise.partition(",")
+        coach.root_noise_eps, coach.root_noise_alpha = float(eps), float(alpha) if alpha else 1.0
     for r in coach.learn(skip_first_play=False, seed=a.seed):
         print(r["iteration"], "samples", r["samples"], "new/prev/draw", r["nwins"], r["pwins"], r["draws"],
               "accepted" if r["accepted"] else "rejected", "loss", r["losses"][-1],

@@ -190,6 +190,33 @@ const char* az_last_error(const az_engine* e);
  *                           (AZ_ERR_BAD_ARGUMENT) while a self-play session is open and while "conv2_table" is 0; "conv2_table" = 0 is
  *                           refused while "net_fp8" is 1 or any model's effective class is fp8.  The option is the class of every model
  *                           that az_net_set_class has not pinned
+ *   root noise  "root_noise_eps_e6"   0 (default, OFF) .. 1000000: eps = (float)(value / 1e6) (the division in double, rounded once to f32)
+ *            "root_noise_alpha_e6" 50000 .. 100000000 (default 1000000): alpha = (float)(value / 1e6)
+ *                           DIRICHLET ROOT NOISE of AlphaZero self-play, strictly opt-in: with eps = 0 (set or never set) every output of
+ *                           every entry is bit for bit what it is without the feature.  Values out of range and any change while a
+ *                           self-play session is open are refused (AZ_ERR_BAD_ARGUMENT).  State of the engine, like every option.  The
+ *                           contract (the sampler, operation by operation: csrc/az_noise.h):
+ *                             where      every get_action_prob of az_selfplay, az_selfplay_begin / _next (lock-step and
+ *                                        "selfplay_async", any num_sim_threads, with slot refill), az_tree_get_action_prob and
+ *                                        az_tree_slot_get_action_prob.  NEVER az_arena: the gate is noise-free whatever the options say
+ *                             when       once per get_action_prob, after the root has its stored prior (already there, or just stored from
+ *                                        the root's own evaluation) and before the call's first selection
+ *                             what       for each root child slot with action a, in place in the child record:
+ *                                        prior <- (1 - eps) * prior + eps * eta[a]   (f32, round to nearest: 1 - eps, two products, one sum);
+ *                                        no re-normalisation; invalid actions stay 0.  The change is PERMANENT: searching the same root
+ *                                        again on the same stream mixes the same eta in again (cannot happen inside an episode: a
+ *                                        position never recurs).  The evaluation cache, the leaf de-duplication and the eval log
+ *                                        (record_evals) keep the raw net outputs
+ *                             stream     eta is a function of (seed, game_id, ply = stones on the root board, alpha, valid-move mask)
+ *                                        alone -- the triple of the tie-break stream; draw j of action a =
+ *                                        rng_draw(seed, game_id, ply, 5 + 256 * a + 65536 * j); uniforms ((r >> 40) + 0.5) * 2^-24
+ *                             sampler    eta[a] = g[a] / sum over the valid actions in ascending order, g[a] ~ Gamma(alpha) by
+ *                                        Marsaglia-Tsang with polar normals (three draws per round, at most 32 rounds, then g = the
+ *                                        shape), the u^(1/alpha) boost (draw 96) for alpha < 1, own polynomial log2 / exp2; a zero sum
+ *                                        gives the uniform distribution over the valid moves.  Correctly rounded f32 only: host (g++
+ *                                        -O2 -ffp-contract=off) and device builds of csrc/az_noise.h give the same bits
+ *                           A captured search graph is keyed on the noise arguments, so one captured with others is never replayed.
+ *                           az_root_noise_eta returns eta for given roots (what a host needs to reconstruct a recorded game's noise)
  *   search   "search_graph" n (default 20, even, 0 = off): n simulation steps per captured hipGraph replay (conv nets) ...
  *            "search_graph_rows" n (default 1024): ... for searches whose expected leaf batch has at most n rows (the arena, the drain
  *                           of a self-play call, single trees: there the host's launch calls set the pace; on big batches the kernels do)
@@ -317,6 +344,10 @@ az_status az_tree_reset(az_tree* t, const uint64_t* root_states);
  * RNG (temp == 0 tie-break) = stream (seed, first_game_id + g, ply = stones on board). */
 az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp, uint64_t seed,
                                   uint64_t first_game_id, float* pi, uint16_t* counts, float* q);
+/* The Dirichlet root noise ("root_noise_eps_e6" above) of n roots at the engine's CURRENT alpha, from the device sampler the searches
+ * run: eta_out [n,7] for root states [n,2] (canonical bitboards) on the streams (seed, game_ids[i], ply = stones of states[i]); the
+ * valid-move mask is the state's, invalid actions get 0.  Independent of eps.  Pointers may be host or device memory. */
+az_status az_root_noise_eta(az_engine* e, int32_t n, uint64_t seed, const uint64_t* game_ids, const uint64_t* states, float* eta_out);
 /* ---- a SHARED tree batch: many host threads, one AsyncMcts (slot) each, one batched search ----
  * The reference's inference_thread (src/async_mcts.rs:117-189) answers the leaf boards of every episode thread with one predict
  * once batch_size of them are waiting.  Here a host that keeps Coach::execute_episode per thread (src/coach.rs:202-205, :241-272)

@@ -117,6 +117,12 @@ class Engine {
         check(az_net_get_class(e_, (int32_t)model_id, &stored, &effective));
         return {stored, effective};
     }
+    // Dirichlet root noise of self-play and the tree calls, never of the arena ("root_noise_eps_e6" / "root_noise_alpha_e6",
+    // include/az_engine.h): prior <- (1 - eps) * prior + eps * eta at the root, eta ~ Dirichlet(alpha).  eps = 0 switches it off
+    void set_root_noise(double eps, double alpha = 1.0) {
+        check(az_set_option(e_, "root_noise_alpha_e6", (int64_t)std::llround(alpha * 1e6)));
+        check(az_set_option(e_, "root_noise_eps_e6", (int64_t)std::llround(eps * 1e6)));
+    }
 
   private:
     az_engine* e_ = nullptr;
@@ -502,7 +508,15 @@ class Coach {
             HistoryEntry h;
             if (!skip_first_play || iteration > start_iteration) {
                 if (selfplay_class != AZ_NET_CLASS_ENGINE) e_.net_set_class(model_id, selfplay_class);
-                h = execute_episodes(model_id, iteration, seed);
+                {
+                    // root noise around the episodes only: on before az_selfplay, off again behind it (also when it throws)
+                    struct NoiseGuard {
+                        Engine& e; double eps, alpha;
+                        NoiseGuard(Engine& e_, double eps_, double alpha_) : e(e_), eps(eps_), alpha(alpha_) { if (eps > 0) e.set_root_noise(eps, alpha); }
+                        ~NoiseGuard() { if (eps > 0) { try { e.set_root_noise(0.0, alpha); } catch (...) {} } }
+                    } guard(e_, root_noise_eps, root_noise_alpha);
+                    h = execute_episodes(model_id, iteration, seed);
+                }
                 if (h.len() > max_queue_length) {                   // keep the newest max_queue_length (:275-277)
                     const size_t drop = h.len() - max_queue_length;
                     h.boards.erase(h.boards.begin(), h.boards.begin() + (std::ptrdiff_t)(drop * 84));
@@ -581,6 +595,9 @@ class Coach {
     // AZ_NET_CLASS_FP8: every iteration pins the playing model to fp8 before az_selfplay and both arena models to bf16 before
     // az_arena (the superseded id's class goes with az_net_free); training is untouched.  ENGINE (default): no class call at all
     az_net_class selfplay_class = AZ_NET_CLASS_ENGINE;
+    // Dirichlet root noise of the episodes (Engine::set_root_noise): set before every az_selfplay and cleared behind it.  eps 0 (the
+    // default): the engine is never asked
+    double root_noise_eps = 0.0, root_noise_alpha = 1.0;
     float update_threshold = 0.f;
     int32_t cpuct = 1;
 
