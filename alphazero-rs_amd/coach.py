@@ -59,6 +59,9 @@ class Coach:
         # Dirichlet root noise of the episodes (Engine.set_root_noise): switched on before every az_selfplay and off again behind it, so
         # nothing else the engine is used for sees it (the arena never does anyway).  eps 0 (the default): the engine is never asked
         self.root_noise_eps, self.root_noise_alpha = 0.0, 1.0
+        # "eval_mirror" (Engine.set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
+        # run under the mirror-canonical function F, so the gate compares like with like.  False (the default): the engine is never asked
+        self.eval_mirror = False
         self.history = collections.deque()
         self.start_iteration = 0
         os.makedirs(self.dir, exist_ok=True)
@@ -149,6 +152,8 @@ class Coach:
         if rank == 0 and not os.path.exists(first):
             self.engine.net_save(model_id, first)                       # the run's initial model: what a restart would load
         free = getattr(self.engine, "net_free", None)
+        if self.eval_mirror:
+            self.engine.set_eval_mirror(True)
         for iteration in range(self.start_iteration, self.start_iteration + self.num_iters):
             t_play = t_train = t_arena = 0.0
             boards, pis, vs = np.zeros((0, 2, 6, 7), np.float32), np.zeros((0, 7), np.float32), np.zeros(0, np.float32)

@@ -138,6 +138,33 @@ LocalCommRegistry g_local_comms{(int64_t)getpid()};
 // (s, pi, z) as one 48-byte tuple: the unit of the episode-batch gather (symmetries are regenerated at the destination)
 struct PackedSample { unsigned long long s0, s1; float pi[7]; float z; };
 static_assert(sizeof(PackedSample) == 48, "48-byte tuples");
+// ---- "eval_mirror" for az_net_predict_states: states[i] <- c(states[i]), flags[i] = mirrored; then pi rows of flagged states reversed ----
+// (the board and its mirror are the same for both games)
+__global__ void k_canonicalise(ulonglong2* __restrict__ states, uint8_t* __restrict__ flags, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t m;
+    const ulonglong2 c = ConnectFour::canonical(states[i], &m);
+    if (m) states[i] = c;
+    flags[i] = (uint8_t)m;
+}
+// one thread per (row, slot) of the [n][8] output rows: slot a < 7 of a flagged row trades places with slot mirror_action(a); slot 7 is v
+__global__ void k_unmirror_rows(float* __restrict__ pi, const uint8_t* __restrict__ flags, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int row = i >> 3, a = i & 7;
+    if (row >= n || !flags[row] || a >= ConnectFour::ACTIONS / 2) return;
+    const size_t lo = (size_t)row * 8 + a, hi = (size_t)row * 8 + ConnectFour::mirror_action(a);
+    const float x = pi[lo];
+    pi[lo] = pi[hi];
+    pi[hi] = x;
+}
+void launch_canonicalise(ulonglong2* states, uint8_t* flags, int n, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_canonicalise, dim3((n + 255) / 256), dim3(256), 0, s, states, flags, n);
+}
+void launch_unmirror_rows(float* pi, const uint8_t* flags, int n, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_unmirror_rows, dim3((n * 8 + 255) / 256), dim3(256), 0, s, pi, flags, n);
+}
+
 __global__ void k_pack_samples(const ulonglong2* st, const float* pi, const float* z, PackedSample* out, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -350,6 +377,7 @@ struct az_engine {
     int search_graph_rows = 1024;   // "search_graph_rows": ... for searches whose expected leaf batch has at most this many rows (the arena, a drain, single trees)
     int fused_search = 1;           // stub / hash nets: the whole search in one launch ("fused_search"; 0 = one launch per simulation)
     int eval_dedup = 1;             // 0 off, 1 conv nets (default), 2 every net (lets the hash fixture exercise the machinery)
+    int eval_mirror = 0;            // "eval_mirror": conv models answer with F (the net on the canonical orientation, pi un-mirrored)
     int eval_cache_log2 = 30;       // entries = 2^log2 (40 B each: 43 GB); 0 = no cache, in-batch de-duplication only
     int eval_cache_max_stones = 42;
     int eval_cache_persist = 0;     // 0: az_selfplay / az_arena / az_tree_get_action_prob start from an empty cache
@@ -462,6 +490,8 @@ az_status fp8_sync_model(az_engine* e, NetModel& m) {
     return AZ_OK;
 }
 
+// "eval_mirror" reaches conv models only: the stub and hash nets are never canonicalised, on any path
+bool mirror_applies(const az_engine* e, const NetModel& net) { return e->eval_mirror != 0 && net.kind == AZ_NET_CONV; }
 bool dedup_applies(const az_engine* e, const NetModel& net) {
     return e->eval_dedup == 2 || (e->eval_dedup == 1 && net.kind == AZ_NET_CONV);
 }
@@ -620,6 +650,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
     const EvalCache ec = cache_for(e, net);
     EvalBatch B[2] = {th.eb, th.eb2};
     B[0].dedup = B[1].dedup = dedup ? 1 : 0;
+    B[0].mirror = B[1].mirror = mirror_applies(e, net) ? 1 : 0;
     B[0].max_n = B[1].max_n = d_max_rows;
     // profile mode brackets every "profile_every"-th simulation step (events cost GPU idle time between dependent kernels)
     const int every = std::max(1, e->profile_every);
@@ -660,7 +691,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
         struct Key {
             const void *th, *conv, *ws, *stream, *root_states, *max_rows, *ec_key, *ec_stat, *log_state, *log_row;
             unsigned long long ec_tag, salt;
-            int kind, rows_hint, rows_typ, S, dedup, block4, log_cap;
+            int kind, rows_hint, rows_typ, S, dedup, mirror, block4, log_cap;
             uint32_t ec_bmask, ec_stones, max_depth, reserve_nodes;
             uint64_t model_gen;
             float cpuct;
@@ -671,6 +702,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
         k.th = &th; k.conv = net.conv; k.ws = net.kind == AZ_NET_CONV ? workspace_for(e, s) : nullptr; k.stream = s; k.root_states = d_root_states;
         k.max_rows = d_max_rows; k.ec_key = ec.key; k.ec_stat = ec.stat; k.log_state = th.d.log_state; k.log_row = th.d.log_row;
         k.ec_tag = ec.tag; k.salt = net.salt; k.kind = net.kind; k.rows_hint = rows_hint; k.rows_typ = rows_typ; k.S = S; k.dedup = dedup ? 1 : 0;
+        k.mirror = B[0].mirror;                    // EvalBatch travels by value too
         k.block4 = th.d.block4; k.log_cap = th.d.log_cap; k.ec_bmask = ec.bmask; k.ec_stones = ec.max_stones; k.max_depth = sp.max_depth; k.cpuct = sp.cpuct_f;
         k.opt = netopt_for(e, net);
         k.noise = th.d.noise;
@@ -965,6 +997,19 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
             }
             return AZ_OK;
         } catch (const HipFail& f) { e->netopt.net_fp8 = 0; return fail_hip(e, f); }
+    }
+    if (is("eval_mirror")) {
+        if (value != 0 && value != 1) return fail(e, AZ_ERR_BAD_ARGUMENT, "eval_mirror must be 0 or 1");
+        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "eval_mirror cannot change while a self-play session is open");
+        if ((int)value == e->eval_mirror) return AZ_OK;
+        e->eval_mirror = (int)value;
+        for (auto& kv : e->nets) {
+            NetModel& m = kv.second;
+            if (m.kind != AZ_NET_CONV) continue;
+            m.cache_tag = 0;                                      // the other class's cached rows (raw N(s) against raw N(c(s))) and captured graphs are never used again
+            m.generation = ++g_model_generation;
+        }
+        return AZ_OK;
     }
     if (is("root_noise_eps_e6") || is("root_noise_alpha_e6")) {
         const bool eps = is("root_noise_eps_e6");
@@ -1304,11 +1349,15 @@ az_status az_net_predict_states(az_engine* e, int32_t model_id, const uint64_t* 
         eb.pi = mem.alloc<float>((size_t)chunk * 8);
         eb.v = mem.alloc<float>(chunk);
         std::vector<float> hp((size_t)chunk * 8);
+        // "eval_mirror": the chunk is canonicalised in place before the forward and its pi rows are un-mirrored after it
+        uint8_t* mflags = mirror_applies(e, *m) ? mem.alloc<uint8_t>(chunk) : nullptr;
         for (int b0 = 0; b0 < B; b0 += chunk) {
             uint32_t nb = (uint32_t)std::min(chunk, B - b0);
             HIPCHK(hipMemcpyAsync(eb.n, &nb, sizeof nb, hipMemcpyHostToDevice, e->stream));
             HIPCHK(hipMemcpyAsync(eb.state, states + 2 * (size_t)b0, (size_t)nb * 16, hipMemcpyDefault, e->stream));
+            if (mflags) launch_canonicalise(eb.state, mflags, (int)nb, e->stream);
             net_forward(e, *m, eb, (int)nb, e->stream);
+            if (mflags) launch_unmirror_rows(eb.pi, mflags, (int)nb, e->stream);
             HIPCHK(hipMemcpyAsync(hp.data(), eb.pi, (size_t)nb * 8 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
             HIPCHK(hipStreamSynchronize(e->stream));
             std::vector<float> packed((size_t)nb * 7);
@@ -1824,6 +1873,7 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
         ss->ec = cache_for(e, *net);
         ss->B[0] = th.eb; ss->B[1] = th.eb2;
         ss->B[0].dedup = ss->B[1].dedup = dedup ? 1 : 0;
+        ss->B[0].mirror = ss->B[1].mirror = mirror_applies(e, *net) ? 1 : 0;
         ss->B[0].max_n = ss->B[1].max_n = gd.counters + 3;
     }
     out = std::move(ss);

@@ -22,6 +22,7 @@
 // ConnectFour is the reference's one implementor (examples/connect_four_lib/connect_four_game.rs:81-238).
 #pragma once
 #include "az_common.h"
+#include "az_mirror.h"
 
 namespace az {
 
@@ -60,12 +61,7 @@ AZ_HD uint32_t c4_ecode(uint64_t mine, uint64_t theirs) {
     if ((mine | theirs) == C4_FULL) return E_DRAW; // ended = DRAW_EPS
     return E_NONE;
 }
-AZ_HD uint64_t c4_mirror(uint64_t b) {
-    uint64_t r = 0;
-#pragma unroll
-    for (int c = 0; c < 7; ++c) r |= ((b >> (c * 7)) & 0x7Full) << ((6 - c) * 7);
-    return r;
-}
+AZ_HD uint64_t c4_mirror(uint64_t b) { return mirror_bits(b); }     // az_mirror.h
 // feature (plane, row-from-top, col) of a canonical state, connect_four_game.rs:219-237 (S8)
 AZ_HD float c4_feature(uint64_t mine, uint64_t theirs, int plane, int r, int c) {
     uint64_t bit = 1ull << (c * 7 + (5 - r));
@@ -76,6 +72,7 @@ AZ_HD uint32_t c4_hash(uint64_t mine, uint64_t theirs) { return (uint32_t)mix64(
 // adding `mine` fills in the mover's stones below it (no carries).  c4_unkey inverts it column by column.
 constexpr uint64_t C4_BOTTOM = 1ull | (1ull << 7) | (1ull << 14) | (1ull << 21) | (1ull << 28) | (1ull << 35) | (1ull << 42);
 AZ_HD uint64_t c4_key(uint64_t mine, uint64_t theirs) { return mine + (mine | theirs) + C4_BOTTOM; }
+static_assert(C4_BOTTOM == MIRROR_BOTTOM, "az_mirror.h restates the pack word of a state");
 AZ_HD void c4_unkey(uint64_t key, uint64_t* mine, uint64_t* theirs) {
     uint64_t m = 0, mask = 0;
 #pragma unroll
@@ -120,6 +117,13 @@ struct ConnectFour {
     }
     AZ_HD static State mirror(State s) { return make_ulonglong2(c4_mirror(s.x), c4_mirror(s.y)); }   // get_symmetries, :205-211
     AZ_HD static int mirror_action(int a) { return ACTIONS - 1 - a; }
+    // c(s) of "eval_mirror": s or mirror(s), whichever packs to the smaller word; *mirrored = 1 when it is the mirror image (az_mirror.h)
+    AZ_HD static State canonical(State s, uint32_t* mirrored) {
+        const MirrorCanon c = mirror_canonical(s.x, s.y);
+        *mirrored = c.mirrored;
+        return make_ulonglong2(c.mine, c.theirs);
+    }
+    AZ_HD static bool mirrored_key(Packed k) { return mirror_is_mirrored_key(k); }     // of a node's own key: no unpack needed
     AZ_HD static float feature(State s, int f) { return c4_feature(s.x, s.y, f / 42, (f % 42) / 7, f % 7); }
 };
 

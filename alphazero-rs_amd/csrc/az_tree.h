@@ -116,6 +116,10 @@ struct EvalBatch {
     // more) clears the batch's keys, so every launch that requests leaves finds its table empty and every launch of a search
     // takes the same arguments -- what lets a run of simulation steps be one hipGraph.
     int32_t dedup;
+    // "eval_mirror" (conv models only): rows, election keys and cache keys are those of the CANONICAL orientation c(s) and hold the raw
+    // net output N(c(s)); each backup un-mirrors pi for its own tree.  Independent of dedup.  Read by the LAUNCHERS only, which pick the
+    // kernels' MIR instantiations (as TreeDev.noise.eps picks NZ): the default instantiations contain none of it.  DESIGN.md 4.1c
+    int32_t mirror;
     unsigned long long* tkey;   // [tmask+1] state key (never 0), 0 = empty
     uint32_t* tuniq;            // [tmask+1] row of the slot's winner
     uint32_t tmask;

@@ -205,10 +205,13 @@ __global__ __launch_bounds__(256) void k_reset_trees(TreeDev t, const uint8_t* f
 //   3. a row of the batch: one atomicAdd per wave (8 trees), rows in lane order inside the wave.
 // Without de-duplication every requesting tree goes straight to 3.  All lanes of the wave that are still alive call
 // this together (the ballots are wave-wide); lanes of trees with nothing to evaluate pass want = false.
-template <class G>
+// MIR ("eval_mirror", EvalBatch.mirror): everything here -- the cache probe, the election and the row -- is about c(s), the canonical
+// orientation; the backup recomputes whether its tree's own s was the mirrored one.  Only the MIR instantiations contain any of it.
+template <class G, bool MIR = false>
 AZ_D uint32_t leaf_request(const EvalBatch& eb, const EvalCache& ec, bool want, typename G::State s, int sub) {
     constexpr int GW = G::GROUP;
     const int lane = (int)(threadIdx.x & 63);
+    if constexpr (MIR) { uint32_t m; s = G::canonical(s, &m); }
     uint32_t src = 0;
     bool hit = false, dup = false, take = want;
     uint32_t tpos = 0;
@@ -368,7 +371,7 @@ AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ul
     return s;
 }
 
-template <class G, bool NZ>
+template <class G, bool NZ, bool MIR>
 __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, EvalCache ec, const ulonglong2* root_states) {
     constexpr int GW = G::GROUP;
     int tid = blockIdx.x * 64 + threadIdx.x;
@@ -376,7 +379,7 @@ __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, Ev
     if (g >= t.G) return;
     TreeHead h = head_load(t, g);
     const typename G::State s = root_prepare_body<G, NZ>(t, h, root_states, g, sub);
-    const uint32_t src = leaf_request<G>(eb, ec, h.leaf_kind == LEAF_ROOT, s, sub);
+    const uint32_t src = leaf_request<G, MIR>(eb, ec, h.leaf_kind == LEAF_ROOT, s, sub);
     if (h.leaf_kind == LEAF_ROOT) h.src = src;
     if (sub == 0) head_store(t, g, h);
 }
@@ -574,7 +577,7 @@ AZ_D void cache_claim_finish(const EvalCache& ec, CacheClaim c, float pv, int su
 // ---- mask/renormalise/store the prior (src/async_mcts.rs:317-353) + backup (:361-370) ----
 // INLINE_PV: the leaf's (pi, v) row is handed over in a register (pv_in: lane a < ACTIONS holds pi[a], lane ACTIONS holds v)
 // instead of being read through TreeHead.src -- the fused search of the fixture nets.
-template <class G, bool INLINE_PV = false, bool NZ = false>
+template <class G, bool INLINE_PV = false, bool NZ = false, bool MIR = false>
 AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const EvalBatch& eb, const EvalCache& ec, int g,
                       int sub, const uint32_t* path, float pv_in = 0.0f) {
     constexpr int GW = G::GROUP;
@@ -591,8 +594,13 @@ AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const 
     if (kind == LEAF_EVAL || kind == LEAF_ROOT) {
         uint4* lp = node_ptr(t, base, leaf);
         const NodeRec lr = node_load(lp);
-        const typename G::State s = G::unpack(node_key(t, base, leaf));
+        const typename G::Packed lkey = node_key(t, base, leaf);
+        const typename G::State s = G::unpack(lkey);
         const uint32_t src = h.src;
+        // "eval_mirror": the row behind src is the raw N(c(s)); whether this tree's s is the mirrored one is recomputed from the leaf's own
+        // key, which the backup loads anyway (TreeHead.src has no free bit: SRC_INDEX is used up at 2^30 cache entries)
+        bool mir = false;
+        if constexpr (MIR) mir = G::mirrored_key(lkey);
         if constexpr (INLINE_PV) {
             pv = pv_in;
         } else if (src & SRC_CACHE) {
@@ -601,10 +609,14 @@ AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const 
             const uint32_t row = (src & SRC_TABLE) ? eb.tuniq[src & SRC_INDEX] : src;
             pv = eb.pi[(size_t)row * 8 + sub];
             publish = !(src & SRC_TABLE) && eb.dedup && ec.key;
-            if (publish) claim = cache_claim_begin<G>(ec, s, sub);
+            if (publish) claim = cache_claim_begin<G>(ec, mir ? G::mirror(s) : s, sub);       // under the key of c(s), with the raw row
         }
         float p = sub < NA ? pv : 0.0f;
         const float v = gshflf<GW>(pv, NA);
+        if constexpr (MIR) {                                        // F(s).pi[a] = N(c(s)).pi[mirror_action(a)]; pv stays raw for the cache
+            const float pm = gshflf<GW>(pv, G::mirror_action(sub < NA ? sub : 0));
+            if (mir && sub < NA) p = pm;
+        }
         if (t.log_cap > 0) {
             uint32_t n = h.log_len;
             if (n < (uint32_t)t.log_cap) {
@@ -714,7 +726,7 @@ AZ_D void clear_election_keys(const EvalBatch& eb) {
     const uint32_t total = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= eb.tmask; i += total) eb.tkey[i] = 0ull;
 }
-template <class G, bool NZ>
+template <class G, bool NZ, bool MIR>
 __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCache ec) {
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * 64 + threadIdx.x;
@@ -724,7 +736,7 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
     if (g >= t.G) return;
     TreeHead h = head_load(t, g);
     const PathRegs pth = path_load(t, g, sub);
-    backup_body<G, false, NZ>(t, h, pth, eb, ec, g, sub, t.path + (size_t)g * PATH_CAP);
+    backup_body<G, false, NZ, MIR>(t, h, pth, eb, ec, g, sub, t.path + (size_t)g * PATH_CAP);
     h.leaf_kind = LEAF_NONE;
     if (sub == 0) head_store(t, g, h);
 }
@@ -732,7 +744,7 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
 // backup of simulation i and select of simulation i+1 in one launch: both belong to the same 8 lanes of the same tree and
 // nothing else touches that tree in between.  The leaf of i+1 goes into the OTHER eval batch (eb_next; its count was
 // zeroed by the previous launch, this one zeroes eb_prev's), so the two ping-pong.
-template <class G, bool STAMP, bool NZ>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
+template <class G, bool STAMP, bool NZ, bool MIR>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
 __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec,
                                                        SearchParams sp, unsigned long long* dbg) {
     constexpr int GW = G::GROUP;
@@ -747,7 +759,7 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     TreeHead h = head_load(t, g);
     PathRegs pth = path_load(t, g, sub);
     AZ_TSTAMP(1);
-    backup_body<G, false, NZ>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * PATH_CAP);
+    backup_body<G, false, NZ, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * PATH_CAP);
     AZ_TSTAMP(2);
     // the counters this tree's other lanes just wrote are read by the selection below
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -756,7 +768,7 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     AZ_TSTAMP(3);
     const typename G::State leaf_s = select_body<G>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP);
     AZ_TSTAMP(4);
-    const uint32_t src = leaf_request<G>(eb_next, ec, h.leaf_kind == LEAF_EVAL, leaf_s, sub);
+    const uint32_t src = leaf_request<G, MIR>(eb_next, ec, h.leaf_kind == LEAF_EVAL, leaf_s, sub);
     AZ_TSTAMP(5);
     if (h.leaf_kind == LEAF_EVAL) h.src = src;
     if (sub == 0) head_store(t, g, h);
@@ -788,7 +800,7 @@ AZ_D void group_memory_sync() {
 struct ThreadRegs { uint32_t leaf, leaf_kind; float leaf_val; uint32_t src, path_len; };
 AZ_D void thread_to_head(TreeHead& h, const ThreadRegs& r) { h.leaf = r.leaf; h.leaf_kind = r.leaf_kind; h.leaf_val = r.leaf_val; h.src = r.src; h.path_len = r.path_len; }
 AZ_D ThreadRegs head_to_thread(const TreeHead& h) { return ThreadRegs{h.leaf, h.leaf_kind, h.leaf_val, h.src, h.path_len}; }
-template <class G, bool NZ>
+template <class G, bool NZ, bool MIR>
 __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp, int first, int last) {
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * 64 + threadIdx.x;
@@ -806,7 +818,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
         if (first) {
             PathRegs pth{0u, 0u};
             thread_to_head(h, root_req);
-            backup_body<G, false, true>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * T * PATH_CAP);
+            backup_body<G, false, true, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * T * PATH_CAP);
             tt0 = T;
         }
     }
@@ -821,7 +833,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
             pth = PathRegs{tl->path16[sub], tl->path16[8 + sub]};
         }
         thread_to_head(h, r);
-        backup_body<G>(t, h, pth, eb_prev, ec, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP);
+        backup_body<G, false, false, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP);
     }
     h.leaf_kind = LEAF_NONE;
     for (int tt = 0; tt < T; ++tt) {                        // selections in thread order
@@ -836,7 +848,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
             leaf_s = select_body<G, true>(t, h, pth, sp, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP, &abandoned);
             want = h.leaf_kind == LEAF_EVAL;
         }
-        const uint32_t src = leaf_request<G>(eb_next, ec, want, leaf_s, sub);      // every wave calls it T times (wave-wide ballots inside)
+        const uint32_t src = leaf_request<G, MIR>(eb_next, ec, want, leaf_s, sub);      // every wave calls it T times (wave-wide ballots inside)
         if (want) h.src = src;
         r = head_to_thread(h);
         if (last) r.leaf_kind = LEAF_NONE;
@@ -1144,7 +1156,7 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
 // net's rows alone -- the schedule decides when a row is evaluated, never what it is.
 //   gd.sims[g]   simulations of the current move done so far; -1 = the move's root is not prepared yet
 //   first        the first launch behind a forward: eb_prev holds that forward's rows (parked trees back up; its table is cleared)
-template <class G, bool NZ>
+template <class G, bool NZ, bool MIR>
 __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp,
                                                     SelfplayMoveParams mp, int num_sims, int first, int max_iters) {
     constexpr int GW = G::GROUP;
@@ -1169,7 +1181,7 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
             if (h.leaf_kind != LEAF_NONE) {                                    // the pending leaf: store its prior, back its value up
                 const bool was_sim = h.leaf_kind != LEAF_ROOT;
                 group_memory_sync();
-                backup_body<G, false, NZ>(t, h, pth, eb_prev, ec, g, sub, path);
+                backup_body<G, false, NZ, MIR>(t, h, pth, eb_prev, ec, g, sub, path);
                 h.leaf_kind = LEAF_NONE;
                 if (was_sim) ++sims;
                 continue;
@@ -1193,7 +1205,7 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
             if (h.leaf_kind == LEAF_NONE) ++sims;                              // an error cut the simulation short (flag set): it still counts
         }
     }
-    const uint32_t src = leaf_request<G>(eb_next, ec, want, leaf_s, sub);
+    const uint32_t src = leaf_request<G, MIR>(eb_next, ec, want, leaf_s, sub);
     if (want) h.src = src;
     if (sub == 0) { head_store(t, g, h); gd.sims[g] = sims; }
     path_store(t, g, sub, pth);
@@ -1303,6 +1315,12 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
         if ((t_).noise.eps != 0.0f) { constexpr bool NZ = true; AZ_FOR_GAME((t_).game, __VA_ARGS__); } \
         else { constexpr bool NZ = false; AZ_FOR_GAME((t_).game, __VA_ARGS__); }         \
     } while (0)
+// ... and per "eval_mirror" setting of the leaf batch the launch requests into / backs up from (both batches of a search carry the same)
+#define AZ_FOR_GAME_NZ_MIR(t_, eb_, ...)                                                 \
+    do {                                                                                 \
+        if ((eb_).mirror) { constexpr bool MIR = true; AZ_FOR_GAME_NZ(t_, __VA_ARGS__); } \
+        else { constexpr bool MIR = false; AZ_FOR_GAME_NZ(t_, __VA_ARGS__); }            \
+    } while (0)
 static inline int group_blocks(int G) { return (G * BLOCK_SLOTS + 63) / 64; }
 #ifdef AZ_DIAG
 // diagnostic library only: the PUCT term of best_child (src/node.rs:352-356) for n (child counter, prior bits, parent N) triples, as the
@@ -1348,10 +1366,10 @@ void launch_reset_trees(const TreeDev& t, const uint8_t* flags, hipStream_t s, c
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_reset_trees<TG>, dim3(t.G), dim3(256), 0, s, t, flags, const_cast<uint8_t*>(flags), roots));
 }
 void launch_root_prepare(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, const ulonglong2* root_states, hipStream_t s) {
-    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_root_prepare<TG, NZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec, root_states));
+    AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_root_prepare<TG, NZ, MIR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec, root_states));
 }
 void launch_backup(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, hipStream_t s) {
-    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_backup<TG, NZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec));
+    AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_backup<TG, NZ, MIR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec));
 }
 void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                           hipStream_t s) {
@@ -1359,16 +1377,16 @@ void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const Eval
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
 #ifdef AZ_DIAG
     if (g_tree_dbg && t.G * 8 / 64 <= TREE_DBG_WAVES) {
-        AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_backup_select<TG, true, NZ>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg));
+        AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg));
         return;
     }
 #endif
-    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_backup_select<TG, false, NZ>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr));
+    AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr));
 }
 void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                     int first, int last, hipStream_t s) {
     // one wave per workgroup: leaf_request is called T times per launch and its one-atomic-per-workgroup path keeps state in LDS
-    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_step_mt<TG, NZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last));
+    AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_step_mt<TG, NZ, MIR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last));
 }
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s) {
@@ -1406,7 +1424,7 @@ void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s) {
     const bool four = t.block4 && (t.G * 8) % 256 == 0;
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
-    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_async_step<TG, NZ>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters));
+    AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_async_step<TG, NZ, MIR>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters));
 }
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s) {
     hipLaunchKernelGGL(k_sync_active, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gd);

@@ -307,6 +307,13 @@ class Engine:
         conv-net forwards on the FP8 (e4m3) matrix path -- a numerics class of its own, default off."""
         self._check(self._lib.az_set_option(self._h, key.encode(), int(value)))
 
+    def set_eval_mirror(self, on):
+        """The opt-in "eval_mirror" (include/az_engine.h, default off): every forward of a conv model of this engine is taken on the
+        canonical one of the position and its left-right mirror image, and pi is un-mirrored for the asker -- the net's function becomes
+        exactly mirror-equivariant, and a position and its mirror share one batch row and one evaluation-cache entry.  A numerics class
+        of its own, like "net_fp8"; refused while a self-play session is open."""
+        self.set_option("eval_mirror", 1 if on else 0)
+
     def set_root_noise(self, eps, alpha=1.0):
         """Dirichlet root noise of self-play and the tree calls (never the arena): prior <- (1 - eps) * prior + eps * eta,
         eta ~ Dirichlet(alpha) over the root's valid moves, once per get_action_prob.  eps = 0 switches it off (the default);

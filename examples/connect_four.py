@@ -28,6 +28,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=10)        # connect_four_net.py:13
     ap.add_argument("--selfplay-fp8", action="store_true")   # episodes in the fp8 class, the arena gate in bf16 (Coach.selfplay_class)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
+    ap.add_argument("--eval-mirror", action="store_true")    # mirror-canonical leaf evaluation for the whole loop (Coach.eval_mirror)
     a = ap.parse_args()
     e = azeng.Engine(device=0, max_batch=max(a.slots, a.arena, 128), net_channels=a.channels)
     e.net_init_random(0, a.seed)
@@ -50,6 +51,7 @@ def main():
                         trainer=Trainer(channels=a.channels, epochs=a.epochs) if a.trainer == "torch" else None)
     if a.selfplay_fp8:
         coach.selfplay_class = azeng.NET_CLASS_FP8
+    coach.eval_mirror = a.eval_mirror
     if a.root_noise:
         eps, _, alpha = a.root_noise.partition(",")
         coach.root_noise_eps, coach.root_noise_alpha = float(eps), float(alpha) if alpha else 1.0

@@ -230,6 +230,26 @@ const char* az_last_error(const az_engine* e);
  *   leaf de-duplication (bit-exact: a row's (pi, v) depends on its state alone; the reference's per-tree analogue is `seen`,
  *   src/node.rs:282-289)
  *            "eval_dedup"   0 off / 1 conv nets (default) / 2 every net: each distinct state of a leaf batch is evaluated once
+ *            "eval_mirror"  0 (default) / 1: mirror-canonical leaf evaluation, a numerics class of its own like "net_fp8".  The board is
+ *                           left-right symmetric, a conv net is not mirror-equivariant.  With 1 every forward of a CONV model of this
+ *                           engine (search, self-play, sessions, the arena, shared tree batches, az_net_predict*) answers with F
+ *                           instead of the raw net N:
+ *                             c(s)       = s or mirror(s), whichever has the smaller Game::pack word as an unsigned 64-bit integer; on
+ *                                          equal words (a self-symmetric position, the empty board included) s itself, "not mirrored"
+ *                             F(s).v     = N(c(s)).v
+ *                             F(s).pi[a] = N(c(s)).pi[a] when s is not mirrored, N(c(s)).pi[mirror_action(a)] when it is
+ *                           Nothing else is touched: masking, renormalisation, root noise and the stored priors run on F(s) exactly as
+ *                           they run on N(s) with 0.  Bit for bit, F(mirror(s)).pi is F(s).pi reversed and v is equal.
+ *                           The leaf batch, the election table and the evaluation cache carry c(s) and the RAW N(c(s)): a position and
+ *                           its mirror image share one row and one cache entry.  The eval log (record_evals, az_*_get_evals) carries
+ *                           the tree's own s with F(s), so replay parity against an unchanged reference keeps working.
+ *                           F depends on the state alone: not on "eval_dedup", the cache, the batch, the schedule (lock-step,
+ *                           "selfplay_async", sessions, num_sim_threads, shared batches) or any bit-identical kernel option.  It
+ *                           composes with the fp8 class (canonicalisation happens before featurisation) and is the same for both
+ *                           games.  Stub and hash models are never affected, on any path (fused search, launch per simulation,
+ *                           "eval_dedup" = 2).  Refused (AZ_ERR_BAD_ARGUMENT) while a self-play session is open and for other values.
+ *                           A real change gives every conv model a new cache tag and generation: no cached row and no captured search
+ *                           graph of the other class is ever reused.  With 0 every output and counter is bit for bit what it was
  *            "eval_cache_log2"  upper bound of log2 entries of the engine's evaluation cache (default 30, 0 = none, 10..30; 40 bytes per
  *                           entry).  A call (or session) allocates and clears only what ITS games can fill (4 x its bound on
  *                           inserted rows, at least 2^10): a 1-tree, 25-simulation call touches 40 KB, a call of 8192 episodes

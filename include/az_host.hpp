@@ -119,6 +119,8 @@ class Engine {
     }
     // Dirichlet root noise of self-play and the tree calls, never of the arena ("root_noise_eps_e6" / "root_noise_alpha_e6",
     // include/az_engine.h): prior <- (1 - eps) * prior + eps * eta at the root, eta ~ Dirichlet(alpha).  eps = 0 switches it off
+    // "eval_mirror" (include/az_engine.h, default off): conv models answer on the canonical orientation of a position, pi un-mirrored
+    void set_eval_mirror(bool on) { check(az_set_option(e_, "eval_mirror", on ? 1 : 0)); }
     void set_root_noise(double eps, double alpha = 1.0) {
         check(az_set_option(e_, "root_noise_alpha_e6", (int64_t)std::llround(alpha * 1e6)));
         check(az_set_option(e_, "root_noise_eps_e6", (int64_t)std::llround(eps * 1e6)));
@@ -504,6 +506,7 @@ class Coach {
             const std::string w = dir_ + "/" + std::to_string(model_id) + ".aznet";
             if (rank_ == 0 && !std::filesystem::exists(w)) e_.check(az_net_save(e_.raw(), (int32_t)model_id, w.c_str()));
         }
+        if (eval_mirror) e_.set_eval_mirror(true);
         for (size_t iteration = start_iteration; iteration < start_iteration + num_iters; ++iteration) {
             HistoryEntry h;
             if (!skip_first_play || iteration > start_iteration) {
@@ -598,6 +601,9 @@ class Coach {
     // Dirichlet root noise of the episodes (Engine::set_root_noise): set before every az_selfplay and cleared behind it.  eps 0 (the
     // default): the engine is never asked
     double root_noise_eps = 0.0, root_noise_alpha = 1.0;
+    // "eval_mirror" (Engine::set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
+    // run under the mirror-canonical function, so the gate compares like with like.  false (the default): the engine is never asked
+    bool eval_mirror = false;
     float update_threshold = 0.f;
     int32_t cpuct = 1;
 
