@@ -12,7 +12,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB = os.path.join(PKG_DIR, "libaz_engine.so")
 # The diagnostic twin: the same sources with -DAZ_DIAG, which adds the superseded kernel generations (csrc/az_net_diag.inc), forced
-# tiles, clock-stamp builds and the timing ablations that compute WRONG results.  tools/ and the kernel-family bit-identity tests
+# tiles and clock-stamp builds (every one bit-identical to the shipped kernels).  tools/ and the kernel-family bit-identity tests
 # load it (engine.Engine(diag=True)); the shipped library above does not contain any of it and refuses those option values.
 LIB_DIAG = os.path.join(PKG_DIR, "libaz_engine_diag.so")
 SOURCES = ["az_tree.hip", "az_net.hip", "az_train.hip", "az_engine.hip"]

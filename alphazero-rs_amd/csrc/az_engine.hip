@@ -1060,16 +1060,15 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     if (is("train_lr_e9") && value > 0) { e->hyper.lr = (float)((double)value * 1e-9); return AZ_OK; }
     if (is("train_dropout_e6") && value >= 0 && value < 1000000) { e->hyper.dropout = (float)((double)value * 1e-6); return AZ_OK; }
 #ifdef AZ_DIAG
-    // ---- libaz_engine_diag.so only: superseded kernel generations, forced tiles, clock-stamp builds, timing ablations (WRONG results) ----
+    // ---- libaz_engine_diag.so only: superseded kernel generations, forced tiles, clock-stamp builds (every one bit-identical to the shipped kernels) ----
     NetOptions& o = e->netopt;
     if (is("conv2_table") && value == 2) { o.conv2_table = 2; return AZ_OK; }
-    if (is("gemm_variant") && (value == 0 || value == 1 || value == 2 || value == 3 || value == 5 || (value >= 11 && value <= 17))) { o.gemm_variant = (int)value; return AZ_OK; }
+    if (is("gemm_variant") && (value == 0 || value == 1 || value == 2 || value == 3 || value == 5 || value == 13)) { o.gemm_variant = (int)value; return AZ_OK; }
     if (is("fc_ring") && value >= 0 && value <= 3) { o.fc_ring = (int)value; return AZ_OK; }
     if (is("ring_tile") && value >= 0 && value < 60000) { const int l = (int)(value / 10000); if (l >= 3 && l <= 5) o.ring_tile[l] = (int)(value % 10000); return AZ_OK; }
     if (is("conv3_ring") && value >= 0 && value <= 3) { o.conv3_ring = (int)value; return AZ_OK; }
     if (is("conv2_pipe") && (value == 0 || value == 1)) { o.conv2_pipe = (int)value; return AZ_OK; }
-    if (is("conv3_pipe") && ((value >= 0 && value <= 3) || (value >= 9 && value <= 16))) { o.conv3_pipe = (int)value; return AZ_OK; }
-    if (is("conv3_pp") && (value == 0 || value == 1 || (value >= 16 && value <= 40))) { o.conv3_pp = (int)value; return AZ_OK; }
+    if (is("conv3_pipe") && value >= 0 && value <= 3) { o.conv3_pipe = (int)value; return AZ_OK; }
     if (is("conv1_table") && (value == 0 || value == 1)) { o.conv1_table = (int)value; return AZ_OK; }
     if (is("conv4_big") && value >= 0 && value <= 2) { o.conv4_big = (int)value; return AZ_OK; }
     if (is("tree_stamps") && (value == 0 || value == 1)) { return tree_set_stamps((int)value) ? AZ_OK : fail(e, AZ_ERR_HIP, "tree_set_stamps"); }
@@ -1105,23 +1104,6 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
         e->err = out;
         return AZ_OK;
     }
-    if (is("print_pp_stamps")) {
-        // conv3_pp 36 / 37: per-segment cycle sums of waves 0 (group 0) and 4 (group 1) of the first 128 workgroups, median over blocks
-        std::vector<unsigned long long> st(2048);
-        if (!e->ws[0] || !netws_read_clock_stamps(e->ws[0], st.data())) return fail(e, AZ_ERR_BAD_ARGUMENT, "no workspace");
-        std::string out;
-        for (int i = 0; i < 16; ++i) {
-            std::vector<unsigned long long> v;
-            for (int b = 0; b < 128; ++b) if (st[16 * b + 7]) v.push_back(st[16 * b + i]);
-            if (v.empty()) return fail(e, AZ_ERR_BAD_ARGUMENT, "no stamps (run a forward with conv3_pp 36 first)");
-            std::sort(v.begin(), v.end());
-            char buf[64];
-            std::snprintf(buf, sizeof buf, "%s%llu", i ? " " : "", v[v.size() / 2]);
-            out += buf;
-        }
-        e->err = out;
-        return AZ_OK;
-    }
     if (is("print_tree_stamps")) {
         // "tree_stamps" = 1: cycles per phase of the last k_backup_select launch, median over its waves:
         // load head+path | backup | wait for its stores | select | leaf request | store head+path | whole kernel
@@ -1143,13 +1125,13 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
 #else
     // the diagnostic keys exist in libaz_engine_diag.so only; their DEFAULT value is accepted here so that a caller resetting them is not an error
     static const struct { const char* k; int64_t dflt; } diag_keys[] = {{"gemm_variant", 5}, {"fc_ring", 1}, {"conv3_ring", 0}, {"conv2_pipe", 1},
-                                                                         {"conv3_pipe", 1}, {"conv1_table", 1}, {"conv4_big", 0}, {"tree_stamps", 0}, {"conv3_pp", 0}};
-    bool diag_key = is("print_clock_stamps") || is("print_seg_stamps") || is("print_pp_stamps") || is("print_tree_stamps") || (is("conv2_table") && value == 2);
+                                                                         {"conv3_pipe", 1}, {"conv1_table", 1}, {"conv4_big", 0}, {"tree_stamps", 0}};
+    bool diag_key = is("print_clock_stamps") || is("print_seg_stamps") || is("print_tree_stamps") || (is("conv2_table") && value == 2);
     if (is("ring_tile")) { if (value >= 30000 && value < 60000 && value % 10000 == 0) return AZ_OK; diag_key = true; }
     for (const auto& dk : diag_keys)
         if (is(dk.k)) { if (value == dk.dflt) return AZ_OK; diag_key = true; }
     if (diag_key)
-        return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(key) + ": diagnostic option or value (superseded kernels, timing ablations and clock stamps live in libaz_engine_diag.so)");
+        return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(key) + ": diagnostic option or value (superseded kernels and clock stamps live in libaz_engine_diag.so)");
 #endif
     return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("unknown option or value: ") + key);
 }

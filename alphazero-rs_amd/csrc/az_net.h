@@ -67,8 +67,9 @@ void netws_resolve_profile(NetWorkspace* ws, NetProfile* prof);
 bool netws_conv3_accounting(NetWorkspace* ws, unsigned long long out[2], bool reset);
 // Kernel-set switches of the conv net (az_set_option).  They live in the az_engine that was handed to az_set_option and are passed
 // down with every forward: one engine's option never changes another engine's results.  The shipped library (built without
-// -DAZ_DIAG) only honours conv2_table 0 / 1 and conv3_small 0 / 1; everything else selects superseded kernel generations, forced tiles,
-// clock-stamp builds or timing ablations that compute WRONG results, which are compiled into libaz_engine_diag.so only (tools/).
+// -DAZ_DIAG) only honours conv2_table 0 / 1 and conv3_small 0 / 1; everything else selects superseded kernel generations, forced tiles
+// or clock-stamp builds, which are compiled into libaz_engine_diag.so only (tools/).  No option value of either library computes a
+// wrong answer: every diagnostic kernel is bit-identical to the shipped one of its layer.
 struct NetOptions {
     int conv2_table = 1;    // 1: conv1 + conv2 as table gathers (k_conv2_table_x); 0: conv2 as the MFMA implicit GEMM (same function, other rounding)
     int conv3_small = 1;    // conv3 of a small expected batch on the 4-stage LDS-DMA ring (bit-identical)
@@ -85,15 +86,12 @@ struct NetOptions {
     int narrow_rows = 32;   // conv3 / conv4 / fc1 / fc2 of a batch of at most this many rows (x 2 for conv4, x 4 for the FCs) run as the register-fed
                             // skinny GEMM (k_gemm_skinny), decided on the device from the exact row count; 0 = never (bit-identical)
     // ---- diagnostic library only ----
-    int conv3_pp = 0;       // 1: conv3 as the ping-pong kernel (k_conv3_pp: ONE 8-wave workgroup per CU, 12 boards x 256 channels, the two waves of a
-                            // SIMD alternating LOAD and COMPUTE slots; bit-identical; measured in round 4, not faster: profiles/README.md); 16..40: its
-                            // timing ablations / schedule variants (WRONG results)
     int gemm_variant = 5;   // 0 128x128 register-staged tiles everywhere; 1 / 2 256x256 LDS-DMA tiles; 3 conv2 image-resident, one 8-wave
-                            // workgroup per CU; 5 the shipped set; 11-17 timing ablations of variant 2 (WRONG results)
+                            // workgroup per CU; 5 the shipped set; 13 variant 2 with clock stamps (print_clock_stamps)
     int conv1_table = 1;    // conv2 as a GEMM gathers its image from the conv1 table (1) / runs k_conv1 into act1 (0)
     int conv2_pipe = 1;     // conv2 as a GEMM: k_conv_same_pipe (1) / round 1's k_conv_img2 (0)
-    int conv3_pipe = 1;     // conv3: 1 k_conv_valid_pipe with interleaved fragment reads; 2 without; 0 round 1's kernel; 3 clock stamps;
-                            // 9-15 its timing ladder, 16 the bound of a register-fed weight operand (WRONG results)
+    int conv3_pipe = 1;     // conv3: 1 the shipped choice; 2 k_conv_valid_pipe without interleaved fragment reads; 3 with them and per-segment clock
+                            // stamps (print_seg_stamps); 0 round 1's kernel (k_conv_valid_img2)
     int conv3_ring = 0;     // force conv3 onto the ring (1 / 2: 128-row tiles with 2 / 4 stages, 3: device-picked tile)
     int conv4_big = 0;      // conv4 on the 256x256 kernel (1 always, 2 from 4096 rows)
     int fc_ring = 1;        // 1 ring with the tile picked on the device; 2 picked on the host; 3 plain 128-row ring; 0 register-staged tiles

@@ -295,7 +295,7 @@ struct GemmDesc {
     int cin;                // channels per tap
     int K, N;
     int relu;
-    unsigned long long* dbg;   // diagnostic builds only (ABLATE == 3): per-block {shader cycles, 100 MHz ticks}
+    unsigned long long* dbg;   // the diagnostic library's clock-stamp builds only: per-block cycle counts (netws_read_clock_stamps)
     const ulonglong2* states;  // k_conv_img2<.., true> only: the batch's canonical bitboards (A is then the conv1 table)
     int out_f16;               // k_gemm_mfma only: store the raw f32 accumulators as f16 (no bias, no ReLU): the conv2 table build
     // device-side hand-over between the small-batch kernel and the tiled kernels of a layer (both may be launched when the host's
@@ -306,7 +306,8 @@ struct GemmDesc {
                                // families of a layer are both launched when the host's estimate cannot tell which one the batch needs
     unsigned long long* acct;  // k_conv3_auto: {rows, working launches} it has processed (device counters of the workspace)
     const uint16_t* c3tab;     // conv_valid_tile<.., PLANES>: the LDS image's cell maps (Conv3Tables, built by convnet_prepare's workspace)
-    const uint16_t* Wp;        // k_conv3_pp: the layer's weights packed as LDS stage images (ConvNet::wp3), nullptr = not available
+    const uint16_t* unused_;   // always nullptr (the removed ping-pong conv3 kernel's weights): the slot keeps the kernel-argument offsets of the
+                               // fields below, and with them the code of every kernel that reads them, as they were
     const uint16_t* Wr;        // gemm_ring_body: the layer's weights as the ring's LDS stage images [N / 128][K / 64][128 rows][128 B] in K-step order
                                // (ConvNet::wr: one stage = 16 KiB of CONSECUTIVE global bytes instead of 128 rows K * 2 bytes apart), nullptr = read W
     const uint16_t* Wf;        // conv_valid_tile<.., WREG>: conv3's weights in MFMA fragment order (ConvNet::wf3), nullptr = not available
@@ -681,36 +682,11 @@ __global__ __launch_bounds__(256, (NS <= 2 ? 2 : 1)) void k_gemm_ring_f8(const G
     }
 }
 
-// ---- 256x256 tile variant for the big layers (conv2, conv3): LDS-DMA staging ------------------------------
-// 8 waves (2 x 4), each wave a 128(m) x 64(n) sub-tile = 8 x 4 accumulators of v_mfma_f32_16x16x32_bf16.
-// Both operands go global -> LDS with global_load_lds_dwordx4 (no VGPR staging, no ds_write): one wave-instruction
-// writes 1 KiB = 8 tile rows x 128 B linearly, so the XOR swizzle (chunk c of row r at slot c ^ (r&7)) is applied
-// to the per-lane SOURCE address and again on the fragment reads.  Two 64 KiB LDS buffers; the next K-step's DMA is
-// issued before this K-step's MFMAs and retired by vmcnt(0) + barrier at the end of the step.
-[[maybe_unused]] constexpr int HBM_ = 256;
-constexpr int HBN_ = 256;
-
-
-// ---- conv2 as an IMAGE-RESIDENT implicit GEMM ----------------------------------------------------------------
-// The 9 filter taps of one 64-channel block read overlapping shifted windows of the same activations.  With an M tile
-// of 6 whole boards (252 output rows) the 64-channel slice of those boards is 6 x 42 x 128 B = 31.5 KiB: it is DMA'd
-// into LDS ONCE per channel block (double-buffered, landing during the previous block's taps) and the A fragments of
-// tap (ky,kx) are read from it at row m + (ky-1)*7 + (kx-1); out-of-board taps read a zero row ('same' padding).
-// Only the weight tile (32 KiB) still streams every K-step, so L2->LDS traffic falls from 64 KiB to 35.5 KiB per
-// K-step.  Same K order (channel block outer, tap inner) and per-row accumulation order as the other kernels.
-constexpr int IMG_NB = 6, IMG_ROWS = IMG_NB * 42, IMG_ZERO_ROW = 252;
-
-
-// ---- conv2 image-resident, TWO independent workgroups per CU ---------------------------------------------------------
-// k_conv_img's 8 waves share one barrier, so the two waves of every SIMD run in lockstep: both in their MFMA clusters
-// (contending for the matrix pipe), then both parked at the wait / barrier (pipe idle; SQ_WAIT_INST_ANY 42 %,
-// SQ_WAIT_ANY 38 % of wave cycles).  Here the same per-wave work (128 rows x 64 columns, 8 x 4 accumulators) is packaged
-// as workgroups of 4 waves -- tile = 6 boards x 128 channels, LDS = one image buffer (32 KiB) + two weight buffers
-// (16 KiB each) = 64 KiB -- so two workgroups fit a CU and every SIMD holds one wave of each: their barriers are
-// independent and their phases drift apart.  The price is a single image buffer (the image switch every 9 K-steps is
-// exposed inside a workgroup and covered by the other one).  Same K order: bit-identical.
-constexpr int HBN2_ = 128;
-
+constexpr int HBN_ = 256;          // conv2 as a GEMM needs the layer's width to be a multiple of this (the 256-column tiles' width)
+constexpr int HBN2_ = 128;         // columns of a k_conv_same_pipe tile (6 boards x 128 channels, two workgroups per CU)
+constexpr int IMG_NB = 6;          // boards of a conv2 image tile: 252 output rows, a 31.5 KiB LDS image per 64-channel block
+constexpr int IMG_ROWS = IMG_NB * 42;   // image rows of that tile
+constexpr int IMG_ZERO_ROW = 252;  // the all-zero LDS row that out-of-board taps read ('same' padding)
 
 // ---- k_conv_img2 with the LDS-DMA issued from inline asm and a software-pipelined K-step (conv2 as the MFMA GEMM, "conv2_table" = 0) --
 // Same tile, LDS layout, DMA maps and K order as k_conv_img2 (bit-identical).  What changes is what k_conv_valid_pipe changed for conv3:
@@ -908,242 +884,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_same_pipe(const GemmDesc d) {
     }
 }
 
-// ---- 'valid' 3x3 convs (conv3: [6][7][C] -> [4][5][C], conv4: [4][5][C] -> [2][3][C]) image-resident, two 4-wave
-// workgroups per CU ---------------------------------------------------------------------------------------------------
-// The lockstep argument of k_conv_img2 for the 'valid' convs.  Tile = NB boards (NB*OH*OW output rows, padded to 128 or
-// 256) x NCOL channels; every wave owns 128 rows x 64 columns (8 x 4 accumulators, 64 MFMAs per K-step):
-//   conv3: NB = 12 (240 of 256 rows), NCOL = 128, waves 2 x 2; LDS = 63 KiB image + 16 KiB weights
-//   (conv4: NB = 19 (114 of 128 rows), NCOL = 256, waves 1 x 4, 47.5 KiB image + 32 KiB weights -- measured neutral, not used)
-// i.e. 80 KiB = the boards' input image (one buffer) + ONE weight buffer: both 32-deep halves of the step's weight
-// fragments are read into registers first, a barrier behind those reads frees the buffer, and the next weight tile is
-// DMA'd under the rest of the step.  A 'valid' conv needs no padding logic: output (y, x) of a board reads image row
-// (y+ky)*IW + (x+kx).  Same K order: bit-identical.
+// ---- conv3 image-resident: the constants of conv_valid_tile --------------------------------------------------------------------------
 // The PLANES layout of the conv3 LDS image (conv_valid_tile<.., true>), see Conv3Tables
 constexpr int C3_PLANE_BYTES = 32768;         // one chunk-parity plane: 512 cells of 64 B
 constexpr int C3_TAB_INV = 512;               // uint16 per LDS row cell: source image row | swizzle << 10
 constexpr int C3_TAB_RD = 9 * 2 * 16 * 8;     // uint16 per (tap, wave row, fragment row, row tile): the cell's byte offset in its plane
 constexpr int WF3_STEP = 4096;                // bf16 per (64-channel group, K-step) of ConvNet::wf3 (conv_valid_tile<.., WREG>): 8 KiB
 constexpr int WF3_PAD = 1;                    // K-steps of padding: the kernel requests one step past the last and never uses it
-constexpr int C3_NB = 12;     // (conv4 as <L, 19, 4, 5, 4> is bit-identical too and was measured neutral: it stays on k_gemm256)
-
-// ---- the same tile with the LDS-DMA issued from inline asm and a software-pipelined K-step ---------------------------
-// hipcc models `__builtin_amdgcn_global_load_lds` as a FLAT access that may touch LDS and global memory at once: while one
-// is pending EVERY s_waitcnt it inserts is vmcnt(0) / lgkmcnt(0), so in k_conv_valid_img2 each MFMA cluster waits for the
-// fragment reads issued just before it (meant for the NEXT cluster) -- three exposed LDS latencies per K-step.  Issued
-// from inline asm (saddr form: uniform base in SGPRs + one loop-invariant 32-bit offset VGPR per piece, LDS base in M0)
-// the compiler does not see the DMA, its own lgkmcnt waits become counted, and the waits for the DMA are the explicit
-// vmcnt(0) + barrier pairs below.  K-step schedule (fbX / faX of step k were requested under step k-1's last cluster):
-//   reads fbY, faY(ks0) | MFMA fbX x faX(ks0) | lgkmcnt(0), barrier: W(k) is in registers everywhere | DMA W(k+1)
-//   reads faX(ks1) | MFMA fbX x faY(ks0) | reads faY(ks1) | MFMA fbY x faX(ks1) | vmcnt(0), barrier: W(k+1) landed
-//   reads fbX, faX(ks0) of step k+1 | MFMA fbY x faY(ks1)
-// Same K order per accumulator as k_conv_valid_img2 (and every other conv3 kernel): bit-identical.
-
-template <int LAYER, int NB, int IH, int IW, bool STAMP = false, int ABLATE = 0, bool IL = false>   // IL: fragment reads interleaved into the MFMA clusters (sched_group_barrier); STAMP: diagnostic build, per-segment s_memtime sums of wave 0 into d.dbg; ABLATE (timing only, WRONG results): 1 no image switch, 2 + no wait for the weight DMA, 3 + no weight DMA, 4 + no barriers, 5 + no fragment reads; 6 the bound of a register-fed weight operand: MFMAs, the 16 image fragment reads and the image switch, no weight tile at all (no DMA, no per-step barrier, weight fragments loop-invariant)
-__global__ __launch_bounds__(256, 2) void k_conv_valid_pipe(const GemmDesc d) {
-    constexpr int OH = IH - 2, OW = IW - 2, OUT_PER = OH * OW, IN_PER = IH * IW;
-    constexpr int OUT_ROWS = NB * OUT_PER, IMG_R = NB * IN_PER;
-    constexpr int NCOL = 128;
-    constexpr int IMG_BYTES = (IMG_R * 128 + 1023) / 1024 * 1024;
-    constexpr int IPIECES = (IMG_R + 31) / 32, WPIECES = NCOL / 32;       // 1 KiB DMA pieces per wave
-    static_assert(IMG_BYTES + NCOL * 128 <= 81920, "two workgroups must fit a CU's 160 KiB");
-    static_assert(IMG_R % 8 == 0 && NB <= 16, "whole 8-row DMA sub-pieces; NetWorkspace keeps 16 boards of slack");
-    __shared__ __attribute__((aligned(16))) unsigned char smem[IMG_BYTES + NCOL * 128];   // img | w
-    const int n_boards = (int)(*d.n_dev);
-    const int M = n_boards * OUT_PER;
-    if (M <= d.m_min) return;                          // the small-batch kernel launched beside this one takes the batch
-    const int C = d.cin;
-    const int NT = d.N / NCOL;
-    const int id = blockIdx.x;
-    const int xcd = id & 7, j = id >> 3;
-    const int ntile = j % NT, mtile = (j / NT) * 8 + xcd;
-    const int b0 = mtile * NB, n0 = ntile * NCOL;
-    if (b0 >= n_boards) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
-    const int lrow = lane >> 3;
-    const int chunk = (lane & 7) ^ lrow;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    // DMA addresses: one loop-invariant 32-bit lane offset per operand; piece q adds a uniform stride to the SGPR base.  Image rows
-    // past the batch's last board are read unclamped (the workspace keeps 16 boards of slack; their output rows are never stored).
-    const uint32_t i_ob = (uint32_t)((b0 * IN_PER + wave * 8 + lrow) * C + chunk * 8) * 2u;
-    const uint32_t w_ob = (uint32_t)((n0 + wave * 8 + lrow) * d.K + chunk * 8) * 2u;
-    const uint32_t lds_img = (uint32_t)(uintptr_t)(lds_ptr)(smem + wave * 1024);
-    const uint32_t lds_w = (uint32_t)(uintptr_t)(lds_ptr)(smem + IMG_BYTES + wave * 1024);
-    const size_t i_stride = (size_t)64 * C, w_stride = (size_t)64 * d.K;          // 32 rows, in bytes
-#define AZ_PDMA_W(kk_)                                                                                       \
-    {                                                                                                        \
-        const char* wbase = (const char*)(d.W + (kk_));                                                      \
-        _Pragma("unroll") for (int q_ = 0; q_ < WPIECES; ++q_) lds_dma16(wbase + q_ * w_stride, w_ob, lds_w + q_ * 4096); \
-    }
-#define AZ_PDMA_IMG(cb_)                                                                                     \
-    {                                                                                                        \
-        const char* ibase = (const char*)(d.A + (cb_) * 64);                                                 \
-        _Pragma("unroll") for (int q_ = 0; q_ < IPIECES; ++q_)                                               \
-            if ((q_ * 4 + 3) * 8 + 7 < IMG_R || (q_ * 4 + wave) * 8 + 7 < IMG_R)                             \
-                lds_dma16(ibase + q_ * i_stride, i_ob, lds_img + q_ * 4096);                                 \
-    }
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int frow = lane & 15, fq = lane >> 4, fsw = lane & 7;
-    int rbase[8];
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt) {
-        int ml = wr * 128 + mt * 16 + frow;
-        ml = ml < OUT_ROWS ? ml : 0;
-        const int bl = ml / OUT_PER, p = ml - bl * OUT_PER, y = p / OW, x = p - y * OW;
-        rbase[mt] = bl * IN_PER + y * IW + x;
-    }
-    const int b_row0 = IMG_BYTES + (wc * 64 + frow) * 128;
-    const int coffB0 = ((0 + fq) ^ fsw) << 4, coffB1 = ((4 + fq) ^ fsw) << 4;
-#define AZ_PLDA(dst_, mt0_, ks_, dt_)                                                                        \
-    if constexpr (ABLATE < 5 || ABLATE == 6) _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                       \
-        const int r_ = rbase[(mt0_) + i_] + (dt_);                                                           \
-        dst_[i_] = *(const bf16x8*)(smem + r_ * 128 + ((((ks_) * 4 + fq) ^ (r_ & 7)) << 4));                 \
-    }
-#define AZ_PLDB(dst_, coff_)                                                                                 \
-    if constexpr (ABLATE < 5) _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                         \
-        dst_[i_] = *(const bf16x8*)(smem + b_row0 + i_ * 2048 + (coff_));
-#define AZ_PMMA(mt0_, fb_, fa_)                                                                              \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                         \
-        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                     \
-            acc[(mt0_) + i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb_[j_], fa_[i_], acc[(mt0_) + i_][j_], 0, 0, 0);
-#define AZ_PSB __builtin_amdgcn_sched_barrier(0)
-#define AZ_PFENCE if constexpr (!IL) __builtin_amdgcn_sched_barrier(0)
-    // IL: the region's reads (for the NEXT cluster) go between this cluster's MFMAs: rep_ x { nmf_ MFMAs, 1 LDS read }
-#define AZ_PMIX(nmf_, rep_, tail_)                                                                           \
-    if constexpr (IL) {                                                                                      \
-        _Pragma("unroll") for (int g_ = 0; g_ < (rep_); ++g_) {                                              \
-            __builtin_amdgcn_sched_group_barrier(0x008, (nmf_), 0);                                          \
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                               \
-        }                                                                                                    \
-        if ((tail_) > 0) __builtin_amdgcn_sched_group_barrier(0x008, (tail_), 0);                            \
-    }
-    AZ_PDMA_W(0);
-    AZ_PDMA_IMG(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    bf16x8 fbX[4], fbY[4], faX[4], faY[4];
-    if constexpr (ABLATE >= 5) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fbX[i] = fbY[i] = faX[i] = faY[i] = *(const bf16x8*)(smem + lane * 16 + i * 1024);
-    }
-    AZ_PLDB(fbX, coffB0);
-    AZ_PLDA(faX, 0, 0, 0);
-    const int ncb = C / 64;
-    const int nk = ABLATE == -2 ? 0 : ncb * 9;          // ABLATE -2: prologue + epilogue only
-    int cb = 0, tap = 0, dt = 0;
-    unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0, t_begin = 0, r_begin = 0;
-    if constexpr (STAMP) { t_begin = tprev = __builtin_amdgcn_s_memtime(); r_begin = __builtin_amdgcn_s_memrealtime(); }
-#define AZ_PSTAMP(i_) if constexpr (STAMP) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); seg[i_] += t_ - tprev; tprev = t_; }
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool sw = tap == 8;
-        const int ntap = sw ? 0 : tap + 1, ncbi = sw ? cb + 1 : cb;
-        const int nky = ntap / 3, ndt = nky * IW + (ntap - nky * 3);
-        const int kk = kt + 1 < nk ? ntap * C + ncbi * 64 : 8 * C + cb * 64;      // last step: re-fetch its own tile (unused)
-        AZ_PLDB(fbY, coffB1);
-        AZ_PLDA(faY, 4, 0, dt);
-        AZ_PFENCE;
-        AZ_PMMA(0, fbX, faX);
-        AZ_PMIX(1, 8, 8);
-        AZ_PSB;
-        AZ_PSTAMP(0);
-        __builtin_amdgcn_s_waitcnt(0xC07F);                      // lgkmcnt(0): this step's weight fragments are in registers
-        if constexpr (ABLATE < 4) __builtin_amdgcn_s_barrier();
-        AZ_PSB;
-        AZ_PSTAMP(1);
-        if constexpr (ABLATE < 3) AZ_PDMA_W(kk);
-        AZ_PSTAMP(2);
-        AZ_PLDA(faX, 0, 1, dt);
-        AZ_PFENCE;
-        AZ_PMMA(4, fbX, faY);
-        AZ_PMIX(2, 4, 8);
-        AZ_PSB;
-        AZ_PSTAMP(3);
-        AZ_PLDA(faY, 4, 1, dt);
-        AZ_PFENCE;
-        AZ_PMMA(0, fbY, faX);
-        AZ_PMIX(2, 4, 8);
-        AZ_PSB;
-        AZ_PSTAMP(4);
-        __builtin_amdgcn_s_waitcnt(0xC07F);                      // my reads of the image slice are done (they are: one cluster old)
-        if constexpr (ABLATE < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the next weight tile has landed
-        if constexpr (ABLATE < 4) __builtin_amdgcn_s_barrier();
-        AZ_PSB;
-        AZ_PSTAMP(5);
-        if ((ABLATE <= 0 || ABLATE == 6) && sw && ncbi < ncb) {                 // single image buffer: the switch is covered by the CU's other workgroup
-            if constexpr (ABLATE == 6) __builtin_amdgcn_s_barrier();            // no per-step barrier: every wave is past its last read of the old slice
-            AZ_PDMA_IMG(ncbi);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        AZ_PSB;
-        AZ_PSTAMP(6);
-        AZ_PLDB(fbX, coffB0);                                    // next step's first fragments, under this step's last cluster
-        AZ_PLDA(faX, 0, 0, ndt);
-        AZ_PFENCE;
-        AZ_PMMA(4, fbY, faY);
-        AZ_PMIX(1, 8, 8);
-        AZ_PSB;
-        AZ_PSTAMP(7);
-        tap = ntap; cb = ncbi; dt = ndt;
-    }
-    if constexpr (STAMP) {
-        if (tid == 0 && d.dbg && blockIdx.x < 128) {
-            for (int i = 0; i < 8; ++i) d.dbg[16 * blockIdx.x + i] = seg[i];
-            d.dbg[16 * blockIdx.x + 8] = __builtin_amdgcn_s_memtime() - t_begin;
-            d.dbg[16 * blockIdx.x + 9] = __builtin_amdgcn_s_memrealtime() - r_begin;
-        }
-    }
-#undef AZ_PSTAMP
-#undef AZ_PDMA_W
-#undef AZ_PDMA_IMG
-#undef AZ_PLDA
-#undef AZ_PLDB
-#undef AZ_PMMA
-#undef AZ_PSB
-#undef AZ_PFENCE
-#undef AZ_PMIX
-    // Epilogue through LDS: a lane holds 4 consecutive channels of 32 (row tile, column tile) pairs -- stored directly that is 32
-    // eight-byte stores per lane in 32-byte pieces of 16 different rows each (7 % of the kernel at 3072 rows).  The image and weight
-    // buffers are dead now: the tile (+ bias, ReLU, bf16) goes to LDS as [240 rows][128 channels] with a 272-byte row stride
-    // (conflict-free for both directions), and leaves as whole 256-byte row segments, 16 bytes per lane.
-    constexpr int EP_STRIDE = NCOL * 2 + 16;
-    static_assert(OUT_ROWS * EP_STRIDE <= IMG_BYTES + NCOL * 128, "the output tile must fit the dead buffers");
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_barrier();                     // every wave is past its last fragment read (and the unused last DMA has landed)
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int nl = wc * 64 + nt * 16 + fq * 4;
-        const float4 bv = *(const float4*)(d.bias + n0 + nl);
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-            const int ml = wr * 128 + mt * 16 + frow;
-            if (ml >= OUT_ROWS) continue;
-            float r0 = acc[mt][nt][0] + bv.x, r1 = acc[mt][nt][1] + bv.y, r2 = acc[mt][nt][2] + bv.z,
-                  r3 = acc[mt][nt][3] + bv.w;
-            if (d.relu) { r0 = fmaxf(r0, 0.f); r1 = fmaxf(r1, 0.f); r2 = fmaxf(r2, 0.f); r3 = fmaxf(r3, 0.f); }
-            uint2 o;
-            o.x = pack_bf16x2(r0, r1);
-            o.y = pack_bf16x2(r2, r3);
-            *(uint2*)(smem + ml * EP_STRIDE + nl * 2) = o;
-        }
-    }
-    __syncthreads();
-    constexpr int EP_CHUNKS = OUT_ROWS * (NCOL / 8);        // 16-byte chunks of the tile
-#pragma unroll
-    for (int it = 0; it < (EP_CHUNKS + 255) / 256; ++it) {
-        const int idx = it * 256 + tid;
-        const int ml = idx / (NCOL / 8), c = idx - ml * (NCOL / 8);
-        const int m = b0 * OUT_PER + ml;
-        if (idx >= EP_CHUNKS || m >= M) continue;
-        const uint4 v = *(const uint4*)(smem + ml * EP_STRIDE + c * 16);
-        if (ABLATE >= 0 || v.x == 0x12345678u) *(uint4*)(d.out + (size_t)m * d.N + n0 + c * 8) = v;      // ABLATE -1: the kernel without its stores
-    }
-}
+constexpr int C3_NB = 12;                    // boards of a conv3 image tile: 240 of 256 output rows, a 63 KiB LDS image per 64-channel block
 
 // ---- the image-resident 'valid' conv tile, generalised: per-wave tile = MT x NTW accumulators of 16x16 ------------------------------
 // Waves 2 x 2; a wave owns 16*MT rows x 16*NTW columns, the workgroup 32*MT rows (NB boards' outputs) x 32*NTW columns.  The pipeline
@@ -1492,279 +1240,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3_auto_wreg(const GemmDesc d, co
     conv3_auto_body<true, 1>(d, smem, full_grid, tail_wgs);
 }
 
-#ifdef AZ_DIAG
-// ---- conv3 as a PING-PONG kernel: ONE 8-wave workgroup per CU, the two waves of every SIMD in opposite phases ------------------------
-// k_conv3_auto's two independent 4-wave workgroups per CU interleave fragment reads, DMA issue and MFMAs in every wave's in-order
-// stream: the matrix pipe waits whenever both waves of a SIMD wait (SQ_WAIT_INST_ANY 56 % of wave cycles, profiles/r03f_pmc_sq_*).
-// Here the two waves of a SIMD belong to ONE workgroup and alternate roles, separated by workgroup barriers: in every slot one of them
-// issues nothing but 32 MFMAs on fragments it already holds in registers (the pipe runs back to back), the other one reads the 12
-// fragments of ITS next 32 MFMAs and issues the slot's LDS-DMA.  Group 0 = waves 0-3 (rows 0..127 of the tile), group 1 = waves 4-7 (rows
-// 128..255), group 1 one barrier behind.
-//   tile     12 boards (240 of 256 rows) x 256 channels; wave = 128 rows x 64 channels (8 x 4 accumulators, as in every conv3 kernel)
-//   stage s  = (channel block cb, tap, k half): 32 deep.  Weights: 256 channels x 32 k = 16 KiB per stage, TWO stage buffers, streamed from
-//            the model's packed copy (ConvNet::wp3: the LDS image of every stage, swizzle included, contiguous -- one DMA piece is 1 KiB
-//            of consecutive global bytes).  Image: the boards' 64-channel slice of act2 (63 KiB), TWO buffers: slice cb + 1 streams in
-//            during the 36 slots of slice cb, so there is no image switch to wait for.  2 x 63 + 2 x 16 = 158 KiB.
-//   slot 2s     group 0: LOAD(s): 12 ds_read_b128, DMA weights of stage s + 1 | group 1: MFMAs of stage s - 1
-//   slot 2s + 1 group 0: MFMAs of stage s, then vmcnt(0)                     | group 1: LOAD(s), DMA one piece of image slice cb + 1
-// Same K order per accumulator as every other conv3 kernel (channel block outer, tap inner, k 0..31 then 32..63): bit-identical.
-constexpr int PP_NB = C3_NB;                       // boards per tile (the cell maps are Conv3Tables')
-constexpr int PP_NCOL = 256;                       // channels per tile
-constexpr int PP_WSTAGE = PP_NCOL * 64;            // one weight stage: 64-byte rows, chunk q of row n at slot q ^ pp_wperm(n)
-// LDS: [chunk-parity plane][image buffer][32 KiB of 64-byte cells] | w[2].  The buffer is bit 15 of an image address (an immediate of
-// the ds_read), the plane bit 16 (per lane).
-constexpr int PP_LDS = 4 * C3_PLANE_BYTES + 2 * PP_WSTAGE;
-constexpr int PP_EP_STRIDE = PP_NCOL * 2 + 16;
-static_assert(PP_LDS <= 163840 && PP_NB * 20 * PP_EP_STRIDE <= PP_LDS, "one workgroup per CU: 160 KiB");
-AZ_HD int pp_wperm(int n) { return (0x1320 >> (((n >> 2) & 3) * 4)) & 3; }      // {0, 2, 3, 1}[(n >> 2) & 3]: conflict-free ds_read_b128 of 64-byte rows
-
-template <int LAYER, int ABL = 0, int SCHED = 2, int TAIL = 2>     // TAIL: row tiles (x 4 MFMAs) of a stage issued behind its closing barrier; SCHED: barriers per stage (2: a LOAD and a COMPUTE slot; 1: see AZ_QSTAGE); ABL (diagnostic library, timing only, WRONG results): 1 no weight DMA, 2 no image DMA, 4 no fragment reads, 8 no MFMAs, 16 THREE weight buffers (the first overlaps the image: what a third buffer would buy)
-__global__ __launch_bounds__(512, 2) void k_conv3_pp(const GemmDesc d) {
-    constexpr int OUT_PER = 20, IN_PER = 42, OUT_ROWS = PP_NB * OUT_PER;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[PP_LDS];
-    const int n_boards = (int)(*d.n_dev);
-    const int M = n_boards * OUT_PER;
-    if (M <= d.m_min) return;                          // the small-batch kernel launched beside this one takes the batch
-    if (blockIdx.x == 0 && threadIdx.x == 0 && d.acct && n_boards > 0) { atomicAdd(&d.acct[0], (unsigned long long)n_boards); atomicAdd(&d.acct[1], 1ull); }
-    const int C = d.cin;
-    const int NT = d.N / PP_NCOL;
-    const int id = blockIdx.x;
-    const int xcd = id & 7, j = id >> 3;
-    const int ntile = j % NT, mtile = (j / NT) * 8 + xcd;
-    const int b0 = mtile * PP_NB, n0 = ntile * PP_NCOL;
-    if (b0 >= n_boards) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = wave >> 2, wr = (wave >> 1) & 1, wc = g * 2 + (wave & 1);   // group (= column half of the tile: each group streams ITS 128 channels' weights), row half, column quarter
-    const int w4 = wave & 3;                           // wave within its group
-    const int frow = lane & 15, fq = lane >> 4;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_ptr)smem;
-    const int ncb = C / 64, nst = ncb * 18;
-    const char* wp = (const char*)d.Wp + (size_t)ntile * nst * PP_WSTAGE;
-    const uint32_t w_vo = (uint32_t)(wave * 2048 + lane * 16);             // wave w: pieces 2 w, 2 w + 1 of a stage (its own group's half)
-    constexpr int R3 = (ABL & 16) ? 1 : 0;             // weight ring of 3 (ablation) or 2 stages
-    constexpr int W_BASE = 4 * C3_PLANE_BYTES - R3 * PP_WSTAGE;
-    const uint32_t lds_w = lds_base + W_BASE + wave * 2048;
-    // image DMA (Conv3Tables' inverse map): piece q of a group's wave w4 fills cells (q & 7) * 64 + w4 * 16 + (lane >> 2) of plane q >> 3;
-    // group 0 brings plane 0 (pieces 0..7), group 1 plane 1 (pieces 8..15)
-    // (kept packed, two per register: image row | chunk position << 10; the byte offset is rebuilt where a piece is issued)
-    uint32_t i_pk[4];
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) {
-        const uint32_t e = d.c3tab[jj * 64 + w4 * 16 + (lane >> 2)];
-        const uint32_t pk = (e & 1023u) | ((((uint32_t)lane & 3u) ^ ((e >> 10) & 3u)) << 10);
-        if (jj & 1) i_pk[jj >> 1] |= pk << 16; else i_pk[jj >> 1] = pk;
-    }
-    const uint32_t i_b0 = (uint32_t)(b0 * IN_PER * C) * 2u, i_rs = (uint32_t)C * 2u;
-    const uint32_t lds_i = lds_base + w4 * 1024;
-#define AZ_QDMA_IMG(q_, cb_)                                                                                                  \
-    {                                                                                                                          \
-        uint32_t pkr_ = i_pk[((q_) & 7) >> 1];                                                                                 \
-        asm volatile("" : "+v"(pkr_));                 /* opaque: the eight offsets are loop-invariant and must not be hoisted (spills) */ \
-        const uint32_t pk_ = (((q_) & 1) ? pkr_ >> 16 : pkr_) & 0xFFFFu;                                                       \
-        lds_dma16((const char*)(d.A + (cb_) * 64) + ((q_) >> 3) * 16, i_b0 + (pk_ & 1023u) * i_rs + ((pk_ >> 10) << 5),        \
-                  lds_i + ((q_) >> 3) * (2 * C3_PLANE_BYTES) + ((cb_) & 1) * C3_PLANE_BYTES + ((q_) & 7) * 4096);              \
-    }
-    // prologue: the first image slice (plane 0 by waves 0-3, plane 1 by waves 4-7) and weight stage 0
-#pragma unroll
-    for (int i = 0; i < 8; ++i) AZ_QDMA_IMG(g * 8 + i, 0)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) lds_dma16(wp + i * 1024, w_vo, lds_w + i * 1024);
-    if ((SCHED == 1 && g == 1) || R3) {                 // SCHED 1: group 1 issues one stage further ahead (see AZ_QSTAGE)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) lds_dma16(wp + PP_WSTAGE + i * 1024, w_vo, lds_w + PP_WSTAGE + i * 1024);
-    }
-    if (SCHED == 1 && g == 1 && R3) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) lds_dma16(wp + 2 * PP_WSTAGE + i * 1024, w_vo, lds_w + 2 * PP_WSTAGE + i * 1024);
-    }
-    // fragment cells of all nine taps: 8 row tiles x 16 bit per tap and lane (Conv3Tables' read map), the lane's chunk position folded in
-    uint32_t tq[9][4];
-    {
-        const uint4* rdtab = (const uint4*)(d.c3tab + C3_TAB_INV) + (wr * 16 + frow);
-        const uint32_t px = ((uint32_t)fq >> 1) << 4, pxx = px | (px << 16);
-#pragma unroll
-        for (int t = 0; t < 9; ++t) { const uint4 v = rdtab[t * 32]; tq[t][0] = v.x ^ pxx; tq[t][1] = v.y ^ pxx; tq[t][2] = v.z ^ pxx; tq[t][3] = v.w ^ pxx; }
-    }
-    const uint32_t lx = ((uint32_t)fq & 1u) << 16;     // the lane's plane
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const unsigned char* wb = smem + W_BASE + (wc * 64 + frow) * 64 + ((fq ^ pp_wperm(frow)) << 4);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    bf16x8 fb[4], fa[8];
-    if constexpr ((ABL & 4) != 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fb[i] = *(const bf16x8*)(smem + 4 * C3_PLANE_BYTES + lane * 16 + i * 1024);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) fa[i] = *(const bf16x8*)(smem + lane * 16 + i * 1024);
-    }
-    if (SCHED == 2 && g == 1) __builtin_amdgcn_s_barrier();       // SCHED 2: group 1 runs one slot behind group 0
-    __builtin_amdgcn_sched_barrier(0);
-    int s = 0;
-    // ABL 128 (diagnostic): per-segment s_memtime sums of waves 0 and 4 -- LOAD until its reads are back | barrier 1 | MFMA issue |
-    // wait for the DMA | barrier 2 -- every stamp sits where lgkmcnt is 0 anyway
-    unsigned long long seg[5] = {0, 0, 0, 0, 0}, tprev = 0, t_begin = 0;
-    if constexpr ((ABL & 128) != 0) { t_begin = tprev = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); }
-#define AZ_QSTAMP(i_)                                                                                                          \
-    if constexpr ((ABL & 128) != 0) {                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        unsigned long long t_;                                                                                                 \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory");                                          \
-        seg[i_] += t_ - tprev; tprev = t_;                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-    }
-    // SCHED 1: both groups run the same sequence LOAD(0) COMPUTE(0) LOAD(1) COMPUTE(1) ...; group 0's barrier stands behind every COMPUTE, group 1's
-    // behind every LOAD, so between two barriers group 0 does LOAD(i), COMPUTE(i) while group 1 does COMPUTE(i - 1), LOAD(i): ONE barrier
-    // per stage keeps the two waves of a SIMD in opposite phases.  Each group opens its interval with its DMA (its half of a weight stage,
-    // then at most one image piece) and waits for the weight pieces just before its barrier: a LOAD and a COMPUTE later.
-    // weight stage st_ -> buffer st_ & 1 (given as a literal); IMG_: this interval also brings one piece of image slice cb + 1
-#define AZ_QDMA(st_, wbuf_, IMG_, TAP_)                                                                                        \
-    {                                                                                                                          \
-        if (!(ABL & 1) && (st_) < nst) {                                                                                       \
-            const char* src_ = wp + (size_t)(st_) * PP_WSTAGE;                                                                 \
-            _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) lds_dma16(src_ + i_ * 1024, w_vo, lds_w + (wbuf_) * PP_WSTAGE + i_ * 1024); \
-        }                                                                                                                      \
-        if (!(ABL & 2) && (IMG_) && cb + 1 < ncb) AZ_QDMA_IMG(g * 8 + (TAP_), cb + 1)                                           \
-    }
-    // wait for the weight pieces of the interval; an image piece issued behind them may stay in flight
-#define AZ_QWAITV(IMG_)                                                                                                        \
-    {                                                                                                                          \
-        if constexpr (R3) {                            /* the stage issued in THIS interval may stay in flight */               \
-            if ((IMG_) && !(ABL & 2) && cb + 1 < ncb) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                          \
-            else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                                                              \
-        } else {                                                                                                               \
-            if ((IMG_) && !(ABL & 2) && cb + 1 < ncb) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");                          \
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                              \
-        }                                                                                                                      \
-    }
-    // one stage: BUF_ (image buffer), TAP_, HALF_ are literals, so every LDS address is a register + an immediate
-#define AZ_QLOAD(BUF_, TAP_, HALF_)                                                                                            \
-        if constexpr (!(ABL & 4)) _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) fb[nt] = *(const bf16x8*)(wb + (R3 ? ((TAP_) * 2 + (HALF_)) % 3 : (HALF_)) * PP_WSTAGE + nt * 1024); \
-        if constexpr (!(ABL & 4)) _Pragma("unroll") for (int mt = 0; mt < 8; ++mt) {                                           \
-            uint32_t a_;   /* asm volatile: the 144 addresses of a slice are loop-invariant and must NOT be hoisted (spills) */ \
-            if (HALF_) asm volatile("v_perm_b32 %0, %1, %2, %3\n\tv_xor_b32 %0, 32, %0" : "=&v"(a_) : "v"(lx), "v"(tq[TAP_][mt >> 1]), "s"((mt & 1) ? 0x0C060302u : 0x0C060100u)); \
-            else asm volatile("v_perm_b32 %0, %1, %2, %3" : "=v"(a_) : "v"(lx), "v"(tq[TAP_][mt >> 1]), "s"((mt & 1) ? 0x0C060302u : 0x0C060100u)); \
-            fa[mt] = *(const bf16x8*)(smem + (BUF_) * C3_PLANE_BYTES + a_);                                                    \
-        }
-    // row tiles [mt0_, mt1_) of the stage's 8 x 4 MFMAs
-#define AZ_QCOMPUTE(mt0_, mt1_)                                                                                                \
-        if constexpr (!(ABL & 96)) __builtin_amdgcn_s_setprio(1);                                                              \
-        if constexpr (!(ABL & 8)) _Pragma("unroll") for (int mt = (mt0_); mt < (mt1_); ++mt)                                   \
-            _Pragma("unroll") for (int nt = 0; nt < 4; ++nt)                                                                   \
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[nt], fa[mt], acc[mt][nt], 0, 0, 0);                   \
-        else { _Pragma("unroll") for (int mt = 0; mt < 8; ++mt) asm volatile("" :: "v"(fa[mt])); _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) asm volatile("" :: "v"(fb[nt])); } \
-        if constexpr (!(ABL & 96)) __builtin_amdgcn_s_setprio(0);
-    // one stage: BUF_ (image buffer), TAP_, HALF_ are literals, so every LDS address is a register + an immediate
-#define AZ_QSTAGE(BUF_, TAP_, HALF_)                                                                                           \
-    if constexpr (SCHED == 2) {                                                                                                \
-        /* two barriers per stage: a LOAD slot and a COMPUTE slot per wave, group 1 one slot behind group 0 */                  \
-        AZ_QDMA(s + 1 + R3, R3 ? ((TAP_) * 2 + (HALF_) + 2) % 3 : 1 - (HALF_), (HALF_) == 0 && (TAP_) < 8, TAP_)               \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        AZ_QLOAD(BUF_, TAP_, HALF_)                                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        __builtin_amdgcn_s_waitcnt(0xC07F);            /* lgkmcnt(0): my reads are done before anybody may overwrite them */   \
-        AZ_QSTAMP(0)                                                                                                           \
-        __builtin_amdgcn_s_barrier();                                                                                          \
-        AZ_QSTAMP(1)                                                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        AZ_QCOMPUTE(0, 8 - TAIL)                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        AZ_QSTAMP(2)                                                                                                           \
-        AZ_QWAITV((HALF_) == 0 && (TAP_) < 8)                                                                                  \
-        AZ_QSTAMP(3)                                                                                                           \
-        __builtin_amdgcn_s_barrier();                                                                                          \
-        AZ_QSTAMP(4)                                                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        /* the last TAIL row tiles' MFMAs issue BEHIND the barrier: they keep the matrix pipe busy while the other group starts */ \
-        if constexpr (TAIL > 0) { AZ_QCOMPUTE(8 - TAIL, 8) __builtin_amdgcn_sched_barrier(0); }                                \
-        ++s;                                                                                                                   \
-    } else {                                                                                                                   \
-        if (g == 0) AZ_QDMA(s + 1 + R3, R3 ? ((TAP_) * 2 + (HALF_) + 2) % 3 : 1 - (HALF_), (HALF_) == 0 && (TAP_) < 8, TAP_)   \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        AZ_QLOAD(BUF_, TAP_, HALF_)                                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        if (g == 1) {                                                                                                          \
-            __builtin_amdgcn_s_waitcnt(0xC07F);        /* lgkmcnt(0): my reads are done before anybody may overwrite them */   \
-            AZ_QWAITV((HALF_) == 1 && (TAP_) < 8)      /* what I issued behind the previous stage's barrier */                 \
-            __builtin_amdgcn_s_barrier();                                                                                      \
-            AZ_QDMA(s + 2 + R3, R3 ? ((TAP_) * 2 + (HALF_)) % 3 : (HALF_), (HALF_) == 0 && (TAP_) < 8, TAP_)                   \
-        }                                                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        AZ_QCOMPUTE(0, 8)                                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        if (g == 0) {                                                                                                          \
-            AZ_QWAITV((HALF_) == 0 && (TAP_) < 8)                                                                              \
-            __builtin_amdgcn_s_barrier();                                                                                      \
-        }                                                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                                                     \
-        ++s;                                                                                                                   \
-    }
-#define AZ_QSLICE(BUF_)                                                                                                        \
-    AZ_QSTAGE(BUF_, 0, 0) AZ_QSTAGE(BUF_, 0, 1) AZ_QSTAGE(BUF_, 1, 0) AZ_QSTAGE(BUF_, 1, 1) AZ_QSTAGE(BUF_, 2, 0) AZ_QSTAGE(BUF_, 2, 1) \
-    AZ_QSTAGE(BUF_, 3, 0) AZ_QSTAGE(BUF_, 3, 1) AZ_QSTAGE(BUF_, 4, 0) AZ_QSTAGE(BUF_, 4, 1) AZ_QSTAGE(BUF_, 5, 0) AZ_QSTAGE(BUF_, 5, 1) \
-    AZ_QSTAGE(BUF_, 6, 0) AZ_QSTAGE(BUF_, 6, 1) AZ_QSTAGE(BUF_, 7, 0) AZ_QSTAGE(BUF_, 7, 1) AZ_QSTAGE(BUF_, 8, 0) AZ_QSTAGE(BUF_, 8, 1)
-    for (int cb = 0; cb < ncb; ++cb) {                 // ncb is even (C % 256 == 0): two slices per trip, the image buffer a literal
-        AZ_QSLICE(0)
-        ++cb;
-        AZ_QSLICE(1)
-    }
-#undef AZ_QDMA
-#undef AZ_QWAITV
-#undef AZ_QLOAD
-#undef AZ_QCOMPUTE
-#undef AZ_QSTAMP
-    if constexpr ((ABL & 128) != 0) {
-        if ((wave & 3) == 0 && lane == 0 && d.dbg && blockIdx.x < 128) {
-            for (int i = 0; i < 5; ++i) d.dbg[16 * blockIdx.x + g * 8 + i] = seg[i];
-            d.dbg[16 * blockIdx.x + g * 8 + 7] = __builtin_amdgcn_s_memtime() - t_begin;
-        }
-    }
-    if (SCHED == 2 && g == 0) __builtin_amdgcn_s_barrier();       // pairs with group 1's last COMPUTE barrier
-#undef AZ_QSLICE
-#undef AZ_QSTAGE
-#undef AZ_QDMA_IMG
-    __builtin_amdgcn_sched_barrier(0);
-    // epilogue through LDS (every buffer is dead): [240][256] bf16 with a 528-byte row stride, out as whole 512-byte row segments
-    // (the lane constants are rebuilt from an opaque thread id: computed before the K loop they would be spilled across it)
-    __syncthreads();
-    int etid = (int)threadIdx.x;
-    asm volatile("" : "+v"(etid));
-    const int efrow = etid & 15, efq = (etid >> 4) & 3;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int nl = wc * 64 + nt * 16 + efq * 4;
-        const float4 bv = *(const float4*)(d.bias + n0 + nl);
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-            const int ml = wr * 128 + mt * 16 + efrow;
-            if (ml >= OUT_ROWS) continue;
-            float r0 = acc[mt][nt][0] + bv.x, r1 = acc[mt][nt][1] + bv.y, r2 = acc[mt][nt][2] + bv.z, r3 = acc[mt][nt][3] + bv.w;
-            if (d.relu) { r0 = fmaxf(r0, 0.f); r1 = fmaxf(r1, 0.f); r2 = fmaxf(r2, 0.f); r3 = fmaxf(r3, 0.f); }
-            uint2 o;
-            o.x = pack_bf16x2(r0, r1);
-            o.y = pack_bf16x2(r2, r3);
-            *(uint2*)(smem + ml * PP_EP_STRIDE + nl * 2) = o;
-        }
-    }
-    __syncthreads();
-    constexpr int EP_CHUNKS = OUT_ROWS * (PP_NCOL / 8);
-#pragma unroll
-    for (int it = 0; it < (EP_CHUNKS + 511) / 512; ++it) {
-        const int idx = it * 512 + etid;
-        const int ml = idx / (PP_NCOL / 8), c = idx - ml * (PP_NCOL / 8);
-        const int m = b0 * OUT_PER + ml;
-        if (idx >= EP_CHUNKS || m >= M) continue;
-        *(uint4*)(d.out + (size_t)m * d.N + n0 + c * 8) = *(const uint4*)(smem + ml * PP_EP_STRIDE + c * 16);
-    }
-}
-
-#endif   // AZ_DIAG (k_conv3_pp)
-
 // ---- SKINNY GEMM for small batches: operands straight into registers, no LDS, no barrier ---------------------------------------------
 // The arena (temp 0: ~20 executed rows per step and model), the drain of a self-play call and single-tree calls run the forward on a
 // few dozen rows.  The tiled kernels are then a chain of K / 64 dependent steps of { DMA, wait, barrier, fragment reads, MFMAs } run by
@@ -2050,7 +1525,6 @@ struct ConvNet {                      // the WEIGHTS of one model id (21 MB bf16
     uint32_t* npat = nullptr;                          // device constant 19683 (the table GEMM's row count)
     uint16_t* wg[5] = {nullptr};                       // conv2,3,4, fc1, fc2 folded bf16 [N][K]
     uint16_t* wr[5] = {nullptr};                       // conv2,3,4, fc1, fc2 as the ring's stage images (GemmDesc::Wr)
-    uint16_t* wp3 = nullptr;                           // conv3's weights as k_conv3_pp's LDS stage images [N / 256][C / 64 * 18][256][32] (C % 256 == 0)
     uint16_t* wf3 = nullptr;                           // conv3's weights in MFMA fragment order (k_conv3_auto_wreg) [C / 64][C / 64 * 9 K-steps][4][2][64 lanes][8]
                                                        // + WF3_PAD K-steps of padding
     float* bg[5] = {nullptr};                          // folded bias f32 [N]
@@ -2166,9 +1640,6 @@ ConvNet* convnet_create(int channels, const char** err) {
     ok &= (n->bh = n->dalloc<float>(8)) != nullptr;
     ok &= (n->wf3 = n->dalloc<uint16_t>(9 * (size_t)C * C + (size_t)WF3_PAD * WF3_STEP)) != nullptr;
     if (n->wf3) ok &= hipMemset(n->wf3 + 9 * (size_t)C * C, 0, (size_t)WF3_PAD * WF3_STEP * sizeof(uint16_t)) == hipSuccess;
-#ifdef AZ_DIAG
-    if (C % PP_NCOL == 0) ok &= (n->wp3 = n->dalloc<uint16_t>(9 * (size_t)C * C)) != nullptr;
-#endif
     if (!ok) {
         if (err) *err = "convnet_create: device allocation failed";
         convnet_destroy(n);
@@ -2190,7 +1661,7 @@ NetWorkspace* netws_create(int channels, int max_batch, const char** err) {
     const int C = channels;
     const size_t B = (size_t)max_batch;
     bool ok = true;
-    ok &= (n->act2 = n->dalloc<uint16_t>((B + 16) * 42 * C)) != nullptr;     // + 16 boards: k_conv_valid_pipe reads its last tile unclamped
+    ok &= (n->act2 = n->dalloc<uint16_t>((B + 16) * 42 * C)) != nullptr;     // + 16 boards: the image-resident conv3 kernels read their last tile unclamped
     ok &= (n->act3 = n->dalloc<uint16_t>(B * 20 * C)) != nullptr;
     ok &= (n->act4 = n->dalloc<uint16_t>(B * 6 * C)) != nullptr;
     ok &= (n->fc1o = n->dalloc<uint16_t>(B * 1024)) != nullptr;
@@ -2313,22 +1784,6 @@ bool convnet_set_params(ConvNet* net, const float* p, int64_t count) {
                 }
             ok &= hipMemcpy(net->wf3, wf.data(), wf.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
         }
-#ifdef AZ_DIAG
-        if (l == 1 && net->wp3) {   // conv3: the same bf16 values as k_conv3_pp's stage images (stage = channel block, tap, k half)
-            std::vector<uint16_t> wp((size_t)9 * C * C);
-            const int nst = C / 64 * 18;
-            for (int nt = 0; nt < C / PP_NCOL; ++nt)
-                for (int st = 0; st < nst; ++st) {
-                    const int cb = st / 18, tap = (st % 18) / 2, half = st & 1;
-                    uint16_t* img = &wp[((size_t)nt * nst + st) * (PP_WSTAGE / 2)];
-                    for (int nl = 0; nl < PP_NCOL; ++nl)
-                        for (int q = 0; q < 4; ++q)
-                            std::memcpy(img + nl * 32 + ((q ^ pp_wperm(nl)) << 3),
-                                        &w[(size_t)(nt * PP_NCOL + nl) * K[1] + (size_t)tap * C + cb * 64 + half * 32 + q * 8], 16);
-                }
-            ok &= hipMemcpy(net->wp3, wp.data(), wp.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
-        }
-#endif
         if (l == 0) {   // conv2: the same bf16 values as [tap*C + co][ci] for the table GEMM, then U = T x W2r^T
             std::vector<uint16_t> wr((size_t)9 * C * C);
             for (int co = 0; co < C; ++co)
@@ -2399,7 +1854,9 @@ void convnet_init_random(ConvNet* net, uint64_t seed) {
 // rows_typ = what the batch is expected to hold (picks the kernel / tile family; any value is correct, a good one is fast).
 // Rejected and removed after measurement (numbers in profiles/README.md, code in git history): XCD column remap, third weight buffer,
 // late / spread DMA issue, mid barrier, 32x32x16 MFMA shape, non-temporal cache policy, wave stagger, persistent tiles, tail split,
-// cross-step fragment prefetch, weights straight into registers, a double-buffered conv3 image, one wave per SIMD.
+// cross-step fragment prefetch, weights straight into registers, a double-buffered conv3 image, one wave per SIMD, conv3 as an 8-wave
+// ping-pong kernel (k_conv3_pp), and the timing ladders that computed wrong results on purpose (the ABLATE arms of k_gemm256,
+// k_conv_valid_pipe and k_conv3_pp: no DMA, no MFMA, no barriers, no stores).
 
 // Small batches (the arena, the drain of a self-play call, single-tree calls): the image-resident conv3 kernel is a chain of 72 K-steps of
 // ~0.8 us for a workgroup alone on its CU (70 us whatever the rows); the ring with 4 stages in flight walks the same K in ~32 us up to
@@ -2414,47 +1871,15 @@ static void launch_conv2_gemm(const GemmDesc& d, int rows_hint, hipStream_t s) {
     const int t8 = (tiles + 7) / 8 * 8;
     hipLaunchKernelGGL((k_conv_same_pipe<1, TABLE>), dim3(t8 * (d.N / HBN2_)), dim3(256), 0, s, d);
 }
-static void launch_conv3_image(const GemmDesc& d, int rows_hint, hipStream_t s, bool tail, bool planes, int pp, bool wreg) {
-#ifdef AZ_DIAG
-    if (pp && d.Wp && d.N % PP_NCOL == 0) {
-        const int t8 = ((rows_hint + PP_NB - 1) / PP_NB + 7) / 8 * 8;
-        const dim3 grid(t8 * (d.N / PP_NCOL)), block(512);
-        switch (pp) {           // 16 + mask: the timing ablations (WRONG results)
-            case 17: hipLaunchKernelGGL((k_conv3_pp<2, 1>), grid, block, 0, s, d); return;
-            case 18: hipLaunchKernelGGL((k_conv3_pp<2, 2>), grid, block, 0, s, d); return;
-            case 19: hipLaunchKernelGGL((k_conv3_pp<2, 3>), grid, block, 0, s, d); return;
-            case 20: hipLaunchKernelGGL((k_conv3_pp<2, 4>), grid, block, 0, s, d); return;
-            case 23: hipLaunchKernelGGL((k_conv3_pp<2, 7>), grid, block, 0, s, d); return;
-            case 24: hipLaunchKernelGGL((k_conv3_pp<2, 8>), grid, block, 0, s, d); return;
-            case 27: hipLaunchKernelGGL((k_conv3_pp<2, 11>), grid, block, 0, s, d); return;
-            case 28: hipLaunchKernelGGL((k_conv3_pp<2, 16>), grid, block, 0, s, d); return;
-            case 34: hipLaunchKernelGGL((k_conv3_pp<2, 0, 1>), grid, block, 0, s, d); return;
-            case 36: hipLaunchKernelGGL((k_conv3_pp<2, 128>), grid, block, 0, s, d); return;
-            case 38: hipLaunchKernelGGL((k_conv3_pp<2, 0, 2, 0>), grid, block, 0, s, d); return;
-            case 39: hipLaunchKernelGGL((k_conv3_pp<2, 0, 2, 1>), grid, block, 0, s, d); return;
-            case 40: hipLaunchKernelGGL((k_conv3_pp<2, 0, 2, 3>), grid, block, 0, s, d); return;
-            case 37: hipLaunchKernelGGL((k_conv3_pp<2, 128 + 16>), grid, block, 0, s, d); return;
-            case 35: hipLaunchKernelGGL((k_conv3_pp<2, 16, 1>), grid, block, 0, s, d); return;
-            case 30: hipLaunchKernelGGL((k_conv3_pp<2, 32>), grid, block, 0, s, d); return;
-            case 31: hipLaunchKernelGGL((k_conv3_pp<2, 64>), grid, block, 0, s, d); return;
-            case 32: hipLaunchKernelGGL((k_conv3_pp<2, 48>), grid, block, 0, s, d); return;
-            case 33: hipLaunchKernelGGL((k_conv3_pp<2, 80>), grid, block, 0, s, d); return;
-            case 29: hipLaunchKernelGGL((k_conv3_pp<2, 24>), grid, block, 0, s, d); return;
-            default: break;
-        }
-        hipLaunchKernelGGL((k_conv3_pp<2>), grid, block, 0, s, d);
-        return;
-    }
-#endif
+static void launch_conv3_image(const GemmDesc& d, int rows_hint, hipStream_t s, bool tail, bool planes, bool wreg) {
     const int tiles = (rows_hint + C3_NB - 1) / C3_NB;
     const int t8 = (tiles + 7) / 8 * 8;
-    const int full_grid = t8 * (d.N / 128);
+    const int full_grid = t8 * (d.N / 128), tail_wgs = tail ? C3_TAIL : 0;       // tail_wgs = 0: no tile is cut, no extra workgroups
+    const dim3 grid(full_grid + tail_wgs), block(256);
     // the register-fed weight operand needs the fragment-ordered copy and the PLANES image (64 KiB: the epilogue's tile fits it)
-    if (wreg && planes && d.Wf)
-        hipLaunchKernelGGL((k_conv3_auto_wreg<2>), dim3(full_grid + (tail ? C3_TAIL : 0)), dim3(256), 0, s, d, full_grid, tail ? C3_TAIL : 0);
-    else if (planes) hipLaunchKernelGGL((k_conv3_auto<2, true>), dim3(full_grid + (tail ? C3_TAIL : 0)), dim3(256), 0, s, d, full_grid, tail ? C3_TAIL : 0);
-    else if (tail) hipLaunchKernelGGL((k_conv3_auto<2, false>), dim3(full_grid + C3_TAIL), dim3(256), 0, s, d, full_grid, C3_TAIL);
-    else hipLaunchKernelGGL((k_conv_valid_pipe<2, C3_NB, 6, 7, false, 0, true>), dim3(full_grid), dim3(256), 0, s, d);
+    if (wreg && planes && d.Wf) hipLaunchKernelGGL((k_conv3_auto_wreg<2>), grid, block, 0, s, d, full_grid, tail_wgs);
+    else if (planes) hipLaunchKernelGGL((k_conv3_auto<2, true>), grid, block, 0, s, d, full_grid, tail_wgs);
+    else hipLaunchKernelGGL((k_conv3_auto<2, false>), grid, block, 0, s, d, full_grid, tail_wgs);
 }
 
 // The LDS-DMA ring with the tile rows picked on the device.  The host picks the FAMILY from its estimate (NS = 4: one workgroup per CU,
@@ -2522,16 +1947,8 @@ static bool launch_gemm_diag(const GemmDesc& d, int rows_hint, int rows_typ, hip
         const int t8 = (tiles + 7) / 8 * 8;
         const dim3 g3(t8 * (d.N / 128)), b3(256);
         switch (o.conv3_pipe) {
-            case 2: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 0, false>), g3, b3, 0, s, d); break;
-            case 3: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, true, 0, true>), g3, b3, 0, s, d); break;
-            case 10: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, -1, true>), g3, b3, 0, s, d); break;
-            case 9: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, -2, true>), g3, b3, 0, s, d); break;
-            case 11: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 1, true>), g3, b3, 0, s, d); break;
-            case 12: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 2, true>), g3, b3, 0, s, d); break;
-            case 13: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 3, true>), g3, b3, 0, s, d); break;
-            case 14: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 4, true>), g3, b3, 0, s, d); break;
-            case 15: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 5, true>), g3, b3, 0, s, d); break;
-            case 16: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, 6, true>), g3, b3, 0, s, d); break;
+            case 2: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, false, false>), g3, b3, 0, s, d); break;
+            case 3: hipLaunchKernelGGL((k_conv_valid_pipe<LAYER, C3_NB, 6, 7, true, true>), g3, b3, 0, s, d); break;
             default: hipLaunchKernelGGL((k_conv_valid_img2<LAYER, C3_NB, 6, 7, 2>), g3, b3, 0, s, d); break;
         }
         return true;
@@ -2542,13 +1959,7 @@ static bool launch_gemm_diag(const GemmDesc& d, int rows_hint, int rows_typ, hip
         const int mt8 = (mt + 7) / 8 * 8;
         const dim3 grid(mt8 * (d.N / HBN_)), block(512);
         if (v == 1) hipLaunchKernelGGL((k_gemm256<LAYER, 0>), grid, block, 0, s, d);
-        else if (v == 11) hipLaunchKernelGGL((k_gemm256<LAYER, 1, 1>), grid, block, 0, s, d);
-        else if (v == 12) hipLaunchKernelGGL((k_gemm256<LAYER, 1, 2>), grid, block, 0, s, d);
-        else if (v == 13) hipLaunchKernelGGL((k_gemm256<LAYER, 1, 3>), grid, block, 0, s, d);
-        else if (v == 14) hipLaunchKernelGGL((k_gemm256<LAYER, 1, 4>), grid, block, 0, s, d);
-        else if (v == 15) hipLaunchKernelGGL((k_gemm256<LAYER, 1, 5>), grid, block, 0, s, d);
-        else if (v == 16) hipLaunchKernelGGL((k_gemm256<LAYER, 1, 6>), grid, block, 0, s, d);
-        else if (v == 17) hipLaunchKernelGGL((k_gemm256<LAYER, 1, 7>), grid, block, 0, s, d);
+        else if (v == 13) hipLaunchKernelGGL((k_gemm256<LAYER, 1, true>), grid, block, 0, s, d);      // the clock-stamp build
         else hipLaunchKernelGGL((k_gemm256<LAYER, 1>), grid, block, 0, s, d);
         return true;
     }
@@ -2632,7 +2043,7 @@ static void launch_gemm(const GemmDesc& d, int rows_hint, int rows_typ, hipStrea
     }
     if constexpr (LAYER == 2) {
         if (o.conv3_small && conv3_is_small(d2, rows_hint, rows_typ)) launch_ring_auto<LAYER>(d2, rows_hint, rows_typ, s, true);
-        else launch_conv3_image(d2, rows_hint, s, o.conv3_tail != 0, o.conv3_planes != 0, o.conv3_pp, o.conv3_wreg != 0);
+        else launch_conv3_image(d2, rows_hint, s, o.conv3_tail != 0, o.conv3_planes != 0, o.conv3_wreg != 0);
         return;
     }
 
@@ -2932,15 +2343,13 @@ void convnet_forward(ConvNet* n, NetWorkspace* ws, const EvalBatch& eb, int rows
     d.A = ws->act2; d.W = n->wg[1]; d.bias = n->bg[1]; d.out = ws->act3;
     d.rows_per_sample = 20; d.out_w = 5; d.in_h = 6; d.in_w = 7;
     d.Wr = o.ring_packed ? n->wr[1] : nullptr;
-    d.Wp = n->wp3;
     d.Wf = n->wf3;
     if (fp8) {           // e4m3 act2 -> e4m3 act3 (the first half of the allocation): the ring, or for small batches the skinny GEMM
         GemmDesc d8 = d;
-        d8.Wr = (const uint16_t*)n->w8[0]; d8.dq = n->dq8[0]; d8.out_scale = n->sa3; d8.Wp = nullptr; d8.Wf = nullptr;
+        d8.Wr = (const uint16_t*)n->w8[0]; d8.dq = n->dq8[0]; d8.out_scale = n->sa3; d8.Wf = nullptr;
         launch_gemm_f8<2, 1>(d8, rows_hint, rows_typ, s, o, ws);
     } else
     launch_gemm<2>(d, rows_hint, rows_typ, s, o);
-    d.Wp = nullptr;
     d.Wf = nullptr;
     if (timed) (void)hipEventRecord(rec.e2b, s);
     // conv4: 3x3 valid [4][5][C] -> [2][3][C]

@@ -61,9 +61,15 @@ __global__ __launch_bounds__(256, (NS <= 2 ? 2 : 1)) void k_gemm_ring(const Gemm
     gemm_ring_body<NS, BM>(d, smem, (int)(*d.n_dev) * d.rows_per_sample);
 }
 
-// ABLATE != 0 are timing experiments (WRONG results; tools/net_bench.py, profiles/README.md): 1 no DMA in the loop, 2 no MFMA,
-// 3 clock stamps, 4 no DMA + no fragment reads, 5 = 4 without the barrier, 6 DMA never waited for, 7 loads to registers
-template <int LAYER, int PIPE, int ABLATE = 0>
+// ---- 256x256 tile variant for the big layers (conv2, conv3): LDS-DMA staging ------------------------------
+// 8 waves (2 x 4), each wave a 128(m) x 64(n) sub-tile = 8 x 4 accumulators of v_mfma_f32_16x16x32_bf16.
+// Both operands go global -> LDS with global_load_lds_dwordx4 (no VGPR staging, no ds_write): one wave-instruction
+// writes 1 KiB = 8 tile rows x 128 B linearly, so the XOR swizzle (chunk c of row r at slot c ^ (r&7)) is applied
+// to the per-lane SOURCE address and again on the fragment reads.  Two 64 KiB LDS buffers; the next K-step's DMA is
+// issued before this K-step's MFMAs and retired by vmcnt(0) + barrier at the end of the step.
+// STAMP: the clock-stamp build ("gemm_variant" 13, tools/clock_probe.py): same results, plus per-block {shader cycles, 100 MHz ticks} of the K loop
+constexpr int HBM_ = 256;
+template <int LAYER, int PIPE, bool STAMP = false>
 __global__ __launch_bounds__(512, 2) void k_gemm256(const GemmDesc d) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (HBM_ + HBN_) * 128];
     const int M = (int)(*d.n_dev) * d.rows_per_sample;
@@ -136,41 +142,22 @@ __global__ __launch_bounds__(512, 2) void k_gemm256(const GemmDesc d) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     unsigned long long st0 = 0, sr0 = 0;
-    if constexpr (ABLATE == 3) { st0 = __builtin_amdgcn_s_memtime(); sr0 = __builtin_amdgcn_s_memrealtime(); }
+    if constexpr (STAMP) { st0 = __builtin_amdgcn_s_memtime(); sr0 = __builtin_amdgcn_s_memrealtime(); }
     // LDS byte offsets of this lane's fragment rows (row-major 128-B rows, XOR-swizzled 16-B slots)
     const int a_row0 = (wr * 128 + frow) * 128, b_row0 = 32768 + (wc * 64 + frow) * 128;
     const int coff0 = ((0 + fq) ^ fsw) << 4, coff1 = ((4 + fq) ^ fsw) << 4;
 #define AZ_LDA(dst_, base_, mt0_, coff_)                                                     \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                       \
-        if constexpr (ABLATE == 4 || ABLATE == 5) { asm volatile("" : "+v"(dst_[i_])); }      \
-        else dst_[i_] = *(const bf16x8*)((base_) + a_row0 + ((mt0_) + i_) * 2048 + (coff_)); \
-    }
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                         \
+        dst_[i_] = *(const bf16x8*)((base_) + a_row0 + ((mt0_) + i_) * 2048 + (coff_));
 #define AZ_LDB(dst_, base_, coff_)                                                           \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                       \
-        if constexpr (ABLATE == 4 || ABLATE == 5) { asm volatile("" : "+v"(dst_[i_])); }      \
-        else dst_[i_] = *(const bf16x8*)((base_) + b_row0 + i_ * 2048 + (coff_));            \
-    }
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                         \
+        dst_[i_] = *(const bf16x8*)((base_) + b_row0 + i_ * 2048 + (coff_));
 #define AZ_MMA(mt0_, fb_, fa_)                                                               \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                         \
-        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                   \
-            if constexpr (ABLATE == 2) { asm volatile("" :: "v"(fb_[j_]), "v"(fa_[i_])); }   \
-            else acc[(mt0_) + i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb_[j_], fa_[i_], acc[(mt0_) + i_][j_], 0, 0, 0); \
-        }
+        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                     \
+            acc[(mt0_) + i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb_[j_], fa_[i_], acc[(mt0_) + i_][j_], 0, 0, 0);
     for (int kt = 0; kt < nk; ++kt) {
-        if (ABLATE != 1 && ABLATE != 4 && ABLATE != 5 && ABLATE != 7 && kt + 1 < nk) AZ_DMA(kt + 1, (kt + 1) & 1);
-        if constexpr (ABLATE == 7) {
-            if (kt + 1 < nk) {      // same addresses and widths, destination = registers (no LDS write)
-                const uint32_t toff = ks_toff, kk = ks_kk;
-                AZ_KSTEP_ADVANCE();
-                uint4 r0 = *(const uint4*)(d.A + a_off0 + toff), r1 = *(const uint4*)(d.A + a_off1 + toff),
-                      r2 = *(const uint4*)(d.A + a_off2 + toff), r3 = *(const uint4*)(d.A + a_off3 + toff),
-                      r4 = *(const uint4*)(d.W + b_off0 + kk), r5 = *(const uint4*)(d.W + b_off0 + b_step + kk),
-                      r6 = *(const uint4*)(d.W + b_off0 + 2 * b_step + kk), r7 = *(const uint4*)(d.W + b_off0 + 3 * b_step + kk);
-                asm volatile("" :: "v"(r0.x ^ r0.y ^ r0.z ^ r0.w), "v"(r1.x ^ r1.y ^ r1.z ^ r1.w), "v"(r2.x ^ r2.y ^ r2.z ^ r2.w),
-                             "v"(r3.x ^ r3.y ^ r3.z ^ r3.w), "v"(r4.x ^ r4.y ^ r4.z ^ r4.w), "v"(r5.x ^ r5.y ^ r5.z ^ r5.w),
-                             "v"(r6.x ^ r6.y ^ r6.z ^ r6.w), "v"(r7.x ^ r7.y ^ r7.z ^ r7.w));
-            }
-        }
+        if (kt + 1 < nk) AZ_DMA(kt + 1, (kt + 1) & 1);
         const unsigned char* sA = smem + (kt & 1) * 65536;
         if constexpr (PIPE == 0) {
             const unsigned char* sB = sA + 32768;
@@ -210,14 +197,13 @@ __global__ __launch_bounds__(512, 2) void k_gemm256(const GemmDesc d) {
             __builtin_amdgcn_sched_barrier(0);
             AZ_MMA(4, fbY, faY);
         }
-        if constexpr (ABLATE != 6) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (ABLATE == 6) __builtin_amdgcn_s_barrier();
-        else if constexpr (ABLATE != 5) __syncthreads();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
     }
 #undef AZ_LDA
 #undef AZ_LDB
 #undef AZ_MMA
-    if constexpr (ABLATE == 3) {
+    if constexpr (STAMP) {
         // in-kernel clock = d(s_memtime) / d(s_memrealtime) x 100 MHz (MI355X_MICROARCH.md, DVFS give-back item 6);
         // the stamps go to a debug buffer nothing else reads
         const unsigned long long st1 = __builtin_amdgcn_s_memtime(), sr1 = __builtin_amdgcn_s_memrealtime();
@@ -244,6 +230,13 @@ __global__ __launch_bounds__(512, 2) void k_gemm256(const GemmDesc d) {
     }
 }
 
+// ---- conv2 as an IMAGE-RESIDENT implicit GEMM ----------------------------------------------------------------
+// The 9 filter taps of one 64-channel block read overlapping shifted windows of the same activations.  With an M tile
+// of 6 whole boards (252 output rows) the 64-channel slice of those boards is 6 x 42 x 128 B = 31.5 KiB: it is DMA'd
+// into LDS ONCE per channel block (double-buffered, landing during the previous block's taps) and the A fragments of
+// tap (ky,kx) are read from it at row m + (ky-1)*7 + (kx-1); out-of-board taps read a zero row ('same' padding).
+// Only the weight tile (32 KiB) still streams every K-step, so L2->LDS traffic falls from 64 KiB to 35.5 KiB per
+// K-step.  Same K order (channel block outer, tap inner) and per-row accumulation order as the other kernels.
 template <int LAYER>
 __global__ __launch_bounds__(512, 2) void k_conv_img(const GemmDesc d) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 32768];   // img[2] | w[2]
@@ -403,6 +396,14 @@ __global__ __launch_bounds__(512, 2) void k_conv_img(const GemmDesc d) {
     }
 }
 
+// ---- conv2 image-resident, TWO independent workgroups per CU ---------------------------------------------------------
+// k_conv_img's 8 waves share one barrier, so the two waves of every SIMD run in lockstep: both in their MFMA clusters
+// (contending for the matrix pipe), then both parked at the wait / barrier (pipe idle; SQ_WAIT_INST_ANY 42 %,
+// SQ_WAIT_ANY 38 % of wave cycles).  Here the same per-wave work (128 rows x 64 columns, 8 x 4 accumulators) is packaged
+// as workgroups of 4 waves -- tile = 6 boards x 128 channels, LDS = one image buffer (32 KiB) + two weight buffers
+// (16 KiB each) = 64 KiB -- so two workgroups fit a CU and every SIMD holds one wave of each: their barriers are
+// independent and their phases drift apart.  The price is a single image buffer (the image switch every 9 K-steps is
+// exposed inside a workgroup and covered by the other one).  Same K order: bit-identical.
 // TABLE: the image rows are gathered from the conv1 table (d.A) by pattern index instead of read from act1.
 template <int LAYER, bool TABLE = false>
 __global__ __launch_bounds__(256, 2) void k_conv_img2(const GemmDesc d) {
@@ -567,6 +568,16 @@ __global__ __launch_bounds__(256, 2) void k_conv_img2(const GemmDesc d) {
     }
 }
 
+// ---- 'valid' 3x3 convs (conv3: [6][7][C] -> [4][5][C], conv4: [4][5][C] -> [2][3][C]) image-resident, two 4-wave
+// workgroups per CU ---------------------------------------------------------------------------------------------------
+// The lockstep argument of k_conv_img2 for the 'valid' convs.  Tile = NB boards (NB*OH*OW output rows, padded to 128 or
+// 256) x NCOL channels; every wave owns 128 rows x 64 columns (8 x 4 accumulators, 64 MFMAs per K-step):
+//   conv3: NB = 12 (240 of 256 rows), NCOL = 128, waves 2 x 2; LDS = 63 KiB image + 16 KiB weights
+//   (conv4: NB = 19 (114 of 128 rows), NCOL = 256, waves 1 x 4, 47.5 KiB image + 32 KiB weights -- measured neutral, not used)
+// i.e. 80 KiB = the boards' input image (one buffer) + ONE weight buffer: both 32-deep halves of the step's weight
+// fragments are read into registers first, a barrier behind those reads frees the buffer, and the next weight tile is
+// DMA'd under the rest of the step.  A 'valid' conv needs no padding logic: output (y, x) of a board reads image row
+// (y+ky)*IW + (x+kx).  Same K order: bit-identical.
 template <int LAYER, int NB, int IH, int IW, int WN>
 __global__ __launch_bounds__(256, 2) void k_conv_valid_img2(const GemmDesc d) {
     constexpr int OH = IH - 2, OW = IW - 2, OUT_PER = OH * OW, IN_PER = IH * IW;
@@ -718,5 +729,218 @@ __global__ __launch_bounds__(256, 2) void k_conv_valid_img2(const GemmDesc d) {
             o.y = pack_bf16x2(r2, r3);
             *(uint2*)(d.out + (size_t)m * d.N + n) = o;
         }
+    }
+}
+
+// ---- the same tile with the LDS-DMA issued from inline asm and a software-pipelined K-step ---------------------------
+// hipcc models `__builtin_amdgcn_global_load_lds` as a FLAT access that may touch LDS and global memory at once: while one
+// is pending EVERY s_waitcnt it inserts is vmcnt(0) / lgkmcnt(0), so in k_conv_valid_img2 each MFMA cluster waits for the
+// fragment reads issued just before it (meant for the NEXT cluster) -- three exposed LDS latencies per K-step.  Issued
+// from inline asm (saddr form: uniform base in SGPRs + one loop-invariant 32-bit offset VGPR per piece, LDS base in M0)
+// the compiler does not see the DMA, its own lgkmcnt waits become counted, and the waits for the DMA are the explicit
+// vmcnt(0) + barrier pairs below.  K-step schedule (fbX / faX of step k were requested under step k-1's last cluster):
+//   reads fbY, faY(ks0) | MFMA fbX x faX(ks0) | lgkmcnt(0), barrier: W(k) is in registers everywhere | DMA W(k+1)
+//   reads faX(ks1) | MFMA fbX x faY(ks0) | reads faY(ks1) | MFMA fbY x faX(ks1) | vmcnt(0), barrier: W(k+1) landed
+//   reads fbX, faX(ks0) of step k+1 | MFMA fbY x faY(ks1)
+// Same K order per accumulator as k_conv_valid_img2 (and every other conv3 kernel): bit-identical.
+
+template <int LAYER, int NB, int IH, int IW, bool STAMP = false, bool IL = false>   // IL: fragment reads interleaved into the MFMA clusters (sched_group_barrier); STAMP: per-segment s_memtime sums of wave 0 into d.dbg (same results)
+__global__ __launch_bounds__(256, 2) void k_conv_valid_pipe(const GemmDesc d) {
+    constexpr int OH = IH - 2, OW = IW - 2, OUT_PER = OH * OW, IN_PER = IH * IW;
+    constexpr int OUT_ROWS = NB * OUT_PER, IMG_R = NB * IN_PER;
+    constexpr int NCOL = 128;
+    constexpr int IMG_BYTES = (IMG_R * 128 + 1023) / 1024 * 1024;
+    constexpr int IPIECES = (IMG_R + 31) / 32, WPIECES = NCOL / 32;       // 1 KiB DMA pieces per wave
+    static_assert(IMG_BYTES + NCOL * 128 <= 81920, "two workgroups must fit a CU's 160 KiB");
+    static_assert(IMG_R % 8 == 0 && NB <= 16, "whole 8-row DMA sub-pieces; NetWorkspace keeps 16 boards of slack");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[IMG_BYTES + NCOL * 128];   // img | w
+    const int n_boards = (int)(*d.n_dev);
+    const int M = n_boards * OUT_PER;
+    if (M <= d.m_min) return;                          // the small-batch kernel launched beside this one takes the batch
+    const int C = d.cin;
+    const int NT = d.N / NCOL;
+    const int id = blockIdx.x;
+    const int xcd = id & 7, j = id >> 3;
+    const int ntile = j % NT, mtile = (j / NT) * 8 + xcd;
+    const int b0 = mtile * NB, n0 = ntile * NCOL;
+    if (b0 >= n_boards) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 1, wc = wave & 1;
+    const int lrow = lane >> 3;
+    const int chunk = (lane & 7) ^ lrow;
+    typedef __attribute__((address_space(3))) void* lds_ptr;
+    // DMA addresses: one loop-invariant 32-bit lane offset per operand; piece q adds a uniform stride to the SGPR base.  Image rows
+    // past the batch's last board are read unclamped (the workspace keeps 16 boards of slack; their output rows are never stored).
+    const uint32_t i_ob = (uint32_t)((b0 * IN_PER + wave * 8 + lrow) * C + chunk * 8) * 2u;
+    const uint32_t w_ob = (uint32_t)((n0 + wave * 8 + lrow) * d.K + chunk * 8) * 2u;
+    const uint32_t lds_img = (uint32_t)(uintptr_t)(lds_ptr)(smem + wave * 1024);
+    const uint32_t lds_w = (uint32_t)(uintptr_t)(lds_ptr)(smem + IMG_BYTES + wave * 1024);
+    const size_t i_stride = (size_t)64 * C, w_stride = (size_t)64 * d.K;          // 32 rows, in bytes
+#define AZ_PDMA_W(kk_)                                                                                       \
+    {                                                                                                        \
+        const char* wbase = (const char*)(d.W + (kk_));                                                      \
+        _Pragma("unroll") for (int q_ = 0; q_ < WPIECES; ++q_) lds_dma16(wbase + q_ * w_stride, w_ob, lds_w + q_ * 4096); \
+    }
+#define AZ_PDMA_IMG(cb_)                                                                                     \
+    {                                                                                                        \
+        const char* ibase = (const char*)(d.A + (cb_) * 64);                                                 \
+        _Pragma("unroll") for (int q_ = 0; q_ < IPIECES; ++q_)                                               \
+            if ((q_ * 4 + 3) * 8 + 7 < IMG_R || (q_ * 4 + wave) * 8 + 7 < IMG_R)                             \
+                lds_dma16(ibase + q_ * i_stride, i_ob, lds_img + q_ * 4096);                                 \
+    }
+    f32x4 acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int jn = 0; jn < 4; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int frow = lane & 15, fq = lane >> 4, fsw = lane & 7;
+    int rbase[8];
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+        int ml = wr * 128 + mt * 16 + frow;
+        ml = ml < OUT_ROWS ? ml : 0;
+        const int bl = ml / OUT_PER, p = ml - bl * OUT_PER, y = p / OW, x = p - y * OW;
+        rbase[mt] = bl * IN_PER + y * IW + x;
+    }
+    const int b_row0 = IMG_BYTES + (wc * 64 + frow) * 128;
+    const int coffB0 = ((0 + fq) ^ fsw) << 4, coffB1 = ((4 + fq) ^ fsw) << 4;
+#define AZ_PLDA(dst_, mt0_, ks_, dt_)                                                                        \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {              \
+        const int r_ = rbase[(mt0_) + i_] + (dt_);                                                           \
+        dst_[i_] = *(const bf16x8*)(smem + r_ * 128 + ((((ks_) * 4 + fq) ^ (r_ & 7)) << 4));                 \
+    }
+#define AZ_PLDB(dst_, coff_)                                                                                 \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                               \
+        dst_[i_] = *(const bf16x8*)(smem + b_row0 + i_ * 2048 + (coff_));
+#define AZ_PMMA(mt0_, fb_, fa_)                                                                              \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                         \
+        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                     \
+            acc[(mt0_) + i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb_[j_], fa_[i_], acc[(mt0_) + i_][j_], 0, 0, 0);
+#define AZ_PSB __builtin_amdgcn_sched_barrier(0)
+#define AZ_PFENCE if constexpr (!IL) __builtin_amdgcn_sched_barrier(0)
+    // IL: the region's reads (for the NEXT cluster) go between this cluster's MFMAs: rep_ x { nmf_ MFMAs, 1 LDS read }
+#define AZ_PMIX(nmf_, rep_, tail_)                                                                           \
+    if constexpr (IL) {                                                                                      \
+        _Pragma("unroll") for (int g_ = 0; g_ < (rep_); ++g_) {                                              \
+            __builtin_amdgcn_sched_group_barrier(0x008, (nmf_), 0);                                          \
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                               \
+        }                                                                                                    \
+        if ((tail_) > 0) __builtin_amdgcn_sched_group_barrier(0x008, (tail_), 0);                            \
+    }
+    AZ_PDMA_W(0);
+    AZ_PDMA_IMG(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    bf16x8 fbX[4], fbY[4], faX[4], faY[4];
+    AZ_PLDB(fbX, coffB0);
+    AZ_PLDA(faX, 0, 0, 0);
+    const int ncb = C / 64;
+    const int nk = ncb * 9;
+    int cb = 0, tap = 0, dt = 0;
+    unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0, t_begin = 0, r_begin = 0;
+    if constexpr (STAMP) { t_begin = tprev = __builtin_amdgcn_s_memtime(); r_begin = __builtin_amdgcn_s_memrealtime(); }
+#define AZ_PSTAMP(i_) if constexpr (STAMP) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); seg[i_] += t_ - tprev; tprev = t_; }
+    for (int kt = 0; kt < nk; ++kt) {
+        const bool sw = tap == 8;
+        const int ntap = sw ? 0 : tap + 1, ncbi = sw ? cb + 1 : cb;
+        const int nky = ntap / 3, ndt = nky * IW + (ntap - nky * 3);
+        const int kk = kt + 1 < nk ? ntap * C + ncbi * 64 : 8 * C + cb * 64;      // last step: re-fetch its own tile (unused)
+        AZ_PLDB(fbY, coffB1);
+        AZ_PLDA(faY, 4, 0, dt);
+        AZ_PFENCE;
+        AZ_PMMA(0, fbX, faX);
+        AZ_PMIX(1, 8, 8);
+        AZ_PSB;
+        AZ_PSTAMP(0);
+        __builtin_amdgcn_s_waitcnt(0xC07F);                      // lgkmcnt(0): this step's weight fragments are in registers
+        __builtin_amdgcn_s_barrier();
+        AZ_PSB;
+        AZ_PSTAMP(1);
+        AZ_PDMA_W(kk);
+        AZ_PSTAMP(2);
+        AZ_PLDA(faX, 0, 1, dt);
+        AZ_PFENCE;
+        AZ_PMMA(4, fbX, faY);
+        AZ_PMIX(2, 4, 8);
+        AZ_PSB;
+        AZ_PSTAMP(3);
+        AZ_PLDA(faY, 4, 1, dt);
+        AZ_PFENCE;
+        AZ_PMMA(0, fbY, faX);
+        AZ_PMIX(2, 4, 8);
+        AZ_PSB;
+        AZ_PSTAMP(4);
+        __builtin_amdgcn_s_waitcnt(0xC07F);                      // my reads of the image slice are done (they are: one cluster old)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the next weight tile has landed
+        __builtin_amdgcn_s_barrier();
+        AZ_PSB;
+        AZ_PSTAMP(5);
+        if (sw && ncbi < ncb) {                                  // single image buffer: the switch is covered by the CU's other workgroup
+            AZ_PDMA_IMG(ncbi);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        AZ_PSB;
+        AZ_PSTAMP(6);
+        AZ_PLDB(fbX, coffB0);                                    // next step's first fragments, under this step's last cluster
+        AZ_PLDA(faX, 0, 0, ndt);
+        AZ_PFENCE;
+        AZ_PMMA(4, fbY, faY);
+        AZ_PMIX(1, 8, 8);
+        AZ_PSB;
+        AZ_PSTAMP(7);
+        tap = ntap; cb = ncbi; dt = ndt;
+    }
+    if constexpr (STAMP) {
+        if (tid == 0 && d.dbg && blockIdx.x < 128) {
+            for (int i = 0; i < 8; ++i) d.dbg[16 * blockIdx.x + i] = seg[i];
+            d.dbg[16 * blockIdx.x + 8] = __builtin_amdgcn_s_memtime() - t_begin;
+            d.dbg[16 * blockIdx.x + 9] = __builtin_amdgcn_s_memrealtime() - r_begin;
+        }
+    }
+#undef AZ_PSTAMP
+#undef AZ_PDMA_W
+#undef AZ_PDMA_IMG
+#undef AZ_PLDA
+#undef AZ_PLDB
+#undef AZ_PMMA
+#undef AZ_PSB
+#undef AZ_PFENCE
+#undef AZ_PMIX
+    // Epilogue through LDS: a lane holds 4 consecutive channels of 32 (row tile, column tile) pairs -- stored directly that is 32
+    // eight-byte stores per lane in 32-byte pieces of 16 different rows each (7 % of the kernel at 3072 rows).  The image and weight
+    // buffers are dead now: the tile (+ bias, ReLU, bf16) goes to LDS as [240 rows][128 channels] with a 272-byte row stride
+    // (conflict-free for both directions), and leaves as whole 256-byte row segments, 16 bytes per lane.
+    constexpr int EP_STRIDE = NCOL * 2 + 16;
+    static_assert(OUT_ROWS * EP_STRIDE <= IMG_BYTES + NCOL * 128, "the output tile must fit the dead buffers");
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_barrier();                     // every wave is past its last fragment read (and the unused last DMA has landed)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int nl = wc * 64 + nt * 16 + fq * 4;
+        const float4 bv = *(const float4*)(d.bias + n0 + nl);
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt) {
+            const int ml = wr * 128 + mt * 16 + frow;
+            if (ml >= OUT_ROWS) continue;
+            float r0 = acc[mt][nt][0] + bv.x, r1 = acc[mt][nt][1] + bv.y, r2 = acc[mt][nt][2] + bv.z,
+                  r3 = acc[mt][nt][3] + bv.w;
+            if (d.relu) { r0 = fmaxf(r0, 0.f); r1 = fmaxf(r1, 0.f); r2 = fmaxf(r2, 0.f); r3 = fmaxf(r3, 0.f); }
+            uint2 o;
+            o.x = pack_bf16x2(r0, r1);
+            o.y = pack_bf16x2(r2, r3);
+            *(uint2*)(smem + ml * EP_STRIDE + nl * 2) = o;
+        }
+    }
+    __syncthreads();
+    constexpr int EP_CHUNKS = OUT_ROWS * (NCOL / 8);        // 16-byte chunks of the tile
+#pragma unroll
+    for (int it = 0; it < (EP_CHUNKS + 255) / 256; ++it) {
+        const int idx = it * 256 + tid;
+        const int ml = idx / (NCOL / 8), c = idx - ml * (NCOL / 8);
+        const int m = b0 * OUT_PER + ml;
+        if (idx >= EP_CHUNKS || m >= M) continue;
+        *(uint4*)(d.out + (size_t)m * d.N + n0 + c * 8) = *(const uint4*)(smem + ml * EP_STRIDE + c * 16);
     }
 }

@@ -282,9 +282,10 @@ const char* az_last_error(const az_engine* e);
  *                           branch beside the BatchNorm-backward / dgrad chain (bit-identical; measured no faster, so off),
  *            "train_fwd_dma" 1 (default): the forward GEMMs' tiles go global -> LDS by LDS-DMA (k_gemm_f32_dma), 0: register-staged
  * libaz_engine_diag.so (the same sources built with -DAZ_DIAG; alphazero-rs_amd/build.py) additionally takes the keys of the
- * SUPERSEDED kernel generations and the TIMING ABLATIONS WITH WRONG RESULTS -- "gemm_variant", "fc_ring", "ring_tile", "conv3_ring",
- * "conv2_pipe", "conv3_pipe", "conv1_table", "conv4_big", "conv2_table" = 2, "tree_stamps", "print_*" -- which the shipped library
- * refuses (it accepts their default values, so a host may set them unconditionally); csrc/az_net.hip, csrc/az_net_diag.inc. */
+ * SUPERSEDED kernel generations and the clock-stamp builds -- "gemm_variant" (0, 1, 2, 3, 5; 13: clock stamps), "fc_ring", "ring_tile",
+ * "conv3_ring", "conv2_pipe", "conv3_pipe" (0 .. 3), "conv1_table", "conv4_big", "conv2_table" = 2, "tree_stamps", "print_*" -- which the
+ * shipped library refuses (it accepts their default values, so a host may set them unconditionally); csrc/az_net.hip,
+ * csrc/az_net_diag.inc.  No value of any key, in either library, computes a wrong answer. */
 az_status az_set_option(az_engine* e, const char* key, int64_t value);
 az_status az_get_stats(az_engine* e, az_stats* out);
 az_status az_reset_stats(az_engine* e);

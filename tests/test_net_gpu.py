@@ -131,6 +131,9 @@ def test_gemm_kernel_variants_are_bit_identical(diag_engine, conv_engine, oracle
             assert np.array_equal(pi, ref_small[0]) and np.array_equal(v, ref_small[1]), (key, val)
         with pytest.raises(Exception):
             conv_engine.set_option("gemm_variant", 4)         # removed variants are refused, not silently mapped
+        for key, val in (("gemm_variant", 12), ("conv3_pipe", 11), ("conv3_pp", 1)):   # the removed wrong-result ablations and the ping-pong kernel too
+            with pytest.raises(Exception):
+                conv_engine.set_option(key, val)
     finally:
         conv_engine.set_option("gemm_variant", 5)
         conv_engine.set_option("conv4_big", 0)
@@ -575,6 +578,30 @@ def test_conv3_image_kernel_accounting(engine, oracle):
     assert engine.stats()["net_conv3_image_rows"] == 0
 
 
+def test_conv3_accounting_counts_the_plain_image_kernel(conv_engine, oracle):
+    """With "conv3_tail" = 0 and "conv3_planes" = 0 the shipped library runs conv3 on k_conv3_auto<2, false> with no tile cut, and that
+    kernel writes the accounting like every other image-resident conv3 kernel: 13 rows are two 12-board tiles (the second ragged), 25 rows
+    three (the third holding one board).  Same bits as the default options (which send batches this small to the skinny GEMM)."""
+    conv_engine.net_init_random(6, seed=17)
+    states = random_states(oracle, 25, seed=41)
+    ref13, ref25 = conv_engine.predict_states(states[:13], 6), conv_engine.predict_states(states, 6)
+    try:
+        for key in ("conv3_small", "narrow_rows", "conv3_tail", "conv3_planes"):
+            conv_engine.set_option(key, 0)
+        conv_engine.reset_stats()
+        got13 = conv_engine.predict_states(states[:13], 6)
+        st = conv_engine.stats()
+        assert (st["net_conv3_image_rows"], st["net_conv3_image_launches"]) == (13, 1)
+        got25 = conv_engine.predict_states(states, 6)
+        st = conv_engine.stats()
+        assert (st["net_conv3_image_rows"], st["net_conv3_image_launches"]) == (38, 2)
+        assert np.array_equal(got13[0], ref13[0]) and np.array_equal(got13[1], ref13[1])
+        assert np.array_equal(got25[0], ref25[0]) and np.array_equal(got25[1], ref25[1])
+    finally:
+        for key, val in (("conv3_small", 1), ("narrow_rows", 32), ("conv3_tail", 1), ("conv3_planes", 1)):
+            conv_engine.set_option(key, val)
+
+
 def test_set_option_is_per_engine(engine_mod, oracle):
     """az_set_option changes the handle it is given and nothing else: two engines in one process, one with conv2 as the MFMA
     GEMM ("conv2_table" = 0: a different rounding of the same function) and the older kernel families, interleaved
@@ -622,8 +649,8 @@ def test_set_option_is_per_engine(engine_mod, oracle):
 
 
 def test_shipped_library_refuses_diagnostic_options(engine_mod):
-    """The timing ablations that compute WRONG results and the clock-stamp builds live in libaz_engine_diag.so (tools/ only):
-    the shipped library does not contain them and refuses their option values."""
+    """The superseded kernels and the clock-stamp builds live in libaz_engine_diag.so (tools/ only): the shipped library does not contain
+    them and refuses their option values, and with them the values of the removed timing ablations."""
     e = engine_mod.Engine(device=0, max_batch=64, net_channels=128)
     try:
         for key, val in (("gemm_variant", 12), ("gemm_variant", 17), ("conv3_pipe", 11), ("conv3_pipe", 15), ("conv3_pipe", 3),
