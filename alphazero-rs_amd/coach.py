@@ -59,6 +59,9 @@ class Coach:
         # Dirichlet root noise of the episodes (Engine.set_root_noise): switched on before every az_selfplay and off again behind it, so
         # nothing else the engine is used for sees it (the arena never does anyway).  eps 0 (the default): the engine is never asked
         self.root_noise_eps, self.root_noise_alpha = 0.0, 1.0
+        # Playout cap randomization of the episodes (Engine.set_playout_cap): switched on before every az_selfplay and off again behind it,
+        # exactly as the root noise is.  sims 0 (the default): the engine is never asked.  An iteration then yields the full moves' tuples only
+        self.playout_cap_sims, self.playout_cap_full = 0, 0.25
         # "eval_mirror" (Engine.set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
         # run under the mirror-canonical function F, so the gate compares like with like.  False (the default): the engine is never asked
         self.eval_mirror = False
@@ -102,6 +105,16 @@ class Coach:
             if self.root_noise_eps > 0:
                 self.engine.set_root_noise(0.0, self.root_noise_alpha)
 
+    @contextlib.contextmanager
+    def _selfplay_playout_cap(self):
+        if self.playout_cap_sims > 0:
+            self.engine.set_playout_cap(self.playout_cap_sims, self.playout_cap_full)
+        try:
+            yield
+        finally:
+            if self.playout_cap_sims > 0:
+                self.engine.set_playout_cap(0, self.playout_cap_full)
+
     def execute_episodes(self, model_id, iteration, seed):
         """The self-play fan-out of src/coach.rs:241-272: num_eps x execute_episode, sharded by global game id."""
         from . import dist as azdist
@@ -109,7 +122,7 @@ class Coach:
         lo, hi = azdist.shard_range(self.num_eps, rank, world)
         first = iteration * self.num_eps
         if hi > lo:
-            with self._selfplay_root_noise():
+            with self._selfplay_root_noise(), self._selfplay_playout_cap():
                 r = self.engine.selfplay(n_games=hi - lo, num_sims=self.num_sims, model_id=model_id, seed=seed,
                                          first_game_id=first + lo, concurrent=min(self.num_episode_threads, hi - lo),
                                          temp_threshold=self.temp_threshold, max_depth=self.max_depth, cpuct=self.cpuct,

@@ -213,6 +213,7 @@ struct TreeHost {
     void recycle(uint64_t reserve_nodes, hipStream_t s) {
         d.reserve_nodes = (uint32_t)reserve_nodes;
         d.noise = RootNoise{};                    // root noise belongs to the call that sets it (the arena never does)
+        d.cap = PlayoutCap{};                     // and so does a playout cap (self-play sessions only)
         HIPCHK(hipMemsetAsync(d.err, 0, ERR_COUNT * sizeof(uint32_t), s));
         HIPCHK(hipMemsetAsync(d_totals, 0, ST_TOTALS * sizeof(unsigned long long), s));
         HIPCHK(hipMemsetAsync(eb.n, 0, sizeof(uint32_t), s));
@@ -333,6 +334,9 @@ struct az_engine {
     int tree_block4 = 1;            // "tree_block4": k_backup_select as 4-wave workgroups
     // Dirichlet root noise of self-play and the tree calls, never of the arena ("root_noise_eps_e6" 0 = off, "root_noise_alpha_e6")
     int64_t root_noise_eps_e6 = 0, root_noise_alpha_e6 = 1000000;
+    // playout cap randomization of self-play ("playout_cap_sims" 0 = off, "playout_cap_full_e6"); never the arena or the tree calls
+    int64_t playout_cap_sims = 0, playout_cap_full_e6 = 250000;
+    std::vector<uint64_t> sp_full_plies;        // az_selfplay_get_full_plies: the full-ply masks of the last az_selfplay / az_selfplay_next
     // activation workspaces of the conv net: [0] the engine stream, [1] a second concurrent stream (az_arena's old-model
     // search); created on first use, shared by every model id
     NetWorkspace* ws[2] = {nullptr, nullptr};
@@ -697,6 +701,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
             float cpuct;
             NetOptions opt;
             RootNoise noise;                           // TreeDev travels by value: a graph captured with other noise arguments is never replayed
+            PlayoutCap cap;                            // ... nor one captured with another playout cap (or without one)
         } k;
         std::memset(&k, 0, sizeof k);
         k.th = &th; k.conv = net.conv; k.ws = net.kind == AZ_NET_CONV ? workspace_for(e, s) : nullptr; k.stream = s; k.root_states = d_root_states;
@@ -706,6 +711,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
         k.block4 = th.d.block4; k.log_cap = th.d.log_cap; k.ec_bmask = ec.bmask; k.ec_stones = ec.max_stones; k.max_depth = sp.max_depth; k.cpuct = sp.cpuct_f;
         k.opt = netopt_for(e, net);
         k.noise = th.d.noise;
+        k.cap = th.d.cap;
         k.reserve_nodes = th.d.reserve_nodes;      // TreeDev travels by value into the captured launches: the capacity threshold is baked in
         k.model_gen = net.generation;              // a freed and re-created model may reuse the ConvNet's address: its weights' identity is the generation
         TreeHost::StepGraph& sg = th.step_graph;
@@ -1017,6 +1023,14 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
             return fail(e, AZ_ERR_BAD_ARGUMENT, eps ? "root_noise_eps_e6 must be in 0 .. 1000000" : "root_noise_alpha_e6 must be in 50000 .. 100000000");
         if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "root noise cannot change while a self-play session is open");
         (eps ? e->root_noise_eps_e6 : e->root_noise_alpha_e6) = value;
+        return AZ_OK;
+    }
+    if (is("playout_cap_sims") || is("playout_cap_full_e6")) {
+        const bool sims = is("playout_cap_sims");
+        if (value < 0 || value > (sims ? PLAYOUT_CAP_MAX_SIMS : PLAYOUT_CAP_E6))
+            return fail(e, AZ_ERR_BAD_ARGUMENT, sims ? "playout_cap_sims must be in 0 .. 65535" : "playout_cap_full_e6 must be in 0 .. 1000000");
+        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "the playout cap cannot change while a self-play session is open");
+        (sims ? e->playout_cap_sims : e->playout_cap_full_e6) = value;
         return AZ_OK;
     }
     if (is("conv3_small") && (value == 0 || value == 1)) { e->netopt.conv3_small = (int)value; return AZ_OK; }
@@ -1763,6 +1777,7 @@ struct SelfplaySession {
     SelfplayMoveParams mp{};
     uint32_t* h_ctr = nullptr;           // pinned read-back of gd.counters
     int active = 0, rows_typ = 0;
+    int round_sims = 0;                  // lock-step: simulation steps of the next move round (playout cap: the largest budget among the slots' moves)
     int delivered = 0;                   // episodes handed out by az_selfplay_next so far
     long long iter = 0;
     bool async_mode = false;
@@ -1771,7 +1786,7 @@ struct SelfplaySession {
     EvalCache ec{};
     int fill = 0;
     long long step = 0;
-    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); if (lease.th) lease.th->d.noise = RootNoise{}; }
+    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); if (lease.th) { lease.th->d.noise = RootNoise{}; lease.th->d.cap = PlayoutCap{}; } }
 };
 
 static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, std::unique_ptr<SelfplaySession>& out) {
@@ -1788,6 +1803,9 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     if (st) return st;
     st = check_batch(e, *net, C * T);
     if (st) return st;
+    const int cap_sims = (int)e->playout_cap_sims;
+    if (cap_sims > 0 && cap_sims >= p->num_sims) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay: playout_cap_sims must be below num_sims");
+    if (cap_sims > 0 && cap_sims % T != 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay: playout_cap_sims % num_sim_threads != 0");
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     const uint64_t nodes = std::min<uint64_t>(p->reserve, reachable_slots(p->num_sims, AZ_MAX_PLIES));
@@ -1813,7 +1831,7 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     gd.g_len = mem.alloc<int32_t>(n_games);
     gd.g_result = mem.alloc<float>(n_games);
     gd.g_final_player = mem.alloc<int8_t>(n_games);
-    gd.counters = mem.alloc<uint32_t>(4);
+    gd.counters = mem.alloc<uint32_t>(8);
     if (p->record_evals > 0) {
         // per-EPISODE logs (row = the slot's current episode id), so they survive slot refills
         gd.g_log_len = mem.alloc<int32_t>(n_games);
@@ -1831,8 +1849,24 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
         HIPCHK(hipMemset(gd.need_reset, 0, C));
         HIPCHK(hipMemset(gd.moves, 0, ns));
         HIPCHK(hipMemset(gd.g_len, 0, n_games * sizeof(int32_t)));
-        uint32_t ctr[4] = {(uint32_t)C, 0u, (uint32_t)C, 0u};
+        uint32_t ctr[8] = {(uint32_t)C, 0u, (uint32_t)C, 0u, 0u, 0u, 0u, 0u};
         HIPCHK(hipMemcpy(gd.counters, ctr, sizeof ctr, hipMemcpyHostToDevice));
+    }
+    ss->round_sims = p->num_sims;
+    if (cap_sims > 0) {
+        // the slots' first moves (ply 0 of episodes 0 .. C-1) are drawn here; every later one by the move that precedes it (selfplay_move_body)
+        PlayoutCap cap{mem.alloc<uint32_t>(C), (uint32_t)p->num_sims, (uint32_t)cap_sims, playout_cap_thresh24((uint64_t)e->playout_cap_full_e6)};
+        std::vector<uint32_t> w((size_t)C);
+        uint32_t most = 0;
+        for (int i = 0; i < C; ++i) {
+            w[(size_t)i] = playout_cap_word(p->seed, p->first_game_id + (uint64_t)i, 0ull, cap.thresh24, cap.num_sims, cap.cap_sims);
+            most = std::max(most, w[(size_t)i] & ~PLAYOUT_FULL_BIT);
+        }
+        HIPCHK(hipMemcpy(cap.word, w.data(), (size_t)C * sizeof(uint32_t), hipMemcpyHostToDevice));
+        gd.g_full = mem.alloc<unsigned long long>(n_games);
+        HIPCHK(hipMemset(gd.g_full, 0, (size_t)n_games * sizeof(unsigned long long)));
+        th.d.cap = cap;
+        ss->round_sims = (int)most;
     }
     launch_reset_trees(th.d, nullptr, s);
     th.d.noise = root_noise_for(e);               // the session's root noise: stream (seed, first_game_id + the slot's episode, ply)
@@ -1840,7 +1874,7 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     prepare_cache(e, dedup_applies(e, *net), (uint64_t)n_games * AZ_MAX_PLIES * ((uint64_t)p->num_sims + 1), s);
     ss->sp = SearchParams{(uint32_t)p->max_depth, (float)p->cpuct};
     ss->mp = SelfplayMoveParams{p->seed, p->first_game_id, p->temp_threshold, C < n_games ? 1 : 0, 0, 0};
-    HIPCHK(hipHostMalloc((void**)&ss->h_ctr, 4 * sizeof(uint32_t)));
+    HIPCHK(hipHostMalloc((void**)&ss->h_ctr, 8 * sizeof(uint32_t)));
     ss->active = C;                               // slots still playing (read back after every move)
     ss->rows_typ = 0;                             // expected rows per leaf batch (0 = unknown: assume `active`)
     // "selfplay_async": free-running slots (k_async_step) -- conv nets (anything that goes through leaf batches), one simulation in
@@ -1916,15 +1950,18 @@ static az_status selfplay_run_until(az_engine* e, SelfplaySession& ss, int hi) {
         launch_selfplay_sync_active(th.d, gd, s);
         // tile choice from the largest batch of the previous move (de-duplication makes batches much smaller than the
         // number of searching trees); the grids still cover `active`
-        run_search(e, th, gd.state, p->num_sims, ss.sp, *net, ss.active, nullptr, ss.rows_typ, gd.counters + 3);
+        // playout cap: the round runs as many steps as the largest budget among its slots' moves (left by the previous round's move kernel);
+        // a tree whose own budget is smaller sits the rest of the round out
+        run_search(e, th, gd.state, ss.round_sims, ss.sp, *net, ss.active, nullptr, ss.rows_typ, gd.counters + 3);
         launch_selfplay_move(th.d, gd, ss.mp, s);
         if (ss.mp.refill) launch_reset_trees(th.d, gd.need_reset, s);
-        HIPCHK(hipMemcpyAsync(h_ctr, gd.counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_ctr, gd.counters, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         resolve_profile(e);
         ss.active = (int)h_ctr[2];
         ss.rows_typ = h_ctr[3] ? (int)std::min<uint32_t>(h_ctr[3], (uint32_t)(C * T)) : 0;      // this move's largest batch
-        HIPCHK(hipMemsetAsync(gd.counters + 3, 0, sizeof(uint32_t), s));
+        if (th.d.cap.word) ss.round_sims = h_ctr[4] ? (int)std::min<uint32_t>(h_ctr[4], (uint32_t)p->num_sims) : p->num_sims;
+        HIPCHK(hipMemsetAsync(gd.counters + 3, 0, 2 * sizeof(uint32_t), s));
         if (h_ctr[1] >= want) { ++ss.iter; break; }
         if ((ss.iter & 7) == 7 || h_ctr[2] == 0) {
             result = check_tree_errors(e, th);
@@ -1947,11 +1984,21 @@ static az_status selfplay_emit(az_engine* e, SelfplaySession& ss, int lo, int hi
     const int n = hi - lo, nsym = p->symmetries ? 2 : 1;
     std::vector<int32_t> glen((size_t)n);
     HIPCHK(hipMemcpy(glen.data(), gd.g_len + lo, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    // the full-ply masks: what az_selfplay_get_full_plies returns.  Without a playout cap every ply is a full move.
+    std::vector<uint64_t>& full = e->sp_full_plies;
+    full.assign((size_t)n, 0ull);
+    if (gd.g_full) HIPCHK(hipMemcpy(full.data(), gd.g_full + lo, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     std::vector<int64_t> off((size_t)n);
-    int64_t total = 0;
-    for (int i = 0; i < n; ++i) { off[(size_t)i] = total; total += glen[(size_t)i]; }
+    int64_t total = 0, plies = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint64_t all = (1ull << glen[(size_t)i]) - 1ull;
+        full[(size_t)i] = gd.g_full ? (full[(size_t)i] & all) : all;
+        off[(size_t)i] = total;
+        total += (int64_t)__builtin_popcountll(full[(size_t)i]);          // recorded plies (== game_len without a cap)
+        plies += glen[(size_t)i];
+    }
     e->stats.games += (uint64_t)n;
-    e->stats.moves += (uint64_t)total;
+    e->stats.moves += (uint64_t)plies;
     e->stats.samples += (uint64_t)total;
     out->count = total * nsym;
     if (out->capacity < out->count) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay: sample buffers too small");
@@ -1969,6 +2016,7 @@ static az_status selfplay_emit(az_engine* e, SelfplaySession& ss, int lo, int hi
         view.n_games = n;
         view.smp_state += (size_t)lo * 42; view.smp_pi += (size_t)lo * 42 * 7; view.smp_player += (size_t)lo * 42; view.moves += (size_t)lo * 42;
         view.g_len += lo; view.g_result += lo; view.g_final_player += lo;
+        if (view.g_full) view.g_full += lo;
         launch_emit_samples(view, d_off, p->symmetries, d_states, d_boards, d_pis, d_zs, s);
         HIPCHK(hipStreamSynchronize(s));
         if (d_states) HIPCHK(hipMemcpy(out->states, d_states, cnt * 16, hipMemcpyDefault));
@@ -2048,6 +2096,13 @@ az_status az_selfplay(az_engine* e, const az_selfplay_params* p, az_samples* out
         HIPCHK(hipStreamSynchronize(e->stream));
         return st;
     } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+az_status az_selfplay_get_full_plies(az_engine* e, uint64_t* mask) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!mask) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay_get_full_plies: null mask");
+    if (!e->sp_full_plies.empty()) std::memcpy(mask, e->sp_full_plies.data(), e->sp_full_plies.size() * sizeof(uint64_t));
+    return AZ_OK;
 }
 
 az_status az_selfplay_get_evals(az_engine* e, int32_t* rec_count, uint64_t* states, float* pis, float* vs) {

@@ -18,6 +18,7 @@
 #pragma once
 #include "az_common.h"
 #include "az_game.h"
+#include "az_playout.h"
 
 namespace az {
 
@@ -68,6 +69,19 @@ struct RootNoise {
     const ulonglong2* stream;    // [G] (seed, game_id) or nullptr
 };
 
+// Playout cap randomization ("playout_cap_sims" / "playout_cap_full_e6", include/az_engine.h; the predicate: az_playout.h).  Self-play only.
+// word == nullptr is OFF: the launchers then pick the kernels' instantiations without a budget (PC = false), which contain none of this.
+// word[g] = the budget of slot g's current move | PLAYOUT_FULL_BIT when that move is a full one.  It is written when the slot's previous
+// move is played (selfplay_move_body; the host writes ply 0 of the first episodes) and read when the move's root is prepared.  The lock-step
+// kernels count the move's simulations down in the upper 31 bits of TreeHead.active (active = 1 | left << 1, set by k_sync_active); the
+// free-running kernel compares GamesDev.sims with the budget.
+struct PlayoutCap {
+    uint32_t* word;              // [G] or nullptr
+    uint32_t num_sims, cap_sims; // N and n
+    uint32_t thresh24;           // playout_cap_thresh24(P)
+    uint32_t pad;                // (no implicit padding: the record is part of the search graph's key)
+};
+
 struct TreeDev {
     int32_t G;               // trees
     uint32_t R;              // slots per tree (a multiple of BLOCK_SLOTS)
@@ -93,6 +107,7 @@ struct TreeDev {
     float* log_v;            // [G*log_cap]
     const int32_t* log_row;  // [G] or nullptr: log row of tree g (az_selfplay: the slot's current episode, so a log survives slot refills); nullptr = g
     RootNoise noise;         // set by the entry point around its searches; zero for the arena
+    PlayoutCap cap;          // set by a self-play session for its own searches; zero everywhere else
 };
 
 // Leaf batch handed to the net (src/async_mcts.rs:117-189 restated as lanes): the DISTINCT states the trees of one
@@ -167,7 +182,9 @@ struct GamesDev {
     float* g_result;         // [n_games] r = get_game_ended(cur_player) at the end (src/coach.rs:144)
     int8_t* g_final_player;  // [n_games]
     int32_t* g_log_len;      // [n_games] or nullptr: eval-log records of the episode (record_evals)
-    // counters: [0] next episode to hand out, [1] episodes finished, [2] active slots
+    unsigned long long* g_full;  // [n_games] or nullptr (playout cap off: every ply is recorded): bit ply = that ply was a full move
+    // counters: [0] next episode to hand out, [1] episodes finished, [2] active slots, [3] largest leaf batch of the round,
+    // [4] playout cap: the largest budget among the moves the slots play NEXT (the lock-step driver runs that many steps)
     uint32_t* counters;
 };
 
@@ -213,6 +230,7 @@ void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch&
                     int first, int last, hipStream_t s);
 // the whole search (root prepare + num_sims simulations + backups) in one launch for the device-function nets
 // (kind 0 = stub, 1 = hash fixture): no leaf batch, no kernel boundary per simulation
+// (with a playout cap, tree g runs its own budget t.cap.word[g] instead of num_sims)
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s);
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,

@@ -318,11 +318,15 @@ AZ_D float root_noise_mix(const TreeDev& t, int g, typename G::State s, uint32_t
     return noise_mix(t.noise.eps, prior, root_noise_eta_lane<G>(stream, t.noise.alpha, nchild, myact, sub));
 }
 
+// Playout cap (az_tree.h PlayoutCap): a slot's fast moves get no noise; without a cap every move does.  Only NZ code reads this.
+AZ_D bool move_noisy(const TreeDev& t, int g) { return !t.cap.word || (t.cap.word[g] & PLAYOUT_FULL_BIT) != 0u; }
+
 // ---- get_action_prob prologue: root lookup (src/async_mcts.rs:81) + S10 + S1 -------------
 // NZ: root noise is on.  A root that already has its prior gets the noise here; one that is evaluated first (LEAF_ROOT) gets it in its
 // backup, right after the prior is stored -- once per get_action_prob either way, before the call's first selection.
+// noisy (read by the NZ instantiations only): this tree's move gets the noise (false: a fast move under a playout cap)
 template <class G, bool NZ = false>
-AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ulonglong2* root_states, int g, int sub) {
+AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ulonglong2* root_states, int g, int sub, bool noisy = true) {
     const bool act = h.active != 0;
     size_t base = (size_t)g * t.R;
     typename G::State s = act ? root_states[g] : G::init();
@@ -352,7 +356,7 @@ AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ul
                 if (sub == 0) atomicOr(&t.err[ERR_TERMINAL_ROOT], 1u);
             } else if (!(meta & META_HAS_PRIOR)) {
                 kind = LEAF_ROOT;  // S1 (A1): evaluate the root once so best_child has a prior (not a simulation: nothing is backed up)
-            } else if constexpr (NZ) {
+            } else if (NZ && noisy) {
                 const NodeRec rr = node_load(node_ptr(t, base, root));
                 const uint32_t nchild = (rr.meta >> META_NCHILD_SHIFT) & 7u;
                 uint4* cp = node_ptr(t, base, rr.child_base + ((uint32_t)sub < nchild ? (uint32_t)sub : 0u));
@@ -378,7 +382,9 @@ __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, Ev
     int g = tid / GW, sub = tid % GW;
     if (g >= t.G) return;
     TreeHead h = head_load(t, g);
-    const typename G::State s = root_prepare_body<G, NZ>(t, h, root_states, g, sub);
+    bool noisy = true;
+    if constexpr (NZ) noisy = move_noisy(t, g);
+    const typename G::State s = root_prepare_body<G, NZ>(t, h, root_states, g, sub, noisy);
     const uint32_t src = leaf_request<G, MIR>(eb, ec, h.leaf_kind == LEAF_ROOT, s, sub);
     if (h.leaf_kind == LEAF_ROOT) h.src = src;
     if (sub == 0) head_store(t, g, h);
@@ -392,12 +398,13 @@ __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, Ev
 //   S11  every child is Locked: `max_by` on an empty iterator -> `unwrap()` (src/node.rs:366-367)
 //   S12  a link leads to a node that is Locked, i.e. expanded by an earlier thread of this step and still without its prior:
 //        `p.as_ref().unwrap()` (src/node.rs:354)
+// go = false (playout cap only): the tree's move has had its budget -- nothing is selected, the tree asks for no leaf
 template <class G, bool MT = false>
 AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth, const SearchParams& sp, int g, int sub, uint32_t* path,
-                                   uint32_t* abandoned = nullptr) {
+                                   uint32_t* abandoned = nullptr, bool go = true) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
-    const bool act = h.active != 0;
+    const bool act = h.active != 0 && go;
     const size_t base = (size_t)g * t.R;
     bool give_up = false, cur_visited = false;
     uint32_t cur = h.root;
@@ -579,7 +586,7 @@ AZ_D void cache_claim_finish(const EvalCache& ec, CacheClaim c, float pv, int su
 // instead of being read through TreeHead.src -- the fused search of the fixture nets.
 template <class G, bool INLINE_PV = false, bool NZ = false, bool MIR = false>
 AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const EvalBatch& eb, const EvalCache& ec, int g,
-                      int sub, const uint32_t* path, float pv_in = 0.0f) {
+                      int sub, const uint32_t* path, float pv_in = 0.0f, bool noisy = true /*NZ only: see root_prepare_body*/) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
     const uint32_t kind = h.leaf_kind;
@@ -644,7 +651,7 @@ AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const 
         const uint32_t nchild = (lr.meta >> META_NCHILD_SHIFT) & 7u, cb = lr.child_base;
         const uint32_t myact = (uint32_t)sub < nchild ? nth_set_bit<NA>(vm, (uint32_t)sub) : 0u;
         float pa = gshflf<GW>(p, (int)myact);
-        if constexpr (NZ) { if (apply_only) pa = root_noise_mix<G>(t, g, s, nchild, myact, pa, sub); }      // the root's own evaluation: mix the noise in
+        if constexpr (NZ) { if (apply_only && noisy) pa = root_noise_mix<G>(t, g, s, nchild, myact, pa, sub); }      // the root's own evaluation: mix the noise in
         if ((uint32_t)sub < nchild) node_set_prior(node_ptr(t, base, cb + sub), __float_as_uint(pa));   // set_policy, :348
         if (sub == 0) node_set_word(lp, (lr.meta | META_HAS_PRIOR) & ~META_LOCKED, lr.link, lr.child_base);      // set_policy + unlock, :348-351
         h.stat[ST_LEAF_EVALS] += 1;
@@ -736,7 +743,9 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
     if (g >= t.G) return;
     TreeHead h = head_load(t, g);
     const PathRegs pth = path_load(t, g, sub);
-    backup_body<G, false, NZ, MIR>(t, h, pth, eb, ec, g, sub, t.path + (size_t)g * PATH_CAP);
+    bool noisy = true;
+    if constexpr (NZ) noisy = move_noisy(t, g);
+    backup_body<G, false, NZ, MIR>(t, h, pth, eb, ec, g, sub, t.path + (size_t)g * PATH_CAP, 0.0f, noisy);
     h.leaf_kind = LEAF_NONE;
     if (sub == 0) head_store(t, g, h);
 }
@@ -744,7 +753,10 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
 // backup of simulation i and select of simulation i+1 in one launch: both belong to the same 8 lanes of the same tree and
 // nothing else touches that tree in between.  The leaf of i+1 goes into the OTHER eval batch (eb_next; its count was
 // zeroed by the previous launch, this one zeroes eb_prev's), so the two ping-pong.
-template <class G, bool STAMP, bool NZ, bool MIR>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
+// PC (playout cap): TreeHead.active carries the simulations the tree's move has left (1 | left << 1); a tree with none left selects nothing
+// and requests no leaf for the rest of the round -- its last backup above still runs, and its lanes still go through leaf_request's
+// workgroup-wide row claim as an inactive tree's do.  So a replayed graph chunk in which some trees are done is correct as it is.
+template <class G, bool STAMP, bool NZ, bool MIR, bool PC>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
 __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec,
                                                        SearchParams sp, unsigned long long* dbg) {
     constexpr int GW = G::GROUP;
@@ -759,14 +771,19 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     TreeHead h = head_load(t, g);
     PathRegs pth = path_load(t, g, sub);
     AZ_TSTAMP(1);
-    backup_body<G, false, NZ, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * PATH_CAP);
+    bool noisy = true;
+    if constexpr (NZ) noisy = move_noisy(t, g);
+    backup_body<G, false, NZ, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * PATH_CAP, 0.0f, noisy);
     AZ_TSTAMP(2);
     // the counters this tree's other lanes just wrote are read by the selection below
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     AZ_TSTAMP(3);
-    const typename G::State leaf_s = select_body<G>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP);
+    bool go = true;
+    if constexpr (PC) go = (h.active >> 1) != 0u;
+    const typename G::State leaf_s = select_body<G>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, go);
+    if constexpr (PC) { if (go) h.active -= 2u; }
     AZ_TSTAMP(4);
     const uint32_t src = leaf_request<G, MIR>(eb_next, ec, h.leaf_kind == LEAF_EVAL, leaf_s, sub);
     AZ_TSTAMP(5);
@@ -800,7 +817,8 @@ AZ_D void group_memory_sync() {
 struct ThreadRegs { uint32_t leaf, leaf_kind; float leaf_val; uint32_t src, path_len; };
 AZ_D void thread_to_head(TreeHead& h, const ThreadRegs& r) { h.leaf = r.leaf; h.leaf_kind = r.leaf_kind; h.leaf_val = r.leaf_val; h.src = r.src; h.path_len = r.path_len; }
 AZ_D ThreadRegs head_to_thread(const TreeHead& h) { return ThreadRegs{h.leaf, h.leaf_kind, h.leaf_val, h.src, h.path_len}; }
-template <class G, bool NZ, bool MIR>
+// PC (playout cap): as in k_backup_select; a step takes T simulations off what the tree's move has left (budgets are multiples of T)
+template <class G, bool NZ, bool MIR, bool PC>
 __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp, int first, int last) {
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * 64 + threadIdx.x;
@@ -818,7 +836,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
         if (first) {
             PathRegs pth{0u, 0u};
             thread_to_head(h, root_req);
-            backup_body<G, false, true, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * T * PATH_CAP);
+            backup_body<G, false, true, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * T * PATH_CAP, 0.0f, move_noisy(t, g));
             tt0 = T;
         }
     }
@@ -836,6 +854,8 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
         backup_body<G, false, false, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP);
     }
     h.leaf_kind = LEAF_NONE;
+    bool go = !last;
+    if constexpr (PC) go = go && (h.active >> 1) >= (uint32_t)T;
     for (int tt = 0; tt < T; ++tt) {                        // selections in thread order
         group_memory_sync();                                // counters, priors, locks and links written so far are read next
         TreeLine* tl = t.thr + (size_t)g * T + tt;
@@ -844,7 +864,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
         uint32_t abandoned = 0u;
         bool want = false;
         typename G::State leaf_s = G::init();
-        if (!last) {
+        if (go) {
             leaf_s = select_body<G, true>(t, h, pth, sp, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP, &abandoned);
             want = h.leaf_kind == LEAF_EVAL;
         }
@@ -861,6 +881,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
         tl->path16[8 + sub] = pth.hi;
         h.leaf_kind = LEAF_NONE;
     }
+    if constexpr (PC) { if (go) h.active -= 2u * (uint32_t)T; }
     if (sub == 0) head_store(t, g, h);
 }
 
@@ -883,7 +904,8 @@ AZ_D float fixture_row(typename G::State s, int kind, uint64_t salt, int sub) {
     for (int a = 0; a < G::ACTIONS; ++a) out = sub == a ? pi[a] : out;
     return out;
 }
-template <class G, bool NZ>
+// PC (playout cap): tree g runs the budget of its own move, t.cap.word[g], instead of num_sims
+template <class G, bool NZ, bool PC>
 __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind,
                                                        uint64_t salt) {
     constexpr int GW = G::GROUP;
@@ -894,12 +916,15 @@ __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglon
     const EvalCache no_ec{};
     TreeHead h = head_load(t, g);
     PathRegs pth{0u, 0u};
-    typename G::State ls = root_prepare_body<G, NZ>(t, h, root_states, g, sub);
+    bool noisy = true;
+    if constexpr (NZ) noisy = move_noisy(t, g);
+    if constexpr (PC) num_sims = (int)(t.cap.word[g] & ~PLAYOUT_FULL_BIT);
+    typename G::State ls = root_prepare_body<G, NZ>(t, h, root_states, g, sub, noisy);
     for (int i = 0; i <= num_sims; ++i) {
         group_memory_sync();
         // backup of the previous leaf (i == 0: the root's priors only, S1), then the next selection
         const float pv = (h.leaf_kind == LEAF_EVAL || h.leaf_kind == LEAF_ROOT) ? fixture_row<G>(ls, kind, salt, sub) : 0.0f;
-        backup_body<G, true, NZ>(t, h, pth, no_eb, no_ec, g, sub, t.path + (size_t)g * PATH_CAP, pv);
+        backup_body<G, true, NZ>(t, h, pth, no_eb, no_ec, g, sub, t.path + (size_t)g * PATH_CAP, pv, noisy);
         if (i == num_sims) break;
         group_memory_sync();
         ls = select_body<G>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP);
@@ -1058,8 +1083,11 @@ __global__ __launch_bounds__(256) void k_call_readback(unsigned long long* total
 // ---- Coach::execute_episode, one ply of one slot (src/coach.rs:118-156) -------------------
 // Returns 0: the game goes on (gd.state / player / ply advanced); 1: the episode ended and the slot got the next one (its tree must be
 // rebuilt: need_reset); 2: the episode ended and the slot stays idle (h.active = 0).
-template <class G>
-AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, const SelfplayMoveParams& mp, int g, int sub) {
+// PC (playout cap): *word = the slot's word for the move being played (az_tree.h PlayoutCap).  The ply's full flag goes into the episode's
+// mask (k_emit_samples compacts to the full plies; pi / state / player are stored by ply either way), the mode of the slot's NEXT move -- the
+// next ply, or ply 0 of the episode a refilled slot gets -- is drawn, and its word is stored and handed back in *word.
+template <class G, bool PC = false>
+AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, const SelfplayMoveParams& mp, int g, int sub, uint32_t* word = nullptr) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
     const int gi = gd.gid[g];
@@ -1096,7 +1124,9 @@ AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, c
     const typename G::State s2 = G::play(s, action);                        // :140-142
     const uint32_t ec = G::ended_code(s2);                                  // r = get_game_ended(cur_player), :144
     int status = 0;
+    uint32_t next_word = 0u;
     if (sub == 0) {
+        if constexpr (PC) { if (*word & PLAYOUT_FULL_BIT) gd.g_full[gi] |= 1ull << ply; }      // one slot owns an episode: a plain read-modify-write
         gd.smp_state[so] = s;
         gd.smp_player[so] = player;
         gd.moves[so] = (uint8_t)action;
@@ -1128,12 +1158,21 @@ AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, c
             gd.player[g] = (int8_t)-player;
             gd.ply[g] = ply + 1;
         }
+        if constexpr (PC) {
+            if (status != 2) {
+                next_word = status == 1 ? playout_cap_word(mp.seed, mp.first_game_id + (uint64_t)gd.gid[g], 0ull, t.cap.thresh24, t.cap.num_sims, t.cap.cap_sims)
+                                        : playout_cap_word(mp.seed, game_id, (uint64_t)ply + 1ull, t.cap.thresh24, t.cap.num_sims, t.cap.cap_sims);
+                t.cap.word[g] = next_word;
+                atomicMax(&gd.counters[4], next_word & ~PLAYOUT_FULL_BIT);
+            }
+        }
     }
     status = (int)gshfl<GW>((uint32_t)status, 0);
+    if constexpr (PC) *word = gshfl<GW>(next_word, 0);
     if (status == 2) h.active = 0;
     return status;
 }
-template <class G>
+template <class G, bool PC>
 __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, SelfplayMoveParams mp) {
     constexpr int GW = G::GROUP;
     int tid = blockIdx.x * 64 + threadIdx.x;
@@ -1142,7 +1181,9 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
     const int gi = gd.gid[g];
     TreeHead h = head_load(t, g);
     if (gi < 0 || !h.active) return;
-    if (selfplay_move_body<G>(t, h, gd, mp, g, sub) == 2 && sub == 0) t.head[g].head.active = 0;
+    uint32_t word = 0u;
+    if constexpr (PC) word = t.cap.word[g];
+    if (selfplay_move_body<G, PC>(t, h, gd, mp, g, sub, &word) == 2 && sub == 0) t.head[g].head.active = 0;
 }
 
 // ---- FREE-RUNNING self-play: every slot on its own timeline ("selfplay_async") -------------------------------------------------------
@@ -1156,7 +1197,9 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
 // net's rows alone -- the schedule decides when a row is evaluated, never what it is.
 //   gd.sims[g]   simulations of the current move done so far; -1 = the move's root is not prepared yet
 //   first        the first launch behind a forward: eb_prev holds that forward's rows (parked trees back up; its table is cleared)
-template <class G, bool NZ, bool MIR>
+// PC (playout cap): the slot's move ends at its own budget (the word of az_tree.h PlayoutCap, redrawn by every move), and its root gets the
+// noise only when the move is a full one.
+template <class G, bool NZ, bool MIR, bool PC>
 __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp,
                                                     SelfplayMoveParams mp, int num_sims, int first, int max_iters) {
     constexpr int GW = G::GROUP;
@@ -1171,6 +1214,8 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
     PathRegs pth = path_load(t, g, sub);
     uint32_t* path = t.path + (size_t)g * PATH_CAP;
     int sims = gd.sims[g];
+    uint32_t word = 0u;                                                        // PC: the word of the slot's current move
+    if constexpr (PC) word = t.cap.word[g];
     const bool alive = gd.gid[g] >= 0 && h.active != 0 && !gd.need_reset[g];
     // a tree whose leaf waits for a row of the batch being filled stays parked; a leaf answered by the cache (or a value) can go on
     const bool parked = h.leaf_kind != LEAF_NONE && h.leaf_kind != LEAF_VALUE && !(h.src & SRC_CACHE) && !first;
@@ -1181,21 +1226,21 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
             if (h.leaf_kind != LEAF_NONE) {                                    // the pending leaf: store its prior, back its value up
                 const bool was_sim = h.leaf_kind != LEAF_ROOT;
                 group_memory_sync();
-                backup_body<G, false, NZ, MIR>(t, h, pth, eb_prev, ec, g, sub, path);
+                backup_body<G, false, NZ, MIR>(t, h, pth, eb_prev, ec, g, sub, path, 0.0f, !PC || (word & PLAYOUT_FULL_BIT) != 0u);
                 h.leaf_kind = LEAF_NONE;
                 if (was_sim) ++sims;
                 continue;
             }
             group_memory_sync();
             if (sims < 0) {                                                    // get_action_prob's prologue for the slot's position (S10, S1)
-                leaf_s = root_prepare_body<G, NZ>(t, h, gd.state, g, sub);
+                leaf_s = root_prepare_body<G, NZ>(t, h, gd.state, g, sub, !PC || (word & PLAYOUT_FULL_BIT) != 0u);
                 sims = 0;
                 if (!h.active) break;                                          // a failed root (error flag set): the call ends with an error
                 if (h.leaf_kind == LEAF_ROOT) { want = true; break; }
                 continue;
             }
-            if (sims >= num_sims) {                                            // the move (src/coach.rs:128-156), then the next position's root
-                const int st = selfplay_move_body<G>(t, h, gd, mp, g, sub);
+            if (sims >= (PC ? (int)(word & ~PLAYOUT_FULL_BIT) : num_sims)) {      // the move (src/coach.rs:128-156), then the next position's root
+                const int st = selfplay_move_body<G, PC>(t, h, gd, mp, g, sub, &word);
                 sims = -1;
                 if (st != 0) break;                                            // episode over: idle, or wait for k_reset_trees
                 continue;
@@ -1220,15 +1265,26 @@ __global__ __launch_bounds__(256) void k_emit_samples(GamesDev gd, const int64_t
     constexpr int NF = G::FEATURES;
     static_assert(NF > NA + 1, "the item loop below spreads pi / z / state stores over the first feature indices");
     const int gi = blockIdx.x;
-    const int len = gd.g_len[gi];
+    int len = gd.g_len[gi];
     const int nsym = symmetries ? 2 : 1;
+    // playout cap: only the full plies are tuples.  s_ply[k] = the k-th full ply; `len` becomes their number (offsets[] counts them too)
+    __shared__ uint8_t s_ply[G::MAX_PLIES];
+    const bool compact = gd.g_full != nullptr;
+    if (compact) {
+        const unsigned long long fm = gd.g_full[gi] & ((1ull << len) - 1ull);
+        const int p = (int)threadIdx.x;
+        if (p < len && ((fm >> p) & 1ull)) s_ply[__popcll(fm & ((1ull << p) - 1ull))] = (uint8_t)p;
+        __syncthreads();
+        len = __popcll(fm);
+    }
     const float r = gd.g_result[gi];
     const int8_t fin = gd.g_final_player[gi];
     for (int item = threadIdx.x; item < len * nsym * NF; item += blockDim.x) {
         const int f = item % NF, rest = item / NF;
-        const int sym = rest % nsym, ply = rest / nsym;
+        const int sym = rest % nsym, k = rest / nsym;
+        const int ply = compact ? (int)s_ply[k] : k;
         const size_t so = (size_t)gi * G::MAX_PLIES + ply;
-        const int64_t o = (offsets[gi] + ply) * nsym + sym;
+        const int64_t o = (offsets[gi] + k) * nsym + sym;
         typename G::State s = gd.smp_state[so];
         if (sym) s = G::mirror(s);                                             // get_symmetries, connect_four_game.rs:205-211
         if (out_boards) out_boards[o * NF + f] = G::feature(s, f);
@@ -1294,7 +1350,10 @@ __global__ __launch_bounds__(64) void k_arena_move(TreeDev t, ArenaDev ad, uint6
 
 __global__ void k_sync_active(TreeDev t, GamesDev gd) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < t.G) t.head[g].head.active = gd.gid[g] >= 0 ? 1u : 0u;
+    if (g >= t.G) return;
+    uint32_t a = gd.gid[g] >= 0 ? 1u : 0u;
+    if (a && t.cap.word) a |= (t.cap.word[g] & ~PLAYOUT_FULL_BIT) << 1;      // playout cap: the simulations the slot's move has left
+    t.head[g].head.active = a;
 }
 
 // ---- launchers: one instantiation of every kernel per Game policy, chosen by TreeDev.game ------------------------------
@@ -1320,6 +1379,12 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
     do {                                                                                 \
         if ((eb_).mirror) { constexpr bool MIR = true; AZ_FOR_GAME_NZ(t_, __VA_ARGS__); } \
         else { constexpr bool MIR = false; AZ_FOR_GAME_NZ(t_, __VA_ARGS__); }            \
+    } while (0)
+// ... and per playout cap: PC = true only for the searches of a self-play session that has one
+#define AZ_FOR_PC(t_, ...)                                                               \
+    do {                                                                                 \
+        if ((t_).cap.word) { constexpr bool PC = true; __VA_ARGS__; }                    \
+        else { constexpr bool PC = false; __VA_ARGS__; }                                 \
     } while (0)
 static inline int group_blocks(int G) { return (G * BLOCK_SLOTS + 63) / 64; }
 #ifdef AZ_DIAG
@@ -1377,20 +1442,20 @@ void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const Eval
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
 #ifdef AZ_DIAG
     if (g_tree_dbg && t.G * 8 / 64 <= TREE_DBG_WAVES) {
-        AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg));
+        AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR, PC>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg)));
         return;
     }
 #endif
-    AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr));
+    AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR, PC>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr)));
 }
 void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                     int first, int last, hipStream_t s) {
     // one wave per workgroup: leaf_request is called T times per launch and its one-atomic-per-workgroup path keeps state in LDS
-    AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_step_mt<TG, NZ, MIR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last));
+    AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_step_mt<TG, NZ, MIR, PC>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last)));
 }
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s) {
-    AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt));
+    AZ_FOR_PC(t, AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ, PC>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt)));
 }
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,
                         uint16_t* counts, float* q, hipStream_t s) {
@@ -1418,13 +1483,13 @@ void launch_call_readback(unsigned long long* totals, unsigned long long* dd_sta
     hipLaunchKernelGGL(k_call_readback, dim3(1), dim3(256), 0, s, totals, dd_stat, err, out);
 }
 void launch_selfplay_move(const TreeDev& t, const GamesDev& gd, SelfplayMoveParams mp, hipStream_t s) {
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_selfplay_move<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, mp));
+    AZ_FOR_PC(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_selfplay_move<TG, PC>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, mp)));
 }
 void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s) {
     const bool four = t.block4 && (t.G * 8) % 256 == 0;
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
-    AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_async_step<TG, NZ, MIR>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters));
+    AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_async_step<TG, NZ, MIR, PC>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters)));
 }
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s) {
     hipLaunchKernelGGL(k_sync_active, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gd);

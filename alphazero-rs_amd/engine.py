@@ -86,7 +86,7 @@ EXPORTS = [
     "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
-    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
+    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
     "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
 COMM_ID_BYTES = 128
@@ -142,6 +142,7 @@ def load_library(path=LIB_PATH):
         "az_selfplay_next": (i32, [vp, C.c_int32, C.POINTER(az_samples)]),
         "az_selfplay_end": (i32, [vp]),
         "az_selfplay_get_evals": (i32, [vp, vp, vp, vp, vp]),
+        "az_selfplay_get_full_plies": (i32, [vp, vp]),
         "az_arena": (i32, [vp, C.POINTER(az_arena_params), vp, vp]),
         "az_arena_get_evals": (i32, [vp, i32, vp, vp, vp, vp]),
         "az_arena_get_moves": (i32, [vp, vp, vp]),
@@ -321,6 +322,21 @@ class Engine:
         self.set_option("root_noise_alpha_e6", int(round(float(alpha) * 1e6)))
         self.set_option("root_noise_eps_e6", int(round(float(eps) * 1e6)))
 
+    def set_playout_cap(self, sims, p_full=0.25):
+        """Playout cap randomization of self-play (never the arena or the tree calls): a share p_full of an episode's moves is searched
+        with the full num_sims, gets root noise if that is on and is recorded; every other move is searched with `sims` simulations and
+        only played.  sims = 0 switches it off (the default); the values travel as "playout_cap_sims" / "playout_cap_full_e6"
+        (include/az_engine.h)."""
+        self.set_option("playout_cap_full_e6", int(round(float(p_full) * 1e6)))
+        self.set_option("playout_cap_sims", int(sims))
+
+    def selfplay_full_plies(self):
+        """az_selfplay_get_full_plies: uint64 [n], bit `ply` of word i set when that ply of the i-th episode of the last selfplay() /
+        selfplay_next() call was a full move, i.e. became a tuple (all plies when the playout cap is off)."""
+        mask = np.zeros(self._sp_last_n, np.uint64)
+        self._check(self._lib.az_selfplay_get_full_plies(self._h, _ptr(mask)))
+        return mask
+
     def root_noise_eta(self, states, game_ids, seed=0):
         """az_root_noise_eta: eta [n,7] the device sampler draws for root states [n,2] on the streams (seed, game_ids[i], stones),
         at the engine's current alpha."""
@@ -370,6 +386,7 @@ class Engine:
         s = az_samples(cap, 0, _as_ptr(out.get("states")), _as_ptr(out.get("boards")), _as_ptr(out["pis"]),
                        _as_ptr(out["zs"]), _ptr(game_len), _ptr(moves))
         self._check(self._lib.az_selfplay(self._h, C.byref(p), C.byref(s)))
+        self._sp_last_n = n_games
         n = int(s.count)
         res = {"count": n, "game_len": game_len, "moves": moves}
         for k in ("states", "boards", "pis", "zs"):
@@ -404,6 +421,7 @@ class Engine:
         s = az_samples(cap, 0, _as_ptr(out.get("states")), _as_ptr(out.get("boards")), _as_ptr(out["pis"]),
                        _as_ptr(out["zs"]), _ptr(game_len), _ptr(moves))
         self._check(self._lib.az_selfplay_next(self._h, n_games, C.byref(s)))
+        self._sp_last_n = n_games
         n = int(s.count)
         res = {"count": n, "game_len": game_len, "moves": moves}
         for k in ("states", "boards", "pis", "zs"):

@@ -1,10 +1,12 @@
 // examples/connect_four.rs (src lines 45-80) on the C++ host: the same Coach::setup parameters, the engine behind it.
 // Build:  g++ -std=c++17 -O2 -I include examples/connect_four.cpp -o connect_four -L alphazero-rs_amd -laz_engine
 //         (and -Wl,-rpath,$PWD/alphazero-rs_amd)
-// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror]
+// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap]
 //         selfplay_fp8 = 1: the episodes are played in the fp8 class, the arena gate in bf16 (Coach::selfplay_class)
 //         root_noise_eps > 0 (e.g. 0.25, with root_noise_alpha 0.3; default alpha 1): Dirichlet root noise in the episodes (Coach::root_noise_eps)
 //         eval_mirror = 1: mirror-canonical leaf evaluation for the whole loop, episodes and gate (Coach::eval_mirror)
+//         playout_cap = N,P (e.g. 20,0.25): playout cap randomization in the episodes -- a share P of the moves gets the full num_sims and is
+//         recorded, every other move gets N simulations and is only played (Coach::playout_cap_sims / playout_cap_full)
 #include <cstdio>
 #include <cstdlib>
 
@@ -20,6 +22,10 @@ int main(int argc, char** argv) {
     const bool selfplay_fp8 = argc > 6 && std::strtoul(argv[6], nullptr, 10) != 0;
     const double noise_eps = argc > 7 ? std::atof(argv[7]) : 0.0, noise_alpha = argc > 8 ? std::atof(argv[8]) : 1.0;
     const bool eval_mirror = argc > 9 && std::strtoul(argv[9], nullptr, 10) != 0;
+    const std::string cap = argc > 10 ? argv[10] : "";
+    const size_t comma = cap.find(',');
+    const long cap_sims = cap.empty() ? 0 : std::strtol(cap.c_str(), nullptr, 10);
+    const double cap_full = comma == std::string::npos ? 0.25 : std::atof(cap.c_str() + comma + 1);
     try {
         Engine e(0, 8192, 512);
         if (az_net_load(e.raw(), 0, (dir + "/0.aznet").c_str()) != AZ_OK) e.check(az_net_init_random(e.raw(), 0, 0));
@@ -28,6 +34,7 @@ int main(int argc, char** argv) {
         if (selfplay_fp8) coach.selfplay_class = AZ_NET_CLASS_FP8;
         coach.eval_mirror = eval_mirror;
         coach.root_noise_eps = noise_eps; coach.root_noise_alpha = noise_alpha;
+        coach.playout_cap_sims = cap_sims; coach.playout_cap_full = cap_full;
         for (const auto& r : coach.learn(false, /*seed*/ 0))
             std::printf("iteration %zu: %zu samples, new/prev/draw %zu/%zu/%zu, %s, loss (%.4f, %.4f)\n", r.iteration, r.samples, r.nwins,
                         r.pwins, r.draws, r.accepted ? "accepted" : "rejected", r.losses.empty() ? 0.f : r.losses[r.losses.size() - 2],

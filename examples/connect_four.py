@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--trainer", default="engine", choices=["engine", "torch"])   # NNet::train: az_net_train or autograd
     ap.add_argument("--epochs", type=int, default=10)        # connect_four_net.py:13
     ap.add_argument("--selfplay-fp8", action="store_true")   # episodes in the fp8 class, the arena gate in bf16 (Coach.selfplay_class)
+    ap.add_argument("--playout-cap", default=None, metavar="N,P")        # playout cap randomization of the episodes, e.g. 20,0.25 (Coach.playout_cap_sims)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
     ap.add_argument("--eval-mirror", action="store_true")    # mirror-canonical leaf evaluation for the whole loop (Coach.eval_mirror)
     a = ap.parse_args()
@@ -55,6 +56,9 @@ def main():
     if a.root_noise:
         eps, _, alpha = a.root_noise.partition(",")
         coach.root_noise_eps, coach.root_noise_alpha = float(eps), float(alpha) if alpha else 1.0
+    if a.playout_cap:
+        n, _, p = a.playout_cap.partition(",")
+        coach.playout_cap_sims, coach.playout_cap_full = int(n), float(p) if p else 0.25
     for r in coach.learn(skip_first_play=False, seed=a.seed):
         print(r["iteration"], "samples", r["samples"], "new/prev/draw", r["nwins"], r["pwins"], r["draws"],
               "accepted" if r["accepted"] else "rejected", "loss", r["losses"][-1],

@@ -217,6 +217,35 @@ const char* az_last_error(const az_engine* e);
  *                                        -O2 -ffp-contract=off) and device builds of csrc/az_noise.h give the same bits
  *                           A captured search graph is keyed on the noise arguments, so one captured with others is never replayed.
  *                           az_root_noise_eta returns eta for given roots (what a host needs to reconstruct a recorded game's noise)
+ *   playout cap "playout_cap_sims"  n: 0 (default, OFF), otherwise 1 .. 65535
+ *            "playout_cap_full_e6" P: 0 .. 1000000 (default 250000)
+ *                           PLAYOUT CAP RANDOMIZATION of self-play (KataGo), strictly opt-in: most moves of an episode are searched with
+ *                           n simulations and are played but not recorded; a random share P / 1e6 of the moves gets the full budget
+ *                           num_sims, gets root noise if that is on, and is recorded as a training tuple.  With n = 0 (set or never
+ *                           set) every output and every counter of every entry is bit for bit what it is without the feature, whatever
+ *                           P is.  Values out of range and any change while a self-play session is open are refused
+ *                           (AZ_ERR_BAD_ARGUMENT); az_selfplay / az_selfplay_begin refuse n >= num_sims and n % num_sim_threads != 0.
+ *                           State of the engine, like every option.  The contract (csrc/az_playout.h), for the
+ *                           move of episode game_id at ply (= stones on the board: the triple of the tie-break and move streams):
+ *                             mode       full = (rng_draw(seed, game_id, ply, 6) >> 40) < thresh24, thresh24 = (P * 2^24) / 1000000 in
+ *                                        unsigned 64-bit arithmetic.  P = 1000000: every move is full and the output is bit for bit that
+ *                                        of the feature off; P = 0: every move is fast and an episode emits no tuple (legal)
+ *                             full move  exactly the move without the feature: num_sims simulations, root noise mixed in if
+ *                                        "root_noise_eps_e6" > 0, tuple recorded
+ *                             fast move  get_action_prob with n simulations on the episode's same persistent tree; no root noise (the
+ *                                        root's stored prior is not touched); pi from the counts as always (temperature by ply, the
+ *                                        tie-break stream unchanged); the move is sampled from pi with the unchanged move draw and goes
+ *                                        into moves[] / game_len; NO tuple
+ *                             samples    game-id order then ply order, full plies only: count = full plies x (2 if symmetries); z is
+ *                                        the game's result from the recorded player's side as always.  az_stats.moves counts every ply,
+ *                                        az_stats.samples the recorded ones, az_stats.simulations the budgets actually run
+ *                             where      az_selfplay and sessions on every path (lock-step, "fused_search" 0 / 1, every "eval_dedup",
+ *                                        num_sim_threads > 1, "selfplay_async", slot refill, both games, fp8 and "eval_mirror" models).
+ *                                        NEVER az_arena, az_tree_* or the slot calls: they return what they return without the keys
+ *                             eval log   record_evals keeps recording every predict of the episode, fast moves included
+ *                             bounds     tree capacity, hash and cache sizes stay those of num_sims (an upper bound of any move)
+ *                           A captured search graph is keyed on the playout-cap arguments, so one captured with others is never
+ *                           replayed.  az_selfplay_get_full_plies returns which plies were full (to line tuples up with moves[])
  *   search   "search_graph" n (default 20, even, 0 = off): n simulation steps per captured hipGraph replay (conv nets) ...
  *            "search_graph_rows" n (default 1024): ... for searches whose expected leaf batch has at most n rows (the arena, the drain
  *                           of a self-play call, single trees: there the host's launch calls set the pace; on big batches the kernels do)
@@ -445,6 +474,10 @@ az_status az_selfplay(az_engine* e, const az_selfplay_params* p, az_samples* out
 az_status az_selfplay_begin(az_engine* e, const az_selfplay_params* p);
 az_status az_selfplay_next(az_engine* e, int32_t n_games, az_samples* out);
 az_status az_selfplay_end(az_engine* e);
+/* Which plies of the episodes of the last az_selfplay / az_selfplay_next call were FULL moves ("playout_cap_sims" above), i.e. became
+ * tuples: bit `ply` of mask[i] for the i-th episode of that call (42 plies fit a word).  All ones up to game_len when the feature is
+ * off.  mask holds as many words as that call returned episodes. */
+az_status az_selfplay_get_full_plies(az_engine* e, uint64_t* mask /* [n_games] */);
 /* Eval log of the last az_selfplay with record_evals > 0: rec_count [n_games], states [n_games,cap,2], ... */
 az_status az_selfplay_get_evals(az_engine* e, int32_t* rec_count, uint64_t* states, float* pis, float* vs);
 

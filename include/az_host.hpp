@@ -125,6 +125,20 @@ class Engine {
         check(az_set_option(e_, "root_noise_alpha_e6", (int64_t)std::llround(alpha * 1e6)));
         check(az_set_option(e_, "root_noise_eps_e6", (int64_t)std::llround(eps * 1e6)));
     }
+    // Playout cap randomization of self-play, never of the arena or the tree calls ("playout_cap_sims" / "playout_cap_full_e6",
+    // include/az_engine.h): a share p_full of an episode's moves is searched with the full num_sims and recorded, every other move with
+    // `sims` simulations and only played.  sims = 0 switches it off
+    void set_playout_cap(int64_t sims, double p_full = 0.25) {
+        check(az_set_option(e_, "playout_cap_full_e6", (int64_t)std::llround(p_full * 1e6)));
+        check(az_set_option(e_, "playout_cap_sims", sims));
+    }
+    // az_selfplay_get_full_plies: bit `ply` of word i = that ply of the i-th episode of the last az_selfplay / az_selfplay_next call
+    // (n_games episodes) was a full move and became a tuple
+    std::vector<uint64_t> selfplay_full_plies(size_t n_games) const {
+        std::vector<uint64_t> mask(n_games, 0);
+        check(az_selfplay_get_full_plies(e_, mask.data()));
+        return mask;
+    }
 
   private:
     az_engine* e_ = nullptr;
@@ -518,6 +532,12 @@ class Coach {
                         NoiseGuard(Engine& e_, double eps_, double alpha_) : e(e_), eps(eps_), alpha(alpha_) { if (eps > 0) e.set_root_noise(eps, alpha); }
                         ~NoiseGuard() { if (eps > 0) { try { e.set_root_noise(0.0, alpha); } catch (...) {} } }
                     } guard(e_, root_noise_eps, root_noise_alpha);
+                    // ... and so is the playout cap
+                    struct CapGuard {
+                        Engine& e; int64_t sims; double p;
+                        CapGuard(Engine& e_, int64_t sims_, double p_) : e(e_), sims(sims_), p(p_) { if (sims > 0) e.set_playout_cap(sims, p); }
+                        ~CapGuard() { if (sims > 0) { try { e.set_playout_cap(0, p); } catch (...) {} } }
+                    } cap_guard(e_, playout_cap_sims, playout_cap_full);
                     h = execute_episodes(model_id, iteration, seed);
                 }
                 if (h.len() > max_queue_length) {                   // keep the newest max_queue_length (:275-277)
@@ -601,6 +621,10 @@ class Coach {
     // Dirichlet root noise of the episodes (Engine::set_root_noise): set before every az_selfplay and cleared behind it.  eps 0 (the
     // default): the engine is never asked
     double root_noise_eps = 0.0, root_noise_alpha = 1.0;
+    // Playout cap randomization of the episodes (Engine::set_playout_cap): set before every az_selfplay and cleared behind it.  sims 0
+    // (the default): the engine is never asked.  An iteration then yields the tuples of the full moves only
+    int64_t playout_cap_sims = 0;
+    double playout_cap_full = 0.25;
     // "eval_mirror" (Engine::set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
     // run under the mirror-canonical function, so the gate compares like with like.  false (the default): the engine is never asked
     bool eval_mirror = false;

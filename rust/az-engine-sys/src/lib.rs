@@ -104,6 +104,9 @@ extern "C" {
     pub fn az_selfplay_begin(e: *mut az_engine, p: *const az_selfplay_params) -> c_int;
     pub fn az_selfplay_next(e: *mut az_engine, n_games: i32, out: *mut az_samples) -> c_int;
     pub fn az_selfplay_end(e: *mut az_engine) -> c_int;
+    /// bit `ply` of mask[i]: that ply of the i-th episode of the last az_selfplay / az_selfplay_next was a full move and became a tuple
+    /// ("playout_cap_sims" / "playout_cap_full_e6"; all plies when the playout cap is off)
+    pub fn az_selfplay_get_full_plies(e: *mut az_engine, mask: *mut u64) -> c_int;
     pub fn az_selfplay_get_evals(e: *mut az_engine, rec_count: *mut i32, states: *mut u64, pis: *mut f32, vs: *mut f32) -> c_int;
     pub fn az_arena(e: *mut az_engine, p: *const az_arena_params, out_wld: *mut u64, results: *mut i8) -> c_int;
     pub fn az_arena_get_evals(e: *mut az_engine, which: i32, rec_count: *mut i32, states: *mut u64, pis: *mut f32, vs: *mut f32) -> c_int;
