@@ -2623,6 +2623,18 @@ long long az_diag_read_conv3_out(az_engine* e, int rows, void* out) {
     if (!e || !out || rows <= 0 || hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;
     return netws_read_conv3_out(e->ws[0], rows, out);
 }
+// Diagnostic library only: any layer's activations of the last forward on the engine's first stream (layer 1 act1 .. 6 fc2o, bf16:
+// netws_read_act), and rows of a model's conv1 / conv2 tables (convnet_read_conv_table).  Bytes copied, or -1.
+long long az_diag_read_act(az_engine* e, int layer, int rows, void* out) {
+    if (!e || !out || rows <= 0 || hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;
+    return netws_read_act(e->ws[0], layer, rows, out);
+}
+long long az_diag_read_conv_table(az_engine* e, int32_t model_id, int which, int first_row, int n_rows, void* out) {
+    if (!e || !out || hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
+    auto it = e->nets.find(model_id);
+    if (it == e->nets.end() || !it->second.conv) return -1;
+    return convnet_read_conv_table(it->second.conv, which, first_row, n_rows, out);
+}
 // Diagnostic library only: the same for a "net_fp8" engine -- `rows` boards of [4][5][C] e4m3 codes; and a model's (sa2, sa3)
 long long az_diag_read_conv3_out_fp8(az_engine* e, int rows, void* out) {
     if (!e || !out || rows <= 0 || hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;

@@ -101,6 +101,15 @@ struct NetOptions {
 bool netws_read_clock_stamps(NetWorkspace* ws, unsigned long long* out2048);
 // diagnostic library's reader: conv3's output of the workspace's last forward, rows x [4][5][C] bf16 -> out; returns the bytes copied or -1
 long long netws_read_conv3_out(NetWorkspace* ws, int rows, void* out);
+#ifdef AZ_DIAG
+// diagnostic library's reader: one layer's activations of the workspace's last forward, `rows` rows of bf16 -> out; returns the bytes
+// copied or -1.  layer 1 act1 [8][9][C] (-1 if never allocated), 2 act2 [42][C], 3 act3 [20][C], 4 act4 [6][C], 5 fc1o [1024],
+// 6 fc2o [512].  Under net_fp8, act2 and act3 hold e4m3 bytes: these bf16 readers are meaningless there (use the _fp8 readers).
+long long netws_read_act(NetWorkspace* ws, int layer, int rows, void* out);
+// diagnostic library's reader: rows [first_row, first_row + n_rows) of a model's conv1 table t1 (which = 1: [19683] rows of [C] bf16)
+// or conv2 table u2 (which = 2: [19683 + 1] rows of [9][C] f16, the last one the appended zero row); the bytes copied or -1
+long long convnet_read_conv_table(const ConvNet* n, int which, int first_row, int n_rows, void* out);
+#endif
 // "net_fp8": the e4m3 conv3 output of the workspace's last forward, rows x [4][5][C] bytes -> out (diagnostic library's reader)
 long long netws_read_conv3_out_fp8(NetWorkspace* ws, int rows, void* out);
 // ... and its e4m3 conv2 output, rows x [6][7][C] bytes

@@ -2140,6 +2140,26 @@ long long netws_read_conv3_out(NetWorkspace* n, int rows, void* out) {
     return hipMemcpy(out, n->act3, bytes, hipMemcpyDeviceToHost) == hipSuccess ? (long long)bytes : -1;
 }
 
+#ifdef AZ_DIAG
+long long netws_read_act(NetWorkspace* n, int layer, int rows, void* out) {
+    if (!n || rows <= 0 || rows > n->max_batch || layer < 1 || layer > 6) return -1;
+    const uint16_t* src[6] = {n->act1, n->act2, n->act3, n->act4, n->fc1o, n->fc2o};
+    const size_t per_row[6] = {72 * (size_t)n->C, 42 * (size_t)n->C, 20 * (size_t)n->C, 6 * (size_t)n->C, 1024, 512};
+    if (!src[layer - 1]) return -1;                     // act1 is only allocated by the kernel sets that run conv1 as a kernel
+    const size_t bytes = (size_t)rows * per_row[layer - 1] * sizeof(uint16_t);
+    return hipMemcpy(out, src[layer - 1], bytes, hipMemcpyDeviceToHost) == hipSuccess ? (long long)bytes : -1;
+}
+
+long long convnet_read_conv_table(const ConvNet* n, int which, int first_row, int n_rows, void* out) {
+    if (!n || !out || (which != 1 && which != 2) || first_row < 0 || n_rows <= 0) return -1;
+    const int total = which == 1 ? CONV1_PATTERNS : CONV1_PATTERNS + 1;
+    if (first_row >= total || n_rows > total - first_row) return -1;
+    const size_t row = (which == 1 ? (size_t)n->C : 9 * (size_t)n->C) * sizeof(uint16_t);
+    const char* src = (const char*)(which == 1 ? n->t1 : n->u2) + (size_t)first_row * row;
+    return hipMemcpy(out, src, (size_t)n_rows * row, hipMemcpyDeviceToHost) == hipSuccess ? (long long)((size_t)n_rows * row) : -1;
+}
+#endif
+
 long long netws_read_conv3_out_fp8(NetWorkspace* n, int rows, void* out) {
     if (!n || rows <= 0 || rows > n->max_batch) return -1;
     const size_t bytes = (size_t)rows * 20 * n->C;

@@ -151,6 +151,11 @@ const char* az_last_error(const az_engine* e);
  *                           which is one of 3^9 table rows per position; 198 of the net's 329 MFLOP per leaf are never executed);
  *                           0: conv2 as the MFMA implicit GEMM -- the same function with its own rounding (each batch-independent and
  *                           within the stated tolerance of the fp32 reference)
+ *                           Range of the table set: a table entry u (one tap's sum over the input channels of conv2's folded weight
+ *                           times conv1's output, before the bias) is stored in f16 -- relative error 2^-11 for |u| >= 2^-14,
+ *                           absolute 2^-25 below that, and |u| must stay below 65504.  The scale of conv1's activations alone does
+ *                           not matter (conv1 x 2^k with conv2's weights x 2^-k leaves every u unchanged; held for k = -12 .. 12 by
+ *                           tests/test_net_layers_gpu.py); a net whose per-tap conv2 sums leave that range wants "conv2_table" 0
  *            "conv3_small"  1 (default): conv3 of a small expected batch runs on the 4-stage LDS-DMA ring; 0: never.  Bit-identical
  *            "conv3_tail"   1 (default): a short last round of conv3 workgroups is cut into half tiles; 0: full tiles.  Bit-identical
  *            "conv3_planes" 1 (default): conv3's LDS image in the bank-conflict-free layout; 0: image rows in order.  Bit-identical

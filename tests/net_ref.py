@@ -71,6 +71,30 @@ def random_params(C, seed, bn_random=True):
     return p
 
 
+def exact_params(channels, seed, head_shift=18):
+    """Integer-valued parameters: BatchNorm folds to exactly 1 (var + eps == 1 in f32), sparse small-integer weights and biases, head
+    weights a power of two (2^-head_shift) small enough for O(1) logits.  Every partial sum of every layer is then an integer far below 2^24 times
+    its quantum, exact in f32 in any order -- and the random sparsity pattern has no symmetry a row / column or k mix-up could hide in."""
+    g = np.random.default_rng(seed)
+    off, total = layout(channels)
+    p = np.zeros(total, np.float32)
+    dens = {"conv1_w": (0.25, [1]), "conv2_w": (1 / 16, [-1, 1]), "conv3_w": (1 / 16, [-2, -1, 1, 2]), "conv4_w": (1 / 16, [-2, -1, 1, 2]),
+            "fc1_w": (1 / 32, [-1, 1]), "fc2_w": (1 / 32, [-1, 1]), "pi_w": (1 / 4, [-1, 1]), "v_w": (1 / 4, [-1, 1])}
+    for k, (o, shp) in off.items():
+        n = int(np.prod(shp))
+        if k.endswith("_w"):
+            d, vals = dens[k]
+            w = g.choice(vals, n) * (g.random(n) < d)
+            p[o:o + n] = w * 2.0 ** -head_shift if k in ("pi_w", "v_w") else w
+        elif k.endswith("_b"):
+            p[o:o + n] = 0 if k in ("pi_b", "v_b") else g.integers(-2, 2, n)
+        else:
+            c = shp[1]
+            p[o:o + c] = 1.0
+            p[o + 3 * c:o + 4 * c] = np.float32(1.0) - np.float32(1e-3)
+    return p
+
+
 def forward_ref(params, boards, C, emulate_bf16=True):
     """boards [B,2,6,7] f32 -> (pi [B,7], v [B]) in f32 on the CPU."""
     P = unpack(np.asarray(params, np.float32), C)

@@ -7,6 +7,9 @@ f32 accumulation order inside the MFMA tiles, which now and then flips a bf16 ro
 Against the textbook f32 net with explicit BatchNorm the bf16 weight/activation rounding is added
 (measured 6e-4 / 3e-3) -> bar |dpi| <= 5e-3, |dv| <= 1.5e-2.  An indexing / tap / fragment-layout bug shows
 up as O(0.1-1) errors, far above either bar.
+
+These bars are on (pi, v), six layers behind conv3: a whole wrong tap shows, one wrong channel or one dropped K-step of one column
+tile need not.  Element-level errors of every layer and of both conv tables are held by tests/test_net_layers_gpu.py.
 """
 import os
 
