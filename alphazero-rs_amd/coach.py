@@ -62,6 +62,9 @@ class Coach:
         # Playout cap randomization of the episodes (Engine.set_playout_cap): switched on before every az_selfplay and off again behind it,
         # exactly as the root noise is.  sims 0 (the default): the engine is never asked.  An iteration then yields the full moves' tuples only
         self.playout_cap_sims, self.playout_cap_full = 0, 0.25
+        # Forced playouts and policy target pruning of the episodes (Engine.set_forced_playouts): switched on before every az_selfplay and
+        # off again behind it, exactly as the playout cap is.  k 0 (the default): the engine is never asked
+        self.forced_playouts_k, self.policy_prune = 0.0, False
         # "eval_mirror" (Engine.set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
         # run under the mirror-canonical function F, so the gate compares like with like.  False (the default): the engine is never asked
         self.eval_mirror = False
@@ -115,6 +118,16 @@ class Coach:
             if self.playout_cap_sims > 0:
                 self.engine.set_playout_cap(0, self.playout_cap_full)
 
+    @contextlib.contextmanager
+    def _selfplay_forced_playouts(self):
+        if self.forced_playouts_k > 0:
+            self.engine.set_forced_playouts(self.forced_playouts_k, self.policy_prune)
+        try:
+            yield
+        finally:
+            if self.forced_playouts_k > 0:
+                self.engine.set_forced_playouts(0.0, False)
+
     def execute_episodes(self, model_id, iteration, seed):
         """The self-play fan-out of src/coach.rs:241-272: num_eps x execute_episode, sharded by global game id."""
         from . import dist as azdist
@@ -122,7 +135,7 @@ class Coach:
         lo, hi = azdist.shard_range(self.num_eps, rank, world)
         first = iteration * self.num_eps
         if hi > lo:
-            with self._selfplay_root_noise(), self._selfplay_playout_cap():
+            with self._selfplay_root_noise(), self._selfplay_playout_cap(), self._selfplay_forced_playouts():
                 r = self.engine.selfplay(n_games=hi - lo, num_sims=self.num_sims, model_id=model_id, seed=seed,
                                          first_game_id=first + lo, concurrent=min(self.num_episode_threads, hi - lo),
                                          temp_threshold=self.temp_threshold, max_depth=self.max_depth, cpuct=self.cpuct,

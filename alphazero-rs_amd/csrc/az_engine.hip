@@ -214,6 +214,7 @@ struct TreeHost {
         d.reserve_nodes = (uint32_t)reserve_nodes;
         d.noise = RootNoise{};                    // root noise belongs to the call that sets it (the arena never does)
         d.cap = PlayoutCap{};                     // and so does a playout cap (self-play sessions only)
+        d.forced = ForcedPlayouts{};              // and forced playouts / pruning (never the arena)
         HIPCHK(hipMemsetAsync(d.err, 0, ERR_COUNT * sizeof(uint32_t), s));
         HIPCHK(hipMemsetAsync(d_totals, 0, ST_TOTALS * sizeof(unsigned long long), s));
         HIPCHK(hipMemsetAsync(eb.n, 0, sizeof(uint32_t), s));
@@ -336,6 +337,8 @@ struct az_engine {
     int64_t root_noise_eps_e6 = 0, root_noise_alpha_e6 = 1000000;
     // playout cap randomization of self-play ("playout_cap_sims" 0 = off, "playout_cap_full_e6"); never the arena or the tree calls
     int64_t playout_cap_sims = 0, playout_cap_full_e6 = 250000;
+    // forced playouts at the root and policy target pruning, on the moves root noise can apply to ("forced_playouts_k_e6" 0 = off, "policy_prune")
+    int64_t forced_playouts_k_e6 = 0, policy_prune = 0;
     std::vector<uint64_t> sp_full_plies;        // az_selfplay_get_full_plies: the full-ply masks of the last az_selfplay / az_selfplay_next
     // activation workspaces of the conv net: [0] the engine stream, [1] a second concurrent stream (az_arena's old-model
     // search); created on first use, shared by every model id
@@ -451,6 +454,16 @@ az_status fail_hip(az_engine* e, const HipFail& f) {
 
 // "root_noise_eps_e6" / "root_noise_alpha_e6" as the kernels take them: the division in double, rounded once to f32.  eps == 0 (off) gives
 // the all-zero record whatever alpha is, so noise-free searches share their captured graphs.
+// "forced_playouts_k_e6" / "policy_prune" as the kernels take them.  k == 0 (off) gives the all-zero record whatever "policy_prune" is: the
+// launchers then pick the kernels' FP = false instantiations and the search graph's key is that of an engine that never set the keys
+ForcedPlayouts forced_for(const az_engine* e, float cpuct_f) {
+    ForcedPlayouts fp{};
+    if (e->forced_playouts_k_e6 == 0) return fp;
+    fp.k = forced_k_of(e->forced_playouts_k_e6);
+    fp.prune = e->policy_prune ? 1u : 0u;
+    fp.cpuct_f = cpuct_f;
+    return fp;
+}
 RootNoise root_noise_for(const az_engine* e) {
     RootNoise rn{};
     if (e->root_noise_eps_e6 == 0) return rn;
@@ -702,6 +715,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
             NetOptions opt;
             RootNoise noise;                           // TreeDev travels by value: a graph captured with other noise arguments is never replayed
             PlayoutCap cap;                            // ... nor one captured with another playout cap (or without one)
+            ForcedPlayouts forced;                     // ... nor one captured with other forced-playout arguments
         } k;
         std::memset(&k, 0, sizeof k);
         k.th = &th; k.conv = net.conv; k.ws = net.kind == AZ_NET_CONV ? workspace_for(e, s) : nullptr; k.stream = s; k.root_states = d_root_states;
@@ -712,6 +726,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
         k.opt = netopt_for(e, net);
         k.noise = th.d.noise;
         k.cap = th.d.cap;
+        k.forced = th.d.forced;
         k.reserve_nodes = th.d.reserve_nodes;      // TreeDev travels by value into the captured launches: the capacity threshold is baked in
         k.model_gen = net.generation;              // a freed and re-created model may reuse the ConvNet's address: its weights' identity is the generation
         TreeHost::StepGraph& sg = th.step_graph;
@@ -877,6 +892,7 @@ void SlotRunner::operator()(CombineBatch<SlotCall>& b) const {
         HIPCHK(hipMemcpyAsync(sh.d_req, sh.h_req, (size_t)n * sizeof(SlotReq), hipMemcpyHostToDevice, s));
         d.noise = root_noise_for(e);
         if (d.noise.eps != 0.0f) d.noise.stream = t->d_noise_streams;         // each request's own (seed, game_id)
+        d.forced = forced_for(e, (float)t->cpuct);
         launch_slot_arm(d, sh.d_req, n, t->d_root_states, sh.d_reset, s, d.noise.stream ? t->d_noise_streams : nullptr);
         if (any_reset) launch_reset_trees(d, sh.d_reset, s);      // AsyncMcts::default for the slots acquired since their last batch
         SearchParams sp{(uint32_t)t->max_depth, (float)t->cpuct};
@@ -1031,6 +1047,14 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
             return fail(e, AZ_ERR_BAD_ARGUMENT, sims ? "playout_cap_sims must be in 0 .. 65535" : "playout_cap_full_e6 must be in 0 .. 1000000");
         if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "the playout cap cannot change while a self-play session is open");
         (sims ? e->playout_cap_sims : e->playout_cap_full_e6) = value;
+        return AZ_OK;
+    }
+    if (is("forced_playouts_k_e6") || is("policy_prune")) {
+        const bool k = is("forced_playouts_k_e6");
+        if (value < 0 || value > (k ? FORCED_K_E6_MAX : 1))
+            return fail(e, AZ_ERR_BAD_ARGUMENT, k ? "forced_playouts_k_e6 must be in 0 .. 16000000" : "policy_prune must be 0 or 1");
+        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "forced playouts cannot change while a self-play session is open");
+        (k ? e->forced_playouts_k_e6 : e->policy_prune) = value;
         return AZ_OK;
     }
     if (is("conv3_small") && (value == 0 || value == 1)) { e->netopt.conv3_small = (int)value; return AZ_OK; }
@@ -1642,6 +1666,7 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
             HIPCHK(hipMemcpyAsync(t->d_root_states, t->h_states, (size_t)G * 16, hipMemcpyHostToDevice, e->stream));
         }
         launch_set_active(d, 1u, e->stream);
+        d.forced = forced_for(e, (float)t->cpuct);
         d.noise = root_noise_for(e);
         if (d.noise.eps != 0.0f) {                 // tree g's stream: (seed, first_game_id + g), from device memory so the search graph survives the call's seed
             launch_noise_streams(t->d_noise_streams, G, seed, first_game_id, e->stream);
@@ -1786,7 +1811,7 @@ struct SelfplaySession {
     EvalCache ec{};
     int fill = 0;
     long long step = 0;
-    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); if (lease.th) { lease.th->d.noise = RootNoise{}; lease.th->d.cap = PlayoutCap{}; } }
+    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); if (lease.th) { lease.th->d.noise = RootNoise{}; lease.th->d.cap = PlayoutCap{}; lease.th->d.forced = ForcedPlayouts{}; } }
 };
 
 static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, std::unique_ptr<SelfplaySession>& out) {
@@ -1869,6 +1894,7 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
         ss->round_sims = (int)most;
     }
     launch_reset_trees(th.d, nullptr, s);
+    th.d.forced = forced_for(e, (float)p->cpuct); // the session's forced playouts / pruning (full moves only under a playout cap)
     th.d.noise = root_noise_for(e);               // the session's root noise: stream (seed, first_game_id + the slot's episode, ply)
     if (th.d.noise.eps != 0.0f) { th.d.noise.seed = p->seed; th.d.noise.first_game_id = p->first_game_id; th.d.noise.row = gd.gid; }
     prepare_cache(e, dedup_applies(e, *net), (uint64_t)n_games * AZ_MAX_PLIES * ((uint64_t)p->num_sims + 1), s);

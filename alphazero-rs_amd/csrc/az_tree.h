@@ -19,6 +19,7 @@
 #include "az_common.h"
 #include "az_game.h"
 #include "az_playout.h"
+#include "az_forced.h"
 
 namespace az {
 
@@ -82,6 +83,17 @@ struct PlayoutCap {
     uint32_t pad;                // (no implicit padding: the record is part of the search graph's key)
 };
 
+// Forced playouts and policy target pruning ("forced_playouts_k_e6" / "policy_prune", include/az_engine.h; the predicates: az_forced.h).
+// k == 0 is OFF: the launchers then pick the kernels' FP = false instantiations, which contain none of this (a template switch, not a
+// runtime field read by the default kernels: DESIGN.md 4.1c).  A FORCED MOVE is every get_action_prob that can carry root noise; under a
+// playout cap the slot's full moves only (PLAYOUT_FULL_BIT of PlayoutCap.word, the bit that gates the noise).
+struct ForcedPlayouts {
+    float k;                     // 0 = OFF
+    uint32_t prune;              // 1: root_policy forms pi from the pruned counts (only read while k != 0)
+    float cpuct_f;               // the cpuct of the entry's searches: root_policy's prune step has no SearchParams of its own
+    uint32_t pad;                // (no implicit padding: the record is part of the search graph's key)
+};
+
 struct TreeDev {
     int32_t G;               // trees
     uint32_t R;              // slots per tree (a multiple of BLOCK_SLOTS)
@@ -108,6 +120,7 @@ struct TreeDev {
     const int32_t* log_row;  // [G] or nullptr: log row of tree g (az_selfplay: the slot's current episode, so a log survives slot refills); nullptr = g
     RootNoise noise;         // set by the entry point around its searches; zero for the arena
     PlayoutCap cap;          // set by a self-play session for its own searches; zero everywhere else
+    ForcedPlayouts forced;   // set by the entry point around its searches, as noise is; zero for the arena
 };
 
 // Leaf batch handed to the net (src/async_mcts.rs:117-189 restated as lanes): the DISTINCT states the trees of one

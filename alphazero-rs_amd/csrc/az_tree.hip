@@ -320,6 +320,8 @@ AZ_D float root_noise_mix(const TreeDev& t, int g, typename G::State s, uint32_t
 
 // Playout cap (az_tree.h PlayoutCap): a slot's fast moves get no noise; without a cap every move does.  Only NZ code reads this.
 AZ_D bool move_noisy(const TreeDev& t, int g) { return !t.cap.word || (t.cap.word[g] & PLAYOUT_FULL_BIT) != 0u; }
+// Forced playouts (az_tree.h ForcedPlayouts): the same moves -- every move without a cap, the full ones with it.  Only FP code reads this.
+AZ_D bool move_forced(const TreeDev& t, int g) { return move_noisy(t, g); }
 
 // ---- get_action_prob prologue: root lookup (src/async_mcts.rs:81) + S10 + S1 -------------
 // NZ: root noise is on.  A root that already has its prior gets the noise here; one that is evaluated first (LEAF_ROOT) gets it in its
@@ -399,9 +401,12 @@ __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, Ev
 //   S12  a link leads to a node that is Locked, i.e. expanded by an earlier thread of this step and still without its prior:
 //        `p.as_ref().unwrap()` (src/node.rs:354)
 // go = false (playout cap only): the tree's move has had its budget -- nothing is selected, the tree asks for no leaf
-template <class G, bool MT = false>
+// FP (forced playouts, az_forced.h): at the FIRST level of the simulation -- the node is the call's root -- a child that has been visited and
+// is still short of nf = sqrt(k * p * S) gets u = +inf; the arg-max, the Locked filter (C8), S11 and S12 then run on the u as written.
+// forced (read by the FP instantiations only): this tree's move is a forced move (false: a fast move under a playout cap)
+template <class G, bool MT = false, bool FP = false>
 AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth, const SearchParams& sp, int g, int sub, uint32_t* path,
-                                   uint32_t* abandoned = nullptr, bool go = true) {
+                                   uint32_t* abandoned = nullptr, bool go = true, bool forced = true) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
     const bool act = h.active != 0 && go;
@@ -417,6 +422,7 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
     // two.  Only the root and link targets (canonical nodes living elsewhere) are fetched by slot.
     NodeRec pr{};
     bool have_pr = false;
+    bool at_root = true;                                        // FP only: the loop's first pass
     while (act) {
         uint4* pp = node_ptr(t, base, cur);
         if (!have_pr) pr = node_load(pp);
@@ -432,6 +438,7 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
         const float sq = puct_sqrt_parent(ctr_n(pc));
         NodeRec cr{0ull, 0u, 0u, NONE, 0u};
         float u = 0.0f;
+        uint32_t fn = 0u;                                       // FP only: this lane's n_j (0 beyond nchild)
         if ((uint32_t)sub < nchild) {
             // the child's record carries its own counter; only a link slot needs the second, dependent fetch of the
             // canonical node's counter (resolve(), src/node.rs:179-193)
@@ -439,6 +446,16 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
             uint64_t cc = cr.ctr;
             if (cr.link != NONE) cc = node_ctr(node_ptr(t, base, cr.link));
             u = puct(cc, __uint_as_float(cr.prior), sq, sp.cpuct_f);
+            if constexpr (FP) fn = ctr_n(cc);
+        }
+        if constexpr (FP) {
+            if (at_root && forced) {
+                uint32_t S = 0u;
+#pragma unroll
+                for (int j = 0; j < NA; ++j) S += gshfl<GW>(fn, j);
+                if ((uint32_t)sub < nchild && forced_child(t.forced.k, __uint_as_float(cr.prior), S, fn)) u = __builtin_inff();
+            }
+            at_root = false;
         }
         uint32_t best = 0;
         float bu = gshflf<GW>(u, 0);
@@ -684,21 +701,24 @@ struct RootPolicy {
     uint32_t count;
     float q;
 };
-template <class G>
-AZ_D RootPolicy root_policy(const TreeDev& t, uint32_t root, int g, int sub, float temp, uint64_t seed, uint64_t game_id, uint64_t ply) {
+// FP && forced && t.forced.prune (policy target pruning, az_forced.h): pi is formed from the PRUNED counts; count and q stay raw
+template <class G, bool FP = false>
+AZ_D RootPolicy root_policy(const TreeDev& t, uint32_t root, int g, int sub, float temp, uint64_t seed, uint64_t game_id, uint64_t ply,
+                            bool forced = true) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
     const size_t base = (size_t)g * t.R;
     const NodeRec pr = node_load(node_ptr(t, base, root));
     const uint32_t nchild = (pr.meta >> META_NCHILD_SHIFT) & 7u, cb = pr.child_base;
     uint32_t ca = 0, cn = 0;
-    float cq = 0.0f;
+    float cq = 0.0f, cp = 0.0f;                                     // cp (FP only): the slot's stored prior
     if ((uint32_t)sub < nchild) {
         const NodeRec cr = node_load(node_ptr(t, base, cb + sub));
         const uint64_t cc = cr.link != NONE ? node_ctr(node_ptr(t, base, cr.link)) : cr.ctr;
         ca = cr.meta & META_A_MASK;                                 // B3: the slot's own action
         cn = ctr_n(cc);
         cq = ctr_q(cc);
+        if constexpr (FP) cp = __uint_as_float(cr.prior);
     }
     RootPolicy out{0.0f, 0u, 0.0f};
 #pragma unroll
@@ -707,17 +727,39 @@ AZ_D RootPolicy root_policy(const TreeDev& t, uint32_t root, int g, int sub, flo
         float qj = gshflf<GW>(cq, j);
         if ((uint32_t)j < nchild && aj == (uint32_t)sub) { out.count = nj; out.q = qj; }
     }
+    uint32_t pcount = out.count;                                    // what pi is formed from: the raw count, or ...
+    if constexpr (FP) {
+        if (forced && t.forced.prune) {                             // ... the pruned one
+            uint32_t S = 0u, b = 0u, bn = 0u;
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                const uint32_t nj = gshfl<GW>(cn, j);               // (0 beyond nchild)
+                S += nj;
+                if ((uint32_t)j < nchild && nj >= bn) { b = (uint32_t)j; bn = nj; }      // the most visited slot, the highest among equals
+            }
+            const float sq = forced_sqrt_parent(ctr_n(pr.ctr));
+            const float u_star = forced_puct(gshflf<GW>(cq, (int)b), bn, gshflf<GW>(cp, (int)b), sq, t.forced.cpuct_f);
+            uint32_t cm = cn;
+            if ((uint32_t)sub < nchild && (uint32_t)sub != b && cn > 0u) cm = forced_prune(t.forced.k, cp, S, cn, cq, sq, t.forced.cpuct_f, u_star);
+            pcount = 0u;
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                const uint32_t aj = gshfl<GW>(ca, j), mj = gshfl<GW>(cm, j);
+                if ((uint32_t)j < nchild && aj == (uint32_t)sub) pcount = mj;
+            }
+        }
+    }
     if (temp == 0.0f) {                                             // :97-107
         uint32_t mx = 0;
 #pragma unroll
-        for (int a = 0; a < NA; ++a) { uint32_t ca2 = gshfl<GW>(out.count, a); mx = ca2 > mx ? ca2 : mx; }
-        uint32_t ties = gballot<GW>(sub < NA && out.count == mx) & ((1u << NA) - 1u);
+        for (int a = 0; a < NA; ++a) { uint32_t ca2 = gshfl<GW>(pcount, a); mx = ca2 > mx ? ca2 : mx; }
+        uint32_t ties = gballot<GW>(sub < NA && pcount == mx) & ((1u << NA) - 1u);
         uint64_t r = rng_draw(seed, game_id, ply, RNG_TIEBREAK);
         uint32_t pick = nth_set_bit<NA>(ties, rng_choose(r, (uint32_t)__popc(ties)));
         out.pi = ((uint32_t)sub == pick) ? 1.0f : 0.0f;
     } else {                                                        // S6 (A7): counts^(1/temp) / sum
         float inv_t = __fdiv_rn(1.0f, temp);
-        float x = (inv_t == 1.0f) ? (float)out.count : powf((float)out.count, inv_t);   // :109
+        float x = (inv_t == 1.0f) ? (float)pcount : powf((float)pcount, inv_t);   // :109
         if (sub >= NA) x = 0.0f;
         float sum = 0.0f;
 #pragma unroll
@@ -756,7 +798,8 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
 // PC (playout cap): TreeHead.active carries the simulations the tree's move has left (1 | left << 1); a tree with none left selects nothing
 // and requests no leaf for the rest of the round -- its last backup above still runs, and its lanes still go through leaf_request's
 // workgroup-wide row claim as an inactive tree's do.  So a replayed graph chunk in which some trees are done is correct as it is.
-template <class G, bool STAMP, bool NZ, bool MIR, bool PC>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
+// FP (forced playouts): select_body's forced branch at the root, on the tree's forced moves
+template <class G, bool STAMP, bool NZ, bool MIR, bool PC, bool FP>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
 __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec,
                                                        SearchParams sp, unsigned long long* dbg) {
     constexpr int GW = G::GROUP;
@@ -782,7 +825,9 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     AZ_TSTAMP(3);
     bool go = true;
     if constexpr (PC) go = (h.active >> 1) != 0u;
-    const typename G::State leaf_s = select_body<G>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, go);
+    bool forced = true;
+    if constexpr (FP) forced = move_forced(t, g);
+    const typename G::State leaf_s = select_body<G, false, FP>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, go, forced);
     if constexpr (PC) { if (go) h.active -= 2u; }
     AZ_TSTAMP(4);
     const uint32_t src = leaf_request<G, MIR>(eb_next, ec, h.leaf_kind == LEAF_EVAL, leaf_s, sub);
@@ -818,7 +863,7 @@ struct ThreadRegs { uint32_t leaf, leaf_kind; float leaf_val; uint32_t src, path
 AZ_D void thread_to_head(TreeHead& h, const ThreadRegs& r) { h.leaf = r.leaf; h.leaf_kind = r.leaf_kind; h.leaf_val = r.leaf_val; h.src = r.src; h.path_len = r.path_len; }
 AZ_D ThreadRegs head_to_thread(const TreeHead& h) { return ThreadRegs{h.leaf, h.leaf_kind, h.leaf_val, h.src, h.path_len}; }
 // PC (playout cap): as in k_backup_select; a step takes T simulations off what the tree's move has left (budgets are multiples of T)
-template <class G, bool NZ, bool MIR, bool PC>
+template <class G, bool NZ, bool MIR, bool PC, bool FP>
 __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp, int first, int last) {
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * 64 + threadIdx.x;
@@ -856,6 +901,8 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
     h.leaf_kind = LEAF_NONE;
     bool go = !last;
     if constexpr (PC) go = go && (h.active >> 1) >= (uint32_t)T;
+    bool forced = true;
+    if constexpr (FP) forced = move_forced(t, g);
     for (int tt = 0; tt < T; ++tt) {                        // selections in thread order
         group_memory_sync();                                // counters, priors, locks and links written so far are read next
         TreeLine* tl = t.thr + (size_t)g * T + tt;
@@ -865,7 +912,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
         bool want = false;
         typename G::State leaf_s = G::init();
         if (go) {
-            leaf_s = select_body<G, true>(t, h, pth, sp, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP, &abandoned);
+            leaf_s = select_body<G, true, FP>(t, h, pth, sp, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP, &abandoned, true, forced);
             want = h.leaf_kind == LEAF_EVAL;
         }
         const uint32_t src = leaf_request<G, MIR>(eb_next, ec, want, leaf_s, sub);      // every wave calls it T times (wave-wide ballots inside)
@@ -905,7 +952,7 @@ AZ_D float fixture_row(typename G::State s, int kind, uint64_t salt, int sub) {
     return out;
 }
 // PC (playout cap): tree g runs the budget of its own move, t.cap.word[g], instead of num_sims
-template <class G, bool NZ, bool PC>
+template <class G, bool NZ, bool PC, bool FP>
 __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind,
                                                        uint64_t salt) {
     constexpr int GW = G::GROUP;
@@ -919,6 +966,8 @@ __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglon
     bool noisy = true;
     if constexpr (NZ) noisy = move_noisy(t, g);
     if constexpr (PC) num_sims = (int)(t.cap.word[g] & ~PLAYOUT_FULL_BIT);
+    bool forced = true;
+    if constexpr (FP) forced = move_forced(t, g);
     typename G::State ls = root_prepare_body<G, NZ>(t, h, root_states, g, sub, noisy);
     for (int i = 0; i <= num_sims; ++i) {
         group_memory_sync();
@@ -927,13 +976,13 @@ __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglon
         backup_body<G, true, NZ>(t, h, pth, no_eb, no_ec, g, sub, t.path + (size_t)g * PATH_CAP, pv, noisy);
         if (i == num_sims) break;
         group_memory_sync();
-        ls = select_body<G>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP);
+        ls = select_body<G, false, FP>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, true, forced);
     }
     h.leaf_kind = LEAF_NONE;
     if (sub == 0) head_store(t, g, h);
 }
 
-template <class G>
+template <class G, bool FP>
 __global__ __launch_bounds__(64) void k_root_policy(TreeDev t, float temp, uint64_t seed, uint64_t first_game_id,
                                                     float* pi, uint16_t* counts, float* q) {
     constexpr int GW = G::GROUP;
@@ -944,7 +993,7 @@ __global__ __launch_bounds__(64) void k_root_policy(TreeDev t, float temp, uint6
     const TreeHead h = head_load(t, g);
     if (!h.active) return;
     const typename G::State s = G::unpack(node_key(t, (size_t)g * t.R, h.root));
-    RootPolicy rp = root_policy<G>(t, h.root, g, sub, temp, seed, first_game_id + (uint64_t)g, (uint64_t)G::stones(s));
+    RootPolicy rp = root_policy<G, FP>(t, h.root, g, sub, temp, seed, first_game_id + (uint64_t)g, (uint64_t)G::stones(s));
     if (sub < NA) {
         pi[(size_t)g * NA + sub] = rp.pi;
         if (counts) counts[(size_t)g * NA + sub] = (uint16_t)rp.count;
@@ -1004,7 +1053,7 @@ __global__ __launch_bounds__(64) void k_root_noise_eta(int n, uint64_t seed, con
 // status: a failed root (the search left the tree inactive: arena exhausted at the root) or a terminal root is this request's own
 // error; a capacity error raised during the search (t.err) is blamed on every tree of the batch that is that close to full (a tree
 // whose push failed always is: node_upgrade refuses exactly when len + 8 > R or count + 8 > reserve could be exceeded).
-template <class G>
+template <class G, bool FP>
 __global__ __launch_bounds__(64) void k_slot_root_policy(TreeDev t, const SlotReq* __restrict__ req, int n, SlotOut* out) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
@@ -1026,7 +1075,7 @@ __global__ __launch_bounds__(64) void k_slot_root_policy(TreeDev t, const SlotRe
         if (ecd != E_NONE) status = 1u << ERR_TERMINAL_ROOT;
         else if (full_err && (h.len + BLOCK_SLOTS > t.R || h.count + BLOCK_SLOTS > t.reserve_nodes)) status = 1u << ERR_CAPACITY;
         const typename G::State s = G::unpack(node_key(t, base, h.root));
-        rp = root_policy<G>(t, h.root, g, sub, r.temp, r.seed, r.game_id, (uint64_t)G::stones(s));
+        rp = root_policy<G, FP>(t, h.root, g, sub, r.temp, r.seed, r.game_id, (uint64_t)G::stones(s));
     }
     if (sub < NA) {
         out[i].pi[sub] = rp.pi;
@@ -1086,7 +1135,8 @@ __global__ __launch_bounds__(256) void k_call_readback(unsigned long long* total
 // PC (playout cap): *word = the slot's word for the move being played (az_tree.h PlayoutCap).  The ply's full flag goes into the episode's
 // mask (k_emit_samples compacts to the full plies; pi / state / player are stored by ply either way), the mode of the slot's NEXT move -- the
 // next ply, or ply 0 of the episode a refilled slot gets -- is drawn, and its word is stored and handed back in *word.
-template <class G, bool PC = false>
+// FP (forced playouts): a forced move's pi -- recorded and sampled from -- is formed from the pruned counts when "policy_prune" is on
+template <class G, bool PC = false, bool FP = false>
 AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, const SelfplayMoveParams& mp, int g, int sub, uint32_t* word = nullptr) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
@@ -1096,7 +1146,9 @@ AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, c
     const typename G::State s = gd.state[g];
     const uint64_t game_id = mp.first_game_id + (uint64_t)gi;
     const float temp = (ply + 1 < mp.temp_threshold) ? 1.0f : 0.0f;         // :122-126 (episode_step = ply + 1)
-    RootPolicy rp = root_policy<G>(t, h.root, g, sub, temp, mp.seed, game_id, (uint64_t)ply);   // :128
+    bool forced = true;
+    if constexpr (FP && PC) forced = (*word & PLAYOUT_FULL_BIT) != 0u;
+    RootPolicy rp = root_policy<G, FP>(t, h.root, g, sub, temp, mp.seed, game_id, (uint64_t)ply, forced);   // :128
     const size_t so = (size_t)gi * G::MAX_PLIES + ply;
     if (sub < NA) gd.smp_pi[so * NA + sub] = rp.pi;                         // :130-135 (symmetries regenerated at emit)
     // choose_weighted, :137-138
@@ -1172,7 +1224,7 @@ AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, c
     if (status == 2) h.active = 0;
     return status;
 }
-template <class G, bool PC>
+template <class G, bool PC, bool FP>
 __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, SelfplayMoveParams mp) {
     constexpr int GW = G::GROUP;
     int tid = blockIdx.x * 64 + threadIdx.x;
@@ -1183,7 +1235,7 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
     if (gi < 0 || !h.active) return;
     uint32_t word = 0u;
     if constexpr (PC) word = t.cap.word[g];
-    if (selfplay_move_body<G, PC>(t, h, gd, mp, g, sub, &word) == 2 && sub == 0) t.head[g].head.active = 0;
+    if (selfplay_move_body<G, PC, FP>(t, h, gd, mp, g, sub, &word) == 2 && sub == 0) t.head[g].head.active = 0;
 }
 
 // ---- FREE-RUNNING self-play: every slot on its own timeline ("selfplay_async") -------------------------------------------------------
@@ -1199,7 +1251,7 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
 //   first        the first launch behind a forward: eb_prev holds that forward's rows (parked trees back up; its table is cleared)
 // PC (playout cap): the slot's move ends at its own budget (the word of az_tree.h PlayoutCap, redrawn by every move), and its root gets the
 // noise only when the move is a full one.
-template <class G, bool NZ, bool MIR, bool PC>
+template <class G, bool NZ, bool MIR, bool PC, bool FP>
 __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp,
                                                     SelfplayMoveParams mp, int num_sims, int first, int max_iters) {
     constexpr int GW = G::GROUP;
@@ -1240,12 +1292,12 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
                 continue;
             }
             if (sims >= (PC ? (int)(word & ~PLAYOUT_FULL_BIT) : num_sims)) {      // the move (src/coach.rs:128-156), then the next position's root
-                const int st = selfplay_move_body<G, PC>(t, h, gd, mp, g, sub, &word);
+                const int st = selfplay_move_body<G, PC, FP>(t, h, gd, mp, g, sub, &word);
                 sims = -1;
                 if (st != 0) break;                                            // episode over: idle, or wait for k_reset_trees
                 continue;
             }
-            leaf_s = select_body<G>(t, h, pth, sp, g, sub, path);
+            leaf_s = select_body<G, false, FP>(t, h, pth, sp, g, sub, path, nullptr, true, !PC || (word & PLAYOUT_FULL_BIT) != 0u);
             if (h.leaf_kind == LEAF_EVAL) { want = true; break; }
             if (h.leaf_kind == LEAF_NONE) ++sims;                              // an error cut the simulation short (flag set): it still counts
         }
@@ -1386,6 +1438,12 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
         if ((t_).cap.word) { constexpr bool PC = true; __VA_ARGS__; }                    \
         else { constexpr bool PC = false; __VA_ARGS__; }                                 \
     } while (0)
+// ... and per forced playouts: FP = true only while the entry point's ForcedPlayouts record has k != 0
+#define AZ_FOR_FP(t_, ...)                                                               \
+    do {                                                                                 \
+        if ((t_).forced.k != 0.0f) { constexpr bool FP = true; __VA_ARGS__; }            \
+        else { constexpr bool FP = false; __VA_ARGS__; }                                 \
+    } while (0)
 static inline int group_blocks(int G) { return (G * BLOCK_SLOTS + 63) / 64; }
 #ifdef AZ_DIAG
 // diagnostic library only: the PUCT term of best_child (src/node.rs:352-356) for n (child counter, prior bits, parent N) triples, as the
@@ -1442,24 +1500,24 @@ void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const Eval
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
 #ifdef AZ_DIAG
     if (g_tree_dbg && t.G * 8 / 64 <= TREE_DBG_WAVES) {
-        AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR, PC>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg)));
+        AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR, PC, FP>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg))));
         return;
     }
 #endif
-    AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR, PC>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr)));
+    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR, PC, FP>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr))));
 }
 void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                     int first, int last, hipStream_t s) {
     // one wave per workgroup: leaf_request is called T times per launch and its one-atomic-per-workgroup path keeps state in LDS
-    AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_step_mt<TG, NZ, MIR, PC>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last)));
+    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_step_mt<TG, NZ, MIR, PC, FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last))));
 }
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s) {
-    AZ_FOR_PC(t, AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ, PC>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt)));
+    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ, PC, FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt))));
 }
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,
                         uint16_t* counts, float* q, hipStream_t s) {
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_root_policy<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, temp, seed, first_game_id, pi, counts, q));
+    AZ_FOR_FP(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_root_policy<TG, FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, temp, seed, first_game_id, pi, counts, q)));
 }
 void launch_slot_arm(const TreeDev& t, const SlotReq* req, int n, ulonglong2* roots, uint8_t* reset_flags, hipStream_t s, ulonglong2* streams) {
     hipLaunchKernelGGL(k_slot_arm, dim3(1), dim3(1024), 0, s, t, req, n, roots, reset_flags, streams);
@@ -1473,7 +1531,7 @@ void launch_root_noise_eta(int game, int n, uint64_t seed, const uint64_t* game_
 }
 void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s) {
     if (n <= 0) return;
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_slot_root_policy<TG>, dim3(group_blocks(n)), dim3(64), 0, s, t, req, n, out));
+    AZ_FOR_FP(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_slot_root_policy<TG, FP>), dim3(group_blocks(n)), dim3(64), 0, s, t, req, n, out)));
 }
 void launch_harvest(const TreeDev& t, unsigned long long* totals, uint32_t* node_counts, hipStream_t s) {
     hipLaunchKernelGGL(k_harvest, dim3((t.G + 255) / 256), dim3(256), 0, s, t, totals, node_counts);
@@ -1483,13 +1541,13 @@ void launch_call_readback(unsigned long long* totals, unsigned long long* dd_sta
     hipLaunchKernelGGL(k_call_readback, dim3(1), dim3(256), 0, s, totals, dd_stat, err, out);
 }
 void launch_selfplay_move(const TreeDev& t, const GamesDev& gd, SelfplayMoveParams mp, hipStream_t s) {
-    AZ_FOR_PC(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_selfplay_move<TG, PC>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, mp)));
+    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_selfplay_move<TG, PC, FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, mp))));
 }
 void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s) {
     const bool four = t.block4 && (t.G * 8) % 256 == 0;
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
-    AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_async_step<TG, NZ, MIR, PC>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters)));
+    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_async_step<TG, NZ, MIR, PC, FP>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters))));
 }
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s) {
     hipLaunchKernelGGL(k_sync_active, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gd);

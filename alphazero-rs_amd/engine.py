@@ -330,6 +330,15 @@ class Engine:
         self.set_option("playout_cap_full_e6", int(round(float(p_full) * 1e6)))
         self.set_option("playout_cap_sims", int(sims))
 
+    def set_forced_playouts(self, k, prune=False):
+        """Forced playouts at the root and policy target pruning (KataGo) on every move root noise can apply to -- self-play and the tree
+        calls, under a playout cap the full moves only, never the arena.  A visited root child with fewer than sqrt(k * prior * visits)
+        visits wins the root's selection; with prune the recorded (and sampled) pi is formed from counts with those forced visits taken
+        back out.  k = 0 switches both off (the default); the values travel as "forced_playouts_k_e6" / "policy_prune"
+        (include/az_engine.h)."""
+        self.set_option("policy_prune", 1 if prune else 0)
+        self.set_option("forced_playouts_k_e6", int(round(float(k) * 1e6)))
+
     def selfplay_full_plies(self):
         """az_selfplay_get_full_plies: uint64 [n], bit `ply` of word i set when that ply of the i-th episode of the last selfplay() /
         selfplay_next() call was a full move, i.e. became a tuple (all plies when the playout cap is off)."""

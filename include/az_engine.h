@@ -251,6 +251,41 @@ const char* az_last_error(const az_engine* e);
  *                             bounds     tree capacity, hash and cache sizes stay those of num_sims (an upper bound of any move)
  *                           A captured search graph is keyed on the playout-cap arguments, so one captured with others is never
  *                           replayed.  az_selfplay_get_full_plies returns which plies were full (to line tuples up with moves[])
+ *   forced playouts "forced_playouts_k_e6"  0 (default, OFF) .. 16000000; k = (float)(value / 1e6): the division in double, rounded once
+ *                           to f32 (KataGo's k = 2 is 2000000)
+ *            "policy_prune" 0 (default) or 1; has an effect only while k > 0, inert with k = 0 whatever its value
+ *                           FORCED PLAYOUTS at the root and POLICY TARGET PRUNING (KataGo, Wu 2019, section 3.2), strictly opt-in.  With
+ *                           k = 0 (set or never set) every output and every counter of every entry is bit for bit what it is without the
+ *                           feature, and the kernels that run are the ones that run without it.  Values out of range and any change
+ *                           while a self-play session is open are refused (AZ_ERR_BAD_ARGUMENT).  State of the engine, like every
+ *                           option.  The contract (csrc/az_forced.h):
+ *                             forced moves  every get_action_prob that can carry root noise: az_selfplay and sessions on every path
+ *                                        (lock-step, "selfplay_async", any num_sim_threads, slot refill, both games, fp8 and
+ *                                        "eval_mirror" models), az_tree_get_action_prob, az_tree_slot_get_action_prob.  Under a playout
+ *                                        cap the FULL moves only: a fast move is exactly the fast move without the keys.  NEVER az_arena.
+ *                                        Independent of "root_noise_eps_e6": the root's stored priors are used as they are (the noised
+ *                                        ones when noise is on)
+ *                             selection  on a forced move, at the first level of a simulation only (the node is the call's root).  For
+ *                                        root child slot j < nchild, with the values PUCT has loaded: cc_j the resolved counter,
+ *                                        n_j = its visit count (in-flight visits included, as PUCT's N), p_j the stored prior:
+ *                                          S = sum of n_j over the root's child slots (u32);  nf_j = sqrt((k * p_j) * (float)S), every
+ *                                          operation f32 round-to-nearest, the square root correctly rounded;
+ *                                          n_j > 0 && (float)n_j < nf_j:  u_j = +inf;  otherwise u_j is PUCT, unchanged.
+ *                                        The arg-max runs over the u_j as always: last-max ties (among several forced children the highest
+ *                                        slot wins), and with several simulations in flight the Locked filter and the two abandonment
+ *                                        rules see these u_j.  No level below the root changes
+ *                             pruning    on a forced move with "policy_prune" = 1, before pi is formed from the final counters:
+ *                                        b = the slot with the largest n_j (the highest slot among equals); sq = sqrt(N_root + 1e-6);
+ *                                        u* = PUCT of slot b.  For every slot j != b with n_j > 0:  f_j = (uint32_t)nf_j;
+ *                                        lo_j = n_j > f_j ? n_j - f_j : 0;  m = n_j;
+ *                                          while (m > lo_j && q_j + ((cpuct * p_j) * sq) / (float)m < u*) --m;
+ *                                        (would the child, one visit fewer and its Q held fixed, still score below the best child?)
+ *                                        If the loop lowered m and it ended at 1, m = 0: a child reduced to a single playout is pruned
+ *                                        outright.  Slot b and slots with n_j = 0 keep their counts.  pi is computed from the pruned
+ *                                        counts by the unchanged rules (temperature 0 and not 0, tie-break and move streams unchanged);
+ *                                        that one pi is both recorded and sampled from.  The `counts` and `q` outputs stay RAW
+ *                           A captured search graph is keyed on the forced-playout arguments, so one captured with others is never
+ *                           replayed.  Playing strength with the option on is unmeasured
  *   search   "search_graph" n (default 20, even, 0 = off): n simulation steps per captured hipGraph replay (conv nets) ...
  *            "search_graph_rows" n (default 1024): ... for searches whose expected leaf batch has at most n rows (the arena, the drain
  *                           of a self-play call, single trees: there the host's launch calls set the pace; on big batches the kernels do)

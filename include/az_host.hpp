@@ -132,6 +132,12 @@ class Engine {
         check(az_set_option(e_, "playout_cap_full_e6", (int64_t)std::llround(p_full * 1e6)));
         check(az_set_option(e_, "playout_cap_sims", sims));
     }
+    // Forced playouts at the root and policy target pruning ("forced_playouts_k_e6" / "policy_prune", include/az_engine.h) on every move
+    // root noise can apply to (under a playout cap the full moves only), never the arena.  k = 0 switches both off
+    void set_forced_playouts(double k, bool prune = false) {
+        check(az_set_option(e_, "policy_prune", prune ? 1 : 0));
+        check(az_set_option(e_, "forced_playouts_k_e6", (int64_t)std::llround(k * 1e6)));
+    }
     // az_selfplay_get_full_plies: bit `ply` of word i = that ply of the i-th episode of the last az_selfplay / az_selfplay_next call
     // (n_games episodes) was a full move and became a tuple
     std::vector<uint64_t> selfplay_full_plies(size_t n_games) const {
@@ -538,6 +544,12 @@ class Coach {
                         CapGuard(Engine& e_, int64_t sims_, double p_) : e(e_), sims(sims_), p(p_) { if (sims > 0) e.set_playout_cap(sims, p); }
                         ~CapGuard() { if (sims > 0) { try { e.set_playout_cap(0, p); } catch (...) {} } }
                     } cap_guard(e_, playout_cap_sims, playout_cap_full);
+                    // ... and so are forced playouts and pruning
+                    struct ForcedGuard {
+                        Engine& e; double k;
+                        ForcedGuard(Engine& e_, double k_, bool prune_) : e(e_), k(k_) { if (k > 0) e.set_forced_playouts(k, prune_); }
+                        ~ForcedGuard() { if (k > 0) { try { e.set_forced_playouts(0.0, false); } catch (...) {} } }
+                    } forced_guard(e_, forced_playouts_k, policy_prune);
                     h = execute_episodes(model_id, iteration, seed);
                 }
                 if (h.len() > max_queue_length) {                   // keep the newest max_queue_length (:275-277)
@@ -625,6 +637,10 @@ class Coach {
     // (the default): the engine is never asked.  An iteration then yields the tuples of the full moves only
     int64_t playout_cap_sims = 0;
     double playout_cap_full = 0.25;
+    // Forced playouts and policy target pruning of the episodes (Engine::set_forced_playouts): set before every az_selfplay and cleared
+    // behind it.  k 0 (the default): the engine is never asked
+    double forced_playouts_k = 0.0;
+    bool policy_prune = false;
     // "eval_mirror" (Engine::set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
     // run under the mirror-canonical function, so the gate compares like with like.  false (the default): the engine is never asked
     bool eval_mirror = false;
