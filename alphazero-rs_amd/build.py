@@ -16,7 +16,7 @@ LIB = os.path.join(PKG_DIR, "libaz_engine.so")
 # load it (engine.Engine(diag=True)); the shipped library above does not contain any of it and refuses those option values.
 LIB_DIAG = os.path.join(PKG_DIR, "libaz_engine_diag.so")
 SOURCES = ["az_tree.hip", "az_net.hip", "az_train.hip", "az_engine.hip"]
-HEADERS = ["az_common.h", "az_combine.h", "az_local_comm.h", "az_game.h", "az_tree.h", "az_net.h", "az_fp8.h", "az_noise.h", "az_playout.h", "az_forced.h", "az_mirror.h", "az_train.h", "az_net_diag.inc", os.path.join("..", "..", "include", "az_engine.h")]
+HEADERS = ["az_common.h", "az_combine.h", "az_local_comm.h", "az_game.h", "az_tree.h", "az_net.h", "az_fp8.h", "az_noise.h", "az_playout.h", "az_forced.h", "az_opening.h", "az_mirror.h", "az_train.h", "az_net_diag.inc", os.path.join("..", "..", "include", "az_engine.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall",
          "-Wno-unused-result"]
 

@@ -65,6 +65,9 @@ class Coach:
         # Forced playouts and policy target pruning of the episodes (Engine.set_forced_playouts): switched on before every az_selfplay and
         # off again behind it, exactly as the playout cap is.  k 0 (the default): the engine is never asked
         self.forced_playouts_k, self.policy_prune = 0.0, False
+        # Paired openings of the gate (Engine.set_arena_openings): switched on before the iteration's az_arena and off again behind it,
+        # exactly as the forced playouts are around self-play.  0 (the default): the engine is never asked
+        self.arena_opening_plies = 0
         # "eval_mirror" (Engine.set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
         # run under the mirror-canonical function F, so the gate compares like with like.  False (the default): the engine is never asked
         self.eval_mirror = False
@@ -127,6 +130,16 @@ class Coach:
         finally:
             if self.forced_playouts_k > 0:
                 self.engine.set_forced_playouts(0.0, False)
+
+    @contextlib.contextmanager
+    def _arena_openings(self):
+        if self.arena_opening_plies > 0:
+            self.engine.set_arena_openings(self.arena_opening_plies)
+        try:
+            yield
+        finally:
+            if self.arena_opening_plies > 0:
+                self.engine.set_arena_openings(0)
 
     def execute_episodes(self, model_id, iteration, seed):
         """The self-play fan-out of src/coach.rs:241-272: num_eps x execute_episode, sharded by global game id."""
@@ -222,25 +235,26 @@ class Coach:
             if self.selfplay_class != -1:                               # the gate is judged in bf16 whatever the episodes were played in
                 self.engine.net_set_class(model_id + 1, 0)
                 self.engine.net_set_class(model_id, 0)
-            if world > 1 and total > 0:
-                from . import dist as azdist
-                import torch
-                import torch.distributed as tdist
-                lo, hi = azdist.shard_range(total, rank, world)
-                wld = np.zeros(3, np.uint64)
-                if hi > lo:
-                    wld, _ = self.engine.arena(hi - lo, self.num_sims, new_model_id=model_id + 1, old_model_id=model_id,
+            with self._arena_openings():
+                if world > 1 and total > 0:
+                    from . import dist as azdist
+                    import torch
+                    import torch.distributed as tdist
+                    lo, hi = azdist.shard_range(total, rank, world)
+                    wld = np.zeros(3, np.uint64)
+                    if hi > lo:
+                        wld, _ = self.engine.arena(hi - lo, self.num_sims, new_model_id=model_id + 1, old_model_id=model_id,
+                                                   seed=a_seed, max_depth=self.max_depth, cpuct=self.cpuct,
+                                                   reserve=self.mcts_reserve_size, first_game=lo, total_games=total,
+                                                   num_sim_threads=self.num_sim_threads)
+                    dev = torch.device("cuda", torch.cuda.current_device()) if tdist.get_backend(self.group) == "nccl" else torch.device("cpu")
+                    t = torch.tensor([int(x) for x in wld], dtype=torch.int64, device=dev)
+                    tdist.all_reduce(t, group=self.group)
+                    wld = t.cpu().numpy()
+                else:
+                    wld, _ = self.engine.arena(self.num_arena_games, self.num_sims, new_model_id=model_id + 1, old_model_id=model_id,
                                                seed=a_seed, max_depth=self.max_depth, cpuct=self.cpuct,
-                                               reserve=self.mcts_reserve_size, first_game=lo, total_games=total,
-                                               num_sim_threads=self.num_sim_threads)
-                dev = torch.device("cuda", torch.cuda.current_device()) if tdist.get_backend(self.group) == "nccl" else torch.device("cpu")
-                t = torch.tensor([int(x) for x in wld], dtype=torch.int64, device=dev)
-                tdist.all_reduce(t, group=self.group)
-                wld = t.cpu().numpy()
-            else:
-                wld, _ = self.engine.arena(self.num_arena_games, self.num_sims, new_model_id=model_id + 1, old_model_id=model_id,
-                                           seed=a_seed, max_depth=self.max_depth, cpuct=self.cpuct,
-                                           reserve=self.mcts_reserve_size, num_sim_threads=self.num_sim_threads)
+                                               reserve=self.mcts_reserve_size, num_sim_threads=self.num_sim_threads)
             t_arena = time.perf_counter() - t0
             nwins, pwins, draws = int(wld[0]), int(wld[1]), int(wld[2])
             self.log(f"NEW/PREV WINS : {nwins} / {pwins}; DRAWS : {draws}")            # :381

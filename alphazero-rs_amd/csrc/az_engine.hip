@@ -339,6 +339,9 @@ struct az_engine {
     int64_t playout_cap_sims = 0, playout_cap_full_e6 = 250000;
     // forced playouts at the root and policy target pruning, on the moves root noise can apply to ("forced_playouts_k_e6" 0 = off, "policy_prune")
     int64_t forced_playouts_k_e6 = 0, policy_prune = 0;
+    // paired openings of az_arena, never of self-play or the tree calls ("arena_opening_plies" 0 = off; az_arena_set_opening_book)
+    int64_t arena_opening_plies = 0;
+    std::vector<uint64_t> ar_book;      // [entries][2] {first seat's stones, second seat's stones}; empty = no book
     std::vector<uint64_t> sp_full_plies;        // az_selfplay_get_full_plies: the full-ply masks of the last az_selfplay / az_selfplay_next
     // activation workspaces of the conv net: [0] the engine stream, [1] a second concurrent stream (az_arena's old-model
     // search); created on first use, shared by every model id
@@ -355,6 +358,10 @@ struct az_engine {
     int ar_log_cap = 0, ar_log_games = 0;
     std::vector<uint8_t> ar_moves;      // [games][AZ_MAX_PLIES] move record of the last az_arena (az_arena_get_moves)
     std::vector<int32_t> ar_len;
+    // az_arena_get_openings: where each game of the last az_arena started, and the random plies that led there from its base
+    std::vector<uint64_t> ar_open_boards;   // [games][2]
+    std::vector<int32_t> ar_open_len;       // [games]
+    std::vector<uint8_t> ar_open_moves;     // [games][OPENING_MAX_PLIES]
     // NNet::train
     Trainer* trainer = nullptr;
     bool train_open = false;
@@ -1055,6 +1062,11 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
             return fail(e, AZ_ERR_BAD_ARGUMENT, k ? "forced_playouts_k_e6 must be in 0 .. 16000000" : "policy_prune must be 0 or 1");
         if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "forced playouts cannot change while a self-play session is open");
         (k ? e->forced_playouts_k_e6 : e->policy_prune) = value;
+        return AZ_OK;
+    }
+    if (is("arena_opening_plies")) {
+        if (value < 0 || value > OPENING_MAX_PLIES || (value & 1)) return fail(e, AZ_ERR_BAD_ARGUMENT, "arena_opening_plies must be 0 or an even value in 2 .. 12");
+        e->arena_opening_plies = value;
         return AZ_OK;
     }
     if (is("conv3_small") && (value == 0 || value == 1)) { e->netopt.conv3_small = (int)value; return AZ_OK; }
@@ -2140,6 +2152,14 @@ az_status az_selfplay_get_evals(az_engine* e, int32_t* rec_count, uint64_t* stat
     return AZ_OK;
 }
 
+// az_arena_get_openings of a call without openings: every game started from the one position, no random ply
+static void record_common_opening(az_engine* e, int G, uint64_t a, uint64_t b) {
+    e->ar_open_boards.resize((size_t)G * 2);
+    for (int g = 0; g < G; ++g) { e->ar_open_boards[2 * (size_t)g] = a; e->ar_open_boards[2 * (size_t)g + 1] = b; }
+    e->ar_open_len.assign((size_t)G, 0);
+    e->ar_open_moves.assign((size_t)G * OPENING_MAX_PLIES, 0);
+}
+
 az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], int8_t* results) {
     if (!e || !p || !out_wld) return AZ_ERR_BAD_ARGUMENT;
     if (p->num_games < 0 || p->num_sims <= 0 || p->max_depth < 0 || p->reserve < 8)
@@ -2163,6 +2183,10 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
     }
     if (G > 1024 * 64) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: at most 65536 games");
     if (p->record_evals < 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: negative record_evals");
+    if (p->use_start_board && !e->ar_book.empty())
+        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: start_board while an opening book is set (az_arena_set_opening_book with n = 0 clears it)");
+    // paired openings: game g and its seat-swapped twin g + half start from the opening of pair g % half (csrc/az_opening.h)
+    const bool openings = e->arena_opening_plies > 0 || !e->ar_book.empty();
     if (p->use_start_board) {
         const uint64_t a = p->start_board[0], b = p->start_board[1];
         if ((a & b) || ((a | b) & ~C4_FULL)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: start_board is not a pair of disjoint 7x6 bitboards");
@@ -2181,6 +2205,7 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
             e->ar_log_cap = 0;
             e->ar_moves.assign((size_t)G * AZ_MAX_PLIES, 0);      // no move is played on a finished board
             e->ar_len.assign((size_t)G, 0);
+            record_common_opening(e, G, a, b);
             if (p->allreduce_wld) return az_allreduce_u64(e, out_wld, 3);     // the shards' tallies, as on the played path
             return AZ_OK;
         }
@@ -2222,12 +2247,33 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
         ad.len = mem.alloc<int32_t>(G);
         HIPCHK(hipMemset(ad.moves, 0, (size_t)G * AZ_MAX_PLIES));
         HIPCHK(hipMemset(ad.len, 0, (size_t)G * sizeof(int32_t)));
-        {
+        ArenaOpenings op{};
+        if (openings) {
+            // one lane per game draws its pair's opening into ad.state and the opening record
+            op.seed = p->seed;
+            op.plies = (int32_t)e->arena_opening_plies;
+            op.nb = (int32_t)(e->ar_book.size() / 2);
+            if (op.nb) {
+                ulonglong2* book = mem.alloc<ulonglong2>((size_t)op.nb);
+                HIPCHK(hipMemcpy(book, e->ar_book.data(), e->ar_book.size() * 8, hipMemcpyHostToDevice));
+                op.book = book;
+            }
+            op.base = p->use_start_board ? make_ulonglong2(p->start_board[0], p->start_board[1]) : make_ulonglong2(0ull, 0ull);
+            op.len = mem.alloc<int32_t>(G);
+            op.moves = mem.alloc<uint8_t>((size_t)G * OPENING_MAX_PLIES);
+            launch_arena_openings(e->cfg.game, ad, op, s);
+        } else {
             // play_games' `board` (src/arena.rs:62-67): None = the initial board
             std::vector<uint64_t> st0((size_t)G * 2, 0ull);
             if (p->use_start_board)
                 for (int g = 0; g < G; ++g) { st0[2 * (size_t)g] = p->start_board[0]; st0[2 * (size_t)g + 1] = p->start_board[1]; }
             HIPCHK(hipMemcpy(ad.state, st0.data(), st0.size() * 8, hipMemcpyHostToDevice));
+        }
+        std::vector<uint64_t> open_boards;                      // the positions the games start from, before the first ply changes ad.state
+        if (openings) {
+            open_boards.resize((size_t)G * 2);
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipMemcpy(open_boards.data(), ad.state, open_boards.size() * 8, hipMemcpyDeviceToHost));
         }
         HIPCHK(hipMemset(ad.player, 1, G));
         HIPCHK(hipMemset(ad.alive, 1, G));
@@ -2303,6 +2349,15 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
         e->ar_len.resize((size_t)G);
         HIPCHK(hipMemcpy(e->ar_moves.data(), ad.moves, e->ar_moves.size(), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(e->ar_len.data(), ad.len, e->ar_len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (openings) {
+            e->ar_open_boards = std::move(open_boards);
+            e->ar_open_len.resize((size_t)G);
+            e->ar_open_moves.resize((size_t)G * OPENING_MAX_PLIES);
+            HIPCHK(hipMemcpy(e->ar_open_len.data(), op.len, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(e->ar_open_moves.data(), op.moves, (size_t)G * OPENING_MAX_PLIES, hipMemcpyDeviceToHost));
+        } else {
+            record_common_opening(e, G, p->use_start_board ? p->start_board[0] : 0ull, p->use_start_board ? p->start_board[1] : 0ull);
+        }
         e->stats.games += (uint64_t)G;
         if (p->allreduce_wld) {       // every rank returns the whole arena's tally (one 3-counter all-reduce)
             az_status rs = az_allreduce_u64(e, out_wld, 3);
@@ -2330,6 +2385,29 @@ az_status az_arena_get_moves(az_engine* e, int32_t* game_len, uint8_t* moves) {
     if (!e || e->ar_len.empty()) return fail(e, AZ_ERR_BAD_ARGUMENT, "no move record (run az_arena first)");
     if (game_len) std::memcpy(game_len, e->ar_len.data(), e->ar_len.size() * sizeof(int32_t));
     if (moves) std::memcpy(moves, e->ar_moves.data(), e->ar_moves.size());
+    return AZ_OK;
+}
+
+az_status az_arena_set_opening_book(az_engine* e, const uint64_t* boards, int32_t n) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (n < 0 || n > OPENING_MAX_BOOK || (n > 0 && !boards)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena_set_opening_book: 0 .. 65536 entries");
+    for (int32_t i = 0; i < n; ++i) {
+        const uint64_t a = boards[2 * (size_t)i], b = boards[2 * (size_t)i + 1];
+        if ((a & b) || ((a | b) & ~C4_FULL))
+            return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena_set_opening_book: entry " + std::to_string(i) + " is not a pair of disjoint 7x6 bitboards");
+        const ulonglong2 s0 = make_ulonglong2(a, b);
+        if ((e->cfg.game == 1 ? ConnectThree::ended_code(s0) : ConnectFour::ended_code(s0)) != E_NONE)
+            return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena_set_opening_book: entry " + std::to_string(i) + " is a finished position");
+    }
+    e->ar_book.assign(boards, boards + 2 * (size_t)n);
+    return AZ_OK;
+}
+
+az_status az_arena_get_openings(az_engine* e, uint64_t* boards, int32_t* len, uint8_t* moves) {
+    if (!e || e->ar_open_len.empty()) return fail(e, AZ_ERR_BAD_ARGUMENT, "no opening record (run az_arena first)");
+    if (boards) std::memcpy(boards, e->ar_open_boards.data(), e->ar_open_boards.size() * 8);
+    if (len) std::memcpy(len, e->ar_open_len.data(), e->ar_open_len.size() * sizeof(int32_t));
+    if (moves) std::memcpy(moves, e->ar_open_moves.data(), e->ar_open_moves.size());
     return AZ_OK;
 }
 

@@ -20,6 +20,7 @@
 #include "az_game.h"
 #include "az_playout.h"
 #include "az_forced.h"
+#include "az_opening.h"
 
 namespace az {
 
@@ -222,6 +223,17 @@ struct ArenaDev {
     int32_t* len;          // [G] plies played
 };
 
+// Paired openings of one az_arena call ("arena_opening_plies" / az_arena_set_opening_book; the rule: az_opening.h): game g of the shard
+// belongs to pair p = (first + g) % half, whose base is book[p % nb] while a book is set (nb > 0), else `base`.
+struct ArenaOpenings {
+    uint64_t seed;           // the arena's seed: ply j of pair p draws rng_draw(seed, p, j, RNG_OPENING)
+    int32_t plies, nb;       // random plies per opening (even, 0 .. OPENING_MAX_PLIES); entries of the book
+    const ulonglong2* book;  // [nb] {first seat's stones, second seat's stones}
+    ulonglong2 base;         // the call's start position without a book (start_board or the initial board)
+    int32_t* len;            // [G] out: the random plies played onto the base
+    uint8_t* moves;          // [G][OPENING_MAX_PLIES] out: those actions, zero behind len
+};
+
 // ---- launchers (all asynchronous on `s`; dispatch on TreeDev.game to the Game policy's instantiation) ------------------
 void launch_count_done(const int32_t* g_len, int lo, int hi, uint32_t* counter, hipStream_t s);   // *counter = #{lo <= i < hi : g_len[i] > 0}
 void launch_init_heads(const TreeDev& t, hipStream_t s);                      // zero every TreeHead, active = 1
@@ -299,6 +311,8 @@ void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s);
 constexpr int GAME_COUNT = 2;    // 0 = ConnectFour (the reference's Game), 1 = ConnectThree (the seam's second instantiation)
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s);
+// writes ad.state[g] (the position game g starts from, first seat to move), op.len and op.moves for every game of the shard
+void launch_arena_openings(int game, const ArenaDev& ad, const ArenaOpenings& op, hipStream_t s);
 void launch_arena_sync(const TreeDev& t_new, const TreeDev& t_old, const ArenaDev& ad, hipStream_t s);
 void launch_arena_move(const TreeDev& t, const ArenaDev& ad, uint64_t seed, hipStream_t s);
 void launch_emit_samples(const GamesDev& gd, const int64_t* offsets, int symmetries, ulonglong2* out_states,

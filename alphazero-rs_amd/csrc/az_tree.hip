@@ -1346,6 +1346,23 @@ __global__ __launch_bounds__(256) void k_emit_samples(GamesDev gd, const int64_t
     }
 }
 
+// ---- paired arena openings: one lane per game grows its pair's opening (az_opening.h) and writes the game's start position ----
+template <class G>
+__global__ __launch_bounds__(256) void k_arena_openings(ArenaDev ad, ArenaOpenings op) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ad.G) return;
+    const uint64_t pair = ad.half > 0 ? (uint64_t)(ad.first + g) % (uint64_t)ad.half : (uint64_t)(ad.first + g);   // (a one-game total has no twin)
+    const ulonglong2 base = op.nb > 0 ? op.book[opening_book_index(pair, (uint32_t)op.nb)] : op.base;
+    uint8_t mv[OPENING_MAX_PLIES];
+#pragma unroll
+    for (int j = 0; j < OPENING_MAX_PLIES; ++j) mv[j] = 0;
+    typename G::State out;
+    const int len = opening_grow<G>(base, op.seed, pair, op.plies, &out, mv);
+    ad.state[g] = out;
+    op.len[g] = len;
+    for (int j = 0; j < OPENING_MAX_PLIES; ++j) op.moves[(size_t)g * OPENING_MAX_PLIES + j] = mv[j];
+}
+
 // ---- arena::play_game, one ply for every running game (src/arena.rs:18-41) ------------------------
 // Which model moves: seat 0 moves when cur_player == +1; games g < half seat (new, old), the rest (old, new).
 __global__ void k_arena_sync(TreeDev tn, TreeDev to, ArenaDev ad) {
@@ -1551,6 +1568,10 @@ void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb
 }
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s) {
     hipLaunchKernelGGL(k_sync_active, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gd);
+}
+static_assert(OPENING_E_NONE == E_NONE && OPENING_E_PLUS1 == E_PLUS1, "az_opening.h restates the ecodes of az_common.h");
+void launch_arena_openings(int game, const ArenaDev& ad, const ArenaOpenings& op, hipStream_t s) {
+    AZ_FOR_GAME(game, hipLaunchKernelGGL(k_arena_openings<TG>, dim3((ad.G + 255) / 256), dim3(256), 0, s, ad, op));
 }
 void launch_arena_sync(const TreeDev& t_new, const TreeDev& t_old, const ArenaDev& ad, hipStream_t s) {
     hipLaunchKernelGGL(k_arena_sync, dim3((ad.G + 255) / 256), dim3(256), 0, s, t_new, t_old, ad);

@@ -87,6 +87,7 @@ EXPORTS = [
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
     "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
+    "az_arena_set_opening_book", "az_arena_get_openings",
     "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
 COMM_ID_BYTES = 128
@@ -146,6 +147,8 @@ def load_library(path=LIB_PATH):
         "az_arena": (i32, [vp, C.POINTER(az_arena_params), vp, vp]),
         "az_arena_get_evals": (i32, [vp, i32, vp, vp, vp, vp]),
         "az_arena_get_moves": (i32, [vp, vp, vp]),
+        "az_arena_set_opening_book": (i32, [vp, vp, i32]),
+        "az_arena_get_openings": (i32, [vp, vp, vp, vp]),
         "az_comm_unique_id": (i32, [vp, vp]),
         "az_comm_local_id": (i32, [vp, i32, vp]),
         "az_comm_init": (i32, [vp, i32, i32, vp]),
@@ -338,6 +341,28 @@ class Engine:
         (include/az_engine.h)."""
         self.set_option("policy_prune", 1 if prune else 0)
         self.set_option("forced_playouts_k_e6", int(round(float(k) * 1e6)))
+
+    def set_arena_openings(self, plies):
+        """Paired arena openings (never self-play or the tree calls): arena game g and its seat-swapped twin g + total/2 start from the
+        same position, `plies` random quiet plies (even, 2 .. 12) played onto the pair's base -- the opening book's entry, start_board or
+        the initial board -- and different from pair to pair.  0 switches the random plies off (the default); the value travels as
+        "arena_opening_plies" (include/az_engine.h)."""
+        self.set_option("arena_opening_plies", int(plies))
+
+    def arena_set_opening_book(self, boards):
+        """az_arena_set_opening_book: boards [n, 2] (first seat's stones, second seat's stones), first seat to move; pair p of every later
+        arena() starts from entry p % n.  None or an empty list clears the book."""
+        b = np.ascontiguousarray(np.zeros((0, 2)) if boards is None else boards, dtype=np.uint64).reshape(-1, 2)
+        self._check(self._lib.az_arena_set_opening_book(self._h, _ptr(b) if len(b) else None, len(b)))
+
+    def arena_get_openings(self, n_games):
+        """Openings of the last arena(): (boards [n_games, 2] the position each game started from, len [n_games] the random plies played
+        onto its base, moves [n_games, 12] those actions)."""
+        boards = np.zeros((n_games, 2), np.uint64)
+        ln = np.zeros(n_games, np.int32)
+        moves = np.zeros((n_games, 12), np.uint8)
+        self._check(self._lib.az_arena_get_openings(self._h, _ptr(boards), _ptr(ln), _ptr(moves)))
+        return boards, ln, moves
 
     def selfplay_full_plies(self):
         """az_selfplay_get_full_plies: uint64 [n], bit `ply` of word i set when that ply of the i-th episode of the last selfplay() /

@@ -286,6 +286,35 @@ const char* az_last_error(const az_engine* e);
  *                                        that one pi is both recorded and sampled from.  The `counts` and `q` outputs stay RAW
  *                           A captured search graph is keyed on the forced-playout arguments, so one captured with others is never
  *                           replayed.  Playing strength with the option on is unmeasured
+ *   arena openings "arena_opening_plies"  0 (default, OFF) or an even value 2 .. 12; odd, negative and larger values are refused
+ *                           (AZ_ERR_BAD_ARGUMENT).  State of the engine, like every option; only az_arena reads it.
+ *                           PAIRED OPENINGS, strictly opt-in: with plies 0 and no opening book (az_arena_set_opening_book) every output
+ *                           of every entry is bit for bit what it is without the feature.  The arena searches at temperature 0 and a
+ *                           net is a function of the state, so from one position all games of a seating are the same game; with
+ *                           openings on, game g of an arena of `total` games (GLOBAL index) and its seat-swapped twin g + total/2
+ *                           start from the same position, which differs from pair to pair: the opening's bias cancels inside the pair
+ *                           and the tally is over total/2 different games.  The rule (csrc/az_opening.h):
+ *                             pair       half = total / 2;  game g belongs to pair p = g % half
+ *                             base       book[p % nb] while a book of nb entries is set; else start_board when use_start_board is
+ *                                        set; else the initial board.  A book together with use_start_board is refused
+ *                             plies      for j = 0 .. n-1, s the current canonical state:
+ *                                          C1 = the legal actions a, ascending, behind which the game goes on;
+ *                                          C2 = those of C1 after which the next mover has no immediately winning reply;
+ *                                          C = C2 if it is not empty, else C1; if C is empty, stop;
+ *                                          a = C[rng_choose(rng_draw(seed, p, j, 7), |C|)] (7 = RNG_OPENING; seed = the call's seed)
+ *                             used       the longest EVEN prefix of what was played (an odd last ply is dropped): the first seat is
+ *                                        to move and the position is {first seat's stones, second seat's stones}, a start_board; it
+ *                                        is never finished
+ *                             contract   game g is bit for bit (result, move record, eval log) the game of the sharded single-game call
+ *                                        {total_games = total, first_game = g, num_games = 1, use_start_board = 1, start_board = the
+ *                                        opening of g} with the feature off.  So shards add up to the unsharded arena, and
+ *                                        allreduce_wld, record_evals, num_sim_threads, both games, fp8 and "eval_mirror" models behave
+ *                                        as they do from a start_board: the tie-break stream stays (seed, global game, ply = stones on
+ *                                        the board), tree, hash and cache bounds stay those of a 42-ply game, az_arena_get_moves and
+ *                                        az_stats hold only the plies the models played (an opening ply adds to no counter), and a
+ *                                        finished start_board takes the early return it takes without the option
+ *                           The openings are drawn on the device by one small kernel per az_arena call.  Whether paired openings change
+ *                           which candidates a gate accepts is unmeasured
  *   search   "search_graph" n (default 20, even, 0 = off): n simulation steps per captured hipGraph replay (conv nets) ...
  *            "search_graph_rows" n (default 1024): ... for searches whose expected leaf batch has at most n rows (the arena, the drain
  *                           of a self-play call, single trees: there the host's launch calls set the pace; on big batches the kernels do)
@@ -558,6 +587,16 @@ az_status az_arena_get_evals(az_engine* e, int32_t which, int32_t* rec_count, ui
  * board sequence play_game's `verbose` prints, src/arena.rs:20-27; what one reaches for when an arena game diverges).  Either
  * may be NULL. */
 az_status az_arena_get_moves(az_engine* e, int32_t* game_len, uint8_t* moves);
+/* Opening book of the paired arena openings (option "arena_opening_plies" above): boards [n][2], each entry written as start_board
+ * is -- {first seat's stones, second seat's stones}, first seat to move.  Pair p of every later az_arena starts from entry p % n
+ * (plus "arena_opening_plies" random plies).  n = 0 clears the book; at most 65536 entries; the book is copied into the engine.
+ * Refused with AZ_ERR_BAD_ARGUMENT, leaving the previous book in place: overlapping stones, bits outside the 7x6 board, an entry
+ * that is finished under the engine's game, n out of range.  While a book is set, az_arena with use_start_board != 0 is refused. */
+az_status az_arena_set_opening_book(az_engine* e, const uint64_t* boards, int32_t n);
+/* Openings of the last az_arena: boards [num_games][2] the position each game started from, len [num_games] the random plies played
+ * onto its base, moves [num_games][12] those actions (zero behind len).  Without the feature: the common start position and len = 0.
+ * Any pointer may be NULL.  AZ_ERR_BAD_ARGUMENT before the first az_arena. */
+az_status az_arena_get_openings(az_engine* e, uint64_t* boards, int32_t* len, uint8_t* moves);
 
 /* ---- the collective of the sharded Coach loop (no reference counterpart: the reference is one process,
  * src/coach.rs:241-272 fans episodes out over a rayon pool; here one process per GPU plays a shard of the global

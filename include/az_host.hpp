@@ -138,6 +138,13 @@ class Engine {
         check(az_set_option(e_, "policy_prune", prune ? 1 : 0));
         check(az_set_option(e_, "forced_playouts_k_e6", (int64_t)std::llround(k * 1e6)));
     }
+    // Paired arena openings ("arena_opening_plies", include/az_engine.h): arena game g and its seat-swapped twin start from the same
+    // position, `plies` random quiet plies (even, 2 .. 12) onto the pair's base; never self-play or the tree calls.  0 switches them off
+    void set_arena_openings(int64_t plies) { check(az_set_option(e_, "arena_opening_plies", plies)); }
+    // az_arena_set_opening_book: boards [n][2] {first seat's stones, second seat's stones}; pair p starts from entry p % n.  Empty clears it
+    void arena_set_opening_book(const std::vector<uint64_t>& boards) {
+        check(az_arena_set_opening_book(e_, boards.empty() ? nullptr : boards.data(), (int32_t)(boards.size() / 2)));
+    }
     // az_selfplay_get_full_plies: bit `ply` of word i = that ply of the i-th episode of the last az_selfplay / az_selfplay_next call
     // (n_games episodes) was a full move and became a tuple
     std::vector<uint64_t> selfplay_full_plies(size_t n_games) const {
@@ -600,7 +607,15 @@ class Coach {
                 e_.net_set_class(model_id, AZ_NET_CLASS_BF16);
             }
             uint64_t wld[3] = {0, 0, 0};
-            e_.check(az_arena(e_.raw(), &a, wld, nullptr));
+            {
+                // paired openings around the gate only: on before az_arena, off again behind it (also when it throws)
+                struct OpeningsGuard {
+                    Engine& e; int64_t plies;
+                    OpeningsGuard(Engine& e_, int64_t plies_) : e(e_), plies(plies_) { if (plies > 0) e.set_arena_openings(plies); }
+                    ~OpeningsGuard() { if (plies > 0) { try { e.set_arena_openings(0); } catch (...) {} } }
+                } openings_guard(e_, arena_opening_plies);
+                e_.check(az_arena(e_.raw(), &a, wld, nullptr));
+            }
             r.nwins = (size_t)wld[0]; r.pwins = (size_t)wld[1]; r.draws = (size_t)wld[2];
             std::printf("NEW/PREV WINS : %zu / %zu; DRAWS : %zu\n", r.nwins, r.pwins, r.draws);        // :381
             r.accepted = !(r.pwins + r.nwins == 0 || (float)r.nwins / (float)(r.pwins + r.nwins) < update_threshold);   // :383-390
@@ -641,6 +656,9 @@ class Coach {
     // behind it.  k 0 (the default): the engine is never asked
     double forced_playouts_k = 0.0;
     bool policy_prune = false;
+    // Paired openings of the gate (Engine::set_arena_openings): set before the iteration's az_arena and cleared behind it.  0 (the
+    // default): the engine is never asked
+    int64_t arena_opening_plies = 0;
     // "eval_mirror" (Engine::set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
     // run under the mirror-canonical function, so the gate compares like with like.  false (the default): the engine is never asked
     bool eval_mirror = false;

@@ -111,6 +111,9 @@ extern "C" {
     pub fn az_arena(e: *mut az_engine, p: *const az_arena_params, out_wld: *mut u64, results: *mut i8) -> c_int;
     pub fn az_arena_get_evals(e: *mut az_engine, which: i32, rec_count: *mut i32, states: *mut u64, pis: *mut f32, vs: *mut f32) -> c_int;
     pub fn az_arena_get_moves(e: *mut az_engine, game_len: *mut i32, moves: *mut u8) -> c_int;
+    // paired arena openings ("arena_opening_plies"): the opening book, and where the games of the last az_arena started
+    pub fn az_arena_set_opening_book(e: *mut az_engine, boards: *const u64, n: i32) -> c_int;
+    pub fn az_arena_get_openings(e: *mut az_engine, boards: *mut u64, len: *mut i32, moves: *mut u8) -> c_int;
     // ---- the collective of the sharded Coach loop (one process per GPU; RCCL on the engine's stream)
     pub fn az_comm_unique_id(e: *mut az_engine, id: *mut u8) -> c_int;
     // an in-process communicator: engines of this process, one host thread each, form one world without RCCL

@@ -2,10 +2,10 @@
 (az_net_set_class), compared two ways:
   move agreement  100-simulation temp-0 searches from at least 2000 distinct positions of the run's own self-play samples, rooted with
                   az_tree_reset: the share of equal moves, and mean / max |d pi| of the visit distributions (counts / sum)
-  arena           az_arena from each of the 49 two-ply openings as start_board, both seatings, fp8 (new) against bf16 (old).  At temp 0
-                  the games of one arena call differ only by tie-breaks, so a call from the empty board is two games, not a sample:
-                  the openings are what makes 98 different games.  A bf16-against-bf16 control of the same shape gives the tally
-                  a pair of equal players produces.
+  arena           ONE 98-game az_arena over a 49-entry opening book (az_arena_set_opening_book: the 49 two-ply openings), fp8 (new) against
+                  bf16 (old): pair p plays opening p in both seatings.  At temp 0 the games of an arena from one position differ only by
+                  tie-breaks, so a call from the empty board is two games, not a sample: the openings are what makes 98 different games.
+                  A bf16-against-bf16 control of the same shape gives the tally a pair of equal players produces.
 The input is the checkpoint directory of a short run of examples/connect_four.py (a random-init net has near-uniform priors and says
 nothing):  python examples/connect_four.py --checkpoint D --iters 3 --eps 1024 --sims 50 --slots 1024 --arena 32 --epochs 4
            python tools/fp8_strength.py D [--positions 2000] [--sims 100]"""
@@ -56,11 +56,10 @@ def openings():
 
 
 tally = {}
+e.arena_set_opening_book([sb for _, _, sb in openings()])
 for name, new_id in (("fp8 vs bf16", 1), ("bf16 vs bf16 (control)", 2)):
-    wld = np.zeros(3, np.int64)
-    for c1, c2, sb in openings():
-        w, _ = e.arena(2, a.sims, new_model_id=new_id, old_model_id=0, seed=1000 + 7 * c1 + c2, start_board=sb)
-        wld += w.astype(np.int64)
+    w, _ = e.arena(98, a.sims, new_model_id=new_id, old_model_id=0, seed=1000)
+    wld = w.astype(np.int64)
     tally[name] = wld.tolist()
     print(f"arena over the 49 two-ply openings x both seatings, {name}: W/L/D of the first-named = {wld[0]} / {wld[1]} / {wld[2]}")
 e.close()
