@@ -4,6 +4,7 @@ hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED: the tree
 kernels reproduce the reference's f32 operation order (src/node.rs:343-357) and
 an FMA contraction would change visit counts.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -16,7 +17,6 @@ LIB = os.path.join(PKG_DIR, "libaz_engine.so")
 # load it (engine.Engine(diag=True)); the shipped library above does not contain any of it and refuses those option values.
 LIB_DIAG = os.path.join(PKG_DIR, "libaz_engine_diag.so")
 SOURCES = ["az_tree.hip", "az_net.hip", "az_train.hip", "az_engine.hip"]
-HEADERS = ["az_common.h", "az_combine.h", "az_local_comm.h", "az_game.h", "az_tree.h", "az_net.h", "az_fp8.h", "az_noise.h", "az_playout.h", "az_forced.h", "az_opening.h", "az_mirror.h", "az_train.h", "az_net_diag.inc", os.path.join("..", "..", "include", "az_engine.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall",
          "-Wno-unused-result"]
 
@@ -38,7 +38,9 @@ def build_engine(force=False, verbose=True, diag=True):
 
 def _build(LIB, suffix, extra_flags, force, verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
+    # every header under csrc/ is a dependency of every source: a new one needs no entry here
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")))
+    hdrs.append(os.path.join(CSRC, "..", "..", "include", "az_engine.h"))
     # a library newer than every source and header is current even where the object files did not travel with it
     if not force and not _stale(LIB, [os.path.join(CSRC, s) for s in SOURCES] + hdrs):
         return LIB

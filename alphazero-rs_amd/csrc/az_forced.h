@@ -1,6 +1,6 @@
 // az_forced.h -- forced playouts at the root and policy target pruning ("forced_playouts_k_e6" / "policy_prune", include/az_engine.h;
 // KataGo, Wu 2019, section 3.2).  HIP-free apart from the host/device qualifier (AZF_HD, as az_playout.h has AZP_HD):
-// the tree kernels and the g++ twin of the tests (tests/cpp/forced_twin.cpp) compile this text, and both give the same bits.  Integer
+// the tree kernels and the g++ twin of the tests (tests/cpp/selfplay_twin.cpp) compile this text, and both give the same bits.  Integer
 // operations and correctly rounded f32 * / + sqrt only: explicit *_rn intrinsics on the device, plain operators under g++ -O2
 // -ffp-contract=off.  The square root is __builtin_sqrtf on both sides, NOT __fsqrt_rn (the comment above puct_sqrt_parent in az_common.h).
 #pragma once

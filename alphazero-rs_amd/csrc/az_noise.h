@@ -1,6 +1,6 @@
 // az_noise.h -- the sampler of the opt-in Dirichlet root noise (include/az_engine.h "root_noise_eps_e6").
 // Plain C++ with no HIP in it: hipcc compiles it for the device (az_tree.hip), g++ -O2 -ffp-contract=off for the host (the twin of
-// tests/cpp/noise_twin.cpp), and both produce the same bits.  It uses integer operations and correctly rounded f32
+// tests/cpp/selfplay_twin.cpp), and both produce the same bits.  It uses integer operations and correctly rounded f32
 // + - * / sqrt only -- explicit *_rn intrinsics on the device, where the compiler would otherwise contract a * b + c and where a bare
 // v_sqrt_f32 is 1 ulp off (az_common.h) -- and carries its own log2 / exp2: no call into libm or the device math library.
 //

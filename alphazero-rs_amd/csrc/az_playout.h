@@ -1,6 +1,6 @@
 // az_playout.h -- playout cap randomization ("playout_cap_sims" / "playout_cap_full_e6", include/az_engine.h): which moves of a self-play
 // episode get the full simulation budget.  HIP-free apart from the host/device qualifier (AZP_HD, as az_noise.h has AZN_HD): the tree kernels, the engine's host code and the g++
-// twin of the tests (tests/cpp/playout_cap_twin.cpp) compile this text.
+// twin of the tests (tests/cpp/selfplay_twin.cpp) compile this text.
 #pragma once
 #include <cstdint>
 #if defined(__HIPCC__)

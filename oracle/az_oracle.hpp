@@ -346,6 +346,9 @@ struct AsyncMcts {
     size_t action_size;
     // one (state, pi, v) record per NN evaluation, for replay parity
     std::function<void(const G&, const float*, float)> on_eval;
+    // TEST SEAM, never set by anything in oracle/: when set, it replaces best_child for the FIRST selection of a simulation (the
+    // loop's first pass, where the node is the call's root); thread = the simulation's index within its lock-step step.
+    std::function<size_t(size_t idx, bool filter, size_t thread)> root_select;
 
     // src/async_mcts.rs:27-48
     AsyncMcts(size_t reserve, size_t sims, size_t threads, size_t maxd, size_t model,
@@ -383,11 +386,8 @@ struct AsyncMcts {
         return {pi, v};
     }
 
-    // src/async_mcts.rs:74-115
-    // Returns pi; fills counts/q (per action) when non-null.
-    std::vector<float> get_action_prob(const G& s, float temp, uint64_t seed, uint64_t game_id,
-                                       uint64_t ply, uint16_t* counts_out = nullptr,
-                                       float* q_out = nullptr) {
+    // src/async_mcts.rs:81 and S10 / S1: the root node of get_action_prob(s), with its prior.
+    size_t root_of(const G& s) {
         size_t root;
         auto found = nodes->lookup_state_id(s);                     // :81
         if (found) {
@@ -408,6 +408,15 @@ struct AsyncMcts {
                 nodes->set_policy_unlocked(root, std::move(pv.first));
             }
         }
+        return root;
+    }
+
+    // src/async_mcts.rs:74-115
+    // Returns pi; fills counts/q (per action) when non-null.
+    std::vector<float> get_action_prob(const G& s, float temp, uint64_t seed, uint64_t game_id,
+                                       uint64_t ply, uint16_t* counts_out = nullptr,
+                                       float* q_out = nullptr) {
+        size_t root = root_of(s);
         search(root);                                               // :82
         Node<G>* root_node = nodes->get(root);
         std::vector<uint16_t> counts(action_size, 0);               // :87
@@ -420,6 +429,11 @@ struct AsyncMcts {
         }
         if (counts_out) for (size_t i = 0; i < action_size; ++i) counts_out[i] = counts[i];
         if (q_out) for (size_t i = 0; i < action_size; ++i) q_out[i] = qs[i];
+        return policy_of(counts, temp, seed, game_id, ply);
+    }
+
+    // src/async_mcts.rs:96-114: the root's visit counts -> pi.
+    std::vector<float> policy_of(const std::vector<uint16_t>& counts, float temp, uint64_t seed, uint64_t game_id, uint64_t ply) {
         std::vector<float> probs(action_size, 0.0f);
         if (temp == 0.0f) {                                         // :97-107
             uint16_t max_val = 0;
@@ -471,13 +485,13 @@ struct AsyncMcts {
         int kind = 0;               // 0 value known (terminal / depth), 1 leaf waits for the net, 2 abandoned
         float v = 0.0f;
     };
-    Pending select_phase(size_t root_idx) {
+    Pending select_phase(size_t root_idx, size_t thread) {
         stats.sims++;
         Pending pd;
         pd.cur = root_idx;
         pd.node_path.reserve(64);
         size_t depth = 0;
-        bool cur_visited = false;
+        bool cur_visited = false, first_pass = true;
         auto abandon = [&]() {
             for (size_t idx : pd.node_path) nodes->get(idx)->revert_visit();
             if (cur_visited) nodes->get(pd.cur)->revert_visit();
@@ -493,11 +507,13 @@ struct AsyncMcts {
             cur_visited = true;
             if (depth > max_depth) { pd.v = head->s->eval_heuristic(); return pd; }   // :241-244 (B10)
             if (head->e != 0.0f) { pd.v = head->e; stats.terminal_hits++; return pd; } // :246-249
-            size_t c = nodes->best_child(cur, cpuct, false);        // :255-258, first_iteration
+            const bool hook = first_pass && root_select;
+            first_pass = false;
+            size_t c = hook ? root_select(cur, false, thread) : nodes->best_child(cur, cpuct, false);   // :255-258, first_iteration
             stats.depth_sum++;
             if (nodes->state(c) == std::optional<NodeState>(NodeState::Locked)) {     // `_ => continue`, :275
                 if (nodes->all_children_locked(cur)) { abandon(); return pd; }        // S11
-                c = nodes->best_child(cur, cpuct, true);            // C8: filter = !first_iteration
+                c = hook ? root_select(cur, true, thread) : nodes->best_child(cur, cpuct, true);        // C8: filter = !first_iteration
             }
             auto st = nodes->state(c);
             if (st == std::optional<NodeState>(NodeState::PlaceHolder)) {             // :261-268
@@ -537,7 +553,7 @@ struct AsyncMcts {
         for (size_t step = 0; step < steps; ++step) {
             std::vector<Pending> pend;
             pend.reserve(num_threads);
-            for (size_t t = 0; t < num_threads; ++t) pend.push_back(select_phase(root_idx));
+            for (size_t t = 0; t < num_threads; ++t) pend.push_back(select_phase(root_idx, t));
             for (auto& pd : pend) {                                 // the step's leaves: evaluated together, finished in thread order
                 if (pd.kind != 1) continue;
                 Node<G>* leaf = nodes->get(pd.cur);
@@ -568,12 +584,15 @@ struct AsyncMcts {
         node_path.reserve(64);
         size_t depth = 0;
         float v;
+        bool first_pass = true;
         for (;;) {
             Node<G>* head = nodes->get(cur);
             head->visit();                                          // :251; S5 (A6): before the checks
             if (depth > max_depth) { v = head->s->eval_heuristic(); break; }  // :241-244 (B10)
             if (head->e != 0.0f) { v = head->e; stats.terminal_hits++; break; } // :246-249
-            size_t c = nodes->best_child(cur, cpuct, false);        // :255-258 (single thread: filter never needed)
+            size_t c = (first_pass && root_select) ? root_select(cur, false, 0)
+                                                   : nodes->best_child(cur, cpuct, false);   // :255-258 (single thread: filter never needed)
+            first_pass = false;
             stats.depth_sum++;
             auto st = nodes->state(c);
             if (st == std::optional<NodeState>(NodeState::PlaceHolder)) {     // :261-268

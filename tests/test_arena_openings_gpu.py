@@ -309,11 +309,11 @@ def test_python_and_cpp_coach_agree_with_arena_openings(engine_mod, tmp_path):
         assert not e.arena_get_openings(4)[1].any()                                # the option is at 0 after learn()
     finally:
         e.close()
-    exe = os.path.join(tmp_path, "test_coach_openings")
+    exe = os.path.join(tmp_path, "test_coach_options")
     libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_openings.cpp"),
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
                            "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "4"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
+    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "arena_opening_plies=4"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
     crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
     assert len(rep) == len(crep) == 1
     for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):

@@ -432,11 +432,11 @@ def test_python_and_cpp_coach_agree_with_eval_mirror(engine_mod, tmp_path):
             e.close()
     rep = run_py(dirs["py"], True)
     run_py(dirs["plain"], False)
-    exe = os.path.join(tmp_path, "test_coach_mirror")
+    exe = os.path.join(tmp_path, "test_coach_options")
     libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_mirror.cpp"),
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
                            "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(Cn), str(seed), "1"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
+    out = subprocess.run([exe, dirs["cpp"], str(Cn), str(seed), "eval_mirror=1", "num_eps=64"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
     crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
     assert len(rep) == len(crep) == 1
     for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):

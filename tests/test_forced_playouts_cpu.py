@@ -1,5 +1,5 @@
 """Forced playouts and policy target pruning without a GPU ("forced_playouts_k_e6" / "policy_prune", include/az_engine.h): the predicates
-of csrc/az_forced.h in their g++ build against a Python restatement in numpy f32, the twin (tests/cpp/forced_twin.cpp) against the unchanged
+of csrc/az_forced.h in their g++ build against a Python restatement in numpy f32, the twin (tests/cpp/selfplay_twin.cpp) against the unchanged
 oracle where the two must agree (k = 0), the conditions that keep the GPU parity tests from passing vacuously -- on the seeds and shapes
 those tests use --, and the keys and Coach fields on both hosts."""
 import os
@@ -11,7 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import forced_twin as ft      # noqa: E402
+import selfplay_twin as ft      # noqa: E402
 
 HASH_SALT, MODEL_SALT = 1234, 0x51ED27
 KEYS = ("forced_playouts_k_e6", "policy_prune")
@@ -107,7 +107,7 @@ def test_twin_with_k_zero_equals_the_oracle_selfplay(oracle, threads):
     n, sims = 12, 24
     ref = oracle.selfplay(n, sims, net_kind=oracle.NET_HASH, salt=HASH_SALT, seed=11, first_game_id=5, sim_threads=threads)
     for prune in (0, 1):                                                # policy_prune is inert while k = 0
-        got = ft.selfplay(n, sims, 0.0, prune, net_kind=ft.NET_HASH, salt=HASH_SALT, seed=11, first_game_id=5, sim_threads=threads)
+        got = ft.selfplay(n, sims, k=0.0, prune=prune, net_kind=ft.NET_HASH, salt=HASH_SALT, seed=11, first_game_id=5, sim_threads=threads)
         assert got["count"] == ref["count"] == 2 * int(ref["game_len"].sum())
         assert np.array_equal(got["game_len"], ref["game_len"]) and np.array_equal(got["moves"], ref["moves"])
         assert np.array_equal(got["boards"], ref["boards"])
@@ -132,7 +132,7 @@ def test_twin_with_k_zero_equals_the_oracle_tree_calls(oracle, threads):
         s = (0, 0)
         for move in range(6):
             temp = 1.0 if move < 4 else 0.0
-            a = tw.get_action_prob(s, temp, 3, 40 + g, k=0.0, prune=1)
+            a = tw.get_action_prob(s[0], s[1], temp, 3, 40 + g, k=0.0, prune=1)
             b = orc.get_action_prob(s[0], s[1], temp, seed=3, game_id=40 + g)
             assert np.array_equal(a[0].view(np.uint32), np.asarray(b[0], np.float32).view(np.uint32)), (g, move)
             assert np.array_equal(a[1], b[1]) and np.array_equal(a[2].view(np.uint32), np.asarray(b[2], np.float32).view(np.uint32))
@@ -146,9 +146,9 @@ def test_twin_with_k_zero_equals_the_oracle_tree_calls(oracle, threads):
 def test_conditions_hold_for_the_gpu_tests_seeds(shape):
     kw = dict(GPU_SHAPES[shape])
     sims = kw.pop("sims")
-    base = ft.selfplay(100, sims, 0.0, 0, net_kind=ft.NET_HASH, salt=GPU_SALT, first_game_id=1000, **kw)
+    base = ft.selfplay(100, sims, k=0.0, prune=0, net_kind=ft.NET_HASH, salt=GPU_SALT, first_game_id=1000, **kw)
     for prune in (0, 1):
-        r = ft.selfplay(100, sims, 2.0, prune, net_kind=ft.NET_HASH, salt=GPU_SALT, first_game_id=1000, **kw)
+        r = ft.selfplay(100, sims, k=2.0, prune=prune, net_kind=ft.NET_HASH, salt=GPU_SALT, first_game_id=1000, **kw)
         print(shape, "prune", prune)
         check_conditions(r["ctr"], prune, inflight=kw.get("sim_threads", 1) > 1)
         assert not np.array_equal(r["moves"], base["moves"])            # the games really differ from those without the feature
@@ -167,7 +167,7 @@ def test_conditions_hold_for_the_tree_call_shape():
             for g in range(40):
                 tw = ft.Tree(48, net_kind=ft.NET_HASH, salt=GPU_SALT, threads=threads)
                 for temp in (1.0, 0.0):
-                    tw.get_action_prob((0, 0), temp, 3, 40 + g, k=2.0, prune=prune)
+                    tw.get_action_prob(0, 0, temp, 3, 40 + g, k=2.0, prune=prune)
                 ctr = ft.add_counters(ctr, ft.counters(tw.ctr))
                 tw.close()
             check_conditions(ctr, prune, inflight=threads > 1)
@@ -175,8 +175,8 @@ def test_conditions_hold_for_the_tree_call_shape():
 
 def test_pruned_pi_keeps_the_raw_counts_and_moves_mass_to_the_best_child():
     tw0, tw1 = ft.Tree(48, net_kind=ft.NET_HASH, salt=HASH_SALT), ft.Tree(48, net_kind=ft.NET_HASH, salt=HASH_SALT)
-    pi0, c0, q0 = tw0.get_action_prob((0, 0), 1.0, 3, 7, k=2.0, prune=0)
-    pi1, c1, q1 = tw1.get_action_prob((0, 0), 1.0, 3, 7, k=2.0, prune=1)
+    pi0, c0, q0 = tw0.get_action_prob(0, 0, 1.0, 3, 7, k=2.0, prune=0)
+    pi1, c1, q1 = tw1.get_action_prob(0, 0, 1.0, 3, 7, k=2.0, prune=1)
     assert np.array_equal(c0, c1) and np.array_equal(q0.view(np.uint32), q1.view(np.uint32))       # the search is the same; counts and q stay raw
     assert int(c0.sum()) == 48
     b = int(np.argmax(c0))

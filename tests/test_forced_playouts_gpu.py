@@ -1,5 +1,5 @@
 """Forced playouts and policy target pruning on the GPU ("forced_playouts_k_e6" / "policy_prune", include/az_engine.h), held to the
-project's bar: bit-exact against the twin (tests/cpp/forced_twin.cpp -- the unchanged oracle with the feature restated around it, and the
+project's bar: bit-exact against the twin (tests/cpp/selfplay_twin.cpp -- the unchanged oracle with the feature restated around it, and the
 g++ build of the predicates the kernels compile) on every path a forced move can take, and bit for bit WITHOUT effect where it must have
 none.
 
@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import forced_twin as ft      # noqa: E402
+import selfplay_twin as ft      # noqa: E402
 
 HASH_SALT, MODEL_SALT = 1234, 0x51ED27
 AZ_ERR_BAD_ARGUMENT = 1
@@ -225,7 +225,7 @@ def test_tree_call_parity(engine, prune, threads):
         for call, temp in enumerate((1.0, 0.0, 1.0, 0.0)):
             pi, counts, q = tb.get_action_prob(states, temp, seed=3, first_game_id=40)
             for g in range(G):
-                rpi, rc, rq = twins[g].get_action_prob((int(states[g, 0]), int(states[g, 1])), temp, 3, 40 + g, k=K, prune=prune)
+                rpi, rc, rq = twins[g].get_action_prob(int(states[g, 0]), int(states[g, 1]), temp, 3, 40 + g, k=K, prune=prune)
                 assert np.array_equal(counts[g], rc), (call, g, counts[g], rc)                      # raw
                 assert np.array_equal(q[g].view(np.uint32), rq.view(np.uint32)), (call, g)
                 assert np.array_equal(pi[g].view(np.uint32), rpi.view(np.uint32)), (call, g, pi[g], rpi)
@@ -283,7 +283,7 @@ def test_slot_call_parity(engine, prune):
     for g in range(G):
         tw = ft.Tree(sims, net_kind=ft.NET_HASH, salt=oracle_salt(10))
         for call, (s, temp, pi, counts, q) in enumerate(got[g]):
-            rpi, rc, rq = tw.get_action_prob(s, temp, 31, 500 + g, k=K, prune=prune)
+            rpi, rc, rq = tw.get_action_prob(s[0], s[1], temp, 31, 500 + g, k=K, prune=prune)
             assert np.array_equal(counts, rc) and np.array_equal(q.view(np.uint32), rq.view(np.uint32)), (g, call)
             assert np.array_equal(pi.view(np.uint32), rpi.view(np.uint32)), (g, call, pi, rpi)
         ctr = ft.add_counters(ctr, ft.counters(tw.ctr))
@@ -309,7 +309,7 @@ MODES = {
 def test_selfplay_parity(engine, mode, prune):
     options, threads, sims, seed = MODES[mode]
     got = forced_selfplay(engine, sims, K, prune, seed, threads=threads, options=options)
-    ref = ft.selfplay(N_GAMES, sims, K, prune, net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=seed, first_game_id=1000, sim_threads=threads)
+    ref = ft.selfplay(N_GAMES, sims, k=K, prune=prune, net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=seed, first_game_id=1000, sim_threads=threads)
     check_against_twin(got, ref, prune, inflight=threads > 1)
 
 
@@ -318,7 +318,7 @@ def test_selfplay_parity_connect_three(engine3, mode):
     options = {"fused": {}, "per-simulation": PER_SIM, "async": {"selfplay_async": 1, "eval_dedup": 2}}[mode]
     try:
         got = forced_selfplay(engine3, 25, K, 1, 12, options=options)
-        ref = ft.selfplay(N_GAMES, 25, K, 1, net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=12, first_game_id=1000, game_kind=ft.GAME_CONNECT3)
+        ref = ft.selfplay(N_GAMES, 25, k=K, prune=1, net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=12, first_game_id=1000, game_kind=ft.GAME_CONNECT3)
         check_against_twin(got, ref, 1)
     finally:
         _restore(engine3)
@@ -331,12 +331,12 @@ def test_composition_with_root_noise_and_playout_cap(engine, mode):
     threads = 4 if mode == "four-sim-threads" else 1
     got = forced_selfplay(engine, 24, K, 1, 11, threads=threads, options=options, cap=(8, 500000), noise=(0.25, 0.3))
     kw = dict(net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=11, first_game_id=1000, sim_threads=threads, cap_sims=8, full_e6=500000, eps=0.25, alpha=0.3)
-    ref = ft.selfplay(N_GAMES, 24, K, 1, **kw)
+    ref = ft.selfplay(N_GAMES, 24, k=K, prune=1, **kw)
     check_against_twin(got, ref, 1, inflight=threads > 1)
     full, plies = sum(bin(int(m)).count("1") for m in ref["full_masks"]), int(ref["game_len"].sum())
     assert 0.1 <= full / plies <= 0.9
     assert ref["ctr"]["moves"] == full and ref["ctr"]["root_sel"] == 24 * full          # only the full moves were forced moves
-    plain = ft.selfplay(N_GAMES, 24, 0.0, 0, **kw)
+    plain = ft.selfplay(N_GAMES, 24, k=0.0, prune=0, **kw)
     assert not np.array_equal(plain["moves"], ref["moves"])              # the feature really changed the games
 
 
@@ -346,7 +346,7 @@ def test_session_in_chunks_equals_one_call(engine, async_mode):
     options = {"selfplay_async": 1, "eval_dedup": 2} if async_mode else PER_SIM
     sims, seed = 44, 12
     one = forced_selfplay(engine, sims, K, 1, seed, options=options)
-    ref = ft.selfplay(N_GAMES, sims, K, 1, net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=seed, first_game_id=1000)
+    ref = ft.selfplay(N_GAMES, sims, k=K, prune=1, net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=seed, first_game_id=1000)
     check_against_twin(one, ref, 1)
     engine.selfplay_begin(N_GAMES, sims, 10, seed=seed, first_game_id=1000, concurrent=SLOTS)
     try:
@@ -384,7 +384,7 @@ def test_conv_net_replay_parity(engine_mod):
         fs = np.concatenate([states[g, :cnt[g]] for g in range(N_GAMES)])
         fp = np.concatenate([pis[g, :cnt[g]] for g in range(N_GAMES)])
         fv = np.concatenate([vs[g, :cnt[g]] for g in range(N_GAMES)])
-        ref = ft.selfplay(N_GAMES, sims, k, 1, net_kind=ft.NET_REPLAY, seed=seed, first_game_id=1000, replay=(off, fs, fp, fv), eps=noise[0],
+        ref = ft.selfplay(N_GAMES, sims, k=k, prune=1, net_kind=ft.NET_REPLAY, seed=seed, first_game_id=1000, replay=(off, fs, fp, fv), eps=noise[0],
                           alpha=noise[1])
         assert not ref["replay_bad"].any()
         check_against_twin(got, ref, 1)
@@ -430,11 +430,11 @@ def test_python_and_cpp_coach_agree_with_forced_playouts(engine_mod, tmp_path):
     finally:
         e.close()
     assert seen == [("policy_prune", 1), ("forced_playouts_k_e6", 2000000), ("policy_prune", 0), ("forced_playouts_k_e6", 0)], seen
-    exe = os.path.join(tmp_path, "test_coach_forced")
+    exe = os.path.join(tmp_path, "test_coach_options")
     libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_forced.cpp"),
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
                            "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "2.0", "1"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
+    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "root_noise_eps=0.25", "root_noise_alpha=0.3", "forced_playouts_k=2.0", "policy_prune=1"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
     crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
     assert len(rep) == len(crep) == 1
     for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):

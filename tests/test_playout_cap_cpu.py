@@ -1,5 +1,5 @@
 """Playout cap randomization without a GPU ("playout_cap_sims" / "playout_cap_full_e6", include/az_engine.h): the predicate of
-csrc/az_playout.h in its g++ build against a Python restatement, the twin (tests/cpp/playout_cap_twin.cpp) against the unchanged oracle
+csrc/az_playout.h in its g++ build against a Python restatement, the twin (tests/cpp/selfplay_twin.cpp) against the unchanged oracle
 where the two must agree, the twin's own bookkeeping, and the new export and keys in every place that names the ABI."""
 import ctypes
 import os
@@ -12,7 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import playout_cap_twin as pc      # noqa: E402
+import selfplay_twin as pc      # noqa: E402
 
 HASH_SALT = 1234
 KEYS = ("playout_cap_sims", "playout_cap_full_e6")
@@ -54,7 +54,7 @@ def test_twin_with_every_move_full_equals_the_oracle(oracle, net, threads):
     kind, okind, salt = (pc.NET_STUB, oracle.NET_STUB, 0) if net == "stub" else (pc.NET_HASH, oracle.NET_HASH, HASH_SALT)
     n, sims = 12, 24
     ref = oracle.selfplay(n, sims, net_kind=okind, salt=salt, seed=11, first_game_id=5, sim_threads=threads)
-    got = pc.selfplay(n, sims, 8, 1000000, net_kind=kind, salt=salt, seed=11, first_game_id=5, sim_threads=threads)
+    got = pc.selfplay(n, sims, cap_sims=8, full_e6=1000000, net_kind=kind, salt=salt, seed=11, first_game_id=5, sim_threads=threads)
     assert got["count"] == ref["count"] == 2 * int(ref["game_len"].sum())
     assert np.array_equal(got["game_len"], ref["game_len"]) and np.array_equal(got["moves"], ref["moves"])
     assert np.array_equal(got["boards"], ref["boards"])
@@ -69,7 +69,7 @@ def test_twin_at_a_quarter_full(oracle, sims, cap_sims, threads, game):
     n, seed, full_e6 = 48, 11, 250000
     kind = pc.GAME_CONNECT3 if game == "c3" else pc.GAME_BITS
     ended = oracle.c3_ended if game == "c3" else oracle.c4_ended
-    r = pc.selfplay(n, sims, cap_sims, full_e6, net_kind=pc.NET_HASH, salt=HASH_SALT, seed=seed, sim_threads=threads, game_kind=kind)
+    r = pc.selfplay(n, sims, cap_sims=cap_sims, full_e6=full_e6, net_kind=pc.NET_HASH, salt=HASH_SALT, seed=seed, sim_threads=threads, game_kind=kind)
     full = pc.popcount(r["full_masks"])
     plies = int(r["game_len"].sum())
     assert r["count"] == 2 * full                                      # tuples = full plies x both symmetries
@@ -95,7 +95,7 @@ def test_twin_at_a_quarter_full(oracle, sims, cap_sims, threads, game):
 
 
 def test_twin_with_no_full_move_emits_nothing():
-    r = pc.selfplay(6, 24, 8, 0, net_kind=pc.NET_HASH, salt=HASH_SALT, seed=12)
+    r = pc.selfplay(6, 24, cap_sims=8, full_e6=0, net_kind=pc.NET_HASH, salt=HASH_SALT, seed=12)
     assert r["count"] == 0 and not r["full_masks"].any() and (r["game_len"] >= 7).all()
     assert r["sims"] == r["budgets"] == 8 * int(r["game_len"].sum())
 

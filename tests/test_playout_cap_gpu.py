@@ -1,5 +1,5 @@
 """Playout cap randomization on the GPU ("playout_cap_sims" / "playout_cap_full_e6", include/az_engine.h), held to the project's bar:
-bit-exact against the twin (tests/cpp/playout_cap_twin.cpp -- the unchanged oracle with the feature restated around it, and the g++
+bit-exact against the twin (tests/cpp/selfplay_twin.cpp -- the unchanged oracle with the feature restated around it, and the g++
 build of the predicate the kernels compile) on every path a self-play move can take, and bit for bit WITHOUT effect where it must have
 none.
 
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import playout_cap_twin as pc      # noqa: E402
+import selfplay_twin as pc      # noqa: E402
 
 HASH_SALT, MODEL_SALT = 1234, 0x51ED27
 AZ_ERR_BAD_ARGUMENT = 1
@@ -190,7 +190,7 @@ MODES = {
 def test_selfplay_parity(engine, mode):
     options, threads, (sims, cap_sims), full_e6, seed = MODES[mode]
     got = capped_selfplay(engine, sims, cap_sims, full_e6, seed, threads=threads, options=options)
-    ref = pc.selfplay(N_GAMES, sims, cap_sims, full_e6, net_kind=pc.NET_HASH, salt=oracle_salt(10), seed=seed, first_game_id=1000, sim_threads=threads)
+    ref = pc.selfplay(N_GAMES, sims, cap_sims=cap_sims, full_e6=full_e6, net_kind=pc.NET_HASH, salt=oracle_salt(10), seed=seed, first_game_id=1000, sim_threads=threads)
     check_against_twin(got, ref)
 
 
@@ -199,7 +199,7 @@ def test_selfplay_parity_connect_three(engine3, mode):
     options = {"fused": {}, "per-simulation": PER_SIM, "async": {"selfplay_async": 1, "eval_dedup": 2}}[mode]
     try:
         got = capped_selfplay(engine3, 25, 5, 500000, 12, options=options)
-        ref = pc.selfplay(N_GAMES, 25, 5, 500000, net_kind=pc.NET_HASH, salt=oracle_salt(10), seed=12, first_game_id=1000, game_kind=pc.GAME_CONNECT3)
+        ref = pc.selfplay(N_GAMES, 25, cap_sims=5, full_e6=500000, net_kind=pc.NET_HASH, salt=oracle_salt(10), seed=12, first_game_id=1000, game_kind=pc.GAME_CONNECT3)
         check_against_twin(got, ref)
     finally:
         _restore(engine3)
@@ -213,15 +213,15 @@ def test_selfplay_parity_with_root_noise(engine, mode):
     engine.set_root_noise(0.25, 0.3)
     got = capped_selfplay(engine, sims, cap_sims, full_e6, seed, threads=threads, options=options)
     kw = dict(net_kind=pc.NET_HASH, salt=oracle_salt(10), seed=seed, first_game_id=1000, sim_threads=threads)
-    ref = pc.selfplay(N_GAMES, sims, cap_sims, full_e6, eps=0.25, alpha=0.3, **kw)
+    ref = pc.selfplay(N_GAMES, sims, cap_sims=cap_sims, full_e6=full_e6, eps=0.25, alpha=0.3, **kw)
     check_against_twin(got, ref)
-    plain = pc.selfplay(N_GAMES, sims, cap_sims, full_e6, **kw)
+    plain = pc.selfplay(N_GAMES, sims, cap_sims=cap_sims, full_e6=full_e6, **kw)
     assert not np.array_equal(plain["moves"], ref["moves"])              # the noise really changed the games
 
 
 def test_no_full_move_emits_no_tuple(engine):
     got = capped_selfplay(engine, 24, 8, 0, 11)
-    ref = pc.selfplay(N_GAMES, 24, 8, 0, net_kind=pc.NET_HASH, salt=oracle_salt(10), seed=11, first_game_id=1000)
+    ref = pc.selfplay(N_GAMES, 24, cap_sims=8, full_e6=0, net_kind=pc.NET_HASH, salt=oracle_salt(10), seed=11, first_game_id=1000)
     assert got["count"] == 0 and not got["full_masks"].any()
     check_against_twin(got, ref, degenerate_ok=True)
 
@@ -274,7 +274,7 @@ def test_conv_net_replay_parity(engine_mod, klass):
             fs = np.concatenate([states[g, :cnt[g]] for g in range(N_GAMES)])
             fp = np.concatenate([pis[g, :cnt[g]] for g in range(N_GAMES)])
             fv = np.concatenate([vs[g, :cnt[g]] for g in range(N_GAMES)])
-            ref = pc.selfplay(N_GAMES, sims, cap_sims, full_e6, net_kind=pc.NET_REPLAY, seed=seed, first_game_id=1000, replay=(off, fs, fp, fv))
+            ref = pc.selfplay(N_GAMES, sims, cap_sims=cap_sims, full_e6=full_e6, net_kind=pc.NET_REPLAY, seed=seed, first_game_id=1000, replay=(off, fs, fp, fv))
             assert not ref["replay_bad"].any()
             check_against_twin(got, ref)
             st = got["stats"]
@@ -350,11 +350,11 @@ def test_python_and_cpp_coach_agree_with_a_playout_cap(engine_mod, tmp_path):
     finally:
         e.close()
     assert len(seen) == 1 and seen[0][1] == seen[0][2] and 0.1 * seen[0][0] <= seen[0][1] <= 0.9 * seen[0][0], seen
-    exe = os.path.join(tmp_path, "test_coach_playout_cap")
+    exe = os.path.join(tmp_path, "test_coach_options")
     libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_playout_cap.cpp"),
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
                            "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "5", "0.5"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
+    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "playout_cap_sims=5", "playout_cap_full=0.5"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
     crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
     assert len(rep) == len(crep) == 1
     for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):

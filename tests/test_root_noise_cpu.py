@@ -1,4 +1,4 @@
-"""Dirichlet root noise without a GPU: the twin (tests/cpp/noise_twin.cpp: the oracle's search with the noise restated around it) against
+"""Dirichlet root noise without a GPU: the twin (tests/cpp/selfplay_twin.cpp: the oracle's search with the noise restated around it) against
 the unchanged oracle, the sampler of csrc/az_noise.h (its g++ build) against the Dirichlet distribution, its polynomials against
 float64, the mixing formula, and the hosts' plumbing."""
 import math
@@ -12,7 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import noise_twin as tw      # noqa: E402
+import selfplay_twin as tw      # noqa: E402
 
 SALT = 4242
 

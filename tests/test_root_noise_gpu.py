@@ -1,5 +1,5 @@
 """Dirichlet root noise on the GPU ("root_noise_eps_e6" / "root_noise_alpha_e6", include/az_engine.h), held to the project's bar: bit-exact
-against the twin (tests/cpp/noise_twin.cpp -- the unchanged oracle search with the noise restated around it, and the g++ build of the
+against the twin (tests/cpp/selfplay_twin.cpp -- the unchanged oracle search with the noise restated around it, and the g++ build of the
 sampler the kernels compile) on every path a get_action_prob can take, and bit for bit WITHOUT effect where it must have none."""
 import json
 import os
@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import noise_twin as tw      # noqa: E402
+import selfplay_twin as tw      # noqa: E402
 
 HASH_SALT, MODEL_SALT = 1234, 0x51ED27
 AZ_ERR_BAD_ARGUMENT = 1
@@ -392,11 +392,11 @@ def test_python_and_cpp_coach_agree_with_root_noise(engine_mod, tmp_path):
             e.close()
     rep = run_py(dirs["py"], 0.25)
     run_py(dirs["plain"], 0.0)
-    exe = os.path.join(tmp_path, "test_coach_noise")
+    exe = os.path.join(tmp_path, "test_coach_options")
     libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_noise.cpp"),
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
                            "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "0.25", "0.3"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
+    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "root_noise_eps=0.25", "root_noise_alpha=0.3"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
     crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
     assert len(rep) == len(crep) == 1
     for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):
