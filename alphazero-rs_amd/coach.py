@@ -101,45 +101,34 @@ class Coach:
         save_examples(path, self.history)
         return path
 
+    @staticmethod
     @contextlib.contextmanager
+    def _scoped(active, apply, clear):
+        """An engine option that holds for one block only: apply() before it when `active`, clear() behind it (also when the block
+        raises).  Not active: the engine is never asked."""
+        if active:
+            apply()
+        try:
+            yield
+        finally:
+            if active:
+                clear()
+
     def _selfplay_root_noise(self):
-        if self.root_noise_eps > 0:
-            self.engine.set_root_noise(self.root_noise_eps, self.root_noise_alpha)
-        try:
-            yield
-        finally:
-            if self.root_noise_eps > 0:
-                self.engine.set_root_noise(0.0, self.root_noise_alpha)
+        return self._scoped(self.root_noise_eps > 0, lambda: self.engine.set_root_noise(self.root_noise_eps, self.root_noise_alpha),
+                            lambda: self.engine.set_root_noise(0.0, self.root_noise_alpha))
 
-    @contextlib.contextmanager
     def _selfplay_playout_cap(self):
-        if self.playout_cap_sims > 0:
-            self.engine.set_playout_cap(self.playout_cap_sims, self.playout_cap_full)
-        try:
-            yield
-        finally:
-            if self.playout_cap_sims > 0:
-                self.engine.set_playout_cap(0, self.playout_cap_full)
+        return self._scoped(self.playout_cap_sims > 0, lambda: self.engine.set_playout_cap(self.playout_cap_sims, self.playout_cap_full),
+                            lambda: self.engine.set_playout_cap(0, self.playout_cap_full))
 
-    @contextlib.contextmanager
     def _selfplay_forced_playouts(self):
-        if self.forced_playouts_k > 0:
-            self.engine.set_forced_playouts(self.forced_playouts_k, self.policy_prune)
-        try:
-            yield
-        finally:
-            if self.forced_playouts_k > 0:
-                self.engine.set_forced_playouts(0.0, False)
+        return self._scoped(self.forced_playouts_k > 0, lambda: self.engine.set_forced_playouts(self.forced_playouts_k, self.policy_prune),
+                            lambda: self.engine.set_forced_playouts(0.0, False))
 
-    @contextlib.contextmanager
     def _arena_openings(self):
-        if self.arena_opening_plies > 0:
-            self.engine.set_arena_openings(self.arena_opening_plies)
-        try:
-            yield
-        finally:
-            if self.arena_opening_plies > 0:
-                self.engine.set_arena_openings(0)
+        return self._scoped(self.arena_opening_plies > 0, lambda: self.engine.set_arena_openings(self.arena_opening_plies),
+                            lambda: self.engine.set_arena_openings(0))
 
     def execute_episodes(self, model_id, iteration, seed):
         """The self-play fan-out of src/coach.rs:241-272: num_eps x execute_episode, sharded by global game id."""

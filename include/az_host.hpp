@@ -368,6 +368,17 @@ inline std::vector<int64_t> shuffle_permutation(size_t n, uint64_t seed, uint64_
     return perm;
 }
 
+// An engine option that holds for one scope only: apply() now when `active`, clear() when the scope is left (also by a throw).
+// active == false: the engine is never asked.  Several in one scope are cleared in the reverse of the order they were applied in.
+template <class Apply, class Clear>
+struct ScopedOption {
+    bool active; Clear clear;
+    ScopedOption(bool active_, Apply apply, Clear clear_) : active(active_), clear(std::move(clear_)) { if (active) apply(); }
+    ~ScopedOption() { if (active) { try { clear(); } catch (...) {} } }
+    ScopedOption(const ScopedOption&) = delete;
+    ScopedOption& operator=(const ScopedOption&) = delete;
+};
+
 class Coach {
   public:
     struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; };
@@ -540,23 +551,14 @@ class Coach {
                 if (selfplay_class != AZ_NET_CLASS_ENGINE) e_.net_set_class(model_id, selfplay_class);
                 {
                     // root noise around the episodes only: on before az_selfplay, off again behind it (also when it throws)
-                    struct NoiseGuard {
-                        Engine& e; double eps, alpha;
-                        NoiseGuard(Engine& e_, double eps_, double alpha_) : e(e_), eps(eps_), alpha(alpha_) { if (eps > 0) e.set_root_noise(eps, alpha); }
-                        ~NoiseGuard() { if (eps > 0) { try { e.set_root_noise(0.0, alpha); } catch (...) {} } }
-                    } guard(e_, root_noise_eps, root_noise_alpha);
+                    ScopedOption noise_guard(root_noise_eps > 0, [&] { e_.set_root_noise(root_noise_eps, root_noise_alpha); },
+                                             [&] { e_.set_root_noise(0.0, root_noise_alpha); });
                     // ... and so is the playout cap
-                    struct CapGuard {
-                        Engine& e; int64_t sims; double p;
-                        CapGuard(Engine& e_, int64_t sims_, double p_) : e(e_), sims(sims_), p(p_) { if (sims > 0) e.set_playout_cap(sims, p); }
-                        ~CapGuard() { if (sims > 0) { try { e.set_playout_cap(0, p); } catch (...) {} } }
-                    } cap_guard(e_, playout_cap_sims, playout_cap_full);
+                    ScopedOption cap_guard(playout_cap_sims > 0, [&] { e_.set_playout_cap(playout_cap_sims, playout_cap_full); },
+                                           [&] { e_.set_playout_cap(0, playout_cap_full); });
                     // ... and so are forced playouts and pruning
-                    struct ForcedGuard {
-                        Engine& e; double k;
-                        ForcedGuard(Engine& e_, double k_, bool prune_) : e(e_), k(k_) { if (k > 0) e.set_forced_playouts(k, prune_); }
-                        ~ForcedGuard() { if (k > 0) { try { e.set_forced_playouts(0.0, false); } catch (...) {} } }
-                    } forced_guard(e_, forced_playouts_k, policy_prune);
+                    ScopedOption forced_guard(forced_playouts_k > 0, [&] { e_.set_forced_playouts(forced_playouts_k, policy_prune); },
+                                              [&] { e_.set_forced_playouts(0.0, false); });
                     h = execute_episodes(model_id, iteration, seed);
                 }
                 if (h.len() > max_queue_length) {                   // keep the newest max_queue_length (:275-277)
@@ -609,11 +611,8 @@ class Coach {
             uint64_t wld[3] = {0, 0, 0};
             {
                 // paired openings around the gate only: on before az_arena, off again behind it (also when it throws)
-                struct OpeningsGuard {
-                    Engine& e; int64_t plies;
-                    OpeningsGuard(Engine& e_, int64_t plies_) : e(e_), plies(plies_) { if (plies > 0) e.set_arena_openings(plies); }
-                    ~OpeningsGuard() { if (plies > 0) { try { e.set_arena_openings(0); } catch (...) {} } }
-                } openings_guard(e_, arena_opening_plies);
+                ScopedOption openings_guard(arena_opening_plies > 0, [&] { e_.set_arena_openings(arena_opening_plies); },
+                                            [&] { e_.set_arena_openings(0); });
                 e_.check(az_arena(e_.raw(), &a, wld, nullptr));
             }
             r.nwins = (size_t)wld[0]; r.pwins = (size_t)wld[1]; r.draws = (size_t)wld[2];

@@ -2,9 +2,7 @@
 device's openings against the g++ build of csrc/az_opening.h (tests/opening_twin.py), every game against the oracle and against the
 contract -- game g IS the sharded single-game call from start_board = opening(g) with the feature off: result, move record and eval log --
 shards, the book, the refusals, the off state, and both Coaches."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,11 +11,12 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import feature_gpu as fg       # noqa: E402
 import opening_twin as ot      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-MODEL_SALT = 0x51ED27
+MODEL_SALT = fg.MODEL_SALT
 KEY = "arena_opening_plies"
 LOG_CAP = 21 * 51 + 8          # records per game and player: at most 21 moves of 50 simulations + a root each
 
@@ -284,42 +283,23 @@ def test_refusals(off, engine_mod, oracle):
 def test_python_and_cpp_coach_agree_with_arena_openings(engine_mod, tmp_path):
     """tests/test_coach_gpu.py::test_python_and_cpp_coach_agree with Coach.arena_opening_plies set on both hosts: byte-identical files; the
     option is on for the gate and off again behind it."""
-    from alphazero_rs_amd.coach import Coach
-    C, seed = 128, 11
-    dirs = {k: os.path.join(tmp_path, k) for k in ("py", "cpp")}
-    e = engine_mod.Engine(device=0, max_batch=256, net_channels=C)
-    try:
-        e.net_init_random(0, 3)
-        e.set_option("train_epochs", 1)
-        coach = Coach.setup(e, dirs["py"], 1000000, 0.55, 15, 3, 100000, 1, 64, 8, 1, 32, 25, 1, 1000, 1, log=lambda m: None)
+    seen = []
+
+    def configure(coach, e):
         coach.arena_opening_plies = 4
-        orig, seen = e.set_option, []
+        orig = e.set_option
 
         def spy(key, value):
             if key == KEY:
                 seen.append((key, value, e.arena_get_openings(8)[1].tolist() if seen else None))   # behind the gate: its games' openings
             return orig(key, value)
         e.set_option = spy
-        rep = coach.learn(seed=seed)
-        e.set_option = orig
+
+    def inspect(e):
+        del e.set_option                                 # the spy: the class's method again
         # on before the gate, off behind it -- and the gate's eight games were played from four-ply openings
         assert seen == [(KEY, 4, None), (KEY, 0, [4] * 8)], seen
         e.net_init_random(5, 1)
         e.arena(4, 10, new_model_id=5, old_model_id=5)
         assert not e.arena_get_openings(4)[1].any()                                # the option is at 0 after learn()
-    finally:
-        e.close()
-    exe = os.path.join(tmp_path, "test_coach_options")
-    libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
-                           "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "arena_opening_plies=4"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
-    crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
-    assert len(rep) == len(crep) == 1
-    for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):
-        assert rep[0][k] == crep[0][k], k
-    files = sorted(os.listdir(dirs["py"]))
-    assert files == sorted(os.listdir(dirs["cpp"])) and "0.examples" in files and "1.aznet" in files
-    for f in files:
-        with open(os.path.join(dirs["py"], f), "rb") as x, open(os.path.join(dirs["cpp"], f), "rb") as y:
-            assert x.read() == y.read(), f
+    fg.run_coach_pair(engine_mod, tmp_path, ["arena_opening_plies=4"], configure, inspect=inspect)

@@ -1,18 +1,15 @@
 """The opt-in "eval_mirror" on the GPU (include/az_engine.h): every forward of a conv model answers with F -- the net on the canonical
 orientation c(s) of the position, pi un-mirrored -- on every path, a position and its mirror image share one batch row and one cache
 entry, and nothing changes while the option is 0.  Every replay check feeds the engine's recorded rows to the unchanged oracle."""
-import json
-import os
-import subprocess
 import threading
 
 import numpy as np
 import pytest
 
+import feature_gpu as fg
 import mirror_twin as mt
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C = 256
 KEYS = ("moves", "game_len", "pis", "zs", "states")
 
@@ -71,17 +68,10 @@ def positions(oracle):
     return np.array(out + [(0, 0)] + SYMMETRIC, np.uint64)
 
 
-def _flatten(cnt, states, pis, vs, ids):
-    off = np.zeros(len(ids) + 1, np.int64)
-    off[1:] = np.cumsum([cnt[g] for g in ids])
-    cat = lambda a: np.ascontiguousarray(np.concatenate([a[g, :cnt[g]] for g in ids]))
-    return off, cat(states), cat(pis), cat(vs)
-
-
 def _replay_selfplay(oracle, got, logs, n, sims, seed, sim_threads=1, game_kind=None):
     kw = {} if game_kind is None else {"game_kind": game_kind}
     ref = oracle.selfplay(n, sims, net_kind=oracle.NET_REPLAY, seed=seed, threads=16, sim_threads=sim_threads,
-                          replay=_flatten(*logs, list(range(n))), **kw)
+                          replay=fg.flatten_eval_log(*logs), **kw)
     assert not ref["replay_bad"].any(), np.flatnonzero(ref["replay_bad"])[:5]
     assert np.array_equal(ref["moves"], got["moves"]) and np.array_equal(ref["game_len"], got["game_len"])
     assert np.array_equal(ref["pis"], got["pis"]) and np.array_equal(ref["zs"], got["zs"])
@@ -138,7 +128,7 @@ def test_selfplay_replays_and_executes_fewer_rows_than_distinct_states(mirror_on
     logs = e.selfplay_get_evals(n, cap)
     assert logs[0].max() <= cap and logs[0].min() > 0
     _replay_selfplay(oracle, got, logs, n, sims, seed)
-    _, fs, fp, fv = _flatten(*logs, list(range(n)))
+    _, fs, fp, fv = fg.flatten_eval_log(*logs)
     keys, first, inv = np.unique(mt.pack_batch(fs), return_index=True, return_inverse=True)
     upi, uv = e.predict_states(fs[first], 0)
     assert same((upi[inv], uv[inv]), (fp, fv))
@@ -275,7 +265,7 @@ def test_arena_replays_for_both_players(mirror_on, oracle):
     cap = 22 * (sims + 1) + 8
     wld, res = e.arena(num, sims, new_model_id=1, old_model_id=0, seed=9, record_evals=cap)
     logs = [e.arena_get_evals(w, num, cap) for w in (0, 1)]
-    rn, ro = (_flatten(*logs[w], list(range(num))) for w in (0, 1))
+    rn, ro = (fg.flatten_eval_log(*logs[w]) for w in (0, 1))
     owld, ores, bad = oracle.arena_ex(num, sims, first_game=0, n_games=num, net_kind=oracle.NET_REPLAY, seed=9, threads=16,
                                       replay_new=rn, replay_old=ro)
     assert not bad.any() and np.array_equal(ores, res) and owld.tolist() == wld.tolist() and int(wld.sum()) == num
@@ -407,7 +397,7 @@ def test_connect_three_replays(engine_mod, oracle):
         got = e.selfplay(n_games=n, num_sims=sims, model_id=0, seed=seed, record_evals=cap, want_boards=False)
         logs = e.selfplay_get_evals(n, cap)
         _replay_selfplay(oracle, got, logs, n, sims, seed, game_kind=oracle.GAME_CONNECT3)
-        _, fs, fp, fv = _flatten(*logs, list(range(n)))
+        _, fs, fp, fv = fg.flatten_eval_log(*logs)
         assert same(e.predict_states(fs[:512], 0), (fp[:512], fv[:512]))
         assert mt.canonical_batch(fs)[1].any()
     finally:
@@ -416,35 +406,8 @@ def test_connect_three_replays(engine_mod, oracle):
 
 # ---- 10. the hosts ----------------------------------------------------------------------------------------------------------------------
 def test_python_and_cpp_coach_agree_with_eval_mirror(engine_mod, tmp_path):
-    from alphazero_rs_amd.coach import Coach
-    Cn, seed = 128, 11
-    dirs = {k: os.path.join(tmp_path, k) for k in ("py", "cpp", "plain")}
-
-    def run_py(d, on):
-        e = engine_mod.Engine(device=0, max_batch=256, net_channels=Cn)
-        try:
-            e.net_init_random(0, 3)
-            e.set_option("train_epochs", 1)
-            coach = Coach.setup(e, d, 1000000, 0.55, 15, 3, 100000, 1, 64, 8, 1, 64, 25, 1, 1000, 1, log=lambda m: None)
+    def mirror(on):
+        def configure(coach, e):
             coach.eval_mirror = on
-            return coach.learn(seed=seed)
-        finally:
-            e.close()
-    rep = run_py(dirs["py"], True)
-    run_py(dirs["plain"], False)
-    exe = os.path.join(tmp_path, "test_coach_options")
-    libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
-                           "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(Cn), str(seed), "eval_mirror=1", "num_eps=64"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
-    crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
-    assert len(rep) == len(crep) == 1
-    for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):
-        assert rep[0][k] == crep[0][k], k
-    files = sorted(os.listdir(dirs["py"]))
-    assert files == sorted(os.listdir(dirs["cpp"])) and "0.examples" in files and "1.aznet" in files
-    for f in files:
-        with open(os.path.join(dirs["py"], f), "rb") as x, open(os.path.join(dirs["cpp"], f), "rb") as y:
-            assert x.read() == y.read(), f
-    with open(os.path.join(dirs["py"], "0.examples"), "rb") as x, open(os.path.join(dirs["plain"], "0.examples"), "rb") as y:
-        assert x.read() != y.read()
+        return configure
+    fg.run_coach_pair(engine_mod, tmp_path, ["eval_mirror=1", "num_eps=64"], mirror(True), num_eps=64, plain=mirror(False))

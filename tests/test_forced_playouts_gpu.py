@@ -10,9 +10,7 @@ least 5 % of the root selections it compared were decided by a forced child, wit
 while earlier simulations of its step were in flight, and with pruning on that the pruned counts differ from the raw ones on at least
 half of the moves and that a child went from two or more visits to none by the single-playout rule
 (tests/test_forced_playouts_cpu.py asserts the same on the CPU alone for these seeds)."""
-import json
 import os
-import subprocess
 import sys
 import threading
 
@@ -23,43 +21,24 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import feature_gpu as fg        # noqa: E402
 import selfplay_twin as ft      # noqa: E402
+from feature_gpu import COUNTERS, HASH_SALT, N_GAMES, PER_SIM, SLOTS, c4_play, oracle_salt      # noqa: E402
 
-HASH_SALT, MODEL_SALT = 1234, 0x51ED27
-AZ_ERR_BAD_ARGUMENT = 1
-N_GAMES, SLOTS = 100, 40
-COUNTERS = ("simulations", "leaf_evals", "expansions", "link_hits", "terminal_hits", "moves", "samples", "games")
 K = 2.0
-
-
-def oracle_salt(model_id):
-    return HASH_SALT + model_id * MODEL_SALT
-
-
-def _restore(e):
-    e.selfplay_end()
-    e.set_forced_playouts(0.0, False)
-    e.set_option("playout_cap_sims", 0)
-    e.set_option("playout_cap_full_e6", 250000)
-    e.set_root_noise(0.0, 1.0)
-    for k, v in (("eval_dedup", 1), ("fused_search", 1), ("selfplay_async", 0)):
-        e.set_option(k, v)
 
 
 @pytest.fixture(autouse=True)
 def forced_off_afterwards(engine):
     """The session's engine is shared with every other module: leave it as it was found."""
     yield
-    _restore(engine)
+    fg.restore(engine)
 
 
 @pytest.fixture(scope="module")
 def engine3(engine_mod):
     """The seam's second game (AZ_GAME_CONNECT_THREE)."""
-    e = engine_mod.Engine(device=0, max_batch=256, net_channels=128, game=engine_mod.GAME_CONNECT_THREE)
-    e.net_set_kind(10, engine_mod.NET_HASH, HASH_SALT)
-    yield e
-    e.close()
+    yield from fg.connect_three_engine(engine_mod)
 
 
 def check_conditions(ctr, prune, inflight=False):
@@ -73,91 +52,26 @@ def check_conditions(ctr, prune, inflight=False):
         assert ctr["to_zero"] >= 1, ctr
 
 
-def forced_selfplay(e, sims, k, prune, seed, threads=1, options=None, cap=None, noise=None, concurrent=SLOTS, n_games=N_GAMES, first_game_id=1000,
-                    model_id=10, **kw):
-    for key, v in (options or {}).items():
-        e.set_option(key, v)
-    if cap:
-        e.set_option("playout_cap_full_e6", cap[1])
-        e.set_option("playout_cap_sims", cap[0])
-    if noise:
-        e.set_root_noise(*noise)
-    e.set_forced_playouts(k, prune)
-    e.reset_stats()
-    got = e.selfplay(n_games=n_games, num_sims=sims, model_id=model_id, seed=seed, first_game_id=first_game_id, concurrent=concurrent,
-                     num_sim_threads=threads, **kw)
-    got["full_masks"] = e.selfplay_full_plies()
-    got["stats"] = e.stats()
-    return got
+def forced_selfplay(e, sims, k, prune, seed, **kw):
+    return fg.run_selfplay(e, sims, seed, forced=(k, prune), **kw)
 
 
 def check_against_twin(got, ref, prune, inflight=False):
-    assert np.array_equal(got["game_len"], ref["game_len"])
-    assert np.array_equal(got["moves"], ref["moves"])
-    assert np.array_equal(got["full_masks"], ref["full_masks"])
-    full = sum(bin(int(m)).count("1") for m in ref["full_masks"])
-    assert got["count"] == ref["count"] == 2 * full
-    assert np.array_equal(got["boards"].reshape(-1, 84), ref["boards"].reshape(-1, 84))
-    assert np.array_equal(got["pis"].view(np.uint32), ref["pis"].view(np.uint32))
-    assert np.array_equal(got["zs"].view(np.uint32), ref["zs"].view(np.uint32))
-    st, plies = got["stats"], int(ref["game_len"].sum())
-    assert st["simulations"] == ref["sims"] == ref["budgets"]
-    assert st["samples"] == full and st["moves"] == plies and st["games"] == len(ref["game_len"])
+    fg.check_samples_against_twin(got, ref)
     check_conditions(ref["ctr"], prune, inflight)
 
 
 # ---- options ------------------------------------------------------------------------------------------------------------------------------
 def test_option_ranges_and_open_session(engine, engine_mod):
-    for key, bad in (("forced_playouts_k_e6", (-1, 16000001, 1 << 40)), ("policy_prune", (-1, 2, 1000000))):
-        for v in bad:
-            with pytest.raises(engine_mod.AzError) as ei:
-                engine.set_option(key, v)
-            assert ei.value.status == AZ_ERR_BAD_ARGUMENT, (key, v)
-    for key, good in (("forced_playouts_k_e6", (0, 1, 16000000, 2000000)), ("policy_prune", (0, 1))):
-        for v in good:
-            engine.set_option(key, v)
-    engine.set_forced_playouts(0.0, False)
-    engine.selfplay_begin(4, 10, 10, seed=1)
-    try:
-        for key, v in (("forced_playouts_k_e6", 2000000), ("policy_prune", 1), ("forced_playouts_k_e6", 0), ("policy_prune", 0)):
-            with pytest.raises(engine_mod.AzError) as ei:
-                engine.set_option(key, v)
-            assert ei.value.status == AZ_ERR_BAD_ARGUMENT
-    finally:
-        engine.selfplay_end()
-    engine.set_option("forced_playouts_k_e6", 2000000)            # accepted again once the session is closed
+    fg.check_option_ranges(engine, engine_mod,
+                           bad=(("forced_playouts_k_e6", (-1, 16000001, 1 << 40)), ("policy_prune", (-1, 2, 1000000))),
+                           good=(("forced_playouts_k_e6", (0, 1, 16000000, 2000000)), ("policy_prune", (0, 1))),
+                           settle=lambda: engine.set_forced_playouts(0.0, False),
+                           locked=(("forced_playouts_k_e6", 2000000), ("policy_prune", 1), ("forced_playouts_k_e6", 0), ("policy_prune", 0)),
+                           reopen=("forced_playouts_k_e6", 2000000))
 
 
 # ---- off means off ----------------------------------------------------------------------------------------------------------------------------
-def _c4_play(mine, theirs, a):
-    mask = mine | theirs
-    nb = (mask + (1 << (a * 7))) & (0x3F << (a * 7))
-    return theirs, mine | nb
-
-
-def _tree_and_arena(e):
-    out = list(e.arena(16, 25, new_model_id=11, old_model_id=10, seed=4))
-    out += list(e.arena_get_moves(16))
-    tb = e.tree_create(6, reserve=ft.default_reserve(30), num_sims=30, max_depth=1000, model_id=10, cpuct=1)
-    states = np.zeros((6, 2), np.uint64)
-    for move in range(3):
-        pi, counts, q = tb.get_action_prob(states, 1.0 if move < 2 else 0.0, seed=3, first_game_id=40)
-        out += [pi, counts, q]
-        states = np.array([_c4_play(int(s[0]), int(s[1]), int(np.argmax(c))) for s, c in zip(states, counts)], np.uint64)
-    tb.close()
-    shared = e.tree_create(2, reserve=ft.default_reserve(30), num_sims=30, max_depth=1000, model_id=10, cpuct=1)
-    shared.share(0)
-    slot = shared.slot_acquire()
-    s = (0, 0)
-    for move in range(3):
-        pi, counts, q = shared.slot_get_action_prob(slot, s, 1.0, seed=31, game_id=5)
-        out += [pi, counts, q]
-        s = _c4_play(s[0], s[1], int(np.argmax(counts)))
-    shared.slot_release(slot)
-    shared.close()
-    return out
-
-
 OFF_RUNS = [dict(options={}, concurrent=SLOTS), dict(options={"selfplay_async": 1, "eval_dedup": 2}, concurrent=SLOTS),
             dict(options={"fused_search": 0}, concurrent=0, threads=4)]
 
@@ -180,7 +94,7 @@ def _off_outputs(e, touch):
     for key, v in (("selfplay_async", 0), ("eval_dedup", 1), ("fused_search", 1)):
         e.set_option(key, v)
     e.reset_stats()
-    other = _tree_and_arena(e)
+    other = fg.other_entry_points(e)
     return out, other, e.stats()
 
 
@@ -202,9 +116,7 @@ def test_off_equals_never_set(engine_mod):
             assert np.array_equal(a[key], b[key]), key
         for key in COUNTERS:
             assert a["stats"][key] == b["stats"][key], (key, a["stats"][key], b["stats"][key])
-    assert len(other_a) == len(other_b)
-    for a, b in zip(other_a, other_b):
-        assert np.array_equal(a, b)
+    fg.assert_same_outputs(other_a, other_b)
     for key in COUNTERS:
         assert st_a[key] == st_b[key], key
 
@@ -236,7 +148,7 @@ def test_tree_call_parity(engine, prune, threads):
                     assert (np.abs(pi - raw).max(axis=1) > 0).mean() >= 0.5
                     assert np.allclose(pi.sum(axis=1), 1.0, atol=1e-6)
             if call == 1:
-                states = np.array([_c4_play(int(s[0]), int(s[1]), int(np.argmax(c))) for s, c in zip(states, counts)], np.uint64)
+                states = np.array([c4_play(int(s[0]), int(s[1]), int(np.argmax(c))) for s, c in zip(states, counts)], np.uint64)
         for t in twins:
             ctr = ft.add_counters(ctr, ft.counters(t.ctr))
         check_conditions(ctr, prune, inflight=threads > 1)
@@ -266,7 +178,7 @@ def test_slot_call_parity(engine, prune):
                 pi, counts, q = shared.slot_get_action_prob(slot, s, temp, seed=31, game_id=500 + g)
                 seq.append((s, temp, pi, counts, q))
                 if call == 1:
-                    s = _c4_play(s[0], s[1], int(np.argmax(counts)))
+                    s = c4_play(s[0], s[1], int(np.argmax(counts)))
             got[g] = seq
             shared.slot_release(slot)
         except Exception as ex:      # noqa: BLE001
@@ -292,7 +204,6 @@ def test_slot_call_parity(engine, prune):
 
 
 # ---- self-play parity against the twin ------------------------------------------------------------------------------------------------------------
-PER_SIM = {"fused_search": 0}
 MODES = {
     # name: (options, threads, sims, seed)
     "fused-24": ({}, 1, 24, 11),
@@ -321,7 +232,7 @@ def test_selfplay_parity_connect_three(engine3, mode):
         ref = ft.selfplay(N_GAMES, 25, k=K, prune=1, net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=12, first_game_id=1000, game_kind=ft.GAME_CONNECT3)
         check_against_twin(got, ref, 1)
     finally:
-        _restore(engine3)
+        fg.restore(engine3)
 
 
 @pytest.mark.parametrize("mode", ["lock-step", "per-simulation", "async", "four-sim-threads"])
@@ -348,20 +259,8 @@ def test_session_in_chunks_equals_one_call(engine, async_mode):
     one = forced_selfplay(engine, sims, K, 1, seed, options=options)
     ref = ft.selfplay(N_GAMES, sims, k=K, prune=1, net_kind=ft.NET_HASH, salt=oracle_salt(10), seed=seed, first_game_id=1000)
     check_against_twin(one, ref, 1)
-    engine.selfplay_begin(N_GAMES, sims, 10, seed=seed, first_game_id=1000, concurrent=SLOTS)
-    try:
-        off = 0
-        for lo, n in ((0, 30), (30, 30), (60, 40)):
-            got = engine.selfplay_next(n)
-            cnt = 2 * int(one["game_len"][lo:lo + n].sum())
-            assert got["count"] == cnt
-            assert np.array_equal(got["game_len"], one["game_len"][lo:lo + n]) and np.array_equal(got["moves"], one["moves"][lo:lo + n])
-            for key in ("states", "boards", "pis", "zs"):
-                assert np.array_equal(got[key], one[key][off:off + cnt]), key
-            off += cnt
-        assert off == one["count"]
-    finally:
-        engine.selfplay_end()
+    fg.check_session_in_chunks(engine, one, ((0, 30), (30, 30), (60, 40)),
+                               dict(n_games=N_GAMES, num_sims=sims, model_id=10, seed=seed, first_game_id=1000, concurrent=SLOTS))
 
 
 # ---- conv-net replay parity ---------------------------------------------------------------------------------------------------------------------------
@@ -379,13 +278,8 @@ def test_conv_net_replay_parity(engine_mod):
         got = forced_selfplay(e, sims, k, 1, seed, model_id=0, record_evals=cap, noise=noise)
         cnt, states, pis, vs = e.selfplay_get_evals(N_GAMES, cap)
         assert (cnt > 0).all() and (cnt < cap).all()
-        off = np.zeros(N_GAMES + 1, np.int64)
-        off[1:] = np.cumsum(cnt)
-        fs = np.concatenate([states[g, :cnt[g]] for g in range(N_GAMES)])
-        fp = np.concatenate([pis[g, :cnt[g]] for g in range(N_GAMES)])
-        fv = np.concatenate([vs[g, :cnt[g]] for g in range(N_GAMES)])
-        ref = ft.selfplay(N_GAMES, sims, k=k, prune=1, net_kind=ft.NET_REPLAY, seed=seed, first_game_id=1000, replay=(off, fs, fp, fv), eps=noise[0],
-                          alpha=noise[1])
+        ref = ft.selfplay(N_GAMES, sims, k=k, prune=1, net_kind=ft.NET_REPLAY, seed=seed, first_game_id=1000,
+                          replay=fg.flatten_eval_log(cnt, states, pis, vs), eps=noise[0], alpha=noise[1])
         assert not ref["replay_bad"].any()
         check_against_twin(got, ref, 1)
         st = got["stats"]
@@ -396,51 +290,26 @@ def test_conv_net_replay_parity(engine_mod):
 
 # ---- the arena never sees it ---------------------------------------------------------------------------------------------------------------------------
 def test_arena_ignores_the_keys(engine):
-    want = list(engine.arena(16, 25, new_model_id=11, old_model_id=10, seed=4)) + list(engine.arena_get_moves(16))
+    want = fg.arena_outputs(engine)
     forced_selfplay(engine, 24, K, 1, 11, n_games=16, concurrent=8)     # leaves a forced arena behind in the pool; the keys stay set
-    got = list(engine.arena(16, 25, new_model_id=11, old_model_id=10, seed=4)) + list(engine.arena_get_moves(16))
-    assert len(got) == len(want)
-    for a, b in zip(got, want):
-        assert np.array_equal(a, b)
+    fg.assert_same_outputs(fg.arena_outputs(engine), want)
 
 
 # ---- the two Coaches ------------------------------------------------------------------------------------------------------------------------------------------
 def test_python_and_cpp_coach_agree_with_forced_playouts(engine_mod, tmp_path):
     """tests/test_coach_gpu.py::test_python_and_cpp_coach_agree with Coach.forced_playouts_k / policy_prune (and root noise) set on both
     hosts: byte-identical files; the option is on for the episodes and off again behind them."""
-    from alphazero_rs_amd.coach import Coach
-    C, seed = 128, 11
-    dirs = {k: os.path.join(tmp_path, k) for k in ("py", "cpp")}
-    e = engine_mod.Engine(device=0, max_batch=256, net_channels=C)
-    try:
-        e.net_init_random(0, 3)
-        e.set_option("train_epochs", 1)
-        coach = Coach.setup(e, dirs["py"], 1000000, 0.55, 15, 3, 100000, 1, 64, 8, 1, 32, 25, 1, 1000, 1, log=lambda m: None)
+    seen = []
+
+    def configure(coach, e):
         coach.root_noise_eps, coach.root_noise_alpha = 0.25, 0.3
         coach.forced_playouts_k, coach.policy_prune = K, True
-        orig, seen = e.set_option, []
+        orig = e.set_option
 
         def spy(key, value):
             if key in ("forced_playouts_k_e6", "policy_prune"):
                 seen.append((key, value))
             return orig(key, value)
         e.set_option = spy
-        rep = coach.learn(seed=seed)
-        e.set_option = orig
-    finally:
-        e.close()
+    fg.run_coach_pair(engine_mod, tmp_path, ["root_noise_eps=0.25", "root_noise_alpha=0.3", "forced_playouts_k=2.0", "policy_prune=1"], configure)
     assert seen == [("policy_prune", 1), ("forced_playouts_k_e6", 2000000), ("policy_prune", 0), ("forced_playouts_k_e6", 0)], seen
-    exe = os.path.join(tmp_path, "test_coach_options")
-    libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
-                           "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "root_noise_eps=0.25", "root_noise_alpha=0.3", "forced_playouts_k=2.0", "policy_prune=1"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
-    crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
-    assert len(rep) == len(crep) == 1
-    for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):
-        assert rep[0][k] == crep[0][k], k
-    files = sorted(os.listdir(dirs["py"]))
-    assert files == sorted(os.listdir(dirs["cpp"])) and "0.examples" in files and "1.aznet" in files
-    for f in files:
-        with open(os.path.join(dirs["py"], f), "rb") as x, open(os.path.join(dirs["cpp"], f), "rb") as y:
-            assert x.read() == y.read(), f

@@ -1,9 +1,7 @@
 """Dirichlet root noise on the GPU ("root_noise_eps_e6" / "root_noise_alpha_e6", include/az_engine.h), held to the project's bar: bit-exact
 against the twin (tests/cpp/selfplay_twin.cpp -- the unchanged oracle search with the noise restated around it, and the g++ build of the
 sampler the kernels compile) on every path a get_action_prob can take, and bit for bit WITHOUT effect where it must have none."""
-import json
 import os
-import subprocess
 import sys
 import threading
 
@@ -14,55 +12,32 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import feature_gpu as fg        # noqa: E402
 import selfplay_twin as tw      # noqa: E402
-
-HASH_SALT, MODEL_SALT = 1234, 0x51ED27
-AZ_ERR_BAD_ARGUMENT = 1
-
-
-def oracle_salt(model_id):
-    return HASH_SALT + model_id * MODEL_SALT
+from feature_gpu import HASH_SALT, c4_play, oracle_salt      # noqa: E402
 
 
 @pytest.fixture(autouse=True)
 def noise_off_afterwards(engine):
     """The session's engine is shared with every other module: leave it as it was found."""
     yield
-    engine.selfplay_end()
-    engine.set_root_noise(0.0, 1.0)
-    for k, v in (("eval_dedup", 1), ("fused_search", 1), ("selfplay_async", 0)):
-        engine.set_option(k, v)
+    fg.restore(engine)
 
 
 @pytest.fixture(scope="module")
 def engine3(engine_mod):
     """The seam's second game (AZ_GAME_CONNECT_THREE)."""
-    e = engine_mod.Engine(device=0, max_batch=256, net_channels=128, game=engine_mod.GAME_CONNECT_THREE)
-    e.net_set_kind(10, engine_mod.NET_HASH, HASH_SALT)
-    yield e
-    e.close()
+    yield from fg.connect_three_engine(engine_mod)
 
 
 # ---- 6. options -------------------------------------------------------------------------------------------------------------------------------
 def test_option_ranges_and_open_session(engine, engine_mod):
-    for key, bad in (("root_noise_eps_e6", (-1, 1000001)), ("root_noise_alpha_e6", (0, 49999, 100000001, -5))):
-        for v in bad:
-            with pytest.raises(engine_mod.AzError) as ei:
-                engine.set_option(key, v)
-            assert ei.value.status == AZ_ERR_BAD_ARGUMENT, (key, v)
-    for key, good in (("root_noise_eps_e6", (0, 1, 1000000, 250000)), ("root_noise_alpha_e6", (50000, 100000000, 300000))):
-        for v in good:
-            engine.set_option(key, v)
-    engine.set_root_noise(0.0, 1.0)
-    engine.selfplay_begin(4, 10, 10, seed=1)
-    try:
-        for key, v in (("root_noise_eps_e6", 250000), ("root_noise_alpha_e6", 300000), ("root_noise_eps_e6", 0)):
-            with pytest.raises(engine_mod.AzError) as ei:
-                engine.set_option(key, v)
-            assert ei.value.status == AZ_ERR_BAD_ARGUMENT
-    finally:
-        engine.selfplay_end()
-    engine.set_option("root_noise_eps_e6", 250000)          # accepted again once the session is closed
+    fg.check_option_ranges(engine, engine_mod,
+                           bad=(("root_noise_eps_e6", (-1, 1000001)), ("root_noise_alpha_e6", (0, 49999, 100000001, -5))),
+                           good=(("root_noise_eps_e6", (0, 1, 1000000, 250000)), ("root_noise_alpha_e6", (50000, 100000000, 300000))),
+                           settle=lambda: engine.set_root_noise(0.0, 1.0),
+                           locked=(("root_noise_eps_e6", 250000), ("root_noise_alpha_e6", 300000), ("root_noise_eps_e6", 0)),
+                           reopen=("root_noise_eps_e6", 250000))
 
 
 def _tree_outputs(engine, fused):
@@ -73,15 +48,9 @@ def _tree_outputs(engine, fused):
     for move in range(4):
         pi, counts, q = tb.get_action_prob(states, 1.0 if move < 2 else 0.0, seed=3, first_game_id=40)
         out += [pi, counts, q]
-        states = np.array([engine_mod_c4_play(int(s[0]), int(s[1]), int(np.argmax(c))) for s, c in zip(states, counts)], np.uint64)
+        states = np.array([c4_play(int(s[0]), int(s[1]), int(np.argmax(c))) for s, c in zip(states, counts)], np.uint64)
     tb.close()
     return out
-
-
-def engine_mod_c4_play(mine, theirs, a):
-    mask = mine | theirs
-    nb = (mask + (1 << (a * 7))) & (0x3F << (a * 7))
-    return theirs, mine | nb
 
 
 def test_eps_0_set_explicitly_equals_never_set(engine_mod):
@@ -130,7 +99,7 @@ def _random_roots(n, seed):
             s, plies, target = (0, 0), 0, int(rng.integers(0, 40))
             continue
         a = legal[min(int(rng.integers(0, 3)), len(legal) - 1)]
-        s = engine_mod_c4_play(s[0], s[1], a)
+        s = c4_play(s[0], s[1], a)
         plies += 1
     return out
 
@@ -213,13 +182,7 @@ def test_whole_game_search_parity_connect_three(engine3, oracle, threads):
 
 # ---- 9. self-play parity --------------------------------------------------------------------------------------------------------------------------
 def _check_selfplay(got, ref, symmetries=True):
-    assert np.array_equal(got["game_len"], ref["game_len"])
-    assert np.array_equal(got["moves"], ref["moves"])
-    step = 1 if symmetries else 2
-    assert got["count"] * step == ref["count"]
-    assert np.array_equal(got["boards"].reshape(-1, 84), ref["boards"].reshape(-1, 84)[::step])
-    assert np.array_equal(got["pis"].view(np.uint32), ref["pis"][::step].view(np.uint32))
-    assert np.array_equal(got["zs"], ref["zs"][::step])
+    fg.check_tuples_against_twin(got, ref, step=1 if symmetries else 2)
 
 
 SELFPLAY_MODES = {
@@ -259,18 +222,8 @@ def test_selfplay_session_in_chunks(engine, async_mode):
         engine.set_option("eval_dedup", 2)
     engine.set_root_noise(eps, alpha)
     ref = tw.selfplay(n, sims, net_kind=tw.NET_HASH, salt=oracle_salt(10), seed=22, first_game_id=7, eps=eps, alpha=alpha)
-    engine.selfplay_begin(n, sims, 10, seed=22, first_game_id=7, concurrent=8)
-    try:
-        off = 0
-        for lo, k in ((0, 5), (5, 11), (16, 8)):
-            got = engine.selfplay_next(k)
-            cnt = 2 * int(ref["game_len"][lo:lo + k].sum())
-            part = {"count": cnt, "game_len": ref["game_len"][lo:lo + k], "moves": ref["moves"][lo:lo + k],
-                    "boards": ref["boards"][off:off + cnt], "pis": ref["pis"][off:off + cnt], "zs": ref["zs"][off:off + cnt]}
-            _check_selfplay(got, part)
-            off += cnt
-    finally:
-        engine.selfplay_end()
+    fg.check_session_in_chunks(engine, ref, ((0, 5), (5, 11), (16, 8)),
+                               dict(n_games=n, num_sims=sims, model_id=10, seed=22, first_game_id=7, concurrent=8))
 
 
 # ---- 10. conv-net replay parity ---------------------------------------------------------------------------------------------------------------------
@@ -290,11 +243,7 @@ def test_conv_net_replay_parity(engine_mod, fp8):
             e.reset_stats()
             got = e.selfplay(n_games=n, num_sims=sims, model_id=0, seed=9, record_evals=cap)
             cnt, states, pis, vs = e.selfplay_get_evals(n, cap)
-            off = np.zeros(n + 1, np.int64)
-            off[1:] = np.cumsum(cnt)
-            fs = np.concatenate([states[g, :cnt[g]] for g in range(n)])
-            fp = np.concatenate([pis[g, :cnt[g]] for g in range(n)])
-            fv = np.concatenate([vs[g, :cnt[g]] for g in range(n)])
+            off, fs, fp, fv = fg.flatten_eval_log(cnt, states, pis, vs)
             ref = tw.selfplay(n, sims, net_kind=tw.NET_REPLAY, seed=9, replay=(off, fs, fp, fv), eps=eps, alpha=alpha)
             assert not ref["replay_bad"].any()
             _check_selfplay(got, ref)
@@ -322,7 +271,7 @@ def test_shared_slots_equal_one_game_trees(engine):
         for move in range(moves):
             pi, counts, q = tb.get_action_prob(np.array([s], np.uint64), 1.0 if move < 3 else 0.0, seed=seed, first_game_id=gid)
             seq.append((pi[0].copy(), counts[0].copy(), q[0].copy()))
-            s = engine_mod_c4_play(s[0], s[1], int(np.argmax(counts[0])))
+            s = c4_play(s[0], s[1], int(np.argmax(counts[0])))
         tb.close()
         want.append(seq)
     assert not np.array_equal(want[0][0][1], want[1][0][1]) or not np.array_equal(want[0][0][2], want[1][0][2])   # streams differ
@@ -339,7 +288,7 @@ def test_shared_slots_equal_one_game_trees(engine):
             for move in range(moves):
                 pi, counts, q = shared.slot_get_action_prob(slot, s, 1.0 if move < 3 else 0.0, seed=seed, game_id=gid)
                 seq.append((pi, counts, q))
-                s = engine_mod_c4_play(s[0], s[1], int(np.argmax(counts)))
+                s = c4_play(s[0], s[1], int(np.argmax(counts)))
             got[i] = seq
             shared.slot_release(slot)
         except Exception as ex:      # noqa: BLE001
@@ -362,49 +311,18 @@ def test_shared_slots_equal_one_game_trees(engine):
 # ---- 12. the arena never sees it ------------------------------------------------------------------------------------------------------------------------
 def test_arena_is_noise_free(engine):
     engine.set_root_noise(0.0, 1.0)
-    w0, r0 = engine.arena(16, 25, new_model_id=11, old_model_id=10, seed=4)
-    m0 = engine.arena_get_moves(16)
+    want = fg.arena_outputs(engine)
     engine.set_root_noise(1.0, 0.3)
     engine.selfplay(n_games=8, num_sims=25, model_id=10, seed=1)          # leaves a noisy arena behind in the pool
-    w1, r1 = engine.arena(16, 25, new_model_id=11, old_model_id=10, seed=4)
-    m1 = engine.arena_get_moves(16)
-    assert np.array_equal(w0, w1) and np.array_equal(r0, r1)
-    assert np.array_equal(m0[0], m1[0]) and np.array_equal(m0[1], m1[1])
+    fg.assert_same_outputs(fg.arena_outputs(engine), want)
 
 
 # ---- 13. the two Coaches ----------------------------------------------------------------------------------------------------------------------------------
 def test_python_and_cpp_coach_agree_with_root_noise(engine_mod, tmp_path):
     """tests/test_coach_gpu.py::test_python_and_cpp_coach_agree with Coach.root_noise_eps / root_noise_alpha set on both hosts:
     byte-identical files, and different ones from the noise-free run's."""
-    from alphazero_rs_amd.coach import Coach
-    C, seed = 128, 11
-    dirs = {k: os.path.join(tmp_path, k) for k in ("py", "cpp", "plain")}
-
-    def run_py(d, eps):
-        e = engine_mod.Engine(device=0, max_batch=256, net_channels=C)
-        try:
-            e.net_init_random(0, 3)
-            e.set_option("train_epochs", 1)
-            coach = Coach.setup(e, d, 1000000, 0.55, 15, 3, 100000, 1, 64, 8, 1, 32, 25, 1, 1000, 1, log=lambda m: None)
+    def noise(eps):
+        def configure(coach, e):
             coach.root_noise_eps, coach.root_noise_alpha = eps, 0.3
-            return coach.learn(seed=seed)
-        finally:
-            e.close()
-    rep = run_py(dirs["py"], 0.25)
-    run_py(dirs["plain"], 0.0)
-    exe = os.path.join(tmp_path, "test_coach_options")
-    libdir = os.path.dirname(engine_mod.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_coach_options.cpp"),
-                           "-o", exe, "-L", libdir, "-laz_engine", f"-Wl,-rpath,{libdir}"])
-    out = subprocess.run([exe, dirs["cpp"], str(C), str(seed), "root_noise_eps=0.25", "root_noise_alpha=0.3"], check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout
-    crep = json.loads([l for l in out.strip().splitlines() if l.startswith("[")][-1])
-    assert len(rep) == len(crep) == 1
-    for k in ("iteration", "samples", "nwins", "pwins", "draws", "accepted", "model_id"):
-        assert rep[0][k] == crep[0][k], k
-    files = sorted(os.listdir(dirs["py"]))
-    assert files == sorted(os.listdir(dirs["cpp"])) and "0.examples" in files and "1.aznet" in files
-    for f in files:
-        with open(os.path.join(dirs["py"], f), "rb") as x, open(os.path.join(dirs["cpp"], f), "rb") as y:
-            assert x.read() == y.read(), f
-    with open(os.path.join(dirs["py"], "0.examples"), "rb") as x, open(os.path.join(dirs["plain"], "0.examples"), "rb") as y:
-        assert x.read() != y.read()
+        return configure
+    fg.run_coach_pair(engine_mod, tmp_path, ["root_noise_eps=0.25", "root_noise_alpha=0.3"], noise(0.25), plain=noise(0.0))
