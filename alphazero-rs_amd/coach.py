@@ -2,7 +2,7 @@
 
 Mirrors src/coach.rs: `Coach.setup` takes the reference's 15 parameters (src/coach.rs:38-54) with the same
 meaning, `learn` runs the iteration loop of src/coach.rs:169-396: self-play episodes -> replay window
-(max_queue_length / max_history_length) -> save examples -> shuffle -> NNet::train -> arena of new vs old ->
+(max_queue_length / max_history_length) -> save examples -> [merge duplicate positions, opt-in] -> shuffle -> NNet::train -> arena of new vs old ->
 accept iff nwins + pwins > 0 and nwins / (nwins + pwins) >= update_threshold (:383-390).  Self-play and the arena
 are ONE engine call each (az_selfplay / az_arena); episodes shard across ranks by global game id when a process
 group is active and the tuples are gathered once per iteration (alphazero-rs_amd/dist.py).
@@ -71,6 +71,14 @@ class Coach:
         # "eval_mirror" (Engine.set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
         # run under the mirror-canonical function F, so the gate compares like with like.  False (the default): the engine is never asked
         self.eval_mirror = False
+        # Position averaging (Engine.merge_samples): every iteration's concatenated window is merged to one tuple per distinct position --
+        # mean pi, mean z -- before the shuffle, so the shuffle and NNet::train see the merged set; `history` and the <iter>.examples files
+        # stay raw (resume is unaffected, a later iteration may merge differently).  merge_canonical also merges a position with its
+        # mirror image: the window already holds both orientations (symmetries are expanded before it is merged) and nothing expands
+        # them again, so the net then trains on the CANONICAL orientation of every position only -- half the set, and no mirrored board
+        # unless it is the canonical one; meant to go with eval_mirror, which evaluates on that orientation.  False (the default): the
+        # engine is never asked
+        self.merge_positions, self.merge_canonical = False, False
         self.history = collections.deque()
         self.start_iteration = 0
         os.makedirs(self.dir, exist_ok=True)
@@ -202,6 +210,13 @@ class Coach:
             allp = np.concatenate([h[1] for h in self.history])
             allv = np.concatenate([h[2] for h in self.history])
             assert allv.shape[0] > 0                                    # :305
+            samples_raw = int(allv.shape[0])
+            t_merge = None
+            if self.merge_positions:                                    # one tuple per distinct position of the window
+                t0 = time.perf_counter()
+                merged = self.engine.merge_samples(allp, allv, boards=allb, canonical=self.merge_canonical, want_boards=True)
+                allb, allp, allv = merged["boards"], merged["pis"], merged["zs"]
+                t_merge = time.perf_counter() - t0
             perm = shuffle_permutation(allv.shape[0], seed, iteration)  # :296-297 shuffle
             allb, allp, allv = allb[perm], allp[perm], allv[perm]
             t0 = time.perf_counter()
@@ -249,9 +264,11 @@ class Coach:
             self.log(f"NEW/PREV WINS : {nwins} / {pwins}; DRAWS : {draws}")            # :381
             accepted = not (pwins + nwins == 0 or nwins / (pwins + nwins) < self.update_threshold)   # :383-390
             self.log("ACCEPTING NEW MODEL" if accepted else "REJECTING NEW MODEL")
-            report.append({"iteration": iteration, "samples": int(allv.shape[0]), "nwins": nwins, "pwins": pwins,
+            report.append({"iteration": iteration, "samples": int(allv.shape[0]), "samples_raw": samples_raw, "nwins": nwins, "pwins": pwins,
                            "draws": draws, "accepted": accepted, "losses": losses, "model_id": model_id,
                            "seconds": {"selfplay": t_play, "train": t_train, "arena": t_arena}})
+            if t_merge is not None:
+                report[-1]["seconds"]["merge"] = t_merge
             # a long run moves to a new model id per accepted iteration: drop the slot nobody will read again
             if free is not None:
                 free(model_id if accepted else model_id + 1)

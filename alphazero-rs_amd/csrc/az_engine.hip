@@ -22,6 +22,7 @@
 
 #include "az_combine.h"
 #include "az_local_comm.h"
+#include "az_merge.h"
 #include "az_net.h"
 #include "az_train.h"
 #include "az_tree.h"
@@ -424,8 +425,16 @@ struct az_engine {
             cap = want;
             return p;
         }
+        void release(hipStream_t s) {
+            if (!p) return;
+            HIPCHK(hipStreamSynchronize(s));
+            (void)hipFree(p);
+            p = nullptr; cap = 0;
+        }
         ~Scratch() { if (p) (void)hipFree(p); }
     } comm_scratch;
+    Scratch merge_scratch;          // workspace of az_samples_merge: sized by the call, kept for later calls of the same or a smaller size, given back
+                                    // when a call needs under a quarter of a workspace of more than 256 MiB (a 2^24-tuple call holds over 10 GB)
 };
 
 struct az_tree {
@@ -2419,6 +2428,105 @@ az_status az_arena_get_evals(az_engine* e, int32_t which, int32_t* rec_count, ui
     if (pis) std::memcpy(pis, l.pi.data(), l.pi.size() * 4);
     if (vs) std::memcpy(vs, l.v.data(), l.v.size() * 4);
     return AZ_OK;
+}
+
+// ---- position averaging: one tuple per distinct position (csrc/az_merge.h) ---------------------------------------
+az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, az_samples* dst, uint32_t* counts) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!src || !dst) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: src and dst are required");
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a self-play session is open");
+    if (flags & ~AZ_MERGE_CANONICAL) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: unknown flag bits");
+    const long long n = src->count;
+    if (n < 0 || n > MERGE_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: 0 .. 2^24 tuples");
+    if (!dst->pis || !dst->zs) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: dst needs pis and zs");
+    if (dst->capacity < n) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: dst->capacity is below src->count");
+    if (n > 0 && (!src->pis || !src->zs || (!src->states && !src->boards)))
+        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: src needs pis, zs and states or boards");
+    {   // no dst array may overlap a src array: the inputs are read after the first outputs could have been written
+        const size_t N = (size_t)n, C = (size_t)dst->capacity;
+        const std::pair<const void*, size_t> in[4] = {{src->states, N * 16}, {src->boards, N * AZ_FEATURES * 4}, {src->pis, N * AZ_ACTIONS * 4}, {src->zs, N * 4}};
+        const std::pair<const void*, size_t> out[5] = {{dst->states, C * 16}, {dst->boards, C * AZ_FEATURES * 4}, {dst->pis, C * AZ_ACTIONS * 4}, {dst->zs, C * 4}, {counts, C * 4}};
+        for (const auto& a : in)
+            for (const auto& b : out) {
+                if (!a.first || !b.first || !a.second || !b.second) continue;
+                const uintptr_t a0 = (uintptr_t)a.first, b0 = (uintptr_t)b.first;
+                if (a0 < b0 + b.second && b0 < a0 + a.second) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a dst array overlaps a src array");
+            }
+    }
+    if (n == 0) { dst->count = 0; return AZ_OK; }
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t N = (size_t)n;
+        const bool from_boards = !src->states;
+        const uint32_t T = std::max<uint32_t>(next_pow2_u32(2 * (uint64_t)N), 64u);
+        const size_t nb = (N + 255) / 256;
+        // one allocation, carved: [hdr] [inputs] [per tuple] [table] [per group] [outputs]
+        size_t total = 0;
+        auto need = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
+        const size_t o_hdr = need(256), o_in_st = need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_in_pi = need(N * 28), o_in_z = need(N * 4),
+                     o_cst = need(N * 16), o_slot = need(N * 4), o_tkey = need((size_t)T * 8), o_tmin = need((size_t)T * 4),
+                     o_trank = need((size_t)T * 4), o_bsum = need(nb * 4), o_first = need(N * 4), o_sums = need(N * 64), o_cnt = need(N * 4),
+                     o_out_st = need(N * 16), o_out_pi = need(N * 28), o_out_z = need(N * 4), o_out_b = need(dst->boards ? N * AZ_FEATURES * 4 : 0);
+        if (e->merge_scratch.cap > ((size_t)1 << 28) && e->merge_scratch.cap / 4 > total) e->merge_scratch.release(s);      // one huge call does not pin its gigabytes
+        char* base = (char*)e->merge_scratch.ensure(total, s);
+        MergeBufs b{};
+        b.n = (uint32_t)N;
+        b.in_states = from_boards ? nullptr : (const ulonglong2*)(base + o_in_st);
+        b.in_boards = from_boards ? (const float*)(base + o_in_st) : nullptr;
+        b.in_pis = (const float*)(base + o_in_pi);
+        b.in_zs = (const float*)(base + o_in_z);
+        b.cst = (ulonglong2*)(base + o_cst);
+        b.slot = (uint32_t*)(base + o_slot);
+        b.tkey = (unsigned long long*)(base + o_tkey);
+        b.tmin = (uint32_t*)(base + o_tmin);
+        b.trank = (uint32_t*)(base + o_trank);
+        b.tmask = T - 1u;
+        b.bsum = (uint32_t*)(base + o_bsum);
+        b.first = (uint32_t*)(base + o_first);
+        b.sums = (unsigned long long*)(base + o_sums);
+        b.cnt = (uint32_t*)(base + o_cnt);
+        b.hdr = (uint32_t*)(base + o_hdr);
+        b.o_states = (ulonglong2*)(base + o_out_st);
+        b.o_boards = dst->boards ? (float*)(base + o_out_b) : nullptr;
+        b.o_pis = (float*)(base + o_out_pi);
+        b.o_zs = (float*)(base + o_out_z);
+        if (from_boards) HIPCHK(hipMemcpyAsync(base + o_in_st, src->boards, N * AZ_FEATURES * 4, hipMemcpyDefault, s));
+        else HIPCHK(hipMemcpyAsync(base + o_in_st, src->states, N * 16, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_in_pi, src->pis, N * 28, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_in_z, src->zs, N * 4, hipMemcpyDefault, s));
+        HIPCHK(hipMemsetAsync(b.hdr, 0, 256, s));
+        HIPCHK(hipMemsetAsync(b.tkey, 0, (size_t)T * 8, s));
+        HIPCHK(hipMemsetAsync(b.tmin, 0xFF, (size_t)T * 4, s));
+        // 1. keys: every refusal that depends on the data is found here, before anything is written for the caller
+        launch_merge_keys(e->cfg.game, b, (flags & AZ_MERGE_CANONICAL) ? 1 : 0, s);
+        uint32_t hdr[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(hdr, b.hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (hdr[0] & MERGE_BAD_FEATURE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a boards feature that is not 0 or 1, or a cell set in both planes");
+        if (hdr[0] & MERGE_BAD_STATE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a state with overlapping stones or bits outside the 7x6 board");
+        if (hdr[0] & MERGE_BAD_VALUE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a pi or z that is NaN or outside [-1, 1]");
+        // 2. output ranks in order of first occurrence; m groups
+        launch_merge_scan(b, s);
+        HIPCHK(hipMemcpyAsync(hdr, b.hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const size_t m = hdr[1];
+        if (m == 0 || m > N) return fail(e, AZ_ERR_HIP, "az_samples_merge: the scan returned an impossible group count");
+        // 3. integer sums per group, 4. means or verbatim copies
+        HIPCHK(hipMemsetAsync(b.sums, 0, m * 64, s));
+        HIPCHK(hipMemsetAsync(b.cnt, 0, m * 4, s));
+        launch_merge_accumulate(b, s);
+        launch_merge_finalise(e->cfg.game, b, (uint32_t)m, s);
+        if (dst->states) HIPCHK(hipMemcpyAsync(dst->states, b.o_states, m * 16, hipMemcpyDefault, s));
+        if (dst->boards) HIPCHK(hipMemcpyAsync(dst->boards, b.o_boards, m * AZ_FEATURES * 4, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(dst->pis, b.o_pis, m * 28, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(dst->zs, b.o_zs, m * 4, hipMemcpyDefault, s));
+        if (counts) HIPCHK(hipMemcpyAsync(counts, b.cnt, m * 4, hipMemcpyDefault, s));
+        HIPCHK(hipStreamSynchronize(s));
+        dst->count = (int64_t)m;
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
 }
 
 // ---- the collective of the sharded Coach loop ---------------------------------------------------------------------------------

@@ -32,6 +32,7 @@ STATUS_NAMES = {
 NET_STUB, NET_HASH, NET_CONV = 0, 1, 2
 GAME_CONNECT_FOUR, GAME_CONNECT_THREE = 0, 1
 NET_CLASS_ENGINE, NET_CLASS_BF16, NET_CLASS_FP8 = -1, 0, 1      # az_net_class
+MERGE_CANONICAL = 1                                              # AZ_MERGE_CANONICAL, flags bit 0 of az_samples_merge
 
 
 class AzError(RuntimeError):
@@ -86,7 +87,7 @@ EXPORTS = [
     "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
-    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
+    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
     "az_arena_set_opening_book", "az_arena_get_openings",
     "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
@@ -144,6 +145,7 @@ def load_library(path=LIB_PATH):
         "az_selfplay_end": (i32, [vp]),
         "az_selfplay_get_evals": (i32, [vp, vp, vp, vp, vp]),
         "az_selfplay_get_full_plies": (i32, [vp, vp]),
+        "az_samples_merge": (i32, [vp, C.POINTER(az_samples), i32, C.POINTER(az_samples), vp]),
         "az_arena": (i32, [vp, C.POINTER(az_arena_params), vp, vp]),
         "az_arena_get_evals": (i32, [vp, i32, vp, vp, vp, vp]),
         "az_arena_get_moves": (i32, [vp, vp, vp]),
@@ -473,6 +475,35 @@ class Engine:
         vs = np.zeros((n_games, cap), np.float32)
         self._check(self._lib.az_selfplay_get_evals(self._h, _ptr(cnt), _ptr(states), _ptr(pis), _ptr(vs)))
         return cnt, states, pis, vs
+
+    # ---- position averaging ----
+    def merge_samples(self, pis, zs, *, states=None, boards=None, canonical=False, want_boards=False):
+        """az_samples_merge: one tuple per distinct position of n tuples, carrying the mean pi and the mean z of its copies, in order
+        of first occurrence (include/az_engine.h).  The position comes from `states` [n,2], or from `boards` [n,2,6,7] when states is
+        None; canonical merges a position with its left-right mirror image.  Inputs may be numpy arrays or torch tensors (host or
+        device).  Returns dict(count, states, pis, zs, counts) as numpy arrays, plus boards with want_boards."""
+        if (states is None) == (boards is None):
+            raise ValueError("merge_samples takes states or boards, not both")
+        n = int(len(zs))
+        if not hasattr(pis, "data_ptr"):
+            pis = np.ascontiguousarray(pis, dtype=np.float32).reshape(n, ACTIONS)
+        if not hasattr(zs, "data_ptr"):
+            zs = np.ascontiguousarray(zs, dtype=np.float32).reshape(n)
+        if states is not None and not hasattr(states, "data_ptr"):
+            states = np.ascontiguousarray(states, dtype=np.uint64).reshape(n, 2)
+        if boards is not None and not hasattr(boards, "data_ptr"):
+            boards = np.ascontiguousarray(boards, dtype=np.float32).reshape(n, 2, 6, 7)
+        out = {"states": np.zeros((n, 2), np.uint64), "pis": np.zeros((n, ACTIONS), np.float32), "zs": np.zeros(n, np.float32),
+               "counts": np.zeros(n, np.uint32)}
+        if want_boards:
+            out["boards"] = np.zeros((n, 2, 6, 7), np.float32)
+        src = az_samples(n, n, _as_ptr(states), _as_ptr(boards), _as_ptr(pis), _as_ptr(zs), None, None)
+        dst = az_samples(n, 0, _ptr(out["states"]), _ptr(out.get("boards")), _ptr(out["pis"]), _ptr(out["zs"]), None, None)
+        self._check(self._lib.az_samples_merge(self._h, C.byref(src), MERGE_CANONICAL if canonical else 0, C.byref(dst), _ptr(out["counts"])))
+        m = int(dst.count)
+        res = {k: v[:m] for k, v in out.items()}
+        res["count"] = m
+        return res
 
     # ---- arena::play_games ----
     def arena(self, num_games, num_sims, new_model_id, old_model_id, seed=0, max_depth=1000, cpuct=1,

@@ -550,6 +550,46 @@ az_status az_selfplay_get_full_plies(az_engine* e, uint64_t* mask /* [n_games] *
 /* Eval log of the last az_selfplay with record_evals > 0: rec_count [n_games], states [n_games,cap,2], ... */
 az_status az_selfplay_get_evals(az_engine* e, int32_t* rec_count, uint64_t* states, float* pis, float* vs);
 
+/* ---- position averaging: one training tuple per distinct position (no reference counterpart: src/coach.rs:296-329 trains on every
+ * copy; credited to the "Lessons from AlphaZero: Connect Four" write-ups).  Strictly opt-in: a host that never calls it runs
+ * nothing of it.  A window of self-play tuples holds the empty board once per episode and the first openings thousands of times, each
+ * copy with its own noisy pi and its own game's z; az_samples_merge returns one tuple per distinct position, carrying the MEAN pi and the
+ * MEAN z of its copies, and NNet::train's cost shrinks with the set.  A pure function of its arguments, deterministic to the bit on every
+ * host, rank and schedule (csrc/az_merge.h).  The contract:
+ *   in         src->count tuples n (0 .. 2^24), host or device memory: the position from src->states [n,2]; when states is NULL, from
+ *              src->boards [n,2,6,7], converted on the device.  src->pis and src->zs are required; capacity, game_len and moves are
+ *              ignored
+ *   out        dst->count = m, the distinct positions; per position dst->states, dst->boards, dst->pis, dst->zs (states and boards may
+ *              be NULL, pis and zs are required); counts [m] the multiplicities (may be NULL; they sum to n).  dst->capacity >= n is
+ *              required (m <= n always fits); no dst array (nor counts) may overlap a src array
+ *   key        Game::pack(s) of the engine's game, the 64-bit identity of a state (never 0).  With AZ_MERGE_CANONICAL in flags the key
+ *              is pack(c(s)), c the canonicalisation of "eval_mirror" (csrc/az_mirror.h): a position and its left-right mirror image
+ *              merge, a tuple whose state is the mirrored one contributes pi reversed (mirror_action), and the output state is c(s).
+ *              A host that expands symmetries afterwards gets both orientations back.  pack is an identity for REACHABLE states (stones
+ *              stacked from the bottom of their columns); the validation below accepts any two disjoint in-board bitboards, and two
+ *              such patterns with floating stones can share a key -- they are then merged under the first one's state
+ *   order      output group j is the j-th distinct key in order of FIRST OCCURRENCE in the input (ascending lowest input index): the
+ *              result does not depend on any hash layout or schedule
+ *   k = 1      a group of one copies its tuple bit for bit (under AZ_MERGE_CANONICAL canonicalised, which is exact): a set without
+ *              duplicates comes back unchanged
+ *   k > 1      each of the eight values (pi[0..6], z) is accumulated as an integer, q(x) = llrint((double)x * 2^38) -- the product is
+ *              exact, llrint rounds to nearest even -- summed in int64: S.  The mean is (float)((double)S / (double)(k * 2^38)): C's
+ *              int64 -> double conversion, a divisor that is exact in double, one IEEE double division, one rounding to f32.  pi is NOT
+ *              renormalised.  Integer addition is associative, so S does not depend on the order in which atomics, wave-level sums or
+ *              the per-workgroup LDS tables deliver the addends; z is not always +-1 (a draw is DRAW_EPS), hence a fixed-point grid and
+ *              not a win/loss counter.  Absolute quantisation error 2^-39 per value; n <= 2^24 keeps every sum below 2^62
+ *   refused    AZ_ERR_BAD_ARGUMENT with nothing written (the data checks run on the device in the first pass): a pi or z outside
+ *              [-1, 1] or NaN; a state with overlapping stones or bits outside the 7x6 board; a boards feature that is not exactly 0 or
+ *              1, or a cell set in both planes; n > 2^24; dst->capacity < n; a dst array overlapping a src array; unknown flag bits; a
+ *              call while a self-play session is open.  n = 0 is legal and gives m = 0
+ *   purity     models, trees, the evaluation cache, options and every az_stats counter but device_ms are untouched.  Runs on the
+ *              engine's stream in a workspace the engine owns: sized by the call (about 200 bytes per tuple, 340 more per tuple for each
+ *              of boards in and boards out: over 10 GB at 2^24 tuples by the boards route), reused by later calls of the same or a
+ *              smaller size, and given back when a call needs under a quarter of a workspace of more than 256 MiB
+ * Whether averaged targets change playing strength is unmeasured. */
+#define AZ_MERGE_CANONICAL 1   /* flags bit 0 */
+az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, az_samples* dst, uint32_t* counts);
+
 /* ---- arena::play_games, src/arena.rs:62-99 + gate, src/coach.rs:377-390 ---- */
 typedef struct az_arena_params {
     int32_t num_games;      /* num/2 per seating, src/arena.rs:83 */

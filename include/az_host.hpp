@@ -27,6 +27,10 @@
 #include <vector>
 
 #include "az_engine.h"
+// Bound weakly, for one reason: the CPU tests link this header against recording doubles of the ABI that define only the entries a
+// Coach used before position averaging (tests/cpp/test_root_noise_host_cpu.cpp and its like), and Coach::learn names az_samples_merge.
+// With a real engine library the symbol resolves as any other; without it Coach::merge_positions panics instead of calling through null.
+#pragma weak az_samples_merge
 
 namespace az_host {
 
@@ -345,7 +349,7 @@ inline std::vector<TrainingSample> execute_episode(const AsyncMcts& mcts, size_t
 }
 
 // ---- Coach (src/coach.rs:17-396) ----------------------------------------------------------------------------------
-// The iteration loop around the engine: self-play episodes -> replay window -> <iter>.examples -> shuffle ->
+// The iteration loop around the engine: self-play episodes -> replay window -> <iter>.examples -> [merge duplicate positions, opt-in] -> shuffle ->
 // NNet::train(samples, model_id, model_id + 1) -> arena of new vs old -> accept iff nwins + pwins > 0 and
 // nwins / (nwins + pwins) >= update_threshold.  Self-play, training and the arena are ONE engine call each.
 // The Python host (alphazero-rs_amd/coach.py) runs the same sequence with the same seeds and writes the same files.
@@ -381,7 +385,8 @@ struct ScopedOption {
 
 class Coach {
   public:
-    struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; };
+    // samples = the tuples trained on, samples_raw = the tuples of the window before position averaging (equal with merge_positions off)
+    struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; size_t samples_raw; };
 
     // Coach::setup(checkpoint_directory, + the reference's 14 numeric parameters), src/coach.rs:38-103
     static Coach setup(Engine& e, const std::string& checkpoint_directory, size_t mcts_reserve_size, float update_threshold,
@@ -577,6 +582,18 @@ class Coach {
             std::vector<float> ab, ap, av;
             ab.reserve(n * 84); ap.reserve(n * 7); av.reserve(n);
             for (auto& h : history) { ab.insert(ab.end(), h.boards.begin(), h.boards.end()); ap.insert(ap.end(), h.pis.begin(), h.pis.end()); av.insert(av.end(), h.vs.begin(), h.vs.end()); }
+            const size_t n_raw = n;
+            if (merge_positions) {                                    // one tuple per distinct position of the window: mean pi, mean z
+                if (!az_samples_merge) throw Panic("merge_positions: the linked engine library has no az_samples_merge");
+                std::vector<float> mb(n * 84), mp(n * 7), mv(n);
+                az_samples src{}, dst{};
+                src.count = (int64_t)n; src.boards = ab.data(); src.pis = ap.data(); src.zs = av.data();
+                dst.capacity = (int64_t)n; dst.boards = mb.data(); dst.pis = mp.data(); dst.zs = mv.data();
+                e_.check(az_samples_merge(e_.raw(), &src, merge_canonical ? AZ_MERGE_CANONICAL : 0, &dst, nullptr));
+                n = (size_t)dst.count;
+                mb.resize(n * 84); mp.resize(n * 7); mv.resize(n);
+                ab.swap(mb); ap.swap(mp); av.swap(mv);
+            }
             const std::vector<int64_t> perm = shuffle_permutation(n, seed, iteration);   // :296-297
             std::vector<float> sb(n * 84), sp(n * 7), sv(n);
             for (size_t i = 0; i < n; ++i) {
@@ -589,7 +606,7 @@ class Coach {
             e_.check(az_net_train(e_.raw(), (int32_t)model_id, (int32_t)model_id + 1, sb.data(), sp.data(), sv.data(), (int64_t)n));   // :329
             if (rank_ == 0) e_.check(az_net_save(e_.raw(), (int32_t)model_id + 1, (dir_ + "/" + std::to_string(model_id + 1) + ".aznet").c_str()));
             Report r{};
-            r.iteration = iteration; r.samples = n; r.model_id = model_id;
+            r.iteration = iteration; r.samples = n; r.samples_raw = n_raw; r.model_id = model_id;
             r.losses.resize(2 * (size_t)az_net_train_history(e_.raw(), nullptr, 0));
             az_net_train_history(e_.raw(), r.losses.data(), (int32_t)(r.losses.size() / 2));
             // arena: new (first listed) vs old, both seatings (:333-375)
@@ -661,6 +678,12 @@ class Coach {
     // "eval_mirror" (Engine::set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
     // run under the mirror-canonical function, so the gate compares like with like.  false (the default): the engine is never asked
     bool eval_mirror = false;
+    // Position averaging (az_samples_merge): every iteration's concatenated window is merged to one tuple per distinct position before
+    // the shuffle, so the shuffle and NNet::train see the merged set; `history` and the <iter>.examples files stay raw.  merge_canonical
+    // also merges a position with its mirror image: the window already holds both orientations (symmetries are expanded before it is merged)
+    // and nothing expands them again, so the net then trains on the CANONICAL orientation of every position only -- half the set; meant to
+    // go with eval_mirror, which evaluates on that orientation.  false (the default): the engine is never asked
+    bool merge_positions = false, merge_canonical = false;
     float update_threshold = 0.f;
     int32_t cpuct = 1;
 

@@ -48,6 +48,9 @@ pub struct az_arena_params {
     pub use_start_board: i32, pub allreduce_wld: i32, pub start_board: [u64; 2],
 }
 
+/// flags bit 0 of az_samples_merge: a position and its left-right mirror image merge (the state kept is the canonical one)
+pub const AZ_MERGE_CANONICAL: i32 = 1;
+
 extern "C" {
     // ---- lifecycle
     pub fn az_create(cfg: *const az_config, out: *mut *mut az_engine) -> c_int;
@@ -108,6 +111,9 @@ extern "C" {
     /// ("playout_cap_sims" / "playout_cap_full_e6"; all plies when the playout cap is off)
     pub fn az_selfplay_get_full_plies(e: *mut az_engine, mask: *mut u64) -> c_int;
     pub fn az_selfplay_get_evals(e: *mut az_engine, rec_count: *mut i32, states: *mut u64, pis: *mut f32, vs: *mut f32) -> c_int;
+    /// position averaging: one tuple per distinct position of src (mean pi, mean z, first-occurrence order); flags bit 0 =
+    /// AZ_MERGE_CANONICAL merges a position with its mirror image; dst.capacity >= src.count; counts [m] may be null
+    pub fn az_samples_merge(e: *mut az_engine, src: *const az_samples, flags: i32, dst: *mut az_samples, counts: *mut u32) -> c_int;
     pub fn az_arena(e: *mut az_engine, p: *const az_arena_params, out_wld: *mut u64, results: *mut i8) -> c_int;
     pub fn az_arena_get_evals(e: *mut az_engine, which: i32, rec_count: *mut i32, states: *mut u64, pis: *mut f32, vs: *mut f32) -> c_int;
     pub fn az_arena_get_moves(e: *mut az_engine, game_len: *mut i32, moves: *mut u8) -> c_int;
