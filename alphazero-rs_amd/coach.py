@@ -79,6 +79,11 @@ class Coach:
         # unless it is the canonical one; meant to go with eval_mirror, which evaluates on that orientation.  False (the default): the
         # engine is never asked
         self.merge_positions, self.merge_canonical = False, False
+        # Move-quality report (Engine.move_quality): after every iteration's arena its games are replayed, every position with at least
+        # solve_min_stones stones is solved exactly (budget solve_max_nodes per position and action) and the move played there classed; the
+        # tally per model goes into the report ("quality") and one log line.  It decides nothing: the gate, the checkpoints, the .examples
+        # files and coach.state are those of a run without it.  0 (the default): the engine is never asked
+        self.solve_min_stones, self.solve_max_nodes = 0, 1 << 20
         self.history = collections.deque()
         self.start_iteration = 0
         os.makedirs(self.dir, exist_ok=True)
@@ -260,6 +265,27 @@ class Coach:
                                                seed=a_seed, max_depth=self.max_depth, cpuct=self.cpuct,
                                                reserve=self.mcts_reserve_size, num_sim_threads=self.num_sim_threads)
             t_arena = time.perf_counter() - t0
+            quality, t_quality = None, None
+            if self.solve_min_stones > 0:                               # the exact move-quality report of the arena just played
+                t0 = time.perf_counter()
+                counts = np.zeros((2, len(QUALITY_KEYS)), np.uint64)
+                if world > 1 and total > 0:
+                    first, local = lo, hi - lo
+                else:
+                    first, local = 0, total
+                if local > 0:
+                    game_len, moves = self.engine.arena_get_moves(local)
+                    boards = self.engine.arena_get_openings(local)[0]
+                    cls, _ = self.engine.move_quality(game_len, moves, start_boards=boards, max_nodes=self.solve_max_nodes,
+                                                      min_stones=self.solve_min_stones)
+                    counts = quality_tally(cls, first, total)
+                if world > 1 and total > 0:
+                    t = torch.tensor(counts.astype(np.int64).reshape(-1), dtype=torch.int64, device=dev)
+                    tdist.all_reduce(t, group=self.group)
+                    counts = t.cpu().numpy().reshape(2, -1)
+                quality = {who: {k: int(v) for k, v in zip(QUALITY_KEYS, row)} for who, row in zip(("new", "old"), counts)}
+                t_quality = time.perf_counter() - t0
+                self.log(f"MOVE QUALITY (from {self.solve_min_stones} stones): NEW {quality['new']}; PREV {quality['old']}")
             nwins, pwins, draws = int(wld[0]), int(wld[1]), int(wld[2])
             self.log(f"NEW/PREV WINS : {nwins} / {pwins}; DRAWS : {draws}")            # :381
             accepted = not (pwins + nwins == 0 or nwins / (pwins + nwins) < self.update_threshold)   # :383-390
@@ -269,6 +295,9 @@ class Coach:
                            "seconds": {"selfplay": t_play, "train": t_train, "arena": t_arena}})
             if t_merge is not None:
                 report[-1]["seconds"]["merge"] = t_merge
+            if quality is not None:
+                report[-1]["quality"] = quality
+                report[-1]["seconds"]["quality"] = t_quality
             # a long run moves to a new model id per accepted iteration: drop the slot nobody will read again
             if free is not None:
                 free(model_id if accepted else model_id + 1)
@@ -278,6 +307,28 @@ class Coach:
                 write_state(self.dir, iteration, model_id)
             self.model_id = model_id
         return report
+
+
+QUALITY_KEYS = ("examined", "kept", "win_to_draw", "win_to_loss", "draw_to_loss", "unknown")
+
+
+def quality_tally(ply_class, first_game, total_games):
+    """The move-quality tally of one arena shard: uint64 [2, 6], row 0 the new model's moves, row 1 the old model's, columns QUALITY_KEYS.
+    ply_class [n, 42] as Engine.move_quality returns it; game g of the shard has global index first_game + g.  The new model holds the
+    first seat in the games below total_games // 2 (az_arena), and the first seat moves at the even plies of the record -- a start
+    board, opening or not, always has the first seat to move (az_arena_get_openings)."""
+    ply_class = np.asarray(ply_class)
+    n = ply_class.shape[0]
+    new_first = (first_game + np.arange(n)) < total_games // 2
+    first_moves = np.arange(ply_class.shape[1]) % 2 == 0
+    is_new = new_first[:, None] == first_moves[None, :]
+    counts = np.zeros((2, len(QUALITY_KEYS)), np.uint64)
+    for row, sel in ((0, is_new), (1, ~is_new)):
+        k = ply_class[sel]
+        counts[row, 0] = int((k != 0).sum())
+        for c in range(1, len(QUALITY_KEYS)):
+            counts[row, c] = int((k == c).sum())
+    return counts
 
 
 def write_state(directory, iteration, model_id):

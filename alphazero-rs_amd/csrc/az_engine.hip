@@ -24,6 +24,7 @@
 #include "az_local_comm.h"
 #include "az_merge.h"
 #include "az_net.h"
+#include "az_solve.h"
 #include "az_train.h"
 #include "az_tree.h"
 
@@ -416,6 +417,7 @@ struct az_engine {
     struct Scratch {
         void* p = nullptr;
         size_t cap = 0;
+        uint64_t serial = 0;        // moves on with every allocation: content kept across calls belongs to ONE serial (an address can come back)
         void* ensure(size_t bytes, hipStream_t s) {
             if (bytes <= cap) return p;
             HIPCHK(hipStreamSynchronize(s));
@@ -423,6 +425,7 @@ struct az_engine {
             const size_t want = std::max<size_t>(bytes + bytes / 4, (size_t)1 << 16);
             HIPCHK(hipMalloc(&p, want));
             cap = want;
+            ++serial;
             return p;
         }
         void release(hipStream_t s) {
@@ -430,11 +433,22 @@ struct az_engine {
             HIPCHK(hipStreamSynchronize(s));
             (void)hipFree(p);
             p = nullptr; cap = 0;
+            ++serial;
         }
         ~Scratch() { if (p) (void)hipFree(p); }
     } comm_scratch;
     Scratch merge_scratch;          // workspace of az_samples_merge: sized by the call, kept for later calls of the same or a smaller size, given back
                                     // when a call needs under a quarter of a workspace of more than 256 MiB (a 2^24-tuple call holds over 10 GB)
+    // az_solve / az_move_quality: solve_table = [counter][generation per lane, room for the device's lanes][lanes << tt_log2 entries], solve_io =
+    // staged inputs and outputs.  Both follow merge_scratch's rule.  The table's content outlives a call (a lane's generation counter tells
+    // its entries from older ones).  The layout does NOT depend on a call's lane count: lane L's counter and slice sit at the same place in
+    // every call of one tt_log2, a call with fewer lanes uses a prefix.  The content belongs to one allocation (Scratch::serial) and one
+    // tt_log2, and is valid for the first solve_table_lanes lanes; anything else zeroes the whole workspace first
+    Scratch solve_table, solve_io;
+    uint64_t solve_table_serial = 0;
+    int solve_table_log2 = -1;
+    uint32_t solve_table_lanes = 0;
+    int solve_device_lanes = 0;     // CUs x resident waves x 64 of the search kernel, asked once
 };
 
 struct az_tree {
@@ -2525,6 +2539,166 @@ az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, a
         if (counts) HIPCHK(hipMemcpyAsync(counts, b.cnt, m * 4, hipMemcpyDefault, s));
         HIPCHK(hipStreamSynchronize(s));
         dst->count = (int64_t)m;
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// ---- exact endgame solver and move-quality report (csrc/az_solve.h) ------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+constexpr size_t SOLVE_TABLE_BUDGET = (size_t)4 << 30;       // bytes of table at most: the lanes are cut to fit (tt_log2 = 16: 8192 lanes)
+
+const char* solve_param_error(int32_t n, uint32_t max_nodes, int32_t min_stones, int32_t tt_log2, int32_t max_lanes) {
+    if (n < 0 || n > (1 << 24)) return "0 .. 2^24 positions";
+    if (max_nodes < 1u || max_nodes > (1u << 30)) return "max_nodes must be in 1 .. 2^30";
+    if (min_stones < 0 || min_stones > AZ_MAX_PLIES) return "min_stones must be in 0 .. 42";
+    if (tt_log2 != 0 && (tt_log2 < 8 || tt_log2 > 16)) return "tt_log2 must be 0 or 8 .. 16";
+    if (max_lanes < 0 || max_lanes % 64 != 0) return "max_lanes must be 0 or a multiple of 64";
+    return nullptr;
+}
+
+void solve_release_outsized(az_engine* e, az_engine::Scratch& sc, size_t need) {
+    if (sc.cap > ((size_t)1 << 28) && sc.cap / 4 > need) sc.release(e->stream);
+}
+
+// The search over b.n positions already on the device (states, active, mv, nodes, values set by the caller): sizes the grid, readies the
+// table, launches.
+void solve_on_device(az_engine* e, SolveBufs b, int32_t max_lanes) {
+    hipStream_t s = e->stream;
+    if (e->solve_device_lanes == 0) e->solve_device_lanes = solve_device_lanes(e->cfg.game);
+    if (e->solve_device_lanes <= 0) throw HipFail{hipErrorUnknown, "solve_device_lanes"};
+    const size_t items = (size_t)b.n * AZ_ACTIONS;
+    size_t lanes = (size_t)e->solve_device_lanes;
+    if (max_lanes > 0) lanes = std::min(lanes, (size_t)max_lanes);
+    lanes = std::min(lanes, (items + 63) / 64 * 64);
+    if (b.tt_log2) lanes = std::min(lanes, std::max<size_t>(64, (SOLVE_TABLE_BUDGET >> (b.tt_log2 + 3)) / 64 * 64));
+    // fixed places: the counters have room for every lane the device can hold, so a slice never moves with the call's lane count
+    const size_t off_gens = 256, off_tt = off_gens + ((size_t)e->solve_device_lanes * 4 + 255) / 256 * 256;
+    const size_t total = off_tt + (b.tt_log2 ? (lanes * 8) << b.tt_log2 : 0);
+    solve_release_outsized(e, e->solve_table, total);
+    char* base = (char*)e->solve_table.ensure(total, s);
+    if (e->solve_table.serial != e->solve_table_serial || (int)b.tt_log2 != e->solve_table_log2 || lanes > e->solve_table_lanes) {
+        HIPCHK(hipMemsetAsync(base, 0, total, s));         // a new allocation, another slice size, or lanes that have no counter yet
+        e->solve_table_serial = e->solve_table.serial;
+        e->solve_table_log2 = (int)b.tt_log2;
+        e->solve_table_lanes = (uint32_t)lanes;
+    } else {
+        HIPCHK(hipMemsetAsync(base, 0, 256, s));          // the item counter
+    }
+    b.counter = (uint32_t*)base;
+    b.gens = (uint32_t*)(base + off_gens);
+    b.tt = (unsigned long long*)(base + off_tt);
+    launch_solve(e->cfg.game, b, (uint32_t)lanes, s);
+    HIPCHK(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+az_status az_solve(az_engine* e, const uint64_t* states, int32_t n, uint32_t max_nodes, int32_t min_stones, int32_t tt_log2, int32_t max_lanes,
+                   int8_t* move_values, int8_t* values, uint32_t* nodes) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!states || !move_values) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_solve: states and move_values are required");
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_solve: a self-play session is open");
+    if (const char* why = solve_param_error(n, max_nodes, min_stones, tt_log2, max_lanes)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_solve: ") + why).c_str());
+    if (n == 0) return AZ_OK;
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t N = (size_t)n;
+        size_t total = 0;
+        auto need = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
+        const size_t o_hdr = need(256), o_st = need(N * 16), o_mv = need(N * 7), o_val = need(N), o_nodes = need(N * 28);
+        solve_release_outsized(e, e->solve_io, total);
+        char* base = (char*)e->solve_io.ensure(total, s);
+        HIPCHK(hipMemcpyAsync(base + o_st, states, N * 16, hipMemcpyDefault, s));
+        HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
+        launch_solve_validate((const ulonglong2*)(base + o_st), (uint32_t)N, (uint32_t*)(base + o_hdr), s);
+        HIPCHK(hipGetLastError());
+        uint32_t verdict = 0;
+        HIPCHK(hipMemcpyAsync(&verdict, base + o_hdr, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (verdict) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_solve: a state with overlapping stones, bits outside the 7x6 board or floating stones");
+        SolveBufs b{};
+        b.states = (const ulonglong2*)(base + o_st);
+        b.n = (uint32_t)N;
+        b.max_nodes = max_nodes;
+        b.min_stones = min_stones;
+        b.tt_log2 = (uint32_t)tt_log2;
+        b.mv = (int8_t*)(base + o_mv);
+        b.values = (int8_t*)(base + o_val);
+        b.nodes = (uint32_t*)(base + o_nodes);
+        solve_on_device(e, b, max_lanes);
+        HIPCHK(hipMemcpyAsync(move_values, b.mv, N * 7, hipMemcpyDefault, s));
+        if (values) HIPCHK(hipMemcpyAsync(values, b.values, N, hipMemcpyDefault, s));
+        if (nodes) HIPCHK(hipMemcpyAsync(nodes, b.nodes, N * 28, hipMemcpyDefault, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+az_status az_move_quality(az_engine* e, const uint64_t* start_boards, const int32_t* game_len, const uint8_t* moves, int32_t n, uint32_t max_nodes,
+                          int32_t min_stones, int32_t tt_log2, int32_t max_lanes, uint8_t* ply_class, int8_t* ply_value) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!game_len || !moves || !ply_class) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_move_quality: game_len, moves and ply_class are required");
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_move_quality: a self-play session is open");
+    if (n > (1 << 24) / AZ_MAX_PLIES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_move_quality: at most 2^24 / 42 games");
+    if (const char* why = solve_param_error(n, max_nodes, min_stones, tt_log2, max_lanes)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_move_quality: ") + why).c_str());
+    if (n == 0) return AZ_OK;
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t N = (size_t)n, P = N * AZ_MAX_PLIES;
+        size_t total = 0;
+        auto need = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
+        const size_t o_hdr = need(256), o_start = need(N * 16), o_len = need(N * 4), o_moves = need(P), o_st = need(P * 16), o_act = need(P),
+                     o_mv = need(P * 7), o_val = need(P), o_nodes = need(P * 28), o_cls = need(P), o_pv = need(P);
+        solve_release_outsized(e, e->solve_io, total);
+        char* base = (char*)e->solve_io.ensure(total, s);
+        if (start_boards) HIPCHK(hipMemcpyAsync(base + o_start, start_boards, N * 16, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_len, game_len, N * 4, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_moves, moves, P, hipMemcpyDefault, s));
+        HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
+        MoveQualityBufs q{};
+        q.start = start_boards ? (const ulonglong2*)(base + o_start) : nullptr;
+        q.game_len = (const int32_t*)(base + o_len);
+        q.moves = (const uint8_t*)(base + o_moves);
+        q.n = (uint32_t)N;
+        q.min_stones = min_stones;
+        q.states = (ulonglong2*)(base + o_st);
+        q.active = (uint8_t*)(base + o_act);
+        q.verdict = (uint32_t*)(base + o_hdr);
+        q.mv = (const int8_t*)(base + o_mv);
+        q.ply_class = (uint8_t*)(base + o_cls);
+        q.ply_value = (int8_t*)(base + o_pv);
+        launch_move_quality_replay(e->cfg.game, q, s);
+        HIPCHK(hipGetLastError());
+        uint32_t verdict = 0;
+        HIPCHK(hipMemcpyAsync(&verdict, q.verdict, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (verdict & SOLVE_BAD_STATE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_move_quality: a start board with overlapping stones, bits outside the 7x6 board or floating stones");
+        if (verdict & SOLVE_BAD_RECORD) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_move_quality: an illegal move in a record, or a game_len beyond the end of its game");
+        SolveBufs b{};
+        b.states = q.states;
+        b.active = q.active;
+        b.n = (uint32_t)P;
+        b.max_nodes = max_nodes;
+        b.min_stones = min_stones;
+        b.tt_log2 = (uint32_t)tt_log2;
+        b.mv = (int8_t*)(base + o_mv);
+        b.values = (int8_t*)(base + o_val);
+        b.nodes = (uint32_t*)(base + o_nodes);
+        solve_on_device(e, b, max_lanes);
+        launch_move_quality_classify(e->cfg.game, q, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ply_class, q.ply_class, P, hipMemcpyDefault, s));
+        if (ply_value) HIPCHK(hipMemcpyAsync(ply_value, q.ply_value, P, hipMemcpyDefault, s));
+        HIPCHK(hipStreamSynchronize(s));
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
 }

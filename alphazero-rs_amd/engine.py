@@ -32,6 +32,9 @@ STATUS_NAMES = {
 NET_STUB, NET_HASH, NET_CONV = 0, 1, 2
 GAME_CONNECT_FOUR, GAME_CONNECT_THREE = 0, 1
 NET_CLASS_ENGINE, NET_CLASS_BF16, NET_CLASS_FP8 = -1, 0, 1      # az_net_class
+SOLVE_ILLEGAL, SOLVE_UNKNOWN = -128, 127                         # AZ_SOLVE_ILLEGAL / AZ_SOLVE_UNKNOWN
+MQ_SKIPPED, MQ_KEPT, MQ_WIN_TO_DRAW, MQ_WIN_TO_LOSS, MQ_DRAW_TO_LOSS, MQ_UNKNOWN = range(6)      # AZ_MQ_*: classes of az_move_quality
+MQ_NAMES = ("skipped", "kept", "win_to_draw", "win_to_loss", "draw_to_loss", "unknown")
 MERGE_CANONICAL = 1                                              # AZ_MERGE_CANONICAL, flags bit 0 of az_samples_merge
 
 
@@ -87,7 +90,7 @@ EXPORTS = [
     "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
-    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
+    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
     "az_arena_set_opening_book", "az_arena_get_openings",
     "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
@@ -146,6 +149,8 @@ def load_library(path=LIB_PATH):
         "az_selfplay_get_evals": (i32, [vp, vp, vp, vp, vp]),
         "az_selfplay_get_full_plies": (i32, [vp, vp]),
         "az_samples_merge": (i32, [vp, C.POINTER(az_samples), i32, C.POINTER(az_samples), vp]),
+        "az_solve": (i32, [vp, vp, i32, C.c_uint32, i32, i32, i32, vp, vp, vp]),
+        "az_move_quality": (i32, [vp, vp, vp, vp, i32, C.c_uint32, i32, i32, i32, vp, vp]),
         "az_arena": (i32, [vp, C.POINTER(az_arena_params), vp, vp]),
         "az_arena_get_evals": (i32, [vp, i32, vp, vp, vp, vp]),
         "az_arena_get_moves": (i32, [vp, vp, vp]),
@@ -504,6 +509,33 @@ class Engine:
         res = {k: v[:m] for k, v in out.items()}
         res["count"] = m
         return res
+
+    # ---- exact endgame solver ----
+    def solve(self, states, max_nodes=1 << 20, min_stones=0, tt_log2=12, max_lanes=0):
+        """az_solve: every root action of n canonical positions [n,2] (numpy or torch, host or device).  Returns (move_values [n,7] int8,
+        values [n] int8, nodes [n,7] uint32): the exact outcome for the side to move after the action (-1, 0, +1), SOLVE_ILLEGAL for an
+        action that is not legal, SOLVE_UNKNOWN where the search passed max_nodes or the position has fewer than min_stones stones
+        (include/az_engine.h)."""
+        if not hasattr(states, "data_ptr"):
+            states = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, 2)
+        n = int(len(states))
+        mv, values, nodes = np.zeros((n, ACTIONS), np.int8), np.zeros(n, np.int8), np.zeros((n, ACTIONS), np.uint32)
+        self._check(self._lib.az_solve(self._h, _as_ptr(states), n, max_nodes, min_stones, tt_log2, max_lanes, _ptr(mv), _ptr(values), _ptr(nodes)))
+        return mv, values, nodes
+
+    def move_quality(self, game_len, moves, start_boards=None, max_nodes=1 << 20, min_stones=0, tt_log2=12, max_lanes=0):
+        """az_move_quality: the recorded games (game_len [n], moves [n,42] as arena_get_moves and selfplay return them; start_boards [n,2]
+        as arena_get_openings returns them, None = the initial board) replayed and every move classed against the exact value of its
+        position.  Returns (ply_class [n,42] uint8 of MQ_*, ply_value [n,42] int8)."""
+        game_len = np.ascontiguousarray(game_len, dtype=np.int32).reshape(-1)
+        n = int(len(game_len))
+        moves = np.ascontiguousarray(moves, dtype=np.uint8).reshape(n, MAX_PLIES)
+        if start_boards is not None:
+            start_boards = np.ascontiguousarray(start_boards, dtype=np.uint64).reshape(n, 2)
+        cls, val = np.zeros((n, MAX_PLIES), np.uint8), np.zeros((n, MAX_PLIES), np.int8)
+        self._check(self._lib.az_move_quality(self._h, _ptr(start_boards), _ptr(game_len), _ptr(moves), n, max_nodes, min_stones, tt_log2, max_lanes,
+                                              _ptr(cls), _ptr(val)))
+        return cls, val
 
     # ---- arena::play_games ----
     def arena(self, num_games, num_sims, new_model_id, old_model_id, seed=0, max_depth=1000, cpuct=1,

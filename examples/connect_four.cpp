@@ -1,7 +1,7 @@
 // examples/connect_four.rs (src lines 45-80) on the C++ host: the same Coach::setup parameters, the engine behind it.
 // Build:  g++ -std=c++17 -O2 -I include examples/connect_four.cpp -o connect_four -L alphazero-rs_amd -laz_engine
 //         (and -Wl,-rpath,$PWD/alphazero-rs_amd)
-// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions]
+// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality]
 //         selfplay_fp8 = 1: the episodes are played in the fp8 class, the arena gate in bf16 (Coach::selfplay_class)
 //         root_noise_eps > 0 (e.g. 0.25, with root_noise_alpha 0.3; default alpha 1): Dirichlet root noise in the episodes (Coach::root_noise_eps)
 //         eval_mirror = 1: mirror-canonical leaf evaluation for the whole loop, episodes and gate (Coach::eval_mirror)
@@ -13,6 +13,8 @@
 //         N random quiet plies, every pair from others (Coach::arena_opening_plies)
 //         merge_positions = 1 or canonical: position averaging before training -- one tuple per distinct position of the window with the mean
 //         pi and the mean z of its copies; canonical also merges a position with its mirror image (Coach::merge_positions / merge_canonical)
+//         move_quality = STONES[,NODES] (e.g. 26): after every arena its games are replayed, the positions with at least STONES stones solved
+//         exactly (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach::solve_min_stones)
 #include <cstdio>
 #include <cstdlib>
 
@@ -37,6 +39,7 @@ int main(int argc, char** argv) {
     const bool prune = forced.find(",prune") != std::string::npos;
     const long arena_openings = argc > 12 ? std::strtol(argv[12], nullptr, 10) : 0;
     const std::string merge = argc > 13 ? argv[13] : "0";
+    const std::string quality = argc > 14 ? argv[14] : "0";
     try {
         Engine e(0, 8192, 512);
         if (az_net_load(e.raw(), 0, (dir + "/0.aznet").c_str()) != AZ_OK) e.check(az_net_init_random(e.raw(), 0, 0));
@@ -50,6 +53,8 @@ int main(int argc, char** argv) {
         coach.arena_opening_plies = arena_openings;
         coach.merge_canonical = merge == "canonical";
         coach.merge_positions = coach.merge_canonical || std::strtol(merge.c_str(), nullptr, 10) != 0;
+        coach.solve_min_stones = (size_t)std::strtoul(quality.c_str(), nullptr, 10);
+        if (quality.find(',') != std::string::npos) coach.solve_max_nodes = (uint32_t)std::strtoul(quality.c_str() + quality.find(',') + 1, nullptr, 10);
         for (const auto& r : coach.learn(false, /*seed*/ 0)) {
             std::printf("iteration %zu: %zu samples, new/prev/draw %zu/%zu/%zu, %s, loss (%.4f, %.4f)\n", r.iteration, r.samples, r.nwins,
                         r.pwins, r.draws, r.accepted ? "accepted" : "rejected", r.losses.empty() ? 0.f : r.losses[r.losses.size() - 2],

@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--forced-playouts", default=None, metavar="K[,prune]")   # forced playouts at the root, e.g. 2,prune: with policy target pruning (Coach.forced_playouts_k)
     ap.add_argument("--arena-openings", type=int, default=0, metavar="N")   # paired openings of the gate: N random quiet plies (even, 2 .. 12) per pair of arena games (Coach.arena_opening_plies)
     ap.add_argument("--merge-positions", nargs="?", const="plain", default=None, choices=["plain", "canonical"])   # position averaging before training: one tuple per distinct position; =canonical also merges mirror images (Coach.merge_positions)
+    ap.add_argument("--move-quality", default=None, metavar="STONES[,NODES]")   # exact move-quality report of every arena: positions with at least STONES stones are solved (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach.solve_min_stones)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
     ap.add_argument("--eval-mirror", action="store_true")    # mirror-canonical leaf evaluation for the whole loop (Coach.eval_mirror)
     a = ap.parse_args()
@@ -67,10 +68,15 @@ def main():
         coach.forced_playouts_k, coach.policy_prune = float(k), prune == "prune"
     coach.arena_opening_plies = a.arena_openings
     coach.merge_positions, coach.merge_canonical = a.merge_positions is not None, a.merge_positions == "canonical"
+    if a.move_quality:
+        stones, _, nodes = a.move_quality.partition(",")
+        coach.solve_min_stones, coach.solve_max_nodes = int(stones), int(nodes) if nodes else 1 << 20
     for r in coach.learn(skip_first_play=False, seed=a.seed):
         print(r["iteration"], "samples", r["samples"], *(("of", r["samples_raw"]) if coach.merge_positions else ()), "new/prev/draw", r["nwins"], r["pwins"], r["draws"],
               "accepted" if r["accepted"] else "rejected", "loss", r["losses"][-1],
               "seconds", {k: round(v, 2) for k, v in r["seconds"].items()})
+        if "quality" in r:
+            print(r["iteration"], "move quality from", coach.solve_min_stones, "stones:", r["quality"])
     e.close()
 
 

@@ -638,6 +638,59 @@ az_status az_arena_set_opening_book(az_engine* e, const uint64_t* boards, int32_
  * Any pointer may be NULL.  AZ_ERR_BAD_ARGUMENT before the first az_arena. */
 az_status az_arena_get_openings(az_engine* e, uint64_t* boards, int32_t* len, uint8_t* moves);
 
+/* ---- exact endgame solver and move-quality report (no reference counterpart).  Strictly opt-in: a host that never calls these runs
+ * nothing of them.  The game-theoretic value of a late position can be computed exactly; a move then either keeps that value or throws it
+ * away, which is an ABSOLUTE measure of play that needs no opponent.  The search, its frozen rule and the table entry are in
+ * alphazero-rs_amd/csrc/az_solve.h, the kernels in az_solve.hip.
+ *
+ * az_solve: n positions (0 .. 2^24; canonical {mine, theirs}, host or device memory), every root action of each.
+ *   move_values [n,7]   the outcome for the side to move after it plays the action: -1, 0, +1; AZ_SOLVE_ILLEGAL for an action that is
+ *                       not legal and for every action of a finished position; AZ_SOLVE_UNKNOWN when the search of that action needed
+ *                       more than max_nodes nodes, or the position has fewer than min_stones stones
+ *   values [n]          (may be NULL) +1 if any action is +1; else AZ_SOLVE_UNKNOWN if any legal action is UNKNOWN; else the maximum
+ *                       over the legal actions.  A finished position: the value of its ended_code as the tree sees it (+1 when the
+ *                       side that moved in has won, 0 for a full board)
+ *   nodes [n,7]         (may be NULL) nodes the search of the action entered (0 for an action decided without a search; max_nodes
+ *                       for an UNKNOWN one)
+ *   max_nodes           budget per (position, action), 1 .. 2^30
+ *   min_stones          0 .. 42: positions with fewer stones are not searched (every legal action UNKNOWN, 0 nodes)
+ *   tt_log2             0 = no transposition table, else 8 .. 16: 2^tt_log2 8-byte entries per resident lane, private to the item
+ *   max_lanes           0 = the grid is sized from the device (CUs x resident waves x 64), else a multiple of 64 that caps it.  The
+ *                       grid is also capped so that the table stays under 4 GiB
+ *   The result of every (position, action) -- value, node count, UNKNOWN or not -- is a pure function of (state, action, max_nodes,
+ *   min_stones, tt_log2, game): it does not depend on n, the grid, the schedule or the other positions of the call.
+ *   refused             AZ_ERR_BAD_ARGUMENT with nothing written: a parameter out of range; n outside 0 .. 2^24; NULL states or
+ *                       move_values; a state with overlapping stones, bits outside the board or floating stones (the search needs a
+ *                       reachable stacking); a call while a self-play session is open.  n = 0 is legal
+ *   purity              models, trees, the evaluation cache, options and every az_stats counter but device_ms are untouched.  Runs on
+ *                       the engine's stream in workspaces the engine owns (lanes x 8 B << tt_log2 of table, about 60 bytes per
+ *                       position), reused by later calls and given back as az_samples_merge's is
+ *
+ * az_move_quality: n recorded games (at most 2^24 / 42), replayed on the device.  start_boards [n,2] as az_arena_get_openings returns
+ *   them (NULL = the initial board), game_len [n] and moves [n,AZ_MAX_PLIES] as az_arena_get_moves and az_samples.game_len / moves
+ *   return them.  Every position that is reached is solved as by az_solve and the move played there classified:
+ *   ply_class [n,AZ_MAX_PLIES]   AZ_MQ_SKIPPED behind game_len and at positions with fewer than min_stones stones; AZ_MQ_KEPT when the
+ *                       value after the move equals the position's value (a played move of value +1 is KEPT even when siblings are
+ *                       UNKNOWN); AZ_MQ_WIN_TO_DRAW, AZ_MQ_WIN_TO_LOSS, AZ_MQ_DRAW_TO_LOSS; AZ_MQ_UNKNOWN when the position's value,
+ *                       or the played move's value where it is needed, is UNKNOWN
+ *   ply_value [n,AZ_MAX_PLIES]   (may be NULL) the position's value as az_solve's values[i]; AZ_SOLVE_UNKNOWN where the class is SKIPPED
+ *   refused             as az_solve, and: an illegal move in a record, a game_len outside 0 .. 42 or beyond the end of its game, a
+ *                       start board that is not a reachable stacking
+ *   The report counts exact value-losing moves from min_stones on.  It says nothing about the opening, nor about a ply the budget
+ *   left UNKNOWN. */
+#define AZ_SOLVE_ILLEGAL (-128)
+#define AZ_SOLVE_UNKNOWN 127
+#define AZ_MQ_SKIPPED 0
+#define AZ_MQ_KEPT 1
+#define AZ_MQ_WIN_TO_DRAW 2
+#define AZ_MQ_WIN_TO_LOSS 3
+#define AZ_MQ_DRAW_TO_LOSS 4
+#define AZ_MQ_UNKNOWN 5
+az_status az_solve(az_engine* e, const uint64_t* states, int32_t n, uint32_t max_nodes, int32_t min_stones, int32_t tt_log2, int32_t max_lanes,
+                   int8_t* move_values, int8_t* values, uint32_t* nodes);
+az_status az_move_quality(az_engine* e, const uint64_t* start_boards, const int32_t* game_len, const uint8_t* moves, int32_t n,
+                          uint32_t max_nodes, int32_t min_stones, int32_t tt_log2, int32_t max_lanes, uint8_t* ply_class, int8_t* ply_value);
+
 /* ---- the collective of the sharded Coach loop (no reference counterpart: the reference is one process,
  * src/coach.rs:241-272 fans episodes out over a rayon pool; here one process per GPU plays a shard of the global
  * episode ids and the (s, pi, z) tuples meet once per episode batch) --------------------------------------------------

@@ -31,6 +31,12 @@
 // Coach used before position averaging (tests/cpp/test_root_noise_host_cpu.cpp and its like), and Coach::learn names az_samples_merge.
 // With a real engine library the symbol resolves as any other; without it Coach::merge_positions panics instead of calling through null.
 #pragma weak az_samples_merge
+// The same holds for what Coach::solve_min_stones reaches: with it off (the default) none of these is called.
+#pragma weak az_solve
+#pragma weak az_move_quality
+#pragma weak az_arena_get_moves
+#pragma weak az_arena_get_openings
+#pragma weak az_allreduce_u64
 
 namespace az_host {
 
@@ -102,9 +108,13 @@ class ConnectFourGame {
     }
 };
 
+// the four search parameters of az_solve / az_move_quality (include/az_engine.h)
+struct SolveParams { uint32_t max_nodes = 1u << 20; int32_t min_stones = 0, tt_log2 = 12, max_lanes = 0; };
+
 // ---- engine handle + NNet ----------------------------------------------------------------------------------
 class Engine {
   public:
+    using SolveParams = az_host::SolveParams;
     explicit Engine(int device = 0, int max_batch = 8192, int channels = 512) {
         az_config cfg{device, max_batch, channels, 0, 0};
         if (az_create(&cfg, &e_) != AZ_OK) throw Panic("az_create failed");
@@ -156,10 +166,47 @@ class Engine {
         check(az_selfplay_get_full_plies(e_, mask.data()));
         return mask;
     }
+    // az_solve (include/az_engine.h): the exact outcome of every root action of n canonical positions {mine, theirs}
+    struct Solved { std::vector<int8_t> move_values, values; std::vector<uint32_t> nodes; };     // [n][7], [n], [n][7]
+    Solved solve(const std::vector<uint64_t>& states, const SolveParams& p = SolveParams()) const {
+        if (!az_solve) throw Panic("solve: the linked engine library has no az_solve");
+        const size_t n = states.size() / 2;
+        Solved r{std::vector<int8_t>(n * 7), std::vector<int8_t>(n), std::vector<uint32_t>(n * 7)};
+        check(az_solve(e_, states.data(), (int32_t)n, p.max_nodes, p.min_stones, p.tt_log2, p.max_lanes, r.move_values.data(), r.values.data(), r.nodes.data()));
+        return r;
+    }
+    // az_move_quality: ply_class [n][AZ_MAX_PLIES] of AZ_MQ_* for n recorded games (start_boards [n][2] or nullptr = the initial board)
+    std::vector<uint8_t> move_quality(const uint64_t* start_boards, const std::vector<int32_t>& game_len, const std::vector<uint8_t>& moves,
+                                      const SolveParams& p, std::vector<int8_t>* ply_value = nullptr) const {
+        if (!az_move_quality) throw Panic("move_quality: the linked engine library has no az_move_quality");
+        const size_t n = game_len.size();
+        std::vector<uint8_t> cls(n * AZ_MAX_PLIES);
+        if (ply_value) ply_value->assign(n * AZ_MAX_PLIES, 0);
+        check(az_move_quality(e_, start_boards, game_len.data(), moves.data(), (int32_t)n, p.max_nodes, p.min_stones, p.tt_log2, p.max_lanes,
+                              cls.data(), ply_value ? ply_value->data() : nullptr));
+        return cls;
+    }
 
   private:
     az_engine* e_ = nullptr;
 };
+
+// The move-quality tally of one arena shard: counts[0] the new model's moves, counts[1] the old model's, each {examined, kept, win_to_draw,
+// win_to_loss, draw_to_loss, unknown}.  Game g of the shard has global index first_game + g; the new model holds the first seat in the
+// games below total_games / 2 (az_arena), and the first seat moves at the even plies of the record -- a start board, opening or not,
+// always has the first seat to move (az_arena_get_openings).
+inline void quality_tally(const std::vector<uint8_t>& ply_class, size_t first_game, size_t total_games, uint64_t counts[2][6]) {
+    const size_t n = ply_class.size() / AZ_MAX_PLIES;
+    for (size_t g = 0; g < n; ++g)
+        for (size_t p = 0; p < AZ_MAX_PLIES; ++p) {
+            const uint8_t c = ply_class[g * AZ_MAX_PLIES + p];
+            if (c == AZ_MQ_SKIPPED) continue;
+            const bool new_first = first_game + g < total_games / 2, first_moves = p % 2 == 0;
+            uint64_t* row = counts[new_first == first_moves ? 0 : 1];
+            ++row[0];
+            ++row[c];
+        }
+}
 
 class NNet {                                                            // src/nnet.rs:35-45
   public:
@@ -386,7 +433,9 @@ struct ScopedOption {
 class Coach {
   public:
     // samples = the tuples trained on, samples_raw = the tuples of the window before position averaging (equal with merge_positions off)
-    struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; size_t samples_raw; };
+    // quality (with solve_min_stones > 0): [0] the new model's arena moves, [1] the old model's, each {examined, kept, win_to_draw, win_to_loss,
+    // draw_to_loss, unknown} (quality_tally above); all zero with the report off
+    struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; size_t samples_raw; uint64_t quality[2][6]; };
 
     // Coach::setup(checkpoint_directory, + the reference's 14 numeric parameters), src/coach.rs:38-103
     static Coach setup(Engine& e, const std::string& checkpoint_directory, size_t mcts_reserve_size, float update_threshold,
@@ -636,6 +685,28 @@ class Coach {
             std::printf("NEW/PREV WINS : %zu / %zu; DRAWS : %zu\n", r.nwins, r.pwins, r.draws);        // :381
             r.accepted = !(r.pwins + r.nwins == 0 || (float)r.nwins / (float)(r.pwins + r.nwins) < update_threshold);   // :383-390
             std::printf(r.accepted ? "ACCEPTING NEW MODEL\n" : "REJECTING NEW MODEL\n");
+            if (solve_min_stones > 0) {                               // the exact move-quality report of the arena just played; decides nothing
+                if (!az_move_quality || !az_arena_get_moves || !az_arena_get_openings || !az_allreduce_u64)
+                    throw Panic("solve_min_stones: the linked engine library has no az_move_quality");
+                const bool sharded = a.total_games > 0;
+                const size_t local = sharded ? (size_t)a.num_games : 2 * (num_arena_games / 2), total = sharded ? (size_t)a.total_games : local;
+                if (local > 0) {
+                    std::vector<int32_t> len(local);
+                    std::vector<uint8_t> moves(local * AZ_MAX_PLIES);
+                    std::vector<uint64_t> boards(local * 2);
+                    e_.check(az_arena_get_moves(e_.raw(), len.data(), moves.data()));
+                    e_.check(az_arena_get_openings(e_.raw(), boards.data(), nullptr, nullptr));
+                    Engine::SolveParams sp;
+                    sp.max_nodes = solve_max_nodes; sp.min_stones = (int32_t)solve_min_stones;
+                    quality_tally(e_.move_quality(boards.data(), len, moves, sp), sharded ? (size_t)a.first_game : 0, total, r.quality);
+                }
+                if (world_ > 1 || use_comm_at_world_1) e_.check(az_allreduce_u64(e_.raw(), &r.quality[0][0], 12));
+                for (int m = 0; m < 2; ++m)
+                    std::printf("MOVE QUALITY %s (from %zu stones): examined %llu kept %llu win->draw %llu win->loss %llu draw->loss %llu unknown %llu\n",
+                                m ? "PREV" : "NEW", solve_min_stones, (unsigned long long)r.quality[m][0], (unsigned long long)r.quality[m][1],
+                                (unsigned long long)r.quality[m][2], (unsigned long long)r.quality[m][3], (unsigned long long)r.quality[m][4],
+                                (unsigned long long)r.quality[m][5]);
+            }
             // a long run moves to a new model id per accepted iteration: drop the slot nobody will read again
             e_.check(az_net_free(e_.raw(), (int32_t)(r.accepted ? model_id : model_id + 1)));
             if (r.accepted) ++model_id;
@@ -684,6 +755,12 @@ class Coach {
     // and nothing expands them again, so the net then trains on the CANONICAL orientation of every position only -- half the set; meant to
     // go with eval_mirror, which evaluates on that orientation.  false (the default): the engine is never asked
     bool merge_positions = false, merge_canonical = false;
+    // Move-quality report (az_move_quality): after every iteration's arena its games are replayed, every position with at least
+    // solve_min_stones stones is solved exactly (budget solve_max_nodes per position and action) and the move played there classed; the
+    // tally per model goes into Report::quality and one log line each.  It decides nothing: the gate, the checkpoints, the .examples files
+    // and coach.state are those of a run without it.  0 (the default): the engine is never asked
+    size_t solve_min_stones = 0;
+    uint32_t solve_max_nodes = 1u << 20;
     float update_threshold = 0.f;
     int32_t cpuct = 1;
 

@@ -51,6 +51,17 @@ pub struct az_arena_params {
 /// flags bit 0 of az_samples_merge: a position and its left-right mirror image merge (the state kept is the canonical one)
 pub const AZ_MERGE_CANONICAL: i32 = 1;
 
+/// az_solve: an action that is not legal (or a finished position) / a search that exhausted max_nodes (or a position below min_stones)
+pub const AZ_SOLVE_ILLEGAL: i8 = -128;
+pub const AZ_SOLVE_UNKNOWN: i8 = 127;
+/// classes of az_move_quality
+pub const AZ_MQ_SKIPPED: u8 = 0;
+pub const AZ_MQ_KEPT: u8 = 1;
+pub const AZ_MQ_WIN_TO_DRAW: u8 = 2;
+pub const AZ_MQ_WIN_TO_LOSS: u8 = 3;
+pub const AZ_MQ_DRAW_TO_LOSS: u8 = 4;
+pub const AZ_MQ_UNKNOWN: u8 = 5;
+
 extern "C" {
     // ---- lifecycle
     pub fn az_create(cfg: *const az_config, out: *mut *mut az_engine) -> c_int;
@@ -114,6 +125,13 @@ extern "C" {
     /// position averaging: one tuple per distinct position of src (mean pi, mean z, first-occurrence order); flags bit 0 =
     /// AZ_MERGE_CANONICAL merges a position with its mirror image; dst.capacity >= src.count; counts [m] may be null
     pub fn az_samples_merge(e: *mut az_engine, src: *const az_samples, flags: i32, dst: *mut az_samples, counts: *mut u32) -> c_int;
+    /// exact endgame solver: every root action of n canonical positions; move_values [n,7] in {-1, 0, +1, AZ_SOLVE_ILLEGAL, AZ_SOLVE_UNKNOWN},
+    /// values [n] and nodes [n,7] may be null; tt_log2 0 or 8..16, max_lanes 0 or a multiple of 64
+    pub fn az_solve(e: *mut az_engine, states: *const u64, n: i32, max_nodes: u32, min_stones: i32, tt_log2: i32, max_lanes: i32,
+                    move_values: *mut i8, values: *mut i8, nodes: *mut u32) -> c_int;
+    /// move-quality report of n recorded games (start_boards may be null): ply_class [n,42] of AZ_MQ_*, ply_value [n,42] may be null
+    pub fn az_move_quality(e: *mut az_engine, start_boards: *const u64, game_len: *const i32, moves: *const u8, n: i32,
+                           max_nodes: u32, min_stones: i32, tt_log2: i32, max_lanes: i32, ply_class: *mut u8, ply_value: *mut i8) -> c_int;
     pub fn az_arena(e: *mut az_engine, p: *const az_arena_params, out_wld: *mut u64, results: *mut i8) -> c_int;
     pub fn az_arena_get_evals(e: *mut az_engine, which: i32, rec_count: *mut i32, states: *mut u64, pis: *mut f32, vs: *mut f32) -> c_int;
     pub fn az_arena_get_moves(e: *mut az_engine, game_len: *mut i32, moves: *mut u8) -> c_int;
