@@ -65,6 +65,9 @@ class Coach:
         # Forced playouts and policy target pruning of the episodes (Engine.set_forced_playouts): switched on before every az_selfplay and
         # off again behind it, exactly as the playout cap is.  k 0 (the default): the engine is never asked
         self.forced_playouts_k, self.policy_prune = 0.0, False
+        # Gumbel root search with sequential halving of the episodes (Engine.set_gumbel): switched on before every az_selfplay and off again
+        # behind it, exactly as the forced playouts are (the engine refuses the two together).  m 0 (the default): the engine is never asked
+        self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale = 0, 50.0, 1.0
         # Paired openings of the gate (Engine.set_arena_openings): switched on before the iteration's az_arena and off again behind it,
         # exactly as the forced playouts are around self-play.  0 (the default): the engine is never asked
         self.arena_opening_plies = 0
@@ -139,6 +142,10 @@ class Coach:
         return self._scoped(self.forced_playouts_k > 0, lambda: self.engine.set_forced_playouts(self.forced_playouts_k, self.policy_prune),
                             lambda: self.engine.set_forced_playouts(0.0, False))
 
+    def _selfplay_gumbel(self):
+        return self._scoped(self.gumbel_m > 0, lambda: self.engine.set_gumbel(self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale),
+                            lambda: self.engine.set_gumbel(0))
+
     def _arena_openings(self):
         return self._scoped(self.arena_opening_plies > 0, lambda: self.engine.set_arena_openings(self.arena_opening_plies),
                             lambda: self.engine.set_arena_openings(0))
@@ -150,7 +157,7 @@ class Coach:
         lo, hi = azdist.shard_range(self.num_eps, rank, world)
         first = iteration * self.num_eps
         if hi > lo:
-            with self._selfplay_root_noise(), self._selfplay_playout_cap(), self._selfplay_forced_playouts():
+            with self._selfplay_root_noise(), self._selfplay_playout_cap(), self._selfplay_forced_playouts(), self._selfplay_gumbel():
                 r = self.engine.selfplay(n_games=hi - lo, num_sims=self.num_sims, model_id=model_id, seed=seed,
                                          first_game_id=first + lo, concurrent=min(self.num_episode_threads, hi - lo),
                                          temp_threshold=self.temp_threshold, max_depth=self.max_depth, cpuct=self.cpuct,

@@ -83,6 +83,9 @@ AZ_HD uint32_t rng_choose(uint64_t r, uint32_t k) { return (uint32_t)(((r >> 32)
 constexpr uint64_t RNG_BATCH = 4;
 // Dirichlet root noise (az_noise.h): draw j of action a of the root (seed, game_id, ply) = rng_draw(seed, game_id, ply, RNG_NOISE + 256 * a + 65536 * j)
 constexpr uint64_t RNG_NOISE = 5;
+// Gumbel root search (az_gumbel.h): the variate of action a of the root (seed, game_id, ply) = rng_draw(seed, game_id, ply, RNG_GUMBEL + 256 * a)
+// (6 and 7 are the playout cap's and the arena openings': az_playout.h, az_opening.h)
+constexpr uint64_t RNG_GUMBEL = 8;
 AZ_HD bool dropout_keep(uint64_t mask_seed, uint32_t layer, uint64_t idx, uint32_t keep_thresh24) {
     const uint64_t r = mix64(mix64(mask_seed ^ ((uint64_t)(layer + 1) * 0xD1B54A32D192ED03ull)) ^ idx);
     return (uint32_t)(r >> 40) < keep_thresh24;

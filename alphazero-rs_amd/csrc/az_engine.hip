@@ -27,6 +27,7 @@
 #include "az_solve.h"
 #include "az_train.h"
 #include "az_tree.h"
+#include "az_gumbel.h"
 
 using namespace az;
 
@@ -204,6 +205,11 @@ struct TreeHost {
     struct StepGraph { hipGraphExec_t exec = nullptr; std::vector<unsigned char> key; };
     StepGraph step_graph;
     unsigned long long* d_totals = nullptr;   // [ST_COUNT] k_harvest's sums
+    // Gumbel root search ("gumbel_m"): per-tree baseline, variates and selected action of the current move; handed to the kernels through
+    // TreeDev.gumbel only while the option is on (gumbel_for)
+    uint4* gz_base = nullptr;                 // [G]
+    float* gz_g = nullptr;                    // [G][8]
+    int32_t* gz_selected = nullptr;           // [G]
     uint32_t* d_counts = nullptr;             // [G] NodeStore::len per tree (k_harvest)
     // blocks = child blocks the trees can use (each holds the <= 7 children of one expansion, or a root);
     // reserve_nodes = reserve_space (src/node.rs:146) clamped to what is reachable
@@ -217,6 +223,7 @@ struct TreeHost {
         d.noise = RootNoise{};                    // root noise belongs to the call that sets it (the arena never does)
         d.cap = PlayoutCap{};                     // and so does a playout cap (self-play sessions only)
         d.forced = ForcedPlayouts{};              // and forced playouts / pruning (never the arena)
+        d.gumbel = Gumbel{};                      // and Gumbel root search (never the arena)
         HIPCHK(hipMemsetAsync(d.err, 0, ERR_COUNT * sizeof(uint32_t), s));
         HIPCHK(hipMemsetAsync(d_totals, 0, ST_TOTALS * sizeof(unsigned long long), s));
         HIPCHK(hipMemsetAsync(eb.n, 0, sizeof(uint32_t), s));
@@ -248,6 +255,12 @@ struct TreeHost {
         }
         d_totals = mem.alloc<unsigned long long>(ST_TOTALS);
         d_counts = mem.alloc<uint32_t>(G);
+        gz_base = mem.alloc<uint4>(G);
+        gz_g = mem.alloc<float>((size_t)G * BLOCK_SLOTS);
+        gz_selected = mem.alloc<int32_t>(G);
+        HIPCHK(hipMemset(gz_base, 0, (size_t)G * sizeof(uint4)));
+        HIPCHK(hipMemset(gz_g, 0, (size_t)G * BLOCK_SLOTS * sizeof(float)));
+        HIPCHK(hipMemset(gz_selected, 0xFF, (size_t)G * sizeof(int32_t)));
         HIPCHK(hipMemset(d.err, 0, ERR_COUNT * sizeof(uint32_t)));
         HIPCHK(hipMemset(d_totals, 0, ST_TOTALS * sizeof(unsigned long long)));
         launch_init_heads(d, nullptr);
@@ -341,6 +354,9 @@ struct az_engine {
     int64_t playout_cap_sims = 0, playout_cap_full_e6 = 250000;
     // forced playouts at the root and policy target pruning, on the moves root noise can apply to ("forced_playouts_k_e6" 0 = off, "policy_prune")
     int64_t forced_playouts_k_e6 = 0, policy_prune = 0;
+    // Gumbel root search with sequential halving on the same moves ("gumbel_m" 0 = off, "gumbel_c_visit_e6", "gumbel_c_scale_e6"); never the
+    // arena or the slot calls
+    int64_t gumbel_m = 0, gumbel_c_visit_e6 = GUMBEL_C_VISIT_E6_DEFAULT, gumbel_c_scale_e6 = GUMBEL_C_SCALE_E6_DEFAULT;
     // paired openings of az_arena, never of self-play or the tree calls ("arena_opening_plies" 0 = off; az_arena_set_opening_book)
     int64_t arena_opening_plies = 0;
     std::vector<uint64_t> ar_book;      // [entries][2] {first seat's stones, second seat's stones}; empty = no book
@@ -457,7 +473,8 @@ struct az_tree {
     DeviceMem mem;
     int num_sims = 0, max_depth = 0, model_id = 0, cpuct = 0;
     ulonglong2* d_root_states = nullptr;
-    ulonglong2* d_noise_streams = nullptr;     // [G] (seed, game_id) of each tree's current call: the root-noise streams
+    ulonglong2* d_noise_streams = nullptr;     // [G] (seed, game_id) of each tree's current call: the root-noise and Gumbel streams
+    bool last_gumbel = false;                  // the last az_tree_get_action_prob was a Gumbel move (az_tree_get_selected)
     // pinned host block of one get_action_prob call: the roots go up from it and k_root_policy / k_call_readback write the
     // results and counters straight into it, so a call costs one stream synchronisation instead of eight blocking copies
     void* h_io = nullptr;
@@ -475,6 +492,13 @@ namespace {
 az_status fail(az_engine* e, az_status st, const std::string& msg) {
     if (e) e->err = msg;
     return st;
+}
+az_status gumbel_refusal(az_engine* e, int T, const char* who) {
+    if (e->gumbel_m == 0) return AZ_OK;
+    if (T > 1) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": gumbel_m needs num_sim_threads = 1");
+    if (e->selfplay_async) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": gumbel_m and selfplay_async exclude each other");
+    if (e->forced_playouts_k_e6 > 0) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": gumbel_m and forced_playouts_k_e6 exclude each other (both claim the root's arg-max)");
+    return AZ_OK;
 }
 az_status fail_hip(az_engine* e, const HipFail& f) {
     char buf[512];
@@ -494,6 +518,21 @@ ForcedPlayouts forced_for(const az_engine* e, float cpuct_f) {
     fp.cpuct_f = cpuct_f;
     return fp;
 }
+// "gumbel_m" / "gumbel_c_visit_e6" / "gumbel_c_scale_e6" as the kernels take them, for moves of num_sims simulations on the trees of th.
+// m == 0 (off) gives the all-zero record whatever the constants are: the launchers then pick today's instantiations and the search graph's
+// key is that of an engine that never set the keys.  The caller adds the stream (seed / first_game_id / row, or stream) and the threshold.
+Gumbel gumbel_for(const az_engine* e, const TreeHost& th, int num_sims) {
+    Gumbel gz{};
+    if (e->gumbel_m == 0) return gz;
+    gz.m = (uint32_t)e->gumbel_m;
+    gz.c_visit = gumbel_of_e6(e->gumbel_c_visit_e6);
+    gz.c_scale = gumbel_of_e6(e->gumbel_c_scale_e6);
+    gz.num_sims = (uint32_t)num_sims;
+    gz.base = th.gz_base; gz.g = th.gz_g; gz.selected = th.gz_selected;
+    return gz;
+}
+// what az_selfplay, az_selfplay_begin and az_tree_get_action_prob refuse while "gumbel_m" is on
+az_status gumbel_refusal(az_engine* e, int T, const char* who);
 RootNoise root_noise_for(const az_engine* e) {
     RootNoise rn{};
     if (e->root_noise_eps_e6 == 0) return rn;
@@ -746,6 +785,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
             RootNoise noise;                           // TreeDev travels by value: a graph captured with other noise arguments is never replayed
             PlayoutCap cap;                            // ... nor one captured with another playout cap (or without one)
             ForcedPlayouts forced;                     // ... nor one captured with other forced-playout arguments
+            Gumbel gumbel;                             // ... nor one captured with other Gumbel arguments
         } k;
         std::memset(&k, 0, sizeof k);
         k.th = &th; k.conv = net.conv; k.ws = net.kind == AZ_NET_CONV ? workspace_for(e, s) : nullptr; k.stream = s; k.root_states = d_root_states;
@@ -757,6 +797,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
         k.noise = th.d.noise;
         k.cap = th.d.cap;
         k.forced = th.d.forced;
+        k.gumbel = th.d.gumbel;
         k.reserve_nodes = th.d.reserve_nodes;      // TreeDev travels by value into the captured launches: the capacity threshold is baked in
         k.model_gen = net.generation;              // a freed and re-created model may reuse the ConvNet's address: its weights' identity is the generation
         TreeHost::StepGraph& sg = th.step_graph;
@@ -923,6 +964,7 @@ void SlotRunner::operator()(CombineBatch<SlotCall>& b) const {
         d.noise = root_noise_for(e);
         if (d.noise.eps != 0.0f) d.noise.stream = t->d_noise_streams;         // each request's own (seed, game_id)
         d.forced = forced_for(e, (float)t->cpuct);
+        d.gumbel = Gumbel{};                                                  // the slot calls never search by the Gumbel rule
         launch_slot_arm(d, sh.d_req, n, t->d_root_states, sh.d_reset, s, d.noise.stream ? t->d_noise_streams : nullptr);
         if (any_reset) launch_reset_trees(d, sh.d_reset, s);      // AsyncMcts::default for the slots acquired since their last batch
         SearchParams sp{(uint32_t)t->max_depth, (float)t->cpuct};
@@ -1085,6 +1127,15 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
             return fail(e, AZ_ERR_BAD_ARGUMENT, k ? "forced_playouts_k_e6 must be in 0 .. 16000000" : "policy_prune must be 0 or 1");
         if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "forced playouts cannot change while a self-play session is open");
         (k ? e->forced_playouts_k_e6 : e->policy_prune) = value;
+        return AZ_OK;
+    }
+    if (is("gumbel_m") || is("gumbel_c_visit_e6") || is("gumbel_c_scale_e6")) {
+        if (is("gumbel_m") && value != 0 && (value < GUMBEL_M_MIN || value > GUMBEL_M_MAX)) return fail(e, AZ_ERR_BAD_ARGUMENT, "gumbel_m must be 0 or in 2 .. 7");
+        if (is("gumbel_c_visit_e6") && (value < 0 || value > GUMBEL_C_VISIT_E6_MAX)) return fail(e, AZ_ERR_BAD_ARGUMENT, "gumbel_c_visit_e6 must be in 0 .. 1000000000");
+        if (is("gumbel_c_scale_e6") && (value < GUMBEL_C_SCALE_E6_MIN || value > GUMBEL_C_SCALE_E6_MAX))
+            return fail(e, AZ_ERR_BAD_ARGUMENT, "gumbel_c_scale_e6 must be in 1 .. 100000000");
+        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "Gumbel root search cannot change while a self-play session is open");
+        (is("gumbel_m") ? e->gumbel_m : is("gumbel_c_visit_e6") ? e->gumbel_c_visit_e6 : e->gumbel_c_scale_e6) = value;
         return AZ_OK;
     }
     if (is("arena_opening_plies")) {
@@ -1687,6 +1738,8 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
     if (st) return st;
     st = check_batch(e, *net, t->th.d.G * t->th.d.T);
     if (st) return st;
+    st = gumbel_refusal(e, t->th.d.T, "az_tree_get_action_prob");
+    if (st) return st;
     ScopedTimer timer{e};
     try {
         HIPCHK(hipSetDevice(e->device));
@@ -1703,9 +1756,12 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
         launch_set_active(d, 1u, e->stream);
         d.forced = forced_for(e, (float)t->cpuct);
         d.noise = root_noise_for(e);
-        if (d.noise.eps != 0.0f) {                 // tree g's stream: (seed, first_game_id + g), from device memory so the search graph survives the call's seed
+        d.gumbel = gumbel_for(e, t->th, t->num_sims);
+        t->last_gumbel = d.gumbel.m != 0u;
+        if (d.noise.eps != 0.0f || d.gumbel.m != 0u) {      // tree g's stream: (seed, first_game_id + g), from device memory so the search graph survives the call's seed
             launch_noise_streams(t->d_noise_streams, G, seed, first_game_id, e->stream);
-            d.noise.stream = t->d_noise_streams;
+            if (d.noise.eps != 0.0f) d.noise.stream = t->d_noise_streams;
+            if (d.gumbel.m != 0u) { d.gumbel.stream = t->d_noise_streams; d.gumbel.temp_threshold = temp == 0.0f ? INT32_MIN : INT32_MAX; }
         }
         SearchParams sp{(uint32_t)t->max_depth, (float)t->cpuct};
         prepare_cache(e, dedup_applies(e, *net), (uint64_t)G * ((uint64_t)t->num_sims + 1), e->stream);
@@ -1746,6 +1802,43 @@ az_status az_root_noise_eta(az_engine* e, int32_t n, uint64_t seed, const uint64
         HIPCHK(hipMemcpyAsync(d_states, states, (size_t)n * 16, hipMemcpyDefault, e->stream));
         launch_root_noise_eta(e->cfg.game, n, seed, d_ids, d_states, (float)((double)e->root_noise_alpha_e6 / 1e6), d_eta, e->stream);
         HIPCHK(hipMemcpyAsync(eta_out, d_eta, (size_t)n * 7 * sizeof(float), hipMemcpyDefault, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// The selected action of each tree's last az_tree_get_action_prob when that was a Gumbel move ("gumbel_m"), else -1.
+az_status az_tree_get_selected(az_tree* t, int32_t* actions) {
+    if (!t || !actions) return AZ_ERR_BAD_ARGUMENT;
+    az_engine* e = t->e;
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        const size_t G = (size_t)t->th.d.G;
+        if (t->last_gumbel) {
+            HIPCHK(hipMemcpy(actions, t->th.gz_selected, G * sizeof(int32_t), hipMemcpyDefault));
+        } else {
+            const std::vector<int32_t> none(G, -1);
+            HIPCHK(hipMemcpy(actions, none.data(), G * sizeof(int32_t), hipMemcpyDefault));
+        }
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// The device's Gumbel variates alone (csrc/az_gumbel.h as the search kernels run it) for n roots: g_out[i][a], 0 for an invalid action.
+az_status az_gumbel_values(az_engine* e, int32_t n, uint64_t seed, const uint64_t* game_ids, const uint64_t* states, int32_t temp_is_zero, float* g_out) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (n < 0 || (n > 0 && (!game_ids || !states || !g_out))) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_gumbel_values: bad argument");
+    if (n == 0) return AZ_OK;
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        DeviceMem mem;
+        uint64_t* d_ids = mem.alloc<uint64_t>((size_t)n);
+        ulonglong2* d_states = mem.alloc<ulonglong2>((size_t)n);
+        float* d_g = mem.alloc<float>((size_t)n * 7);
+        HIPCHK(hipMemcpyAsync(d_ids, game_ids, (size_t)n * 8, hipMemcpyDefault, e->stream));
+        HIPCHK(hipMemcpyAsync(d_states, states, (size_t)n * 16, hipMemcpyDefault, e->stream));
+        launch_gumbel_values(e->cfg.game, n, seed, d_ids, d_states, temp_is_zero != 0, d_g, e->stream);
+        HIPCHK(hipMemcpyAsync(g_out, d_g, (size_t)n * 7 * sizeof(float), hipMemcpyDefault, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
@@ -1846,7 +1939,7 @@ struct SelfplaySession {
     EvalCache ec{};
     int fill = 0;
     long long step = 0;
-    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); if (lease.th) { lease.th->d.noise = RootNoise{}; lease.th->d.cap = PlayoutCap{}; lease.th->d.forced = ForcedPlayouts{}; } }
+    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); if (lease.th) { lease.th->d.noise = RootNoise{}; lease.th->d.cap = PlayoutCap{}; lease.th->d.forced = ForcedPlayouts{}; lease.th->d.gumbel = Gumbel{}; } }
 };
 
 static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, std::unique_ptr<SelfplaySession>& out) {
@@ -1862,6 +1955,8 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     st = check_threads(e, p->num_sims, &T);
     if (st) return st;
     st = check_batch(e, *net, C * T);
+    if (st) return st;
+    st = gumbel_refusal(e, T, "az_selfplay");
     if (st) return st;
     const int cap_sims = (int)e->playout_cap_sims;
     if (cap_sims > 0 && cap_sims >= p->num_sims) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay: playout_cap_sims must be below num_sims");
@@ -1932,6 +2027,8 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     th.d.forced = forced_for(e, (float)p->cpuct); // the session's forced playouts / pruning (full moves only under a playout cap)
     th.d.noise = root_noise_for(e);               // the session's root noise: stream (seed, first_game_id + the slot's episode, ply)
     if (th.d.noise.eps != 0.0f) { th.d.noise.seed = p->seed; th.d.noise.first_game_id = p->first_game_id; th.d.noise.row = gd.gid; }
+    th.d.gumbel = gumbel_for(e, th, p->num_sims); // the session's Gumbel root search: the same stream, the budget of a full move
+    if (th.d.gumbel.m != 0u) { th.d.gumbel.seed = p->seed; th.d.gumbel.first_game_id = p->first_game_id; th.d.gumbel.row = gd.gid; th.d.gumbel.temp_threshold = p->temp_threshold; }
     prepare_cache(e, dedup_applies(e, *net), (uint64_t)n_games * AZ_MAX_PLIES * ((uint64_t)p->num_sims + 1), s);
     ss->sp = SearchParams{(uint32_t)p->max_depth, (float)p->cpuct};
     ss->mp = SelfplayMoveParams{p->seed, p->first_game_id, p->temp_threshold, C < n_games ? 1 : 0, 0, 0};

@@ -95,6 +95,26 @@ struct ForcedPlayouts {
     uint32_t pad;                // (no implicit padding: the record is part of the search graph's key)
 };
 
+// Gumbel root search with sequential halving ("gumbel_m" / "gumbel_c_visit_e6" / "gumbel_c_scale_e6", include/az_engine.h; the rule:
+// az_gumbel.h).  m == 0 is OFF: the launchers then pick today's instantiations, which contain none of this (one template axis with forced
+// playouts: the two exclude each other).  A GUMBEL MOVE is every get_action_prob that can carry root noise; under a playout cap the slot's
+// full moves only.  Tree g's variates are drawn on (seed, game_id, ply = stones on the root board) with (seed, game_id) = stream[g] when
+// stream is set (az_tree_get_action_prob), else (seed, first_game_id + (row ? row[g] : g)) (self-play: row = the slot's current episode).
+struct Gumbel {
+    uint32_t m;                  // 0 = OFF, else 2 .. 7: the largest number of root actions considered
+    float c_visit, c_scale;
+    uint32_t num_sims;           // n: the budget of a Gumbel move (num_sims; of a full move under a playout cap)
+    int32_t temp_threshold;      // the variates are 0 when stones + 1 >= temp_threshold (the tree call: INT32_MIN for temp == 0, INT32_MAX else)
+    uint32_t pad;                // (no implicit padding: the record is part of the search graph's key)
+    uint64_t seed, first_game_id;
+    const int32_t* row;          // [G] or nullptr
+    const ulonglong2* stream;    // [G] (seed, game_id) or nullptr
+    uint4* base;                 // [G] u16 x 8: the root children's visit counts when the move began (slot j < nchild; written once per move)
+    float* g;                    // [G][8] the slots' Gumbel variates of the move
+    int32_t* selected;           // [G] out (k_root_policy): the selected action of the tree's last az_tree_get_action_prob
+};
+static_assert(sizeof(Gumbel) == 80, "no implicit padding");
+
 struct TreeDev {
     int32_t G;               // trees
     uint32_t R;              // slots per tree (a multiple of BLOCK_SLOTS)
@@ -122,6 +142,7 @@ struct TreeDev {
     RootNoise noise;         // set by the entry point around its searches; zero for the arena
     PlayoutCap cap;          // set by a self-play session for its own searches; zero everywhere else
     ForcedPlayouts forced;   // set by the entry point around its searches, as noise is; zero for the arena
+    Gumbel gumbel;           // set by the entry point around its searches, as noise is; zero for the arena and the slot calls
 };
 
 // Leaf batch handed to the net (src/async_mcts.rs:117-189 restated as lanes): the DISTINCT states the trees of one
@@ -291,6 +312,9 @@ void launch_noise_streams(ulonglong2* streams, int n, uint64_t seed, uint64_t fi
 // eta_out[i][0..7) = the Dirichlet(alpha) noise of root states[i] on the stream (seed, game_ids[i], stones(states[i])): what a search with root
 // noise mixes into that root's priors (all device pointers)
 void launch_root_noise_eta(int game, int n, uint64_t seed, const uint64_t* game_ids, const ulonglong2* states, float alpha, float* eta_out, hipStream_t s);
+// g_out[i][a] = the Gumbel variate of action a of root states[i] on the stream (seed, game_ids[i], stones(states[i])), 0 for an invalid action
+// and for every action when temp_is_zero: what a Gumbel move's baseline stores for that root (all device pointers)
+void launch_gumbel_values(int game, int n, uint64_t seed, const uint64_t* game_ids, const ulonglong2* states, bool temp_is_zero, float* g_out, hipStream_t s);
 // get_action_prob's epilogue for each request with its own temperature and RNG stream (root_policy), plus its status word
 void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s);
 // what one get_action_prob call hands back besides pi / counts / q: written into PINNED host memory by k_call_readback

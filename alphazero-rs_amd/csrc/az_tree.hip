@@ -9,9 +9,14 @@
 // src/coach.rs:104-157; with the repairs of SURVEY.md section 0.2 (tagged S#/B#).
 #include "az_tree.h"
 #include "az_noise.h"
+#include "az_gumbel.h"
 
 namespace az {
 static_assert(NOISE_PURPOSE == RNG_NOISE, "az_noise.h restates the purpose word of az_common.h");
+static_assert(GUMBEL_PURPOSE == RNG_GUMBEL, "az_gumbel.h restates the purpose word of az_common.h");
+// THE ROOT RULE of a search: one template axis with three values (forced playouts and Gumbel exclude each other, az_engine.hip), so the
+// kernels that carry it exist three times, not four
+enum RootRule : int { RR_NONE = 0, RR_FORCED = 1, RR_GUMBEL = 2 };
 
 // ---- lane-group primitives (GW = Game::GROUP lanes per tree) ------------------------------------------------------
 template <int GW> AZ_D uint32_t gshfl(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src, GW); }
@@ -323,11 +328,65 @@ AZ_D bool move_noisy(const TreeDev& t, int g) { return !t.cap.word || (t.cap.wor
 // Forced playouts (az_tree.h ForcedPlayouts): the same moves -- every move without a cap, the full ones with it.  Only FP code reads this.
 AZ_D bool move_forced(const TreeDev& t, int g) { return move_noisy(t, g); }
 
+// ---- Gumbel root search (az_gumbel.h; only the RR_GUMBEL / GZ instantiations of the kernels contain it) ------------------------------------
+// A GUMBEL MOVE is every move that can carry root noise (move_noisy).  Its BASELINE is taken where the noise is mixed in -- once per move,
+// after the root has its prior and before the first selection: lane sub < nchild stores the resolved visit count of its root child and the
+// child's Gumbel variate (16 + 32 bytes per tree).  s = the root's state, cb = its child block.
+template <class G>
+AZ_D void gumbel_capture(const TreeDev& t, int g, size_t base, typename G::State s, uint32_t nchild, uint32_t cb, int sub) {
+    uint32_t n = 0u;
+    float gv = 0.0f;
+    if ((uint32_t)sub < nchild) {
+        const NodeRec cr = node_load(node_ptr(t, base, cb + (uint32_t)sub));
+        const uint64_t cc = cr.link != NONE ? node_ctr(node_ptr(t, base, cr.link)) : cr.ctr;
+        n = ctr_n(cc);
+        uint64_t seed = t.gumbel.seed, game_id;
+        if (t.gumbel.stream) { const ulonglong2 st = t.gumbel.stream[g]; seed = st.x; game_id = st.y; }
+        else game_id = t.gumbel.first_game_id + (uint64_t)(t.gumbel.row ? t.gumbel.row[g] : g);
+        const uint32_t ply = G::stones(s);
+        gv = gumbel_variate(seed, game_id, (uint64_t)ply, cr.meta & META_A_MASK, (int32_t)ply + 1 >= t.gumbel.temp_threshold);
+    }
+    ((uint16_t*)t.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub] = (uint16_t)n;
+    t.gumbel.g[(size_t)g * BLOCK_SLOTS + sub] = gv;
+}
+// what lane sub of a Gumbel move's root holds besides its child's counters: the slot's visits in this move and its variate
+struct GumbelLane { uint32_t d; float g; };
+AZ_D GumbelLane gumbel_lane(const TreeDev& t, int g, uint32_t nchild, uint32_t n, int sub) {
+    GumbelLane r{0u, 0.0f};
+    if ((uint32_t)sub < nchild) {
+        r.d = (n - (uint32_t)((const uint16_t*)t.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub]) & 0xFFFFu;
+        r.g = t.gumbel.g[(size_t)g * BLOCK_SLOTS + sub];
+    }
+    return r;
+}
+// sigma of lane sub's slot: v_mix and max n over the slots in ascending order (group shuffles); *sum_d = t, *max_d = the largest d
+template <class G>
+AZ_D float gumbel_sigma_lane(const TreeDev& t, uint32_t nchild, uint32_t n, float q, float p, uint32_t d, uint32_t* sum_d, uint32_t* max_d) {
+    constexpr int GW = G::GROUP;
+    GumbelMix mx{0.0f, 0.0f};
+    uint32_t max_n = 0u, sd = 0u, md = 0u;
+#pragma unroll
+    for (int j = 0; j < G::ACTIONS; ++j) {
+        const uint32_t nj = gshfl<GW>(n, j), dj = gshfl<GW>(d, j);
+        const float pj = gshflf<GW>(p, j), qj = gshflf<GW>(q, j);
+        if ((uint32_t)j < nchild) {
+            gumbel_mix_add(mx, pj, qj, nj);
+            max_n = nj > max_n ? nj : max_n;
+            sd += dj;
+            md = dj > md ? dj : md;
+        }
+    }
+    *sum_d = sd;
+    *max_d = md;
+    return gumbel_sigma(t.gumbel.c_visit, t.gumbel.c_scale, max_n, n, q, gumbel_vmix(mx));
+}
+
 // ---- get_action_prob prologue: root lookup (src/async_mcts.rs:81) + S10 + S1 -------------
 // NZ: root noise is on.  A root that already has its prior gets the noise here; one that is evaluated first (LEAF_ROOT) gets it in its
 // backup, right after the prior is stored -- once per get_action_prob either way, before the call's first selection.
 // noisy (read by the NZ instantiations only): this tree's move gets the noise (false: a fast move under a playout cap)
-template <class G, bool NZ = false>
+// GZ (Gumbel root search): the move's baseline is taken here too, on the same moves (`noisy`)
+template <class G, bool NZ = false, bool GZ = false>
 AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ulonglong2* root_states, int g, int sub, bool noisy = true) {
     const bool act = h.active != 0;
     size_t base = (size_t)g * t.R;
@@ -358,13 +417,16 @@ AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ul
                 if (sub == 0) atomicOr(&t.err[ERR_TERMINAL_ROOT], 1u);
             } else if (!(meta & META_HAS_PRIOR)) {
                 kind = LEAF_ROOT;  // S1 (A1): evaluate the root once so best_child has a prior (not a simulation: nothing is backed up)
-            } else if (NZ && noisy) {
+            } else if ((NZ || GZ) && noisy) {
                 const NodeRec rr = node_load(node_ptr(t, base, root));
                 const uint32_t nchild = (rr.meta >> META_NCHILD_SHIFT) & 7u;
-                uint4* cp = node_ptr(t, base, rr.child_base + ((uint32_t)sub < nchild ? (uint32_t)sub : 0u));
-                const NodeRec cr = node_load(cp);
-                const float mixed = root_noise_mix<G>(t, g, s, nchild, cr.meta & META_A_MASK, __uint_as_float(cr.prior), sub);
-                if ((uint32_t)sub < nchild) node_set_prior(cp, __float_as_uint(mixed));
+                if constexpr (NZ) {
+                    uint4* cp = node_ptr(t, base, rr.child_base + ((uint32_t)sub < nchild ? (uint32_t)sub : 0u));
+                    const NodeRec cr = node_load(cp);
+                    const float mixed = root_noise_mix<G>(t, g, s, nchild, cr.meta & META_A_MASK, __uint_as_float(cr.prior), sub);
+                    if ((uint32_t)sub < nchild) node_set_prior(cp, __float_as_uint(mixed));
+                }
+                if constexpr (GZ) gumbel_capture<G>(t, g, base, s, nchild, rr.child_base, sub);
             }
         }
         h.root = (root == NONE) ? 0u : root;
@@ -377,7 +439,7 @@ AZ_D typename G::State root_prepare_body(const TreeDev& t, TreeHead& h, const ul
     return s;
 }
 
-template <class G, bool NZ, bool MIR>
+template <class G, bool NZ, bool MIR, bool GZ>
 __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, EvalCache ec, const ulonglong2* root_states) {
     constexpr int GW = G::GROUP;
     int tid = blockIdx.x * 64 + threadIdx.x;
@@ -385,8 +447,8 @@ __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, Ev
     if (g >= t.G) return;
     TreeHead h = head_load(t, g);
     bool noisy = true;
-    if constexpr (NZ) noisy = move_noisy(t, g);
-    const typename G::State s = root_prepare_body<G, NZ>(t, h, root_states, g, sub, noisy);
+    if constexpr (NZ || GZ) noisy = move_noisy(t, g);
+    const typename G::State s = root_prepare_body<G, NZ, GZ>(t, h, root_states, g, sub, noisy);
     const uint32_t src = leaf_request<G, MIR>(eb, ec, h.leaf_kind == LEAF_ROOT, s, sub);
     if (h.leaf_kind == LEAF_ROOT) h.src = src;
     if (sub == 0) head_store(t, g, h);
@@ -403,8 +465,10 @@ __global__ __launch_bounds__(64) void k_root_prepare(TreeDev t, EvalBatch eb, Ev
 // go = false (playout cap only): the tree's move has had its budget -- nothing is selected, the tree asks for no leaf
 // FP (forced playouts, az_forced.h): at the FIRST level of the simulation -- the node is the call's root -- a child that has been visited and
 // is still short of nf = sqrt(k * p * S) gets u = +inf; the arg-max, the Locked filter (C8), S11 and S12 then run on the u as written.
-// forced (read by the FP instantiations only): this tree's move is a forced move (false: a fast move under a playout cap)
-template <class G, bool MT = false, bool FP = false>
+// forced (read by the RR != RR_NONE instantiations only): this tree's move is a forced / Gumbel move (false: a fast move under a playout cap)
+// RR_GUMBEL (az_gumbel.h): at the first level the children's u is s_j = (g_j + l_j) + sigma_j for the slots whose visits in this move equal
+// the considered visit count c(t), -inf for the others; PUCT does not decide there.  Every level below the root is unchanged.
+template <class G, bool MT = false, int RR = RR_NONE>
 AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth, const SearchParams& sp, int g, int sub, uint32_t* path,
                                    uint32_t* abandoned = nullptr, bool go = true, bool forced = true) {
     constexpr int GW = G::GROUP;
@@ -422,11 +486,19 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
     // two.  Only the root and link targets (canonical nodes living elsewhere) are fetched by slot.
     NodeRec pr{};
     bool have_pr = false;
-    bool at_root = true;                                        // FP only: the loop's first pass
+    bool at_root = true;                                        // RR only: the loop's first pass
+    uint32_t gz_relink = NONE;                                  // RR_GUMBEL only: the root slot whose placeholder this simulation just turned into a link
     while (act) {
         uint4* pp = node_ptr(t, base, cur);
         if (!have_pr) pr = node_load(pp);
         have_pr = false;
+        if constexpr (RR == RR_GUMBEL) {
+            // the slot's visits before this move are those of the node it now resolves to, not the placeholder's 0 the baseline took
+            if (gz_relink != NONE) {
+                if ((uint32_t)sub == gz_relink) ((uint16_t*)t.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub] = (uint16_t)ctr_n(pr.ctr);
+                gz_relink = NONE;
+            }
+        }
         if constexpr (MT) { if (pr.meta & META_LOCKED) { give_up = true; cur_visited = false; break; } }   // S12
         const uint64_t pc = pr.ctr + CTR_VISIT;                 // visit(), src/node.rs:77-80; S5: before the checks
         if (sub == 0) node_set_ctr(pp, pc);
@@ -438,7 +510,8 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
         const float sq = puct_sqrt_parent(ctr_n(pc));
         NodeRec cr{0ull, 0u, 0u, NONE, 0u};
         float u = 0.0f;
-        uint32_t fn = 0u;                                       // FP only: this lane's n_j (0 beyond nchild)
+        uint32_t fn = 0u;                                       // RR only: this lane's n_j (0 beyond nchild)
+        float fq = 0.0f;                                        // RR_GUMBEL only: this lane's q_j
         if ((uint32_t)sub < nchild) {
             // the child's record carries its own counter; only a link slot needs the second, dependent fetch of the
             // canonical node's counter (resolve(), src/node.rs:179-193)
@@ -446,9 +519,22 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
             uint64_t cc = cr.ctr;
             if (cr.link != NONE) cc = node_ctr(node_ptr(t, base, cr.link));
             u = puct(cc, __uint_as_float(cr.prior), sq, sp.cpuct_f);
-            if constexpr (FP) fn = ctr_n(cc);
+            if constexpr (RR != RR_NONE) fn = ctr_n(cc);
+            if constexpr (RR == RR_GUMBEL) fq = ctr_q(cc);
         }
-        if constexpr (FP) {
+        if constexpr (RR == RR_GUMBEL) {
+            if (at_root && forced) {
+                const GumbelLane gl = gumbel_lane(t, g, nchild, fn, sub);
+                const float p = __uint_as_float(cr.prior);
+                uint32_t tt, md;
+                const float sigma = gumbel_sigma_lane<G>(t, nchild, fn, fq, p, gl.d, &tt, &md);
+                const uint32_t m_eff = t.gumbel.m < nchild ? t.gumbel.m : nchild;
+                const uint32_t want = gumbel_considered_visit(m_eff, t.gumbel.num_sims, tt);
+                u = ((uint32_t)sub < nchild && gl.d == want) ? gumbel_score(gl.g, gumbel_logit(p), sigma) : -__builtin_inff();
+            }
+            at_root = false;
+        }
+        if constexpr (RR == RR_FORCED) {
             if (at_root && forced) {
                 uint32_t S = 0u;
 #pragma unroll
@@ -508,6 +594,7 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
         hash_find<G>(t, g, base, s2, sub, &found, &ins);
         if (found != NONE) {                                    // upgrade -> Some(false): become a link (src/node.rs:285-289)
             if (sub == 0) node_set_word(node_ptr(t, base, cslot), cmeta, found, 0u);
+            if constexpr (RR == RR_GUMBEL) { if (plen == 1u && forced) gz_relink = best; }      // (plen == 1: still the first pass, the node is the root)
             cur = found;
             ++n_link;
             continue;                                           // :297-298
@@ -601,7 +688,8 @@ AZ_D void cache_claim_finish(const EvalCache& ec, CacheClaim c, float pv, int su
 // ---- mask/renormalise/store the prior (src/async_mcts.rs:317-353) + backup (:361-370) ----
 // INLINE_PV: the leaf's (pi, v) row is handed over in a register (pv_in: lane a < ACTIONS holds pi[a], lane ACTIONS holds v)
 // instead of being read through TreeHead.src -- the fused search of the fixture nets.
-template <class G, bool INLINE_PV = false, bool NZ = false, bool MIR = false>
+// GZ (Gumbel root search): the root's own evaluation is also where the move's baseline is taken (gumbel_capture), on the same moves
+template <class G, bool INLINE_PV = false, bool NZ = false, bool MIR = false, bool GZ = false>
 AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const EvalBatch& eb, const EvalCache& ec, int g,
                       int sub, const uint32_t* path, float pv_in = 0.0f, bool noisy = true /*NZ only: see root_prepare_body*/) {
     constexpr int GW = G::GROUP;
@@ -671,6 +759,7 @@ AZ_D void backup_body(const TreeDev& t, TreeHead& h, const PathRegs& pth, const 
         if constexpr (NZ) { if (apply_only && noisy) pa = root_noise_mix<G>(t, g, s, nchild, myact, pa, sub); }      // the root's own evaluation: mix the noise in
         if ((uint32_t)sub < nchild) node_set_prior(node_ptr(t, base, cb + sub), __float_as_uint(pa));   // set_policy, :348
         if (sub == 0) node_set_word(lp, (lr.meta | META_HAS_PRIOR) & ~META_LOCKED, lr.link, lr.child_base);      // set_policy + unlock, :348-351
+        if constexpr (GZ) { if (apply_only && noisy) gumbel_capture<G>(t, g, base, s, nchild, cb, sub); }
         h.stat[ST_LEAF_EVALS] += 1;
         val = -v;                                                   // :353 (C9)
     } else {
@@ -700,9 +789,12 @@ struct RootPolicy {
     float pi;        // this lane's action (sub < ACTIONS)
     uint32_t count;
     float q;
+    int32_t sel;     // RR_GUMBEL on a Gumbel move: the selected action (the same in every lane); else -1
 };
-// FP && forced && t.forced.prune (policy target pruning, az_forced.h): pi is formed from the PRUNED counts; count and q stay raw
-template <class G, bool FP = false>
+// RR_FORCED && forced && t.forced.prune (policy target pruning, az_forced.h): pi is formed from the PRUNED counts; count and q stay raw
+// RR_GUMBEL && forced (az_gumbel.h): pi = softmax(l + sigma) over the root's slots and sel = the selected action; count and q stay raw,
+// temp and the tie-break stream are not used
+template <class G, int RR = RR_NONE>
 AZ_D RootPolicy root_policy(const TreeDev& t, uint32_t root, int g, int sub, float temp, uint64_t seed, uint64_t game_id, uint64_t ply,
                             bool forced = true) {
     constexpr int GW = G::GROUP;
@@ -718,17 +810,53 @@ AZ_D RootPolicy root_policy(const TreeDev& t, uint32_t root, int g, int sub, flo
         ca = cr.meta & META_A_MASK;                                 // B3: the slot's own action
         cn = ctr_n(cc);
         cq = ctr_q(cc);
-        if constexpr (FP) cp = __uint_as_float(cr.prior);
+        if constexpr (RR != RR_NONE) cp = __uint_as_float(cr.prior);
     }
-    RootPolicy out{0.0f, 0u, 0.0f};
+    RootPolicy out{0.0f, 0u, 0.0f, -1};
 #pragma unroll
     for (int j = 0; j < NA; ++j) {                                  // counts[a] = n, :88-94
         uint32_t aj = gshfl<GW>(ca, j), nj = gshfl<GW>(cn, j);
         float qj = gshflf<GW>(cq, j);
         if ((uint32_t)j < nchild && aj == (uint32_t)sub) { out.count = nj; out.q = qj; }
     }
+    if constexpr (RR == RR_GUMBEL) {
+        if (forced) {
+            const bool in = (uint32_t)sub < nchild;
+            const GumbelLane gl = gumbel_lane(t, g, nchild, cn, sub);
+            uint32_t tt, md;
+            const float sigma = gumbel_sigma_lane<G>(t, nchild, cn, cq, cp, gl.d, &tt, &md);
+            const float l = gumbel_logit(cp);
+            const float x = gumbel_x(l, sigma);
+            const float u = (in && gl.d == md) ? gumbel_score(gl.g, l, sigma) : -__builtin_inff();
+            float max_x = gshflf<GW>(x, 0);
+            uint32_t best = 0;
+            float bu = gshflf<GW>(u, 0);
+#pragma unroll
+            for (int j = 1; j < NA; ++j) {
+                const float xj = gshflf<GW>(x, j), uj = gshflf<GW>(u, j);
+                if ((uint32_t)j < nchild && xj > max_x) max_x = xj;
+                if ((uint32_t)j < nchild && !(bu > uj)) { best = (uint32_t)j; bu = uj; }
+            }
+            const float e = in ? gumbel_softmax_term(x, max_x) : 0.0f;
+            float sum = 0.0f;
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                const float ej = gshflf<GW>(e, j);
+                if ((uint32_t)j < nchild) sum = __fadd_rn(sum, ej);
+            }
+            const float ps = __fdiv_rn(e, sum);
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                const uint32_t aj = gshfl<GW>(ca, j);
+                const float pj = gshflf<GW>(ps, j);
+                if ((uint32_t)j < nchild && aj == (uint32_t)sub) out.pi = pj;
+            }
+            out.sel = (int32_t)gshfl<GW>(ca, (int)best);
+            return out;
+        }
+    }
     uint32_t pcount = out.count;                                    // what pi is formed from: the raw count, or ...
-    if constexpr (FP) {
+    if constexpr (RR == RR_FORCED) {
         if (forced && t.forced.prune) {                             // ... the pruned one
             uint32_t S = 0u, b = 0u, bn = 0u;
 #pragma unroll
@@ -775,7 +903,7 @@ AZ_D void clear_election_keys(const EvalBatch& eb) {
     const uint32_t total = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= eb.tmask; i += total) eb.tkey[i] = 0ull;
 }
-template <class G, bool NZ, bool MIR>
+template <class G, bool NZ, bool MIR, bool GZ>
 __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCache ec) {
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * 64 + threadIdx.x;
@@ -786,8 +914,8 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
     TreeHead h = head_load(t, g);
     const PathRegs pth = path_load(t, g, sub);
     bool noisy = true;
-    if constexpr (NZ) noisy = move_noisy(t, g);
-    backup_body<G, false, NZ, MIR>(t, h, pth, eb, ec, g, sub, t.path + (size_t)g * PATH_CAP, 0.0f, noisy);
+    if constexpr (NZ || GZ) noisy = move_noisy(t, g);
+    backup_body<G, false, NZ, MIR, GZ>(t, h, pth, eb, ec, g, sub, t.path + (size_t)g * PATH_CAP, 0.0f, noisy);
     h.leaf_kind = LEAF_NONE;
     if (sub == 0) head_store(t, g, h);
 }
@@ -798,8 +926,8 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
 // PC (playout cap): TreeHead.active carries the simulations the tree's move has left (1 | left << 1); a tree with none left selects nothing
 // and requests no leaf for the rest of the round -- its last backup above still runs, and its lanes still go through leaf_request's
 // workgroup-wide row claim as an inactive tree's do.  So a replayed graph chunk in which some trees are done is correct as it is.
-// FP (forced playouts): select_body's forced branch at the root, on the tree's forced moves
-template <class G, bool STAMP, bool NZ, bool MIR, bool PC, bool FP>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
+// RR (the root rule): select_body's forced / Gumbel branch at the root, on the tree's forced / Gumbel moves
+template <class G, bool STAMP, bool NZ, bool MIR, bool PC, int RR>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
 __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec,
                                                        SearchParams sp, unsigned long long* dbg) {
     constexpr int GW = G::GROUP;
@@ -814,9 +942,10 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     TreeHead h = head_load(t, g);
     PathRegs pth = path_load(t, g, sub);
     AZ_TSTAMP(1);
+    constexpr bool GZ = RR == RR_GUMBEL;
     bool noisy = true;
-    if constexpr (NZ) noisy = move_noisy(t, g);
-    backup_body<G, false, NZ, MIR>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * PATH_CAP, 0.0f, noisy);
+    if constexpr (NZ || GZ) noisy = move_noisy(t, g);
+    backup_body<G, false, NZ, MIR, GZ>(t, h, pth, eb_prev, ec, g, sub, t.path + (size_t)g * PATH_CAP, 0.0f, noisy);
     AZ_TSTAMP(2);
     // the counters this tree's other lanes just wrote are read by the selection below
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -826,8 +955,8 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     bool go = true;
     if constexpr (PC) go = (h.active >> 1) != 0u;
     bool forced = true;
-    if constexpr (FP) forced = move_forced(t, g);
-    const typename G::State leaf_s = select_body<G, false, FP>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, go, forced);
+    if constexpr (RR != RR_NONE) forced = move_forced(t, g);
+    const typename G::State leaf_s = select_body<G, false, RR>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, go, forced);
     if constexpr (PC) { if (go) h.active -= 2u; }
     AZ_TSTAMP(4);
     const uint32_t src = leaf_request<G, MIR>(eb_next, ec, h.leaf_kind == LEAF_EVAL, leaf_s, sub);
@@ -912,7 +1041,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
         bool want = false;
         typename G::State leaf_s = G::init();
         if (go) {
-            leaf_s = select_body<G, true, FP>(t, h, pth, sp, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP, &abandoned, true, forced);
+            leaf_s = select_body<G, true, FP ? RR_FORCED : RR_NONE>(t, h, pth, sp, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP, &abandoned, true, forced);
             want = h.leaf_kind == LEAF_EVAL;
         }
         const uint32_t src = leaf_request<G, MIR>(eb_next, ec, want, leaf_s, sub);      // every wave calls it T times (wave-wide ballots inside)
@@ -952,7 +1081,7 @@ AZ_D float fixture_row(typename G::State s, int kind, uint64_t salt, int sub) {
     return out;
 }
 // PC (playout cap): tree g runs the budget of its own move, t.cap.word[g], instead of num_sims
-template <class G, bool NZ, bool PC, bool FP>
+template <class G, bool NZ, bool PC, int RR>
 __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind,
                                                        uint64_t salt) {
     constexpr int GW = G::GROUP;
@@ -963,26 +1092,27 @@ __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglon
     const EvalCache no_ec{};
     TreeHead h = head_load(t, g);
     PathRegs pth{0u, 0u};
+    constexpr bool GZ = RR == RR_GUMBEL;
     bool noisy = true;
-    if constexpr (NZ) noisy = move_noisy(t, g);
+    if constexpr (NZ || GZ) noisy = move_noisy(t, g);
     if constexpr (PC) num_sims = (int)(t.cap.word[g] & ~PLAYOUT_FULL_BIT);
     bool forced = true;
-    if constexpr (FP) forced = move_forced(t, g);
-    typename G::State ls = root_prepare_body<G, NZ>(t, h, root_states, g, sub, noisy);
+    if constexpr (RR != RR_NONE) forced = move_forced(t, g);
+    typename G::State ls = root_prepare_body<G, NZ, GZ>(t, h, root_states, g, sub, noisy);
     for (int i = 0; i <= num_sims; ++i) {
         group_memory_sync();
         // backup of the previous leaf (i == 0: the root's priors only, S1), then the next selection
         const float pv = (h.leaf_kind == LEAF_EVAL || h.leaf_kind == LEAF_ROOT) ? fixture_row<G>(ls, kind, salt, sub) : 0.0f;
-        backup_body<G, true, NZ>(t, h, pth, no_eb, no_ec, g, sub, t.path + (size_t)g * PATH_CAP, pv, noisy);
+        backup_body<G, true, NZ, false, GZ>(t, h, pth, no_eb, no_ec, g, sub, t.path + (size_t)g * PATH_CAP, pv, noisy);
         if (i == num_sims) break;
         group_memory_sync();
-        ls = select_body<G, false, FP>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, true, forced);
+        ls = select_body<G, false, RR>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, true, forced);
     }
     h.leaf_kind = LEAF_NONE;
     if (sub == 0) head_store(t, g, h);
 }
 
-template <class G, bool FP>
+template <class G, int RR>
 __global__ __launch_bounds__(64) void k_root_policy(TreeDev t, float temp, uint64_t seed, uint64_t first_game_id,
                                                     float* pi, uint16_t* counts, float* q) {
     constexpr int GW = G::GROUP;
@@ -993,7 +1123,8 @@ __global__ __launch_bounds__(64) void k_root_policy(TreeDev t, float temp, uint6
     const TreeHead h = head_load(t, g);
     if (!h.active) return;
     const typename G::State s = G::unpack(node_key(t, (size_t)g * t.R, h.root));
-    RootPolicy rp = root_policy<G, FP>(t, h.root, g, sub, temp, seed, first_game_id + (uint64_t)g, (uint64_t)G::stones(s));
+    RootPolicy rp = root_policy<G, RR>(t, h.root, g, sub, temp, seed, first_game_id + (uint64_t)g, (uint64_t)G::stones(s));
+    if constexpr (RR == RR_GUMBEL) { if (sub == 0) t.gumbel.selected[g] = rp.sel; }      // az_tree_get_selected
     if (sub < NA) {
         pi[(size_t)g * NA + sub] = rp.pi;
         if (counts) counts[(size_t)g * NA + sub] = (uint16_t)rp.count;
@@ -1049,6 +1180,20 @@ __global__ __launch_bounds__(64) void k_root_noise_eta(int n, uint64_t seed, con
     if (sub < NA) eta_out[(size_t)i * NA + sub] = mine;
 }
 
+// az_gumbel_values: the variates alone, lane a of a root's 8 lanes holds action a
+template <class G>
+__global__ __launch_bounds__(64) void k_gumbel_values(int n, uint64_t seed, const uint64_t* __restrict__ game_ids, const ulonglong2* __restrict__ states,
+                                                      bool temp_is_zero, float* __restrict__ g_out) {
+    constexpr int GW = G::GROUP;
+    constexpr int NA = G::ACTIONS;
+    const int tid = blockIdx.x * 64 + threadIdx.x;
+    const int i = tid / GW, sub = tid % GW;
+    if (i >= n || sub >= NA) return;
+    const typename G::State s = states[i];
+    const bool valid = (G::valid_mask(s) >> sub) & 1u;
+    g_out[(size_t)i * NA + sub] = valid ? gumbel_variate(seed, game_ids[i], (uint64_t)G::stones(s), (uint32_t)sub, temp_is_zero) : 0.0f;
+}
+
 // k_root_policy per REQUEST: request i's tree is req[i].slot, its temperature and RNG stream are its own, its answer goes to out[i].
 // status: a failed root (the search left the tree inactive: arena exhausted at the root) or a terminal root is this request's own
 // error; a capacity error raised during the search (t.err) is blamed on every tree of the batch that is that close to full (a tree
@@ -1075,7 +1220,7 @@ __global__ __launch_bounds__(64) void k_slot_root_policy(TreeDev t, const SlotRe
         if (ecd != E_NONE) status = 1u << ERR_TERMINAL_ROOT;
         else if (full_err && (h.len + BLOCK_SLOTS > t.R || h.count + BLOCK_SLOTS > t.reserve_nodes)) status = 1u << ERR_CAPACITY;
         const typename G::State s = G::unpack(node_key(t, base, h.root));
-        rp = root_policy<G, FP>(t, h.root, g, sub, r.temp, r.seed, r.game_id, (uint64_t)G::stones(s));
+        rp = root_policy<G, FP ? RR_FORCED : RR_NONE>(t, h.root, g, sub, r.temp, r.seed, r.game_id, (uint64_t)G::stones(s));
     }
     if (sub < NA) {
         out[i].pi[sub] = rp.pi;
@@ -1135,8 +1280,9 @@ __global__ __launch_bounds__(256) void k_call_readback(unsigned long long* total
 // PC (playout cap): *word = the slot's word for the move being played (az_tree.h PlayoutCap).  The ply's full flag goes into the episode's
 // mask (k_emit_samples compacts to the full plies; pi / state / player are stored by ply either way), the mode of the slot's NEXT move -- the
 // next ply, or ply 0 of the episode a refilled slot gets -- is drawn, and its word is stored and handed back in *word.
-// FP (forced playouts): a forced move's pi -- recorded and sampled from -- is formed from the pruned counts when "policy_prune" is on
-template <class G, bool PC = false, bool FP = false>
+// RR_FORCED (forced playouts): a forced move's pi -- recorded and sampled from -- is formed from the pruned counts when "policy_prune" is on
+// RR_GUMBEL: a Gumbel move records the improved policy and PLAYS the selected action; its RNG_MOVE draw is not used (draws are counter-based)
+template <class G, bool PC = false, int RR = RR_NONE>
 AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, const SelfplayMoveParams& mp, int g, int sub, uint32_t* word = nullptr) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
@@ -1147,8 +1293,8 @@ AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, c
     const uint64_t game_id = mp.first_game_id + (uint64_t)gi;
     const float temp = (ply + 1 < mp.temp_threshold) ? 1.0f : 0.0f;         // :122-126 (episode_step = ply + 1)
     bool forced = true;
-    if constexpr (FP && PC) forced = (*word & PLAYOUT_FULL_BIT) != 0u;
-    RootPolicy rp = root_policy<G, FP>(t, h.root, g, sub, temp, mp.seed, game_id, (uint64_t)ply, forced);   // :128
+    if constexpr (RR != RR_NONE && PC) forced = (*word & PLAYOUT_FULL_BIT) != 0u;
+    RootPolicy rp = root_policy<G, RR>(t, h.root, g, sub, temp, mp.seed, game_id, (uint64_t)ply, forced);   // :128
     const size_t so = (size_t)gi * G::MAX_PLIES + ply;
     if (sub < NA) gd.smp_pi[so * NA + sub] = rp.pi;                         // :130-135 (symmetries regenerated at emit)
     // choose_weighted, :137-138
@@ -1173,6 +1319,7 @@ AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, c
     }
     if (action < 0) action = last;
     if (action < 0) action = 0;
+    if constexpr (RR == RR_GUMBEL) { if (forced) action = rp.sel; }
     const typename G::State s2 = G::play(s, action);                        // :140-142
     const uint32_t ec = G::ended_code(s2);                                  // r = get_game_ended(cur_player), :144
     int status = 0;
@@ -1224,7 +1371,7 @@ AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, c
     if (status == 2) h.active = 0;
     return status;
 }
-template <class G, bool PC, bool FP>
+template <class G, bool PC, int RR>
 __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, SelfplayMoveParams mp) {
     constexpr int GW = G::GROUP;
     int tid = blockIdx.x * 64 + threadIdx.x;
@@ -1235,7 +1382,7 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
     if (gi < 0 || !h.active) return;
     uint32_t word = 0u;
     if constexpr (PC) word = t.cap.word[g];
-    if (selfplay_move_body<G, PC, FP>(t, h, gd, mp, g, sub, &word) == 2 && sub == 0) t.head[g].head.active = 0;
+    if (selfplay_move_body<G, PC, RR>(t, h, gd, mp, g, sub, &word) == 2 && sub == 0) t.head[g].head.active = 0;
 }
 
 // ---- FREE-RUNNING self-play: every slot on its own timeline ("selfplay_async") -------------------------------------------------------
@@ -1292,12 +1439,12 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
                 continue;
             }
             if (sims >= (PC ? (int)(word & ~PLAYOUT_FULL_BIT) : num_sims)) {      // the move (src/coach.rs:128-156), then the next position's root
-                const int st = selfplay_move_body<G, PC, FP>(t, h, gd, mp, g, sub, &word);
+                const int st = selfplay_move_body<G, PC, FP ? RR_FORCED : RR_NONE>(t, h, gd, mp, g, sub, &word);
                 sims = -1;
                 if (st != 0) break;                                            // episode over: idle, or wait for k_reset_trees
                 continue;
             }
-            leaf_s = select_body<G, false, FP>(t, h, pth, sp, g, sub, path, nullptr, true, !PC || (word & PLAYOUT_FULL_BIT) != 0u);
+            leaf_s = select_body<G, false, FP ? RR_FORCED : RR_NONE>(t, h, pth, sp, g, sub, path, nullptr, true, !PC || (word & PLAYOUT_FULL_BIT) != 0u);
             if (h.leaf_kind == LEAF_EVAL) { want = true; break; }
             if (h.leaf_kind == LEAF_NONE) ++sims;                              // an error cut the simulation short (flag set): it still counts
         }
@@ -1461,6 +1608,19 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
         if ((t_).forced.k != 0.0f) { constexpr bool FP = true; __VA_ARGS__; }            \
         else { constexpr bool FP = false; __VA_ARGS__; }                                 \
     } while (0)
+// ... and per root rule: Gumbel while the entry point's Gumbel record has m != 0, else forced playouts while k != 0 (the two exclude
+// each other), else today's kernels.  GZ = the baseline capture of a Gumbel move in the kernels that carry no selection.
+#define AZ_FOR_RR(t_, ...)                                                               \
+    do {                                                                                 \
+        if ((t_).gumbel.m != 0u) { constexpr int RR = RR_GUMBEL; __VA_ARGS__; }          \
+        else if ((t_).forced.k != 0.0f) { constexpr int RR = RR_FORCED; __VA_ARGS__; }   \
+        else { constexpr int RR = RR_NONE; __VA_ARGS__; }                                \
+    } while (0)
+#define AZ_FOR_GZ(t_, ...)                                                               \
+    do {                                                                                 \
+        if ((t_).gumbel.m != 0u) { constexpr bool GZ = true; __VA_ARGS__; }              \
+        else { constexpr bool GZ = false; __VA_ARGS__; }                                 \
+    } while (0)
 static inline int group_blocks(int G) { return (G * BLOCK_SLOTS + 63) / 64; }
 #ifdef AZ_DIAG
 // diagnostic library only: the PUCT term of best_child (src/node.rs:352-356) for n (child counter, prior bits, parent N) triples, as the
@@ -1506,10 +1666,10 @@ void launch_reset_trees(const TreeDev& t, const uint8_t* flags, hipStream_t s, c
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_reset_trees<TG>, dim3(t.G), dim3(256), 0, s, t, flags, const_cast<uint8_t*>(flags), roots));
 }
 void launch_root_prepare(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, const ulonglong2* root_states, hipStream_t s) {
-    AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_root_prepare<TG, NZ, MIR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec, root_states));
+    AZ_FOR_GZ(t, AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_root_prepare<TG, NZ, MIR, GZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec, root_states)));
 }
 void launch_backup(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, hipStream_t s) {
-    AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_backup<TG, NZ, MIR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec));
+    AZ_FOR_GZ(t, AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_backup<TG, NZ, MIR, GZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec)));
 }
 void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                           hipStream_t s) {
@@ -1517,11 +1677,11 @@ void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const Eval
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
 #ifdef AZ_DIAG
     if (g_tree_dbg && t.G * 8 / 64 <= TREE_DBG_WAVES) {
-        AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR, PC, FP>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg))));
+        AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR, PC, RR>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg))));
         return;
     }
 #endif
-    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR, PC, FP>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr))));
+    AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR, PC, RR>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr))));
 }
 void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                     int first, int last, hipStream_t s) {
@@ -1530,11 +1690,11 @@ void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch&
 }
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s) {
-    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ, PC, FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt))));
+    AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ, PC, RR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt))));
 }
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,
                         uint16_t* counts, float* q, hipStream_t s) {
-    AZ_FOR_FP(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_root_policy<TG, FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, temp, seed, first_game_id, pi, counts, q)));
+    AZ_FOR_RR(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_root_policy<TG, RR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, temp, seed, first_game_id, pi, counts, q)));
 }
 void launch_slot_arm(const TreeDev& t, const SlotReq* req, int n, ulonglong2* roots, uint8_t* reset_flags, hipStream_t s, ulonglong2* streams) {
     hipLaunchKernelGGL(k_slot_arm, dim3(1), dim3(1024), 0, s, t, req, n, roots, reset_flags, streams);
@@ -1545,6 +1705,10 @@ void launch_noise_streams(ulonglong2* streams, int n, uint64_t seed, uint64_t fi
 void launch_root_noise_eta(int game, int n, uint64_t seed, const uint64_t* game_ids, const ulonglong2* states, float alpha, float* eta_out, hipStream_t s) {
     if (n <= 0) return;
     AZ_FOR_GAME(game, hipLaunchKernelGGL(k_root_noise_eta<TG>, dim3(group_blocks(n)), dim3(64), 0, s, n, seed, game_ids, states, alpha, eta_out));
+}
+void launch_gumbel_values(int game, int n, uint64_t seed, const uint64_t* game_ids, const ulonglong2* states, bool temp_is_zero, float* g_out, hipStream_t s) {
+    if (n <= 0) return;
+    AZ_FOR_GAME(game, hipLaunchKernelGGL(k_gumbel_values<TG>, dim3(group_blocks(n)), dim3(64), 0, s, n, seed, game_ids, states, temp_is_zero, g_out));
 }
 void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s) {
     if (n <= 0) return;
@@ -1558,7 +1722,7 @@ void launch_call_readback(unsigned long long* totals, unsigned long long* dd_sta
     hipLaunchKernelGGL(k_call_readback, dim3(1), dim3(256), 0, s, totals, dd_stat, err, out);
 }
 void launch_selfplay_move(const TreeDev& t, const GamesDev& gd, SelfplayMoveParams mp, hipStream_t s) {
-    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_selfplay_move<TG, PC, FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, mp))));
+    AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_selfplay_move<TG, PC, RR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, mp))));
 }
 void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s) {

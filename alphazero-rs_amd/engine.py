@@ -90,7 +90,7 @@ EXPORTS = [
     "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
-    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
+    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_tree_get_selected", "az_gumbel_values", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
     "az_arena_set_opening_book", "az_arena_get_openings",
     "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
@@ -142,6 +142,8 @@ def load_library(path=LIB_PATH):
         "az_tree_slot_error": (C.c_char_p, [vp, i32]),
         "az_tree_share_stats": (i32, [vp, vp]),
         "az_root_noise_eta": (i32, [vp, i32, u64, vp, vp, vp]),
+        "az_tree_get_selected": (i32, [vp, vp]),
+        "az_gumbel_values": (i32, [vp, i32, u64, vp, vp, i32, vp]),
         "az_selfplay": (i32, [vp, C.POINTER(az_selfplay_params), C.POINTER(az_samples)]),
         "az_selfplay_begin": (i32, [vp, C.POINTER(az_selfplay_params)]),
         "az_selfplay_next": (i32, [vp, C.c_int32, C.POINTER(az_samples)]),
@@ -349,6 +351,16 @@ class Engine:
         self.set_option("policy_prune", 1 if prune else 0)
         self.set_option("forced_playouts_k_e6", int(round(float(k) * 1e6)))
 
+    def set_gumbel(self, m, c_visit=50.0, c_scale=1.0):
+        """Gumbel root search with sequential halving (Danihelka et al. 2022) on every move root noise can apply to -- lock-step self-play
+        and az_tree_get_action_prob, under a playout cap the full moves only, never the arena or the slot calls.  The root samples at most
+        m actions without replacement through Gumbel noise, spends the budget by sequential halving, plays the winner and records
+        softmax(logits + sigma(completed Q)) as pi.  m = 0 switches it off (the default); the values travel as "gumbel_m" /
+        "gumbel_c_visit_e6" / "gumbel_c_scale_e6" (include/az_engine.h)."""
+        self.set_option("gumbel_c_visit_e6", int(round(float(c_visit) * 1e6)))
+        self.set_option("gumbel_c_scale_e6", int(round(float(c_scale) * 1e6)))
+        self.set_option("gumbel_m", int(m))
+
     def set_arena_openings(self, plies):
         """Paired arena openings (never self-play or the tree calls): arena game g and its seat-swapped twin g + total/2 start from the
         same position, `plies` random quiet plies (even, 2 .. 12) played onto the pair's base -- the opening book's entry, start_board or
@@ -388,6 +400,16 @@ class Engine:
         self._check(self._lib.az_root_noise_eta(self._h, s.shape[0], seed, _ptr(g), _ptr(s), _ptr(eta)))
         return eta
 
+    def gumbel_values(self, states, game_ids, seed=0, temp_is_zero=False):
+        """az_gumbel_values: g [n,7] the device draws for root states [n,2] on the streams (seed, game_ids[i], stones); 0 for invalid
+        actions, and everywhere when temp_is_zero."""
+        s = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, 2)
+        g = np.ascontiguousarray(game_ids, dtype=np.uint64).reshape(-1)
+        assert g.shape[0] == s.shape[0]
+        out = np.empty((s.shape[0], ACTIONS), np.float32)
+        self._check(self._lib.az_gumbel_values(self._h, s.shape[0], seed, _ptr(g), _ptr(s), 1 if temp_is_zero else 0, _ptr(out)))
+        return out
+
     # ---- stats ----
     def stats(self):
         s = az_stats()
@@ -400,6 +422,10 @@ class Engine:
     # ---- AsyncMcts ----
     def tree_create(self, n_games, reserve, num_sims, max_depth, model_id, cpuct, num_threads=1):
         return TreeBatch(self, n_games, reserve, num_sims, max_depth, model_id, cpuct, num_threads)
+
+    def tree_selected(self, tree):
+        """az_tree_get_selected of a TreeBatch (see TreeBatch.selected)."""
+        return tree.selected()
 
     # ---- Coach::execute_episode x many ----
     def selfplay(self, n_games, num_sims, model_id, seed=0, first_game_id=0, concurrent=0, temp_threshold=15,
@@ -652,6 +678,13 @@ class TreeBatch:
         self.engine._check(self.engine._lib.az_tree_get_action_prob(self._h, _ptr(s), temp, seed, first_game_id, _ptr(pi),
                                                         _ptr(counts), _ptr(q)))
         return pi, counts, q
+
+    def selected(self):
+        """az_tree_get_selected: int32 [G], the selected action of each tree's last get_action_prob when that was a Gumbel move
+        ("gumbel_m" > 0), else -1."""
+        out = np.zeros(self.n_games, np.int32)
+        self.engine._check(self.engine._lib.az_tree_get_selected(self._h, _ptr(out)))
+        return out
 
     def reset(self, root_states=None):
         """AsyncMcts::from_state: re-root every tree (None = the initial board)."""

@@ -1,7 +1,7 @@
 // examples/connect_four.rs (src lines 45-80) on the C++ host: the same Coach::setup parameters, the engine behind it.
 // Build:  g++ -std=c++17 -O2 -I include examples/connect_four.cpp -o connect_four -L alphazero-rs_amd -laz_engine
 //         (and -Wl,-rpath,$PWD/alphazero-rs_amd)
-// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality]
+// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]]
 //         selfplay_fp8 = 1: the episodes are played in the fp8 class, the arena gate in bf16 (Coach::selfplay_class)
 //         root_noise_eps > 0 (e.g. 0.25, with root_noise_alpha 0.3; default alpha 1): Dirichlet root noise in the episodes (Coach::root_noise_eps)
 //         eval_mirror = 1: mirror-canonical leaf evaluation for the whole loop, episodes and gate (Coach::eval_mirror)
@@ -15,13 +15,25 @@
 //         pi and the mean z of its copies; canonical also merges a position with its mirror image (Coach::merge_positions / merge_canonical)
 //         move_quality = STONES[,NODES] (e.g. 26): after every arena its games are replayed, the positions with at least STONES stones solved
 //         exactly (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach::solve_min_stones)
+//         --gumbel M[,CVISIT,CSCALE] (anywhere on the line, e.g. --gumbel 4 or --gumbel 4,50,1): Gumbel root search with sequential halving in
+//         the episodes -- at most M root actions considered, the improved policy recorded, the winner played (Coach::gumbel_m / gumbel_c_visit /
+//         gumbel_c_scale); not together with forced_playouts
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "az_host.hpp"
 
 int main(int argc, char** argv) {
     using namespace az_host;
+    std::string gumbel;
+    for (int i = 1; i + 1 < argc; ++i) {          // take "--gumbel VALUE" out of the line: the positionals keep their places
+        if (std::strcmp(argv[i], "--gumbel") != 0) continue;
+        gumbel = argv[i + 1];
+        for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+        argc -= 2;
+        break;
+    }
     const std::string dir = argc > 1 ? argv[1] : "./checkpoint";
     const size_t iters = argc > 2 ? std::strtoul(argv[2], nullptr, 10) : 1;       // num_iters, examples/connect_four.rs:65
     const size_t eps = argc > 3 ? std::strtoul(argv[3], nullptr, 10) : 1;         // num_eps, :66
@@ -50,6 +62,12 @@ int main(int argc, char** argv) {
         coach.root_noise_eps = noise_eps; coach.root_noise_alpha = noise_alpha;
         coach.playout_cap_sims = cap_sims; coach.playout_cap_full = cap_full;
         coach.forced_playouts_k = forced_k; coach.policy_prune = prune;
+        if (!gumbel.empty()) {
+            coach.gumbel_m = std::strtol(gumbel.c_str(), nullptr, 10);
+            const size_t c1 = gumbel.find(','), c2 = c1 == std::string::npos ? c1 : gumbel.find(',', c1 + 1);
+            if (c1 != std::string::npos) coach.gumbel_c_visit = std::atof(gumbel.c_str() + c1 + 1);
+            if (c2 != std::string::npos) coach.gumbel_c_scale = std::atof(gumbel.c_str() + c2 + 1);
+        }
         coach.arena_opening_plies = arena_openings;
         coach.merge_canonical = merge == "canonical";
         coach.merge_positions = coach.merge_canonical || std::strtol(merge.c_str(), nullptr, 10) != 0;

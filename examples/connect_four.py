@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--selfplay-fp8", action="store_true")   # episodes in the fp8 class, the arena gate in bf16 (Coach.selfplay_class)
     ap.add_argument("--playout-cap", default=None, metavar="N,P")        # playout cap randomization of the episodes, e.g. 20,0.25 (Coach.playout_cap_sims)
     ap.add_argument("--forced-playouts", default=None, metavar="K[,prune]")   # forced playouts at the root, e.g. 2,prune: with policy target pruning (Coach.forced_playouts_k)
+    ap.add_argument("--gumbel", default=None, metavar="M[,CVISIT,CSCALE]")   # Gumbel root search with sequential halving in the episodes, e.g. 4 or 4,50,1: at most M root actions considered (Coach.gumbel_m)
     ap.add_argument("--arena-openings", type=int, default=0, metavar="N")   # paired openings of the gate: N random quiet plies (even, 2 .. 12) per pair of arena games (Coach.arena_opening_plies)
     ap.add_argument("--merge-positions", nargs="?", const="plain", default=None, choices=["plain", "canonical"])   # position averaging before training: one tuple per distinct position; =canonical also merges mirror images (Coach.merge_positions)
     ap.add_argument("--move-quality", default=None, metavar="STONES[,NODES]")   # exact move-quality report of every arena: positions with at least STONES stones are solved (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach.solve_min_stones)
@@ -66,6 +67,10 @@ def main():
     if a.forced_playouts:
         k, _, prune = a.forced_playouts.partition(",")
         coach.forced_playouts_k, coach.policy_prune = float(k), prune == "prune"
+    if a.gumbel:
+        parts = a.gumbel.split(",")
+        coach.gumbel_m = int(parts[0])
+        coach.gumbel_c_visit, coach.gumbel_c_scale = (float(parts[1]) if len(parts) > 1 else 50.0), (float(parts[2]) if len(parts) > 2 else 1.0)
     coach.arena_opening_plies = a.arena_openings
     coach.merge_positions, coach.merge_canonical = a.merge_positions is not None, a.merge_positions == "canonical"
     if a.move_quality:

@@ -286,6 +286,44 @@ const char* az_last_error(const az_engine* e);
  *                                        that one pi is both recorded and sampled from.  The `counts` and `q` outputs stay RAW
  *                           A captured search graph is keyed on the forced-playout arguments, so one captured with others is never
  *                           replayed.  Playing strength with the option on is unmeasured
+ *   Gumbel search "gumbel_m"  0 (default, OFF), otherwise 2 .. 7: the largest number of root actions considered
+ *            "gumbel_c_visit_e6"  0 .. 1000000000 (default 50000000); c_visit = (float)(value / 1e6): the division in double, rounded once
+ *            "gumbel_c_scale_e6"  1 .. 100000000 (default 1000000);  c_scale likewise.  The defaults are the paper's Go / chess setting;
+ *                           q is used as stored, in [-1, 1]
+ *                           GUMBEL ROOT SEARCH with SEQUENTIAL HALVING (Danihelka et al., ICLR 2022), strictly opt-in.  With m = 0 (set or
+ *                           never set) every output and every counter of every entry is bit for bit what it is without the feature, and
+ *                           the kernels that run are the ones that run without it.  Values out of range and any change while a self-play
+ *                           session is open are refused (AZ_ERR_BAD_ARGUMENT).  State of the engine, like every option.  While m > 0,
+ *                           az_selfplay, az_selfplay_begin and az_tree_get_action_prob refuse (AZ_ERR_BAD_ARGUMENT) num_sim_threads > 1,
+ *                           "selfplay_async" = 1 and "forced_playouts_k_e6" > 0 (both features claim the root's arg-max).  The contract
+ *                           (csrc/az_gumbel.h states every formula operation by operation):
+ *                             Gumbel moves  every get_action_prob that can carry root noise, on az_selfplay and sessions in lock-step
+ *                                        ("fused_search" 0 / 1, every "eval_dedup", slot refill, both games, fp8 and "eval_mirror"
+ *                                        models) and on az_tree_get_action_prob.  Under a playout cap the FULL moves only: a fast move is
+ *                                        exactly the fast move without the keys.  NEVER az_arena or the slot calls.  Independent of
+ *                                        "root_noise_eps_e6": the root's stored priors are used as they are
+ *                             baseline   once per Gumbel move, where root noise is mixed in: base_j = the resolved visit count of root
+ *                                        child slot j.  d_j = n_j - base_j is the slot's visits in THIS call, t = sum of d_j the index of
+ *                                        the current simulation within the move
+ *                             variate    g_j = -ln(-ln(U)), U = ((float)(r >> 41) + 0.5f) * 2^-23, r = rng_draw(seed, game_id, ply,
+ *                                        8 + 256 * a_j) on the triple of the tie-break stream; every g_j = 0 when the move's temperature
+ *                                        is 0 (self-play: ply + 1 >= temp_threshold; the tree call: temp == 0)
+ *                             selection  at the first level of a simulation only: l_j = ln(max(p_j, 2^-126));
+ *                                        v_mix = sum_{n_b>0} p_b q_b / sum_{n_b>0} p_b (0 when no slot is visited); qh_j = n_j > 0 ? q_j :
+ *                                        v_mix;  sigma_j = ((c_visit + (float)max_b n_b) * c_scale) * qh_j;  s_j = (g_j + l_j) + sigma_j.
+ *                                        The arg-max (last-max ties, as always) runs over the slots with d_j == c(t), where c(t) is
+ *                                        entry t of sequential halving's considered-visit sequence for min(m, nchild) actions and the
+ *                                        move's budget (num_sims; of a full move).  PUCT does not decide at the root; no level below
+ *                                        the root changes
+ *                             result     the SELECTED ACTION is the arg-max of s_j over the slots with the largest d_j; self-play plays
+ *                                        it (the move draw is not used) and records it in moves[].  pi = softmax(l_j + sigma_j) over
+ *                                        the root's slots, 0 for invalid actions; temperature does not enter.  The `counts` and `q`
+ *                                        outputs stay RAW
+ *                           The value mix is the paper's in its limit of many visits, WITHOUT the net's raw root value: a root reused
+ *                           from an earlier move's tree no longer has its own net value (a deliberate deviation).  A captured search
+ *                           graph is keyed on the Gumbel arguments, so one captured with others is never replayed.
+ *                           az_tree_get_selected returns the selected actions of the last tree call, az_gumbel_values the variates of
+ *                           given roots.  Playing strength with the option on is unmeasured
  *   arena openings "arena_opening_plies"  0 (default, OFF) or an even value 2 .. 12; odd, negative and larger values are refused
  *                           (AZ_ERR_BAD_ARGUMENT).  State of the engine, like every option; only az_arena reads it.
  *                           PAIRED OPENINGS, strictly opt-in: with plies 0 and no opening book (az_arena_set_opening_book) every output
@@ -467,6 +505,14 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
  * run: eta_out [n,7] for root states [n,2] (canonical bitboards) on the streams (seed, game_ids[i], ply = stones of states[i]); the
  * valid-move mask is the state's, invalid actions get 0.  Independent of eps.  Pointers may be host or device memory. */
 az_status az_root_noise_eta(az_engine* e, int32_t n, uint64_t seed, const uint64_t* game_ids, const uint64_t* states, float* eta_out);
+/* The selected action of each tree's last az_tree_get_action_prob: actions [G], -1 for every tree when that call was not a Gumbel move
+ * ("gumbel_m" above was 0).  The pointer may be host or device memory. */
+az_status az_tree_get_selected(az_tree* t, int32_t* actions);
+/* The Gumbel variates ("gumbel_m" above) of n roots, from the device code the searches run: g_out [n,7] for root states [n,2] (canonical
+ * bitboards) on the streams (seed, game_ids[i], ply = stones of states[i]); invalid actions get 0, and so does every action when
+ * temp_is_zero != 0.  Independent of the option's value.  Pointers may be host or device memory. */
+az_status az_gumbel_values(az_engine* e, int32_t n, uint64_t seed, const uint64_t* game_ids, const uint64_t* states, int32_t temp_is_zero,
+                           float* g_out);
 /* ---- a SHARED tree batch: many host threads, one AsyncMcts (slot) each, one batched search ----
  * The reference's inference_thread (src/async_mcts.rs:117-189) answers the leaf boards of every episode thread with one predict
  * once batch_size of them are waiting.  Here a host that keeps Coach::execute_episode per thread (src/coach.rs:202-205, :241-272)

@@ -152,6 +152,13 @@ class Engine {
         check(az_set_option(e_, "policy_prune", prune ? 1 : 0));
         check(az_set_option(e_, "forced_playouts_k_e6", (int64_t)std::llround(k * 1e6)));
     }
+    // Gumbel root search with sequential halving ("gumbel_m" / "gumbel_c_visit_e6" / "gumbel_c_scale_e6", include/az_engine.h) on every move
+    // root noise can apply to (under a playout cap the full moves only), never the arena or the slot calls.  m = 0 switches it off
+    void set_gumbel(int64_t m, double c_visit = 50.0, double c_scale = 1.0) {
+        check(az_set_option(e_, "gumbel_c_visit_e6", (int64_t)std::llround(c_visit * 1e6)));
+        check(az_set_option(e_, "gumbel_c_scale_e6", (int64_t)std::llround(c_scale * 1e6)));
+        check(az_set_option(e_, "gumbel_m", m));
+    }
     // Paired arena openings ("arena_opening_plies", include/az_engine.h): arena game g and its seat-swapped twin start from the same
     // position, `plies` random quiet plies (even, 2 .. 12) onto the pair's base; never self-play or the tree calls.  0 switches them off
     void set_arena_openings(int64_t plies) { check(az_set_option(e_, "arena_opening_plies", plies)); }
@@ -613,6 +620,8 @@ class Coach {
                     // ... and so are forced playouts and pruning
                     ScopedOption forced_guard(forced_playouts_k > 0, [&] { e_.set_forced_playouts(forced_playouts_k, policy_prune); },
                                               [&] { e_.set_forced_playouts(0.0, false); });
+                    // ... and so is Gumbel root search
+                    ScopedOption gumbel_guard(gumbel_m > 0, [&] { e_.set_gumbel(gumbel_m, gumbel_c_visit, gumbel_c_scale); }, [&] { e_.set_gumbel(0); });
                     h = execute_episodes(model_id, iteration, seed);
                 }
                 if (h.len() > max_queue_length) {                   // keep the newest max_queue_length (:275-277)
@@ -743,6 +752,10 @@ class Coach {
     // behind it.  k 0 (the default): the engine is never asked
     double forced_playouts_k = 0.0;
     bool policy_prune = false;
+    // Gumbel root search with sequential halving of the episodes (Engine::set_gumbel): set before every az_selfplay and cleared behind it
+    // (the engine refuses it together with forced playouts).  m 0 (the default): the engine is never asked
+    int64_t gumbel_m = 0;
+    double gumbel_c_visit = 50.0, gumbel_c_scale = 1.0;
     // Paired openings of the gate (Engine::set_arena_openings): set before the iteration's az_arena and cleared behind it.  0 (the
     // default): the engine is never asked
     int64_t arena_opening_plies = 0;

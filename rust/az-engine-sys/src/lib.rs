@@ -112,6 +112,8 @@ extern "C" {
     /// eta [n,7] of the Dirichlet root noise ("root_noise_eps_e6" / "root_noise_alpha_e6") for root states [n,2] on the streams
     /// (seed, game_ids[i], ply = stones), at the engine's current alpha
     pub fn az_root_noise_eta(e: *mut az_engine, n: i32, seed: u64, game_ids: *const u64, states: *const u64, eta_out: *mut f32) -> c_int;
+    pub fn az_tree_get_selected(t: *mut az_tree, actions: *mut i32) -> c_int;
+    pub fn az_gumbel_values(e: *mut az_engine, n: i32, seed: u64, game_ids: *const u64, states: *const u64, temp_is_zero: i32, g_out: *mut f32) -> c_int;
     // ---- Coach::execute_episode x many, src/coach.rs:104-157; arena::play_games, src/arena.rs:62-99
     pub fn az_selfplay(e: *mut az_engine, p: *const az_selfplay_params, out: *mut az_samples) -> c_int;
     // the same as a session: the slots stay full across the calls that fetch the episodes (no drain per chunk)
