@@ -206,7 +206,7 @@ struct TreeHost {
     StepGraph step_graph;
     unsigned long long* d_totals = nullptr;   // [ST_COUNT] k_harvest's sums
     // Gumbel root search ("gumbel_m"): per-tree baseline, variates and selected action of the current move; handed to the kernels through
-    // TreeDev.gumbel only while the option is on (gumbel_for)
+    // TreeDev.move.gumbel only while the option is on (root_move_for)
     uint4* gz_base = nullptr;                 // [G]
     float* gz_g = nullptr;                    // [G][8]
     int32_t* gz_selected = nullptr;           // [G]
@@ -220,10 +220,7 @@ struct TreeHost {
     // make a kept arena look freshly created (the trees themselves are rebuilt by launch_reset_trees)
     void recycle(uint64_t reserve_nodes, hipStream_t s) {
         d.reserve_nodes = (uint32_t)reserve_nodes;
-        d.noise = RootNoise{};                    // root noise belongs to the call that sets it (the arena never does)
-        d.cap = PlayoutCap{};                     // and so does a playout cap (self-play sessions only)
-        d.forced = ForcedPlayouts{};              // and forced playouts / pruning (never the arena)
-        d.gumbel = Gumbel{};                      // and Gumbel root search (never the arena)
+        d.move = RootMove{};                      // the root-move options belong to the call that arms them (ScopedRootMove; the arena never does)
         HIPCHK(hipMemsetAsync(d.err, 0, ERR_COUNT * sizeof(uint32_t), s));
         HIPCHK(hipMemsetAsync(d_totals, 0, ST_TOTALS * sizeof(unsigned long long), s));
         HIPCHK(hipMemsetAsync(eb.n, 0, sizeof(uint32_t), s));
@@ -493,6 +490,7 @@ az_status fail(az_engine* e, az_status st, const std::string& msg) {
     if (e) e->err = msg;
     return st;
 }
+// what az_selfplay, az_selfplay_begin and az_tree_get_action_prob refuse while "gumbel_m" is on
 az_status gumbel_refusal(az_engine* e, int T, const char* who) {
     if (e->gumbel_m == 0) return AZ_OK;
     if (T > 1) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": gumbel_m needs num_sim_threads = 1");
@@ -506,40 +504,31 @@ az_status fail_hip(az_engine* e, const HipFail& f) {
     return fail(e, AZ_ERR_HIP, buf);
 }
 
-// "root_noise_eps_e6" / "root_noise_alpha_e6" as the kernels take them: the division in double, rounded once to f32.  eps == 0 (off) gives
-// the all-zero record whatever alpha is, so noise-free searches share their captured graphs.
-// "forced_playouts_k_e6" / "policy_prune" as the kernels take them.  k == 0 (off) gives the all-zero record whatever "policy_prune" is: the
-// launchers then pick the kernels' FP = false instantiations and the search graph's key is that of an engine that never set the keys
-ForcedPlayouts forced_for(const az_engine* e, float cpuct_f) {
-    ForcedPlayouts fp{};
-    if (e->forced_playouts_k_e6 == 0) return fp;
-    fp.k = forced_k_of(e->forced_playouts_k_e6);
-    fp.prune = e->policy_prune ? 1u : 0u;
-    fp.cpuct_f = cpuct_f;
-    return fp;
+// The root-move options as the kernels take them, for searches of num_sims simulations at cpuct_f on the trees of th.  Each option that is
+// off gives its all-zero sub-record whatever its secondary keys say ("root_noise_alpha_e6", "policy_prune", the Gumbel constants): the
+// launchers then pick today's instantiations and the search graph's key is that of an engine that never set the keys.  The caller adds what
+// only it knows: the stream (while noise or Gumbel is on), Gumbel's temp_threshold and the playout cap.
+RootMove root_move_for(const az_engine* e, const TreeHost& th, int num_sims, float cpuct_f, bool gumbel_allowed) {
+    RootMove m{};
+    if (e->root_noise_eps_e6 != 0) {           // the divisions in double, rounded once to f32
+        m.noise.eps = (float)((double)e->root_noise_eps_e6 / 1e6);
+        m.noise.alpha = (float)((double)e->root_noise_alpha_e6 / 1e6);
+    }
+    if (e->forced_playouts_k_e6 != 0) {
+        m.forced.k = forced_k_of(e->forced_playouts_k_e6);
+        m.forced.prune = e->policy_prune ? 1u : 0u;
+        m.forced.cpuct_f = cpuct_f;
+    }
+    if (gumbel_allowed && e->gumbel_m != 0) {
+        m.gumbel.m = (uint32_t)e->gumbel_m;
+        m.gumbel.c_visit = gumbel_of_e6(e->gumbel_c_visit_e6);
+        m.gumbel.c_scale = gumbel_of_e6(e->gumbel_c_scale_e6);
+        m.gumbel.num_sims = (uint32_t)num_sims;
+        m.gumbel.base = th.gz_base; m.gumbel.g = th.gz_g; m.gumbel.selected = th.gz_selected;
+    }
+    return m;
 }
-// "gumbel_m" / "gumbel_c_visit_e6" / "gumbel_c_scale_e6" as the kernels take them, for moves of num_sims simulations on the trees of th.
-// m == 0 (off) gives the all-zero record whatever the constants are: the launchers then pick today's instantiations and the search graph's
-// key is that of an engine that never set the keys.  The caller adds the stream (seed / first_game_id / row, or stream) and the threshold.
-Gumbel gumbel_for(const az_engine* e, const TreeHost& th, int num_sims) {
-    Gumbel gz{};
-    if (e->gumbel_m == 0) return gz;
-    gz.m = (uint32_t)e->gumbel_m;
-    gz.c_visit = gumbel_of_e6(e->gumbel_c_visit_e6);
-    gz.c_scale = gumbel_of_e6(e->gumbel_c_scale_e6);
-    gz.num_sims = (uint32_t)num_sims;
-    gz.base = th.gz_base; gz.g = th.gz_g; gz.selected = th.gz_selected;
-    return gz;
-}
-// what az_selfplay, az_selfplay_begin and az_tree_get_action_prob refuse while "gumbel_m" is on
-az_status gumbel_refusal(az_engine* e, int T, const char* who);
-RootNoise root_noise_for(const az_engine* e) {
-    RootNoise rn{};
-    if (e->root_noise_eps_e6 == 0) return rn;
-    rn.eps = (float)((double)e->root_noise_eps_e6 / 1e6);
-    rn.alpha = (float)((double)e->root_noise_alpha_e6 / 1e6);
-    return rn;
-}
+inline bool uses_root_stream(const RootMove& m) { return m.noise.eps != 0.0f || m.gumbel.m != 0u; }
 
 NetWorkspace* workspace_for(az_engine* e, hipStream_t s) {
     const int i = (s == e->stream) ? 0 : 1;
@@ -695,6 +684,14 @@ struct ScopedEvalLog {
     }
 };
 
+// The root-move record of one entry point's searches (az_tree.h RootMove), installed on a tree arena for their duration: the arena goes back
+// to the pool, and an az_tree waits for its next call, with the all-zero record.
+struct ScopedRootMove {
+    TreeHost* th = nullptr;
+    void install(TreeHost& t, const RootMove& m) { th = &t; t.d.move = m; }
+    ~ScopedRootMove() { if (th) th->d.move = RootMove{}; }
+};
+
 // fold the device-side de-duplication counters into the engine stats (after a stream sync)
 void fold_dedup(az_engine* e, const unsigned long long* h) {
     e->stats.leaf_rows_requested += h[DD_REQUESTED];
@@ -782,10 +779,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
             uint64_t model_gen;
             float cpuct;
             NetOptions opt;
-            RootNoise noise;                           // TreeDev travels by value: a graph captured with other noise arguments is never replayed
-            PlayoutCap cap;                            // ... nor one captured with another playout cap (or without one)
-            ForcedPlayouts forced;                     // ... nor one captured with other forced-playout arguments
-            Gumbel gumbel;                             // ... nor one captured with other Gumbel arguments
+            RootMove move;                             // TreeDev travels by value: a graph captured with other root-move arguments is never replayed
         } k;
         std::memset(&k, 0, sizeof k);
         k.th = &th; k.conv = net.conv; k.ws = net.kind == AZ_NET_CONV ? workspace_for(e, s) : nullptr; k.stream = s; k.root_states = d_root_states;
@@ -794,10 +788,7 @@ void run_search(az_engine* e, TreeHost& th, const ulonglong2* d_root_states, int
         k.mirror = B[0].mirror;                    // EvalBatch travels by value too
         k.block4 = th.d.block4; k.log_cap = th.d.log_cap; k.ec_bmask = ec.bmask; k.ec_stones = ec.max_stones; k.max_depth = sp.max_depth; k.cpuct = sp.cpuct_f;
         k.opt = netopt_for(e, net);
-        k.noise = th.d.noise;
-        k.cap = th.d.cap;
-        k.forced = th.d.forced;
-        k.gumbel = th.d.gumbel;
+        k.move = th.d.move;
         k.reserve_nodes = th.d.reserve_nodes;      // TreeDev travels by value into the captured launches: the capacity threshold is baked in
         k.model_gen = net.generation;              // a freed and re-created model may reuse the ConvNet's address: its weights' identity is the generation
         TreeHost::StepGraph& sg = th.step_graph;
@@ -961,11 +952,11 @@ void SlotRunner::operator()(CombineBatch<SlotCall>& b) const {
             any_reset = any_reset || b.reset[i];
         }
         HIPCHK(hipMemcpyAsync(sh.d_req, sh.h_req, (size_t)n * sizeof(SlotReq), hipMemcpyHostToDevice, s));
-        d.noise = root_noise_for(e);
-        if (d.noise.eps != 0.0f) d.noise.stream = t->d_noise_streams;         // each request's own (seed, game_id)
-        d.forced = forced_for(e, (float)t->cpuct);
-        d.gumbel = Gumbel{};                                                  // the slot calls never search by the Gumbel rule
-        launch_slot_arm(d, sh.d_req, n, t->d_root_states, sh.d_reset, s, d.noise.stream ? t->d_noise_streams : nullptr);
+        RootMove mv = root_move_for(e, t->th, t->num_sims, (float)t->cpuct, false);      // the slot calls never search by the Gumbel rule
+        if (uses_root_stream(mv)) mv.stream.stream = t->d_noise_streams;                 // each request's own (seed, game_id)
+        ScopedRootMove armed;
+        armed.install(t->th, mv);
+        launch_slot_arm(d, sh.d_req, n, t->d_root_states, sh.d_reset, s, mv.stream.stream ? t->d_noise_streams : nullptr);
         if (any_reset) launch_reset_trees(d, sh.d_reset, s);      // AsyncMcts::default for the slots acquired since their last batch
         SearchParams sp{(uint32_t)t->max_depth, (float)t->cpuct};
         // sized by the whole batch, not by this batch's requests: every batch replays the same captured graph
@@ -1011,6 +1002,28 @@ void SlotRunner::operator()(CombineBatch<SlotCall>& b) const {
         fail_hip(e, f);
         fail_all(AZ_ERR_HIP, e->err);
     }
+}
+
+// out[i][0..7) = what launch(d_game_ids, d_states, d_out) computes for root states[i] on game_ids[i] (az_root_noise_eta, az_gumbel_values):
+// the caller's pointers may be host or device memory
+template <class Launch>
+az_status per_root_values(az_engine* e, const char* who, int32_t n, const uint64_t* game_ids, const uint64_t* states, float* out, Launch launch) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (n < 0 || (n > 0 && (!game_ids || !states || !out))) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": bad argument");
+    if (n == 0) return AZ_OK;
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        DeviceMem mem;
+        uint64_t* d_ids = mem.alloc<uint64_t>((size_t)n);
+        ulonglong2* d_states = mem.alloc<ulonglong2>((size_t)n);
+        float* d_out = mem.alloc<float>((size_t)n * 7);
+        HIPCHK(hipMemcpyAsync(d_ids, game_ids, (size_t)n * 8, hipMemcpyDefault, e->stream));
+        HIPCHK(hipMemcpyAsync(d_states, states, (size_t)n * 16, hipMemcpyDefault, e->stream));
+        launch(d_ids, d_states, d_out);
+        HIPCHK(hipMemcpyAsync(out, d_out, (size_t)n * 7 * sizeof(float), hipMemcpyDefault, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
 }
 
 }  // namespace
@@ -1105,37 +1118,24 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
         }
         return AZ_OK;
     }
-    if (is("root_noise_eps_e6") || is("root_noise_alpha_e6")) {
-        const bool eps = is("root_noise_eps_e6");
-        if (eps ? (value < 0 || value > 1000000) : (value < 50000 || value > 100000000))
-            return fail(e, AZ_ERR_BAD_ARGUMENT, eps ? "root_noise_eps_e6 must be in 0 .. 1000000" : "root_noise_alpha_e6 must be in 50000 .. 100000000");
-        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "root noise cannot change while a self-play session is open");
-        (eps ? e->root_noise_eps_e6 : e->root_noise_alpha_e6) = value;
-        return AZ_OK;
-    }
-    if (is("playout_cap_sims") || is("playout_cap_full_e6")) {
-        const bool sims = is("playout_cap_sims");
-        if (value < 0 || value > (sims ? PLAYOUT_CAP_MAX_SIMS : PLAYOUT_CAP_E6))
-            return fail(e, AZ_ERR_BAD_ARGUMENT, sims ? "playout_cap_sims must be in 0 .. 65535" : "playout_cap_full_e6 must be in 0 .. 1000000");
-        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "the playout cap cannot change while a self-play session is open");
-        (sims ? e->playout_cap_sims : e->playout_cap_full_e6) = value;
-        return AZ_OK;
-    }
-    if (is("forced_playouts_k_e6") || is("policy_prune")) {
-        const bool k = is("forced_playouts_k_e6");
-        if (value < 0 || value > (k ? FORCED_K_E6_MAX : 1))
-            return fail(e, AZ_ERR_BAD_ARGUMENT, k ? "forced_playouts_k_e6 must be in 0 .. 16000000" : "policy_prune must be 0 or 1");
-        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "forced playouts cannot change while a self-play session is open");
-        (k ? e->forced_playouts_k_e6 : e->policy_prune) = value;
-        return AZ_OK;
-    }
-    if (is("gumbel_m") || is("gumbel_c_visit_e6") || is("gumbel_c_scale_e6")) {
-        if (is("gumbel_m") && value != 0 && (value < GUMBEL_M_MIN || value > GUMBEL_M_MAX)) return fail(e, AZ_ERR_BAD_ARGUMENT, "gumbel_m must be 0 or in 2 .. 7");
-        if (is("gumbel_c_visit_e6") && (value < 0 || value > GUMBEL_C_VISIT_E6_MAX)) return fail(e, AZ_ERR_BAD_ARGUMENT, "gumbel_c_visit_e6 must be in 0 .. 1000000000");
-        if (is("gumbel_c_scale_e6") && (value < GUMBEL_C_SCALE_E6_MIN || value > GUMBEL_C_SCALE_E6_MAX))
-            return fail(e, AZ_ERR_BAD_ARGUMENT, "gumbel_c_scale_e6 must be in 1 .. 100000000");
-        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "Gumbel root search cannot change while a self-play session is open");
-        (is("gumbel_m") ? e->gumbel_m : is("gumbel_c_visit_e6") ? e->gumbel_c_visit_e6 : e->gumbel_c_scale_e6) = value;
+    // the root-move keys (root_move_for): one range per key, fixed for the life of a self-play session
+    struct RootMoveKey { const char* key; int64_t lo, hi; bool or_zero; int64_t az_engine::* field; const char* range; };
+    static const RootMoveKey root_move_keys[] = {
+        {"root_noise_eps_e6", 0, 1000000, false, &az_engine::root_noise_eps_e6, "root_noise_eps_e6 must be in 0 .. 1000000"},
+        {"root_noise_alpha_e6", 50000, 100000000, false, &az_engine::root_noise_alpha_e6, "root_noise_alpha_e6 must be in 50000 .. 100000000"},
+        {"playout_cap_sims", 0, PLAYOUT_CAP_MAX_SIMS, false, &az_engine::playout_cap_sims, "playout_cap_sims must be in 0 .. 65535"},
+        {"playout_cap_full_e6", 0, PLAYOUT_CAP_E6, false, &az_engine::playout_cap_full_e6, "playout_cap_full_e6 must be in 0 .. 1000000"},
+        {"forced_playouts_k_e6", 0, FORCED_K_E6_MAX, false, &az_engine::forced_playouts_k_e6, "forced_playouts_k_e6 must be in 0 .. 16000000"},
+        {"policy_prune", 0, 1, false, &az_engine::policy_prune, "policy_prune must be 0 or 1"},
+        {"gumbel_m", GUMBEL_M_MIN, GUMBEL_M_MAX, true, &az_engine::gumbel_m, "gumbel_m must be 0 or in 2 .. 7"},
+        {"gumbel_c_visit_e6", 0, GUMBEL_C_VISIT_E6_MAX, false, &az_engine::gumbel_c_visit_e6, "gumbel_c_visit_e6 must be in 0 .. 1000000000"},
+        {"gumbel_c_scale_e6", GUMBEL_C_SCALE_E6_MIN, GUMBEL_C_SCALE_E6_MAX, false, &az_engine::gumbel_c_scale_e6, "gumbel_c_scale_e6 must be in 1 .. 100000000"},
+    };
+    for (const RootMoveKey& r : root_move_keys) {
+        if (!is(r.key)) continue;
+        if ((value < r.lo || value > r.hi) && !(r.or_zero && value == 0)) return fail(e, AZ_ERR_BAD_ARGUMENT, r.range);
+        if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(r.key) + " cannot change while a self-play session is open");
+        e->*r.field = value;
         return AZ_OK;
     }
     if (is("arena_opening_plies")) {
@@ -1754,15 +1754,15 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
             HIPCHK(hipMemcpyAsync(t->d_root_states, t->h_states, (size_t)G * 16, hipMemcpyHostToDevice, e->stream));
         }
         launch_set_active(d, 1u, e->stream);
-        d.forced = forced_for(e, (float)t->cpuct);
-        d.noise = root_noise_for(e);
-        d.gumbel = gumbel_for(e, t->th, t->num_sims);
-        t->last_gumbel = d.gumbel.m != 0u;
-        if (d.noise.eps != 0.0f || d.gumbel.m != 0u) {      // tree g's stream: (seed, first_game_id + g), from device memory so the search graph survives the call's seed
+        RootMove mv = root_move_for(e, t->th, t->num_sims, (float)t->cpuct, true);
+        t->last_gumbel = mv.gumbel.m != 0u;
+        if (uses_root_stream(mv)) {      // tree g's stream: (seed, first_game_id + g), from device memory so the search graph survives the call's seed
             launch_noise_streams(t->d_noise_streams, G, seed, first_game_id, e->stream);
-            if (d.noise.eps != 0.0f) d.noise.stream = t->d_noise_streams;
-            if (d.gumbel.m != 0u) { d.gumbel.stream = t->d_noise_streams; d.gumbel.temp_threshold = temp == 0.0f ? INT32_MIN : INT32_MAX; }
+            mv.stream.stream = t->d_noise_streams;
         }
+        if (mv.gumbel.m != 0u) mv.gumbel.temp_threshold = temp == 0.0f ? INT32_MIN : INT32_MAX;
+        ScopedRootMove armed;
+        armed.install(t->th, mv);
         SearchParams sp{(uint32_t)t->max_depth, (float)t->cpuct};
         prepare_cache(e, dedup_applies(e, *net), (uint64_t)G * ((uint64_t)t->num_sims + 1), e->stream);
         run_search(e, t->th, t->d_root_states, t->num_sims, sp, *net, G);
@@ -1789,22 +1789,9 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
 
 // The device sampler alone (csrc/az_noise.h as the search kernels run it) for n roots at the engine's current alpha.
 az_status az_root_noise_eta(az_engine* e, int32_t n, uint64_t seed, const uint64_t* game_ids, const uint64_t* states, float* eta_out) {
-    if (!e) return AZ_ERR_BAD_ARGUMENT;
-    if (n < 0 || (n > 0 && (!game_ids || !states || !eta_out))) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_root_noise_eta: bad argument");
-    if (n == 0) return AZ_OK;
-    try {
-        HIPCHK(hipSetDevice(e->device));
-        DeviceMem mem;
-        uint64_t* d_ids = mem.alloc<uint64_t>((size_t)n);
-        ulonglong2* d_states = mem.alloc<ulonglong2>((size_t)n);
-        float* d_eta = mem.alloc<float>((size_t)n * 7);
-        HIPCHK(hipMemcpyAsync(d_ids, game_ids, (size_t)n * 8, hipMemcpyDefault, e->stream));
-        HIPCHK(hipMemcpyAsync(d_states, states, (size_t)n * 16, hipMemcpyDefault, e->stream));
+    return per_root_values(e, "az_root_noise_eta", n, game_ids, states, eta_out, [&](const uint64_t* d_ids, const ulonglong2* d_states, float* d_eta) {
         launch_root_noise_eta(e->cfg.game, n, seed, d_ids, d_states, (float)((double)e->root_noise_alpha_e6 / 1e6), d_eta, e->stream);
-        HIPCHK(hipMemcpyAsync(eta_out, d_eta, (size_t)n * 7 * sizeof(float), hipMemcpyDefault, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        return AZ_OK;
-    } catch (const HipFail& f) { return fail_hip(e, f); }
+    });
 }
 
 // The selected action of each tree's last az_tree_get_action_prob when that was a Gumbel move ("gumbel_m"), else -1.
@@ -1826,22 +1813,9 @@ az_status az_tree_get_selected(az_tree* t, int32_t* actions) {
 
 // The device's Gumbel variates alone (csrc/az_gumbel.h as the search kernels run it) for n roots: g_out[i][a], 0 for an invalid action.
 az_status az_gumbel_values(az_engine* e, int32_t n, uint64_t seed, const uint64_t* game_ids, const uint64_t* states, int32_t temp_is_zero, float* g_out) {
-    if (!e) return AZ_ERR_BAD_ARGUMENT;
-    if (n < 0 || (n > 0 && (!game_ids || !states || !g_out))) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_gumbel_values: bad argument");
-    if (n == 0) return AZ_OK;
-    try {
-        HIPCHK(hipSetDevice(e->device));
-        DeviceMem mem;
-        uint64_t* d_ids = mem.alloc<uint64_t>((size_t)n);
-        ulonglong2* d_states = mem.alloc<ulonglong2>((size_t)n);
-        float* d_g = mem.alloc<float>((size_t)n * 7);
-        HIPCHK(hipMemcpyAsync(d_ids, game_ids, (size_t)n * 8, hipMemcpyDefault, e->stream));
-        HIPCHK(hipMemcpyAsync(d_states, states, (size_t)n * 16, hipMemcpyDefault, e->stream));
+    return per_root_values(e, "az_gumbel_values", n, game_ids, states, g_out, [&](const uint64_t* d_ids, const ulonglong2* d_states, float* d_g) {
         launch_gumbel_values(e->cfg.game, n, seed, d_ids, d_states, temp_is_zero != 0, d_g, e->stream);
-        HIPCHK(hipMemcpyAsync(g_out, d_g, (size_t)n * 7 * sizeof(float), hipMemcpyDefault, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        return AZ_OK;
-    } catch (const HipFail& f) { return fail_hip(e, f); }
+    });
 }
 
 // ---- shared tree batch: many host threads, one slot (one AsyncMcts) each ---------------------------------------------------
@@ -1925,6 +1899,7 @@ struct SelfplaySession {
     TreeLease lease;
     DeviceMem mem;
     ScopedEvalLog evlog;
+    ScopedRootMove armed;                // the session's root-move record on the leased arena, for the session's life
     GamesDev gd{};
     SearchParams sp{};
     SelfplayMoveParams mp{};
@@ -1939,7 +1914,7 @@ struct SelfplaySession {
     EvalCache ec{};
     int fill = 0;
     long long step = 0;
-    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); if (lease.th) { lease.th->d.noise = RootNoise{}; lease.th->d.cap = PlayoutCap{}; lease.th->d.forced = ForcedPlayouts{}; lease.th->d.gumbel = Gumbel{}; } }
+    ~SelfplaySession() { if (h_ctr) (void)hipHostFree(h_ctr); }
 };
 
 static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, std::unique_ptr<SelfplaySession>& out) {
@@ -2008,6 +1983,10 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
         HIPCHK(hipMemcpy(gd.counters, ctr, sizeof ctr, hipMemcpyHostToDevice));
     }
     ss->round_sims = p->num_sims;
+    // the session's root-move record: forced playouts and the Gumbel rule on the full moves only under a playout cap, the budget of a full move
+    RootMove mv = root_move_for(e, th, p->num_sims, (float)p->cpuct, true);
+    if (uses_root_stream(mv)) mv.stream = RootStream{p->seed, p->first_game_id, gd.gid, nullptr};      // (seed, first_game_id + the slot's episode, ply)
+    if (mv.gumbel.m != 0u) mv.gumbel.temp_threshold = p->temp_threshold;
     if (cap_sims > 0) {
         // the slots' first moves (ply 0 of episodes 0 .. C-1) are drawn here; every later one by the move that precedes it (selfplay_move_body)
         PlayoutCap cap{mem.alloc<uint32_t>(C), (uint32_t)p->num_sims, (uint32_t)cap_sims, playout_cap_thresh24((uint64_t)e->playout_cap_full_e6)};
@@ -2020,15 +1999,11 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
         HIPCHK(hipMemcpy(cap.word, w.data(), (size_t)C * sizeof(uint32_t), hipMemcpyHostToDevice));
         gd.g_full = mem.alloc<unsigned long long>(n_games);
         HIPCHK(hipMemset(gd.g_full, 0, (size_t)n_games * sizeof(unsigned long long)));
-        th.d.cap = cap;
+        mv.cap = cap;
         ss->round_sims = (int)most;
     }
+    ss->armed.install(th, mv);
     launch_reset_trees(th.d, nullptr, s);
-    th.d.forced = forced_for(e, (float)p->cpuct); // the session's forced playouts / pruning (full moves only under a playout cap)
-    th.d.noise = root_noise_for(e);               // the session's root noise: stream (seed, first_game_id + the slot's episode, ply)
-    if (th.d.noise.eps != 0.0f) { th.d.noise.seed = p->seed; th.d.noise.first_game_id = p->first_game_id; th.d.noise.row = gd.gid; }
-    th.d.gumbel = gumbel_for(e, th, p->num_sims); // the session's Gumbel root search: the same stream, the budget of a full move
-    if (th.d.gumbel.m != 0u) { th.d.gumbel.seed = p->seed; th.d.gumbel.first_game_id = p->first_game_id; th.d.gumbel.row = gd.gid; th.d.gumbel.temp_threshold = p->temp_threshold; }
     prepare_cache(e, dedup_applies(e, *net), (uint64_t)n_games * AZ_MAX_PLIES * ((uint64_t)p->num_sims + 1), s);
     ss->sp = SearchParams{(uint32_t)p->max_depth, (float)p->cpuct};
     ss->mp = SelfplayMoveParams{p->seed, p->first_game_id, p->temp_threshold, C < n_games ? 1 : 0, 0, 0};
@@ -2118,7 +2093,7 @@ static az_status selfplay_run_until(az_engine* e, SelfplaySession& ss, int hi) {
         resolve_profile(e);
         ss.active = (int)h_ctr[2];
         ss.rows_typ = h_ctr[3] ? (int)std::min<uint32_t>(h_ctr[3], (uint32_t)(C * T)) : 0;      // this move's largest batch
-        if (th.d.cap.word) ss.round_sims = h_ctr[4] ? (int)std::min<uint32_t>(h_ctr[4], (uint32_t)p->num_sims) : p->num_sims;
+        if (th.d.move.cap.word) ss.round_sims = h_ctr[4] ? (int)std::min<uint32_t>(h_ctr[4], (uint32_t)p->num_sims) : p->num_sims;
         HIPCHK(hipMemsetAsync(gd.counters + 3, 0, 2 * sizeof(uint32_t), s));
         if (h_ctr[1] >= want) { ++ss.iter; break; }
         if ((ss.iter & 7) == 7 || h_ctr[2] == 0) {

@@ -60,15 +60,22 @@ struct TreeLine {
 };
 static_assert(sizeof(TreeLine) == 128, "head + inline path = one 128-byte line");
 
-// Dirichlet root noise ("root_noise_eps_e6" / "root_noise_alpha_e6", include/az_engine.h; the sampler: az_noise.h).  eps == 0 is OFF: the
-// launchers then pick the kernels' noise-free instantiations, which contain none of this.  Tree g's stream is (seed, game_id, ply = stones
-// on the root board) with (seed, game_id) = stream[g] when stream is set (the tree calls: one pair per tree / per slot request), else
-// (seed, first_game_id + (row ? row[g] : g)) (self-play: row = the slot's current episode).
-struct RootNoise {
-    float eps, alpha;
+// ---- THE ROOT MOVE: how the root of the current get_action_prob is treated (one record, RootMove, armed by the entry point around its
+// searches and zero at every other time: az_engine.hip ScopedRootMove).  All of it is part of the search graph's key, which is compared
+// with memcmp: no sub-record may have implicit padding.
+// The RNG stream of tree g's move, shared by the root noise and the Gumbel variates: (seed, game_id, ply = stones on the root board) with
+// (seed, game_id) = stream[g] when stream is set (the tree calls: one pair per tree / per slot request), else
+// (seed, first_game_id + (row ? row[g] : g)) (self-play: row = the slot's current episode).  All-zero unless noise or Gumbel is on.
+struct RootStream {
     uint64_t seed, first_game_id;
     const int32_t* row;          // [G] or nullptr
     const ulonglong2* stream;    // [G] (seed, game_id) or nullptr
+};
+
+// Dirichlet root noise ("root_noise_eps_e6" / "root_noise_alpha_e6", include/az_engine.h; the sampler: az_noise.h).  eps == 0 is OFF: the
+// launchers then pick the kernels' noise-free instantiations, which contain none of this.
+struct RootNoise {
+    float eps, alpha;
 };
 
 // Playout cap randomization ("playout_cap_sims" / "playout_cap_full_e6", include/az_engine.h; the predicate: az_playout.h).  Self-play only.
@@ -81,39 +88,44 @@ struct PlayoutCap {
     uint32_t* word;              // [G] or nullptr
     uint32_t num_sims, cap_sims; // N and n
     uint32_t thresh24;           // playout_cap_thresh24(P)
-    uint32_t pad;                // (no implicit padding: the record is part of the search graph's key)
+    uint32_t pad;
 };
 
 // Forced playouts and policy target pruning ("forced_playouts_k_e6" / "policy_prune", include/az_engine.h; the predicates: az_forced.h).
-// k == 0 is OFF: the launchers then pick the kernels' FP = false instantiations, which contain none of this (a template switch, not a
+// k == 0 is OFF: the launchers then pick the kernels' RR_NONE instantiations, which contain none of this (a template switch, not a
 // runtime field read by the default kernels: DESIGN.md 4.1c).  A FORCED MOVE is every get_action_prob that can carry root noise; under a
 // playout cap the slot's full moves only (PLAYOUT_FULL_BIT of PlayoutCap.word, the bit that gates the noise).
 struct ForcedPlayouts {
     float k;                     // 0 = OFF
     uint32_t prune;              // 1: root_policy forms pi from the pruned counts (only read while k != 0)
     float cpuct_f;               // the cpuct of the entry's searches: root_policy's prune step has no SearchParams of its own
-    uint32_t pad;                // (no implicit padding: the record is part of the search graph's key)
+    uint32_t pad;
 };
 
 // Gumbel root search with sequential halving ("gumbel_m" / "gumbel_c_visit_e6" / "gumbel_c_scale_e6", include/az_engine.h; the rule:
 // az_gumbel.h).  m == 0 is OFF: the launchers then pick today's instantiations, which contain none of this (one template axis with forced
 // playouts: the two exclude each other).  A GUMBEL MOVE is every get_action_prob that can carry root noise; under a playout cap the slot's
-// full moves only.  Tree g's variates are drawn on (seed, game_id, ply = stones on the root board) with (seed, game_id) = stream[g] when
-// stream is set (az_tree_get_action_prob), else (seed, first_game_id + (row ? row[g] : g)) (self-play: row = the slot's current episode).
+// full moves only.  Tree g's variates are drawn on its RootStream.
 struct Gumbel {
     uint32_t m;                  // 0 = OFF, else 2 .. 7: the largest number of root actions considered
     float c_visit, c_scale;
     uint32_t num_sims;           // n: the budget of a Gumbel move (num_sims; of a full move under a playout cap)
     int32_t temp_threshold;      // the variates are 0 when stones + 1 >= temp_threshold (the tree call: INT32_MIN for temp == 0, INT32_MAX else)
-    uint32_t pad;                // (no implicit padding: the record is part of the search graph's key)
-    uint64_t seed, first_game_id;
-    const int32_t* row;          // [G] or nullptr
-    const ulonglong2* stream;    // [G] (seed, game_id) or nullptr
+    uint32_t pad;
     uint4* base;                 // [G] u16 x 8: the root children's visit counts when the move began (slot j < nchild; written once per move)
     float* g;                    // [G][8] the slots' Gumbel variates of the move
     int32_t* selected;           // [G] out (k_root_policy): the selected action of the tree's last az_tree_get_action_prob
 };
-static_assert(sizeof(Gumbel) == 80, "no implicit padding");
+
+struct RootMove {
+    RootNoise noise;             // (ahead of the stream on purpose: with the stream first k_async_step<NZ> spills 32 .. 64 bytes more)
+    RootStream stream;
+    PlayoutCap cap;              // a self-play session's own searches only
+    ForcedPlayouts forced;
+    Gumbel gumbel;               // never set for the slot calls
+};
+static_assert(sizeof(RootStream) == 32 && sizeof(RootNoise) == 8 && sizeof(PlayoutCap) == 24 && sizeof(ForcedPlayouts) == 16 && sizeof(Gumbel) == 48 &&
+              sizeof(RootMove) == 128, "no implicit padding: the record is part of the search graph's key");
 
 struct TreeDev {
     int32_t G;               // trees
@@ -139,10 +151,7 @@ struct TreeDev {
     float* log_pi;           // [G*log_cap*7]
     float* log_v;            // [G*log_cap]
     const int32_t* log_row;  // [G] or nullptr: log row of tree g (az_selfplay: the slot's current episode, so a log survives slot refills); nullptr = g
-    RootNoise noise;         // set by the entry point around its searches; zero for the arena
-    PlayoutCap cap;          // set by a self-play session for its own searches; zero everywhere else
-    ForcedPlayouts forced;   // set by the entry point around its searches, as noise is; zero for the arena
-    Gumbel gumbel;           // set by the entry point around its searches, as noise is; zero for the arena and the slot calls
+    RootMove move;           // set by the entry point around its searches (ScopedRootMove, az_engine.hip); zero at every other time and for the arena
 };
 
 // Leaf batch handed to the net (src/async_mcts.rs:117-189 restated as lanes): the DISTINCT states the trees of one
@@ -168,7 +177,7 @@ struct EvalBatch {
     int32_t dedup;
     // "eval_mirror" (conv models only): rows, election keys and cache keys are those of the CANONICAL orientation c(s) and hold the raw
     // net output N(c(s)); each backup un-mirrors pi for its own tree.  Independent of dedup.  Read by the LAUNCHERS only, which pick the
-    // kernels' MIR instantiations (as TreeDev.noise.eps picks NZ): the default instantiations contain none of it.  DESIGN.md 4.1c
+    // kernels' MIR instantiations (as TreeDev.move.noise.eps picks NZ): the default instantiations contain none of it.  DESIGN.md 4.1c
     int32_t mirror;
     unsigned long long* tkey;   // [tmask+1] state key (never 0), 0 = empty
     uint32_t* tuniq;            // [tmask+1] row of the slot's winner
@@ -276,7 +285,7 @@ void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch&
                     int first, int last, hipStream_t s);
 // the whole search (root prepare + num_sims simulations + backups) in one launch for the device-function nets
 // (kind 0 = stub, 1 = hash fixture): no leaf batch, no kernel boundary per simulation
-// (with a playout cap, tree g runs its own budget t.cap.word[g] instead of num_sims)
+// (with a playout cap, tree g runs its own budget t.move.cap.word[g] instead of num_sims)
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s);
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,

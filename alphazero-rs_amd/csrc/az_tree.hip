@@ -313,20 +313,25 @@ AZ_D float root_noise_eta_lane(uint64_t stream, float alpha, uint32_t nchild, ui
     }
     return noise_normalise(gm, sum, nchild);
 }
+// (seed, game_id) of tree g's root-move stream (az_tree.h RootStream): what the root noise and the Gumbel variates of its move are drawn on
+AZ_D ulonglong2 root_stream_of(const TreeDev& t, int g) {
+    const RootStream& r = t.move.stream;
+    uint64_t seed = r.seed, game_id;
+    if (r.stream) { const ulonglong2 st = r.stream[g]; seed = st.x; game_id = st.y; }
+    else game_id = r.first_game_id + (uint64_t)(r.row ? r.row[g] : g);
+    return make_ulonglong2(seed, game_id);
+}
 // the prior of lane sub's root child after the mix: (1 - eps) * prior + eps * eta[myact]; s = the root's state
 template <class G>
 AZ_D float root_noise_mix(const TreeDev& t, int g, typename G::State s, uint32_t nchild, uint32_t myact, float prior, int sub) {
-    uint64_t seed = t.noise.seed, game_id;
-    if (t.noise.stream) { const ulonglong2 st = t.noise.stream[g]; seed = st.x; game_id = st.y; }
-    else game_id = t.noise.first_game_id + (uint64_t)(t.noise.row ? t.noise.row[g] : g);
-    const uint64_t stream = noise_stream(seed, game_id, (uint64_t)G::stones(s));
-    return noise_mix(t.noise.eps, prior, root_noise_eta_lane<G>(stream, t.noise.alpha, nchild, myact, sub));
+    const ulonglong2 rs = root_stream_of(t, g);
+    const uint64_t stream = noise_stream(rs.x, rs.y, (uint64_t)G::stones(s));
+    return noise_mix(t.move.noise.eps, prior, root_noise_eta_lane<G>(stream, t.move.noise.alpha, nchild, myact, sub));
 }
 
-// Playout cap (az_tree.h PlayoutCap): a slot's fast moves get no noise; without a cap every move does.  Only NZ code reads this.
-AZ_D bool move_noisy(const TreeDev& t, int g) { return !t.cap.word || (t.cap.word[g] & PLAYOUT_FULL_BIT) != 0u; }
-// Forced playouts (az_tree.h ForcedPlayouts): the same moves -- every move without a cap, the full ones with it.  Only FP code reads this.
-AZ_D bool move_forced(const TreeDev& t, int g) { return move_noisy(t, g); }
+// Playout cap (az_tree.h PlayoutCap): a slot's fast moves get no noise, no forced playouts and no Gumbel rule; without a cap every move
+// does.  Only NZ / RR != RR_NONE code reads this.
+AZ_D bool move_noisy(const TreeDev& t, int g) { return !t.move.cap.word || (t.move.cap.word[g] & PLAYOUT_FULL_BIT) != 0u; }
 
 // ---- Gumbel root search (az_gumbel.h; only the RR_GUMBEL / GZ instantiations of the kernels contain it) ------------------------------------
 // A GUMBEL MOVE is every move that can carry root noise (move_noisy).  Its BASELINE is taken where the noise is mixed in -- once per move,
@@ -340,22 +345,20 @@ AZ_D void gumbel_capture(const TreeDev& t, int g, size_t base, typename G::State
         const NodeRec cr = node_load(node_ptr(t, base, cb + (uint32_t)sub));
         const uint64_t cc = cr.link != NONE ? node_ctr(node_ptr(t, base, cr.link)) : cr.ctr;
         n = ctr_n(cc);
-        uint64_t seed = t.gumbel.seed, game_id;
-        if (t.gumbel.stream) { const ulonglong2 st = t.gumbel.stream[g]; seed = st.x; game_id = st.y; }
-        else game_id = t.gumbel.first_game_id + (uint64_t)(t.gumbel.row ? t.gumbel.row[g] : g);
+        const ulonglong2 rs = root_stream_of(t, g);
         const uint32_t ply = G::stones(s);
-        gv = gumbel_variate(seed, game_id, (uint64_t)ply, cr.meta & META_A_MASK, (int32_t)ply + 1 >= t.gumbel.temp_threshold);
+        gv = gumbel_variate(rs.x, rs.y, (uint64_t)ply, cr.meta & META_A_MASK, (int32_t)ply + 1 >= t.move.gumbel.temp_threshold);
     }
-    ((uint16_t*)t.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub] = (uint16_t)n;
-    t.gumbel.g[(size_t)g * BLOCK_SLOTS + sub] = gv;
+    ((uint16_t*)t.move.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub] = (uint16_t)n;
+    t.move.gumbel.g[(size_t)g * BLOCK_SLOTS + sub] = gv;
 }
 // what lane sub of a Gumbel move's root holds besides its child's counters: the slot's visits in this move and its variate
 struct GumbelLane { uint32_t d; float g; };
 AZ_D GumbelLane gumbel_lane(const TreeDev& t, int g, uint32_t nchild, uint32_t n, int sub) {
     GumbelLane r{0u, 0.0f};
     if ((uint32_t)sub < nchild) {
-        r.d = (n - (uint32_t)((const uint16_t*)t.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub]) & 0xFFFFu;
-        r.g = t.gumbel.g[(size_t)g * BLOCK_SLOTS + sub];
+        r.d = (n - (uint32_t)((const uint16_t*)t.move.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub]) & 0xFFFFu;
+        r.g = t.move.gumbel.g[(size_t)g * BLOCK_SLOTS + sub];
     }
     return r;
 }
@@ -378,7 +381,7 @@ AZ_D float gumbel_sigma_lane(const TreeDev& t, uint32_t nchild, uint32_t n, floa
     }
     *sum_d = sd;
     *max_d = md;
-    return gumbel_sigma(t.gumbel.c_visit, t.gumbel.c_scale, max_n, n, q, gumbel_vmix(mx));
+    return gumbel_sigma(t.move.gumbel.c_visit, t.move.gumbel.c_scale, max_n, n, q, gumbel_vmix(mx));
 }
 
 // ---- get_action_prob prologue: root lookup (src/async_mcts.rs:81) + S10 + S1 -------------
@@ -495,7 +498,7 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
         if constexpr (RR == RR_GUMBEL) {
             // the slot's visits before this move are those of the node it now resolves to, not the placeholder's 0 the baseline took
             if (gz_relink != NONE) {
-                if ((uint32_t)sub == gz_relink) ((uint16_t*)t.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub] = (uint16_t)ctr_n(pr.ctr);
+                if ((uint32_t)sub == gz_relink) ((uint16_t*)t.move.gumbel.base)[(size_t)g * BLOCK_SLOTS + sub] = (uint16_t)ctr_n(pr.ctr);
                 gz_relink = NONE;
             }
         }
@@ -528,8 +531,8 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
                 const float p = __uint_as_float(cr.prior);
                 uint32_t tt, md;
                 const float sigma = gumbel_sigma_lane<G>(t, nchild, fn, fq, p, gl.d, &tt, &md);
-                const uint32_t m_eff = t.gumbel.m < nchild ? t.gumbel.m : nchild;
-                const uint32_t want = gumbel_considered_visit(m_eff, t.gumbel.num_sims, tt);
+                const uint32_t m_eff = t.move.gumbel.m < nchild ? t.move.gumbel.m : nchild;
+                const uint32_t want = gumbel_considered_visit(m_eff, t.move.gumbel.num_sims, tt);
                 u = ((uint32_t)sub < nchild && gl.d == want) ? gumbel_score(gl.g, gumbel_logit(p), sigma) : -__builtin_inff();
             }
             at_root = false;
@@ -539,7 +542,7 @@ AZ_D typename G::State select_body(const TreeDev& t, TreeHead& h, PathRegs& pth,
                 uint32_t S = 0u;
 #pragma unroll
                 for (int j = 0; j < NA; ++j) S += gshfl<GW>(fn, j);
-                if ((uint32_t)sub < nchild && forced_child(t.forced.k, __uint_as_float(cr.prior), S, fn)) u = __builtin_inff();
+                if ((uint32_t)sub < nchild && forced_child(t.move.forced.k, __uint_as_float(cr.prior), S, fn)) u = __builtin_inff();
             }
             at_root = false;
         }
@@ -791,7 +794,7 @@ struct RootPolicy {
     float q;
     int32_t sel;     // RR_GUMBEL on a Gumbel move: the selected action (the same in every lane); else -1
 };
-// RR_FORCED && forced && t.forced.prune (policy target pruning, az_forced.h): pi is formed from the PRUNED counts; count and q stay raw
+// RR_FORCED && forced && t.move.forced.prune (policy target pruning, az_forced.h): pi is formed from the PRUNED counts; count and q stay raw
 // RR_GUMBEL && forced (az_gumbel.h): pi = softmax(l + sigma) over the root's slots and sel = the selected action; count and q stay raw,
 // temp and the tie-break stream are not used
 template <class G, int RR = RR_NONE>
@@ -857,7 +860,7 @@ AZ_D RootPolicy root_policy(const TreeDev& t, uint32_t root, int g, int sub, flo
     }
     uint32_t pcount = out.count;                                    // what pi is formed from: the raw count, or ...
     if constexpr (RR == RR_FORCED) {
-        if (forced && t.forced.prune) {                             // ... the pruned one
+        if (forced && t.move.forced.prune) {                             // ... the pruned one
             uint32_t S = 0u, b = 0u, bn = 0u;
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
@@ -866,9 +869,9 @@ AZ_D RootPolicy root_policy(const TreeDev& t, uint32_t root, int g, int sub, flo
                 if ((uint32_t)j < nchild && nj >= bn) { b = (uint32_t)j; bn = nj; }      // the most visited slot, the highest among equals
             }
             const float sq = forced_sqrt_parent(ctr_n(pr.ctr));
-            const float u_star = forced_puct(gshflf<GW>(cq, (int)b), bn, gshflf<GW>(cp, (int)b), sq, t.forced.cpuct_f);
+            const float u_star = forced_puct(gshflf<GW>(cq, (int)b), bn, gshflf<GW>(cp, (int)b), sq, t.move.forced.cpuct_f);
             uint32_t cm = cn;
-            if ((uint32_t)sub < nchild && (uint32_t)sub != b && cn > 0u) cm = forced_prune(t.forced.k, cp, S, cn, cq, sq, t.forced.cpuct_f, u_star);
+            if ((uint32_t)sub < nchild && (uint32_t)sub != b && cn > 0u) cm = forced_prune(t.move.forced.k, cp, S, cn, cq, sq, t.move.forced.cpuct_f, u_star);
             pcount = 0u;
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
@@ -955,7 +958,7 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     bool go = true;
     if constexpr (PC) go = (h.active >> 1) != 0u;
     bool forced = true;
-    if constexpr (RR != RR_NONE) forced = move_forced(t, g);
+    if constexpr (RR != RR_NONE) forced = move_noisy(t, g);
     const typename G::State leaf_s = select_body<G, false, RR>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, go, forced);
     if constexpr (PC) { if (go) h.active -= 2u; }
     AZ_TSTAMP(4);
@@ -992,8 +995,9 @@ struct ThreadRegs { uint32_t leaf, leaf_kind; float leaf_val; uint32_t src, path
 AZ_D void thread_to_head(TreeHead& h, const ThreadRegs& r) { h.leaf = r.leaf; h.leaf_kind = r.leaf_kind; h.leaf_val = r.leaf_val; h.src = r.src; h.path_len = r.path_len; }
 AZ_D ThreadRegs head_to_thread(const TreeHead& h) { return ThreadRegs{h.leaf, h.leaf_kind, h.leaf_val, h.src, h.path_len}; }
 // PC (playout cap): as in k_backup_select; a step takes T simulations off what the tree's move has left (budgets are multiples of T)
-template <class G, bool NZ, bool MIR, bool PC, bool FP>
+template <class G, bool NZ, bool MIR, bool PC, int RR>
 __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp, int first, int last) {
+    static_assert(RR != RR_GUMBEL, "never launched with Gumbel on: no such instantiation (AZ_FOR_RR)");
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * 64 + threadIdx.x;
     const int g = tid / GW, sub = tid % GW;
@@ -1031,7 +1035,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
     bool go = !last;
     if constexpr (PC) go = go && (h.active >> 1) >= (uint32_t)T;
     bool forced = true;
-    if constexpr (FP) forced = move_forced(t, g);
+    if constexpr (RR != RR_NONE) forced = move_noisy(t, g);
     for (int tt = 0; tt < T; ++tt) {                        // selections in thread order
         group_memory_sync();                                // counters, priors, locks and links written so far are read next
         TreeLine* tl = t.thr + (size_t)g * T + tt;
@@ -1041,7 +1045,7 @@ __global__ __launch_bounds__(64) void k_step_mt(TreeDev t, EvalBatch eb_prev, Ev
         bool want = false;
         typename G::State leaf_s = G::init();
         if (go) {
-            leaf_s = select_body<G, true, FP ? RR_FORCED : RR_NONE>(t, h, pth, sp, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP, &abandoned, true, forced);
+            leaf_s = select_body<G, true, RR>(t, h, pth, sp, g, sub, t.path + ((size_t)g * T + tt) * PATH_CAP, &abandoned, true, forced);
             want = h.leaf_kind == LEAF_EVAL;
         }
         const uint32_t src = leaf_request<G, MIR>(eb_next, ec, want, leaf_s, sub);      // every wave calls it T times (wave-wide ballots inside)
@@ -1080,7 +1084,7 @@ AZ_D float fixture_row(typename G::State s, int kind, uint64_t salt, int sub) {
     for (int a = 0; a < G::ACTIONS; ++a) out = sub == a ? pi[a] : out;
     return out;
 }
-// PC (playout cap): tree g runs the budget of its own move, t.cap.word[g], instead of num_sims
+// PC (playout cap): tree g runs the budget of its own move, t.move.cap.word[g], instead of num_sims
 template <class G, bool NZ, bool PC, int RR>
 __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind,
                                                        uint64_t salt) {
@@ -1095,9 +1099,9 @@ __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglon
     constexpr bool GZ = RR == RR_GUMBEL;
     bool noisy = true;
     if constexpr (NZ || GZ) noisy = move_noisy(t, g);
-    if constexpr (PC) num_sims = (int)(t.cap.word[g] & ~PLAYOUT_FULL_BIT);
+    if constexpr (PC) num_sims = (int)(t.move.cap.word[g] & ~PLAYOUT_FULL_BIT);
     bool forced = true;
-    if constexpr (RR != RR_NONE) forced = move_forced(t, g);
+    if constexpr (RR != RR_NONE) forced = move_noisy(t, g);
     typename G::State ls = root_prepare_body<G, NZ, GZ>(t, h, root_states, g, sub, noisy);
     for (int i = 0; i <= num_sims; ++i) {
         group_memory_sync();
@@ -1124,7 +1128,7 @@ __global__ __launch_bounds__(64) void k_root_policy(TreeDev t, float temp, uint6
     if (!h.active) return;
     const typename G::State s = G::unpack(node_key(t, (size_t)g * t.R, h.root));
     RootPolicy rp = root_policy<G, RR>(t, h.root, g, sub, temp, seed, first_game_id + (uint64_t)g, (uint64_t)G::stones(s));
-    if constexpr (RR == RR_GUMBEL) { if (sub == 0) t.gumbel.selected[g] = rp.sel; }      // az_tree_get_selected
+    if constexpr (RR == RR_GUMBEL) { if (sub == 0) t.move.gumbel.selected[g] = rp.sel; }      // az_tree_get_selected
     if (sub < NA) {
         pi[(size_t)g * NA + sub] = rp.pi;
         if (counts) counts[(size_t)g * NA + sub] = (uint16_t)rp.count;
@@ -1198,8 +1202,9 @@ __global__ __launch_bounds__(64) void k_gumbel_values(int n, uint64_t seed, cons
 // status: a failed root (the search left the tree inactive: arena exhausted at the root) or a terminal root is this request's own
 // error; a capacity error raised during the search (t.err) is blamed on every tree of the batch that is that close to full (a tree
 // whose push failed always is: node_upgrade refuses exactly when len + 8 > R or count + 8 > reserve could be exceeded).
-template <class G, bool FP>
+template <class G, int RR>
 __global__ __launch_bounds__(64) void k_slot_root_policy(TreeDev t, const SlotReq* __restrict__ req, int n, SlotOut* out) {
+    static_assert(RR != RR_GUMBEL, "never launched with Gumbel on: no such instantiation (AZ_FOR_RR)");
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
     const int tid = blockIdx.x * 64 + threadIdx.x;
@@ -1220,7 +1225,7 @@ __global__ __launch_bounds__(64) void k_slot_root_policy(TreeDev t, const SlotRe
         if (ecd != E_NONE) status = 1u << ERR_TERMINAL_ROOT;
         else if (full_err && (h.len + BLOCK_SLOTS > t.R || h.count + BLOCK_SLOTS > t.reserve_nodes)) status = 1u << ERR_CAPACITY;
         const typename G::State s = G::unpack(node_key(t, base, h.root));
-        rp = root_policy<G, FP ? RR_FORCED : RR_NONE>(t, h.root, g, sub, r.temp, r.seed, r.game_id, (uint64_t)G::stones(s));
+        rp = root_policy<G, RR>(t, h.root, g, sub, r.temp, r.seed, r.game_id, (uint64_t)G::stones(s));
     }
     if (sub < NA) {
         out[i].pi[sub] = rp.pi;
@@ -1359,9 +1364,9 @@ AZ_D int selfplay_move_body(const TreeDev& t, TreeHead& h, const GamesDev& gd, c
         }
         if constexpr (PC) {
             if (status != 2) {
-                next_word = status == 1 ? playout_cap_word(mp.seed, mp.first_game_id + (uint64_t)gd.gid[g], 0ull, t.cap.thresh24, t.cap.num_sims, t.cap.cap_sims)
-                                        : playout_cap_word(mp.seed, game_id, (uint64_t)ply + 1ull, t.cap.thresh24, t.cap.num_sims, t.cap.cap_sims);
-                t.cap.word[g] = next_word;
+                next_word = status == 1 ? playout_cap_word(mp.seed, mp.first_game_id + (uint64_t)gd.gid[g], 0ull, t.move.cap.thresh24, t.move.cap.num_sims, t.move.cap.cap_sims)
+                                        : playout_cap_word(mp.seed, game_id, (uint64_t)ply + 1ull, t.move.cap.thresh24, t.move.cap.num_sims, t.move.cap.cap_sims);
+                t.move.cap.word[g] = next_word;
                 atomicMax(&gd.counters[4], next_word & ~PLAYOUT_FULL_BIT);
             }
         }
@@ -1381,7 +1386,7 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
     TreeHead h = head_load(t, g);
     if (gi < 0 || !h.active) return;
     uint32_t word = 0u;
-    if constexpr (PC) word = t.cap.word[g];
+    if constexpr (PC) word = t.move.cap.word[g];
     if (selfplay_move_body<G, PC, RR>(t, h, gd, mp, g, sub, &word) == 2 && sub == 0) t.head[g].head.active = 0;
 }
 
@@ -1398,9 +1403,10 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
 //   first        the first launch behind a forward: eb_prev holds that forward's rows (parked trees back up; its table is cleared)
 // PC (playout cap): the slot's move ends at its own budget (the word of az_tree.h PlayoutCap, redrawn by every move), and its root gets the
 // noise only when the move is a full one.
-template <class G, bool NZ, bool MIR, bool PC, bool FP>
+template <class G, bool NZ, bool MIR, bool PC, int RR>
 __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec, SearchParams sp,
                                                     SelfplayMoveParams mp, int num_sims, int first, int max_iters) {
+    static_assert(RR != RR_GUMBEL, "never launched with Gumbel on: no such instantiation (AZ_FOR_RR)");
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;      // whole workgroups only (the launcher pads nothing: leaf_request synchronises)
     const int g = tid / GW, sub = tid % GW;
@@ -1414,7 +1420,7 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
     uint32_t* path = t.path + (size_t)g * PATH_CAP;
     int sims = gd.sims[g];
     uint32_t word = 0u;                                                        // PC: the word of the slot's current move
-    if constexpr (PC) word = t.cap.word[g];
+    if constexpr (PC) word = t.move.cap.word[g];
     const bool alive = gd.gid[g] >= 0 && h.active != 0 && !gd.need_reset[g];
     // a tree whose leaf waits for a row of the batch being filled stays parked; a leaf answered by the cache (or a value) can go on
     const bool parked = h.leaf_kind != LEAF_NONE && h.leaf_kind != LEAF_VALUE && !(h.src & SRC_CACHE) && !first;
@@ -1439,12 +1445,12 @@ __global__ __launch_bounds__(256) void k_async_step(TreeDev t, GamesDev gd, Eval
                 continue;
             }
             if (sims >= (PC ? (int)(word & ~PLAYOUT_FULL_BIT) : num_sims)) {      // the move (src/coach.rs:128-156), then the next position's root
-                const int st = selfplay_move_body<G, PC, FP ? RR_FORCED : RR_NONE>(t, h, gd, mp, g, sub, &word);
+                const int st = selfplay_move_body<G, PC, RR>(t, h, gd, mp, g, sub, &word);
                 sims = -1;
                 if (st != 0) break;                                            // episode over: idle, or wait for k_reset_trees
                 continue;
             }
-            leaf_s = select_body<G, false, FP ? RR_FORCED : RR_NONE>(t, h, pth, sp, g, sub, path, nullptr, true, !PC || (word & PLAYOUT_FULL_BIT) != 0u);
+            leaf_s = select_body<G, false, RR>(t, h, pth, sp, g, sub, path, nullptr, true, !PC || (word & PLAYOUT_FULL_BIT) != 0u);
             if (h.leaf_kind == LEAF_EVAL) { want = true; break; }
             if (h.leaf_kind == LEAF_NONE) ++sims;                              // an error cut the simulation short (flag set): it still counts
         }
@@ -1568,7 +1574,7 @@ __global__ void k_sync_active(TreeDev t, GamesDev gd) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= t.G) return;
     uint32_t a = gd.gid[g] >= 0 ? 1u : 0u;
-    if (a && t.cap.word) a |= (t.cap.word[g] & ~PLAYOUT_FULL_BIT) << 1;      // playout cap: the simulations the slot's move has left
+    if (a && t.move.cap.word) a |= (t.move.cap.word[g] & ~PLAYOUT_FULL_BIT) << 1;      // playout cap: the simulations the slot's move has left
     t.head[g].head.active = a;
 }
 
@@ -1587,7 +1593,7 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
 // ... and per root-noise setting: NZ = true only when the tree batch carries a non-zero eps
 #define AZ_FOR_GAME_NZ(t_, ...)                                                          \
     do {                                                                                 \
-        if ((t_).noise.eps != 0.0f) { constexpr bool NZ = true; AZ_FOR_GAME((t_).game, __VA_ARGS__); } \
+        if ((t_).move.noise.eps != 0.0f) { constexpr bool NZ = true; AZ_FOR_GAME((t_).game, __VA_ARGS__); } \
         else { constexpr bool NZ = false; AZ_FOR_GAME((t_).game, __VA_ARGS__); }         \
     } while (0)
 // ... and per "eval_mirror" setting of the leaf batch the launch requests into / backs up from (both batches of a search carry the same)
@@ -1599,28 +1605,24 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
 // ... and per playout cap: PC = true only for the searches of a self-play session that has one
 #define AZ_FOR_PC(t_, ...)                                                               \
     do {                                                                                 \
-        if ((t_).cap.word) { constexpr bool PC = true; __VA_ARGS__; }                    \
+        if ((t_).move.cap.word) { constexpr bool PC = true; __VA_ARGS__; }                    \
         else { constexpr bool PC = false; __VA_ARGS__; }                                 \
     } while (0)
-// ... and per forced playouts: FP = true only while the entry point's ForcedPlayouts record has k != 0
-#define AZ_FOR_FP(t_, ...)                                                               \
-    do {                                                                                 \
-        if ((t_).forced.k != 0.0f) { constexpr bool FP = true; __VA_ARGS__; }            \
-        else { constexpr bool FP = false; __VA_ARGS__; }                                 \
+// ... and per root rule: Gumbel while the entry point's record has gumbel.m != 0, else forced playouts while forced.k != 0 (the two exclude
+// each other), else today's kernels.  GZ = the baseline capture of a Gumbel move in the kernels that carry no selection; FP = the rule of
+// k_step_mt / k_async_step / k_slot_root_policy, which are never launched with Gumbel on (refused for T > 1 and selfplay_async, zero for
+// the slot calls): they take RR_OF_FP, so RR_GUMBEL resolves to their RR_NONE instantiation and no RR_GUMBEL one exists.
+#define AZ_FOR_RR(t_, ...)                                                                    \
+    do {                                                                                      \
+        if ((t_).move.gumbel.m != 0u) { AZ_WITH_RR(RR_GUMBEL, __VA_ARGS__); }                 \
+        else if ((t_).move.forced.k != 0.0f) { AZ_WITH_RR(RR_FORCED, __VA_ARGS__); }          \
+        else { AZ_WITH_RR(RR_NONE, __VA_ARGS__); }                                            \
     } while (0)
-// ... and per root rule: Gumbel while the entry point's Gumbel record has m != 0, else forced playouts while k != 0 (the two exclude
-// each other), else today's kernels.  GZ = the baseline capture of a Gumbel move in the kernels that carry no selection.
-#define AZ_FOR_RR(t_, ...)                                                               \
-    do {                                                                                 \
-        if ((t_).gumbel.m != 0u) { constexpr int RR = RR_GUMBEL; __VA_ARGS__; }          \
-        else if ((t_).forced.k != 0.0f) { constexpr int RR = RR_FORCED; __VA_ARGS__; }   \
-        else { constexpr int RR = RR_NONE; __VA_ARGS__; }                                \
-    } while (0)
-#define AZ_FOR_GZ(t_, ...)                                                               \
-    do {                                                                                 \
-        if ((t_).gumbel.m != 0u) { constexpr bool GZ = true; __VA_ARGS__; }              \
-        else { constexpr bool GZ = false; __VA_ARGS__; }                                 \
-    } while (0)
+#define AZ_WITH_RR(rr_, ...)                                                                  \
+    constexpr int RR = rr_; constexpr bool GZ = RR == RR_GUMBEL, FP = RR == RR_FORCED;        \
+    (void)RR; (void)GZ; (void)FP;                                                             \
+    __VA_ARGS__
+#define RR_OF_FP (FP ? RR_FORCED : RR_NONE)
 static inline int group_blocks(int G) { return (G * BLOCK_SLOTS + 63) / 64; }
 #ifdef AZ_DIAG
 // diagnostic library only: the PUCT term of best_child (src/node.rs:352-356) for n (child counter, prior bits, parent N) triples, as the
@@ -1666,10 +1668,10 @@ void launch_reset_trees(const TreeDev& t, const uint8_t* flags, hipStream_t s, c
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_reset_trees<TG>, dim3(t.G), dim3(256), 0, s, t, flags, const_cast<uint8_t*>(flags), roots));
 }
 void launch_root_prepare(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, const ulonglong2* root_states, hipStream_t s) {
-    AZ_FOR_GZ(t, AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_root_prepare<TG, NZ, MIR, GZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec, root_states)));
+    AZ_FOR_RR(t, AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_root_prepare<TG, NZ, MIR, GZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec, root_states)));
 }
 void launch_backup(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, hipStream_t s) {
-    AZ_FOR_GZ(t, AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_backup<TG, NZ, MIR, GZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec)));
+    AZ_FOR_RR(t, AZ_FOR_GAME_NZ_MIR(t, eb, hipLaunchKernelGGL((k_backup<TG, NZ, MIR, GZ>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb, ec)));
 }
 void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                           hipStream_t s) {
@@ -1686,7 +1688,7 @@ void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const Eval
 void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                     int first, int last, hipStream_t s) {
     // one wave per workgroup: leaf_request is called T times per launch and its one-atomic-per-workgroup path keeps state in LDS
-    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_step_mt<TG, NZ, MIR, PC, FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last))));
+    AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_step_mt<TG, NZ, MIR, PC, RR_OF_FP>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, eb_prev, eb_next, ec, sp, first, last))));
 }
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s) {
@@ -1712,7 +1714,7 @@ void launch_gumbel_values(int game, int n, uint64_t seed, const uint64_t* game_i
 }
 void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s) {
     if (n <= 0) return;
-    AZ_FOR_FP(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_slot_root_policy<TG, FP>), dim3(group_blocks(n)), dim3(64), 0, s, t, req, n, out)));
+    AZ_FOR_RR(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_slot_root_policy<TG, RR_OF_FP>), dim3(group_blocks(n)), dim3(64), 0, s, t, req, n, out)));
 }
 void launch_harvest(const TreeDev& t, unsigned long long* totals, uint32_t* node_counts, hipStream_t s) {
     hipLaunchKernelGGL(k_harvest, dim3((t.G + 255) / 256), dim3(256), 0, s, t, totals, node_counts);
@@ -1728,7 +1730,7 @@ void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s) {
     const bool four = t.block4 && (t.G * 8) % 256 == 0;
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
-    AZ_FOR_FP(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_async_step<TG, NZ, MIR, PC, FP>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters))));
+    AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_async_step<TG, NZ, MIR, PC, RR_OF_FP>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters))));
 }
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s) {
     hipLaunchKernelGGL(k_sync_active, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gd);

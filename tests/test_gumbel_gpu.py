@@ -252,6 +252,119 @@ def test_tree_call_parity(engine, shape, temp):
             t.close()
 
 
+SMALL = {"fused_search": 0, "search_graph": 4}      # per-simulation launches, four steps per captured graph: 16 simulations = four replays
+
+
+def c4_over(mine, theirs):
+    """The position is finished: the side that just moved (`theirs`) has four in a row, or the board is full."""
+    for d in (1, 6, 7, 8):
+        x = theirs & (theirs >> d)
+        if x & (x >> 2 * d):
+            return True
+    return bin(mine | theirs).count("1") == 42
+
+
+def test_tree_call_parity_with_root_noise(engine):
+    """Root noise 0.25 (default alpha) and gumbel_m 4 together on az_tree_get_action_prob: both consumers of a tree's one RNG stream in the
+    same call, through captured graphs.  8 trees play a whole game each, one call per ply (exploring variates on the first 6 plies, greedy
+    behind them; a finished game searches its last position again): pi, counts, q and the selected action are the twin's, bit for bit."""
+    sims, m, seed, G = 16, 4, 12, 8
+    for k, v in SMALL.items():
+        engine.set_option(k, v)
+    tb = engine.tree_create(G, reserve=gt.default_reserve(sims), num_sims=sims, max_depth=1000, model_id=10, cpuct=1)
+    twins = [gt.Tree(sims, net_kind=gt.NET_HASH, salt=oracle_salt(10)) for _ in range(G + 1)]
+    try:
+        engine.set_root_noise(0.25)
+        engine.set_gumbel(m)
+        states, done, calls = np.zeros((G, 2), np.uint64), [False] * G, 0
+        for ply in range(42):
+            temp = 1.0 if ply < 6 else 0.0
+            pi, counts, q = tb.get_action_prob(states, temp, seed=seed, first_game_id=40)
+            sel = tb.selected()
+            calls += 1
+            for g in range(G):
+                rpi, rc, rq, rsel, d = twins[g].get_action_prob(int(states[g, 0]), int(states[g, 1]), temp, seed, 40 + g, m=m, eps=0.25, alpha=1.0)
+                assert np.array_equal(counts[g], rc), (ply, g, counts[g], rc)
+                assert np.array_equal(q[g].view(np.uint32), rq.view(np.uint32)), (ply, g)
+                assert np.array_equal(pi[g].view(np.uint32), rpi.view(np.uint32)), (ply, g, pi[g], rpi)
+                assert sel[g] == rsel, (ply, g, sel[g], rsel)
+                if ply == 0 and g == 0:           # the noise really entered: the same call without it gives another policy
+                    qpi = twins[G].get_action_prob(0, 0, temp, seed, 40, m=m)[0]
+                    assert not np.array_equal(qpi, rpi)
+                if not done[g]:
+                    nxt = c4_play(int(states[g, 0]), int(states[g, 1]), int(sel[g]))
+                    if c4_over(*nxt):
+                        done[g] = True
+                    else:
+                        states[g] = nxt
+            if all(done):
+                break
+        ctr = {}
+        for t in twins[:G]:
+            ctr = gt.add_counters(ctr, gt.counters(t.ctr))
+        print(calls, ctr)
+        assert all(done) and calls > 6
+        assert ctr["no_considered"] == 0 and ctr["bad_schedule"] == 0 and ctr["moves"] == calls * G, ctr
+        assert ctr["root_not_puct"] >= 0.25 * ctr["root_sel"] and 0 < ctr["moves_g_zero"] < ctr["moves"], ctr
+    finally:
+        engine.set_option("search_graph", 20)
+        tb.close()
+        for t in twins:
+            t.close()
+
+
+def test_the_root_move_record_does_not_outlive_its_call(engine_mod):
+    """Engine A runs tree calls and a self-play with root noise and gumbel_m on, then sets both to 0; engine B never sets them.  The same
+    calls on both -- six tree calls on a re-rooted batch, one az_selfplay on the pooled arena A used with the keys on -- agree bit for bit."""
+    sims, G = 16, 8
+    sp = dict(n_games=G, num_sims=sims, model_id=10, seed=5, first_game_id=1000, concurrent=G)
+    eng, tbs = [], []
+    try:
+        for _ in range(2):
+            e = engine_mod.Engine(device=0, max_batch=256, net_channels=128)
+            eng.append(e)
+            e.net_set_kind(10, engine_mod.NET_HASH, HASH_SALT)
+            for k, v in SMALL.items():
+                e.set_option(k, v)
+            tbs.append(e.tree_create(G, reserve=gt.default_reserve(sims), num_sims=sims, max_depth=1000, model_id=10, cpuct=1))
+        a, b = eng
+        a.set_root_noise(0.25)
+        a.set_gumbel(4)
+        zeros = np.zeros((G, 2), np.uint64)
+        for _ in range(2):
+            tbs[0].get_action_prob(zeros, 1.0, seed=3, first_game_id=40)
+        assert (tbs[0].selected() >= 0).all()                       # they were Gumbel moves
+        a.set_option("root_noise_eps_e6", 0)
+        a.set_option("gumbel_m", 0)
+        tbs[0].reset()
+        st = [zeros.copy(), zeros.copy()]
+        for call in range(6):
+            outs = [tb.get_action_prob(s, 1.0 if call < 4 else 0.0, seed=3, first_game_id=40) for tb, s in zip(tbs, st)]
+            for x, y in zip(*outs):                                 # pi, counts, q
+                assert np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8)), call
+            assert (tbs[0].selected() == -1).all() and (tbs[1].selected() == -1).all()
+            st = [np.array([c4_play(int(r[0]), int(r[1]), int(np.argmax(c))) for r, c in zip(s, o[1])], np.uint64) for s, o in zip(st, outs)]
+        assert (outs[0][1].sum(axis=1) > 0).all()
+        # through the pool: the arena of A's first az_selfplay (keys on) serves its second one (keys off)
+        a.set_root_noise(0.25)
+        a.set_gumbel(4)
+        keys = ("count", "game_len", "moves", "states", "boards", "pis", "zs")
+        on = a.selfplay(**sp)
+        a.set_option("root_noise_eps_e6", 0)
+        a.set_option("gumbel_m", 0)
+        allocs = a.stats()["tree_arena_allocs"]
+        off_a = a.selfplay(**sp)
+        assert a.stats()["tree_arena_allocs"] == allocs             # the pooled arena was reused
+        off_b = b.selfplay(**sp)
+        fg.assert_same_outputs([off_a[k] for k in keys], [off_b[k] for k in keys])
+        assert not np.array_equal(on["moves"], off_a["moves"])      # the keys really changed the games while they were on
+    finally:
+        for tb in tbs:
+            tb.close()
+        for e in eng:
+            e.close()
+
+
 # ---- off is off, and the arena never sees it --------------------------------------------------------------------------------------------------------------
 def _plain_outputs(e):
     e.reset_stats()
