@@ -82,6 +82,12 @@ class Coach:
         # unless it is the canonical one; meant to go with eval_mirror, which evaluates on that orientation.  False (the default): the
         # engine is never asked
         self.merge_positions, self.merge_canonical = False, False
+        # The optimiser rules of NNet::train (Engine.set_train_optim): decoupled weight decay, gradient-norm clipping, warm-up and decay of
+        # the learning rate (lr_decay 0 none / 1 cosine / 2 linear, over the call's own steps) and an averaged shadow of the weights, set
+        # before the iteration's one az_net_train and cleared behind it.  With ema_decay > 0 the candidate -- what the arena gates, what
+        # is saved as <id>.aznet and what the next iteration trains from -- is the averaged model (Engine.train_ema).  All 0 (the
+        # default): the engine is never asked
+        self.weight_decay, self.clip_norm, self.lr_warmup_steps, self.lr_decay, self.lr_floor, self.ema_decay = 0.0, 0.0, 0, 0, 0.0, 0.0
         # Move-quality report (Engine.move_quality): after every iteration's arena its games are replayed, every position with at least
         # solve_min_stones stones is solved exactly (budget solve_max_nodes per position and action) and the move played there classed; the
         # tally per model goes into the report ("quality") and one log line.  It decides nothing: the gate, the checkpoints, the .examples
@@ -145,6 +151,12 @@ class Coach:
     def _selfplay_gumbel(self):
         return self._scoped(self.gumbel_m > 0, lambda: self.engine.set_gumbel(self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale),
                             lambda: self.engine.set_gumbel(0))
+
+    def _train_optim(self):
+        on = self.weight_decay > 0 or self.clip_norm > 0 or self.lr_warmup_steps > 0 or self.lr_decay != 0 or self.ema_decay > 0
+        return self._scoped(on, lambda: self.engine.set_train_optim(self.weight_decay, self.clip_norm, self.lr_warmup_steps, self.lr_decay,
+                                                                    self.lr_floor, self.ema_decay),
+                            lambda: self.engine.set_train_optim())
 
     def _arena_openings(self):
         return self._scoped(self.arena_opening_plies > 0, lambda: self.engine.set_arena_openings(self.arena_opening_plies),
@@ -234,7 +246,10 @@ class Coach:
             t0 = time.perf_counter()
             if self.trainer is None:                                    # :329 -> NNet::train(samples, id, id + 1)
                 self.engine.set_option("train_seed", seed + iteration)
-                losses = self.engine.train(model_id, model_id + 1, allb, allp, allv)
+                with self._train_optim():
+                    losses = self.engine.train(model_id, model_id + 1, allb, allp, allv)
+                if self.ema_decay > 0:                                  # the candidate is the averaged model
+                    self.engine.train_ema(model_id + 1)
             else:
                 prev = self.engine.net_get_params(model_id)
                 new = self.trainer.train(prev, allb, allp, allv, seed=seed + iteration)

@@ -24,6 +24,7 @@
 #include "az_local_comm.h"
 #include "az_merge.h"
 #include "az_net.h"
+#include "az_optim.h"
 #include "az_solve.h"
 #include "az_train.h"
 #include "az_tree.h"
@@ -392,6 +393,11 @@ struct az_engine {
     int train_fork = 0;             // "train_fork": the wgrad chains of a step on a second stream branch (csrc/az_train.hip)
     int train_fwd_dma = 1;
     std::vector<float> train_history;              // (loss_pi, loss_v) mean per epoch of the last az_net_train
+    // the opt-in optimiser rules (csrc/az_optim.h), read by az_net_train_begin: "train_weight_decay_e9", "train_clip_norm_e6",
+    // "train_lr_warmup_steps", "train_lr_decay", "train_lr_floor_e6", "train_lr_total_steps", "train_ema_decay_e9"
+    int64_t train_weight_decay_e9 = 0, train_clip_norm_e6 = 0, train_lr_warmup_steps = 0, train_lr_decay = 0, train_lr_floor_e6 = 0,
+            train_lr_total_steps = 0, train_ema_decay_e9 = 0;
+    bool train_ema_session = false;                // the last az_net_train_begin saw "train_ema_decay_e9" > 0
     // leaf de-duplication + evaluation cache (az_set_option "eval_dedup", "eval_cache_log2", "eval_cache_max_stones",
     // "eval_cache_persist")
     int profile_every = 1;          // profile mode: bracket every n-th simulation step ("profile_every")
@@ -1183,6 +1189,23 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     if (is("train_fwd_dma") && (value == 0 || value == 1)) { e->train_fwd_dma = (int)value; if (e->trainer) trainer_set_fwd_dma(e->trainer, value != 0); return AZ_OK; }
     if (is("train_lr_e9") && value > 0) { e->hyper.lr = (float)((double)value * 1e-9); return AZ_OK; }
     if (is("train_dropout_e6") && value >= 0 && value < 1000000) { e->hyper.dropout = (float)((double)value * 1e-6); return AZ_OK; }
+    // the opt-in optimiser rules (csrc/az_optim.h): one range per key, read by the next az_net_train_begin
+    struct OptimKey { const char* key; int64_t lo, hi; bool or_zero; int64_t az_engine::* field; const char* range; };
+    static const OptimKey optim_keys[] = {
+        {"train_weight_decay_e9", 0, OPTIM_WD_E9_MAX, false, &az_engine::train_weight_decay_e9, "train_weight_decay_e9 must be in 0 .. 1000000000"},
+        {"train_clip_norm_e6", 1, OPTIM_CLIP_E6_MAX, true, &az_engine::train_clip_norm_e6, "train_clip_norm_e6 must be 0 or in 1 .. 1000000000000"},
+        {"train_lr_warmup_steps", 0, OPTIM_STEPS_MAX, false, &az_engine::train_lr_warmup_steps, "train_lr_warmup_steps must be in 0 .. 2147483647"},
+        {"train_lr_decay", 0, 2, false, &az_engine::train_lr_decay, "train_lr_decay must be 0, 1 or 2"},
+        {"train_lr_floor_e6", 0, OPTIM_FLOOR_E6_MAX, false, &az_engine::train_lr_floor_e6, "train_lr_floor_e6 must be in 0 .. 1000000"},
+        {"train_lr_total_steps", 0, OPTIM_STEPS_MAX, false, &az_engine::train_lr_total_steps, "train_lr_total_steps must be in 0 .. 2147483647"},
+        {"train_ema_decay_e9", 1, OPTIM_EMA_E9_MAX, true, &az_engine::train_ema_decay_e9, "train_ema_decay_e9 must be 0 or in 1 .. 999999999"},
+    };
+    for (const OptimKey& r : optim_keys) {
+        if (!is(r.key)) continue;
+        if ((value < r.lo || value > r.hi) && !(r.or_zero && value == 0)) return fail(e, AZ_ERR_BAD_ARGUMENT, r.range);
+        e->*r.field = value;
+        return AZ_OK;
+    }
 #ifdef AZ_DIAG
     // ---- libaz_engine_diag.so only: superseded kernel generations, forced tiles, clock-stamp builds (every one bit-identical to the shipped kernels) ----
     NetOptions& o = e->netopt;
@@ -1521,6 +1544,17 @@ az_status az_net_train_begin(az_engine* e, int32_t previous_model_id) {
         std::vector<float> p((size_t)n);
         if (!convnet_get_params(m->conv, p.data(), n)) return fail(e, AZ_ERR_BAD_ARGUMENT, "parameter count mismatch");
         if (!trainer_set_params(e->trainer, p.data(), n)) return fail(e, AZ_ERR_HIP, "trainer_set_params failed");
+        TrainOptim o;
+        o.weight_decay = (float)((double)e->train_weight_decay_e9 / 1e9);
+        o.clip_norm = (double)e->train_clip_norm_e6 / 1e6;
+        o.warmup = e->train_lr_warmup_steps;
+        o.decay = (int)e->train_lr_decay;
+        o.floor = (double)e->train_lr_floor_e6 / 1e6;
+        o.total = e->train_lr_total_steps;
+        o.ema = (float)((double)e->train_ema_decay_e9 / 1e9);
+        e->train_ema_session = false;
+        if (!trainer_set_optim(e->trainer, o)) return fail(e, AZ_ERR_HIP, "trainer_set_optim failed");
+        e->train_ema_session = o.ema > 0.0f;
         e->train_open = true;
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
@@ -1579,6 +1613,7 @@ az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id
         std::vector<int64_t> idx((size_t)steps * b);
         Trainer* t = e->trainer;
         e->train_history.clear();
+        if (!trainer_set_lr_table(t, e->hyper, (int64_t)e->train_epochs * steps, e->stream)) return fail(e, AZ_ERR_HIP, "trainer_set_lr_table failed");
         uint64_t gstep = 0;
         for (int epoch = 0; epoch < e->train_epochs; ++epoch) {
             // batches are drawn with replacement (np.random.randint, :130), from the build's counter RNG
@@ -1600,6 +1635,26 @@ az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id
         HIPCHK(hipStreamSynchronize(e->stream));
     } catch (const HipFail& f) { e->train_open = false; return fail_hip(e, f); }
     return az_net_train_end(e, model_id);
+}
+
+az_status az_net_train_ema(az_engine* e, int32_t model_id) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!e->trainer || !e->train_ema_session)
+        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_ema: the last az_net_train_begin did not see \"train_ema_decay_e9\" > 0");
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        const int64_t n = az_net_param_count(e);
+        std::vector<float> p((size_t)n);
+        if (!trainer_get_ema(e->trainer, p.data(), n, e->stream)) return fail(e, AZ_ERR_HIP, "trainer_get_ema failed");
+        return az_net_set_params(e, model_id, p.data(), n);
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+az_status az_net_train_step_info(const az_engine* e, double out[4]) {
+    if (!e || !out) return AZ_ERR_BAD_ARGUMENT;
+    if (!e->trainer) return AZ_ERR_BAD_ARGUMENT;
+    if (hipSetDevice(e->device) != hipSuccess || !trainer_step_info(e->trainer, out, e->stream)) return AZ_ERR_HIP;
+    return AZ_OK;
 }
 
 int32_t az_net_train_history(const az_engine* e, float* out, int32_t cap_epochs) {

@@ -21,6 +21,19 @@ struct TrainHyper {
     float dropout = 0.3f;        // connect_four_net.py:15
 };
 
+// The opt-in optimiser rules of one training session (az_optim.h; include/az_engine.h "train_weight_decay_e9" ...).  All off (the
+// default): a step ends in the plain Adam kernel.
+struct TrainOptim {
+    float weight_decay = 0.0f;   // decoupled (torch.optim.AdamW), on the weight tensors only
+    double clip_norm = 0.0;      // 0 = off; else torch.nn.utils.clip_grad_norm_ over the whole gradient
+    int64_t warmup = 0;          // linear warm-up over that many applied steps
+    int decay = 0;               // 0 none / 1 cosine / 2 linear, down to floor x lr at step `total`
+    double floor = 0.0;
+    int64_t total = 0;           // the step entries' horizon; trainer_set_lr_table's callers use their own
+    float ema = 0.0f;            // 0 = off; else the decay of the averaged shadow weights
+    bool on() const { return weight_decay > 0.0f || clip_norm > 0.0 || warmup > 0 || decay != 0 || ema > 0.0f; }
+};
+
 constexpr int TRAIN_MAX_BATCH = 256;
 
 Trainer* trainer_create(int channels, const char** err);
@@ -28,6 +41,14 @@ void trainer_destroy(Trainer* t);
 // host f32 parameters in weights-file order; resets the Adam moments and the step counter
 bool trainer_set_params(Trainer* t, const float* host_params, int64_t count);
 bool trainer_get_params(Trainer* t, float* host_params, int64_t count, hipStream_t s);
+// the optimiser rules of the session trainer_set_params opened (which resets them to all-off); the shadow starts at the parameters
+bool trainer_set_optim(Trainer* t, const TrainOptim& o);
+// with the rules on: the schedule of a trainer_run_epoch sequence of `steps` steps in all (step i of it runs at entry i); synchronises
+bool trainer_set_lr_table(Trainer* t, const TrainHyper& h, int64_t steps, hipStream_t s);
+// the averaged weights (the moving averages are the live ones); false unless the session's rules have ema > 0
+bool trainer_get_ema(Trainer* t, float* host_params, int64_t count, hipStream_t s);
+// {gradient norm (-1 with clipping off), clip factor (1), learning rate, applied steps since trainer_set_params} of the last step
+bool trainer_step_info(Trainer* t, double out[4], hipStream_t s);
 // One optimisation step on a device-resident batch: boards [b][2][6][7], pis [b][7], vs [b] (f32).
 // mask_seed keys the dropout masks of this step (hash of (mask_seed, layer, element): az_common.h dropout_keep).
 // apply = false computes the loss and the gradients only.  The per-step losses are accumulated on the device

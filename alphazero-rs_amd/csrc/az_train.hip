@@ -11,6 +11,8 @@
 //          --GEMM--> zf1 -BN,ReLU,dropout-> af1 --GEMM--> zf2 -BN,ReLU,dropout-> af2 -> (logits, v) -> loss
 //   and back: heads -> BN/ReLU/dropout backward (two-stage column sums) -> wgrad GEMM (A^T dz), dgrad GEMM
 //   (dz W^T) -> col2im -> previous layer ...; then one Adam kernel over the flat vector.
+//   Opt-in (az_optim.h; "train_weight_decay_e9" ... "train_ema_decay_e9", all off by default): that last kernel is k_adamw instead --
+//   clipped gradient, decoupled weight decay, a scheduled learning rate, an averaged shadow -- behind k_grad_sqnorm when clipping is on.
 //
 // Parameters, activations (row-major [rows][channels], rows = (sample, y, x)), gradients and the optimiser state are f32; k_gemm_f32
 // (v_mfma_f32_16x16x4_f32, 64 x 64 or 128 x 128 block tiles, deterministic split-K) runs the forward GEMMs and, with "train_gemm" = 0,
@@ -24,6 +26,7 @@
 
 #include "az_common.h"
 #include "az_net.h"
+#include "az_optim.h"
 
 namespace az {
 
@@ -962,6 +965,8 @@ struct StepState {
     uint64_t mask_seed;     // keys the dropout masks of this step
     float bc1, sqrt_bc2;    // Adam bias corrections 1 - beta1^t, sqrt(1 - beta2^t)
     int64_t idx_offset;     // first row of this step's batch in the epoch's index array
+    float lr_t;             // k_adamw only: the scheduled learning rate of this step (az_optim.h optim_lr, evaluated on the host)
+    float pad_;
 };
 
 // epoch driver state: k_step_advance derives each step's StepState on the device
@@ -972,8 +977,7 @@ struct EpochCounters {
     double beta1, beta2;
     double pow1, pow2;      // beta1^t, beta2^t as running products (the host keeps the same products: Trainer::pow1/2)
 };
-__global__ void k_step_advance(StepState* st, EpochCounters* c, int b) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+AZ_D void step_advance(StepState* st, EpochCounters* c, int b) {
     st->mask_seed = mix64(c->seed_key ^ c->gstep);
     c->pow1 *= c->beta1;
     c->pow2 *= c->beta2;
@@ -982,6 +986,16 @@ __global__ void k_step_advance(StepState* st, EpochCounters* c, int b) {
     st->idx_offset = c->epoch_step * b;
     c->gstep += 1;
     c->epoch_step += 1;
+}
+__global__ void k_step_advance(StepState* st, EpochCounters* c, int b) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    step_advance(st, c, b);
+}
+// the opt-in optimiser rules only: also the step's learning rate, from the call's table [epochs x steps] by the global step
+__global__ void k_step_advance_sched(StepState* st, EpochCounters* c, int b, const float* __restrict__ lr_table) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    st->lr_t = lr_table[c->gstep];
+    step_advance(st, c, b);
 }
 
 // ---- data movement -------------------------------------------------------------------------------------------
@@ -1550,6 +1564,107 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
     }
 }
 
+// ---- the opt-in optimiser rules (az_optim.h): gradient-norm clipping, decoupled weight decay, a scheduled lr, an averaged shadow ------
+// Sum of squares of g[0 .. n) in f64: block k sums the fixed chunk [k * chunk, (k + 1) * chunk) (chunk a multiple of 4) -- a thread its
+// strided float4s in order, a wave by a fixed shuffle tree, the block's waves in wave order -- into partial[k].  The consumer
+// (k_adamw's prologue) adds the GRAD_PARTS partials in index order: no atomics, the same bits whatever the schedule.
+constexpr int GRAD_PARTS = 256, GRAD_BLOCK = 1024;
+__global__ __launch_bounds__(GRAD_BLOCK) void k_grad_sqnorm(const float* __restrict__ g, int64_t n, int64_t chunk, double* __restrict__ partial) {
+    __shared__ double wsum[GRAD_BLOCK / 64];
+    const int64_t lo0 = (int64_t)blockIdx.x * chunk, lo = lo0 < n ? lo0 : n, hi = lo + chunk < n ? lo + chunk : n;
+    const int64_t nv = (hi - lo) >> 2;      // whole float4s of the chunk (lo is a multiple of 4; only the array's last chunk has a tail)
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    const float4* gv = (const float4*)(g + lo);
+#pragma unroll 4
+    for (int64_t i = threadIdx.x; i < nv; i += GRAD_BLOCK) {
+        const float4 x = gv[i];
+        a0 += (double)x.x * (double)x.x; a1 += (double)x.y * (double)x.y; a2 += (double)x.z * (double)x.z; a3 += (double)x.w * (double)x.w;
+    }
+    double a = (a0 + a1) + (a2 + a3);
+    if (threadIdx.x == 0)
+        for (int64_t i = lo + nv * 4; i < hi; ++i) a += (double)g[i] * (double)g[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < GRAD_BLOCK / 64; ++w) s += wsum[w];
+        partial[blockIdx.x] = s;
+    }
+}
+
+// what k_adamw needs beside k_adam's arguments; everything that changes from step to step comes from device memory (StepState, partial)
+struct AdamW {
+    float wd;                   // decoupled decay: p *= 1 - lr_t * wd on the segments that decay
+    float ema;                  // EMA only: s = ema * s + (1 - ema) * p on the trainable segments
+    double clip;                // with partial: c of optim_clip_scale
+    const double* partial;      // k_grad_sqnorm's GRAD_PARTS sums, nullptr = no clipping (scale 1)
+    float* shadow;              // EMA only
+};
+template <bool EMA>
+AZ_D void adamw_elem(float& p, float g, float& m, float& v, float& s, bool decays, bool trainable, float scale, float lr, float b1, float b2,
+                     float eps, float bc1, float sqrt_bc2, float wd, float ema) {
+    const float gi = g * scale;
+    const float mi = b1 * m + (1.0f - b1) * gi;
+    const float vi = b2 * v + (1.0f - b2) * gi * gi;
+    m = mi; v = vi;
+    float pi = p;
+    if (decays) pi *= 1.0f - lr * wd;
+    pi -= (lr / bc1) * mi / (sqrtf(vi) / sqrt_bc2 + eps);
+    p = pi;
+    if (EMA && trainable) s = ema * s + (1.0f - ema) * pi;
+}
+// One pass over the flat vector, float4 wide.  Segment boundaries are not 16-byte aligned behind pi_b (7 floats) and L.total is odd: a
+// vector whose ends lie in different segments classifies each of its elements, the last n % 4 elements go one by one.
+template <bool EMA>
+__global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                               const Layout L, float b1, float b2, float eps, const AdamW o, const StepState* __restrict__ st) {
+    static_assert(GRAD_PARTS == 256, "one partial per thread of the block");
+    __shared__ double part[GRAD_PARTS];
+    __shared__ float sh_scale;
+    float scale = 1.0f;
+    if (o.partial) {      // uniform
+        // the partials are loaded together (one per thread) and added in index order by one thread: 256 dependent adds fed from LDS,
+        // not a chain of dependent global loads
+        part[threadIdx.x] = o.partial[threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double s = 0.0;
+#pragma unroll 16
+            for (int k = 0; k < GRAD_PARTS; ++k) s += part[k];
+            sh_scale = optim_clip_scale(sqrt(s), o.clip);
+        }
+        __syncthreads();
+        scale = sh_scale;
+    }
+    const float bc1 = st->bc1, sqrt_bc2 = st->sqrt_bc2, lr = st->lr_t;
+    const int64_t n = L.total, nv = n >> 2;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nv; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = j << 2;
+        const float4 g4 = ((const float4*)g)[j];
+        float4 m4 = ((float4*)m)[j], v4 = ((float4*)v)[j], p4 = ((float4*)p)[j], s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (EMA) s4 = ((float4*)o.shadow)[j];
+        const int sa = optim_segment(L, i), sb = optim_segment(L, i + 3);
+        int s1 = sa, s2 = sa;
+        if (sa != sb) { s1 = optim_segment(L, i + 1); s2 = optim_segment(L, i + 2); }
+        adamw_elem<EMA>(p4.x, g4.x, m4.x, v4.x, s4.x, optim_segment_decays(sa), optim_segment_trainable(sa), scale, lr, b1, b2, eps, bc1, sqrt_bc2, o.wd, o.ema);
+        adamw_elem<EMA>(p4.y, g4.y, m4.y, v4.y, s4.y, optim_segment_decays(s1), optim_segment_trainable(s1), scale, lr, b1, b2, eps, bc1, sqrt_bc2, o.wd, o.ema);
+        adamw_elem<EMA>(p4.z, g4.z, m4.z, v4.z, s4.z, optim_segment_decays(s2), optim_segment_trainable(s2), scale, lr, b1, b2, eps, bc1, sqrt_bc2, o.wd, o.ema);
+        adamw_elem<EMA>(p4.w, g4.w, m4.w, v4.w, s4.w, optim_segment_decays(sb), optim_segment_trainable(sb), scale, lr, b1, b2, eps, bc1, sqrt_bc2, o.wd, o.ema);
+        ((float4*)m)[j] = m4; ((float4*)v)[j] = v4; ((float4*)p)[j] = p4;
+        if (EMA) ((float4*)o.shadow)[j] = s4;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t i = (nv << 2) + threadIdx.x;
+        const int sg = optim_segment(L, i);
+        float s = EMA ? o.shadow[i] : 0.0f;
+        adamw_elem<EMA>(p[i], g[i], m[i], v[i], s, optim_segment_decays(sg), optim_segment_trainable(sg), scale, lr, b1, b2, eps, bc1, sqrt_bc2, o.wd, o.ema);
+        if (EMA) o.shadow[i] = s;
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------
 struct Trainer {
     int C = 512;
@@ -1600,6 +1715,15 @@ struct Trainer {
     size_t splitk2_floats = 0;
     int64_t step = 0;
     double pow1 = 1.0, pow2 = 1.0;     // beta1^step, beta2^step
+    // the opt-in optimiser rules (az_optim.h; trainer_set_optim): while optim.on() a step ends in k_adamw instead of k_adam, behind
+    // k_grad_sqnorm when clipping is on
+    TrainOptim optim;
+    double* grad_partial = nullptr;    // [GRAD_PARTS]
+    float* shadow = nullptr;           // [L.total]: the averaged weights, allocated by the first session that asks for them
+    float* lr_table = nullptr;         // az_net_train's schedule, one f32 per step of the call
+    int64_t lr_table_cap = 0;
+    std::vector<float> host_lr_table;
+    float last_lr = 0.0f;              // lr_t of the last step
     template <class T> T* dalloc(size_t n) {
         void* p = nullptr;
         if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
@@ -1648,6 +1772,7 @@ Trainer* trainer_create(int channels, const char** err) {
     ok &= hipHostMalloc((void**)&t->host_state, HOST_STATE_RING * sizeof(StepState), hipHostMallocDefault) == hipSuccess;
     ok &= (t->counters = t->dalloc<EpochCounters>(1)) != nullptr;
     ok &= (t->act_scale = t->dalloc<float>(8)) != nullptr;
+    ok &= (t->grad_partial = t->dalloc<double>(GRAD_PARTS)) != nullptr;
     {
         const size_t NM = std::max<size_t>(C, 1024), Mp = (B * 42 + 63) / 64 * 64;
         for (uint16_t** q : {&t->w_hi, &t->w_lo}) ok &= (*q = t->dalloc<uint16_t>(T)) != nullptr;
@@ -1701,6 +1826,62 @@ bool trainer_set_params(Trainer* t, const float* host_params, int64_t count) {
         return false;
     t->step = 0;
     t->pow1 = t->pow2 = 1.0;
+    t->optim = TrainOptim{};
+    t->last_lr = 0.0f;
+    return true;
+}
+
+bool trainer_set_optim(Trainer* t, const TrainOptim& o) {
+    if (!t) return false;
+    if (o.ema > 0.0f) {
+        const size_t bytes = (size_t)t->L.total * sizeof(float);
+        if (!t->shadow && !(t->shadow = t->dalloc<float>((size_t)t->L.total))) return false;
+        if (hipMemcpy(t->shadow, t->params, bytes, hipMemcpyDeviceToDevice) != hipSuccess) return false;      // no de-biasing: the average starts at the weights
+    }
+    if (hipMemset(t->grad_partial, 0, GRAD_PARTS * sizeof(double)) != hipSuccess) return false;
+    t->optim = o;
+    return true;
+}
+
+bool trainer_set_lr_table(Trainer* t, const TrainHyper& h, int64_t steps, hipStream_t s) {
+    if (!t || steps <= 0) return false;
+    if (!t->optim.on()) return true;
+    const TrainOptim& o = t->optim;
+    t->host_lr_table.resize((size_t)steps);
+    for (int64_t i = 0; i < steps; ++i) t->host_lr_table[(size_t)i] = optim_lr(h.lr, i + 1, o.warmup, steps, o.decay, o.floor);
+    if (steps > t->lr_table_cap) {
+        if (!(t->lr_table = t->dalloc<float>((size_t)steps))) return false;      // the smaller one stays in `dev` until trainer_destroy
+        t->lr_table_cap = steps;
+    }
+    if (hipMemcpyAsync(t->lr_table, t->host_lr_table.data(), (size_t)steps * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return false;
+    return hipStreamSynchronize(s) == hipSuccess;
+}
+
+bool trainer_get_ema(Trainer* t, float* host_params, int64_t count, hipStream_t s) {
+    if (!t || count != t->L.total || !t->shadow || !(t->optim.ema > 0.0f)) return false;
+    if (hipStreamSynchronize(s) != hipSuccess) return false;
+    const size_t bytes = (size_t)count * sizeof(float);
+    if (hipMemcpy(host_params, t->shadow, bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    // the moving averages are no optimiser state: the live trainer's
+    std::vector<float> live((size_t)count);
+    if (hipMemcpy(live.data(), t->params, bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (int64_t i = 0; i < count; ++i)
+        if (!optim_trainable(t->L, i)) host_params[i] = live[(size_t)i];
+    return true;
+}
+
+bool trainer_step_info(Trainer* t, double out[4], hipStream_t s) {
+    if (!t) return false;
+    out[0] = -1.0; out[1] = 1.0; out[2] = (double)t->last_lr; out[3] = (double)t->step;
+    if (t->optim.clip_norm > 0.0) {
+        double part[GRAD_PARTS];
+        if (hipStreamSynchronize(s) != hipSuccess) return false;
+        if (hipMemcpy(part, t->grad_partial, sizeof part, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        double sum = 0.0;
+        for (int k = 0; k < GRAD_PARTS; ++k) sum += part[k];      // k_adamw's order
+        out[0] = std::sqrt(sum);
+        out[1] = (double)optim_clip_scale(out[0], t->optim.clip_norm);
+    }
     return true;
 }
 
@@ -2050,6 +2231,20 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
         }
     }
     hand(t->ev_join, s2, s);
+    if (t->optim.on()) {
+        const TrainOptim& o = t->optim;
+        const bool clip = o.clip_norm > 0.0;
+        if (clip) {
+            const int64_t chunk = ((L.total + GRAD_PARTS - 1) / GRAD_PARTS + 3) / 4 * 4;
+            hipLaunchKernelGGL(k_grad_sqnorm, dim3(GRAD_PARTS), dim3(GRAD_BLOCK), 0, s, G, L.total, chunk, t->grad_partial);
+        }
+        if (apply) {
+            const AdamW a{o.weight_decay, o.ema, o.clip_norm, clip ? t->grad_partial : nullptr, t->shadow};
+            if (o.ema > 0.0f) hipLaunchKernelGGL((k_adamw<true>), grid1(L.total / 4), dim3(256), 0, s, P, G, t->m, t->v, L, h.beta1, h.beta2, h.adam_eps, a, st);
+            else hipLaunchKernelGGL((k_adamw<false>), grid1(L.total / 4), dim3(256), 0, s, P, G, t->m, t->v, L, h.beta1, h.beta2, h.adam_eps, a, st);
+        }
+        return;
+    }
     if (apply)
         hipLaunchKernelGGL(k_adam, grid1(L.total), dim3(256), 0, s, P, G, t->m, t->v, L.total, h.lr, h.beta1, h.beta2, h.adam_eps, st);
 }
@@ -2065,6 +2260,9 @@ bool trainer_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
     st.bc1 = (float)(1.0 - p1);
     st.sqrt_bc2 = sqrtf((float)(1.0 - p2));
     st.idx_offset = 0;
+    st.lr_t = t->optim.on() ? optim_lr(h.lr, t->step + 1, t->optim.warmup, t->optim.total, t->optim.decay, t->optim.floor) : h.lr;
+    st.pad_ = 0.0f;
+    t->last_lr = st.lr_t;
     if (hipMemcpyAsync(t->step_state, &st, sizeof st, hipMemcpyHostToDevice, s) != hipSuccess) return false;
     enqueue_step(t, h, d_boards, d_pis, d_vs, b, apply, s);
     if (apply) { t->step += 1; t->pow1 = p1; t->pow2 = p2; }
@@ -2074,11 +2272,14 @@ bool trainer_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
 bool trainer_run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards, const float* all_pis, const float* all_vs,
                        const int64_t* d_idx, int64_t steps, int b, uint64_t seed_key, uint64_t gstep0, hipStream_t s) {
     if (!t || b <= 1 || b > TRAIN_MAX_BATCH || steps <= 0) return false;
+    const bool sched = t->optim.on();
+    if (sched && (int64_t)t->host_lr_table.size() < (int64_t)gstep0 + steps) return false;      // trainer_set_lr_table covers the whole call
     EpochCounters c{seed_key, gstep0, 0, (double)h.beta1, (double)h.beta2, t->pow1, t->pow2};
     if (hipMemcpyAsync(t->counters, &c, sizeof c, hipMemcpyHostToDevice, s) != hipSuccess) return false;
     if (hipStreamSynchronize(s) != hipSuccess) return false;      // `c` is a stack object
     auto one_step = [&]() {
-        hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(64), 0, s, t->step_state, t->counters, b);
+        if (sched) hipLaunchKernelGGL(k_step_advance_sched, dim3(1), dim3(64), 0, s, t->step_state, t->counters, b, (const float*)t->lr_table);
+        else hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(64), 0, s, t->step_state, t->counters, b);
         hipLaunchKernelGGL(k_gather_col1, dim3((b * 42 * 20 + 255) / 256), dim3(256), 0, s, all_boards, all_pis, all_vs, d_idx, b, t->bboards,
                            t->bpis, t->bvs, t->col[0], (const StepState*)t->step_state);
         enqueue_step(t, h, t->bboards, t->bpis, t->bvs, b, true, s, true);
@@ -2102,6 +2303,7 @@ bool trainer_run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards,
     if (exec) (void)hipGraphExecDestroy(exec);
     if (graph) (void)hipGraphDestroy(graph);
     t->step += steps;
+    if (sched) t->last_lr = t->host_lr_table[(size_t)((int64_t)gstep0 + steps - 1)];
     for (int64_t i = 0; i < steps; ++i) { t->pow1 *= (double)h.beta1; t->pow2 *= (double)h.beta2; }
     return ok;
 }

@@ -87,7 +87,7 @@ EXPORTS = [
     "az_net_set_class", "az_net_get_class",
     "az_net_init_random", "az_net_load", "az_net_save", "az_net_param_count", "az_net_set_params",
     "az_net_get_params", "az_net_predict", "az_net_predict_states", "az_net_train", "az_net_train_history",
-    "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_tree_create",
+    "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_net_train_ema", "az_net_train_step_info", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
     "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_tree_get_selected", "az_gumbel_values", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
@@ -128,6 +128,8 @@ def load_library(path=LIB_PATH):
         "az_net_train_begin": (i32, [vp, i32]),
         "az_net_train_step": (i32, [vp, vp, vp, vp, i32, u64, i32, vp, vp]),
         "az_net_train_end": (i32, [vp, i32]),
+        "az_net_train_ema": (i32, [vp, i32]),
+        "az_net_train_step_info": (i32, [vp, vp]),
         "az_tree_create": (i32, [vp, i32, u64, i32, i32, i32, i32, i32, C.POINTER(vp)]),
         "az_tree_destroy": (None, [vp]),
         "az_tree_reset": (i32, [vp, vp]),
@@ -315,6 +317,16 @@ class Engine:
     def train_end(self, model_id):
         self._check(self._lib.az_net_train_end(self._h, model_id))
 
+    def train_ema(self, model_id):
+        """Store the averaged weights of "train_ema_decay_e9" (the last train_begin saw it > 0) under model_id."""
+        self._check(self._lib.az_net_train_ema(self._h, model_id))
+
+    def train_step_info(self):
+        """(grad_norm, clip_scale, lr_t, applied steps since train_begin) of the last step; (-1, 1, ..) with clipping off."""
+        out = np.zeros(4, np.float64)
+        self._check(self._lib.az_net_train_step_info(self._h, _ptr(out)))
+        return float(out[0]), float(out[1]), float(out[2]), int(out[3])
+
     def set_option(self, key, value):
         """az_set_option on this engine (keys: include/az_engine.h), e.g. set_option("net_fp8", 1): conv3 and conv4 of this engine's
         conv-net forwards on the FP8 (e4m3) matrix path -- a numerics class of its own, default off."""
@@ -360,6 +372,20 @@ class Engine:
         self.set_option("gumbel_c_visit_e6", int(round(float(c_visit) * 1e6)))
         self.set_option("gumbel_c_scale_e6", int(round(float(c_scale) * 1e6)))
         self.set_option("gumbel_m", int(m))
+
+    def set_train_optim(self, weight_decay=0.0, clip_norm=0.0, lr_warmup_steps=0, lr_decay=0, lr_floor=0.0, ema_decay=0.0, lr_total_steps=0):
+        """The opt-in optimiser rules of NNet::train, read by the next train() / train_begin(): decoupled AdamW weight decay, global
+        gradient-norm clipping, linear warm-up with cosine (1) or linear (2) decay to lr_floor x lr, and an averaged shadow of the weights
+        (train_ema).  Everything 0 (the default) switches them off; the values travel as "train_weight_decay_e9", "train_clip_norm_e6",
+        "train_lr_warmup_steps", "train_lr_decay", "train_lr_floor_e6", "train_lr_total_steps" (the step entries only) and
+        "train_ema_decay_e9" (include/az_engine.h)."""
+        self.set_option("train_weight_decay_e9", int(round(float(weight_decay) * 1e9)))
+        self.set_option("train_clip_norm_e6", int(round(float(clip_norm) * 1e6)))
+        self.set_option("train_lr_warmup_steps", int(lr_warmup_steps))
+        self.set_option("train_lr_decay", int(lr_decay))
+        self.set_option("train_lr_floor_e6", int(round(float(lr_floor) * 1e6)))
+        self.set_option("train_lr_total_steps", int(lr_total_steps))
+        self.set_option("train_ema_decay_e9", int(round(float(ema_decay) * 1e9)))
 
     def set_arena_openings(self, plies):
         """Paired arena openings (never self-play or the tree calls): arena game g and its seat-swapped twin g + total/2 start from the

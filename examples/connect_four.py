@@ -31,6 +31,10 @@ def main():
     ap.add_argument("--forced-playouts", default=None, metavar="K[,prune]")   # forced playouts at the root, e.g. 2,prune: with policy target pruning (Coach.forced_playouts_k)
     ap.add_argument("--gumbel", default=None, metavar="M[,CVISIT,CSCALE]")   # Gumbel root search with sequential halving in the episodes, e.g. 4 or 4,50,1: at most M root actions considered (Coach.gumbel_m)
     ap.add_argument("--arena-openings", type=int, default=0, metavar="N")   # paired openings of the gate: N random quiet plies (even, 2 .. 12) per pair of arena games (Coach.arena_opening_plies)
+    ap.add_argument("--weight-decay", type=float, default=0.0)       # decoupled AdamW decay of the weight tensors in NNet::train, e.g. 1e-4 (Coach.weight_decay)
+    ap.add_argument("--clip-norm", type=float, default=0.0)          # global gradient-norm clipping, e.g. 1.0 (Coach.clip_norm)
+    ap.add_argument("--lr-schedule", default=None, metavar="WARMUP,MODE,FLOOR")   # e.g. 100,cosine,0.1: linear warm-up over WARMUP steps, then cosine / linear / none down to FLOOR x lr over the call's steps (Coach.lr_warmup_steps / lr_decay / lr_floor)
+    ap.add_argument("--ema", type=float, default=0.0)                # decay of the averaged weights, e.g. 0.999: the candidate is the averaged model (Coach.ema_decay)
     ap.add_argument("--merge-positions", nargs="?", const="plain", default=None, choices=["plain", "canonical"])   # position averaging before training: one tuple per distinct position; =canonical also merges mirror images (Coach.merge_positions)
     ap.add_argument("--move-quality", default=None, metavar="STONES[,NODES]")   # exact move-quality report of every arena: positions with at least STONES stones are solved (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach.solve_min_stones)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
@@ -72,6 +76,13 @@ def main():
         coach.gumbel_m = int(parts[0])
         coach.gumbel_c_visit, coach.gumbel_c_scale = (float(parts[1]) if len(parts) > 1 else 50.0), (float(parts[2]) if len(parts) > 2 else 1.0)
     coach.arena_opening_plies = a.arena_openings
+    coach.weight_decay, coach.clip_norm, coach.ema_decay = a.weight_decay, a.clip_norm, a.ema
+    if a.lr_schedule:
+        parts = a.lr_schedule.split(",")
+        coach.lr_warmup_steps = int(parts[0])
+        mode = parts[1] if len(parts) > 1 else "none"
+        coach.lr_decay = {"none": 0, "cosine": 1, "linear": 2}[mode] if mode in ("none", "cosine", "linear") else int(mode)
+        coach.lr_floor = float(parts[2]) if len(parts) > 2 else 0.0
     coach.merge_positions, coach.merge_canonical = a.merge_positions is not None, a.merge_positions == "canonical"
     if a.move_quality:
         stones, _, nodes = a.move_quality.partition(",")

@@ -417,6 +417,40 @@ const char* az_last_error(const az_engine* e);
  *            "train_fork" 0 (default) / 1: with "train_gemm" 1, a step's weight split and wgrad chains run on a second stream
  *                           branch beside the BatchNorm-backward / dgrad chain (bit-identical; measured no faster, so off),
  *            "train_fwd_dma" 1 (default): the forward GEMMs' tiles go global -> LDS by LDS-DMA (k_gemm_f32_dma), 0: register-staged
+ *   optimiser rules  seven keys, all 0 (OFF) by default, strictly opt-in (csrc/az_optim.h states every formula):
+ *            "train_weight_decay_e9"  0 .. 1000000000; wd = (float)(value / 1e9).  Decoupled decay as torch.optim.AdamW
+ *            "train_clip_norm_e6"     0 (off) or 1 .. 1000000000000; c = value / 1e6.  torch.nn.utils.clip_grad_norm_ over the whole gradient
+ *            "train_lr_warmup_steps"  0 .. 2147483647: linear warm-up over that many applied steps
+ *            "train_lr_decay"         0 none / 1 cosine / 2 linear, from the end of the warm-up down to floor x lr at step `total`
+ *            "train_lr_floor_e6"      0 .. 1000000; floor = value / 1e6
+ *            "train_lr_total_steps"   0 (no decay) .. 2147483647: `total` for az_net_train_step sessions; az_net_train always uses its
+ *                                     own epochs x (n / batch)
+ *            "train_ema_decay_e9"     0 (off) or 1 .. 999999999; d = (float)(value / 1e9): an averaged shadow of the weights (az_net_train_ema)
+ *                           on         az_net_train_begin (and so az_net_train) reads the seven keys; they hold for that session, whatever is
+ *                                      set later.  With any of them on, a step's update runs in ONE other kernel (k_adamw) instead of the
+ *                                      Adam kernel, behind one more launch (k_grad_sqnorm) when clipping is on
+ *                           where      per applied step t = 1, 2, .. since az_net_train_begin, g the step's gradient:
+ *                                        lr_t  = (float)(lr * warm * dec) in double, lr = "train_lr_e9":  warm = warmup > 0 ? min(1, t / warmup)
+ *                                                : 1;  dec = 1 when decay = 0 or total = 0, else with x = clamp((t - warmup) / max(1, total -
+ *                                                warmup), 0, 1): cosine floor + (1 - floor) * 0.5 * (1 + cos(pi x)), linear floor + (1 - floor)
+ *                                                * (1 - x).  Evaluated on the host for both entries
+ *                                        scale = clipping on ? (float)min(1, c / (|g| + 1e-6)) : 1, |g| = sqrt of the f64 sum of squares of
+ *                                                the whole gradient (fixed chunks, fixed order: the same bits run to run, captured graph or
+ *                                                not, "train_fork" 0 / 1); a non-finite norm propagates
+ *                                        g' = g * scale;  m, v advance with g' as always
+ *                                        p  = p * (1 - lr_t * wd) for every element of the conv, FC, pi and v WEIGHT tensors; biases,
+ *                                                BatchNorm gamma / beta and the moving averages never decay
+ *                                        p  = p - (lr_t / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+ *                                        s  = d * s + (1 - d) * p for every parameter but the moving averages; s starts at the weights
+ *                                                az_net_train_begin loaded (no de-biasing); a step with apply = 0 does not move it
+ *                                      grads_out stays the RAW gradient g.  az_net_train_ema stores the shadow, az_net_train_step_info
+ *                                      reports |g|, scale, lr_t and t of the last step
+ *                           refused    values outside the ranges above (AZ_ERR_BAD_ARGUMENT, nothing changes)
+ *                           purity     with all seven at 0 (set or never set) the trainer launches the kernels it launches without the
+ *                                      feature and every weight is bit for bit what it is without it; an engine whose keys were on and are
+ *                                      back at 0 trains the same bits as one that never touched them.  Clipping with a c no step reaches
+ *                                      (scale exactly 1) is bit-identical to clipping off.  State of the engine, like every option.
+ *                                      Playing strength with any of the keys on is unmeasured
  * libaz_engine_diag.so (the same sources built with -DAZ_DIAG; alphazero-rs_amd/build.py) additionally takes the keys of the
  * SUPERSEDED kernel generations and the clock-stamp builds -- "gemm_variant" (0, 1, 2, 3, 5; 13: clock stamps), "fc_ring", "ring_tile",
  * "conv3_ring", "conv2_pipe", "conv3_pipe" (0 .. 3), "conv1_table", "conv4_big", "conv2_table" = 2, "tree_stamps", "print_*" -- which the
@@ -480,6 +514,14 @@ az_status az_net_train_begin(az_engine* e, int32_t prev_id);
 az_status az_net_train_step(az_engine* e, const float* boards, const float* pis, const float* vs, int32_t b,
                             uint64_t mask_seed, int32_t apply, float* loss_out, float* grads_out);
 az_status az_net_train_end(az_engine* e, int32_t model_id);
+/* The averaged weights of "train_ema_decay_e9" as a model: every parameter is the shadow s, the BatchNorm moving averages are the live
+ * trainer's.  Valid after an az_net_train_begin that saw the key > 0 -- between begin and end, after end, after az_net_train -- until
+ * the next az_net_train_begin; AZ_ERR_BAD_ARGUMENT otherwise (no training yet, a session with the key at 0).  Stores like
+ * az_net_set_params (the id's class is kept, its cached rows are dropped). */
+az_status az_net_train_ema(az_engine* e, int32_t model_id);
+/* out = {|g| of the last step (-1 with clipping off), its clip factor (1 with clipping off), its lr_t, applied steps since
+ * az_net_train_begin}; after az_net_train: of its last step.  AZ_ERR_BAD_ARGUMENT before any az_net_train_begin. */
+az_status az_net_train_step_info(const az_engine* e, double out[4]);
 
 /* ---- AsyncMcts, src/async_mcts.rs:14-115 -------------------------------- */
 /* n_games independent AsyncMcts::default(reserve, num_sims, num_threads, max_depth, model_id, cpuct, ..)

@@ -37,6 +37,8 @@
 #pragma weak az_arena_get_moves
 #pragma weak az_arena_get_openings
 #pragma weak az_allreduce_u64
+// Coach::ema_decay: with it 0 (the default) it is never called.
+#pragma weak az_net_train_ema
 
 namespace az_host {
 
@@ -158,6 +160,19 @@ class Engine {
         check(az_set_option(e_, "gumbel_c_visit_e6", (int64_t)std::llround(c_visit * 1e6)));
         check(az_set_option(e_, "gumbel_c_scale_e6", (int64_t)std::llround(c_scale * 1e6)));
         check(az_set_option(e_, "gumbel_m", m));
+    }
+    // The opt-in optimiser rules of NNet::train, read by the next az_net_train / az_net_train_begin ("train_weight_decay_e9",
+    // "train_clip_norm_e6", "train_lr_warmup_steps", "train_lr_decay", "train_lr_floor_e6", "train_lr_total_steps", "train_ema_decay_e9",
+    // include/az_engine.h).  Everything 0 switches them off
+    void set_train_optim(double weight_decay = 0.0, double clip_norm = 0.0, int64_t lr_warmup_steps = 0, int64_t lr_decay = 0, double lr_floor = 0.0,
+                         double ema_decay = 0.0, int64_t lr_total_steps = 0) {
+        check(az_set_option(e_, "train_weight_decay_e9", (int64_t)std::llround(weight_decay * 1e9)));
+        check(az_set_option(e_, "train_clip_norm_e6", (int64_t)std::llround(clip_norm * 1e6)));
+        check(az_set_option(e_, "train_lr_warmup_steps", lr_warmup_steps));
+        check(az_set_option(e_, "train_lr_decay", lr_decay));
+        check(az_set_option(e_, "train_lr_floor_e6", (int64_t)std::llround(lr_floor * 1e6)));
+        check(az_set_option(e_, "train_lr_total_steps", lr_total_steps));
+        check(az_set_option(e_, "train_ema_decay_e9", (int64_t)std::llround(ema_decay * 1e9)));
     }
     // Paired arena openings ("arena_opening_plies", include/az_engine.h): arena game g and its seat-swapped twin start from the same
     // position, `plies` random quiet plies (even, 2 .. 12) onto the pair's base; never self-play or the tree calls.  0 switches them off
@@ -661,7 +676,16 @@ class Coach {
                 sv[i] = av[src];
             }
             e_.check(az_set_option(e_.raw(), "train_seed", (int64_t)(seed + iteration)));
-            e_.check(az_net_train(e_.raw(), (int32_t)model_id, (int32_t)model_id + 1, sb.data(), sp.data(), sv.data(), (int64_t)n));   // :329
+            {
+                ScopedOption optim_guard(weight_decay > 0 || clip_norm > 0 || lr_warmup_steps > 0 || lr_decay != 0 || ema_decay > 0,
+                                         [&] { e_.set_train_optim(weight_decay, clip_norm, lr_warmup_steps, lr_decay, lr_floor, ema_decay); },
+                                         [&] { e_.set_train_optim(); });
+                e_.check(az_net_train(e_.raw(), (int32_t)model_id, (int32_t)model_id + 1, sb.data(), sp.data(), sv.data(), (int64_t)n));   // :329
+            }
+            if (ema_decay > 0) {                                      // the candidate is the averaged model
+                if (!az_net_train_ema) throw Panic("ema_decay: the linked engine library has no az_net_train_ema");
+                e_.check(az_net_train_ema(e_.raw(), (int32_t)model_id + 1));
+            }
             if (rank_ == 0) e_.check(az_net_save(e_.raw(), (int32_t)model_id + 1, (dir_ + "/" + std::to_string(model_id + 1) + ".aznet").c_str()));
             Report r{};
             r.iteration = iteration; r.samples = n; r.samples_raw = n_raw; r.model_id = model_id;
@@ -768,6 +792,14 @@ class Coach {
     // and nothing expands them again, so the net then trains on the CANONICAL orientation of every position only -- half the set; meant to
     // go with eval_mirror, which evaluates on that orientation.  false (the default): the engine is never asked
     bool merge_positions = false, merge_canonical = false;
+    // The optimiser rules of NNet::train (Engine::set_train_optim): decoupled weight decay, gradient-norm clipping, warm-up and decay of the
+    // learning rate (lr_decay 0 none / 1 cosine / 2 linear, over the call's own steps) and an averaged shadow of the weights, set before
+    // the iteration's one az_net_train and cleared behind it.  With ema_decay > 0 the candidate -- what the arena gates, what is saved as
+    // <id>.aznet and what the next iteration trains from -- is the averaged model (az_net_train_ema).  All 0 (the default): the engine is
+    // never asked
+    double weight_decay = 0.0, clip_norm = 0.0;
+    int64_t lr_warmup_steps = 0, lr_decay = 0;
+    double lr_floor = 0.0, ema_decay = 0.0;
     // Move-quality report (az_move_quality): after every iteration's arena its games are replayed, every position with at least
     // solve_min_stones stones is solved exactly (budget solve_max_nodes per position and action) and the move played there classed; the
     // tally per model goes into Report::quality and one log line each.  It decides nothing: the gate, the checkpoints, the .examples files

@@ -92,6 +92,8 @@ extern "C" {
     pub fn az_net_train_step(e: *mut az_engine, boards: *const f32, pis: *const f32, vs: *const f32, b: i32, mask_seed: u64,
                              apply: i32, loss_out: *mut f32, grads_out: *mut f32) -> c_int;
     pub fn az_net_train_end(e: *mut az_engine, model_id: i32) -> c_int;
+    pub fn az_net_train_ema(e: *mut az_engine, model_id: i32) -> c_int;
+    pub fn az_net_train_step_info(e: *const az_engine, out: *mut f64) -> c_int;
     // ---- AsyncMcts, src/async_mcts.rs:14-115
     pub fn az_tree_create(e: *mut az_engine, n_games: i32, reserve: u64, num_sims: i32, num_threads: i32, max_depth: i32,
                           model_id: i32, cpuct: i32, out: *mut *mut az_tree) -> c_int;

@@ -1,4 +1,6 @@
-"""Time az_net_train (NNet::train on the device): C=512, batch 64, `steps` optimisation steps in one epoch."""
+"""Time az_net_train (NNet::train on the device): C=512, batch 64, `steps` optimisation steps in one epoch.
+The optimiser rules through the environment: TRAIN_WD (weight decay), TRAIN_CLIP (clip norm), TRAIN_SCHED=WARMUP,MODE,FLOOR, TRAIN_EMA (decay);
+TRAIN_VARIANTS=1 times the defaults and each rule and all of them in turn, TRAIN_REPEAT times over, inside this one process."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,7 +34,31 @@ if os.environ.get("TRAIN_IMPLICIT"):
     e.set_option("train_implicit", int(os.environ["TRAIN_IMPLICIT"]))
 if os.environ.get("TRAIN_GEMM"):
     e.set_option("train_gemm", int(os.environ["TRAIN_GEMM"]))
+optim = {}
+if os.environ.get("TRAIN_WD"):
+    optim["weight_decay"] = float(os.environ["TRAIN_WD"])
+if os.environ.get("TRAIN_CLIP"):
+    optim["clip_norm"] = float(os.environ["TRAIN_CLIP"])
+if os.environ.get("TRAIN_SCHED"):
+    w, m, f = os.environ["TRAIN_SCHED"].split(",")
+    optim.update(lr_warmup_steps=int(w), lr_decay=int(m), lr_floor=float(f))
+if os.environ.get("TRAIN_EMA"):
+    optim["ema_decay"] = float(os.environ["TRAIN_EMA"])
+if optim:
+    e.set_train_optim(**optim)
 e.train(0, 1, boards[: 4 * batch], pis[: 4 * batch], vs[: 4 * batch])     # warm-up (allocations, code load)
+if os.environ.get("TRAIN_VARIANTS"):
+    variants = {"defaults": {}, "weight_decay": dict(weight_decay=1e-4), "clip": dict(clip_norm=1.0),
+                "schedule": dict(lr_warmup_steps=20, lr_decay=1, lr_floor=0.1), "ema": dict(ema_decay=0.999)}
+    variants["all"] = {k: v for d in variants.values() for k, v in d.items()}
+    for rep in range(int(os.environ.get("TRAIN_REPEAT", "5"))):
+        for name, kw in variants.items():
+            e.set_train_optim(**kw)
+            t0 = time.time()
+            e.train(0, 1, boards, pis, vs)
+            print(f"variant {name}: {(time.time() - t0) / steps * 1e3:.4f} ms/step", flush=True)
+    e.set_train_optim()
+    sys.exit(0)
 t0 = time.time()
 hist = e.train(0, 1, boards, pis, vs)
 dt = time.time() - t0
