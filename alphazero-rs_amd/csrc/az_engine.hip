@@ -26,6 +26,7 @@
 #include "az_net.h"
 #include "az_optim.h"
 #include "az_solve.h"
+#include "az_rating.h"
 #include "az_train.h"
 #include "az_tree.h"
 #include "az_gumbel.h"
@@ -361,7 +362,11 @@ struct az_engine {
     std::vector<uint64_t> sp_full_plies;        // az_selfplay_get_full_plies: the full-ply masks of the last az_selfplay / az_selfplay_next
     // activation workspaces of the conv net: [0] the engine stream, [1] a second concurrent stream (az_arena's old-model
     // search); created on first use, shared by every model id
-    NetWorkspace* ws[2] = {nullptr, nullptr};
+    // [2], [3]: the further side streams of az_tournament (side[1], side[2] below; side[0] shares [1])
+    NetWorkspace* ws[4] = {nullptr, nullptr, nullptr, nullptr};
+    // az_tournament's side streams, created by its first call and kept (a search graph's key holds its stream): the models' searches of
+    // a ply run on the engine's stream and these
+    hipStream_t side[3] = {nullptr, nullptr, nullptr};
     // eval log of the last az_selfplay
     std::vector<int32_t> sp_log_count;
     std::vector<uint64_t> sp_log_states;
@@ -537,7 +542,8 @@ RootMove root_move_for(const az_engine* e, const TreeHost& th, int num_sims, flo
 inline bool uses_root_stream(const RootMove& m) { return m.noise.eps != 0.0f || m.gumbel.m != 0u; }
 
 NetWorkspace* workspace_for(az_engine* e, hipStream_t s) {
-    const int i = (s == e->stream) ? 0 : 1;
+    int i = (s == e->stream) ? 0 : 1;
+    for (int j = 1; j < 3; ++j) if (e->side[j] && s == e->side[j]) i = 1 + j;
     if (!e->ws[i]) {
         const char* why = nullptr;
         e->ws[i] = netws_create(e->cfg.net_channels, e->cfg.max_batch, &why);
@@ -1074,6 +1080,7 @@ void az_destroy(az_engine* e) {
     e->tree_pool.clear();
     trainer_destroy(e->trainer);
     { double ms[RG_COUNT] = {0, 0}; e->prof.resolve(ms); }
+    for (hipStream_t ss : e->side) if (ss) (void)hipStreamDestroy(ss);
     (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -2529,6 +2536,228 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
         }
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// ---- az_tournament: one batched round robin ---------------------------------------------------------------------
+// The games of all P = K (K - 1) / 2 pairs share one chain of plies: game p * n + g is game g of az_arena(model_ids[i], model_ids[j]), and
+// model k searches ONE tree batch of the (K - 1) n games it plays in, whichever pair they belong to.
+namespace {
+constexpr int TOURNAMENT_MAX_MODELS = 16;
+
+az_status tournament_run(az_engine* e, int K, int n, int32_t num_sims, int32_t max_depth, int32_t cpuct, int T, uint64_t reserve, uint64_t seed,
+                         NetModel* const* nets, uint64_t* wld, int8_t* results) {
+    const int P = K * (K - 1) / 2, PN = P * n, half = n / 2, Gk = (K - 1) * n;
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const int calls = AZ_MAX_PLIES / 2 + 1;
+        const uint64_t nodes = std::min<uint64_t>(reserve, reachable_slots(num_sims, calls));
+        const uint64_t blocks = reachable_blocks(num_sims, calls, nodes);
+        if (az_status cs = check_tree_slots(e, blocks)) return cs;
+        // the streams: models dealt round robin over the engine's stream and up to three side streams; two ids on one set of weights share a stream
+        int stream_of[TOURNAMENT_MAX_MODELS], n_streams = 0;
+        for (int k = 0; k < K; ++k) {
+            stream_of[k] = -1;
+            for (int j = 0; j < k; ++j)
+                if (nets[k]->conv && nets[k]->conv == nets[j]->conv) { stream_of[k] = stream_of[j]; break; }
+            if (stream_of[k] < 0) stream_of[k] = n_streams++ % 4;
+        }
+        n_streams = std::min(n_streams, 4);
+        hipStream_t streams[4] = {s, nullptr, nullptr, nullptr};
+        for (int i = 1; i < n_streams; ++i) {
+            if (!e->side[i - 1]) HIPCHK(hipStreamCreate(&e->side[i - 1]));
+            streams[i] = e->side[i - 1];
+        }
+        struct Events {
+            hipEvent_t fork = nullptr, join[3] = {nullptr, nullptr, nullptr};
+            ~Events() { if (fork) (void)hipEventDestroy(fork); for (hipEvent_t j : join) if (j) (void)hipEventDestroy(j); }
+        } ev;
+        if (n_streams > 1) {
+            HIPCHK(hipEventCreateWithFlags(&ev.fork, hipEventDisableTiming));
+            for (int i = 1; i < n_streams; ++i) HIPCHK(hipEventCreateWithFlags(&ev.join[i - 1], hipEventDisableTiming));
+        }
+        // one tree per game and model, as the arena's pair: 2 P n trees in all
+        TreeLease lease[TOURNAMENT_MAX_MODELS];
+        for (int k = 0; k < K; ++k) acquire_trees(e, lease[k], Gk, blocks, nodes, hash_entries(num_sims, calls), T, s);
+        DeviceMem mem;
+        ArenaDev ad{};
+        ad.G = PN; ad.half = half; ad.first = 0;
+        ad.state = mem.alloc<ulonglong2>(PN);
+        ad.player = mem.alloc<int8_t>(PN);
+        ad.alive = mem.alloc<uint8_t>(PN);
+        ad.results = mem.alloc<int8_t>(PN);
+        ad.counters = mem.alloc<uint32_t>(2 + TOURNAMENT_MAX_MODELS);    // [2 + k]: the largest leaf batch of the ply of model k
+        ad.moves = mem.alloc<uint8_t>((size_t)PN * AZ_MAX_PLIES);
+        ad.len = mem.alloc<int32_t>(PN);
+        HIPCHK(hipMemset(ad.moves, 0, (size_t)PN * AZ_MAX_PLIES));
+        HIPCHK(hipMemset(ad.len, 0, (size_t)PN * sizeof(int32_t)));
+        // the tables: model k's trees are its pairs in the pairs' order, n games each
+        TournamentTable tb[TOURNAMENT_MAX_MODELS];
+        {
+            std::vector<uint32_t> h((size_t)K * Gk);
+            std::vector<int> fill((size_t)K, 0);
+            int pidx = 0;
+            for (int i = 0; i < K; ++i)
+                for (int j = i + 1; j < K; ++j, ++pidx)
+                    for (int g = 0; g < n; ++g) {
+                        h[(size_t)i * Gk + fill[i]++] = (uint32_t)(pidx * n + g);
+                        h[(size_t)j * Gk + fill[j]++] = (uint32_t)(pidx * n + g) | 0x80000000u;
+                    }
+            uint32_t* d_tab = mem.alloc<uint32_t>(h.size());
+            ulonglong2* d_roots = mem.alloc<ulonglong2>((size_t)K * Gk);
+            HIPCHK(hipMemcpy(d_tab, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIPCHK(hipMemset(d_roots, 0, (size_t)K * Gk * sizeof(ulonglong2)));
+            for (int k = 0; k < K; ++k) tb[k] = TournamentTable{d_tab + (size_t)k * Gk, d_roots + (size_t)k * Gk, n, 0};
+        }
+        const bool openings = e->arena_opening_plies > 0 || !e->ar_book.empty();
+        ArenaOpenings op{};
+        std::vector<uint64_t> open_boards;
+        if (openings) {
+            // every pair of models plays az_arena's openings of an n-game call: the index inside the pair draws them
+            op.seed = seed;
+            op.plies = (int32_t)e->arena_opening_plies;
+            op.nb = (int32_t)(e->ar_book.size() / 2);
+            if (op.nb) {
+                ulonglong2* book = mem.alloc<ulonglong2>((size_t)op.nb);
+                HIPCHK(hipMemcpy(book, e->ar_book.data(), e->ar_book.size() * 8, hipMemcpyHostToDevice));
+                op.book = book;
+            }
+            op.base = make_ulonglong2(0ull, 0ull);
+            op.len = mem.alloc<int32_t>(PN);
+            op.moves = mem.alloc<uint8_t>((size_t)PN * OPENING_MAX_PLIES);
+            for (int p = 0; p < P; ++p) {
+                ArenaDev av = ad;
+                av.G = n; av.state = ad.state + (size_t)p * n;
+                ArenaOpenings ov = op;
+                ov.len = op.len + (size_t)p * n; ov.moves = op.moves + (size_t)p * n * OPENING_MAX_PLIES;
+                launch_arena_openings(e->cfg.game, av, ov, s);
+            }
+            open_boards.resize((size_t)PN * 2);
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipMemcpy(open_boards.data(), ad.state, open_boards.size() * 8, hipMemcpyDeviceToHost));
+        } else {
+            HIPCHK(hipMemset(ad.state, 0, (size_t)PN * sizeof(ulonglong2)));
+        }
+        HIPCHK(hipMemset(ad.player, 1, PN));
+        HIPCHK(hipMemset(ad.alive, 1, PN));
+        HIPCHK(hipMemset(ad.results, 0, PN));
+        uint32_t ctr[2 + TOURNAMENT_MAX_MODELS] = {(uint32_t)PN, 0u};
+        HIPCHK(hipMemcpy(ad.counters, ctr, sizeof ctr, hipMemcpyHostToDevice));
+        int typ[TOURNAMENT_MAX_MODELS] = {};              // expected rows per leaf batch, per model (0 = unknown)
+        bool any_dedup = false;
+        for (int k = 0; k < K; ++k) { launch_reset_trees(lease[k]->d, nullptr, s); any_dedup = any_dedup || dedup_applies(e, *nets[k]); }
+        prepare_cache(e, any_dedup, (uint64_t)PN * AZ_MAX_PLIES * ((uint64_t)num_sims + 1), s);
+        for (int k = 0; k < K; ++k) (void)cache_for(e, *nets[k]);      // all tags are fixed before the first fork (retagging may clear the cache)
+        SearchParams sp{(uint32_t)max_depth, (float)cpuct};
+        az_status result = AZ_OK;
+        for (int ply = 0; ply <= AZ_MAX_PLIES; ++ply) {
+            for (int k = 0; k < K; ++k) launch_tournament_sync(lease[k]->d, ad, tb[k], s);
+            if (n_streams > 1) {
+                HIPCHK(hipEventRecord(ev.fork, s));
+                for (int i = 1; i < n_streams; ++i) HIPCHK(hipStreamWaitEvent(streams[i], ev.fork, 0));
+            }
+            // the side streams' models first, so that their searches are queued while the host issues the engine stream's
+            for (int pass = 0; pass < 2; ++pass)
+                for (int k = 0; k < K; ++k) {
+                    if ((stream_of[k] == 0) != (pass == 1)) continue;
+                    run_search(e, *lease[k], tb[k].roots, num_sims, sp, *nets[k], (int)std::min<uint32_t>(ctr[0], (uint32_t)Gk), streams[stream_of[k]],
+                               typ[k], ad.counters + 2 + k);
+                }
+            for (int i = 1; i < n_streams; ++i) {
+                HIPCHK(hipEventRecord(ev.join[i - 1], streams[i]));
+                HIPCHK(hipStreamWaitEvent(s, ev.join[i - 1], 0));
+            }
+            for (int k = 0; k < K; ++k) launch_tournament_move(lease[k]->d, ad, tb[k], seed, s);
+            HIPCHK(hipMemcpyAsync(ctr, ad.counters, sizeof ctr, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            resolve_profile(e);
+            for (int k = 0; k < K; ++k) typ[k] = (int)std::min<uint32_t>(ctr[2 + k], (uint32_t)(Gk * T));
+            HIPCHK(hipMemsetAsync(ad.counters + 2, 0, TOURNAMENT_MAX_MODELS * sizeof(uint32_t), s));
+            if (ctr[1]) { result = fail(e, AZ_ERR_INVALID_MOVE, "tournament: action is not valid (src/arena.rs:31-35)"); break; }
+            if (ctr[0] == 0) break;
+        }
+        for (int k = 0; k < K; ++k) harvest_stats(e, *lease[k], *nets[k]);
+        for (int k = 0; k < K; ++k) if (result == AZ_OK) result = check_tree_errors(e, *lease[k]);
+        if (result) return result;
+        if (ctr[0] != 0) return fail(e, AZ_ERR_HIP, "az_tournament: games did not finish");
+        std::vector<int8_t> res((size_t)PN);
+        HIPCHK(hipMemcpy(res.data(), ad.results, (size_t)PN, hipMemcpyDeviceToHost));
+        std::vector<uint8_t> moves((size_t)PN * AZ_MAX_PLIES), open_moves;
+        std::vector<int32_t> len((size_t)PN), open_len;
+        HIPCHK(hipMemcpy(moves.data(), ad.moves, moves.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(len.data(), ad.len, len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (openings) {
+            open_len.resize((size_t)PN);
+            open_moves.resize((size_t)PN * OPENING_MAX_PLIES);
+            HIPCHK(hipMemcpy(open_len.data(), op.len, open_len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(open_moves.data(), op.moves, open_moves.size(), hipMemcpyDeviceToHost));
+        }
+        if (results) HIPCHK(hipMemcpy(results, res.data(), (size_t)PN, hipMemcpyDefault));
+        // nothing can fail from here on: the outputs and the move record change together
+        for (size_t i = 0; i < (size_t)K * K * 3; ++i) wld[i] = 0;
+        int pidx = 0;
+        for (int i = 0; i < K; ++i)
+            for (int j = i + 1; j < K; ++j, ++pidx) {
+                uint64_t c[3] = {0, 0, 0};
+                for (int g = 0; g < n; ++g) {
+                    const int win_cond = g < half ? 1 : -1, r = res[(size_t)pidx * n + g];       // src/arena.rs:80-81
+                    c[r == win_cond ? 0 : (r == -win_cond ? 1 : 2)]++;
+                }
+                uint64_t *a = wld + ((size_t)i * K + j) * 3, *b = wld + ((size_t)j * K + i) * 3;
+                a[0] = c[0]; a[1] = c[1]; a[2] = c[2];
+                b[0] = c[1]; b[1] = c[0]; b[2] = c[2];
+            }
+        e->ar_moves = std::move(moves);
+        e->ar_len = std::move(len);
+        if (openings) {
+            e->ar_open_boards = std::move(open_boards);
+            e->ar_open_len = std::move(open_len);
+            e->ar_open_moves = std::move(open_moves);
+        } else {
+            record_common_opening(e, PN, 0ull, 0ull);
+        }
+        e->ar_log_cap = 0;            // there is no eval log here: az_arena_get_evals is refused
+        e->stats.games += (uint64_t)PN;
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+}  // namespace
+
+az_status az_tournament(az_engine* e, const int32_t* model_ids, int32_t num_models, int32_t games_per_pair, int32_t num_sims, int32_t max_depth,
+                        int32_t cpuct, int32_t num_sim_threads, uint64_t reserve, uint64_t seed, uint64_t* wld, int8_t* results) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!model_ids || !wld) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: model_ids and wld are required");
+    const int K = num_models, n = games_per_pair;
+    if (K < 2 || K > TOURNAMENT_MAX_MODELS) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: 2 .. 16 models");
+    if (n < 2 || (n & 1)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: games_per_pair must be even and at least 2 (half per seating)");
+    if ((int64_t)(K * (K - 1) / 2) * (int64_t)n > 1024 * 64) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: at most 65536 games");
+    if (num_sims <= 0 || max_depth < 0 || reserve < 8) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: bad argument");
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: a self-play session is open (az_selfplay_end first)");
+    NetModel* nets[TOURNAMENT_MAX_MODELS];
+    for (int k = 0; k < K; ++k) {
+        for (int j = 0; j < k; ++j)
+            if (model_ids[j] == model_ids[k]) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: model id " + std::to_string(model_ids[k]) + " is listed twice");
+        if (find_net(e, model_ids[k], &nets[k])) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: model id " + std::to_string(model_ids[k]) + " is not initialised");
+    }
+    int T = num_sim_threads;
+    if (az_status st = check_threads(e, num_sims, &T)) return st;
+    for (int k = 0; k < K; ++k)
+        if (az_status st = check_batch(e, *nets[k], (K - 1) * n * T)) return st;
+    const az_status st = tournament_run(e, K, n, num_sims, max_depth, cpuct, T, reserve, seed, nets, wld, results);
+    // the pool keeps what it would keep after an az_arena: at most three idle tree arenas (the newest go first)
+    try {
+        for (size_t i = e->tree_pool.size(); i-- > 0 && e->tree_pool.size() > 3;)
+            if (!e->tree_pool[i]->in_use) {
+                HIPCHK(hipStreamSynchronize(e->stream));
+                e->tree_pool.erase(e->tree_pool.begin() + (long)i);
+            }
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+    return st;
+}
+
+az_status az_rating_fit(const uint64_t* wld, int32_t K, double prior_games, double* elo, double* elo_se, int32_t* sweeps) {
+    return rating_fit(wld, K, prior_games, elo, elo_se, sweeps) ? AZ_OK : AZ_ERR_BAD_ARGUMENT;
 }
 
 az_status az_arena_get_moves(az_engine* e, int32_t* game_len, uint8_t* moves) {

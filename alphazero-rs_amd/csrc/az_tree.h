@@ -264,6 +264,16 @@ struct ArenaOpenings {
     uint8_t* moves;          // [G][OPENING_MAX_PLIES] out: those actions, zero behind len
 };
 
+// az_tournament: tree g of ONE model's batch plays game (game[g] & TOURNAMENT_GAME_MASK) of the tournament's ArenaDev, whose games are
+// p * n + index inside pair p; bit 31 is set when the model is the pair's second listed one (az_arena's "old" model).
+constexpr uint32_t TOURNAMENT_GAME_MASK = 0x7FFFFFFFu;
+struct TournamentTable {
+    const uint32_t* game;    // [TreeDev.G]
+    ulonglong2* roots;       // [TreeDev.G] out (k_tournament_sync): the root state of the tree's game, what run_search takes as root_states
+    int32_t n;               // games per pair
+    int32_t pad;
+};
+
 // ---- launchers (all asynchronous on `s`; dispatch on TreeDev.game to the Game policy's instantiation) ------------------
 void launch_count_done(const int32_t* g_len, int lo, int hi, uint32_t* counter, hipStream_t s);   // *counter = #{lo <= i < hi : g_len[i] > 0}
 void launch_init_heads(const TreeDev& t, hipStream_t s);                      // zero every TreeHead, active = 1
@@ -348,6 +358,10 @@ void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream
 void launch_arena_openings(int game, const ArenaDev& ad, const ArenaOpenings& op, hipStream_t s);
 void launch_arena_sync(const TreeDev& t_new, const TreeDev& t_old, const ArenaDev& ad, hipStream_t s);
 void launch_arena_move(const TreeDev& t, const ArenaDev& ad, uint64_t seed, hipStream_t s);
+// az_tournament (ad.half = n / 2, ad.first = 0, ad.G = pairs * n): head.active and tb.roots of one model's batch from the per-game arrays;
+// then k_arena_move's rule for the trees that searched, through the table
+void launch_tournament_sync(const TreeDev& t, const ArenaDev& ad, const TournamentTable& tb, hipStream_t s);
+void launch_tournament_move(const TreeDev& t, const ArenaDev& ad, const TournamentTable& tb, uint64_t seed, hipStream_t s);
 void launch_emit_samples(const GamesDev& gd, const int64_t* offsets, int symmetries, ulonglong2* out_states,
                          float* out_boards, float* out_pis, float* out_zs, hipStream_t s);
 

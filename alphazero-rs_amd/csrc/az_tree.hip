@@ -1528,19 +1528,18 @@ __global__ void k_arena_sync(TreeDev tn, TreeDev to, ArenaDev ad) {
     to.head[g].head.active = (alive && mover == 1) ? 1u : 0u;
 }
 
-// The searching tree's owner plays argmax(get_action_prob(s, temp = 0)) (src/coach.rs:356-372).
+// The searching tree's owner plays argmax(get_action_prob(s, temp = 0)) (src/coach.rs:356-372): the rule of one ply of one game, shared by
+// az_arena (tree g plays game g) and az_tournament (tree g of a model's batch plays game gi of the tournament through the model's table).
+//   g     the tree of t that searched           gi    the game's row in ad (state, player, alive, results, moves, len)
+//   rid   the game's index in the tie-break stream (seed, rid, ply): the arena's global game index, the index inside the pair
 template <class G>
-__global__ __launch_bounds__(64) void k_arena_move(TreeDev t, ArenaDev ad, uint64_t seed) {
+__device__ __forceinline__ void arena_move_body(const TreeDev& t, const TreeHead& h, const ArenaDev& ad, int g, int gi, uint64_t rid, int sub,
+                                                uint64_t seed) {
     constexpr int GW = G::GROUP;
     constexpr int NA = G::ACTIONS;
-    int tid = blockIdx.x * 64 + threadIdx.x;
-    int g = tid / GW, sub = tid % GW;
-    if (g >= t.G) return;
-    const TreeHead h = head_load(t, g);
-    if (!h.active) return;
-    const typename G::State s = ad.state[g];
-    const int8_t player = ad.player[g];
-    RootPolicy rp = root_policy<G>(t, h.root, g, sub, 0.0f, seed, (uint64_t)(ad.first + g), (uint64_t)G::stones(s));
+    const typename G::State s = ad.state[gi];
+    const int8_t player = ad.player[gi];
+    RootPolicy rp = root_policy<G>(t, h.root, g, sub, 0.0f, seed, rid, (uint64_t)G::stones(s));
     // argmax with max_by (last max) over the one-hot pi = the index of the 1
     const uint32_t hot = gballot<GW>(sub < NA && rp.pi == 1.0f) & ((1u << NA) - 1u);
     const int action = hot ? (31 - __clz((int)hot)) : 0;
@@ -1549,25 +1548,65 @@ __global__ __launch_bounds__(64) void k_arena_move(TreeDev t, ArenaDev ad, uint6
     const uint32_t ec = G::ended_code(s2);
     if (sub == 0) {
         if (valid && hot) {                           // the game's move record
-            const int32_t k = ad.len[g];
-            if (k < G::MAX_PLIES) ad.moves[(size_t)g * G::MAX_PLIES + k] = (uint8_t)action;
-            ad.len[g] = k + 1;
+            const int32_t k = ad.len[gi];
+            if (k < G::MAX_PLIES) ad.moves[(size_t)gi * G::MAX_PLIES + k] = (uint8_t)action;
+            ad.len[gi] = k + 1;
         }
         if (!valid || !hot) {
             atomicOr(&ad.counters[1], 1u);
-            ad.alive[g] = 0;
+            ad.alive[gi] = 0;
             atomicSub(&ad.counters[0], 1u);
         } else if (ec != E_NONE) {
             // cur_player' = -player; result = cur_player' * round(get_game_ended(cur_player')) (src/arena.rs:51):
             // ended = -1 -> the player who just moved won; DRAW_EPS rounds to 0
-            ad.results[g] = (ec == E_PLUS1) ? player : (ec == E_MINUS1 ? (int8_t)-player : (int8_t)0);
-            ad.alive[g] = 0;
+            ad.results[gi] = (ec == E_PLUS1) ? player : (ec == E_MINUS1 ? (int8_t)-player : (int8_t)0);
+            ad.alive[gi] = 0;
             atomicSub(&ad.counters[0], 1u);
         } else {
-            ad.state[g] = s2;
-            ad.player[g] = (int8_t)-player;
+            ad.state[gi] = s2;
+            ad.player[gi] = (int8_t)-player;
         }
     }
+}
+
+template <class G>
+__global__ __launch_bounds__(64) void k_arena_move(TreeDev t, ArenaDev ad, uint64_t seed) {
+    constexpr int GW = G::GROUP;
+    int tid = blockIdx.x * 64 + threadIdx.x;
+    int g = tid / GW, sub = tid % GW;
+    if (g >= t.G) return;
+    const TreeHead h = head_load(t, g);
+    if (!h.active) return;
+    arena_move_body<G>(t, h, ad, g, g, (uint64_t)(ad.first + g), sub, seed);
+}
+
+// ---- az_tournament: the games of all pairs in one ArenaDev (game p * n + g), one tree batch per MODEL ------------------------------------
+// Tree g of a model's batch plays the game its table names (TournamentTable, az_tree.h).  k_arena_sync generalised by the table: the tree
+// searches this ply when its game is running and its model is to move, and its root state is gathered from the per-game array.
+__global__ void k_tournament_sync(TreeDev t, ArenaDev ad, TournamentTable tb) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= t.G) return;
+    const uint32_t w = tb.game[g];
+    const int gi = (int)(w & TOURNAMENT_GAME_MASK);
+    if (gi >= ad.G) { t.head[g].head.active = 0u; return; }            // (a table entry outside the games: never built, never followed)
+    const int second = (int)(w >> 31);                                  // 0: this model is the pair's first listed ("new"), 1: its second ("old")
+    const int first_model = gi % tb.n < ad.half ? 0 : 1;                // the seating uses the index inside the pair, as az_arena's global index
+    const int mover = ad.player[gi] == 1 ? first_model : 1 - first_model;
+    t.head[g].head.active = (ad.alive[gi] != 0 && mover == second) ? 1u : 0u;
+    tb.roots[g] = ad.state[gi];
+}
+
+template <class G>
+__global__ __launch_bounds__(64) void k_tournament_move(TreeDev t, ArenaDev ad, TournamentTable tb, uint64_t seed) {
+    constexpr int GW = G::GROUP;
+    int tid = blockIdx.x * 64 + threadIdx.x;
+    int g = tid / GW, sub = tid % GW;
+    if (g >= t.G) return;
+    const TreeHead h = head_load(t, g);
+    if (!h.active) return;
+    const int gi = (int)(tb.game[g] & TOURNAMENT_GAME_MASK);
+    if (gi >= ad.G) return;
+    arena_move_body<G>(t, h, ad, g, gi, (uint64_t)(gi % tb.n), sub, seed);
 }
 
 __global__ void k_sync_active(TreeDev t, GamesDev gd) {
@@ -1744,6 +1783,12 @@ void launch_arena_sync(const TreeDev& t_new, const TreeDev& t_old, const ArenaDe
 }
 void launch_arena_move(const TreeDev& t, const ArenaDev& ad, uint64_t seed, hipStream_t s) {
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_arena_move<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, ad, seed));
+}
+void launch_tournament_sync(const TreeDev& t, const ArenaDev& ad, const TournamentTable& tb, hipStream_t s) {
+    hipLaunchKernelGGL(k_tournament_sync, dim3((t.G + 255) / 256), dim3(256), 0, s, t, ad, tb);
+}
+void launch_tournament_move(const TreeDev& t, const ArenaDev& ad, const TournamentTable& tb, uint64_t seed, hipStream_t s) {
+    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_tournament_move<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, ad, tb, seed));
 }
 // episodes of [lo, hi) that have already finished (g_len is set when an episode ends): a session's chunk starts its count from here
 __global__ void k_count_done(const int32_t* __restrict__ g_len, int lo, int hi, uint32_t* __restrict__ counter) {

@@ -91,7 +91,7 @@ EXPORTS = [
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
     "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_tree_get_selected", "az_gumbel_values", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
-    "az_arena_set_opening_book", "az_arena_get_openings",
+    "az_arena_set_opening_book", "az_arena_get_openings", "az_tournament", "az_rating_fit",
     "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
 COMM_ID_BYTES = 128
@@ -160,6 +160,8 @@ def load_library(path=LIB_PATH):
         "az_arena_get_moves": (i32, [vp, vp, vp]),
         "az_arena_set_opening_book": (i32, [vp, vp, i32]),
         "az_arena_get_openings": (i32, [vp, vp, vp, vp]),
+        "az_tournament": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, u64, u64, vp, vp]),
+        "az_rating_fit": (i32, [vp, i32, C.c_double, vp, vp, vp]),
         "az_comm_unique_id": (i32, [vp, vp]),
         "az_comm_local_id": (i32, [vp, i32, vp]),
         "az_comm_init": (i32, [vp, i32, i32, vp]),
@@ -612,6 +614,22 @@ class Engine:
         self._check(self._lib.az_arena_get_moves(self._h, _ptr(game_len), _ptr(moves)))
         return game_len, moves
 
+    def tournament(self, model_ids, games_per_pair, num_sims, seed=0, max_depth=1000, cpuct=1, reserve=1000000, num_sim_threads=1):
+        """az_tournament: one batched round robin of the K = len(model_ids) models, games_per_pair games (half per seating) for each of the
+        P = K (K - 1) / 2 pairs (i, j), i < j, in lexicographic order.  Game g of pair p is bit for bit game g of
+        arena(games_per_pair, num_sims, model_ids[i], model_ids[j], seed, ...) and has index p * games_per_pair + g.  Returns a dict:
+        wld [K,K,3] uint64 (wld[i,j] = (W, L, D) from model i's side), results [P*n] int8 (+1: the first seat won), game_len [P*n] and
+        moves [P*n,42] (the move record arena_get_moves returns afterwards).  Switch paired openings on first (set_arena_openings)."""
+        ids = np.ascontiguousarray(model_ids, dtype=np.int32).reshape(-1)
+        K, n = int(len(ids)), int(games_per_pair)
+        games = max(K * (K - 1) // 2 * max(n, 0), 1)
+        wld = np.zeros((K, K, 3), np.uint64)
+        results = np.zeros(games, np.int8)
+        self._check(self._lib.az_tournament(self._h, _ptr(ids), K, n, num_sims, max_depth, cpuct, num_sim_threads, reserve, seed,
+                                            _ptr(wld), _ptr(results)))
+        game_len, moves = self.arena_get_moves(games)
+        return {"wld": wld, "results": results, "game_len": game_len, "moves": moves}
+
     def arena_get_evals(self, which, n_games, cap):
         """Eval log of the last arena(record_evals=cap): rows the trees of player `which` (0 new, 1 old) consumed, per game."""
         cnt = np.zeros(n_games, np.int32)
@@ -778,6 +796,21 @@ class TreeBatch:
 
 
 # ---- host-side helpers on canonical bitboards (mirror of the Game trait for Connect Four) ----
+def rating_fit(wld, prior_games=2.0):
+    """az_rating_fit: Bradley-Terry ratings (a draw = half a win, Hunter's MM iteration) from a result matrix wld [K,K,3] as
+    Engine.tournament returns it.  Needs no engine and no GPU.  Returns (elo [K] with mean 0, elo_se [K] -- the diagonal Fisher
+    approximation --, sweeps).  prior_games virtual games are added to every pair, half won by each side; 2 is the recommended value."""
+    wld = np.ascontiguousarray(wld, dtype=np.uint64)
+    if wld.ndim != 3 or wld.shape[0] != wld.shape[1] or wld.shape[2] != 3:
+        raise ValueError("wld must be [K, K, 3]")
+    K = int(wld.shape[0])
+    elo, se, sweeps = np.zeros(K, np.float64), np.zeros(K, np.float64), C.c_int32(0)
+    st = _lib.az_rating_fit(_ptr(wld), K, float(prior_games), _ptr(elo), _ptr(se), C.byref(sweeps))
+    if st != AZ_OK:
+        raise AzError(st, "az_rating_fit: K outside 2 .. 16, or a negative or non-finite prior_games")
+    return elo, se, int(sweeps.value)
+
+
 def c4_play(mine, theirs, a):
     """get_next_state(1, a) then get_canonical_form(next_player) (connect_four_game.rs:90-103, :198-203)."""
     mask = mine | theirs

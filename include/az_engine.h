@@ -726,6 +726,52 @@ az_status az_arena_set_opening_book(az_engine* e, const uint64_t* boards, int32_
  * Any pointer may be NULL.  AZ_ERR_BAD_ARGUMENT before the first az_arena. */
 az_status az_arena_get_openings(az_engine* e, uint64_t* boards, int32_t* len, uint8_t* moves);
 
+/* ---- az_tournament: one batched round robin of K models (no reference counterpart).  Strictly opt-in.
+ * az_arena seats two models; ranking K checkpoints by it costs K (K - 1) / 2 calls, each a chain of 42 plies x num_sims dependent steps
+ * that leaves the GPU almost empty.  This call plays the games of ALL pairs in one such chain.
+ *   model_ids [num_models]   K = 2 .. 16 pairwise distinct, initialised model ids
+ *   games_per_pair           n, even, >= 2: n / 2 per seating, as az_arena's num_games
+ *   num_sims, max_depth, cpuct, num_sim_threads (0 = 1), reserve, seed: as the fields of az_arena_params
+ * The pairs are (i, j), i < j, in lexicographic order, P = K (K - 1) / 2 of them; game g of pair p has TOURNAMENT INDEX p * n + g.
+ * THE CONTRACT: game (p, g) is bit for bit -- result, length, every move, opening -- game g of az_arena on the same engine with the same
+ * options, called with num_games = n, new_model_id = model_ids[i], old_model_id = model_ids[j], the same num_sims, max_depth, cpuct,
+ * reserve, seed and num_sim_threads, and every other field 0.  Seating, the tie-break stream (seed, g, ply) and the opening of pair
+ * g % (n / 2) therefore use the index INSIDE the pair; "arena_opening_plies" and the opening book apply exactly as to az_arena, so every
+ * pair of models plays the same n / 2 openings in both seatings, which is what a rating wants.  SWITCH OPENINGS ON for a tournament:
+ * without them every game of a pair at temperature 0 is one of two games.  Per-model classes (az_net_set_class), "net_fp8",
+ * "eval_mirror", the evaluation cache, both games and stub, hash and conv models work as in az_arena; root noise, playout cap, forced
+ * playouts and Gumbel never apply, as in az_arena.  There is no start_board (the openings are the book and the random plies), no
+ * sharding and no communicator: the call plays on one engine.
+ *   wld [K][K][3]            wld[i][j] = {W, L, D} from model_ids[i]'s side = az_arena's out_wld of that pair; wld[j][i] = {L, W, D}; the
+ *                            diagonal is 0
+ *   results [P * n]          (may be NULL) az_arena's convention, in tournament order: +1 when the first seat won
+ * Afterwards az_arena_get_moves and az_arena_get_openings return the P * n games in tournament order (az_move_quality runs on them
+ * unchanged); az_arena_get_evals is refused, there is no eval log here.  az_stats.games and the tree counters advance as over the P
+ * az_arena calls (leaf_rows_executed by no more: the pairs share openings and each model's leaves of a step share one election table).
+ * How it runs: one tree batch per MODEL ((K - 1) n trees, 2 P n in all, the arena's two per game), one search per model and ply on the
+ * engine's stream and at most three side streams of the engine's own (models dealt round robin; ids that share weights share a stream).
+ * Refused with AZ_ERR_BAD_ARGUMENT, nothing written and the last move record kept: K outside 2 .. 16; n odd or < 2; P * n > 65536; a
+ * NULL model_ids or wld; a repeated or uninitialised model id; a conv model whose (K - 1) n threads rows exceed az_config.max_batch;
+ * whatever az_arena refuses for num_sims, max_depth, reserve and num_sim_threads; an open self-play session.
+ * The parameters travel as arguments, not as a struct: the set of ABI structs is closed. */
+az_status az_tournament(az_engine* e, const int32_t* model_ids, int32_t num_models, int32_t games_per_pair, int32_t num_sims,
+                        int32_t max_depth, int32_t cpuct, int32_t num_sim_threads, uint64_t reserve, uint64_t seed, uint64_t* wld,
+                        int8_t* results);
+/* Ratings from a result matrix (alphazero-rs_amd/csrc/az_rating.h).  Takes no engine: the library answers it without a GPU.
+ * Bradley-Terry with a draw counted as half a win, by Hunter's MM iteration; every sum in ascending j, in double.
+ *   wld [K][K][3]   as az_tournament writes it (the diagonal is ignored); K = 2 .. 16
+ *   prior_games     >= 0, finite: virtual games added to every pair, half won by each side (s_ij = W + D/2 + prior/2,
+ *                   n_ij = W + L + D + prior).  2 is the recommended value; 0 with a model that has no games, or only wins or only
+ *                   losses, diverges (the iteration then stops at its limit of 100 000 sweeps)
+ *   elo [K]         400 log10(gamma_i) minus the mean over the models, gamma the fixed point of
+ *                   gamma_i = S_i / sum_j n_ij / (gamma_i + gamma_j), S_i = sum_j s_ij, iterated from gamma = 1 (each sweep scaled to
+ *                   sum gamma = K) until max_i |gamma'_i - gamma_i| / gamma_i < 1e-13
+ *   elo_se [K]      (may be NULL) (400 / ln 10) / sqrt(sum_j n_ij gamma_i gamma_j / (gamma_i + gamma_j)^2).  APPROXIMATE: the diagonal
+ *                   of the Fisher information only, which ignores the covariance between the models; prior games count as games
+ *   sweeps          (may be NULL) sweeps run
+ * Refused with AZ_ERR_BAD_ARGUMENT, nothing written: K outside 2 .. 16, a negative or non-finite prior_games, a NULL wld or elo. */
+az_status az_rating_fit(const uint64_t* wld, int32_t K, double prior_games, double* elo, double* elo_se, int32_t* sweeps);
+
 /* ---- exact endgame solver and move-quality report (no reference counterpart).  Strictly opt-in: a host that never calls these runs
  * nothing of them.  The game-theoretic value of a late position can be computed exactly; a move then either keeps that value or throws it
  * away, which is an ABSOLUTE measure of play that needs no opponent.  The search, its frozen rule and the table entry are in

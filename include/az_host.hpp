@@ -39,6 +39,9 @@
 #pragma weak az_allreduce_u64
 // Coach::ema_decay: with it 0 (the default) it is never called.
 #pragma weak az_net_train_ema
+// az_host::tournament / az_host::rating_fit: no Coach calls them.
+#pragma weak az_tournament
+#pragma weak az_rating_fit
 
 namespace az_host {
 
@@ -212,6 +215,49 @@ class Engine {
   private:
     az_engine* e_ = nullptr;
 };
+
+// ---- az_tournament / az_rating_fit (include/az_engine.h): one batched round robin of K models, and ratings from its result matrix ----------
+// The pairs are (i, j), i < j, in lexicographic order; game g of pair p is bit for bit game g of az_arena {num_games = games_per_pair,
+// new_model_id = model_ids[i], old_model_id = model_ids[j], the same search parameters} and has index p * games_per_pair + g.  Paired
+// openings (Engine::set_arena_openings / arena_set_opening_book) apply as to the arena: switch them on first.
+struct TournamentParams {
+    std::vector<int32_t> model_ids;                  // K = 2 .. 16, pairwise distinct
+    int32_t games_per_pair = 2;                      // even: half per seating
+    int32_t num_sims = 25, max_depth = 1000, cpuct = 1, num_sim_threads = 1;
+    uint64_t reserve = 1000000, seed = 0;
+};
+struct TournamentResult {
+    size_t K = 0, games = 0;
+    std::vector<uint64_t> wld;                       // [K][K][3]: wld[i][j] = {W, L, D} from model i's side
+    std::vector<int8_t> results;                     // [games] +1: the first seat won
+    std::vector<int32_t> game_len;                   // [games]
+    std::vector<uint8_t> moves;                      // [games][AZ_MAX_PLIES]
+};
+inline TournamentResult tournament(const Engine& e, const TournamentParams& p) {
+    if (!az_tournament || !az_arena_get_moves) throw Panic("tournament: the linked engine library has no az_tournament");
+    TournamentResult r;
+    r.K = p.model_ids.size();
+    r.games = r.K * (r.K > 0 ? r.K - 1 : 0) / 2 * (size_t)std::max(p.games_per_pair, 0);
+    r.wld.assign(r.K * r.K * 3, 0);
+    r.results.assign(std::max<size_t>(r.games, 1), 0);
+    e.check(az_tournament(e.raw(), p.model_ids.data(), (int32_t)r.K, p.games_per_pair, p.num_sims, p.max_depth, p.cpuct, p.num_sim_threads, p.reserve,
+                          p.seed, r.wld.data(), r.results.data()));
+    r.results.resize(r.games);
+    r.game_len.assign(r.games, 0);
+    r.moves.assign(r.games * AZ_MAX_PLIES, 0);
+    e.check(az_arena_get_moves(e.raw(), r.game_len.data(), r.moves.data()));
+    return r;
+}
+// Bradley-Terry ratings (a draw = half a win): elo [K] with mean 0 and elo_se [K], the diagonal Fisher approximation.  Needs no engine
+struct Ratings { std::vector<double> elo, elo_se; int32_t sweeps = 0; };
+inline Ratings rating_fit(const std::vector<uint64_t>& wld, size_t K, double prior_games = 2.0) {
+    if (!az_rating_fit) throw Panic("rating_fit: the linked engine library has no az_rating_fit");
+    if (wld.size() != K * K * 3) throw Panic("rating_fit: wld must hold K * K * 3 counts");
+    Ratings r{std::vector<double>(K, 0.0), std::vector<double>(K, 0.0), 0};
+    if (az_rating_fit(wld.data(), (int32_t)K, prior_games, r.elo.data(), r.elo_se.data(), &r.sweeps) != AZ_OK)
+        throw Panic("rating_fit: K outside 2 .. 16, or a negative or non-finite prior_games");
+    return r;
+}
 
 // The move-quality tally of one arena shard: counts[0] the new model's moves, counts[1] the old model's, each {examined, kept, win_to_draw,
 // win_to_loss, draw_to_loss, unknown}.  Game g of the shard has global index first_game + g; the new model holds the first seat in the

@@ -142,6 +142,11 @@ extern "C" {
     // paired arena openings ("arena_opening_plies"): the opening book, and where the games of the last az_arena started
     pub fn az_arena_set_opening_book(e: *mut az_engine, boards: *const u64, n: i32) -> c_int;
     pub fn az_arena_get_openings(e: *mut az_engine, boards: *mut u64, len: *mut i32, moves: *mut u8) -> c_int;
+    // one batched round robin of num_models models: wld [K][K][3], results [pairs * games_per_pair] in tournament order (game g of pair p of
+    // the pairs (i, j), i < j, is game g of az_arena(model_ids[i], model_ids[j]) bit for bit); plain scalars, no new #[repr(C)] type
+    pub fn az_tournament(e: *mut az_engine, model_ids: *const i32, num_models: i32, games_per_pair: i32, num_sims: i32, max_depth: i32, cpuct: i32, num_sim_threads: i32, reserve: u64, seed: u64, wld: *mut u64, results: *mut i8) -> c_int;
+    // Bradley-Terry ratings from that matrix (no engine, no GPU): elo [K] with mean 0, elo_se [K] (approximate; may be null), sweeps (may be null)
+    pub fn az_rating_fit(wld: *const u64, K: i32, prior_games: f64, elo: *mut f64, elo_se: *mut f64, sweeps: *mut i32) -> c_int;
     // ---- the collective of the sharded Coach loop (one process per GPU; RCCL on the engine's stream)
     pub fn az_comm_unique_id(e: *mut az_engine, id: *mut u8) -> c_int;
     // an in-process communicator: engines of this process, one host thread each, form one world without RCCL
