@@ -360,12 +360,12 @@ struct az_engine {
     int64_t arena_opening_plies = 0;
     std::vector<uint64_t> ar_book;      // [entries][2] {first seat's stones, second seat's stones}; empty = no book
     std::vector<uint64_t> sp_full_plies;        // az_selfplay_get_full_plies: the full-ply masks of the last az_selfplay / az_selfplay_next
-    // activation workspaces of the conv net: [0] the engine stream, [1] a second concurrent stream (az_arena's old-model
-    // search); created on first use, shared by every model id
-    // [2], [3]: the further side streams of az_tournament (side[1], side[2] below; side[0] shares [1])
+    // activation workspaces of the conv net, one per stream that runs forwards: [0] the engine stream, [1 + i] side[i] below; created on
+    // first use, shared by every model id
     NetWorkspace* ws[4] = {nullptr, nullptr, nullptr, nullptr};
-    // az_tournament's side streams, created by its first call and kept (a search graph's key holds its stream): the models' searches of
-    // a ply run on the engine's stream and these
+    // the side streams of az_arena and az_tournament (match_run): the models' searches of a ply run on the engine's stream and these.  Each
+    // is created by the first call that needs it and kept until az_destroy (a search graph's key holds its stream); az_arena's old model
+    // searches on side[0]
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     // eval log of the last az_selfplay
     std::vector<int32_t> sp_log_count;
@@ -2317,6 +2317,227 @@ static void record_common_opening(az_engine* e, int G, uint64_t a, uint64_t b) {
     e->ar_open_moves.assign((size_t)G * OPENING_MAX_PLIES, 0);
 }
 
+// ---- the match driver of az_arena and az_tournament -------------------------------------------------------------
+// P = K (K - 1) / 2 pairs of K models play n games each in ONE chain of plies: game p * n + g is game first + g of the pair's arena, and
+// model k searches ONE tree batch of the (K - 1) n games it plays in, whichever pair they belong to.  K = 2, P = 1 is az_arena itself (or
+// one shard of it): the table is the identity and each model's batch is the arena's n trees.
+namespace {
+constexpr int MATCH_MAX_MODELS = 16;
+
+struct MatchParams {
+    const char* who;                 // "arena" / "tournament": the error texts' prefix
+    int K;
+    NetModel* const* nets;           // [K]; the pairs are (i, j), i < j, in lexicographic order: i is the pair's "new" model, j its "old" one
+    int n, half, first;              // games per pair played here; ArenaDev::half and ::first (a shard's offset; 0 for the tournament)
+    int32_t num_sims, max_depth, cpuct;
+    int T;
+    uint64_t reserve, seed;
+    const uint64_t* start_board;     // [2] play_games' `board` (src/arena.rs:62-67), the openings' base; nullptr = the initial board
+    int record_evals;                // > 0 (K == 2 only): eval logs of the two models' trees, kept in e->ar_log
+};
+
+// {W, L, D} of a pair's first listed model over the pair's games [first, first + n): it holds the first seat below half (src/arena.rs:80-81)
+void tally_wld(const int8_t* res, int n, int first, int half, uint64_t wld[3]) {
+    wld[0] = wld[1] = wld[2] = 0;
+    for (int g = 0; g < n; ++g) {
+        const int win_cond = first + g < half ? 1 : -1;
+        wld[res[g] == win_cond ? 0 : (res[g] == -win_cond ? 1 : 2)]++;
+    }
+}
+
+// pair_wld [P][3] and results [P * n] (may be nullptr) are written, and the e->ar_* records replaced, only when the whole call succeeded
+az_status match_run(az_engine* e, const MatchParams& m, uint64_t* pair_wld, int8_t* results) {
+    const int K = m.K, n = m.n, P = K * (K - 1) / 2, PN = P * n, Gk = (K - 1) * n, T = m.T;
+    NetModel* const* nets = m.nets;
+    const std::string who = m.who;
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        // one tree PAIR per game (B8 repair): the reference shares one nmcts / one pmcts across all games
+        // (src/coach.rs:333-354) and their u16 root counters would wrap at 65536 visits.
+        const int calls = AZ_MAX_PLIES / 2 + 1;
+        const uint64_t nodes = std::min<uint64_t>(m.reserve, reachable_slots(m.num_sims, calls));
+        const uint64_t blocks = reachable_blocks(m.num_sims, calls, nodes);
+        if (az_status cs = check_tree_slots(e, blocks)) return cs;
+        // The searches of a ply touch disjoint trees and (for different models) disjoint net workspaces, so they overlap: the models are dealt
+        // round robin over the engine's stream and up to three side streams; two seats on one model or on one set of weights share a stream
+        int stream_of[MATCH_MAX_MODELS], n_streams = 0;
+        for (int k = 0; k < K; ++k) {
+            stream_of[k] = -1;
+            for (int j = 0; j < k; ++j)
+                if (nets[k] == nets[j] || (nets[k]->conv && nets[k]->conv == nets[j]->conv)) { stream_of[k] = stream_of[j]; break; }
+            if (stream_of[k] < 0) stream_of[k] = n_streams++ % 4;
+        }
+        n_streams = std::min(n_streams, 4);
+        hipStream_t streams[4] = {s, nullptr, nullptr, nullptr};
+        for (int i = 1; i < n_streams; ++i) {
+            if (!e->side[i - 1]) HIPCHK(hipStreamCreate(&e->side[i - 1]));
+            streams[i] = e->side[i - 1];
+        }
+        struct Events {
+            hipEvent_t fork = nullptr, join[3] = {nullptr, nullptr, nullptr};
+            ~Events() { if (fork) (void)hipEventDestroy(fork); for (hipEvent_t j : join) if (j) (void)hipEventDestroy(j); }
+        } ev;
+        if (n_streams > 1) {
+            HIPCHK(hipEventCreateWithFlags(&ev.fork, hipEventDisableTiming));
+            for (int i = 1; i < n_streams; ++i) HIPCHK(hipEventCreateWithFlags(&ev.join[i - 1], hipEventDisableTiming));
+        }
+        TreeLease lease[MATCH_MAX_MODELS];
+        for (int k = 0; k < K; ++k) acquire_trees(e, lease[k], Gk, blocks, nodes, hash_entries(m.num_sims, calls), T, s);
+        DeviceMem mem;
+        ArenaDev ad{};
+        ad.G = PN; ad.half = m.half; ad.first = m.first;
+        ad.state = mem.alloc<ulonglong2>(PN);
+        ad.player = mem.alloc<int8_t>(PN);
+        ad.alive = mem.alloc<uint8_t>(PN);
+        ad.results = mem.alloc<int8_t>(PN);
+        ad.counters = mem.alloc<uint32_t>(2 + MATCH_MAX_MODELS);    // [2 + k]: the largest leaf batch of the ply of model k (tile / kernel choice of the next ply)
+        ad.moves = mem.alloc<uint8_t>((size_t)PN * AZ_MAX_PLIES);
+        ad.len = mem.alloc<int32_t>(PN);
+        HIPCHK(hipMemset(ad.moves, 0, (size_t)PN * AZ_MAX_PLIES));
+        HIPCHK(hipMemset(ad.len, 0, (size_t)PN * sizeof(int32_t)));
+        // the tables: model k's trees are its pairs in the pairs' order, n games each
+        MatchTable tb[MATCH_MAX_MODELS];
+        {
+            std::vector<uint32_t> h((size_t)K * Gk);
+            std::vector<int> fill((size_t)K, 0);
+            int pidx = 0;
+            for (int i = 0; i < K; ++i)
+                for (int j = i + 1; j < K; ++j, ++pidx)
+                    for (int g = 0; g < n; ++g) {
+                        h[(size_t)i * Gk + fill[i]++] = (uint32_t)(pidx * n + g);
+                        h[(size_t)j * Gk + fill[j]++] = (uint32_t)(pidx * n + g) | 0x80000000u;
+                    }
+            uint32_t* d_tab = mem.alloc<uint32_t>(h.size());
+            ulonglong2* d_roots = mem.alloc<ulonglong2>((size_t)K * Gk);
+            HIPCHK(hipMemcpy(d_tab, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIPCHK(hipMemset(d_roots, 0, (size_t)K * Gk * sizeof(ulonglong2)));
+            for (int k = 0; k < K; ++k) tb[k] = MatchTable{d_tab + (size_t)k * Gk, d_roots + (size_t)k * Gk, n, 0};
+        }
+        // paired openings: game g of a pair and its seat-swapped twin g + half start from the opening of pair g % half (csrc/az_opening.h)
+        const bool openings = e->arena_opening_plies > 0 || !e->ar_book.empty();
+        const ulonglong2 base = m.start_board ? make_ulonglong2(m.start_board[0], m.start_board[1]) : make_ulonglong2(0ull, 0ull);
+        ArenaOpenings op{};
+        std::vector<uint64_t> open_boards;                      // the positions the games start from, before the first ply changes ad.state
+        if (openings) {
+            // one lane per game draws its opening into ad.state and the opening record; every pair of models plays the same ones
+            op.seed = m.seed;
+            op.plies = (int32_t)e->arena_opening_plies;
+            op.nb = (int32_t)(e->ar_book.size() / 2);
+            if (op.nb) {
+                ulonglong2* book = mem.alloc<ulonglong2>((size_t)op.nb);
+                HIPCHK(hipMemcpy(book, e->ar_book.data(), e->ar_book.size() * 8, hipMemcpyHostToDevice));
+                op.book = book;
+            }
+            op.base = base;
+            op.len = mem.alloc<int32_t>(PN);
+            op.moves = mem.alloc<uint8_t>((size_t)PN * OPENING_MAX_PLIES);
+            for (int p = 0; p < P; ++p) {
+                ArenaDev av = ad;
+                av.G = n; av.state = ad.state + (size_t)p * n;
+                ArenaOpenings ov = op;
+                ov.len = op.len + (size_t)p * n; ov.moves = op.moves + (size_t)p * n * OPENING_MAX_PLIES;
+                launch_arena_openings(e->cfg.game, av, ov, s);
+            }
+            open_boards.resize((size_t)PN * 2);
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipMemcpy(open_boards.data(), ad.state, open_boards.size() * 8, hipMemcpyDeviceToHost));
+        } else {
+            const std::vector<ulonglong2> st0((size_t)PN, base);
+            HIPCHK(hipMemcpy(ad.state, st0.data(), st0.size() * sizeof(ulonglong2), hipMemcpyHostToDevice));
+        }
+        HIPCHK(hipMemset(ad.player, 1, PN));
+        HIPCHK(hipMemset(ad.alive, 1, PN));
+        HIPCHK(hipMemset(ad.results, 0, PN));
+        uint32_t ctr[2 + MATCH_MAX_MODELS] = {(uint32_t)PN, 0u};
+        HIPCHK(hipMemcpy(ad.counters, ctr, sizeof ctr, hipMemcpyHostToDevice));
+        int typ[MATCH_MAX_MODELS] = {};              // expected rows per leaf batch, per model (0 = unknown: assume every running game)
+        ScopedEvalLog logs[2];
+        if (m.record_evals > 0)
+            for (int k = 0; k < 2; ++k) logs[k].attach(*lease[k], (size_t)Gk, m.record_evals, nullptr);
+        bool any_dedup = false;
+        for (int k = 0; k < K; ++k) { launch_reset_trees(lease[k]->d, nullptr, s); any_dedup = any_dedup || dedup_applies(e, *nets[k]); }
+        prepare_cache(e, any_dedup, (uint64_t)PN * AZ_MAX_PLIES * ((uint64_t)m.num_sims + 1), s);
+        for (int k = 0; k < K; ++k) (void)cache_for(e, *nets[k]);      // all tags are fixed before the first fork (retagging may clear the cache)
+        SearchParams sp{(uint32_t)m.max_depth, (float)m.cpuct};
+        az_status result = AZ_OK;
+        for (int ply = 0; ply <= AZ_MAX_PLIES; ++ply) {
+            for (int k = 0; k < K; ++k) launch_match_sync(lease[k]->d, ad, tb[k], s);
+            if (n_streams > 1) {
+                HIPCHK(hipEventRecord(ev.fork, s));
+                for (int i = 1; i < n_streams; ++i) HIPCHK(hipStreamWaitEvent(streams[i], ev.fork, 0));
+            }
+            // the side streams' models first, so that their searches are queued while the host issues the engine stream's
+            for (int pass = 0; pass < 2; ++pass)
+                for (int k = 0; k < K; ++k) {
+                    if ((stream_of[k] == 0) != (pass == 1)) continue;
+                    run_search(e, *lease[k], tb[k].roots, m.num_sims, sp, *nets[k], (int)std::min<uint32_t>(ctr[0], (uint32_t)Gk), streams[stream_of[k]],
+                               typ[k], ad.counters + 2 + k);
+                }
+            for (int i = 1; i < n_streams; ++i) {
+                HIPCHK(hipEventRecord(ev.join[i - 1], streams[i]));
+                HIPCHK(hipStreamWaitEvent(s, ev.join[i - 1], 0));
+            }
+            for (int k = 0; k < K; ++k) launch_match_move(lease[k]->d, ad, tb[k], m.seed, s);
+            HIPCHK(hipMemcpyAsync(ctr, ad.counters, sizeof ctr, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            resolve_profile(e);
+            for (int k = 0; k < K; ++k) typ[k] = (int)std::min<uint32_t>(ctr[2 + k], (uint32_t)(Gk * T));
+            HIPCHK(hipMemsetAsync(ad.counters + 2, 0, MATCH_MAX_MODELS * sizeof(uint32_t), s));
+            if (ctr[1]) { result = fail(e, AZ_ERR_INVALID_MOVE, who + ": action is not valid (src/arena.rs:31-35)"); break; }
+            if (ctr[0] == 0) break;
+        }
+        for (int k = 0; k < K; ++k) harvest_stats(e, *lease[k], *nets[k]);
+        for (int k = 0; k < K; ++k) if (result == AZ_OK) result = check_tree_errors(e, *lease[k]);
+        if (result) return result;
+        if (ctr[0] != 0) return fail(e, AZ_ERR_HIP, "az_" + who + ": games did not finish");
+        // everything to host vectors first ...
+        std::vector<int8_t> res((size_t)PN);
+        HIPCHK(hipMemcpy(res.data(), ad.results, (size_t)PN, hipMemcpyDeviceToHost));
+        std::vector<uint8_t> moves((size_t)PN * AZ_MAX_PLIES), open_moves;
+        std::vector<int32_t> len((size_t)PN), open_len;
+        HIPCHK(hipMemcpy(moves.data(), ad.moves, moves.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(len.data(), ad.len, len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (openings) {
+            open_len.resize((size_t)PN);
+            open_moves.resize((size_t)PN * OPENING_MAX_PLIES);
+            HIPCHK(hipMemcpy(open_len.data(), op.len, open_len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(open_moves.data(), op.moves, open_moves.size(), hipMemcpyDeviceToHost));
+        }
+        az_engine::EvalLog evals[2];
+        if (m.record_evals > 0)
+            for (int k = 0; k < 2; ++k) {
+                std::vector<TreeLine> heads((size_t)Gk);
+                HIPCHK(hipMemcpy(heads.data(), lease[k]->d.head, heads.size() * sizeof(TreeLine), hipMemcpyDeviceToHost));
+                evals[k].count.resize((size_t)Gk);
+                for (int g = 0; g < Gk; ++g) evals[k].count[g] = (int32_t)heads[g].head.log_len;
+                logs[k].copy_out(evals[k].states, evals[k].pi, evals[k].v);
+            }
+        if (results) HIPCHK(hipMemcpy(results, res.data(), (size_t)PN, hipMemcpyDefault));
+        // ... nothing can fail from here on: the outputs and the records of the last call change together
+        for (int p = 0; p < P; ++p) tally_wld(res.data() + (size_t)p * n, n, m.first, m.half, pair_wld + 3 * (size_t)p);
+        e->ar_moves = std::move(moves);
+        e->ar_len = std::move(len);
+        if (openings) {
+            e->ar_open_boards = std::move(open_boards);
+            e->ar_open_len = std::move(open_len);
+            e->ar_open_moves = std::move(open_moves);
+        } else {
+            record_common_opening(e, PN, base.x, base.y);
+        }
+        e->ar_log_cap = 0;            // without record_evals there is no eval log: az_arena_get_evals is refused
+        if (m.record_evals > 0) {
+            for (int k = 0; k < 2; ++k) e->ar_log[k] = std::move(evals[k]);
+            e->ar_log_cap = m.record_evals;
+            e->ar_log_games = PN;
+        }
+        e->stats.games += (uint64_t)PN;
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+}  // namespace
+
 az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], int8_t* results) {
     if (!e || !p || !out_wld) return AZ_ERR_BAD_ARGUMENT;
     if (p->num_games < 0 || p->num_sims <= 0 || p->max_depth < 0 || p->reserve < 8)
@@ -2342,8 +2563,6 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
     if (p->record_evals < 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: negative record_evals");
     if (p->use_start_board && !e->ar_book.empty())
         return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: start_board while an opening book is set (az_arena_set_opening_book with n = 0 clears it)");
-    // paired openings: game g and its seat-swapped twin g + half start from the opening of pair g % half (csrc/az_opening.h)
-    const bool openings = e->arena_opening_plies > 0 || !e->ar_book.empty();
     if (p->use_start_board) {
         const uint64_t a = p->start_board[0], b = p->start_board[1];
         if ((a & b) || ((a | b) & ~C4_FULL)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: start_board is not a pair of disjoint 7x6 bitboards");
@@ -2353,10 +2572,7 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
         if (ec != E_NONE) {
             const int8_t r = ec == E_MINUS1 ? 1 : (ec == E_PLUS1 ? -1 : 0);
             std::vector<int8_t> res((size_t)G, r);
-            for (int g = 0; g < G; ++g) {
-                const int win_cond = first + g < half ? 1 : -1;
-                if (r == win_cond) out_wld[0]++; else if (r == -win_cond) out_wld[1]++; else out_wld[2]++;
-            }
+            tally_wld(res.data(), G, first, half, out_wld);
             if (results && hipMemcpy(results, res.data(), (size_t)G, hipMemcpyDefault) != hipSuccess) return fail(e, AZ_ERR_HIP, "az_arena: results copy");
             e->stats.games += (uint64_t)G;
             e->ar_log_cap = 0;
@@ -2367,374 +2583,37 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
             return AZ_OK;
         }
     }
-    NetModel *net_new, *net_old;
-    az_status st = find_net(e, p->new_model_id, &net_new);
+    NetModel* nets[2];          // {new, old}
+    az_status st = find_net(e, p->new_model_id, &nets[0]);
     if (st) return st;
-    st = find_net(e, p->old_model_id, &net_old);
+    st = find_net(e, p->old_model_id, &nets[1]);
     if (st) return st;
     int T = p->num_sim_threads;
     st = check_threads(e, p->num_sims, &T);
     if (st) return st;
-    st = check_batch(e, *net_new, G * T);
+    st = check_batch(e, *nets[0], G * T);
     if (st) return st;
-    st = check_batch(e, *net_old, G * T);
+    st = check_batch(e, *nets[1], G * T);
     if (st) return st;
-    ScopedTimer timer{e};
-    try {
-        HIPCHK(hipSetDevice(e->device));
-        hipStream_t s = e->stream;
-        // one tree PAIR per game (B8 repair): the reference shares one nmcts / one pmcts across all games
-        // (src/coach.rs:333-354) and their u16 root counters would wrap at 65536 visits.
-        const int calls = AZ_MAX_PLIES / 2 + 1;
-        const uint64_t nodes = std::min<uint64_t>(p->reserve, reachable_slots(p->num_sims, calls));
-        TreeLease lease_n, lease_o;
-        if (az_status cs = check_tree_slots(e, reachable_blocks(p->num_sims, calls, nodes))) return cs;
-        acquire_trees(e, lease_n, G, reachable_blocks(p->num_sims, calls, nodes), nodes, hash_entries(p->num_sims, calls), T, s);
-        acquire_trees(e, lease_o, G, reachable_blocks(p->num_sims, calls, nodes), nodes, hash_entries(p->num_sims, calls), T, s);
-        TreeHost &tn = *lease_n, &to = *lease_o;
-        DeviceMem mem;
-        ArenaDev ad{};
-        ad.G = G; ad.half = half; ad.first = first;
-        ad.state = mem.alloc<ulonglong2>(G);
-        ad.player = mem.alloc<int8_t>(G);
-        ad.alive = mem.alloc<uint8_t>(G);
-        ad.results = mem.alloc<int8_t>(G);
-        ad.counters = mem.alloc<uint32_t>(4);          // [2], [3]: the largest leaf batch of the ply, per model (tile / kernel choice of the next ply)
-        ad.moves = mem.alloc<uint8_t>((size_t)G * AZ_MAX_PLIES);
-        ad.len = mem.alloc<int32_t>(G);
-        HIPCHK(hipMemset(ad.moves, 0, (size_t)G * AZ_MAX_PLIES));
-        HIPCHK(hipMemset(ad.len, 0, (size_t)G * sizeof(int32_t)));
-        ArenaOpenings op{};
-        if (openings) {
-            // one lane per game draws its pair's opening into ad.state and the opening record
-            op.seed = p->seed;
-            op.plies = (int32_t)e->arena_opening_plies;
-            op.nb = (int32_t)(e->ar_book.size() / 2);
-            if (op.nb) {
-                ulonglong2* book = mem.alloc<ulonglong2>((size_t)op.nb);
-                HIPCHK(hipMemcpy(book, e->ar_book.data(), e->ar_book.size() * 8, hipMemcpyHostToDevice));
-                op.book = book;
-            }
-            op.base = p->use_start_board ? make_ulonglong2(p->start_board[0], p->start_board[1]) : make_ulonglong2(0ull, 0ull);
-            op.len = mem.alloc<int32_t>(G);
-            op.moves = mem.alloc<uint8_t>((size_t)G * OPENING_MAX_PLIES);
-            launch_arena_openings(e->cfg.game, ad, op, s);
-        } else {
-            // play_games' `board` (src/arena.rs:62-67): None = the initial board
-            std::vector<uint64_t> st0((size_t)G * 2, 0ull);
-            if (p->use_start_board)
-                for (int g = 0; g < G; ++g) { st0[2 * (size_t)g] = p->start_board[0]; st0[2 * (size_t)g + 1] = p->start_board[1]; }
-            HIPCHK(hipMemcpy(ad.state, st0.data(), st0.size() * 8, hipMemcpyHostToDevice));
-        }
-        std::vector<uint64_t> open_boards;                      // the positions the games start from, before the first ply changes ad.state
-        if (openings) {
-            open_boards.resize((size_t)G * 2);
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipMemcpy(open_boards.data(), ad.state, open_boards.size() * 8, hipMemcpyDeviceToHost));
-        }
-        HIPCHK(hipMemset(ad.player, 1, G));
-        HIPCHK(hipMemset(ad.alive, 1, G));
-        HIPCHK(hipMemset(ad.results, 0, G));
-        uint32_t ctr[4] = {(uint32_t)G, 0u, 0u, 0u};
-        HIPCHK(hipMemcpy(ad.counters, ctr, sizeof ctr, hipMemcpyHostToDevice));
-        int typ_new = 0, typ_old = 0;                   // expected rows per leaf batch (0 = unknown: assume every running game)
-        ScopedEvalLog log_n, log_o;
-        if (p->record_evals > 0) {
-            log_n.attach(tn, (size_t)G, p->record_evals, nullptr);
-            log_o.attach(to, (size_t)G, p->record_evals, nullptr);
-        }
-        launch_reset_trees(tn.d, nullptr, s);
-        launch_reset_trees(to.d, nullptr, s);
-        prepare_cache(e, dedup_applies(e, *net_new) || dedup_applies(e, *net_old), (uint64_t)G * AZ_MAX_PLIES * ((uint64_t)p->num_sims + 1), s);
-        // both models' tags are fixed before the two streams fork (retagging may clear the cache)
-        (void)cache_for(e, *net_new);
-        (void)cache_for(e, *net_old);
-        SearchParams sp{(uint32_t)p->max_depth, (float)p->cpuct};
-        az_status result = AZ_OK;
-        // The two searches of a ply touch disjoint trees and (for two different models) disjoint net workspaces:
-        // run the old model's on a second stream so its half batches overlap the new model's.
-        struct Side {
-            hipStream_t s2 = nullptr; hipEvent_t fork = nullptr, join = nullptr;
-            ~Side() { if (s2) (void)hipStreamDestroy(s2); if (fork) (void)hipEventDestroy(fork); if (join) (void)hipEventDestroy(join); }
-        } side;
-        const bool overlap = net_new != net_old && !(net_new->conv && net_new->conv == net_old->conv);
-        if (overlap) {
-            HIPCHK(hipStreamCreate(&side.s2));
-            HIPCHK(hipEventCreateWithFlags(&side.fork, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&side.join, hipEventDisableTiming));
-        }
-        for (int ply = 0; ply <= AZ_MAX_PLIES; ++ply) {
-            launch_arena_sync(tn.d, to.d, ad, s);
-            if (overlap) {
-                HIPCHK(hipEventRecord(side.fork, s));
-                HIPCHK(hipStreamWaitEvent(side.s2, side.fork, 0));
-                run_search(e, to, ad.state, p->num_sims, sp, *net_old, (int)ctr[0], side.s2, typ_old, ad.counters + 3);
-                run_search(e, tn, ad.state, p->num_sims, sp, *net_new, (int)ctr[0], s, typ_new, ad.counters + 2);
-                HIPCHK(hipEventRecord(side.join, side.s2));
-                HIPCHK(hipStreamWaitEvent(s, side.join, 0));
-            } else {
-                run_search(e, tn, ad.state, p->num_sims, sp, *net_new, (int)ctr[0], nullptr, typ_new, ad.counters + 2);
-                run_search(e, to, ad.state, p->num_sims, sp, *net_old, (int)ctr[0], nullptr, typ_old, ad.counters + 3);
-            }
-            launch_arena_move(tn.d, ad, p->seed, s);
-            launch_arena_move(to.d, ad, p->seed, s);
-            HIPCHK(hipMemcpyAsync(ctr, ad.counters, sizeof ctr, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            resolve_profile(e);
-            typ_new = (int)std::min<uint32_t>(ctr[2], (uint32_t)(G * T));
-            typ_old = (int)std::min<uint32_t>(ctr[3], (uint32_t)(G * T));
-            HIPCHK(hipMemsetAsync(ad.counters + 2, 0, 2 * sizeof(uint32_t), s));
-            if (ctr[1]) { result = fail(e, AZ_ERR_INVALID_MOVE, "arena: action is not valid (src/arena.rs:31-35)"); break; }
-            if (ctr[0] == 0) break;
-        }
-        harvest_stats(e, tn, *net_new);
-        harvest_stats(e, to, *net_old);
-        if (result == AZ_OK) result = check_tree_errors(e, tn);
-        if (result == AZ_OK) result = check_tree_errors(e, to);
-        if (result) return result;
-        if (ctr[0] != 0) return fail(e, AZ_ERR_HIP, "az_arena: games did not finish");
-        std::vector<int8_t> res(G);
-        HIPCHK(hipMemcpy(res.data(), ad.results, G, hipMemcpyDeviceToHost));
-        for (int g = 0; g < G; ++g) {
-            const int win_cond = first + g < half ? 1 : -1, lose_cond = -win_cond;   // src/arena.rs:80-81
-            if (res[g] == win_cond) out_wld[0]++;
-            else if (res[g] == lose_cond) out_wld[1]++;
-            else out_wld[2]++;
-        }
-        if (results) HIPCHK(hipMemcpy(results, res.data(), G, hipMemcpyDefault));
-        e->ar_moves.resize((size_t)G * AZ_MAX_PLIES);
-        e->ar_len.resize((size_t)G);
-        HIPCHK(hipMemcpy(e->ar_moves.data(), ad.moves, e->ar_moves.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(e->ar_len.data(), ad.len, e->ar_len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (openings) {
-            e->ar_open_boards = std::move(open_boards);
-            e->ar_open_len.resize((size_t)G);
-            e->ar_open_moves.resize((size_t)G * OPENING_MAX_PLIES);
-            HIPCHK(hipMemcpy(e->ar_open_len.data(), op.len, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(e->ar_open_moves.data(), op.moves, (size_t)G * OPENING_MAX_PLIES, hipMemcpyDeviceToHost));
-        } else {
-            record_common_opening(e, G, p->use_start_board ? p->start_board[0] : 0ull, p->use_start_board ? p->start_board[1] : 0ull);
-        }
-        e->stats.games += (uint64_t)G;
-        if (p->allreduce_wld) {       // every rank returns the whole arena's tally (one 3-counter all-reduce)
-            az_status rs = az_allreduce_u64(e, out_wld, 3);
-            if (rs) return rs;
-        }
-        e->ar_log_cap = 0;
-        if (p->record_evals > 0) {
-            TreeHost* ths[2] = {&tn, &to};
-            const ScopedEvalLog* logs[2] = {&log_n, &log_o};
-            for (int w = 0; w < 2; ++w) {
-                std::vector<TreeLine> heads(G);
-                HIPCHK(hipMemcpy(heads.data(), ths[w]->d.head, (size_t)G * sizeof(TreeLine), hipMemcpyDeviceToHost));
-                e->ar_log[w].count.resize(G);
-                for (int g = 0; g < G; ++g) e->ar_log[w].count[g] = (int32_t)heads[g].head.log_len;
-                logs[w]->copy_out(e->ar_log[w].states, e->ar_log[w].pi, e->ar_log[w].v);
-            }
-            e->ar_log_cap = p->record_evals;
-            e->ar_log_games = G;
-        }
-        return AZ_OK;
-    } catch (const HipFail& f) { return fail_hip(e, f); }
+    const MatchParams m{"arena", 2, nets, G, half, first, p->num_sims, p->max_depth, p->cpuct, T, p->reserve, p->seed,
+                        p->use_start_board ? p->start_board : nullptr, p->record_evals};
+    st = match_run(e, m, out_wld, results);
+    if (st) return st;
+    if (p->allreduce_wld) return az_allreduce_u64(e, out_wld, 3);     // every rank returns the whole arena's tally (one 3-counter all-reduce)
+    return AZ_OK;
 }
-
-// ---- az_tournament: one batched round robin ---------------------------------------------------------------------
-// The games of all P = K (K - 1) / 2 pairs share one chain of plies: game p * n + g is game g of az_arena(model_ids[i], model_ids[j]), and
-// model k searches ONE tree batch of the (K - 1) n games it plays in, whichever pair they belong to.
-namespace {
-constexpr int TOURNAMENT_MAX_MODELS = 16;
-
-az_status tournament_run(az_engine* e, int K, int n, int32_t num_sims, int32_t max_depth, int32_t cpuct, int T, uint64_t reserve, uint64_t seed,
-                         NetModel* const* nets, uint64_t* wld, int8_t* results) {
-    const int P = K * (K - 1) / 2, PN = P * n, half = n / 2, Gk = (K - 1) * n;
-    ScopedTimer timer{e};
-    try {
-        HIPCHK(hipSetDevice(e->device));
-        hipStream_t s = e->stream;
-        const int calls = AZ_MAX_PLIES / 2 + 1;
-        const uint64_t nodes = std::min<uint64_t>(reserve, reachable_slots(num_sims, calls));
-        const uint64_t blocks = reachable_blocks(num_sims, calls, nodes);
-        if (az_status cs = check_tree_slots(e, blocks)) return cs;
-        // the streams: models dealt round robin over the engine's stream and up to three side streams; two ids on one set of weights share a stream
-        int stream_of[TOURNAMENT_MAX_MODELS], n_streams = 0;
-        for (int k = 0; k < K; ++k) {
-            stream_of[k] = -1;
-            for (int j = 0; j < k; ++j)
-                if (nets[k]->conv && nets[k]->conv == nets[j]->conv) { stream_of[k] = stream_of[j]; break; }
-            if (stream_of[k] < 0) stream_of[k] = n_streams++ % 4;
-        }
-        n_streams = std::min(n_streams, 4);
-        hipStream_t streams[4] = {s, nullptr, nullptr, nullptr};
-        for (int i = 1; i < n_streams; ++i) {
-            if (!e->side[i - 1]) HIPCHK(hipStreamCreate(&e->side[i - 1]));
-            streams[i] = e->side[i - 1];
-        }
-        struct Events {
-            hipEvent_t fork = nullptr, join[3] = {nullptr, nullptr, nullptr};
-            ~Events() { if (fork) (void)hipEventDestroy(fork); for (hipEvent_t j : join) if (j) (void)hipEventDestroy(j); }
-        } ev;
-        if (n_streams > 1) {
-            HIPCHK(hipEventCreateWithFlags(&ev.fork, hipEventDisableTiming));
-            for (int i = 1; i < n_streams; ++i) HIPCHK(hipEventCreateWithFlags(&ev.join[i - 1], hipEventDisableTiming));
-        }
-        // one tree per game and model, as the arena's pair: 2 P n trees in all
-        TreeLease lease[TOURNAMENT_MAX_MODELS];
-        for (int k = 0; k < K; ++k) acquire_trees(e, lease[k], Gk, blocks, nodes, hash_entries(num_sims, calls), T, s);
-        DeviceMem mem;
-        ArenaDev ad{};
-        ad.G = PN; ad.half = half; ad.first = 0;
-        ad.state = mem.alloc<ulonglong2>(PN);
-        ad.player = mem.alloc<int8_t>(PN);
-        ad.alive = mem.alloc<uint8_t>(PN);
-        ad.results = mem.alloc<int8_t>(PN);
-        ad.counters = mem.alloc<uint32_t>(2 + TOURNAMENT_MAX_MODELS);    // [2 + k]: the largest leaf batch of the ply of model k
-        ad.moves = mem.alloc<uint8_t>((size_t)PN * AZ_MAX_PLIES);
-        ad.len = mem.alloc<int32_t>(PN);
-        HIPCHK(hipMemset(ad.moves, 0, (size_t)PN * AZ_MAX_PLIES));
-        HIPCHK(hipMemset(ad.len, 0, (size_t)PN * sizeof(int32_t)));
-        // the tables: model k's trees are its pairs in the pairs' order, n games each
-        TournamentTable tb[TOURNAMENT_MAX_MODELS];
-        {
-            std::vector<uint32_t> h((size_t)K * Gk);
-            std::vector<int> fill((size_t)K, 0);
-            int pidx = 0;
-            for (int i = 0; i < K; ++i)
-                for (int j = i + 1; j < K; ++j, ++pidx)
-                    for (int g = 0; g < n; ++g) {
-                        h[(size_t)i * Gk + fill[i]++] = (uint32_t)(pidx * n + g);
-                        h[(size_t)j * Gk + fill[j]++] = (uint32_t)(pidx * n + g) | 0x80000000u;
-                    }
-            uint32_t* d_tab = mem.alloc<uint32_t>(h.size());
-            ulonglong2* d_roots = mem.alloc<ulonglong2>((size_t)K * Gk);
-            HIPCHK(hipMemcpy(d_tab, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIPCHK(hipMemset(d_roots, 0, (size_t)K * Gk * sizeof(ulonglong2)));
-            for (int k = 0; k < K; ++k) tb[k] = TournamentTable{d_tab + (size_t)k * Gk, d_roots + (size_t)k * Gk, n, 0};
-        }
-        const bool openings = e->arena_opening_plies > 0 || !e->ar_book.empty();
-        ArenaOpenings op{};
-        std::vector<uint64_t> open_boards;
-        if (openings) {
-            // every pair of models plays az_arena's openings of an n-game call: the index inside the pair draws them
-            op.seed = seed;
-            op.plies = (int32_t)e->arena_opening_plies;
-            op.nb = (int32_t)(e->ar_book.size() / 2);
-            if (op.nb) {
-                ulonglong2* book = mem.alloc<ulonglong2>((size_t)op.nb);
-                HIPCHK(hipMemcpy(book, e->ar_book.data(), e->ar_book.size() * 8, hipMemcpyHostToDevice));
-                op.book = book;
-            }
-            op.base = make_ulonglong2(0ull, 0ull);
-            op.len = mem.alloc<int32_t>(PN);
-            op.moves = mem.alloc<uint8_t>((size_t)PN * OPENING_MAX_PLIES);
-            for (int p = 0; p < P; ++p) {
-                ArenaDev av = ad;
-                av.G = n; av.state = ad.state + (size_t)p * n;
-                ArenaOpenings ov = op;
-                ov.len = op.len + (size_t)p * n; ov.moves = op.moves + (size_t)p * n * OPENING_MAX_PLIES;
-                launch_arena_openings(e->cfg.game, av, ov, s);
-            }
-            open_boards.resize((size_t)PN * 2);
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipMemcpy(open_boards.data(), ad.state, open_boards.size() * 8, hipMemcpyDeviceToHost));
-        } else {
-            HIPCHK(hipMemset(ad.state, 0, (size_t)PN * sizeof(ulonglong2)));
-        }
-        HIPCHK(hipMemset(ad.player, 1, PN));
-        HIPCHK(hipMemset(ad.alive, 1, PN));
-        HIPCHK(hipMemset(ad.results, 0, PN));
-        uint32_t ctr[2 + TOURNAMENT_MAX_MODELS] = {(uint32_t)PN, 0u};
-        HIPCHK(hipMemcpy(ad.counters, ctr, sizeof ctr, hipMemcpyHostToDevice));
-        int typ[TOURNAMENT_MAX_MODELS] = {};              // expected rows per leaf batch, per model (0 = unknown)
-        bool any_dedup = false;
-        for (int k = 0; k < K; ++k) { launch_reset_trees(lease[k]->d, nullptr, s); any_dedup = any_dedup || dedup_applies(e, *nets[k]); }
-        prepare_cache(e, any_dedup, (uint64_t)PN * AZ_MAX_PLIES * ((uint64_t)num_sims + 1), s);
-        for (int k = 0; k < K; ++k) (void)cache_for(e, *nets[k]);      // all tags are fixed before the first fork (retagging may clear the cache)
-        SearchParams sp{(uint32_t)max_depth, (float)cpuct};
-        az_status result = AZ_OK;
-        for (int ply = 0; ply <= AZ_MAX_PLIES; ++ply) {
-            for (int k = 0; k < K; ++k) launch_tournament_sync(lease[k]->d, ad, tb[k], s);
-            if (n_streams > 1) {
-                HIPCHK(hipEventRecord(ev.fork, s));
-                for (int i = 1; i < n_streams; ++i) HIPCHK(hipStreamWaitEvent(streams[i], ev.fork, 0));
-            }
-            // the side streams' models first, so that their searches are queued while the host issues the engine stream's
-            for (int pass = 0; pass < 2; ++pass)
-                for (int k = 0; k < K; ++k) {
-                    if ((stream_of[k] == 0) != (pass == 1)) continue;
-                    run_search(e, *lease[k], tb[k].roots, num_sims, sp, *nets[k], (int)std::min<uint32_t>(ctr[0], (uint32_t)Gk), streams[stream_of[k]],
-                               typ[k], ad.counters + 2 + k);
-                }
-            for (int i = 1; i < n_streams; ++i) {
-                HIPCHK(hipEventRecord(ev.join[i - 1], streams[i]));
-                HIPCHK(hipStreamWaitEvent(s, ev.join[i - 1], 0));
-            }
-            for (int k = 0; k < K; ++k) launch_tournament_move(lease[k]->d, ad, tb[k], seed, s);
-            HIPCHK(hipMemcpyAsync(ctr, ad.counters, sizeof ctr, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            resolve_profile(e);
-            for (int k = 0; k < K; ++k) typ[k] = (int)std::min<uint32_t>(ctr[2 + k], (uint32_t)(Gk * T));
-            HIPCHK(hipMemsetAsync(ad.counters + 2, 0, TOURNAMENT_MAX_MODELS * sizeof(uint32_t), s));
-            if (ctr[1]) { result = fail(e, AZ_ERR_INVALID_MOVE, "tournament: action is not valid (src/arena.rs:31-35)"); break; }
-            if (ctr[0] == 0) break;
-        }
-        for (int k = 0; k < K; ++k) harvest_stats(e, *lease[k], *nets[k]);
-        for (int k = 0; k < K; ++k) if (result == AZ_OK) result = check_tree_errors(e, *lease[k]);
-        if (result) return result;
-        if (ctr[0] != 0) return fail(e, AZ_ERR_HIP, "az_tournament: games did not finish");
-        std::vector<int8_t> res((size_t)PN);
-        HIPCHK(hipMemcpy(res.data(), ad.results, (size_t)PN, hipMemcpyDeviceToHost));
-        std::vector<uint8_t> moves((size_t)PN * AZ_MAX_PLIES), open_moves;
-        std::vector<int32_t> len((size_t)PN), open_len;
-        HIPCHK(hipMemcpy(moves.data(), ad.moves, moves.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(len.data(), ad.len, len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (openings) {
-            open_len.resize((size_t)PN);
-            open_moves.resize((size_t)PN * OPENING_MAX_PLIES);
-            HIPCHK(hipMemcpy(open_len.data(), op.len, open_len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(open_moves.data(), op.moves, open_moves.size(), hipMemcpyDeviceToHost));
-        }
-        if (results) HIPCHK(hipMemcpy(results, res.data(), (size_t)PN, hipMemcpyDefault));
-        // nothing can fail from here on: the outputs and the move record change together
-        for (size_t i = 0; i < (size_t)K * K * 3; ++i) wld[i] = 0;
-        int pidx = 0;
-        for (int i = 0; i < K; ++i)
-            for (int j = i + 1; j < K; ++j, ++pidx) {
-                uint64_t c[3] = {0, 0, 0};
-                for (int g = 0; g < n; ++g) {
-                    const int win_cond = g < half ? 1 : -1, r = res[(size_t)pidx * n + g];       // src/arena.rs:80-81
-                    c[r == win_cond ? 0 : (r == -win_cond ? 1 : 2)]++;
-                }
-                uint64_t *a = wld + ((size_t)i * K + j) * 3, *b = wld + ((size_t)j * K + i) * 3;
-                a[0] = c[0]; a[1] = c[1]; a[2] = c[2];
-                b[0] = c[1]; b[1] = c[0]; b[2] = c[2];
-            }
-        e->ar_moves = std::move(moves);
-        e->ar_len = std::move(len);
-        if (openings) {
-            e->ar_open_boards = std::move(open_boards);
-            e->ar_open_len = std::move(open_len);
-            e->ar_open_moves = std::move(open_moves);
-        } else {
-            record_common_opening(e, PN, 0ull, 0ull);
-        }
-        e->ar_log_cap = 0;            // there is no eval log here: az_arena_get_evals is refused
-        e->stats.games += (uint64_t)PN;
-        return AZ_OK;
-    } catch (const HipFail& f) { return fail_hip(e, f); }
-}
-}  // namespace
 
 az_status az_tournament(az_engine* e, const int32_t* model_ids, int32_t num_models, int32_t games_per_pair, int32_t num_sims, int32_t max_depth,
                         int32_t cpuct, int32_t num_sim_threads, uint64_t reserve, uint64_t seed, uint64_t* wld, int8_t* results) {
     if (!e) return AZ_ERR_BAD_ARGUMENT;
     if (!model_ids || !wld) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: model_ids and wld are required");
     const int K = num_models, n = games_per_pair;
-    if (K < 2 || K > TOURNAMENT_MAX_MODELS) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: 2 .. 16 models");
+    if (K < 2 || K > MATCH_MAX_MODELS) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: 2 .. 16 models");
     if (n < 2 || (n & 1)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: games_per_pair must be even and at least 2 (half per seating)");
     if ((int64_t)(K * (K - 1) / 2) * (int64_t)n > 1024 * 64) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: at most 65536 games");
     if (num_sims <= 0 || max_depth < 0 || reserve < 8) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: bad argument");
     if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: a self-play session is open (az_selfplay_end first)");
-    NetModel* nets[TOURNAMENT_MAX_MODELS];
+    NetModel* nets[MATCH_MAX_MODELS];
     for (int k = 0; k < K; ++k) {
         for (int j = 0; j < k; ++j)
             if (model_ids[j] == model_ids[k]) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tournament: model id " + std::to_string(model_ids[k]) + " is listed twice");
@@ -2744,7 +2623,20 @@ az_status az_tournament(az_engine* e, const int32_t* model_ids, int32_t num_mode
     if (az_status st = check_threads(e, num_sims, &T)) return st;
     for (int k = 0; k < K; ++k)
         if (az_status st = check_batch(e, *nets[k], (K - 1) * n * T)) return st;
-    const az_status st = tournament_run(e, K, n, num_sims, max_depth, cpuct, T, reserve, seed, nets, wld, results);
+    const int P = K * (K - 1) / 2;
+    std::vector<uint64_t> pair_wld((size_t)P * 3);
+    const MatchParams m{"tournament", K, nets, n, n / 2, 0, num_sims, max_depth, cpuct, T, reserve, seed, nullptr, 0};
+    const az_status st = match_run(e, m, pair_wld.data(), results);
+    if (st == AZ_OK) {
+        for (size_t i = 0; i < (size_t)K * K * 3; ++i) wld[i] = 0;
+        const uint64_t* c = pair_wld.data();
+        for (int i = 0; i < K; ++i)
+            for (int j = i + 1; j < K; ++j, c += 3) {
+                uint64_t *a = wld + ((size_t)i * K + j) * 3, *b = wld + ((size_t)j * K + i) * 3;
+                a[0] = c[0]; a[1] = c[1]; a[2] = c[2];
+                b[0] = c[1]; b[1] = c[0]; b[2] = c[2];
+            }
+    }
     // the pool keeps what it would keep after an az_arena: at most three idle tree arenas (the newest go first)
     try {
         for (size_t i = e->tree_pool.size(); i-- > 0 && e->tree_pool.size() > 3;)

@@ -240,10 +240,11 @@ struct SelfplayMoveParams {
     int32_t done_lo, done_hi; // counters[1] counts the finished episodes with done_lo <= index < done_hi (a session delivers its episodes in chunks)
 };
 
-// arena::play_games state (src/arena.rs:7-99): game g < half is seated (new, old), g >= half (old, new)
+// arena::play_games state (src/arena.rs:7-99) of az_arena (one pair of models, maybe one shard of its games) and az_tournament (every
+// pair's n games, pair after pair): a game whose index inside its pair is < half is seated (new, old), the others (old, new)
 struct ArenaDev {
-    int32_t G, half;       // games in this shard; global index below which a game is seated (new, old)
-    int32_t first;         // global index of this shard's game 0
+    int32_t G, half;       // games held here (the shard's; all pairs'); index inside the pair below which a game is seated (new, old)
+    int32_t first;         // index inside the pair of the pair's first game held here: the shard's first_game, 0 for a tournament
     ulonglong2* state;     // [G] canonical board of the position to move
     int8_t* player;        // [G] cur_player: +1 = first seat to move
     uint8_t* alive;        // [G]
@@ -264,13 +265,13 @@ struct ArenaOpenings {
     uint8_t* moves;          // [G][OPENING_MAX_PLIES] out: those actions, zero behind len
 };
 
-// az_tournament: tree g of ONE model's batch plays game (game[g] & TOURNAMENT_GAME_MASK) of the tournament's ArenaDev, whose games are
-// p * n + index inside pair p; bit 31 is set when the model is the pair's second listed one (az_arena's "old" model).
-constexpr uint32_t TOURNAMENT_GAME_MASK = 0x7FFFFFFFu;
-struct TournamentTable {
+// Tree g of ONE model's batch plays game (game[g] & MATCH_GAME_MASK) of the ArenaDev, whose games are p * n + g' for pair p; the game's
+// index inside its pair is first + g' (seating, tie-break stream).  Bit 31 is set when the model is the pair's second listed one ("old").
+constexpr uint32_t MATCH_GAME_MASK = 0x7FFFFFFFu;
+struct MatchTable {
     const uint32_t* game;    // [TreeDev.G]
-    ulonglong2* roots;       // [TreeDev.G] out (k_tournament_sync): the root state of the tree's game, what run_search takes as root_states
-    int32_t n;               // games per pair
+    ulonglong2* roots;       // [TreeDev.G] out (k_match_sync): the root state of the tree's game, what run_search takes as root_states
+    int32_t n;               // games per pair held in the ArenaDev
     int32_t pad;
 };
 
@@ -356,12 +357,10 @@ constexpr int GAME_COUNT = 2;    // 0 = ConnectFour (the reference's Game), 1 = 
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s);
 // writes ad.state[g] (the position game g starts from, first seat to move), op.len and op.moves for every game of the shard
 void launch_arena_openings(int game, const ArenaDev& ad, const ArenaOpenings& op, hipStream_t s);
-void launch_arena_sync(const TreeDev& t_new, const TreeDev& t_old, const ArenaDev& ad, hipStream_t s);
-void launch_arena_move(const TreeDev& t, const ArenaDev& ad, uint64_t seed, hipStream_t s);
-// az_tournament (ad.half = n / 2, ad.first = 0, ad.G = pairs * n): head.active and tb.roots of one model's batch from the per-game arrays;
-// then k_arena_move's rule for the trees that searched, through the table
-void launch_tournament_sync(const TreeDev& t, const ArenaDev& ad, const TournamentTable& tb, hipStream_t s);
-void launch_tournament_move(const TreeDev& t, const ArenaDev& ad, const TournamentTable& tb, uint64_t seed, hipStream_t s);
+// one ply of az_arena / az_tournament, per model: head.active and tb.roots of the model's batch from the per-game arrays; after the searches,
+// arena::play_game's rule for the trees that searched
+void launch_match_sync(const TreeDev& t, const ArenaDev& ad, const MatchTable& tb, hipStream_t s);
+void launch_match_move(const TreeDev& t, const ArenaDev& ad, const MatchTable& tb, uint64_t seed, hipStream_t s);
 void launch_emit_samples(const GamesDev& gd, const int64_t* offsets, int symmetries, ulonglong2* out_states,
                          float* out_boards, float* out_pis, float* out_zs, hipStream_t s);
 

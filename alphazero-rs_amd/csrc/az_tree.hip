@@ -1517,19 +1517,8 @@ __global__ __launch_bounds__(256) void k_arena_openings(ArenaDev ad, ArenaOpenin
 }
 
 // ---- arena::play_game, one ply for every running game (src/arena.rs:18-41) ------------------------
-// Which model moves: seat 0 moves when cur_player == +1; games g < half seat (new, old), the rest (old, new).
-__global__ void k_arena_sync(TreeDev tn, TreeDev to, ArenaDev ad) {
-    int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= ad.G) return;
-    const bool alive = ad.alive[g] != 0;
-    const int first_model = ad.first + g < ad.half ? 0 : 1;            // 0 = new, 1 = old (global game index)
-    const int mover = ad.player[g] == 1 ? first_model : 1 - first_model;
-    tn.head[g].head.active = (alive && mover == 0) ? 1u : 0u;
-    to.head[g].head.active = (alive && mover == 1) ? 1u : 0u;
-}
-
-// The searching tree's owner plays argmax(get_action_prob(s, temp = 0)) (src/coach.rs:356-372): the rule of one ply of one game, shared by
-// az_arena (tree g plays game g) and az_tournament (tree g of a model's batch plays game gi of the tournament through the model's table).
+// The searching tree's owner plays argmax(get_action_prob(s, temp = 0)) (src/coach.rs:356-372): the rule of one ply of one game, for az_arena
+// and az_tournament alike (tree g of a model's batch plays game gi through the model's table; in the arena gi == g).
 //   g     the tree of t that searched           gi    the game's row in ad (state, player, alive, results, moves, len)
 //   rid   the game's index in the tie-break stream (seed, rid, ply): the arena's global game index, the index inside the pair
 template <class G>
@@ -1569,44 +1558,34 @@ __device__ __forceinline__ void arena_move_body(const TreeDev& t, const TreeHead
     }
 }
 
-template <class G>
-__global__ __launch_bounds__(64) void k_arena_move(TreeDev t, ArenaDev ad, uint64_t seed) {
-    constexpr int GW = G::GROUP;
-    int tid = blockIdx.x * 64 + threadIdx.x;
-    int g = tid / GW, sub = tid % GW;
-    if (g >= t.G) return;
-    const TreeHead h = head_load(t, g);
-    if (!h.active) return;
-    arena_move_body<G>(t, h, ad, g, g, (uint64_t)(ad.first + g), sub, seed);
-}
-
-// ---- az_tournament: the games of all pairs in one ArenaDev (game p * n + g), one tree batch per MODEL ------------------------------------
-// Tree g of a model's batch plays the game its table names (TournamentTable, az_tree.h).  k_arena_sync generalised by the table: the tree
-// searches this ply when its game is running and its model is to move, and its root state is gathered from the per-game array.
-__global__ void k_tournament_sync(TreeDev t, ArenaDev ad, TournamentTable tb) {
+// ---- az_arena and az_tournament: the games of all pairs in one ArenaDev (game p * n + g; the arena is the one pair), one tree batch per MODEL
+// Tree g of a model's batch plays the game its table names (MatchTable, az_tree.h).  Which model moves: seat 0 moves when cur_player == +1;
+// the games of a pair below ad.half seat (first listed, second listed), the rest the other way round.  The tree searches this ply when its
+// game is running and its model is to move, and its root state is gathered from the per-game array.
+__global__ void k_match_sync(TreeDev t, ArenaDev ad, MatchTable tb) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= t.G) return;
     const uint32_t w = tb.game[g];
-    const int gi = (int)(w & TOURNAMENT_GAME_MASK);
+    const int gi = (int)(w & MATCH_GAME_MASK);
     if (gi >= ad.G) { t.head[g].head.active = 0u; return; }            // (a table entry outside the games: never built, never followed)
     const int second = (int)(w >> 31);                                  // 0: this model is the pair's first listed ("new"), 1: its second ("old")
-    const int first_model = gi % tb.n < ad.half ? 0 : 1;                // the seating uses the index inside the pair, as az_arena's global index
+    const int first_model = ad.first + gi % tb.n < ad.half ? 0 : 1;     // the seating uses the arena's global index, the index inside the pair
     const int mover = ad.player[gi] == 1 ? first_model : 1 - first_model;
     t.head[g].head.active = (ad.alive[gi] != 0 && mover == second) ? 1u : 0u;
     tb.roots[g] = ad.state[gi];
 }
 
 template <class G>
-__global__ __launch_bounds__(64) void k_tournament_move(TreeDev t, ArenaDev ad, TournamentTable tb, uint64_t seed) {
+__global__ __launch_bounds__(64) void k_match_move(TreeDev t, ArenaDev ad, MatchTable tb, uint64_t seed) {
     constexpr int GW = G::GROUP;
     int tid = blockIdx.x * 64 + threadIdx.x;
     int g = tid / GW, sub = tid % GW;
     if (g >= t.G) return;
     const TreeHead h = head_load(t, g);
     if (!h.active) return;
-    const int gi = (int)(tb.game[g] & TOURNAMENT_GAME_MASK);
+    const int gi = (int)(tb.game[g] & MATCH_GAME_MASK);
     if (gi >= ad.G) return;
-    arena_move_body<G>(t, h, ad, g, gi, (uint64_t)(gi % tb.n), sub, seed);
+    arena_move_body<G>(t, h, ad, g, gi, (uint64_t)(ad.first + gi % tb.n), sub, seed);
 }
 
 __global__ void k_sync_active(TreeDev t, GamesDev gd) {
@@ -1778,17 +1757,11 @@ static_assert(OPENING_E_NONE == E_NONE && OPENING_E_PLUS1 == E_PLUS1, "az_openin
 void launch_arena_openings(int game, const ArenaDev& ad, const ArenaOpenings& op, hipStream_t s) {
     AZ_FOR_GAME(game, hipLaunchKernelGGL(k_arena_openings<TG>, dim3((ad.G + 255) / 256), dim3(256), 0, s, ad, op));
 }
-void launch_arena_sync(const TreeDev& t_new, const TreeDev& t_old, const ArenaDev& ad, hipStream_t s) {
-    hipLaunchKernelGGL(k_arena_sync, dim3((ad.G + 255) / 256), dim3(256), 0, s, t_new, t_old, ad);
+void launch_match_sync(const TreeDev& t, const ArenaDev& ad, const MatchTable& tb, hipStream_t s) {
+    hipLaunchKernelGGL(k_match_sync, dim3((t.G + 255) / 256), dim3(256), 0, s, t, ad, tb);
 }
-void launch_arena_move(const TreeDev& t, const ArenaDev& ad, uint64_t seed, hipStream_t s) {
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_arena_move<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, ad, seed));
-}
-void launch_tournament_sync(const TreeDev& t, const ArenaDev& ad, const TournamentTable& tb, hipStream_t s) {
-    hipLaunchKernelGGL(k_tournament_sync, dim3((t.G + 255) / 256), dim3(256), 0, s, t, ad, tb);
-}
-void launch_tournament_move(const TreeDev& t, const ArenaDev& ad, const TournamentTable& tb, uint64_t seed, hipStream_t s) {
-    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_tournament_move<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, ad, tb, seed));
+void launch_match_move(const TreeDev& t, const ArenaDev& ad, const MatchTable& tb, uint64_t seed, hipStream_t s) {
+    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_match_move<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, ad, tb, seed));
 }
 // episodes of [lo, hi) that have already finished (g_len is set when an episode ends): a session's chunk starts its count from here
 __global__ void k_count_done(const int32_t* __restrict__ g_len, int lo, int hi, uint32_t* __restrict__ counter) {

@@ -30,7 +30,8 @@
  *     allreduce_wld) blocks until every rank of the communicator has called it, so the ranks of an in-process
  *     communicator (az_comm_local_id) are driven by one host thread each; a rank that never arrives is waited for
  *     (there is no timeout, as with RCCL).
- *     az_arena overlaps its two models' searches on two HIP streams; streams share the device's few hardware queues, so a
+ *     az_arena overlaps its two models' searches on two HIP streams (the engine's own and a side stream that the engine creates
+ *     at the first such call, shares with az_tournament and keeps until az_destroy); streams share the device's few hardware queues, so a
  *     process that keeps many other streams alive can make the two share one (measured: 2755 -> 1860 games/s with one extra
  *     idle stream).
  *   - Game state: Connect Four as two 7x6 bitboards in canonical form

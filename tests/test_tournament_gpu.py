@@ -221,6 +221,39 @@ def test_purity(hash_engine):
     fg.assert_same_outputs(fg.other_entry_points(e), before)
 
 
+def test_arena_tournament_arena_share_streams_and_trees(hash_engine):
+    """az_arena with eval logs, az_tournament of three models, the same az_arena again: the order in which the two entry points reuse the
+    engine's side streams, workspaces and leased tree arenas.  The two arenas agree in every output, eval logs included; the tournament in
+    between leaves no eval log.  (One launch per simulation step: the path that writes the log rows.)"""
+    e = hash_engine
+    n, sims, cap = 16, 25, 21 * 26 + 8
+    e.set_arena_openings(4)
+    e.set_option("fused_search", 0)
+
+    def arena():
+        out = list(e.arena(n, sims, new_model_id=HASH_IDS[0], old_model_id=HASH_IDS[1], seed=15, record_evals=cap))
+        out += list(e.arena_get_moves(n)) + list(e.arena_get_openings(n))
+        for which in (0, 1):
+            cnt, states, pis, vs = e.arena_get_evals(which, n, cap)
+            assert 0 < cnt.min() and cnt.max() <= cap
+            live = np.arange(cap)[None, :] < cnt[:, None]                # rows behind a game's count are never written
+            out += [cnt, states[live], pis[live], vs[live]]
+        return out
+    try:
+        first = arena()
+        got = tournament(e, HASH_IDS, 18, sims, seed=13)
+        with pytest.raises(Exception):
+            e.arena_get_evals(0, 54, cap)
+        second = arena()
+    finally:
+        e.set_option("fused_search", 1)
+        e.set_arena_openings(0)
+    assert len(got["results"]) == 54
+    assert len(first) == len(second) == 15
+    for a, b in zip(first, second):
+        assert a.shape == b.shape and np.array_equal(a, b)
+
+
 def test_refusals(hash_engine, engine_mod):
     """Every refusal: AZ_ERR_BAD_ARGUMENT, the sentinel-filled outputs untouched, the previous move record still served."""
     e = hash_engine

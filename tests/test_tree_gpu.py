@@ -340,6 +340,60 @@ def test_arena_matches_play_games(engine, oracle, engine_mod, num, sims):
     assert wld.tolist() == owld.tolist() and int(wld.sum()) == 2 * (num // 2)
 
 
+def _assert_moves_lead_to_results(oracle, glen, gmoves, res):
+    """The move record, played move by move under the oracle's rules, ends each game exactly at its recorded result."""
+    for g in range(len(res)):
+        s, player = (0, 0), 1
+        for k in range(int(glen[g])):
+            assert oracle.c4_ended(*s) == 0.0 and (oracle.c4_valid_mask(*s) >> int(gmoves[g, k])) & 1, (g, k)
+            s = oracle.c4_play(s[0], s[1], int(gmoves[g, k]))
+            player = -player
+        e = oracle.c4_ended(*s)
+        assert e != 0.0 and int(res[g]) == (-player if e == -1.0 else (player if e == 1.0 else 0)), g
+
+
+@pytest.mark.parametrize("sims,threads", [(25, 1), (26, 2)])
+def test_arena_same_model_on_both_seats(engine, oracle, engine_mod, sims, threads):
+    """new_model_id == old_model_id: both seats' trees search with ONE model (one stream, no fork), game for game the oracle's arena
+    with equal ids.  Salt 13 is one for which the twelve games are not all alike (the tie-break stream alone tells them apart).
+    Two simulations in flight need an even num_sims (src/async_mcts.rs:192): 26 there."""
+    engine.net_set_kind(35, engine_mod.NET_HASH, 13 - 35 * MODEL_SALT)          # oracle model id 0, salt 13
+    wld, results = engine.arena(12, sims, new_model_id=35, old_model_id=35, seed=13, num_sim_threads=threads)
+    glen, gmoves = engine.arena_get_moves(12)
+    owld, oresults, _ = oracle.arena_ex(12, sims, net_kind=oracle.NET_HASH, salt=13, seed=13, new_model_id=0, old_model_id=0, threads=8,
+                                        sim_threads=threads)
+    if threads == 1:
+        owld1, oresults1 = oracle.arena(12, sims, net_kind=oracle.NET_HASH, salt=13, seed=13, new_model_id=0, old_model_id=0, threads=8)
+        assert np.array_equal(oresults1, oresults) and owld1.tolist() == owld.tolist()
+    assert len(set(oresults.tolist())) > 1 and len({tuple(m) for m in gmoves.tolist()}) > 1
+    assert np.array_equal(results, oresults)
+    assert wld.tolist() == owld.tolist() and int(wld.sum()) == 12
+    _assert_moves_lead_to_results(oracle, glen, gmoves, results)
+
+
+def test_arena_odd_shards_through_the_table(engine, oracle, engine_mod):
+    """A 10-game arena (half = 5) in shards of 3, 3 and 4 games, two simulations in flight: the smallest case where a shard's size is odd,
+    a shard straddles half, and the game's index in the seating and the tie-break stream (first + index in the shard) is not its row.
+    Salt 31 is one for which both seatings see both results.  Every game of every shard against the oracle's shard; the tallies add up to
+    the unsharded call's."""
+    engine.net_set_kind(53, engine_mod.NET_HASH, 31 - 53 * MODEL_SALT)
+    engine.net_set_kind(52, engine_mod.NET_HASH, 31 + MODEL_SALT - 52 * MODEL_SALT)
+    wld, res = engine.arena(10, 26, new_model_id=53, old_model_id=52, seed=9, num_sim_threads=2)
+    tot = np.zeros(3, np.uint64)
+    parts = []
+    for lo, hi in ((0, 3), (3, 6), (6, 10)):
+        w, r = engine.arena(hi - lo, 26, new_model_id=53, old_model_id=52, seed=9, first_game=lo, total_games=10, num_sim_threads=2)
+        glen, gmoves = engine.arena_get_moves(hi - lo)
+        ow, ores, _ = oracle.arena_ex(10, 26, first_game=lo, n_games=hi - lo, net_kind=oracle.NET_HASH, salt=31, seed=9, new_model_id=0,
+                                      old_model_id=1, threads=8, sim_threads=2)
+        assert np.array_equal(r, ores) and w.tolist() == ow.tolist(), lo
+        _assert_moves_lead_to_results(oracle, glen, gmoves, r)
+        tot += w
+        parts.append(r)
+    assert np.array_equal(np.concatenate(parts), res) and tot.tolist() == wld.tolist() and int(wld.sum()) == 10
+    assert len(set(res.tolist())) > 1
+
+
 def test_arena_golden(engine, engine_mod):
     import json, os
     g = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "arena.json")))
