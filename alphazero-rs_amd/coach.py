@@ -82,6 +82,12 @@ class Coach:
         # unless it is the canonical one; meant to go with eval_mirror, which evaluates on that orientation.  False (the default): the
         # engine is never asked
         self.merge_positions, self.merge_canonical = False, False
+        # merge_weighted (requires merge_positions): the merge's multiplicities are kept, shuffled with their tuples, and NNet::train draws
+        # every batch row in proportion to them (Engine.train_samples, from the merged STATES: no feature planes are made) -- the raw
+        # window's distribution at the merged set's size and step count; under merge_canonical rows are mirrored at random, so the net
+        # sees both orientations again.  The report gains samples_weight, the sum of the multiplicities (= samples_raw).  Files on disk
+        # stay raw.  False (the default): the counts are dropped and az_net_train runs as before
+        self.merge_weighted = False
         # The optimiser rules of NNet::train (Engine.set_train_optim): decoupled weight decay, gradient-norm clipping, warm-up and decay of
         # the learning rate (lr_decay 0 none / 1 cosine / 2 linear, over the call's own steps) and an averaged shadow of the weights, set
         # before the iteration's one az_net_train and cleared behind it.  With ema_decay > 0 the candidate -- what the arena gates, what
@@ -236,23 +242,40 @@ class Coach:
             assert allv.shape[0] > 0                                    # :305
             samples_raw = int(allv.shape[0])
             t_merge = None
+            if self.merge_weighted and not self.merge_positions:
+                raise ValueError("merge_weighted requires merge_positions")
+            weighted = self.merge_weighted
+            on_engine = weighted and self.trainer is None               # states in, states out: no planes
+            mult = None
             if self.merge_positions:                                    # one tuple per distinct position of the window
                 t0 = time.perf_counter()
-                merged = self.engine.merge_samples(allp, allv, boards=allb, canonical=self.merge_canonical, want_boards=True)
-                allb, allp, allv = merged["boards"], merged["pis"], merged["zs"]
+                merged = self.engine.merge_samples(allp, allv, boards=allb, canonical=self.merge_canonical, want_boards=not on_engine)
+                allb, allp, allv = merged["states"] if on_engine else merged["boards"], merged["pis"], merged["zs"]
+                if weighted:
+                    mult = np.asarray(merged["counts"], np.uint32)
                 t_merge = time.perf_counter() - t0
             perm = shuffle_permutation(allv.shape[0], seed, iteration)  # :296-297 shuffle
             allb, allp, allv = allb[perm], allp[perm], allv[perm]
+            if weighted:
+                mult = mult[perm]                                       # the multiplicities travel with their tuples
+                samples_weight = int(mult.sum(dtype=np.uint64))
             t0 = time.perf_counter()
             if self.trainer is None:                                    # :329 -> NNet::train(samples, id, id + 1)
                 self.engine.set_option("train_seed", seed + iteration)
                 with self._train_optim():
-                    losses = self.engine.train(model_id, model_id + 1, allb, allp, allv)
+                    if weighted:
+                        losses = self.engine.train_samples(model_id, model_id + 1, allp, allv, states=allb, weights=mult,
+                                                           mirror=self.merge_canonical)
+                    else:
+                        losses = self.engine.train(model_id, model_id + 1, allb, allp, allv)
                 if self.ema_decay > 0:                                  # the candidate is the averaged model
                     self.engine.train_ema(model_id + 1)
             else:
                 prev = self.engine.net_get_params(model_id)
-                new = self.trainer.train(prev, allb, allp, allv, seed=seed + iteration)
+                if weighted:
+                    new = self.trainer.train(prev, allb, allp, allv, seed=seed + iteration, weights=mult, mirror=self.merge_canonical)
+                else:
+                    new = self.trainer.train(prev, allb, allp, allv, seed=seed + iteration)
                 self.engine.net_set_params(model_id + 1, new)
                 losses = list(self.trainer.history)
             t_train = time.perf_counter() - t0
@@ -317,6 +340,8 @@ class Coach:
                            "seconds": {"selfplay": t_play, "train": t_train, "arena": t_arena}})
             if t_merge is not None:
                 report[-1]["seconds"]["merge"] = t_merge
+            if weighted:
+                report[-1]["samples_weight"] = samples_weight
             if quality is not None:
                 report[-1]["quality"] = quality
                 report[-1]["seconds"]["quality"] = t_quality

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "az_combine.h"
+#include "az_draw.h"
 #include "az_local_comm.h"
 #include "az_merge.h"
 #include "az_net.h"
@@ -1641,6 +1642,141 @@ az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id
         }
         HIPCHK(hipStreamSynchronize(e->stream));
     } catch (const HipFail& f) { e->train_open = false; return fail_hip(e, f); }
+    return az_net_train_end(e, model_id);
+}
+
+// ---- NNet::train from an az_samples, rows drawn in proportion to their multiplicities (csrc/az_draw.h) ---------------
+}  // extern "C"
+
+namespace {
+
+// The weights on the device and their prefix sum: Q == nullptr (weights NULL) means all ones and W = n.
+struct DrawTable {
+    const uint64_t* Q = nullptr;
+    uint64_t W = 0;
+};
+DrawTable draw_table(az_engine* e, DeviceMem& mem, int64_t n, const uint32_t* weights) {
+    DrawTable d;
+    if (!weights) { d.W = (uint64_t)n; return d; }
+    uint32_t* d_w = mem.alloc<uint32_t>((size_t)n);
+    uint64_t* d_q = mem.alloc<uint64_t>((size_t)n);
+    uint64_t* d_bsum = mem.alloc<uint64_t>(draw_scan_blocks(n) + 1);
+    uint64_t* d_total = d_bsum + draw_scan_blocks(n);
+    HIPCHK(hipMemcpyAsync(d_w, weights, (size_t)n * sizeof(uint32_t), hipMemcpyDefault, e->stream));
+    launch_draw_scan(d_w, n, d_q, d_bsum, d_total, e->stream);
+    HIPCHK(hipMemcpyAsync(&d.W, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
+    d.Q = d_q;
+    return d;
+}
+const char* draw_arg_error(const az_engine* e, int64_t n, int32_t flags) {
+    if (flags & ~(AZ_TRAIN_EPOCH_BY_WEIGHT | AZ_TRAIN_MIRROR)) return "unknown flag bits";
+    if (n < 1 || n > DRAW_MAX_TUPLES) return "1 .. 2^31 - 1 tuples";
+    if (e->train_open) return "a training session is open";
+    if (e->sp_session) return "a self-play session is open";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+az_status az_net_train_draw(az_engine* e, int64_t n, const uint32_t* weights, int32_t flags, uint64_t t0, int64_t steps, int64_t* idx_out,
+                            uint8_t* mirror_out) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (const char* why = draw_arg_error(e, n, flags)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_net_train_draw: ") + why).c_str());
+    if (!idx_out || steps < 1) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_draw: idx_out and steps >= 1 are required");
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        DeviceMem mem;
+        const DrawTable d = draw_table(e, mem, n, weights);
+        if (d.W == 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_draw: the weights sum to 0");
+        const int b = e->train_batch;
+        const size_t rows = (size_t)steps * (size_t)b;
+        int64_t* d_idx = mem.alloc<int64_t>(rows);
+        uint8_t* d_mir = mem.alloc<uint8_t>(rows);
+        launch_draw_rows(d.Q, n, d.W, e->train_seed, t0, steps, b, (flags & AZ_TRAIN_MIRROR) != 0, d_idx, d_mir, e->stream);
+        HIPCHK(hipMemcpyAsync(idx_out, d_idx, rows * sizeof(int64_t), hipMemcpyDefault, e->stream));
+        if (mirror_out) HIPCHK(hipMemcpyAsync(mirror_out, d_mir, rows, hipMemcpyDefault, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipGetLastError());
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+az_status az_net_train_samples(az_engine* e, int32_t previous_model_id, int32_t model_id, const az_samples* s, const uint32_t* weights,
+                               int32_t flags) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!s) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_samples: the samples are required");
+    const int64_t n = s->count;
+    if (const char* why = draw_arg_error(e, n, flags)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_net_train_samples: ") + why).c_str());
+    if (!s->pis || !s->zs || (!s->states && !s->boards))
+        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_samples: the samples need pis, zs and states or boards");
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        DeviceMem mem;
+        // the resident set: states (16 bytes; or the planes the caller holds, 336) + pis + zs (+ weights + Q) per tuple
+        TrainSamples src{};
+        if (s->states) {
+            ulonglong2* d_states = mem.alloc<ulonglong2>((size_t)n);
+            uint32_t* d_bad = mem.alloc<uint32_t>(1);
+            HIPCHK(hipMemcpyAsync(d_states, s->states, (size_t)n * 16, hipMemcpyDefault, e->stream));
+            HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), e->stream));
+            launch_draw_check_states(d_states, n, d_bad, e->stream);
+            uint32_t bad = 0;
+            HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipStreamSynchronize(e->stream));
+            if (bad) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_samples: a state with overlapping stones or bits outside the 7x6 board");
+            src.states = d_states;
+        } else {
+            float* d_boards = mem.alloc<float>((size_t)n * 84);
+            HIPCHK(hipMemcpyAsync(d_boards, s->boards, (size_t)n * 84 * sizeof(float), hipMemcpyDefault, e->stream));
+            src.boards = d_boards;
+        }
+        const DrawTable d = draw_table(e, mem, n, weights);
+        if (d.W == 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_samples: the weights sum to 0");
+        float* d_pis = mem.alloc<float>((size_t)n * 7);
+        float* d_vs = mem.alloc<float>((size_t)n);
+        HIPCHK(hipMemcpyAsync(d_pis, s->pis, (size_t)n * 7 * sizeof(float), hipMemcpyDefault, e->stream));
+        HIPCHK(hipMemcpyAsync(d_vs, s->zs, (size_t)n * sizeof(float), hipMemcpyDefault, e->stream));
+        src.pis = d_pis;
+        src.vs = d_vs;
+        const int b = e->train_batch;
+        const int64_t steps = draw_epoch_steps((flags & AZ_TRAIN_EPOCH_BY_WEIGHT) ? d.W : (uint64_t)n, b);
+        const bool mirror = (flags & AZ_TRAIN_MIRROR) != 0;
+        int64_t* d_idx = mem.alloc<int64_t>((size_t)steps * b);
+        uint8_t* d_mir = mirror ? mem.alloc<uint8_t>((size_t)steps * b) : nullptr;
+        HIPCHK(hipStreamSynchronize(e->stream));
+        // every refusal is behind us: from here on it is az_net_train with another index table and another gather
+        az_status st = az_net_train_begin(e, previous_model_id);
+        if (st) return st;
+        try {
+            Trainer* t = e->trainer;
+            e->train_history.clear();
+            if (!trainer_set_lr_table(t, e->hyper, (int64_t)e->train_epochs * steps, e->stream)) {
+                e->train_open = false;
+                return fail(e, AZ_ERR_HIP, "trainer_set_lr_table failed");
+            }
+            uint64_t gstep = 0;
+            for (int epoch = 0; epoch < e->train_epochs; ++epoch) {
+                launch_draw_rows(d.Q, n, d.W, e->train_seed, gstep, steps, b, mirror, d_idx, d_mir, e->stream);
+                if (!trainer_run_epoch_samples(t, e->hyper, src, d_idx, d_mir, steps, b, mix64(e->train_seed ^ 0xD6E8FEB86659FD93ull), gstep,
+                                               e->stream)) {
+                    e->train_open = false;
+                    return fail(e, AZ_ERR_HIP, "trainer_run_epoch_samples failed");
+                }
+                gstep += (uint64_t)steps;
+                double l[2];
+                if (!trainer_read_losses(t, l, true, e->stream)) { e->train_open = false; return fail(e, AZ_ERR_HIP, "trainer_read_losses failed"); }
+                e->train_history.push_back((float)(l[0] / (double)steps));
+                e->train_history.push_back((float)(l[1] / (double)steps));
+            }
+            HIPCHK(hipStreamSynchronize(e->stream));
+        } catch (const HipFail& f) { e->train_open = false; return fail_hip(e, f); }
+    } catch (const HipFail& f) { return fail_hip(e, f); }
     return az_net_train_end(e, model_id);
 }
 

@@ -68,6 +68,17 @@ float* trainer_batch_vs(Trainer* t);
 // The launch sequence of a step is captured in a hipGraph and replayed.  Synchronises the stream.
 bool trainer_run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards, const float* all_pis, const float* all_vs,
                        const int64_t* d_idx, int64_t steps, int b, uint64_t seed_key, uint64_t gstep0, hipStream_t s);
+// The same epoch for az_net_train_samples (az_draw.h): the rows come from `samples` -- feature planes, or 16-byte states whose planes
+// are built per batch on the device -- and row k of the epoch is gathered mirrored where d_mir[k] != 0 (d_mir may be nullptr: none).
+// Only the gather launch differs from trainer_run_epoch; an unmirrored row taken from boards gives the same floats.
+struct TrainSamples {
+    const float* boards;          // [n][84], or nullptr: states
+    const ulonglong2* states;     // [n] (mine, theirs) bitboards of az_game.h
+    const float* pis;             // [n][7]
+    const float* vs;              // [n]
+};
+bool trainer_run_epoch_samples(Trainer* t, const TrainHyper& h, const TrainSamples& samples, const int64_t* d_idx, const uint8_t* d_mir,
+                               int64_t steps, int b, uint64_t seed_key, uint64_t gstep0, hipStream_t s);
 void trainer_set_graph(Trainer* t, bool on);      // A/B switch: replay a captured graph (default) or launch directly
 void trainer_set_fwd_dma(Trainer* t, bool on);    // 1 (default): forward GEMMs fed by LDS-DMA (k_gemm_f32_dma); 0: register-staged k_gemm_f32
 void trainer_set_fork(Trainer* t, bool on);       // true: a step's wgrad chains on a second stream branch, joined before Adam (default false: no gain)

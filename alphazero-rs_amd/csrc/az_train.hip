@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "az_common.h"
+#include "az_mirror.h"
 #include "az_net.h"
 #include "az_optim.h"
 
@@ -1093,6 +1094,40 @@ __global__ void k_gather_col1(const float* __restrict__ all_boards, const float*
         if (k < 18) {
             const int tap = k >> 1, ci = k & 1, iy = y + tap / 3 - 1, ix = x + tap % 3 - 1;
             if (iy >= 0 && iy < 6 && ix >= 0 && ix < 7) v = all_boards[(size_t)idx[off + s] * 84 + ci * 42 + iy * 7 + ix];
+        }
+        col[i] = v;
+    }
+}
+
+// k_gather_col1 for az_net_train_samples (az_draw.h): the row's planes come from src.boards, or from the 16-byte state src.states[row]
+// (bit c * 7 + (5 - r) of word `plane` is cell (r, c): states_to_boards), and a row whose mirror bit is set is gathered mirrored -- column
+// c of both planes from column 6 - c, pi reversed, z as it is.  An unmirrored row taken from boards gets the floats k_gather_col1 writes.
+__device__ __forceinline__ float sample_cell(const TrainSamples& src, int64_t row, bool mirrored, int ci, int y, int x) {
+    const int xs = mirrored ? mirror_action_index(x) : x;
+    if (src.boards) return src.boards[(size_t)row * 84 + ci * 42 + y * 7 + xs];
+    const ulonglong2 st = src.states[row];
+    return (((ci ? st.y : st.x) >> (xs * 7 + (5 - y))) & 1ull) ? 1.0f : 0.0f;
+}
+__global__ void k_gather_col1_samples(const TrainSamples src, const int64_t* __restrict__ idx, const uint8_t* __restrict__ mir, int b,
+                                      float* __restrict__ boards, float* __restrict__ pis, float* __restrict__ vs, float* __restrict__ col,
+                                      const StepState* __restrict__ st) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t off = st->idx_offset;
+    if (i < b * 92) {
+        const int j = i / 92, f = i % 92;
+        const int64_t row = idx[off + j];
+        const bool m = mir && mir[off + j] != 0;
+        if (f < 84) boards[(size_t)j * 84 + f] = sample_cell(src, row, m, f / 42, (f % 42) / 7, f % 7);
+        else if (f < 91) pis[(size_t)j * 7 + (f - 84)] = src.pis[(size_t)row * 7 + (m ? mirror_action_index(f - 84) : f - 84)];
+        else vs[j] = src.vs[row];
+    }
+    if (i < b * 42 * 20) {
+        const int k = i % 20, r = i / 20;
+        const int s = r / 42, p = r % 42, y = p / 7, x = p % 7;
+        float v = 0.0f;
+        if (k < 18) {
+            const int tap = k >> 1, ci = k & 1, iy = y + tap / 3 - 1, ix = x + tap % 3 - 1;
+            if (iy >= 0 && iy < 6 && ix >= 0 && ix < 7) v = sample_cell(src, idx[off + s], mir && mir[off + s] != 0, ci, iy, ix);
         }
         col[i] = v;
     }
@@ -2269,8 +2304,11 @@ bool trainer_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
     return hipGetLastError() == hipSuccess;
 }
 
-bool trainer_run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards, const float* all_pis, const float* all_vs,
-                       const int64_t* d_idx, int64_t steps, int b, uint64_t seed_key, uint64_t gstep0, hipStream_t s) {
+// samples == nullptr: the rows of (all_boards, all_pis, all_vs) through k_gather_col1; else the rows of *samples through
+// k_gather_col1_samples with the mirror bits d_mir.  The gather is the one launch of a step that differs.
+static bool run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards, const float* all_pis, const float* all_vs,
+                      const TrainSamples* samples, const int64_t* d_idx, const uint8_t* d_mir, int64_t steps, int b, uint64_t seed_key,
+                      uint64_t gstep0, hipStream_t s) {
     if (!t || b <= 1 || b > TRAIN_MAX_BATCH || steps <= 0) return false;
     const bool sched = t->optim.on();
     if (sched && (int64_t)t->host_lr_table.size() < (int64_t)gstep0 + steps) return false;      // trainer_set_lr_table covers the whole call
@@ -2280,8 +2318,12 @@ bool trainer_run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards,
     auto one_step = [&]() {
         if (sched) hipLaunchKernelGGL(k_step_advance_sched, dim3(1), dim3(64), 0, s, t->step_state, t->counters, b, (const float*)t->lr_table);
         else hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(64), 0, s, t->step_state, t->counters, b);
-        hipLaunchKernelGGL(k_gather_col1, dim3((b * 42 * 20 + 255) / 256), dim3(256), 0, s, all_boards, all_pis, all_vs, d_idx, b, t->bboards,
-                           t->bpis, t->bvs, t->col[0], (const StepState*)t->step_state);
+        if (samples)
+            hipLaunchKernelGGL(k_gather_col1_samples, dim3((b * 42 * 20 + 255) / 256), dim3(256), 0, s, *samples, d_idx, d_mir, b, t->bboards,
+                               t->bpis, t->bvs, t->col[0], (const StepState*)t->step_state);
+        else
+            hipLaunchKernelGGL(k_gather_col1, dim3((b * 42 * 20 + 255) / 256), dim3(256), 0, s, all_boards, all_pis, all_vs, d_idx, b, t->bboards,
+                               t->bpis, t->bvs, t->col[0], (const StepState*)t->step_state);
         enqueue_step(t, h, t->bboards, t->bpis, t->bvs, b, true, s, true);
     };
     // the step's ~60 launches are captured once and replayed: the epoch is launch-bound otherwise
@@ -2306,6 +2348,16 @@ bool trainer_run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards,
     if (sched) t->last_lr = t->host_lr_table[(size_t)((int64_t)gstep0 + steps - 1)];
     for (int64_t i = 0; i < steps; ++i) { t->pow1 *= (double)h.beta1; t->pow2 *= (double)h.beta2; }
     return ok;
+}
+
+bool trainer_run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards, const float* all_pis, const float* all_vs,
+                       const int64_t* d_idx, int64_t steps, int b, uint64_t seed_key, uint64_t gstep0, hipStream_t s) {
+    return run_epoch(t, h, all_boards, all_pis, all_vs, nullptr, d_idx, nullptr, steps, b, seed_key, gstep0, s);
+}
+bool trainer_run_epoch_samples(Trainer* t, const TrainHyper& h, const TrainSamples& samples, const int64_t* d_idx, const uint8_t* d_mir,
+                               int64_t steps, int b, uint64_t seed_key, uint64_t gstep0, hipStream_t s) {
+    if (!samples.pis || !samples.vs || (!samples.boards && !samples.states)) return false;
+    return run_epoch(t, h, nullptr, nullptr, nullptr, &samples, d_idx, d_mir, steps, b, seed_key, gstep0, s);
 }
 
 void trainer_set_graph(Trainer* t, bool on) { if (t) t->use_graph = on; }

@@ -36,6 +36,7 @@ SOLVE_ILLEGAL, SOLVE_UNKNOWN = -128, 127                         # AZ_SOLVE_ILLE
 MQ_SKIPPED, MQ_KEPT, MQ_WIN_TO_DRAW, MQ_WIN_TO_LOSS, MQ_DRAW_TO_LOSS, MQ_UNKNOWN = range(6)      # AZ_MQ_*: classes of az_move_quality
 MQ_NAMES = ("skipped", "kept", "win_to_draw", "win_to_loss", "draw_to_loss", "unknown")
 MERGE_CANONICAL = 1                                              # AZ_MERGE_CANONICAL, flags bit 0 of az_samples_merge
+TRAIN_EPOCH_BY_WEIGHT, TRAIN_MIRROR = 1, 2                       # AZ_TRAIN_*: flags of az_net_train_samples / az_net_train_draw
 
 
 class AzError(RuntimeError):
@@ -87,7 +88,8 @@ EXPORTS = [
     "az_net_set_class", "az_net_get_class",
     "az_net_init_random", "az_net_load", "az_net_save", "az_net_param_count", "az_net_set_params",
     "az_net_get_params", "az_net_predict", "az_net_predict_states", "az_net_train", "az_net_train_history",
-    "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_net_train_ema", "az_net_train_step_info", "az_tree_create",
+    "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_net_train_ema", "az_net_train_step_info",
+    "az_net_train_samples", "az_net_train_draw", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
     "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_tree_get_selected", "az_gumbel_values", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
@@ -130,6 +132,8 @@ def load_library(path=LIB_PATH):
         "az_net_train_end": (i32, [vp, i32]),
         "az_net_train_ema": (i32, [vp, i32]),
         "az_net_train_step_info": (i32, [vp, vp]),
+        "az_net_train_samples": (i32, [vp, i32, i32, C.POINTER(az_samples), vp, i32]),
+        "az_net_train_draw": (i32, [vp, i64, vp, i32, u64, i64, vp, vp]),
         "az_tree_create": (i32, [vp, i32, u64, i32, i32, i32, i32, i32, C.POINTER(vp)]),
         "az_tree_destroy": (None, [vp]),
         "az_tree_reset": (i32, [vp, vp]),
@@ -294,6 +298,46 @@ class Engine:
         v = np.ascontiguousarray(vs, dtype=np.float32)
         self._check(self._lib.az_net_train(self._h, prev_id, model_id, _ptr(b), _ptr(p), _ptr(v), v.size))
         return self.train_history()
+
+    @staticmethod
+    def _train_flags(epoch_by_weight, mirror):
+        return (TRAIN_EPOCH_BY_WEIGHT if epoch_by_weight else 0) | (TRAIN_MIRROR if mirror else 0)
+
+    def train_samples(self, prev_id, model_id, pis, zs, *, states=None, boards=None, weights=None, epoch_by_weight=False, mirror=False):
+        """az_net_train_samples: NNet::train on n tuples whose batch rows are drawn in proportion to `weights` (u32 [n], None = all
+        ones: az_net_train's draw), mirrored at random with `mirror` (include/az_engine.h).  The position comes from `states` [n,2]
+        -- the planes are then built per batch on the device -- or from `boards` [n,2,6,7] when states is None.  Inputs may be numpy
+        arrays or torch tensors (host or device).  epoch_by_weight: an epoch has sum(weights) / batch steps, not n / batch."""
+        if (states is None) == (boards is None):
+            raise ValueError("train_samples takes states or boards, not both")
+        n = int(len(zs))
+        if not hasattr(pis, "data_ptr"):
+            pis = np.ascontiguousarray(pis, dtype=np.float32).reshape(n, ACTIONS)
+        if not hasattr(zs, "data_ptr"):
+            zs = np.ascontiguousarray(zs, dtype=np.float32).reshape(n)
+        if states is not None and not hasattr(states, "data_ptr"):
+            states = np.ascontiguousarray(states, dtype=np.uint64).reshape(n, 2)
+        if boards is not None and not hasattr(boards, "data_ptr"):
+            boards = np.ascontiguousarray(boards, dtype=np.float32).reshape(n, 2, 6, 7)
+        if weights is not None and not hasattr(weights, "data_ptr"):
+            weights = np.ascontiguousarray(weights, dtype=np.uint32).reshape(n)
+        src = az_samples(n, n, _as_ptr(states), _as_ptr(boards), _as_ptr(pis), _as_ptr(zs), None, None)
+        self._check(self._lib.az_net_train_samples(self._h, prev_id, model_id, C.byref(src), _as_ptr(weights),
+                                                   self._train_flags(epoch_by_weight, mirror)))
+        return self.train_history()
+
+    def train_draw(self, n, steps, *, weights=None, t0=0, batch, epoch_by_weight=False, mirror=False, out=None):
+        """az_net_train_draw: the tuples (and mirror bits) of the `steps` batches of global steps t0 .. t0 + steps that train_samples
+        would draw from n tuples with these weights, at the engine's current "train_seed" and "train_batch" -- `batch` must name
+        that value (it sizes the outputs).  Runs the device prefix sum and the draw kernel alone.  Returns (idx [steps*batch] int64,
+        mirror [steps*batch] uint8); out = (idx, mirror) writes into the caller's arrays or tensors (host or device) instead."""
+        if weights is not None and not hasattr(weights, "data_ptr"):
+            weights = np.ascontiguousarray(weights, dtype=np.uint32).reshape(int(n))
+        rows = int(steps) * int(batch)
+        idx, mir = out if out is not None else (np.full(max(rows, 0), -1, np.int64), np.full(max(rows, 0), 255, np.uint8))
+        self._check(self._lib.az_net_train_draw(self._h, int(n), _as_ptr(weights), self._train_flags(epoch_by_weight, mirror), int(t0),
+                                                int(steps), _as_ptr(idx), _as_ptr(mir)))
+        return idx, mir
 
     def train_history(self):
         """[(loss_pi, loss_v)] per epoch of the last train()."""

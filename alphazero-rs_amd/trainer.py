@@ -107,7 +107,10 @@ class Trainer:
         self.device = device or (torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
         self.history = []
 
-    def train(self, prev_params, boards, pis, vs, seed=0):
+    def train(self, prev_params, boards, pis, vs, seed=0, weights=None, mirror=False):
+        """weights (u32 [n], None = all ones) and mirror: the draw rule of az_net_train_samples (csrc/az_draw.h) through THIS trainer's
+        generator -- u = randint(0, W), the row is the first tuple whose inclusive prefix sum exceeds u, and with mirror every row is
+        flipped left-right (pi reversed) on a fair coin.  The same rule in distribution, not bit for bit."""
         torch.manual_seed(seed)                  # dropout masks (batches use their own generator below)
         net = PolicyValueNet(self.C, prev_params, self.device)
         net.train()
@@ -118,13 +121,28 @@ class Trainer:
         n = X.shape[0]
         gen = torch.Generator(device="cpu").manual_seed(seed)
         steps = max(1, n // self.batch_size)
+        prefix = W = None
+        if weights is not None:
+            prefix = torch.as_tensor(np.cumsum(np.asarray(weights, np.uint32).reshape(n).astype(np.int64)))
+            W = int(prefix[-1])
+            if W <= 0:
+                raise ValueError("the weights sum to 0")
         self.history = []
         for epoch in range(self.epochs):
             tot = [0.0, 0.0]
             for _ in range(steps):
-                idx = torch.randint(0, n, (self.batch_size,), generator=gen).to(self.device)   # :130 randint batches
-                logits, v = net(X[idx], self.dropout)
-                lp, lv = loss_fn(logits, v, P[idx], V[idx])
+                if prefix is None:
+                    idx = torch.randint(0, n, (self.batch_size,), generator=gen).to(self.device)   # :130 randint batches
+                else:
+                    u = torch.randint(0, W, (self.batch_size,), generator=gen)
+                    idx = torch.searchsorted(prefix, u, right=True).to(self.device)
+                xb, pb = X[idx], P[idx]
+                if mirror:
+                    m = (torch.randint(0, 2, (self.batch_size,), generator=gen) == 1).to(self.device)
+                    xb = torch.where(m[:, None, None, None], xb.flip(3), xb)
+                    pb = torch.where(m[:, None], pb.flip(1), pb)
+                logits, v = net(xb, self.dropout)
+                lp, lv = loss_fn(logits, v, pb, V[idx])
                 opt.zero_grad(set_to_none=True)
                 (lp + lv).backward()
                 opt.step()

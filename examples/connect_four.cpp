@@ -11,8 +11,9 @@
 //         of the recorded pi (Coach::forced_playouts_k / policy_prune)
 //         arena_openings = N (even, 2 .. 12, e.g. 6): paired openings in the gate -- arena game g and its seat-swapped twin start from the same
 //         N random quiet plies, every pair from others (Coach::arena_opening_plies)
-//         merge_positions = 1 or canonical: position averaging before training -- one tuple per distinct position of the window with the mean
-//         pi and the mean z of its copies; canonical also merges a position with its mirror image (Coach::merge_positions / merge_canonical)
+//         merge_positions = 1, canonical, weighted or canonical,weighted: position averaging before training -- one tuple per distinct position of the window with the mean
+//         pi and the mean z of its copies; canonical also merges a position with its mirror image (Coach::merge_positions / merge_canonical); weighted
+//         keeps the multiplicities and draws every training row in proportion to them, mirrored at random under canonical (Coach::merge_weighted)
 //         move_quality = STONES[,NODES] (e.g. 26): after every arena its games are replayed, the positions with at least STONES stones solved
 //         exactly (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach::solve_min_stones)
 //         --gumbel M[,CVISIT,CSCALE] (anywhere on the line, e.g. --gumbel 4 or --gumbel 4,50,1): Gumbel root search with sequential halving in
@@ -69,8 +70,9 @@ int main(int argc, char** argv) {
             if (c2 != std::string::npos) coach.gumbel_c_scale = std::atof(gumbel.c_str() + c2 + 1);
         }
         coach.arena_opening_plies = arena_openings;
-        coach.merge_canonical = merge == "canonical";
-        coach.merge_positions = coach.merge_canonical || std::strtol(merge.c_str(), nullptr, 10) != 0;
+        coach.merge_canonical = merge == "canonical" || merge == "canonical,weighted";
+        coach.merge_weighted = merge == "weighted" || merge == "canonical,weighted";
+        coach.merge_positions = coach.merge_canonical || coach.merge_weighted || std::strtol(merge.c_str(), nullptr, 10) != 0;
         coach.solve_min_stones = (size_t)std::strtoul(quality.c_str(), nullptr, 10);
         if (quality.find(',') != std::string::npos) coach.solve_max_nodes = (uint32_t)std::strtoul(quality.c_str() + quality.find(',') + 1, nullptr, 10);
         for (const auto& r : coach.learn(false, /*seed*/ 0)) {
@@ -78,6 +80,7 @@ int main(int argc, char** argv) {
                         r.pwins, r.draws, r.accepted ? "accepted" : "rejected", r.losses.empty() ? 0.f : r.losses[r.losses.size() - 2],
                         r.losses.empty() ? 0.f : r.losses.back());
             if (coach.merge_positions) std::printf("iteration %zu: merged from %zu raw samples\n", r.iteration, r.samples_raw);
+            if (coach.merge_weighted) std::printf("iteration %zu: rows drawn by multiplicity, total weight %zu\n", r.iteration, r.samples_weight);
         }
         return 0;
     } catch (const std::exception& ex) {

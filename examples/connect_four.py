@@ -35,7 +35,7 @@ def main():
     ap.add_argument("--clip-norm", type=float, default=0.0)          # global gradient-norm clipping, e.g. 1.0 (Coach.clip_norm)
     ap.add_argument("--lr-schedule", default=None, metavar="WARMUP,MODE,FLOOR")   # e.g. 100,cosine,0.1: linear warm-up over WARMUP steps, then cosine / linear / none down to FLOOR x lr over the call's steps (Coach.lr_warmup_steps / lr_decay / lr_floor)
     ap.add_argument("--ema", type=float, default=0.0)                # decay of the averaged weights, e.g. 0.999: the candidate is the averaged model (Coach.ema_decay)
-    ap.add_argument("--merge-positions", nargs="?", const="plain", default=None, choices=["plain", "canonical"])   # position averaging before training: one tuple per distinct position; =canonical also merges mirror images (Coach.merge_positions)
+    ap.add_argument("--merge-positions", nargs="?", const="plain", default=None, choices=["plain", "canonical", "weighted", "canonical,weighted"])   # position averaging before training: one tuple per distinct position; canonical also merges mirror images (Coach.merge_positions); weighted draws every training row in proportion to its multiplicity (Coach.merge_weighted)
     ap.add_argument("--move-quality", default=None, metavar="STONES[,NODES]")   # exact move-quality report of every arena: positions with at least STONES stones are solved (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach.solve_min_stones)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
     ap.add_argument("--eval-mirror", action="store_true")    # mirror-canonical leaf evaluation for the whole loop (Coach.eval_mirror)
@@ -83,7 +83,8 @@ def main():
         mode = parts[1] if len(parts) > 1 else "none"
         coach.lr_decay = {"none": 0, "cosine": 1, "linear": 2}[mode] if mode in ("none", "cosine", "linear") else int(mode)
         coach.lr_floor = float(parts[2]) if len(parts) > 2 else 0.0
-    coach.merge_positions, coach.merge_canonical = a.merge_positions is not None, a.merge_positions == "canonical"
+    modes = (a.merge_positions or "").split(",")
+    coach.merge_positions, coach.merge_canonical, coach.merge_weighted = a.merge_positions is not None, "canonical" in modes, "weighted" in modes
     if a.move_quality:
         stones, _, nodes = a.move_quality.partition(",")
         coach.solve_min_stones, coach.solve_max_nodes = int(stones), int(nodes) if nodes else 1 << 20

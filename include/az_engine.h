@@ -679,6 +679,38 @@ az_status az_selfplay_get_evals(az_engine* e, int32_t* rec_count, uint64_t* stat
 #define AZ_MERGE_CANONICAL 1   /* flags bit 0 */
 az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, az_samples* dst, uint32_t* counts);
 
+/* ---- NNet::train from merged positions: batch rows drawn in proportion to their multiplicities (no reference counterpart; csrc/az_draw.h,
+ * DESIGN.md section 8.2).  Strictly opt-in: az_net_train and every kernel it launches are untouched.  az_samples_merge gives one tuple per
+ * distinct position and `counts`; the cross-entropy of k copies against a policy is k times the cross-entropy of their mean pi plus a
+ * constant (likewise the squared error of z), and az_net_train draws every batch row with replacement, so drawing merged tuple i with
+ * probability counts[i] / sum(counts) IS the raw window's distribution -- at the merged set's size and step count.  The rule:
+ *   weights    u32 [n], host or device; NULL = all ones; a weight of 0 is legal (the tuple is never drawn).  Q[i] = weights[0] + .. +
+ *              weights[i] in u64 (a device prefix sum), W = Q[n-1]
+ *   steps      an epoch has max(1, S / "train_batch") steps, S = n; with AZ_TRAIN_EPOCH_BY_WEIGHT S = W (the raw window's step count)
+ *   row        row j of global step t (counted over the call's epochs): r = rng_draw("train_seed", t, j, RNG_BATCH), az_net_train's own
+ *              draw; u = (r * W) >> 64 of the 128-bit product; the row is tuple min{ i : Q[i] > u }.  With every weight 1 that is i = u,
+ *              az_net_train's row
+ *   mirror     with AZ_TRAIN_MIRROR the row is mirrored iff the top bit of rng_draw("train_seed", t, j, RNG_TRAIN_MIRROR = 9) is set:
+ *              column c of both planes comes from column 6 - c, pi is reversed, z stays (what a host needs behind AZ_MERGE_CANONICAL,
+ *              whose output holds one orientation of every position)
+ *   the rest   dropout masks, Adam's bias corrections, the learning-rate table, the averaged shadow and az_net_train_history are
+ *              az_net_train's, keyed by the same global step: with weights NULL and flags 0 the result is az_net_train's bit for bit
+ * az_net_train_samples reads s->count (n), s->pis, s->zs and s->states [n,2], or s->boards [n,2,6,7] when states is NULL; every array
+ * may be host or device memory.  From states the device holds 16 bytes per position and builds each batch's planes from the bits (bit
+ * c * 7 + (5 - r) of word p is cell (r, c) of plane p); about 60 bytes per tuple with weights, 368 by az_net_train's planes.
+ * az_net_train_draw runs the prefix sum and the draw alone, with the engine's current "train_seed" and "train_batch", for global steps
+ * t0 .. t0 + steps: idx_out [steps * batch] and mirror_out [steps * batch] (may be NULL; all 0 without AZ_TRAIN_MIRROR), host or device.
+ * It touches no model, no trainer state and no az_stats counter but device_ms (the kind of entry az_root_noise_eta is).
+ * Refused with AZ_ERR_BAD_ARGUMENT and nothing written: n < 1 or n > 2^31 - 1; W = 0; unknown flag bits; pis or zs NULL, or states and
+ * boards both NULL; a states entry with overlapping stones or bits outside the 7x6 board; a call while a training session
+ * (az_net_train_begin) or a self-play session is open.  Playing strength under this route is unmeasured. */
+#define AZ_TRAIN_EPOCH_BY_WEIGHT 1
+#define AZ_TRAIN_MIRROR          2
+az_status az_net_train_samples(az_engine* e, int32_t prev_id, int32_t id, const az_samples* s,
+                               const uint32_t* weights, int32_t flags);
+az_status az_net_train_draw(az_engine* e, int64_t n, const uint32_t* weights, int32_t flags, uint64_t t0,
+                            int64_t steps, int64_t* idx_out /* [steps*b] */, uint8_t* mirror_out /* [steps*b], may be NULL */);
+
 /* ---- arena::play_games, src/arena.rs:62-99 + gate, src/coach.rs:377-390 ---- */
 typedef struct az_arena_params {
     int32_t num_games;      /* num/2 per seating, src/arena.rs:83 */

@@ -42,6 +42,9 @@
 // az_host::tournament / az_host::rating_fit: no Coach calls them.
 #pragma weak az_tournament
 #pragma weak az_rating_fit
+// Coach::merge_weighted / az_host::train_samples / az_host::train_draw: with merge_weighted off (the default) no Coach calls them.
+#pragma weak az_net_train_samples
+#pragma weak az_net_train_draw
 
 namespace az_host {
 
@@ -250,6 +253,29 @@ inline TournamentResult tournament(const Engine& e, const TournamentParams& p) {
 }
 // Bradley-Terry ratings (a draw = half a win): elo [K] with mean 0 and elo_se [K], the diagonal Fisher approximation.  Needs no engine
 struct Ratings { std::vector<double> elo, elo_se; int32_t sweeps = 0; };
+// NNet::train on n tuples whose batch rows are drawn in proportion to `weights` (az_net_train_samples; nullptr = all ones), from states
+// [n,2] -- the device builds each batch's planes from the bits -- or, with states nullptr, from boards [n,2,6,7].  flags: AZ_TRAIN_*.
+inline void train_samples(const Engine& e, size_t prev_id, size_t id, int64_t n, const uint64_t* states, const float* boards, const float* pis,
+                          const float* zs, const uint32_t* weights = nullptr, int32_t flags = 0) {
+    if (!az_net_train_samples) throw Panic("train_samples: the linked engine library has no az_net_train_samples");
+    az_samples s{};
+    s.capacity = n; s.count = n;
+    s.states = const_cast<uint64_t*>(states); s.boards = const_cast<float*>(boards);
+    s.pis = const_cast<float*>(pis); s.zs = const_cast<float*>(zs);
+    e.check(az_net_train_samples(e.raw(), (int32_t)prev_id, (int32_t)id, &s, weights, flags));
+}
+// The rows az_net_train_samples would draw for global steps t0 .. t0 + steps at the engine's "train_seed" and "train_batch" (`batch` names
+// that value: it sizes the result): the tuple of every row and, under AZ_TRAIN_MIRROR, whether it is mirrored.
+struct TrainDraw { std::vector<int64_t> idx; std::vector<uint8_t> mirror; };
+inline TrainDraw train_draw(const Engine& e, int64_t n, const uint32_t* weights, int32_t flags, uint64_t t0, int64_t steps, int64_t batch) {
+    if (!az_net_train_draw) throw Panic("train_draw: the linked engine library has no az_net_train_draw");
+    TrainDraw d;
+    d.idx.assign((size_t)std::max<int64_t>(steps * batch, 0), -1);
+    d.mirror.assign(d.idx.size(), 0);
+    e.check(az_net_train_draw(e.raw(), n, weights, flags, t0, steps, d.idx.data(), d.mirror.data()));
+    return d;
+}
+
 inline Ratings rating_fit(const std::vector<uint64_t>& wld, size_t K, double prior_games = 2.0) {
     if (!az_rating_fit) throw Panic("rating_fit: the linked engine library has no az_rating_fit");
     if (wld.size() != K * K * 3) throw Panic("rating_fit: wld must hold K * K * 3 counts");
@@ -501,9 +527,10 @@ struct ScopedOption {
 class Coach {
   public:
     // samples = the tuples trained on, samples_raw = the tuples of the window before position averaging (equal with merge_positions off)
+    // samples_weight (with merge_weighted): the sum of the multiplicities the batches were drawn by (= samples_raw); 0 with it off
     // quality (with solve_min_stones > 0): [0] the new model's arena moves, [1] the old model's, each {examined, kept, win_to_draw, win_to_loss,
     // draw_to_loss, unknown} (quality_tally above); all zero with the report off
-    struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; size_t samples_raw; uint64_t quality[2][6]; };
+    struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; size_t samples_raw; uint64_t quality[2][6]; size_t samples_weight; };
 
     // Coach::setup(checkpoint_directory, + the reference's 14 numeric parameters), src/coach.rs:38-103
     static Coach setup(Engine& e, const std::string& checkpoint_directory, size_t mcts_reserve_size, float update_threshold,
@@ -702,22 +729,37 @@ class Coach {
             ab.reserve(n * 84); ap.reserve(n * 7); av.reserve(n);
             for (auto& h : history) { ab.insert(ab.end(), h.boards.begin(), h.boards.end()); ap.insert(ap.end(), h.pis.begin(), h.pis.end()); av.insert(av.end(), h.vs.begin(), h.vs.end()); }
             const size_t n_raw = n;
+            if (merge_weighted && !merge_positions) throw Panic("merge_weighted requires merge_positions");
+            std::vector<uint64_t> as;                                 // merge_weighted: the merged states (no planes are made)
+            std::vector<uint32_t> mult;                               // ... and their multiplicities
             if (merge_positions) {                                    // one tuple per distinct position of the window: mean pi, mean z
                 if (!az_samples_merge) throw Panic("merge_positions: the linked engine library has no az_samples_merge");
-                std::vector<float> mb(n * 84), mp(n * 7), mv(n);
+                std::vector<float> mb(merge_weighted ? 0 : n * 84), mp(n * 7), mv(n);
                 az_samples src{}, dst{};
                 src.count = (int64_t)n; src.boards = ab.data(); src.pis = ap.data(); src.zs = av.data();
-                dst.capacity = (int64_t)n; dst.boards = mb.data(); dst.pis = mp.data(); dst.zs = mv.data();
-                e_.check(az_samples_merge(e_.raw(), &src, merge_canonical ? AZ_MERGE_CANONICAL : 0, &dst, nullptr));
+                dst.capacity = (int64_t)n; dst.pis = mp.data(); dst.zs = mv.data();
+                if (merge_weighted) { as.resize(n * 2); mult.resize(n); dst.states = as.data(); }
+                else dst.boards = mb.data();
+                e_.check(az_samples_merge(e_.raw(), &src, merge_canonical ? AZ_MERGE_CANONICAL : 0, &dst, merge_weighted ? mult.data() : nullptr));
                 n = (size_t)dst.count;
-                mb.resize(n * 84); mp.resize(n * 7); mv.resize(n);
+                mb.resize(merge_weighted ? 0 : n * 84); mp.resize(n * 7); mv.resize(n);
+                as.resize(merge_weighted ? n * 2 : 0); mult.resize(merge_weighted ? n : 0);
                 ab.swap(mb); ap.swap(mp); av.swap(mv);
             }
             const std::vector<int64_t> perm = shuffle_permutation(n, seed, iteration);   // :296-297
-            std::vector<float> sb(n * 84), sp(n * 7), sv(n);
+            std::vector<float> sb(merge_weighted ? 0 : n * 84), sp(n * 7), sv(n);
+            std::vector<uint64_t> ss(as.size());
+            std::vector<uint32_t> sw(mult.size());
+            size_t weight_sum = 0;
             for (size_t i = 0; i < n; ++i) {
                 const size_t src = (size_t)perm[i];
-                std::memcpy(&sb[i * 84], &ab[src * 84], 84 * sizeof(float));
+                if (merge_weighted) {                                 // the multiplicities travel with their tuples
+                    ss[2 * i] = as[2 * src]; ss[2 * i + 1] = as[2 * src + 1];
+                    sw[i] = mult[src];
+                    weight_sum += mult[src];
+                } else {
+                    std::memcpy(&sb[i * 84], &ab[src * 84], 84 * sizeof(float));
+                }
                 std::memcpy(&sp[i * 7], &ap[src * 7], 7 * sizeof(float));
                 sv[i] = av[src];
             }
@@ -726,7 +768,10 @@ class Coach {
                 ScopedOption optim_guard(weight_decay > 0 || clip_norm > 0 || lr_warmup_steps > 0 || lr_decay != 0 || ema_decay > 0,
                                          [&] { e_.set_train_optim(weight_decay, clip_norm, lr_warmup_steps, lr_decay, lr_floor, ema_decay); },
                                          [&] { e_.set_train_optim(); });
-                e_.check(az_net_train(e_.raw(), (int32_t)model_id, (int32_t)model_id + 1, sb.data(), sp.data(), sv.data(), (int64_t)n));   // :329
+                if (merge_weighted)       // rows in proportion to the multiplicities, mirrored at random under merge_canonical; an epoch keeps the merged set's cost
+                    train_samples(e_, model_id, model_id + 1, (int64_t)n, ss.data(), nullptr, sp.data(), sv.data(), sw.data(), merge_canonical ? AZ_TRAIN_MIRROR : 0);
+                else
+                    e_.check(az_net_train(e_.raw(), (int32_t)model_id, (int32_t)model_id + 1, sb.data(), sp.data(), sv.data(), (int64_t)n));   // :329
             }
             if (ema_decay > 0) {                                      // the candidate is the averaged model
                 if (!az_net_train_ema) throw Panic("ema_decay: the linked engine library has no az_net_train_ema");
@@ -734,7 +779,7 @@ class Coach {
             }
             if (rank_ == 0) e_.check(az_net_save(e_.raw(), (int32_t)model_id + 1, (dir_ + "/" + std::to_string(model_id + 1) + ".aznet").c_str()));
             Report r{};
-            r.iteration = iteration; r.samples = n; r.samples_raw = n_raw; r.model_id = model_id;
+            r.iteration = iteration; r.samples = n; r.samples_raw = n_raw; r.samples_weight = weight_sum; r.model_id = model_id;
             r.losses.resize(2 * (size_t)az_net_train_history(e_.raw(), nullptr, 0));
             az_net_train_history(e_.raw(), r.losses.data(), (int32_t)(r.losses.size() / 2));
             // arena: new (first listed) vs old, both seatings (:333-375)
@@ -838,6 +883,12 @@ class Coach {
     // and nothing expands them again, so the net then trains on the CANONICAL orientation of every position only -- half the set; meant to
     // go with eval_mirror, which evaluates on that orientation.  false (the default): the engine is never asked
     bool merge_positions = false, merge_canonical = false;
+    // merge_weighted (requires merge_positions): the merge's multiplicities are kept, shuffled with their tuples, and NNet::train draws every
+    // batch row in proportion to them (az_net_train_samples, from the merged STATES: no feature planes are made) -- the raw window's
+    // distribution at the merged set's size and step count; under merge_canonical rows are mirrored at random (AZ_TRAIN_MIRROR), so the net
+    // sees both orientations again.  Report::samples_weight is the sum of the multiplicities (= samples_raw).  Files on disk stay raw.
+    // false (the default): the counts are dropped and az_net_train runs as before
+    bool merge_weighted = false;
     // The optimiser rules of NNet::train (Engine::set_train_optim): decoupled weight decay, gradient-norm clipping, warm-up and decay of the
     // learning rate (lr_decay 0 none / 1 cosine / 2 linear, over the call's own steps) and an averaged shadow of the weights, set before
     // the iteration's one az_net_train and cleared behind it.  With ema_decay > 0 the candidate -- what the arena gates, what is saved as

@@ -50,6 +50,9 @@ pub struct az_arena_params {
 
 /// flags bit 0 of az_samples_merge: a position and its left-right mirror image merge (the state kept is the canonical one)
 pub const AZ_MERGE_CANONICAL: i32 = 1;
+/// flags of az_net_train_samples / az_net_train_draw: an epoch has sum(weights) / batch steps (not n / batch); rows are mirrored at random
+pub const AZ_TRAIN_EPOCH_BY_WEIGHT: i32 = 1;
+pub const AZ_TRAIN_MIRROR: i32 = 2;
 
 /// az_solve: an action that is not legal (or a finished position) / a search that exhausted max_nodes (or a position below min_stones)
 pub const AZ_SOLVE_ILLEGAL: i8 = -128;
@@ -94,6 +97,12 @@ extern "C" {
     pub fn az_net_train_end(e: *mut az_engine, model_id: i32) -> c_int;
     pub fn az_net_train_ema(e: *mut az_engine, model_id: i32) -> c_int;
     pub fn az_net_train_step_info(e: *const az_engine, out: *mut f64) -> c_int;
+    /// NNet::train from an az_samples (s.count tuples; s.states, or s.boards when states is null; s.pis; s.zs; host or device): every
+    /// batch row is tuple i with probability weights[i] / sum(weights) (u32, null = all ones: az_net_train's draw), flags = AZ_TRAIN_*
+    pub fn az_net_train_samples(e: *mut az_engine, prev_id: i32, id: i32, s: *const az_samples, weights: *const u32, flags: i32) -> c_int;
+    /// the draw alone for global steps t0 .. t0 + steps: idx_out [steps * "train_batch"], mirror_out the same length (may be null)
+    pub fn az_net_train_draw(e: *mut az_engine, n: i64, weights: *const u32, flags: i32, t0: u64, steps: i64, idx_out: *mut i64,
+                             mirror_out: *mut u8) -> c_int;
     // ---- AsyncMcts, src/async_mcts.rs:14-115
     pub fn az_tree_create(e: *mut az_engine, n_games: i32, reserve: u64, num_sims: i32, num_threads: i32, max_depth: i32,
                           model_id: i32, cpuct: i32, out: *mut *mut az_tree) -> c_int;

@@ -7,7 +7,11 @@ episodes, 100 sims/move, symmetries expanded at the destination as both Coaches 
      few of them share a key (m is printed)
   C  the merge as both Coaches call it (feature planes in pageable host memory in, planes back out: wall time of Engine.merge_samples,
      best of 3), then az_net_train seconds on the raw set and on the merged set (`epochs` epochs each; steps = epochs * n / batch)
-python tools/merge_positions_ab.py A|B|C [episodes=8192] [sims=100] [channels=512] [epochs=2] [reps=5]"""
+  D  the weighted arm (az_net_train_samples): az_net_train on the raw set, on the merged set, and
+     az_net_train_samples on the merged STATES with the counts as weights (mirrored at random under AZ_MERGE_CANONICAL) -- seconds, ms per
+     step and the last epoch's training losses.  The losses are each route's own: merged targets are means, so their cross-entropy floor
+     is higher than the raw one-game targets' even where the gradients agree in expectation
+python tools/merge_positions_ab.py A|B|C|D [episodes=8192] [sims=100] [channels=512] [epochs=2] [reps=5]"""
 import os, sys, time
 import numpy as np
 import torch                   # before the engine library: one HIP runtime per process
@@ -106,4 +110,21 @@ elif part == "C":
         dt = time.perf_counter() - t
         steps = epochs * (len(zz) // 64)
         print(f"C  {name:18s} n {len(zz)}  {epochs} epochs  {steps} steps  az_net_train {dt:8.2f} s  {dt / max(steps, 1) * 1e3:.3f} ms/step  last loss {losses[-1]}", flush=True)
+elif part == "D":
+    s, p, z = iteration_tuples(e, False)
+    e.set_option("train_epochs", epochs)
+
+    def report(name, n, fn):
+        t = time.perf_counter()
+        losses = fn()
+        dt = time.perf_counter() - t
+        steps = epochs * max(1, n // 64)
+        print(f"D  {name:28s} n {n}  {epochs} epochs  {steps} steps  {dt:8.2f} s  {dt / steps * 1e3:.3f} ms/step  last loss {losses[-1]}", flush=True)
+    report("raw az_net_train", len(z), lambda: e.train(0, 1, states_to_boards(s), p, z))
+    for canonical in (False, True):
+        r = e.merge_samples(p, z, states=s, canonical=canonical)
+        m = r["count"]
+        print(f"D  canonical {int(canonical)}: n {len(z)}  m {m}  sum of counts {int(r['counts'].sum(dtype=np.uint64))}", flush=True)
+        report(f"merged c{int(canonical)} az_net_train", m, lambda: e.train(0, 1, states_to_boards(r["states"]), r["pis"], r["zs"]))
+        report(f"merged c{int(canonical)} weighted", m, lambda: e.train_samples(0, 1, r["pis"], r["zs"], states=r["states"], weights=r["counts"], mirror=canonical))
 e.close()
