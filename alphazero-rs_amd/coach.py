@@ -99,6 +99,15 @@ class Coach:
         # tally per model goes into the report ("quality") and one log line.  It decides nothing: the gate, the checkpoints, the .examples
         # files and coach.state are those of a run without it.  0 (the default): the engine is never asked
         self.solve_min_stones, self.solve_max_nodes = 0, 1 << 20
+        # Search statistics as targets (Engine.blend_z / Engine.surprise; csrc/az_target.h).  Either one switches "selfplay_record_search" on
+        # before every az_selfplay and off again behind it.  value_target_q (0 .. 1): right behind self-play the rank's own zs become
+        # (1 - q) * z + q * R, R the root value of the tuple's search -- before any gather, so the result does not depend on the world size.
+        # surprise_share (0 .. 1): the rank's own tuples are replaced by Engine.surprise's resampling (seed = seed + iteration), tuple i
+        # repeated c_i times with a share surprise_share of the weight in proportion to KL(pi || root prior) -- before the gather and the
+        # symmetry expansion; refused with a world above 1 (the normalisation would be per shard).  History, the .examples files, the merge
+        # and the trainers see ordinary tuples; merge_positions + merge_weighted turn the duplicates back into draw weights.  Both 0 (the
+        # default): the engine is never asked
+        self.value_target_q, self.surprise_share = 0.0, 0.0
         self.history = collections.deque()
         self.start_iteration = 0
         os.makedirs(self.dir, exist_ok=True)
@@ -158,6 +167,10 @@ class Coach:
         return self._scoped(self.gumbel_m > 0, lambda: self.engine.set_gumbel(self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale),
                             lambda: self.engine.set_gumbel(0))
 
+    def _selfplay_record_search(self):
+        return self._scoped(self.value_target_q > 0 or self.surprise_share > 0, lambda: self.engine.set_option("selfplay_record_search", 1),
+                            lambda: self.engine.set_option("selfplay_record_search", 0))
+
     def _train_optim(self):
         on = self.weight_decay > 0 or self.clip_norm > 0 or self.lr_warmup_steps > 0 or self.lr_decay != 0 or self.ema_decay > 0
         return self._scoped(on, lambda: self.engine.set_train_optim(self.weight_decay, self.clip_norm, self.lr_warmup_steps, self.lr_decay,
@@ -172,16 +185,28 @@ class Coach:
         """The self-play fan-out of src/coach.rs:241-272: num_eps x execute_episode, sharded by global game id."""
         from . import dist as azdist
         rank, world = self._world()
+        if not (0.0 <= self.value_target_q <= 1.0 and 0.0 <= self.surprise_share <= 1.0):
+            raise ValueError("value_target_q and surprise_share must be in 0 .. 1")
+        if self.surprise_share > 0 and world > 1:
+            raise ValueError("surprise_share needs a world of 1: the weights would be normalised per shard")
         lo, hi = azdist.shard_range(self.num_eps, rank, world)
         first = iteration * self.num_eps
         if hi > lo:
-            with self._selfplay_root_noise(), self._selfplay_playout_cap(), self._selfplay_forced_playouts(), self._selfplay_gumbel():
+            with self._selfplay_root_noise(), self._selfplay_playout_cap(), self._selfplay_forced_playouts(), self._selfplay_gumbel(), \
+                    self._selfplay_record_search():
                 r = self.engine.selfplay(n_games=hi - lo, num_sims=self.num_sims, model_id=model_id, seed=seed,
                                          first_game_id=first + lo, concurrent=min(self.num_episode_threads, hi - lo),
                                          temp_threshold=self.temp_threshold, max_depth=self.max_depth, cpuct=self.cpuct,
                                          reserve=self.mcts_reserve_size, symmetries=False, want_boards=False,
                                          num_sim_threads=self.num_sim_threads)
+                if self.value_target_q > 0 or self.surprise_share > 0:
+                    root_q, root_prior = self.engine.selfplay_search()
             states, pis, zs = r["states"], r["pis"], r["zs"]
+            if self.value_target_q > 0:                                 # a blended z is still a z
+                zs = self.engine.blend_z(zs, root_q, self.value_target_q)
+            if self.surprise_share > 0:                                 # a resampled set is still a set of tuples
+                sp = self.engine.surprise(pis, zs, root_prior, self.surprise_share, seed + iteration, states=states)
+                states, pis, zs = sp["states"], sp["pis"], sp["zs"]
         else:
             states, pis, zs = np.zeros((0, 2), np.uint64), np.zeros((0, 7), np.float32), np.zeros(0, np.float32)
         if world > 1:

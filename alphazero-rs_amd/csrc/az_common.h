@@ -89,6 +89,8 @@ constexpr uint64_t RNG_GUMBEL = 8;
 // weighted training draws (az_draw.h): batch row j of step t is mirrored iff the top bit of rng_draw(seed, t, j, RNG_TRAIN_MIRROR) is set
 // (purposes 1 to 8 and their + 256 * a sub-streams are taken)
 constexpr uint64_t RNG_TRAIN_MIRROR = 9;
+// surprise resampling (az_target.h): the uniform behind the copies of tuple i = rng_draw(seed, i, 0, RNG_SURPRISE)
+constexpr uint64_t RNG_SURPRISE = 10;
 AZ_HD bool dropout_keep(uint64_t mask_seed, uint32_t layer, uint64_t idx, uint32_t keep_thresh24) {
     const uint64_t r = mix64(mix64(mask_seed ^ ((uint64_t)(layer + 1) * 0xD1B54A32D192ED03ull)) ^ idx);
     return (uint32_t)(r >> 40) < keep_thresh24;

@@ -27,6 +27,7 @@
 #include "az_net.h"
 #include "az_optim.h"
 #include "az_solve.h"
+#include "az_target.h"
 #include "az_rating.h"
 #include "az_train.h"
 #include "az_tree.h"
@@ -361,6 +362,11 @@ struct az_engine {
     int64_t arena_opening_plies = 0;
     std::vector<uint64_t> ar_book;      // [entries][2] {first seat's stones, second seat's stones}; empty = no book
     std::vector<uint64_t> sp_full_plies;        // az_selfplay_get_full_plies: the full-ply masks of the last az_selfplay / az_selfplay_next
+    // "selfplay_record_search": self-play keeps the root value and the root's stored priors of every move (csrc/az_target.h); the rows of the
+    // last az_selfplay / az_selfplay_next, tuple for tuple in az_samples' order (az_selfplay_get_search)
+    int64_t selfplay_record_search = 0;
+    std::vector<float> sp_search_q, sp_search_prior;
+    bool sp_search_valid = false;               // the last az_selfplay / az_selfplay_next ran with the option on
     // activation workspaces of the conv net, one per stream that runs forwards: [0] the engine stream, [1 + i] side[i] below; created on
     // first use, shared by every model id
     NetWorkspace* ws[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -462,6 +468,7 @@ struct az_engine {
         }
         ~Scratch() { if (p) (void)hipFree(p); }
     } comm_scratch;
+    Scratch target_scratch;         // workspace of az_samples_blend_z / az_samples_surprise; follows merge_scratch's rule
     Scratch merge_scratch;          // workspace of az_samples_merge: sized by the call, kept for later calls of the same or a smaller size, given back
                                     // when a call needs under a quarter of a workspace of more than 256 MiB (a 2^24-tuple call holds over 10 GB)
     // az_solve / az_move_quality: solve_table = [counter][generation per lane, room for the device's lanes][lanes << tt_log2 entries], solve_io =
@@ -1143,6 +1150,7 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
         {"policy_prune", 0, 1, false, &az_engine::policy_prune, "policy_prune must be 0 or 1"},
         {"gumbel_m", GUMBEL_M_MIN, GUMBEL_M_MAX, true, &az_engine::gumbel_m, "gumbel_m must be 0 or in 2 .. 7"},
         {"gumbel_c_visit_e6", 0, GUMBEL_C_VISIT_E6_MAX, false, &az_engine::gumbel_c_visit_e6, "gumbel_c_visit_e6 must be in 0 .. 1000000000"},
+        {"selfplay_record_search", 0, 1, false, &az_engine::selfplay_record_search, "selfplay_record_search must be 0 or 1"},
         {"gumbel_c_scale_e6", GUMBEL_C_SCALE_E6_MIN, GUMBEL_C_SCALE_E6_MAX, false, &az_engine::gumbel_c_scale_e6, "gumbel_c_scale_e6 must be in 1 .. 100000000"},
     };
     for (const RootMoveKey& r : root_move_keys) {
@@ -2099,6 +2107,7 @@ struct SelfplaySession {
     ScopedEvalLog evlog;
     ScopedRootMove armed;                // the session's root-move record on the leased arena, for the session's life
     GamesDev gd{};
+    SearchRecDev rec{};                  // "selfplay_record_search": both nullptr while the option is off
     SearchParams sp{};
     SelfplayMoveParams mp{};
     uint32_t* h_ctr = nullptr;           // pinned read-back of gd.counters
@@ -2131,6 +2140,8 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     if (st) return st;
     st = gumbel_refusal(e, T, "az_selfplay");
     if (st) return st;
+    if (e->selfplay_record_search && e->selfplay_async)
+        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay: selfplay_record_search and selfplay_async exclude each other");
     const int cap_sims = (int)e->playout_cap_sims;
     if (cap_sims > 0 && cap_sims >= p->num_sims) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay: playout_cap_sims must be below num_sims");
     if (cap_sims > 0 && cap_sims % T != 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay: playout_cap_sims % num_sim_threads != 0");
@@ -2160,6 +2171,10 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     gd.g_result = mem.alloc<float>(n_games);
     gd.g_final_player = mem.alloc<int8_t>(n_games);
     gd.counters = mem.alloc<uint32_t>(8);
+    if (e->selfplay_record_search) {
+        ss->rec.root_q = mem.alloc<float>(ns);
+        ss->rec.root_prior = mem.alloc<float>(ns * 7);
+    }
     if (p->record_evals > 0) {
         // per-EPISODE logs (row = the slot's current episode id), so they survive slot refills
         gd.g_log_len = mem.alloc<int32_t>(n_games);
@@ -2284,6 +2299,7 @@ static az_status selfplay_run_until(az_engine* e, SelfplaySession& ss, int hi) {
         // playout cap: the round runs as many steps as the largest budget among its slots' moves (left by the previous round's move kernel);
         // a tree whose own budget is smaller sits the rest of the round out
         run_search(e, th, gd.state, ss.round_sims, ss.sp, *net, ss.active, nullptr, ss.rows_typ, gd.counters + 3);
+        if (ss.rec.root_q) launch_selfplay_record(th.d, gd, ss.rec, s);
         launch_selfplay_move(th.d, gd, ss.mp, s);
         if (ss.mp.refill) launch_reset_trees(th.d, gd.need_reset, s);
         HIPCHK(hipMemcpyAsync(h_ctr, gd.counters, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -2357,6 +2373,31 @@ static az_status selfplay_emit(az_engine* e, SelfplaySession& ss, int lo, int hi
     }
     if (out->game_len) HIPCHK(hipMemcpy(out->game_len, glen.data(), (size_t)n * sizeof(int32_t), hipMemcpyDefault));
     if (out->moves) HIPCHK(hipMemcpy(out->moves, gd.moves + (size_t)lo * 42, ns, hipMemcpyDefault));
+    e->sp_search_valid = ss.rec.root_q != nullptr;
+    if (ss.rec.root_q) {             // the search record's rows, emitted as the tuples are (az_selfplay_get_search)
+        const size_t cnt = (size_t)out->count;
+        e->sp_search_q.assign(cnt, 0.0f);
+        e->sp_search_prior.assign(cnt * 7, 0.0f);
+        if (cnt) {
+            DeviceMem mem;
+            int64_t* d_off = mem.alloc<int64_t>((size_t)n);
+            HIPCHK(hipMemcpy(d_off, off.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+            float* d_q = mem.alloc<float>(cnt);
+            float* d_prior = mem.alloc<float>(cnt * 7);
+            GamesDev view = gd;
+            view.n_games = n;
+            view.g_len += lo;
+            if (view.g_full) view.g_full += lo;
+            SearchRecDev rv{ss.rec.root_q + (size_t)lo * 42, ss.rec.root_prior + (size_t)lo * 42 * 7};
+            launch_emit_search(view, rv, d_off, p->symmetries, d_q, d_prior, s);
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipMemcpy(e->sp_search_q.data(), d_q, cnt * sizeof(float), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(e->sp_search_prior.data(), d_prior, cnt * 7 * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    } else {
+        e->sp_search_q.clear();
+        e->sp_search_prior.clear();
+    }
     return AZ_OK;
 }
 
@@ -2434,6 +2475,18 @@ az_status az_selfplay_get_full_plies(az_engine* e, uint64_t* mask) {
     if (!mask) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay_get_full_plies: null mask");
     if (!e->sp_full_plies.empty()) std::memcpy(mask, e->sp_full_plies.data(), e->sp_full_plies.size() * sizeof(uint64_t));
     return AZ_OK;
+}
+
+az_status az_selfplay_get_search(az_engine* e, float* root_q, float* root_prior) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!e->sp_search_valid) return fail(e, AZ_ERR_BAD_ARGUMENT, "no search record (run az_selfplay with selfplay_record_search = 1)");
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        if (root_q && !e->sp_search_q.empty()) HIPCHK(hipMemcpy(root_q, e->sp_search_q.data(), e->sp_search_q.size() * sizeof(float), hipMemcpyDefault));
+        if (root_prior && !e->sp_search_prior.empty())
+            HIPCHK(hipMemcpy(root_prior, e->sp_search_prior.data(), e->sp_search_prior.size() * sizeof(float), hipMemcpyDefault));
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
 }
 
 az_status az_selfplay_get_evals(az_engine* e, int32_t* rec_count, uint64_t* states, float* pis, float* vs) {
@@ -2923,6 +2976,134 @@ az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, a
         if (counts) HIPCHK(hipMemcpyAsync(counts, b.cnt, m * 4, hipMemcpyDefault, s));
         HIPCHK(hipStreamSynchronize(s));
         dst->count = (int64_t)m;
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// ---- search statistics as training targets: z/q blend and surprise resampling (csrc/az_target.h) -----------------------
+az_status az_samples_blend_z(az_engine* e, int64_t n, const float* zs, const float* root_q, int64_t lambda_e6, float* zs_out) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_blend_z: a self-play session is open");
+    if (e->train_open) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_blend_z: a training session is open");
+    if (n < 0 || n > DRAW_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_blend_z: 0 .. 2^31 - 1 values");
+    if (lambda_e6 < 0 || lambda_e6 > TARGET_E6) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_blend_z: lambda_e6 must be in 0 .. 1000000");
+    if (n == 0) return AZ_OK;
+    if (!zs || !root_q || !zs_out) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_blend_z: zs, root_q and zs_out are required");
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t N = (size_t)n, row = (N * 4 + 255) / 256 * 256;
+        const size_t total = 256 + 3 * row;
+        if (e->target_scratch.cap > ((size_t)1 << 28) && e->target_scratch.cap / 4 > total) e->target_scratch.release(s);
+        char* base = (char*)e->target_scratch.ensure(total, s);
+        uint32_t* d_bad = (uint32_t*)base;
+        float *d_z = (float*)(base + 256), *d_r = (float*)(base + 256 + row), *d_o = (float*)(base + 256 + 2 * row);
+        HIPCHK(hipMemsetAsync(d_bad, 0, 256, s));
+        HIPCHK(hipMemcpyAsync(d_z, zs, N * 4, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(d_r, root_q, N * 4, hipMemcpyDefault, s));
+        launch_target_blend(d_z, d_r, n, lambda_e6, d_o, d_bad, s);
+        uint32_t bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (bad) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_blend_z: a z or a root_q that is NaN or outside [-1, 1]");
+        HIPCHK(hipMemcpyAsync(zs_out, d_o, N * 4, hipMemcpyDefault, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+az_status az_samples_surprise(az_engine* e, const az_samples* src, const float* priors, int64_t share_e6, uint64_t seed, az_samples* dst,
+                              uint32_t* counts, float* kl) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!src) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: src is required");
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a self-play session is open");
+    if (e->train_open) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a training session is open");
+    if (share_e6 < 0 || share_e6 > TARGET_E6) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: share_e6 must be in 0 .. 1000000");
+    const long long n = src->count;
+    if (n < 0 || n > TARGET_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: 0 .. 2^24 tuples");
+    if (n > 0 && (!priors || !src->pis || !src->zs || (!src->states && !src->boards)))
+        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: needs priors and src's pis, zs and states or boards");
+    if (dst) {
+        if (!dst->pis || !dst->zs) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: dst needs pis and zs");
+        if (dst->capacity < 2 * n) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: dst->capacity is below 2 * src->count");
+        if (n > 0 && ((dst->states && !src->states) || (dst->boards && !src->boards)))
+            return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: dst asks for an array (states / boards) that src does not have");
+        // no dst array may overlap a src array, as in az_samples_merge
+        const size_t N = (size_t)n, C = (size_t)dst->capacity;
+        const std::pair<const void*, size_t> in[5] = {{src->states, N * 16}, {src->boards, N * AZ_FEATURES * 4}, {src->pis, N * AZ_ACTIONS * 4}, {src->zs, N * 4},
+                                                      {priors, N * AZ_ACTIONS * 4}};
+        const std::pair<const void*, size_t> out[4] = {{dst->states, C * 16}, {dst->boards, C * AZ_FEATURES * 4}, {dst->pis, C * AZ_ACTIONS * 4}, {dst->zs, C * 4}};
+        for (const auto& a : in)
+            for (const auto& b : out) {
+                if (!a.first || !b.first || !a.second || !b.second) continue;
+                const uintptr_t a0 = (uintptr_t)a.first, b0 = (uintptr_t)b.first;
+                if (a0 < b0 + b.second && b0 < a0 + a.second) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a dst array overlaps a src array");
+            }
+    }
+    if (n == 0) { if (dst) dst->count = 0; return AZ_OK; }
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t N = (size_t)n, M = 2 * N;
+        const bool st = src->states != nullptr, bd = src->boards != nullptr;
+        const bool o_st = dst && dst->states, o_bd = dst && dst->boards;
+        const size_t nb = draw_scan_blocks(n);
+        size_t total = 0;
+        auto need = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
+        // [hdr: bad, SK, W] [inputs] [per tuple] [outputs, 2n rows]
+        const size_t o_hdr = need(256), o_in_st = need(st ? N * 16 : 0), o_in_b = need(bd ? N * AZ_FEATURES * 4 : 0), o_in_pi = need(N * 28),
+                     o_in_z = need(N * 4), o_in_pr = need(N * 28), o_kl = need(N * 4), o_K = need(N * 8), o_cnt = need(N * 4), o_Q = need(N * 8),
+                     o_bsum = need(nb * 8), o_idx = need(dst ? M * 4 : 0), o_out_st = need(o_st ? M * 16 : 0), o_out_b = need(o_bd ? M * AZ_FEATURES * 4 : 0),
+                     o_out_pi = need(dst ? M * 28 : 0), o_out_z = need(dst ? M * 4 : 0);
+        if (e->target_scratch.cap > ((size_t)1 << 28) && e->target_scratch.cap / 4 > total) e->target_scratch.release(s);
+        char* base = (char*)e->target_scratch.ensure(total, s);
+        uint32_t* d_bad = (uint32_t*)(base + o_hdr);
+        uint64_t *d_SK = (uint64_t*)(base + o_hdr + 8), *d_W = (uint64_t*)(base + o_hdr + 16);
+        const ulonglong2* d_st = st ? (const ulonglong2*)(base + o_in_st) : nullptr;
+        const float* d_b = bd ? (const float*)(base + o_in_b) : nullptr;
+        const float *d_pi = (const float*)(base + o_in_pi), *d_z = (const float*)(base + o_in_z), *d_pr = (const float*)(base + o_in_pr);
+        float* d_kl = (float*)(base + o_kl);
+        uint64_t *d_K = (uint64_t*)(base + o_K), *d_Q = (uint64_t*)(base + o_Q), *d_bsum = (uint64_t*)(base + o_bsum);
+        uint32_t* d_cnt = (uint32_t*)(base + o_cnt);
+        HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
+        if (st) HIPCHK(hipMemcpyAsync(base + o_in_st, src->states, N * 16, hipMemcpyDefault, s));
+        if (bd) HIPCHK(hipMemcpyAsync(base + o_in_b, src->boards, N * AZ_FEATURES * 4, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_in_pi, src->pis, N * 28, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_in_z, src->zs, N * 4, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_in_pr, priors, N * 28, hipMemcpyDefault, s));
+        // 1. KL, K and their integer sum; every refusal that depends on the data is found here, before anything is written for the caller
+        launch_target_kl(d_st, st ? nullptr : d_b, d_pi, d_z, d_pr, n, d_kl, d_K, d_SK, d_bad, s);
+        uint32_t bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (bad & TARGET_BAD_FEATURE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a boards feature that is not 0 or 1, or a cell set in both planes");
+        if (bad & TARGET_BAD_STATE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a state with overlapping stones or bits outside the 7x6 board");
+        if (bad & TARGET_BAD_VALUE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a pi or z that is NaN or outside [-1, 1]");
+        if (bad & TARGET_BAD_PRIOR) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a prior that is NaN or outside [0, 1]");
+        // 2. copies, 3. their inclusive prefix
+        launch_target_copies(d_K, d_SK, n, share_e6, seed, d_cnt, s);
+        launch_draw_scan(d_cnt, n, d_Q, d_bsum, d_W, s);
+        uint64_t W = 0;
+        HIPCHK(hipMemcpyAsync(&W, d_W, sizeof W, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (dst) {
+            if (W > (uint64_t)M) return fail(e, AZ_ERR_HIP, "az_samples_surprise: the scan returned an impossible row count");
+            // 4. the gather
+            launch_target_gather(d_Q, n, (int64_t)W, (uint32_t*)(base + o_idx), d_st, d_b, d_pi, d_z, o_st ? (ulonglong2*)(base + o_out_st) : nullptr,
+                                 o_bd ? (float*)(base + o_out_b) : nullptr, (float*)(base + o_out_pi), (float*)(base + o_out_z), s);
+            if (W) {
+                if (o_st) HIPCHK(hipMemcpyAsync(dst->states, base + o_out_st, (size_t)W * 16, hipMemcpyDefault, s));
+                if (o_bd) HIPCHK(hipMemcpyAsync(dst->boards, base + o_out_b, (size_t)W * AZ_FEATURES * 4, hipMemcpyDefault, s));
+                HIPCHK(hipMemcpyAsync(dst->pis, base + o_out_pi, (size_t)W * 28, hipMemcpyDefault, s));
+                HIPCHK(hipMemcpyAsync(dst->zs, base + o_out_z, (size_t)W * 4, hipMemcpyDefault, s));
+            }
+        }
+        if (counts) HIPCHK(hipMemcpyAsync(counts, d_cnt, N * 4, hipMemcpyDefault, s));
+        if (kl) HIPCHK(hipMemcpyAsync(kl, d_kl, N * 4, hipMemcpyDefault, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (dst) dst->count = (int64_t)W;
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
 }

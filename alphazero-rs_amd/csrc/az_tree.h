@@ -232,6 +232,14 @@ struct GamesDev {
     uint32_t* counters;
 };
 
+// "selfplay_record_search" (az_target.h): what the root's search knew when a move was played, per (episode, ply) next to
+// smp_pi.  The arrays exist only while the option is on (both nullptr otherwise, as GamesDev::g_full); no kernel of the option-off path
+// takes this struct.
+struct SearchRecDev {
+    float* root_q;           // [n_games*42] R: the visit-weighted mean of the root children's raw q, clamped to [-1, 1]
+    float* root_prior;       // [n_games*42*7] the root children's stored prior by action, as the search used it (root noise included); 0 = invalid
+};
+
 struct SelfplayMoveParams {
     uint64_t seed;
     uint64_t first_game_id;
@@ -363,5 +371,12 @@ void launch_match_sync(const TreeDev& t, const ArenaDev& ad, const MatchTable& t
 void launch_match_move(const TreeDev& t, const ArenaDev& ad, const MatchTable& tb, uint64_t seed, hipStream_t s);
 void launch_emit_samples(const GamesDev& gd, const int64_t* offsets, int symmetries, ulonglong2* out_states,
                          float* out_boards, float* out_pis, float* out_zs, hipStream_t s);
+// "selfplay_record_search": launched in front of launch_selfplay_move on the lock-step paths; every slot that is about to move writes the
+// (episode, ply) slot of rec from its root record and child block, read exactly as root_policy reads them
+void launch_selfplay_record(const TreeDev& t, const GamesDev& gd, const SearchRecDev& rec, hipStream_t s);
+// launch_emit_samples' sibling for rec: the same offsets, playout-cap compaction and symmetry expansion (a mirrored tuple's prior is reversed,
+// its R is the same)
+void launch_emit_search(const GamesDev& gd, const SearchRecDev& rec, const int64_t* offsets, int symmetries, float* out_q, float* out_prior,
+                        hipStream_t s);
 
 }  // namespace az

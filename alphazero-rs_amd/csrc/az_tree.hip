@@ -10,6 +10,7 @@
 #include "az_tree.h"
 #include "az_noise.h"
 #include "az_gumbel.h"
+#include "az_target.h"
 
 namespace az {
 static_assert(NOISE_PURPOSE == RNG_NOISE, "az_noise.h restates the purpose word of az_common.h");
@@ -1390,6 +1391,49 @@ __global__ __launch_bounds__(64) void k_selfplay_move(TreeDev t, GamesDev gd, Se
     if (selfplay_move_body<G, PC, RR>(t, h, gd, mp, g, sub, &word) == 2 && sub == 0) t.head[g].head.active = 0;
 }
 
+// "selfplay_record_search": the root value R (az_target.h) and the root children's stored priors by action of the move k_selfplay_move is
+// about to play, into the (episode, ply) slot.  Reads the root record and its child block as root_policy does; writes nothing else.
+template <class G>
+__global__ __launch_bounds__(64) void k_selfplay_record(TreeDev t, GamesDev gd, SearchRecDev rec) {
+    constexpr int GW = G::GROUP;
+    constexpr int NA = G::ACTIONS;
+    static_assert(NA == TARGET_ACTIONS, "az_target.h's rule is stated for 7 actions");
+    const int tid = blockIdx.x * 64 + threadIdx.x;
+    const int g = tid / GW, sub = tid % GW;
+    if (g >= t.G) return;
+    const int gi = gd.gid[g];
+    const TreeHead h = head_load(t, g);
+    if (gi < 0 || !h.active) return;
+    const size_t base = (size_t)g * t.R;
+    const NodeRec pr = node_load(node_ptr(t, base, h.root));
+    const uint32_t nchild = (pr.meta >> META_NCHILD_SHIFT) & 7u, cb = pr.child_base;
+    uint32_t ca = 0, cn = 0;
+    float cq = 0.0f, cp = 0.0f;
+    if ((uint32_t)sub < nchild) {
+        const NodeRec cr = node_load(node_ptr(t, base, cb + sub));
+        const uint64_t cc = cr.link != NONE ? node_ctr(node_ptr(t, base, cr.link)) : cr.ctr;
+        ca = cr.meta & META_A_MASK;
+        cn = ctr_n(cc);
+        cq = ctr_q(cc);
+        cp = __uint_as_float(cr.prior);
+    }
+    uint32_t an = 0u;                                                // lane a: action a's count, q and prior (0 for an invalid action)
+    float aq = 0.0f, ap = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        const uint32_t aj = gshfl<GW>(ca, j), nj = gshfl<GW>(cn, j);
+        const float qj = gshflf<GW>(cq, j), pj = gshflf<GW>(cp, j);
+        if ((uint32_t)j < nchild && aj == (uint32_t)sub) { an = nj; aq = qj; ap = pj; }
+    }
+    float acc = 0.0f;
+    uint32_t N = 0u;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) target_root_term(acc, N, gshfl<GW>(an, a), gshflf<GW>(aq, a));
+    const size_t so = (size_t)gi * G::MAX_PLIES + gd.ply[g];
+    if (sub < NA) rec.root_prior[so * NA + sub] = ap;
+    if (sub == 0) rec.root_q[so] = target_root_finish(acc, N);
+}
+
 // ---- FREE-RUNNING self-play: every slot on its own timeline ("selfplay_async") -------------------------------------------------------
 // The lock-step driver runs one simulation per tree per forward, and every tree waits for the move boundary of all: of 8192 trees only
 // ~40 % put a row into a step's batch (the others hit the evaluation cache, a terminal node or a transposition), so the net runs on
@@ -1496,6 +1540,33 @@ __global__ __launch_bounds__(256) void k_emit_samples(GamesDev gd, const int64_t
         if (f < NA) out_pis[o * NA + f] = gd.smp_pi[so * NA + (sym ? G::mirror_action(f) : f)];
         if (f == NA) out_zs[o] = __fmul_rn(r, gd.smp_player[so] == fin ? 1.0f : -1.0f);   // B4
         if (f == NA + 1 && out_states) out_states[o] = s;
+    }
+}
+
+// k_emit_samples' sibling for the search record: the same rows in the same order
+template <class G>
+__global__ __launch_bounds__(256) void k_emit_search(GamesDev gd, SearchRecDev rec, const int64_t* offsets, int symmetries, float* out_q, float* out_prior) {
+    constexpr int NA = G::ACTIONS;
+    const int gi = blockIdx.x;
+    int len = gd.g_len[gi];
+    const int nsym = symmetries ? 2 : 1;
+    __shared__ uint8_t s_ply[G::MAX_PLIES];
+    const bool compact = gd.g_full != nullptr;
+    if (compact) {
+        const unsigned long long fm = gd.g_full[gi] & ((1ull << len) - 1ull);
+        const int p = (int)threadIdx.x;
+        if (p < len && ((fm >> p) & 1ull)) s_ply[__popcll(fm & ((1ull << p) - 1ull))] = (uint8_t)p;
+        __syncthreads();
+        len = __popcll(fm);
+    }
+    for (int item = threadIdx.x; item < len * nsym * (NA + 1); item += blockDim.x) {
+        const int f = item % (NA + 1), rest = item / (NA + 1);
+        const int sym = rest % nsym, k = rest / nsym;
+        const int ply = compact ? (int)s_ply[k] : k;
+        const size_t so = (size_t)gi * G::MAX_PLIES + ply;
+        const int64_t o = (offsets[gi] + k) * nsym + sym;
+        if (f < NA) { if (out_prior) out_prior[o * NA + f] = rec.root_prior[so * NA + (sym ? G::mirror_action(f) : f)]; }
+        else if (out_q) out_q[o] = rec.root_q[so];
     }
 }
 
@@ -1744,6 +1815,9 @@ void launch_call_readback(unsigned long long* totals, unsigned long long* dd_sta
 void launch_selfplay_move(const TreeDev& t, const GamesDev& gd, SelfplayMoveParams mp, hipStream_t s) {
     AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_selfplay_move<TG, PC, RR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, mp))));
 }
+void launch_selfplay_record(const TreeDev& t, const GamesDev& gd, const SearchRecDev& rec, hipStream_t s) {
+    AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_selfplay_record<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, rec));
+}
 void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s) {
     const bool four = t.block4 && (t.G * 8) % 256 == 0;
@@ -1784,6 +1858,10 @@ void launch_emit_samples(const GamesDev& gd, const int64_t* offsets, int symmetr
     // features, mirror and plies are the board's, not the rules': both games share ConnectFour's
     hipLaunchKernelGGL(k_emit_samples<ConnectFour>, dim3(gd.n_games), dim3(256), 0, s, gd, offsets, symmetries, out_states,
                        out_boards, out_pis, out_zs);
+}
+void launch_emit_search(const GamesDev& gd, const SearchRecDev& rec, const int64_t* offsets, int symmetries, float* out_q, float* out_prior,
+                        hipStream_t s) {
+    hipLaunchKernelGGL(k_emit_search<ConnectFour>, dim3(gd.n_games), dim3(256), 0, s, gd, rec, offsets, symmetries, out_q, out_prior);
 }
 
 }  // namespace az

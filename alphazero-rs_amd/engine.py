@@ -92,7 +92,7 @@ EXPORTS = [
     "az_net_train_samples", "az_net_train_draw", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
-    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_tree_get_selected", "az_gumbel_values", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_samples_merge", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
+    "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_tree_get_selected", "az_gumbel_values", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_selfplay_get_search", "az_samples_merge", "az_samples_blend_z", "az_samples_surprise", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
     "az_arena_set_opening_book", "az_arena_get_openings", "az_tournament", "az_rating_fit",
     "az_comm_unique_id", "az_comm_local_id", "az_comm_init", "az_comm_destroy", "az_gather_samples", "az_allreduce_u64",
 ]
@@ -157,6 +157,9 @@ def load_library(path=LIB_PATH):
         "az_selfplay_get_evals": (i32, [vp, vp, vp, vp, vp]),
         "az_selfplay_get_full_plies": (i32, [vp, vp]),
         "az_samples_merge": (i32, [vp, C.POINTER(az_samples), i32, C.POINTER(az_samples), vp]),
+        "az_selfplay_get_search": (i32, [vp, vp, vp]),
+        "az_samples_blend_z": (i32, [vp, i64, vp, vp, i64, vp]),
+        "az_samples_surprise": (i32, [vp, C.POINTER(az_samples), vp, i64, u64, C.POINTER(az_samples), vp, vp]),
         "az_solve": (i32, [vp, vp, i32, C.c_uint32, i32, i32, i32, vp, vp, vp]),
         "az_move_quality": (i32, [vp, vp, vp, vp, i32, C.c_uint32, i32, i32, i32, vp, vp]),
         "az_arena": (i32, [vp, C.POINTER(az_arena_params), vp, vp]),
@@ -462,6 +465,15 @@ class Engine:
         self._check(self._lib.az_selfplay_get_full_plies(self._h, _ptr(mask)))
         return mask
 
+    def selfplay_search(self):
+        """az_selfplay_get_search: (root_q [count], root_prior [count,7]) of the last selfplay() / selfplay_next(), tuple for tuple in the
+        order of its pis and zs -- the root value R of the move and the root children's stored priors as the search used them.  Needs
+        set_option("selfplay_record_search", 1) before that call."""
+        n = getattr(self, "_sp_last_count", 0)
+        q, prior = np.zeros(n, np.float32), np.zeros((n, ACTIONS), np.float32)
+        self._check(self._lib.az_selfplay_get_search(self._h, _ptr(q), _ptr(prior)))
+        return q, prior
+
     def root_noise_eta(self, states, game_ids, seed=0):
         """az_root_noise_eta: eta [n,7] the device sampler draws for root states [n,2] on the streams (seed, game_ids[i], stones),
         at the engine's current alpha."""
@@ -526,6 +538,7 @@ class Engine:
                        _as_ptr(out["zs"]), _ptr(game_len), _ptr(moves))
         self._check(self._lib.az_selfplay(self._h, C.byref(p), C.byref(s)))
         self._sp_last_n = n_games
+        self._sp_last_count = int(s.count)
         n = int(s.count)
         res = {"count": n, "game_len": game_len, "moves": moves}
         for k in ("states", "boards", "pis", "zs"):
@@ -561,6 +574,7 @@ class Engine:
                        _as_ptr(out["zs"]), _ptr(game_len), _ptr(moves))
         self._check(self._lib.az_selfplay_next(self._h, n_games, C.byref(s)))
         self._sp_last_n = n_games
+        self._sp_last_count = int(s.count)
         n = int(s.count)
         res = {"count": n, "game_len": game_len, "moves": moves}
         for k in ("states", "boards", "pis", "zs"):
@@ -606,6 +620,60 @@ class Engine:
         m = int(dst.count)
         res = {k: v[:m] for k, v in out.items()}
         res["count"] = m
+        return res
+
+    # ---- z/q value targets and surprise resampling ----
+    def blend_z(self, zs, root_q, lam, out=None):
+        """az_samples_blend_z: (1 - lam) * zs + lam * root_q in f32 (csrc/az_target.h); lam travels as lambda_e6.  Inputs may be numpy arrays
+        or torch tensors (host or device); `out` may be either, zs itself included; without it a new numpy array is returned."""
+        n = int(len(zs))
+        if not hasattr(zs, "data_ptr"):
+            zs = np.ascontiguousarray(zs, dtype=np.float32).reshape(n)
+        if not hasattr(root_q, "data_ptr"):
+            root_q = np.ascontiguousarray(root_q, dtype=np.float32).reshape(n)
+        if len(root_q) != n:
+            raise ValueError("blend_z: zs and root_q differ in length")
+        if out is None:
+            out = np.zeros(n, np.float32)
+        self._check(self._lib.az_samples_blend_z(self._h, n, _as_ptr(zs), _as_ptr(root_q), int(round(float(lam) * 1e6)), _as_ptr(out)))
+        return out
+
+    def surprise(self, pis, zs, priors, share, seed, *, states=None, boards=None, want=True):
+        """az_samples_surprise: tuple i repeated c_i times, c_i drawn around a weight of which a share `share` is in proportion to
+        KL(pi_i || prior_i) and the rest uniform (include/az_engine.h).  The position comes from `states` [n,2] and/or `boards` [n,2,6,7];
+        inputs may be numpy arrays or torch tensors (host or device).  Returns dict(counts, kl) and, with want, count and the expanded
+        pis, zs and states / boards (whichever were given) as numpy arrays."""
+        if states is None and boards is None:
+            raise ValueError("surprise needs states or boards")
+        n = int(len(zs))
+        if not hasattr(pis, "data_ptr"):
+            pis = np.ascontiguousarray(pis, dtype=np.float32).reshape(n, ACTIONS)
+        if not hasattr(zs, "data_ptr"):
+            zs = np.ascontiguousarray(zs, dtype=np.float32).reshape(n)
+        if not hasattr(priors, "data_ptr"):
+            priors = np.ascontiguousarray(priors, dtype=np.float32).reshape(n, ACTIONS)
+        if states is not None and not hasattr(states, "data_ptr"):
+            states = np.ascontiguousarray(states, dtype=np.uint64).reshape(n, 2)
+        if boards is not None and not hasattr(boards, "data_ptr"):
+            boards = np.ascontiguousarray(boards, dtype=np.float32).reshape(n, 2, 6, 7)
+        res = {"counts": np.zeros(n, np.uint32), "kl": np.zeros(n, np.float32)}
+        src = az_samples(n, n, _as_ptr(states), _as_ptr(boards), _as_ptr(pis), _as_ptr(zs), None, None)
+        out, dst = {}, None
+        if want:
+            cap = 2 * n
+            out = {"pis": np.zeros((cap, ACTIONS), np.float32), "zs": np.zeros(cap, np.float32)}
+            if states is not None:
+                out["states"] = np.zeros((cap, 2), np.uint64)
+            if boards is not None:
+                out["boards"] = np.zeros((cap, 2, 6, 7), np.float32)
+            dst = az_samples(cap, 0, _ptr(out.get("states")), _ptr(out.get("boards")), _ptr(out["pis"]), _ptr(out["zs"]), None, None)
+        self._check(self._lib.az_samples_surprise(self._h, C.byref(src), _as_ptr(priors), int(round(float(share) * 1e6)), int(seed) & ((1 << 64) - 1),
+                                                  C.byref(dst) if dst is not None else None, _ptr(res["counts"]), _ptr(res["kl"])))
+        if want:
+            m = int(dst.count)
+            res["count"] = m
+            for k, v in out.items():
+                res[k] = v[:m]
         return res
 
     # ---- exact endgame solver ----

@@ -1,7 +1,7 @@
 // examples/connect_four.rs (src lines 45-80) on the C++ host: the same Coach::setup parameters, the engine behind it.
 // Build:  g++ -std=c++17 -O2 -I include examples/connect_four.cpp -o connect_four -L alphazero-rs_amd -laz_engine
 //         (and -Wl,-rpath,$PWD/alphazero-rs_amd)
-// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]]
+// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]] [--value-target-q L] [--surprise S]
 //         selfplay_fp8 = 1: the episodes are played in the fp8 class, the arena gate in bf16 (Coach::selfplay_class)
 //         root_noise_eps > 0 (e.g. 0.25, with root_noise_alpha 0.3; default alpha 1): Dirichlet root noise in the episodes (Coach::root_noise_eps)
 //         eval_mirror = 1: mirror-canonical leaf evaluation for the whole loop, episodes and gate (Coach::eval_mirror)
@@ -19,6 +19,10 @@
 //         --gumbel M[,CVISIT,CSCALE] (anywhere on the line, e.g. --gumbel 4 or --gumbel 4,50,1): Gumbel root search with sequential halving in
 //         the episodes -- at most M root actions considered, the improved policy recorded, the winner played (Coach::gumbel_m / gumbel_c_visit /
 //         gumbel_c_scale); not together with forced_playouts
+//         --value-target-q L (anywhere on the line, e.g. 0.5): the value target is (1 - L) z + L q, the game outcome mixed with the root value of
+//         the tuple's own search (Coach::value_target_q)
+//         --surprise S (anywhere on the line, e.g. 0.5): policy surprise weighting -- the iteration's tuples are resampled, a share S of the
+//         weight in proportion to KL(pi || root prior) (Coach::surprise_share)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,14 +31,19 @@
 
 int main(int argc, char** argv) {
     using namespace az_host;
-    std::string gumbel;
-    for (int i = 1; i + 1 < argc; ++i) {          // take "--gumbel VALUE" out of the line: the positionals keep their places
-        if (std::strcmp(argv[i], "--gumbel") != 0) continue;
-        gumbel = argv[i + 1];
-        for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
-        argc -= 2;
-        break;
-    }
+    // take "--name VALUE" out of the line: the positionals keep their places
+    auto take = [&](const char* name) {
+        std::string v;
+        for (int i = 1; i + 1 < argc; ++i) {
+            if (std::strcmp(argv[i], name) != 0) continue;
+            v = argv[i + 1];
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+        return v;
+    };
+    const std::string gumbel = take("--gumbel"), value_q = take("--value-target-q"), surprise_s = take("--surprise");
     const std::string dir = argc > 1 ? argv[1] : "./checkpoint";
     const size_t iters = argc > 2 ? std::strtoul(argv[2], nullptr, 10) : 1;       // num_iters, examples/connect_four.rs:65
     const size_t eps = argc > 3 ? std::strtoul(argv[3], nullptr, 10) : 1;         // num_eps, :66
@@ -63,6 +72,8 @@ int main(int argc, char** argv) {
         coach.root_noise_eps = noise_eps; coach.root_noise_alpha = noise_alpha;
         coach.playout_cap_sims = cap_sims; coach.playout_cap_full = cap_full;
         coach.forced_playouts_k = forced_k; coach.policy_prune = prune;
+        if (!value_q.empty()) coach.value_target_q = std::atof(value_q.c_str());
+        if (!surprise_s.empty()) coach.surprise_share = std::atof(surprise_s.c_str());
         if (!gumbel.empty()) {
             coach.gumbel_m = std::strtol(gumbel.c_str(), nullptr, 10);
             const size_t c1 = gumbel.find(','), c2 = c1 == std::string::npos ? c1 : gumbel.find(',', c1 + 1);

@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--ema", type=float, default=0.0)                # decay of the averaged weights, e.g. 0.999: the candidate is the averaged model (Coach.ema_decay)
     ap.add_argument("--merge-positions", nargs="?", const="plain", default=None, choices=["plain", "canonical", "weighted", "canonical,weighted"])   # position averaging before training: one tuple per distinct position; canonical also merges mirror images (Coach.merge_positions); weighted draws every training row in proportion to its multiplicity (Coach.merge_weighted)
     ap.add_argument("--move-quality", default=None, metavar="STONES[,NODES]")   # exact move-quality report of every arena: positions with at least STONES stones are solved (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach.solve_min_stones)
+    ap.add_argument("--value-target-q", type=float, default=0.0, metavar="L")   # value target (1 - L) z + L q: the game outcome mixed with the root value of the tuple's own search, e.g. 0.5 (Coach.value_target_q)
+    ap.add_argument("--surprise", type=float, default=0.0, metavar="S")   # policy surprise weighting: the iteration's tuples resampled, a share S of the weight in proportion to KL(pi || root prior), e.g. 0.5 (Coach.surprise_share)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
     ap.add_argument("--eval-mirror", action="store_true")    # mirror-canonical leaf evaluation for the whole loop (Coach.eval_mirror)
     a = ap.parse_args()
@@ -76,6 +78,7 @@ def main():
         coach.gumbel_m = int(parts[0])
         coach.gumbel_c_visit, coach.gumbel_c_scale = (float(parts[1]) if len(parts) > 1 else 50.0), (float(parts[2]) if len(parts) > 2 else 1.0)
     coach.arena_opening_plies = a.arena_openings
+    coach.value_target_q, coach.surprise_share = a.value_target_q, a.surprise
     coach.weight_decay, coach.clip_norm, coach.ema_decay = a.weight_decay, a.clip_norm, a.ema
     if a.lr_schedule:
         parts = a.lr_schedule.split(",")

@@ -636,6 +636,23 @@ az_status az_selfplay_end(az_engine* e);
  * tuples: bit `ply` of mask[i] for the i-th episode of that call (42 plies fit a word).  All ones up to game_len when the feature is
  * off.  mask holds as many words as that call returned episodes. */
 az_status az_selfplay_get_full_plies(az_engine* e, uint64_t* mask /* [n_games] */);
+/* ---- the search's own statistics per tuple (no reference counterpart; csrc/az_target.h) ----
+ * az_set_option(e, "selfplay_record_search", 1) (0 = default, OFF; state of the engine; refused while a self-play session is open) makes
+ * self-play keep, per episode and ply next to pi:
+ *   R        the root value of the move: the visit-weighted mean of the root children's RAW q (the `q` and `counts` of
+ *            az_tree_get_action_prob: raw under forced playouts, pruning and Gumbel), summed in ascending action order in f32 and clamped
+ *            to [-1, 1]; in the perspective of the side to move, the sign of the tuple's z
+ *   prior    the root children's stored prior by action AS THE SEARCH USED IT: root noise is included while that is on; 0 for an invalid
+ *            action.  The raw net output is not recovered
+ * With the option off no array exists, no kernel is added to any path and every output and counter is what it was.  With it on the tuples
+ * are unchanged bit for bit; one small kernel runs in front of each move of the lock-step paths ("fused_search" 0 / 1, every "eval_dedup",
+ * num_sim_threads > 1, slot refill, sessions, both games, fp8 and "eval_mirror" models, root noise, playout cap, forced playouts, Gumbel).
+ * az_selfplay / az_selfplay_begin refuse (AZ_ERR_BAD_ARGUMENT) the option together with "selfplay_async" = 1.  az_arena, az_tree_* and the
+ * slot calls never record.
+ * az_selfplay_get_search: rows of the last az_selfplay / az_selfplay_next, tuple for tuple in az_samples' order (the same playout-cap
+ * compaction and symmetry expansion: a mirrored tuple's prior is reversed, its R is the same); host or device pointers; either may be NULL.
+ * AZ_ERR_BAD_ARGUMENT when that call ran with the option off. */
+az_status az_selfplay_get_search(az_engine* e, float* root_q /* [count] */, float* root_prior /* [count,7] */);
 /* Eval log of the last az_selfplay with record_evals > 0: rec_count [n_games], states [n_games,cap,2], ... */
 az_status az_selfplay_get_evals(az_engine* e, int32_t* rec_count, uint64_t* states, float* pis, float* vs);
 
@@ -678,6 +695,32 @@ az_status az_selfplay_get_evals(az_engine* e, int32_t* rec_count, uint64_t* stat
  * Whether averaged targets change playing strength is unmeasured. */
 #define AZ_MERGE_CANONICAL 1   /* flags bit 0 */
 az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, az_samples* dst, uint32_t* counts);
+
+/* ---- z/q value targets and surprise resampling (no reference counterpart; csrc/az_target.h states every formula operation by operation;
+ * DESIGN.md section 4.1k).  Both are pure in az_samples_merge's sense -- models, trees, the cache, options and every az_stats counter but
+ * device_ms stay untouched --, run on the engine's stream, take host or device pointers and are refused while a self-play or a training
+ * session is open.  Their outputs are ordinary tuples: az_samples_merge, the trainers, the .examples files and az_gather_samples need not know.
+ *
+ * az_samples_blend_z: zs_out[i] = a * zs[i] + b * root_q[i] with b = (float)lambda_e6 / 1e6f and a = 1.0f - b (four f32 roundings);
+ * lambda_e6 = 0 returns zs and 1000000 returns root_q bit for bit.  zs_out may equal zs.  n = 0 is legal.  Refused (AZ_ERR_BAD_ARGUMENT),
+ * with nothing written: n < 0, lambda_e6 outside 0 .. 1000000, a NaN or a |value| > 1 in either input.
+ *
+ * az_samples_surprise: writes tuple i of src c_i times (KataGo's policy surprise weighting as a resampling of the window):
+ *   KL_i     KL(pi_i || prior_i) in f32 over the actions with pi >= 2^-126 (prior floored at 2^-126), clamped to [0, 64]
+ *   K_i, SK  K_i = llrint(KL_i * 2^32); SK = their sum in u64: an integer sum, so no result depends on the order of the additions
+ *   w_i      (1 - s) + s * n * K_i / SK in f64 with s = share_e6 / 1e6 (1 when SK = 0): the weights average 1 -- a share 1 - s spread
+ *            uniformly, a share s in proportion to KL
+ *   c_i      floor(w_i) + (U_i < frac(w_i)), U_i = (rng_draw(seed, i, 0, RNG_SURPRISE) >> 11) * 2^-53; sum c_i <= 2n
+ * It reads src->count, pis, zs and states and/or boards (validated as az_samples_merge validates them; a prior outside [0, 1] is refused as
+ * well); n <= 2^24; share_e6 in 0 .. 1000000.  counts[i] = c_i and kl[i] = KL_i (each may be NULL).  With dst set, dst holds tuple i
+ * repeated c_i times in input order, every copy bit for bit, in the arrays dst has (pis and zs are required; states / boards only where src
+ * has them), and dst->count = sum c_i; dst->capacity >= 2n is required and no dst array may overlap a src array or priors.  share_e6 = 0, or
+ * a window with SK = 0, returns the input unchanged with all counts 1.  Every refusal leaves dst, counts and kl unwritten.
+ * az_samples_merge turns the duplicates back into multiplicities (its `counts`), which az_net_train_samples draws by.
+ * Whether either target changes playing strength is unmeasured. */
+az_status az_samples_blend_z(az_engine* e, int64_t n, const float* zs, const float* root_q, int64_t lambda_e6, float* zs_out);
+az_status az_samples_surprise(az_engine* e, const az_samples* src, const float* priors /* [n,7] */, int64_t share_e6, uint64_t seed,
+                              az_samples* dst /* may be NULL */, uint32_t* counts /* [n], may be NULL */, float* kl /* [n], may be NULL */);
 
 /* ---- NNet::train from merged positions: batch rows drawn in proportion to their multiplicities (no reference counterpart; csrc/az_draw.h,
  * DESIGN.md section 8.2).  Strictly opt-in: az_net_train and every kernel it launches are untouched.  az_samples_merge gives one tuple per

@@ -45,6 +45,10 @@
 // Coach::merge_weighted / az_host::train_samples / az_host::train_draw: with merge_weighted off (the default) no Coach calls them.
 #pragma weak az_net_train_samples
 #pragma weak az_net_train_draw
+// Coach::value_target_q / Coach::surprise_share / az_host::selfplay_search / blend_z / surprise: with both fields 0 (the default) no Coach calls them.
+#pragma weak az_selfplay_get_search
+#pragma weak az_samples_blend_z
+#pragma weak az_samples_surprise
 
 namespace az_host {
 
@@ -143,6 +147,9 @@ class Engine {
     // include/az_engine.h): prior <- (1 - eps) * prior + eps * eta at the root, eta ~ Dirichlet(alpha).  eps = 0 switches it off
     // "eval_mirror" (include/az_engine.h, default off): conv models answer on the canonical orientation of a position, pi un-mirrored
     void set_eval_mirror(bool on) { check(az_set_option(e_, "eval_mirror", on ? 1 : 0)); }
+    // "selfplay_record_search" (include/az_engine.h): self-play keeps the root value and the root's stored priors of every move
+    // (az_host::selfplay_search reads them); never the arena or the tree calls
+    void set_record_search(bool on) { check(az_set_option(e_, "selfplay_record_search", on ? 1 : 0)); }
     void set_root_noise(double eps, double alpha = 1.0) {
         check(az_set_option(e_, "root_noise_alpha_e6", (int64_t)std::llround(alpha * 1e6)));
         check(az_set_option(e_, "root_noise_eps_e6", (int64_t)std::llround(eps * 1e6)));
@@ -274,6 +281,43 @@ inline TrainDraw train_draw(const Engine& e, int64_t n, const uint32_t* weights,
     d.mirror.assign(d.idx.size(), 0);
     e.check(az_net_train_draw(e.raw(), n, weights, flags, t0, steps, d.idx.data(), d.mirror.data()));
     return d;
+}
+
+// ---- search statistics as targets (include/az_engine.h; csrc/az_target.h) --------------------------------------------------------------
+// az_selfplay_get_search: the root value and the root's stored priors of the `count` tuples of the last az_selfplay / az_selfplay_next,
+// in their order ("selfplay_record_search" must have been 1 for that call)
+struct SearchRecord { std::vector<float> root_q, root_prior; };      // [count], [count][7]
+inline SearchRecord selfplay_search(const Engine& e, size_t count) {
+    if (!az_selfplay_get_search) throw Panic("selfplay_search: the linked engine library has no az_selfplay_get_search");
+    SearchRecord r{std::vector<float>(count), std::vector<float>(count * 7)};
+    e.check(az_selfplay_get_search(e.raw(), r.root_q.data(), r.root_prior.data()));
+    return r;
+}
+// az_samples_blend_z: (1 - lam) * zs + lam * root_q in f32; lam travels as lambda_e6
+inline std::vector<float> blend_z(const Engine& e, const std::vector<float>& zs, const std::vector<float>& root_q, double lam) {
+    if (!az_samples_blend_z) throw Panic("blend_z: the linked engine library has no az_samples_blend_z");
+    if (zs.size() != root_q.size()) throw Panic("blend_z: zs and root_q differ in length");
+    std::vector<float> out(zs.size());
+    e.check(az_samples_blend_z(e.raw(), (int64_t)zs.size(), zs.data(), root_q.data(), (int64_t)std::llround(lam * 1e6), out.data()));
+    return out;
+}
+// az_samples_surprise on n tuples given by states [n][2]: tuple i repeated counts[i] times, a share `share` of the weight in proportion to
+// KL(pi_i || prior_i).  The expanded set comes back in states / pis / zs
+struct Surprised { std::vector<uint64_t> states; std::vector<float> pis, zs, kl; std::vector<uint32_t> counts; };
+inline Surprised surprise(const Engine& e, const std::vector<uint64_t>& states, const std::vector<float>& pis, const std::vector<float>& zs,
+                          const std::vector<float>& priors, double share, uint64_t seed) {
+    if (!az_samples_surprise) throw Panic("surprise: the linked engine library has no az_samples_surprise");
+    const size_t n = zs.size();
+    if (states.size() != n * 2 || pis.size() != n * 7 || priors.size() != n * 7) throw Panic("surprise: the arrays differ in length");
+    Surprised r{std::vector<uint64_t>(4 * n), std::vector<float>(14 * n), std::vector<float>(2 * n), std::vector<float>(n), std::vector<uint32_t>(n)};
+    az_samples src{}, dst{};
+    src.capacity = src.count = (int64_t)n;
+    src.states = const_cast<uint64_t*>(states.data()); src.pis = const_cast<float*>(pis.data()); src.zs = const_cast<float*>(zs.data());
+    dst.capacity = (int64_t)(2 * n); dst.states = r.states.data(); dst.pis = r.pis.data(); dst.zs = r.zs.data();
+    e.check(az_samples_surprise(e.raw(), &src, priors.data(), (int64_t)std::llround(share * 1e6), seed, &dst, r.counts.data(), r.kl.data()));
+    const size_t m = (size_t)dst.count;
+    r.states.resize(2 * m); r.pis.resize(7 * m); r.zs.resize(m);
+    return r;
 }
 
 inline Ratings rating_fit(const std::vector<uint64_t>& wld, size_t K, double prior_games = 2.0) {
@@ -622,7 +666,11 @@ class Coach {
 
     // the self-play fan-out of src/coach.rs:241-272: num_eps x execute_episode, emitted with both symmetries
     HistoryEntry execute_episodes(size_t model_id, size_t iteration, uint64_t seed) {
-        if (world_ > 1 || use_comm_at_world_1) return execute_episodes_sharded(model_id, iteration, seed);
+        if (!(value_target_q >= 0.0 && value_target_q <= 1.0 && surprise_share >= 0.0 && surprise_share <= 1.0))
+            throw Panic("value_target_q and surprise_share must be in 0 .. 1");
+        if (surprise_share > 0 && world_ > 1) throw Panic("surprise_share needs a world of 1: the weights would be normalised per shard");
+        // the target options work on the compact (state, pi, z) tuples before the symmetries are expanded: the sharded path's shape
+        if (world_ > 1 || use_comm_at_world_1 || value_target_q > 0 || surprise_share > 0) return execute_episodes_sharded(model_id, iteration, seed);
         az_selfplay_params p{};
         p.n_games = (int32_t)num_eps; p.concurrent = (int32_t)std::min(num_episode_threads, num_eps);
         p.num_sims = (int32_t)num_sims; p.temp_threshold = (int32_t)temp_threshold; p.max_depth = (int32_t)max_depth;
@@ -656,14 +704,39 @@ class Coach {
             p.cpuct = cpuct; p.model_id = (int32_t)model_id; p.symmetries = 0; p.reserve = mcts_reserve_size; p.seed = seed;
             p.first_game_id = (uint64_t)(iteration * num_eps + lo);
             p.num_sim_threads = (int32_t)num_sim_threads;
-            e_.check(az_selfplay(e_.raw(), &p, &loc));
+            const bool targets = value_target_q > 0 || surprise_share > 0;
+            {
+                // the search record around the episodes only, as the other self-play options are
+                ScopedOption record_guard(targets, [&] { e_.set_record_search(true); }, [&] { e_.set_record_search(false); });
+                e_.check(az_selfplay(e_.raw(), &p, &loc));
+            }
+            if (targets) {                                            // this rank's own tuples, before any gather
+                const size_t k = (size_t)loc.count;
+                st.resize(k * 2); pi.resize(k * 7); z.resize(k);
+                const SearchRecord rec = selfplay_search(e_, k);
+                if (value_target_q > 0) z = blend_z(e_, z, rec.root_q, value_target_q);          // a blended z is still a z
+                if (surprise_share > 0) {                             // a resampled set is still a set of tuples
+                    Surprised sp = surprise(e_, st, pi, z, rec.root_prior, surprise_share, seed + (uint64_t)iteration);
+                    st.swap(sp.states); pi.swap(sp.pis); z.swap(sp.zs);
+                }
+                loc.count = (int64_t)z.size(); loc.capacity = loc.count;
+                if (z.empty()) { st.resize(2); pi.resize(7); z.resize(1); }
+                loc.states = st.data(); loc.pis = pi.data(); loc.zs = z.data();
+            }
         }
-        const size_t cap = num_eps * 42;
+        const size_t cap = std::max(num_eps * 42, (size_t)loc.count);      // (surprise_share holds at world 1 only: its at most 2x growth is all here)
         std::vector<uint64_t> gs(cap * 2);
         std::vector<float> gp(cap * 7), gz(cap);
         az_samples all{};
         all.capacity = (int64_t)cap; all.states = gs.data(); all.pis = gp.data(); all.zs = gz.data();
-        e_.check(az_gather_samples(e_.raw(), &loc, -1, &all, nullptr));
+        if (world_ > 1 || use_comm_at_world_1) e_.check(az_gather_samples(e_.raw(), &loc, -1, &all, nullptr));
+        else {                                                        // one rank and no communicator: its own tuples are all there are
+            const size_t k = (size_t)loc.count;
+            std::copy(st.begin(), st.begin() + (std::ptrdiff_t)(k * 2), gs.begin());
+            std::copy(pi.begin(), pi.begin() + (std::ptrdiff_t)(k * 7), gp.begin());
+            std::copy(z.begin(), z.begin() + (std::ptrdiff_t)k, gz.begin());
+            all.count = (int64_t)k;
+        }
         const size_t n = (size_t)all.count;
         HistoryEntry h;
         h.boards.assign(n * 2 * 84, 0.f); h.pis.resize(n * 2 * 7); h.vs.resize(n * 2);
@@ -903,6 +976,14 @@ class Coach {
     // and coach.state are those of a run without it.  0 (the default): the engine is never asked
     size_t solve_min_stones = 0;
     uint32_t solve_max_nodes = 1u << 20;
+    // Search statistics as targets (az_samples_blend_z / az_samples_surprise; csrc/az_target.h).  Either one sets "selfplay_record_search"
+    // before every az_selfplay and clears it behind it.  value_target_q (0 .. 1): right behind self-play the rank's own zs become
+    // (1 - q) * z + q * R, R the root value of the tuple's search -- before any gather, so the result does not depend on the world size.
+    // surprise_share (0 .. 1): the rank's own tuples are replaced by az_samples_surprise's resampling (seed = seed + iteration) -- before the
+    // gather and the symmetry expansion; refused with a world above 1 (the normalisation would be per shard).  History, the .examples
+    // files, the merge and the trainers see ordinary tuples; merge_positions + merge_weighted turn the duplicates back into draw weights.
+    // Both 0 (the default): the engine is never asked
+    double value_target_q = 0.0, surprise_share = 0.0;
     float update_threshold = 0.f;
     int32_t cpuct = 1;
 

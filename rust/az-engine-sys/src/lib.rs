@@ -135,9 +135,18 @@ extern "C" {
     /// ("playout_cap_sims" / "playout_cap_full_e6"; all plies when the playout cap is off)
     pub fn az_selfplay_get_full_plies(e: *mut az_engine, mask: *mut u64) -> c_int;
     pub fn az_selfplay_get_evals(e: *mut az_engine, rec_count: *mut i32, states: *mut u64, pis: *mut f32, vs: *mut f32) -> c_int;
+    /// rows of the last az_selfplay / az_selfplay_next in az_samples' order ("selfplay_record_search" = 1): root_q [count] the root value of
+    /// each tuple's search, root_prior [count,7] the root's stored priors as the search used them; host or device pointers, either may be null
+    pub fn az_selfplay_get_search(e: *mut az_engine, root_q: *mut f32, root_prior: *mut f32) -> c_int;
     /// position averaging: one tuple per distinct position of src (mean pi, mean z, first-occurrence order); flags bit 0 =
     /// AZ_MERGE_CANONICAL merges a position with its mirror image; dst.capacity >= src.count; counts [m] may be null
     pub fn az_samples_merge(e: *mut az_engine, src: *const az_samples, flags: i32, dst: *mut az_samples, counts: *mut u32) -> c_int;
+    /// z/q value target: zs_out[i] = (1 - lambda) zs[i] + lambda root_q[i] in f32, lambda = lambda_e6 / 1e6 in 0 .. 1000000; zs_out may be zs
+    pub fn az_samples_blend_z(e: *mut az_engine, n: i64, zs: *const f32, root_q: *const f32, lambda_e6: i64, zs_out: *mut f32) -> c_int;
+    /// surprise resampling: tuple i of src written counts[i] times into dst (capacity >= 2 src.count; may be null), a share share_e6 / 1e6 of
+    /// the weight in proportion to kl[i] = KL(pi_i || priors_i); priors [n,7]; counts [n] and kl [n] may be null
+    pub fn az_samples_surprise(e: *mut az_engine, src: *const az_samples, priors: *const f32, share_e6: i64, seed: u64,
+                               dst: *mut az_samples, counts: *mut u32, kl: *mut f32) -> c_int;
     /// exact endgame solver: every root action of n canonical positions; move_values [n,7] in {-1, 0, +1, AZ_SOLVE_ILLEGAL, AZ_SOLVE_UNKNOWN},
     /// values [n] and nodes [n,7] may be null; tt_log2 0 or 8..16, max_lanes 0 or a multiple of 64
     pub fn az_solve(e: *mut az_engine, states: *const u64, n: i32, max_nodes: u32, min_stones: i32, tt_log2: i32, max_lanes: i32,
