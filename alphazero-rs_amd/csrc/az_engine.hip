@@ -3608,6 +3608,18 @@ long long az_diag_fp8_skinny_launches(az_engine* e) {
     for (NetWorkspace* w : e->ws) n += (long long)netws_fp8_skinny_launches(w);
     return n;
 }
+// Diagnostic library only: the trainer's workspace after an az_net_train_step (az_train.h TrainDiagBuf: z, a, mean, invstd of a layer,
+// the heads' logits / dhead / per-sample losses, and -- from steps taken while keep is on -- every layer's d loss / d a and dz).  keep:
+// 0, or -1 refused (no training session yet, "train_fork" 1).  read: bytes copied, or -1 and nothing copied.
+int az_diag_train_keep(az_engine* e, int on) {
+    if (!e || !e->trainer || hipSetDevice(e->device) != hipSuccess) return -1;
+    if (on && e->train_fork) return -1;
+    return trainer_diag_set_keep(e->trainer, on != 0) ? 0 : -1;
+}
+long long az_diag_train_read(az_engine* e, int what, int layer, int rows, void* out) {
+    if (!e || !e->trainer || !out || hipSetDevice(e->device) != hipSuccess) return -1;
+    return trainer_diag_read(e->trainer, what, layer, rows, out, e->stream);
+}
 // Diagnostic library only (not part of the ABI): the children of the node reached from tree g's current root by following `path`
 // (child indices, not actions).  out rows of 8 u64: slot, a, ctr (resolved through a link), prior bits, link, meta, own ctr, key.
 // Returns the number of children, or -1.

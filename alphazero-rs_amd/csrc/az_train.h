@@ -88,4 +88,28 @@ void trainer_set_wgrad_tr(Trainer* t, bool on);   // true (default): conv wgrad 
 void trainer_set_implicit(Trainer* t, bool on);   // true (default): conv2..conv4's GEMMs gather their rows from the activations (no im2col / col2im)
 void trainer_set_gemm(Trainer* t, int mode);      // 1 (default): the GEMMs as bf16 x 3 on the bf16 matrix cores; 0: v_mfma_f32_16x16x4_f32
 
+// ---- the workspace reader of the per-kernel tests (tests/test_train_layers_gpu.py) ----------------------------------------------------
+// Called by the diagnostic library's az_diag_train_* exports only (az_engine.hip under AZ_DIAG): nothing in the shipped library reaches
+// these, so `keep` below is always off there and enqueue_step launches what it always launched.
+// What a step leaves in the workspace, per layer l = 0..5 (conv1..conv4, fc1, fc2) or per step:
+enum TrainDiagBuf {
+    TRAIN_DIAG_Z = 0,         // z[l]       [rows of l][N_l]  pre-BatchNorm
+    TRAIN_DIAG_A = 1,         // a[l]       [rows of l][N_l]  behind BatchNorm, ReLU and dropout
+    TRAIN_DIAG_MEAN = 2,      // mean[l]    [N_l]
+    TRAIN_DIAG_INVSTD = 3,    // invstd[l]  [N_l]
+    TRAIN_DIAG_LOGITS = 4,    // [b][8]: the seven logits, then v
+    TRAIN_DIAG_DHEAD = 5,     // [b][8]
+    TRAIN_DIAG_LOSS = 6,      // [b][2]: the sample's (loss_pi, loss_v)
+    TRAIN_DIAG_KEPT_DACT = 7, // d loss / d a[l] as it entered layer l's BatchNorm backward (kept steps only)
+    TRAIN_DIAG_KEPT_DZ = 8,   // d loss / d z[l] as it left it (kept steps only)
+};
+// While keep is on, a trainer_step copies the two backward tensors above into buffers of their own, per layer, device to device on the
+// step's stream (the scratch they live in is rewritten by the next layer).  trainer_run_epoch never keeps.  Refused (false) while the
+// fork is on; the buffers are allocated by the first call that switches keep on.
+bool trainer_diag_set_keep(Trainer* t, bool on);
+// Copies buffer `what` of layer `layer` for the first `rows` samples of the last step to the host -> bytes copied, or -1 with nothing
+// copied: no such buffer or layer, rows <= 0 or above the last step's batch, no step since trainer_set_params, a kept buffer when the
+// last step kept nothing.
+long long trainer_diag_read(Trainer* t, int what, int layer, int rows, void* out, hipStream_t s);
+
 }  // namespace az

@@ -1759,6 +1759,11 @@ struct Trainer {
     int64_t lr_table_cap = 0;
     std::vector<float> host_lr_table;
     float last_lr = 0.0f;              // lr_t of the last step
+    // the per-kernel tests' reader (trainer_diag_*; the diagnostic library only): with keep on, a trainer_step copies d loss / d a[l] and
+    // dz of every layer out of the shared backward scratch
+    bool keep = false;
+    float *keep_dact[6] = {nullptr}, *keep_dz[6] = {nullptr};
+    int last_b = 0, kept_b = 0;        // batch of the last step; of the last step if it kept its backward tensors, else 0
     template <class T> T* dalloc(size_t n) {
         void* p = nullptr;
         if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
@@ -1863,6 +1868,7 @@ bool trainer_set_params(Trainer* t, const float* host_params, int64_t count) {
     t->pow1 = t->pow2 = 1.0;
     t->optim = TrainOptim{};
     t->last_lr = 0.0f;
+    t->last_b = t->kept_b = 0;      // the reader answers from this session's steps only
     return true;
 }
 
@@ -2068,7 +2074,7 @@ namespace {
 
 // every kernel of one optimisation step, in order, on stream s (no host synchronisation: capturable in a hipGraph)
 void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const float* d_pis, const float* d_vs, int b, bool apply,
-                  hipStream_t s, bool col1_done = false) {
+                  hipStream_t s, bool col1_done = false, bool keep_bwd = false) {
     const int C = t->C;
     const Layout& L = t->L;
     float* P = t->params;
@@ -2206,6 +2212,8 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
         if (g3) { bn.out_hi = t->dz_hi; bn.out_lo = t->dz_lo; }
         const int parts = red_parts(d.M), rpb = (d.M + parts - 1) / parts;
         if (fork && l <= 4) (void)hipStreamWaitEvent(s, t->ev_tr[l + 1], 0);      // dz is rewritten: the layer above has transposed it
+        const size_t keep_bytes = (size_t)d.M * d.N * sizeof(float);
+        if (keep_bwd) (void)hipMemcpyAsync(t->keep_dact[l], t->dact, keep_bytes, hipMemcpyDeviceToDevice, s);
         if (d.M <= BN_SMALL_ROWS) {
             hipLaunchKernelGGL(k_bn_bwd_small, dim3(d.N / BN_COLS), dim3(256), 0, s, bn, G + d.bn, G + d.bn + d.N, st);
         } else {
@@ -2213,6 +2221,7 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
             hipLaunchKernelGGL(k_bn_bwd_apply, dim3(d.N / BN_COLS, (d.M + APPLY_ROWS - 1) / APPLY_ROWS), dim3(256), 0, s, bn, t->partial,
                                parts, APPLY_ROWS, G + d.bn, G + d.bn + d.N, st);
         }
+        if (keep_bwd) (void)hipMemcpyAsync(t->keep_dz[l], t->dz, keep_bytes, hipMemcpyDeviceToDevice, s);
         // The gradient of a bias in front of a BatchNorm is identically zero (the batch mean absorbs it); the kernels
         // leave those slots at 0 instead of the rounding residue a column sum of dz would give, which Adam would
         // turn into a random walk of size lr.
@@ -2299,7 +2308,10 @@ bool trainer_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
     st.pad_ = 0.0f;
     t->last_lr = st.lr_t;
     if (hipMemcpyAsync(t->step_state, &st, sizeof st, hipMemcpyHostToDevice, s) != hipSuccess) return false;
-    enqueue_step(t, h, d_boards, d_pis, d_vs, b, apply, s);
+    const bool keep = t->keep && !t->fork;      // the diagnostic reader's switch: never on in the shipped library
+    enqueue_step(t, h, d_boards, d_pis, d_vs, b, apply, s, false, keep);
+    t->last_b = b;
+    t->kept_b = keep ? b : 0;
     if (apply) { t->step += 1; t->pow1 = p1; t->pow2 = p2; }
     return hipGetLastError() == hipSuccess;
 }
@@ -2345,6 +2357,8 @@ static bool run_epoch(Trainer* t, const TrainHyper& h, const float* all_boards, 
     if (exec) (void)hipGraphExecDestroy(exec);
     if (graph) (void)hipGraphDestroy(graph);
     t->step += steps;
+    t->last_b = b;
+    t->kept_b = 0;
     if (sched) t->last_lr = t->host_lr_table[(size_t)((int64_t)gstep0 + steps - 1)];
     for (int64_t i = 0; i < steps; ++i) { t->pow1 *= (double)h.beta1; t->pow2 *= (double)h.beta2; }
     return ok;
@@ -2382,5 +2396,47 @@ void trainer_set_wgrad_tr(Trainer* t, bool on) { if (t) t->wgrad_tr = on; }
 void trainer_set_implicit(Trainer* t, bool on) { if (t) t->implicit = on; }
 void trainer_set_gemm3_ring(Trainer* t, bool on) { if (t) t->gemm3_ring = on; }
 void trainer_set_fwd_dma(Trainer* t, bool on) { if (t) t->fwd_dma = on; }
+
+// ---- the per-kernel tests' reader (az_train.h) ---------------------------------------------------------------------------------------
+bool trainer_diag_set_keep(Trainer* t, bool on) {
+    if (!t) return false;
+    if (!on) { t->keep = false; return true; }
+    if (t->fork) return false;
+    const size_t B = TRAIN_MAX_BATCH, C = (size_t)t->C;
+    const size_t n[6] = {B * 42 * C, B * 42 * C, B * 20 * C, B * 6 * C, B * 1024, B * 512};
+    for (int l = 0; l < 6; ++l)
+        for (float** q : {&t->keep_dact[l], &t->keep_dz[l]})
+            if (!*q && !(*q = t->dalloc<float>(n[l]))) return false;
+    t->keep = true;
+    return true;
+}
+
+long long trainer_diag_read(Trainer* t, int what, int layer, int rows, void* out, hipStream_t s) {
+    if (!t || !out || t->last_b <= 0 || rows <= 0 || rows > t->last_b) return -1;
+    const size_t per[6] = {42, 42, 20, 6, 1, 1}, nout[6] = {(size_t)t->C, (size_t)t->C, (size_t)t->C, (size_t)t->C, 1024, 512};
+    const bool layered = what != TRAIN_DIAG_LOGITS && what != TRAIN_DIAG_DHEAD && what != TRAIN_DIAG_LOSS;
+    if (layered && (layer < 0 || layer > 5)) return -1;
+    const float* src = nullptr;
+    size_t count = 0;
+    switch (what) {
+    case TRAIN_DIAG_Z: src = t->z[layer]; count = (size_t)rows * per[layer] * nout[layer]; break;
+    case TRAIN_DIAG_A: src = t->a[layer]; count = (size_t)rows * per[layer] * nout[layer]; break;
+    case TRAIN_DIAG_MEAN: src = t->mean[layer]; count = nout[layer]; break;
+    case TRAIN_DIAG_INVSTD: src = t->invstd[layer]; count = nout[layer]; break;
+    case TRAIN_DIAG_LOGITS: src = t->logits; count = (size_t)rows * 8; break;
+    case TRAIN_DIAG_DHEAD: src = t->dhead; count = (size_t)rows * 8; break;
+    case TRAIN_DIAG_LOSS: src = t->sample_loss; count = (size_t)rows * 2; break;
+    case TRAIN_DIAG_KEPT_DACT:
+    case TRAIN_DIAG_KEPT_DZ:
+        if (t->kept_b <= 0 || rows > t->kept_b) return -1;
+        src = what == TRAIN_DIAG_KEPT_DACT ? t->keep_dact[layer] : t->keep_dz[layer];
+        count = (size_t)rows * per[layer] * nout[layer];
+        break;
+    default: return -1;
+    }
+    if (!src || hipStreamSynchronize(s) != hipSuccess) return -1;
+    if (hipMemcpy(out, src, count * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (long long)(count * sizeof(float));
+}
 
 }  // namespace az
