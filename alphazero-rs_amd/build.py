@@ -16,7 +16,7 @@ LIB = os.path.join(PKG_DIR, "libaz_engine.so")
 # tiles and clock-stamp builds (every one bit-identical to the shipped kernels).  tools/ and the kernel-family bit-identity tests
 # load it (engine.Engine(diag=True)); the shipped library above does not contain any of it and refuses those option values.
 LIB_DIAG = os.path.join(PKG_DIR, "libaz_engine_diag.so")
-SOURCES = ["az_tree.hip", "az_net.hip", "az_train.hip", "az_merge.hip", "az_draw.hip", "az_target.hip", "az_solve.hip", "az_engine.hip"]
+SOURCES = ["az_tree.hip", "az_net.hip", "az_train.hip", "az_merge.hip", "az_draw.hip", "az_target.hip", "az_score.hip", "az_solve.hip", "az_engine.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall",
          "-Wno-unused-result"]
 
@@ -46,7 +46,7 @@ def _build(LIB, suffix, extra_flags, force, verbose):
         return LIB
     objs, procs = [], []
     for src in SOURCES:
-        if suffix and src in ("az_train.hip", "az_merge.hip", "az_draw.hip", "az_target.hip", "az_solve.hip"):      # no diagnostic code in these: one object serves both libraries
+        if suffix and src in ("az_train.hip", "az_merge.hip", "az_draw.hip", "az_target.hip", "az_score.hip", "az_solve.hip"):      # no diagnostic code in these: one object serves both libraries
             objs.append(os.path.join(CSRC, src.replace(".hip", ".o")))
             continue
         s = os.path.join(CSRC, src)

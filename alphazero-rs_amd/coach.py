@@ -108,6 +108,14 @@ class Coach:
         # and the trainers see ordinary tuples; merge_positions + merge_weighted turn the duplicates back into draw weights.  Both 0 (the
         # default): the engine is never asked
         self.value_target_q, self.surprise_share = 0.0, 0.0
+        # Held-out validation (Engine.samples_holdout / train_set_validation; csrc/az_score.h).  validation_share (0 .. 1): every iteration
+        # the assembled window is split by the hold-out rule BEFORE merge and shuffle, with learn()'s constant seed -- a function of the
+        # position alone, so a position (and its mirror image) is on the same side in every iteration; the rest is trained on, the held-out
+        # part is registered raw and scored at the end of every epoch.  The report gains val_n, val_loss_pi, val_loss_v, val_top1 (one
+        # entry per epoch) and best_epoch.  keep_best stores the best epoch's weights, patience > 0 stops after that many epochs without a
+        # new best ("train_keep_best", "train_patience").  `history` and the .examples files keep every tuple.  The engine's trainer only.
+        # 0 (the default): the engine is never asked and reports and files are what they were
+        self.validation_share, self.keep_best, self.patience = 0.0, False, 0
         self.history = collections.deque()
         self.start_iteration = 0
         os.makedirs(self.dir, exist_ok=True)
@@ -176,6 +184,17 @@ class Coach:
         return self._scoped(on, lambda: self.engine.set_train_optim(self.weight_decay, self.clip_norm, self.lr_warmup_steps, self.lr_decay,
                                                                     self.lr_floor, self.ema_decay),
                             lambda: self.engine.set_train_optim())
+
+    def _train_validation(self, active):
+        def apply():
+            self.engine.set_option("train_keep_best", 1 if self.keep_best else 0)
+            self.engine.set_option("train_patience", int(self.patience))
+
+        def clear():
+            self.engine.set_option("train_keep_best", 0)
+            self.engine.set_option("train_patience", 0)
+            self.engine.train_set_validation()
+        return self._scoped(active, apply, clear)
 
     def _arena_openings(self):
         return self._scoped(self.arena_opening_plies > 0, lambda: self.engine.set_arena_openings(self.arena_opening_plies),
@@ -266,6 +285,21 @@ class Coach:
             allv = np.concatenate([h[2] for h in self.history])
             assert allv.shape[0] > 0                                    # :305
             samples_raw = int(allv.shape[0])
+            val_n = 0
+            if self.validation_share > 0:                               # the split: before merge and shuffle, by the position alone
+                if not 0.0 < self.validation_share < 1.0:
+                    raise ValueError("validation_share must be in 0 .. 1 (exclusive)")
+                if self.trainer is not None:
+                    raise ValueError("validation_share needs the engine's trainer")
+                held = np.asarray(self.engine.samples_holdout(self.validation_share, seed, allp, allv, boards=allb), bool)
+                val_n = int(held.sum())
+                if val_n == samples_raw:
+                    raise ValueError("validation_share holds the whole window out")
+                if val_n > 0:
+                    self.engine.train_set_validation(allp[held], allv[held], boards=allb[held])
+                    allb, allp, allv = allb[~held], allp[~held], allv[~held]
+            elif self.keep_best or self.patience:
+                raise ValueError("keep_best and patience need validation_share > 0")
             t_merge = None
             if self.merge_weighted and not self.merge_positions:
                 raise ValueError("merge_weighted requires merge_positions")
@@ -287,12 +321,14 @@ class Coach:
             t0 = time.perf_counter()
             if self.trainer is None:                                    # :329 -> NNet::train(samples, id, id + 1)
                 self.engine.set_option("train_seed", seed + iteration)
-                with self._train_optim():
+                with self._train_optim(), self._train_validation(val_n > 0):
                     if weighted:
                         losses = self.engine.train_samples(model_id, model_id + 1, allp, allv, states=allb, weights=mult,
                                                            mirror=self.merge_canonical)
                     else:
                         losses = self.engine.train(model_id, model_id + 1, allb, allp, allv)
+                    if self.validation_share > 0:
+                        val_rows, val_best = self.engine.train_validation() if val_n > 0 else ([], -1)
                 if self.ema_decay > 0:                                  # the candidate is the averaged model
                     self.engine.train_ema(model_id + 1)
             else:
@@ -367,6 +403,9 @@ class Coach:
                 report[-1]["seconds"]["merge"] = t_merge
             if weighted:
                 report[-1]["samples_weight"] = samples_weight
+            if self.validation_share > 0:
+                report[-1].update({"val_n": val_n, "val_loss_pi": [r[0] for r in val_rows], "val_loss_v": [r[1] for r in val_rows],
+                                   "val_top1": [r[3] for r in val_rows], "best_epoch": val_best})
             if quality is not None:
                 report[-1]["quality"] = quality
                 report[-1]["seconds"]["quality"] = t_quality

@@ -26,6 +26,7 @@
 #include "az_merge.h"
 #include "az_net.h"
 #include "az_optim.h"
+#include "az_score.h"
 #include "az_solve.h"
 #include "az_target.h"
 #include "az_rating.h"
@@ -410,6 +411,17 @@ struct az_engine {
     int64_t train_weight_decay_e9 = 0, train_clip_norm_e6 = 0, train_lr_warmup_steps = 0, train_lr_decay = 0, train_lr_floor_e6 = 0,
             train_lr_total_steps = 0, train_ema_decay_e9 = 0;
     bool train_ema_session = false;                // the last az_net_train_begin saw "train_ema_decay_e9" > 0
+    // per-epoch validation of az_net_train / az_net_train_samples (az_net_train_set_validation; csrc/az_score.h): the
+    // registered set on the device (validated states, pis, zs, weights or nullptr), the model slot no id names, the last run's history
+    DeviceMem val_mem;
+    int64_t val_n = 0;
+    ulonglong2* val_states = nullptr;
+    float *val_pis = nullptr, *val_zs = nullptr;
+    uint32_t* val_weights = nullptr;
+    NetModel val_model;
+    int64_t train_keep_best = 0, train_patience = 0;       // "train_keep_best", "train_patience"
+    std::vector<double> val_history;               // (loss_pi, loss_v, kl, top1) per epoch of the last az_net_train / az_net_train_samples
+    int val_best = -1;
     // leaf de-duplication + evaluation cache (az_set_option "eval_dedup", "eval_cache_log2", "eval_cache_max_stones",
     // "eval_cache_persist")
     int profile_every = 1;          // profile mode: bracket every n-th simulation step ("profile_every")
@@ -468,6 +480,7 @@ struct az_engine {
         }
         ~Scratch() { if (p) (void)hipFree(p); }
     } comm_scratch;
+    Scratch score_scratch;          // workspace of az_net_evaluate / az_samples_holdout and of the per-epoch validation; follows merge_scratch's rule
     Scratch target_scratch;         // workspace of az_samples_blend_z / az_samples_surprise; follows merge_scratch's rule
     Scratch merge_scratch;          // workspace of az_samples_merge: sized by the call, kept for later calls of the same or a smaller size, given back
                                     // when a call needs under a quarter of a workspace of more than 256 MiB (a 2^24-tuple call holds over 10 GB)
@@ -1080,6 +1093,7 @@ void az_destroy(az_engine* e) {
     (void)hipStreamSynchronize(e->stream);
     (void)az_selfplay_end(e);
     for (auto& kv : e->nets) if (kv.second.conv) convnet_destroy(kv.second.conv);
+    if (e->val_model.conv) convnet_destroy(e->val_model.conv);
     for (NetWorkspace* w : e->ws) netws_destroy(w);
     if (e->cache_keys) (void)hipFree(e->cache_keys);
     if (e->cache_pv) (void)hipFree(e->cache_pv);
@@ -1205,6 +1219,13 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     if (is("train_fwd_dma") && (value == 0 || value == 1)) { e->train_fwd_dma = (int)value; if (e->trainer) trainer_set_fwd_dma(e->trainer, value != 0); return AZ_OK; }
     if (is("train_lr_e9") && value > 0) { e->hyper.lr = (float)((double)value * 1e-9); return AZ_OK; }
     if (is("train_dropout_e6") && value >= 0 && value < 1000000) { e->hyper.dropout = (float)((double)value * 1e-6); return AZ_OK; }
+    // per-epoch validation (csrc/az_score.h): read when az_net_train / az_net_train_samples begin
+    if (is("train_keep_best") && (value == 0 || value == 1)) { e->train_keep_best = value; return AZ_OK; }
+    if (is("train_patience")) {
+        if (value < 0 || value > SCORE_MAX_PATIENCE) return fail(e, AZ_ERR_BAD_ARGUMENT, "train_patience must be in 0 .. 1000");
+        e->train_patience = value;
+        return AZ_OK;
+    }
     // the opt-in optimiser rules (csrc/az_optim.h): one range per key, read by the next az_net_train_begin
     struct OptimKey { const char* key; int64_t lo, hi; bool or_zero; int64_t az_engine::* field; const char* range; };
     static const OptimKey optim_keys[] = {
@@ -1534,6 +1555,304 @@ az_status az_net_predict(az_engine* e, int32_t model_id, const float* boards, in
     } catch (const HipFail& f) { return fail_hip(e, f); }
 }
 
+// ---- held-out loss on the device and the hold-out mask (csrc/az_score.h, DESIGN.md sections 4.1l and 8.3) ----------------------------------
+}  // extern "C"
+
+namespace {
+
+struct ScoreSet {               // a window on the device: validated states, targets, weights (nullptr = all ones)
+    int64_t n;
+    const ulonglong2* states;
+    const float* pis;
+    const float* zs;
+    const uint32_t* weights;
+};
+struct ScoreOut { float* ce; float* se; float* kl; };        // device, each [n] or nullptr
+inline size_t score_pad(size_t bytes) { return (bytes + 255) / 256 * 256; }
+// the part of the workspace a run of forwards needs: [row counts] [chunk states] [chunk pi] [chunk v] [mirror flags]
+size_t score_work_bytes(const az_engine* e) {
+    const size_t c = (size_t)e->cfg.max_batch;
+    return 256 + score_pad(c * 16) + score_pad(c * 32) + score_pad(c * 4) + score_pad(c);
+}
+// Enqueues, on the engine's stream, the forward of every max_batch chunk of the window and the score kernel behind it: what
+// az_net_predict_states runs per chunk, with (pi, v) read where the forward left them.  No synchronisation, no copy to the host.
+void score_enqueue(az_engine* e, const NetModel& m, char* work, const ScoreSet& w, uint64_t* d_sums, const ScoreOut& o) {
+    hipStream_t s = e->stream;
+    const int chunk = e->cfg.max_batch;
+    const size_t c = (size_t)chunk;
+    uint32_t* d_rows = (uint32_t*)work;                     // [0] a full chunk, [1] the last one
+    EvalBatch eb{};
+    eb.cap = chunk;
+    eb.state = (ulonglong2*)(work + 256);
+    eb.pi = (float*)(work + 256 + score_pad(c * 16));
+    eb.v = (float*)(work + 256 + score_pad(c * 16) + score_pad(c * 32));
+    uint8_t* mflags = mirror_applies(e, m) ? (uint8_t*)(work + 256 + score_pad(c * 16) + score_pad(c * 32) + score_pad(c * 4)) : nullptr;
+    const int64_t chunks = (w.n + chunk - 1) / chunk;
+    const uint32_t h_rows[2] = {(uint32_t)chunk, (uint32_t)(w.n - (chunks - 1) * chunk)};
+    HIPCHK(hipMemcpy(d_rows, h_rows, sizeof h_rows, hipMemcpyHostToDevice));
+    for (int64_t k = 0; k < chunks; ++k) {
+        const bool last = k + 1 == chunks;
+        const int nb = (int)h_rows[last ? 1 : 0];
+        eb.n = d_rows + (last ? 1 : 0);
+        HIPCHK(hipMemcpyAsync(eb.state, w.states + (size_t)k * c, (size_t)nb * 16, hipMemcpyDeviceToDevice, s));
+        if (mflags) launch_canonicalise(eb.state, mflags, nb, s);
+        net_forward(e, m, eb, nb, s);
+        if (mflags) launch_unmirror_rows(eb.pi, mflags, nb, s);
+        launch_score(eb.pi, eb.v, w.states, w.pis, w.zs, w.weights, k * (int64_t)chunk, nb, d_sums, o.ce, o.se, o.kl, s);
+    }
+    HIPCHK(hipGetLastError());
+}
+const char* score_bad_text(uint32_t bad) {
+    if (bad & SCORE_BAD_FEATURE) return "a boards feature that is not 0 or 1, or a cell set in both planes";
+    if (bad & SCORE_BAD_STATE) return "a state with overlapping stones or bits outside the 7x6 board";
+    if (bad & SCORE_BAD_VALUE) return "a pi that is NaN or outside [0, 1], or a z that is NaN or outside [-1, 1]";
+    return nullptr;
+}
+const char* score_sum_text(const uint64_t* sums) {
+    if (sums[4] == 0) return "the weights sum to 0";
+    if (sums[4] > SCORE_MAX_WEIGHT) return "the weights sum to more than 2^24";
+    return nullptr;
+}
+// out[0 .. 4) = loss_pi, loss_v, kl, top1 from the integers
+void score_results(const uint64_t* sums, double* out) {
+    const double W = (double)sums[4], one = 1073741824.0;
+    out[0] = (double)sums[0] / one / W;
+    out[1] = (double)sums[2] / one / W;
+    out[2] = (double)sums[1] / one / W;
+    out[3] = (double)sums[3] / W;
+}
+
+}  // namespace
+
+extern "C" {
+
+az_status az_net_evaluate(az_engine* e, int32_t model_id, const az_samples* smp, const uint32_t* weights, double* score, uint64_t* sums_out, float* ce,
+                          float* se, float* kl) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!smp || !score) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_evaluate: the samples and score are required");
+    const int64_t n = smp->count;
+    if (n < 1 || n > SCORE_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_evaluate: 1 .. 2^24 tuples");
+    if (!smp->pis || !smp->zs || (!smp->states && !smp->boards)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_evaluate: the samples need pis, zs and states or boards");
+    NetModel* m;
+    az_status st = find_net(e, model_id, &m);
+    if (st) return st;
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t N = (size_t)n;
+        const bool from_boards = !smp->states;
+        size_t total = 0;
+        auto need = [&](size_t bytes) { const size_t off = total; total += score_pad(bytes); return off; };
+        // [hdr: verdict, sums] [inputs] [validated states] [per-tuple outputs] [the forwards' part]
+        const size_t o_hdr = need(256), o_in = need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_st = need(N * 16), o_pi = need(N * 28), o_z = need(N * 4),
+                     o_w = need(weights ? N * 4 : 0), o_ce = need(ce ? N * 4 : 0), o_se = need(se ? N * 4 : 0), o_kl = need(kl ? N * 4 : 0),
+                     o_work = need(score_work_bytes(e));
+        if (e->score_scratch.cap > ((size_t)1 << 28) && e->score_scratch.cap / 4 > total) e->score_scratch.release(s);
+        char* base = (char*)e->score_scratch.ensure(total, s);
+        uint32_t* d_bad = (uint32_t*)(base + o_hdr);
+        uint64_t* d_sums = (uint64_t*)(base + o_hdr + 8);
+        // the whole window is staged once
+        HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
+        HIPCHK(hipMemcpyAsync(base + o_in, from_boards ? (const void*)smp->boards : (const void*)smp->states, from_boards ? N * AZ_FEATURES * 4 : N * 16,
+                              hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_pi, smp->pis, N * 28, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_z, smp->zs, N * 4, hipMemcpyDefault, s));
+        if (weights) HIPCHK(hipMemcpyAsync(base + o_w, weights, N * 4, hipMemcpyDefault, s));
+        launch_score_states(from_boards ? nullptr : (const ulonglong2*)(base + o_in), from_boards ? (const float*)(base + o_in) : nullptr,
+                            (const float*)(base + o_pi), (const float*)(base + o_z), 1, n, (ulonglong2*)(base + o_st), d_bad, s);
+        const ScoreSet w{n, (const ulonglong2*)(base + o_st), (const float*)(base + o_pi), (const float*)(base + o_z),
+                         weights ? (const uint32_t*)(base + o_w) : nullptr};
+        const ScoreOut o{ce ? (float*)(base + o_ce) : nullptr, se ? (float*)(base + o_se) : nullptr, kl ? (float*)(base + o_kl) : nullptr};
+        score_enqueue(e, *m, base + o_work, w, d_sums, o);
+        uint64_t hdr[1 + SCORE_SUMS] = {0, 0, 0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(hdr, base + o_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));                    // the one synchronisation
+        resolve_profile(e);
+        if (const char* why = score_bad_text((uint32_t)hdr[0])) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_evaluate: ") + why);
+        if (const char* why = score_sum_text(hdr + 1)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_evaluate: ") + why);
+        score[0] = (double)n;
+        score[1] = (double)hdr[1 + 4];
+        score_results(hdr + 1, score + 2);
+        if (sums_out) std::memcpy(sums_out, hdr + 1, SCORE_SUMS * sizeof(uint64_t));
+        if (ce || se || kl) {                               // a refused call leaves the caller's arrays unwritten
+            if (ce) HIPCHK(hipMemcpyAsync(ce, base + o_ce, N * 4, hipMemcpyDefault, s));
+            if (se) HIPCHK(hipMemcpyAsync(se, base + o_se, N * 4, hipMemcpyDefault, s));
+            if (kl) HIPCHK(hipMemcpyAsync(kl, base + o_kl, N * 4, hipMemcpyDefault, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+az_status az_samples_holdout(az_engine* e, const az_samples* smp, int64_t share_e6, uint64_t seed, uint8_t* held) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (!smp || !held) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: the samples and held are required");
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: a self-play session is open");
+    if (share_e6 < 0 || share_e6 > TARGET_E6) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: share_e6 must be in 0 .. 1000000");
+    const int64_t n = smp->count;
+    if (n < 0 || n > SCORE_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: 0 .. 2^24 tuples");
+    if (n == 0) return AZ_OK;
+    if (!smp->pis || !smp->zs || (!smp->states && !smp->boards)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: the samples need pis, zs and states or boards");
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t N = (size_t)n;
+        const bool from_boards = !smp->states;
+        size_t total = 0;
+        auto need = [&](size_t bytes) { const size_t off = total; total += score_pad(bytes); return off; };
+        const size_t o_hdr = need(256), o_in = need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_st = need(N * 16), o_pi = need(N * 28), o_z = need(N * 4),
+                     o_held = need(N);
+        if (e->score_scratch.cap > ((size_t)1 << 28) && e->score_scratch.cap / 4 > total) e->score_scratch.release(s);
+        char* base = (char*)e->score_scratch.ensure(total, s);
+        uint32_t* d_bad = (uint32_t*)(base + o_hdr);
+        HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
+        HIPCHK(hipMemcpyAsync(base + o_in, from_boards ? (const void*)smp->boards : (const void*)smp->states, from_boards ? N * AZ_FEATURES * 4 : N * 16,
+                              hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_pi, smp->pis, N * 28, hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(base + o_z, smp->zs, N * 4, hipMemcpyDefault, s));
+        launch_score_states(from_boards ? nullptr : (const ulonglong2*)(base + o_in), from_boards ? (const float*)(base + o_in) : nullptr,
+                            (const float*)(base + o_pi), (const float*)(base + o_z), 0, n, (ulonglong2*)(base + o_st), d_bad, s);
+        launch_score_holdout((const ulonglong2*)(base + o_st), n, seed, score_thresh24((uint64_t)share_e6), (uint8_t*)(base + o_held), s);
+        uint32_t bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipGetLastError());
+        if (bad & SCORE_BAD_VALUE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: a pi or z that is NaN or outside [-1, 1]");
+        if (const char* why = score_bad_text(bad)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_samples_holdout: ") + why);
+        HIPCHK(hipMemcpy(held, base + o_held, N, hipMemcpyDefault));
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// ---- per-epoch validation of az_net_train / az_net_train_samples (csrc/az_score.h) -----------------------------------
+}  // extern "C"
+
+namespace {
+
+// what az_net_train and az_net_train_samples refuse before they begin
+const char* validation_arg_error(const az_engine* e) {
+    if ((e->train_keep_best || e->train_patience) && e->val_n == 0) return "\"train_keep_best\" and \"train_patience\" need a validation set (az_net_train_set_validation)";
+    return nullptr;
+}
+// One epoch's row of the validation history: the trainer's live parameters and moving averages (what az_net_train_end would store now) go
+// into the slot no id names, in the effective class of `model_id` (a fresh id: the engine's), and are scored on the registered set.  Reads
+// the trainer, writes nothing of it.  *stop = the patience rule's verdict; with "train_keep_best" `best_params` follows the best epoch.
+az_status validate_epoch(az_engine* e, int32_t model_id, std::vector<float>& params, std::vector<float>& best_params, bool* stop) {
+    *stop = false;
+    if (e->val_n == 0) return AZ_OK;
+    const int64_t n = az_net_param_count(e);
+    params.resize((size_t)n);
+    if (!trainer_get_params(e->trainer, params.data(), n, e->stream)) return fail(e, AZ_ERR_HIP, "trainer_get_params failed");
+    NetModel& m = e->val_model;
+    if (!m.conv) {
+        const char* why = nullptr;
+        m.conv = convnet_create(e->cfg.net_channels, &why);
+        if (!m.conv) return fail(e, AZ_ERR_HIP, why ? why : "convnet_create failed");
+    }
+    if (!convnet_set_params(m.conv, params.data(), n)) return fail(e, AZ_ERR_HIP, "convnet_set_params failed");
+    m.kind = AZ_NET_CONV;
+    const auto dst = e->nets.find(model_id);
+    m.klass = dst != e->nets.end() && dst->second.kind == AZ_NET_CONV ? dst->second.klass : AZ_NET_CLASS_ENGINE;
+    if (az_status st = fp8_sync_model(e, m)) return st;
+    hipStream_t s = e->stream;
+    const size_t total = 256 + score_work_bytes(e);
+    char* base = (char*)e->score_scratch.ensure(total, s);
+    uint64_t* d_sums = (uint64_t*)(base + 8);
+    HIPCHK(hipMemsetAsync(base, 0, 256, s));
+    const ScoreSet w{e->val_n, e->val_states, e->val_pis, e->val_zs, e->val_weights};
+    score_enqueue(e, m, base + 256, w, d_sums, ScoreOut{nullptr, nullptr, nullptr});
+    uint64_t sums[SCORE_SUMS];
+    HIPCHK(hipMemcpyAsync(sums, d_sums, sizeof sums, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    double row[4];
+    score_results(sums, row);
+    e->val_history.insert(e->val_history.end(), row, row + 4);
+    const int epochs = (int)(e->val_history.size() / 4);
+    int best = 0;
+    *stop = score_best_stop(e->val_history.data(), 4, epochs, (int)e->train_patience, &best);
+    e->val_best = best;
+    if (e->train_keep_best && best == epochs - 1) best_params = params;
+    return AZ_OK;
+}
+// az_net_train_end, storing the best epoch's parameters where "train_keep_best" kept some
+az_status train_store(az_engine* e, int32_t model_id, const std::vector<float>& best_params) {
+    if (!e->train_keep_best || best_params.empty()) return az_net_train_end(e, model_id);
+    e->train_open = false;
+    return az_net_set_params(e, model_id, best_params.data(), (int64_t)best_params.size());
+}
+
+}  // namespace
+
+extern "C" {
+
+az_status az_net_train_set_validation(az_engine* e, const az_samples* v, const uint32_t* weights) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (e->train_open) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_set_validation: a training session is open");
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        if (!v) {
+            HIPCHK(hipStreamSynchronize(s));
+            e->val_mem.release();
+            e->val_n = 0;
+            e->val_states = nullptr; e->val_pis = nullptr; e->val_zs = nullptr; e->val_weights = nullptr;
+            return AZ_OK;
+        }
+        const int64_t n = v->count;
+        if (n < 1 || n > SCORE_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_set_validation: 1 .. 2^24 tuples");
+        if (!v->pis || !v->zs || (!v->states && !v->boards)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_set_validation: the samples need pis, zs and states or boards");
+        const size_t N = (size_t)n;
+        uint64_t W = (uint64_t)n;
+        if (weights) {
+            std::vector<uint32_t> hw(N);
+            HIPCHK(hipMemcpy(hw.data(), weights, N * 4, hipMemcpyDefault));
+            W = 0;
+            for (uint32_t x : hw) W += x;
+        }
+        if (W == 0 || W > SCORE_MAX_WEIGHT) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_set_validation: the weights must sum to 1 .. 2^24");
+        // the new set is built beside the old one, which a refusal leaves registered
+        DeviceMem mem;
+        const bool from_boards = !v->states;
+        ulonglong2* d_st = mem.alloc<ulonglong2>(N);
+        float* d_pi = mem.alloc<float>(N * 7);
+        float* d_z = mem.alloc<float>(N);
+        uint32_t* d_w = weights ? mem.alloc<uint32_t>(N) : nullptr;
+        uint32_t* d_bad = mem.alloc<uint32_t>(1);
+        {
+            DeviceMem in;
+            void* d_in = from_boards ? (void*)in.alloc<float>(N * AZ_FEATURES) : (void*)in.alloc<ulonglong2>(N);
+            HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), s));
+            HIPCHK(hipMemcpyAsync(d_in, from_boards ? (const void*)v->boards : (const void*)v->states, from_boards ? N * AZ_FEATURES * 4 : N * 16, hipMemcpyDefault, s));
+            HIPCHK(hipMemcpyAsync(d_pi, v->pis, N * 28, hipMemcpyDefault, s));
+            HIPCHK(hipMemcpyAsync(d_z, v->zs, N * 4, hipMemcpyDefault, s));
+            if (d_w) HIPCHK(hipMemcpyAsync(d_w, weights, N * 4, hipMemcpyDefault, s));
+            launch_score_states(from_boards ? nullptr : (const ulonglong2*)d_in, from_boards ? (const float*)d_in : nullptr, d_pi, d_z, 1, n, d_st, d_bad, s);
+            uint32_t bad = 0;
+            HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipGetLastError());
+            if (const char* why = score_bad_text(bad)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_train_set_validation: ") + why);
+        }
+        e->val_mem.release();
+        std::swap(e->val_mem.ptrs, mem.ptrs);
+        e->val_n = n;
+        e->val_states = d_st; e->val_pis = d_pi; e->val_zs = d_z; e->val_weights = d_w;
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+int32_t az_net_train_validation(const az_engine* e, double* out, int32_t cap_epochs, int32_t* best_epoch) {
+    if (!e) return 0;
+    const int32_t epochs = (int32_t)(e->val_history.size() / 4);
+    if (out)
+        for (int32_t i = 0; i < std::min(epochs, cap_epochs); ++i)
+            for (int j = 0; j < 4; ++j) out[4 * i + j] = e->val_history[(size_t)4 * i + j];
+    if (best_epoch) *best_epoch = epochs ? e->val_best : -1;
+    return epochs;
+}
+
 // ---- NNet::train, src/nnet.rs:38 ----------------------------------------------------------------
 az_status az_net_train_begin(az_engine* e, int32_t previous_model_id) {
     if (!e) return AZ_ERR_BAD_ARGUMENT;
@@ -1612,9 +1931,11 @@ az_status az_net_train_end(az_engine* e, int32_t model_id) {
 az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id, const float* boards, const float* pis,
                        const float* vs, int64_t n) {
     if (!e || !boards || !pis || !vs || n <= 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train: bad argument");
+    if (const char* why = validation_arg_error(e)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_net_train: ") + why).c_str());
     az_status st = az_net_train_begin(e, previous_model_id);
     if (st) return st;
     ScopedTimer timer{e};
+    std::vector<float> val_params, best_params;
     try {
         DeviceMem mem;
         float* d_boards = mem.alloc<float>((size_t)n * 84);
@@ -1629,6 +1950,8 @@ az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id
         std::vector<int64_t> idx((size_t)steps * b);
         Trainer* t = e->trainer;
         e->train_history.clear();
+        e->val_history.clear();
+        e->val_best = -1;
         if (!trainer_set_lr_table(t, e->hyper, (int64_t)e->train_epochs * steps, e->stream)) return fail(e, AZ_ERR_HIP, "trainer_set_lr_table failed");
         uint64_t gstep = 0;
         for (int epoch = 0; epoch < e->train_epochs; ++epoch) {
@@ -1647,10 +1970,13 @@ az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id
             if (!trainer_read_losses(t, l, true, e->stream)) return fail(e, AZ_ERR_HIP, "trainer_read_losses failed");
             e->train_history.push_back((float)(l[0] / (double)steps));
             e->train_history.push_back((float)(l[1] / (double)steps));
+            bool stop = false;
+            if (az_status vst = validate_epoch(e, model_id, val_params, best_params, &stop)) { e->train_open = false; return vst; }
+            if (stop) break;
         }
         HIPCHK(hipStreamSynchronize(e->stream));
     } catch (const HipFail& f) { e->train_open = false; return fail_hip(e, f); }
-    return az_net_train_end(e, model_id);
+    return train_store(e, model_id, best_params);
 }
 
 // ---- NNet::train from an az_samples, rows drawn in proportion to their multiplicities (csrc/az_draw.h) ---------------
@@ -1722,7 +2048,9 @@ az_status az_net_train_samples(az_engine* e, int32_t previous_model_id, int32_t 
     if (const char* why = draw_arg_error(e, n, flags)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_net_train_samples: ") + why).c_str());
     if (!s->pis || !s->zs || (!s->states && !s->boards))
         return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_samples: the samples need pis, zs and states or boards");
+    if (const char* why = validation_arg_error(e)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_net_train_samples: ") + why).c_str());
     ScopedTimer timer{e};
+    std::vector<float> val_params, best_params;
     try {
         HIPCHK(hipSetDevice(e->device));
         DeviceMem mem;
@@ -1764,6 +2092,8 @@ az_status az_net_train_samples(az_engine* e, int32_t previous_model_id, int32_t 
         try {
             Trainer* t = e->trainer;
             e->train_history.clear();
+            e->val_history.clear();
+            e->val_best = -1;
             if (!trainer_set_lr_table(t, e->hyper, (int64_t)e->train_epochs * steps, e->stream)) {
                 e->train_open = false;
                 return fail(e, AZ_ERR_HIP, "trainer_set_lr_table failed");
@@ -1781,11 +2111,14 @@ az_status az_net_train_samples(az_engine* e, int32_t previous_model_id, int32_t 
                 if (!trainer_read_losses(t, l, true, e->stream)) { e->train_open = false; return fail(e, AZ_ERR_HIP, "trainer_read_losses failed"); }
                 e->train_history.push_back((float)(l[0] / (double)steps));
                 e->train_history.push_back((float)(l[1] / (double)steps));
+                bool stop = false;
+                if (az_status vst = validate_epoch(e, model_id, val_params, best_params, &stop)) { e->train_open = false; return vst; }
+                if (stop) break;
             }
             HIPCHK(hipStreamSynchronize(e->stream));
         } catch (const HipFail& f) { e->train_open = false; return fail_hip(e, f); }
     } catch (const HipFail& f) { return fail_hip(e, f); }
-    return az_net_train_end(e, model_id);
+    return train_store(e, model_id, best_params);
 }
 
 az_status az_net_train_ema(az_engine* e, int32_t model_id) {

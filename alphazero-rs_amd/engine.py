@@ -89,7 +89,8 @@ EXPORTS = [
     "az_net_init_random", "az_net_load", "az_net_save", "az_net_param_count", "az_net_set_params",
     "az_net_get_params", "az_net_predict", "az_net_predict_states", "az_net_train", "az_net_train_history",
     "az_net_train_begin", "az_net_train_step", "az_net_train_end", "az_net_train_ema", "az_net_train_step_info",
-    "az_net_train_samples", "az_net_train_draw", "az_tree_create",
+    "az_net_train_samples", "az_net_train_draw", "az_net_evaluate", "az_samples_holdout", "az_net_train_set_validation",
+    "az_net_train_validation", "az_tree_create",
     "az_tree_destroy", "az_tree_reset", "az_tree_get_action_prob", "az_tree_record_evals", "az_tree_get_evals",
     "az_tree_node_counts", "az_tree_share", "az_tree_slot_acquire", "az_tree_slot_release", "az_tree_slot_get_action_prob",
     "az_tree_slot_error", "az_tree_share_stats", "az_root_noise_eta", "az_tree_get_selected", "az_gumbel_values", "az_selfplay", "az_selfplay_begin", "az_selfplay_next", "az_selfplay_end", "az_selfplay_get_evals", "az_selfplay_get_full_plies", "az_selfplay_get_search", "az_samples_merge", "az_samples_blend_z", "az_samples_surprise", "az_solve", "az_move_quality", "az_arena", "az_arena_get_evals", "az_arena_get_moves",
@@ -134,6 +135,10 @@ def load_library(path=LIB_PATH):
         "az_net_train_step_info": (i32, [vp, vp]),
         "az_net_train_samples": (i32, [vp, i32, i32, C.POINTER(az_samples), vp, i32]),
         "az_net_train_draw": (i32, [vp, i64, vp, i32, u64, i64, vp, vp]),
+        "az_net_evaluate": (i32, [vp, i32, C.POINTER(az_samples), vp, vp, vp, vp, vp, vp]),
+        "az_samples_holdout": (i32, [vp, C.POINTER(az_samples), i64, u64, vp]),
+        "az_net_train_set_validation": (i32, [vp, C.POINTER(az_samples), vp]),
+        "az_net_train_validation": (i32, [vp, vp, i32, C.POINTER(i32)]),
         "az_tree_create": (i32, [vp, i32, u64, i32, i32, i32, i32, i32, C.POINTER(vp)]),
         "az_tree_destroy": (None, [vp]),
         "az_tree_reset": (i32, [vp, vp]),
@@ -348,6 +353,67 @@ class Engine:
         out = np.zeros((n, 2), np.float32)
         self._lib.az_net_train_history(self._h, _ptr(out), n)
         return [tuple(float(x) for x in r) for r in out]
+
+    @staticmethod
+    def _tuples(pis, zs, states, boards, weights):
+        """(az_samples, weights, n) of a window given as numpy arrays or torch tensors (host or device); the arrays are returned so
+        that they outlive the call."""
+        if (states is None) == (boards is None):
+            raise ValueError("states or boards, not both")
+        n = int(len(zs))
+        if not hasattr(pis, "data_ptr"):
+            pis = np.ascontiguousarray(pis, dtype=np.float32).reshape(n, ACTIONS)
+        if not hasattr(zs, "data_ptr"):
+            zs = np.ascontiguousarray(zs, dtype=np.float32).reshape(n)
+        if states is not None and not hasattr(states, "data_ptr"):
+            states = np.ascontiguousarray(states, dtype=np.uint64).reshape(n, 2)
+        if boards is not None and not hasattr(boards, "data_ptr"):
+            boards = np.ascontiguousarray(boards, dtype=np.float32).reshape(n, 2, 6, 7)
+        if weights is not None and not hasattr(weights, "data_ptr"):
+            weights = np.ascontiguousarray(weights, dtype=np.uint32).reshape(n)
+        return az_samples(n, n, _as_ptr(states), _as_ptr(boards), _as_ptr(pis), _as_ptr(zs), None, None), (pis, zs, states, boards, weights), n
+
+    def evaluate(self, model_id, pis, zs, *, states=None, boards=None, weights=None, per_tuple=False, out=None):
+        """az_net_evaluate: the held-out loss of model_id as self-play runs it (its effective class, "eval_mirror", any model kind) over
+        the window (states [n,2] or boards [n,2,6,7], pis, zs; weights u32 [n], None = all ones), scored on the device in one call.
+        Returns a dict: n, weight_sum, loss_pi, loss_v, kl, top1 (doubles from the integer sums) and sums = (S_ce, S_kl, S_se, S_hit, W).
+        per_tuple adds the f32 arrays ce, se, kl [n]; out = (ce, se, kl) writes them into the caller's arrays or tensors instead."""
+        src, keep, n = self._tuples(pis, zs, states, boards, weights)
+        score = np.zeros(6, np.float64)
+        sums = np.zeros(5, np.uint64)
+        arrs = out if out is not None else (tuple(np.full(n, np.nan, np.float32) for _ in range(3)) if per_tuple else (None, None, None))
+        self._check(self._lib.az_net_evaluate(self._h, model_id, C.byref(src), _as_ptr(keep[4]), _ptr(score), _ptr(sums),
+                                              _as_ptr(arrs[0]), _as_ptr(arrs[1]), _as_ptr(arrs[2])))
+        r = {"n": int(score[0]), "weight_sum": int(score[1]), "loss_pi": float(score[2]), "loss_v": float(score[3]), "kl": float(score[4]),
+             "top1": float(score[5]), "sums": tuple(int(x) for x in sums)}
+        if per_tuple or out is not None:
+            r["ce"], r["se"], r["kl_rows"] = arrs
+        return r
+
+    def samples_holdout(self, share, seed, pis, zs, *, states=None, boards=None, out=None):
+        """az_samples_holdout: the hold-out mask (bool [n]) of a window at share (a fraction; share_e6 = round(share * 1e6)) and seed: a
+        function of the position alone, the same for a position and its mirror image.  out: a uint8 array or tensor to write into."""
+        src, keep, n = self._tuples(pis, zs, states, boards, None)
+        held = out if out is not None else np.full(n, 255, np.uint8)
+        self._check(self._lib.az_samples_holdout(self._h, C.byref(src), int(round(float(share) * 1e6)), int(seed) & (2 ** 64 - 1), _as_ptr(held)))
+        return held if out is not None else held.astype(bool)
+
+    def train_set_validation(self, pis=None, zs=None, *, states=None, boards=None, weights=None):
+        """az_net_train_set_validation: register (copy to the device) the set train() and train_samples() score at the end of every
+        epoch; no arguments clear it."""
+        if pis is None:
+            self._check(self._lib.az_net_train_set_validation(self._h, None, None))
+            return
+        src, keep, n = self._tuples(pis, zs, states, boards, weights)
+        self._check(self._lib.az_net_train_set_validation(self._h, C.byref(src), _as_ptr(keep[4])))
+
+    def train_validation(self):
+        """([(loss_pi, loss_v, kl, top1)] per epoch of the last train() / train_samples() with a validation set, best_epoch or -1)."""
+        best = C.c_int32(-1)
+        n = self._lib.az_net_train_validation(self._h, None, 0, None)
+        out = np.zeros((n, 4), np.float64)
+        self._lib.az_net_train_validation(self._h, _ptr(out), n, C.byref(best))
+        return [tuple(float(x) for x in r) for r in out], int(best.value)
 
     def train_begin(self, prev_id):
         self._check(self._lib.az_net_train_begin(self._h, prev_id))

@@ -1,7 +1,7 @@
 // examples/connect_four.rs (src lines 45-80) on the C++ host: the same Coach::setup parameters, the engine behind it.
 // Build:  g++ -std=c++17 -O2 -I include examples/connect_four.cpp -o connect_four -L alphazero-rs_amd -laz_engine
 //         (and -Wl,-rpath,$PWD/alphazero-rs_amd)
-// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]] [--value-target-q L] [--surprise S]
+// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]] [--value-target-q L] [--surprise S] [--validation SHARE[,PATIENCE[,best]]]
 //         selfplay_fp8 = 1: the episodes are played in the fp8 class, the arena gate in bf16 (Coach::selfplay_class)
 //         root_noise_eps > 0 (e.g. 0.25, with root_noise_alpha 0.3; default alpha 1): Dirichlet root noise in the episodes (Coach::root_noise_eps)
 //         eval_mirror = 1: mirror-canonical leaf evaluation for the whole loop, episodes and gate (Coach::eval_mirror)
@@ -23,6 +23,9 @@
 //         the tuple's own search (Coach::value_target_q)
 //         --surprise S (anywhere on the line, e.g. 0.5): policy surprise weighting -- the iteration's tuples are resampled, a share S of the
 //         weight in proportion to KL(pi || root prior) (Coach::surprise_share)
+//         --validation SHARE[,PATIENCE[,best]] (anywhere on the line, e.g. 0.05 or 0.05,3,best): held-out validation -- a share SHARE of the
+//         window's positions is never trained on and scored at the end of every epoch; PATIENCE > 0 stops after that many epochs without a
+//         new best, best keeps the best epoch's weights (Coach::validation_share / patience / keep_best)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,7 +46,7 @@ int main(int argc, char** argv) {
         }
         return v;
     };
-    const std::string gumbel = take("--gumbel"), value_q = take("--value-target-q"), surprise_s = take("--surprise");
+    const std::string gumbel = take("--gumbel"), value_q = take("--value-target-q"), surprise_s = take("--surprise"), validation = take("--validation");
     const std::string dir = argc > 1 ? argv[1] : "./checkpoint";
     const size_t iters = argc > 2 ? std::strtoul(argv[2], nullptr, 10) : 1;       // num_iters, examples/connect_four.rs:65
     const size_t eps = argc > 3 ? std::strtoul(argv[3], nullptr, 10) : 1;         // num_eps, :66
@@ -74,6 +77,12 @@ int main(int argc, char** argv) {
         coach.forced_playouts_k = forced_k; coach.policy_prune = prune;
         if (!value_q.empty()) coach.value_target_q = std::atof(value_q.c_str());
         if (!surprise_s.empty()) coach.surprise_share = std::atof(surprise_s.c_str());
+        if (!validation.empty()) {
+            coach.validation_share = std::atof(validation.c_str());
+            const size_t c1 = validation.find(','), c2 = c1 == std::string::npos ? c1 : validation.find(',', c1 + 1);
+            if (c1 != std::string::npos) coach.patience = (size_t)std::strtoul(validation.c_str() + c1 + 1, nullptr, 10);
+            coach.keep_best = c2 != std::string::npos && validation.substr(c2 + 1) == "best";
+        }
         if (!gumbel.empty()) {
             coach.gumbel_m = std::strtol(gumbel.c_str(), nullptr, 10);
             const size_t c1 = gumbel.find(','), c2 = c1 == std::string::npos ? c1 : gumbel.find(',', c1 + 1);
@@ -91,6 +100,9 @@ int main(int argc, char** argv) {
                         r.pwins, r.draws, r.accepted ? "accepted" : "rejected", r.losses.empty() ? 0.f : r.losses[r.losses.size() - 2],
                         r.losses.empty() ? 0.f : r.losses.back());
             if (coach.merge_positions) std::printf("iteration %zu: merged from %zu raw samples\n", r.iteration, r.samples_raw);
+            if (coach.validation_share > 0 && !r.val_loss_pi.empty())
+                std::printf("iteration %zu: %zu held out, %zu epochs, best epoch %d with val loss (%.4f, %.4f) top1 %.4f\n", r.iteration, r.val_n, r.val_loss_pi.size(),
+                            (int)r.best_epoch, r.val_loss_pi[(size_t)r.best_epoch], r.val_loss_v[(size_t)r.best_epoch], r.val_top1[(size_t)r.best_epoch]);
             if (coach.merge_weighted) std::printf("iteration %zu: rows drawn by multiplicity, total weight %zu\n", r.iteration, r.samples_weight);
         }
         return 0;

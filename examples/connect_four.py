@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--move-quality", default=None, metavar="STONES[,NODES]")   # exact move-quality report of every arena: positions with at least STONES stones are solved (budget NODES per position and action, default 2^20) and each model's value-losing moves counted (Coach.solve_min_stones)
     ap.add_argument("--value-target-q", type=float, default=0.0, metavar="L")   # value target (1 - L) z + L q: the game outcome mixed with the root value of the tuple's own search, e.g. 0.5 (Coach.value_target_q)
     ap.add_argument("--surprise", type=float, default=0.0, metavar="S")   # policy surprise weighting: the iteration's tuples resampled, a share S of the weight in proportion to KL(pi || root prior), e.g. 0.5 (Coach.surprise_share)
+    ap.add_argument("--validation", default=None, metavar="SHARE[,PATIENCE[,best]]")   # held-out validation, e.g. 0.05 or 0.05,3,best: a share SHARE of the window's positions is never trained on and scored at the end of every epoch; PATIENCE > 0 stops after that many epochs without a new best, best keeps the best epoch's weights (Coach.validation_share / patience / keep_best)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
     ap.add_argument("--eval-mirror", action="store_true")    # mirror-canonical leaf evaluation for the whole loop (Coach.eval_mirror)
     a = ap.parse_args()
@@ -88,6 +89,11 @@ def main():
         coach.lr_floor = float(parts[2]) if len(parts) > 2 else 0.0
     modes = (a.merge_positions or "").split(",")
     coach.merge_positions, coach.merge_canonical, coach.merge_weighted = a.merge_positions is not None, "canonical" in modes, "weighted" in modes
+    if a.validation:
+        parts = a.validation.split(",")
+        coach.validation_share = float(parts[0])
+        coach.patience = int(parts[1]) if len(parts) > 1 and parts[1] else 0
+        coach.keep_best = len(parts) > 2 and parts[2] == "best"
     if a.move_quality:
         stones, _, nodes = a.move_quality.partition(",")
         coach.solve_min_stones, coach.solve_max_nodes = int(stones), int(nodes) if nodes else 1 << 20
@@ -95,6 +101,9 @@ def main():
         print(r["iteration"], "samples", r["samples"], *(("of", r["samples_raw"]) if coach.merge_positions else ()), "new/prev/draw", r["nwins"], r["pwins"], r["draws"],
               "accepted" if r["accepted"] else "rejected", "loss", r["losses"][-1],
               "seconds", {k: round(v, 2) for k, v in r["seconds"].items()})
+        if "val_n" in r:
+            print(r["iteration"], "held out", r["val_n"], "val loss_pi", [round(x, 4) for x in r["val_loss_pi"]], "loss_v", [round(x, 4) for x in r["val_loss_v"]],
+                  "top1", [round(x, 4) for x in r["val_top1"]], "best epoch", r["best_epoch"])
         if "quality" in r:
             print(r["iteration"], "move quality from", coach.solve_min_stones, "stones:", r["quality"])
     e.close()

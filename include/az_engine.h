@@ -754,6 +754,62 @@ az_status az_net_train_samples(az_engine* e, int32_t prev_id, int32_t id, const 
 az_status az_net_train_draw(az_engine* e, int64_t n, const uint32_t* weights, int32_t flags, uint64_t t0,
                             int64_t steps, int64_t* idx_out /* [steps*b] */, uint8_t* mirror_out /* [steps*b], may be NULL */);
 
+/* ---- held-out loss on the device, a hold-out rule and per-epoch validation inside NNet::train (no reference counterpart; csrc/az_score.h,
+ * DESIGN.md sections 4.1l and 8.3).  Strictly opt-in: with no set registered and "train_keep_best" / "train_patience" at 0 every kernel
+ * launched and every bit computed is what it was.
+ *
+ * az_net_evaluate: the loss of model_id AS SELF-PLAY RUNS IT over a whole window in one call.  (p, v) of tuple i is, by definition, what
+ * az_net_predict_states returns for its state on this engine now: the model's effective class, "eval_mirror" if it is on, any model kind
+ * (the stub and hash nets included).  Per tuple, against its target (pi, z), with weight w_i (u32; 1 when weights is NULL):
+ *   ce    t = 0; for a ascending with pi[a] >= 2^-126: t = t + pi[a] * log2(max(p[a], 2^-126)); ce = -(t * ln 2) clamped to [0, 128] (NaN: 128)
+ *   kl    az_samples_surprise's KL(pi || p), clamped to [0, 64]
+ *   se    (v - z)^2 (a NaN or a value above 4 counts as 4)
+ *   hit   the lowest a that maximises pi[a] == the lowest LEGAL a (its column is not full) that maximises p[a]
+ * all in f32, operation by operation (csrc/az_score.h), then K(x) = llrint(x * 2^30) and the u64 sums S_ce = sum w_i K(ce_i), S_kl, S_se,
+ * S_hit = sum w_i hit_i, W = sum w_i: integer sums, the same bits whatever the order of the additions.
+ *   score [AZ_SCORE_FIELDS]   n, W, loss_pi = S_ce / 2^30 / W, loss_v = S_se / 2^30 / W, kl = S_kl / 2^30 / W, top1 = S_hit / W (n and W are
+ *                             integers of at most 2^24, exact in a double)
+ *   sums [AZ_SCORE_SUMS]      S_ce, S_kl, S_se, S_hit, W (may be NULL)
+ *   ce, se, kl [n]            the per-tuple values (each may be NULL; host or device)
+ * It reads s->count (n), s->pis, s->zs and s->states [n,2], or s->boards [n,2,6,7] when states is NULL; every array, weights included, may
+ * be host or device memory.  The window is staged once; the forwards of all max_batch chunks and the score kernel behind each run on the
+ * engine's stream with one synchronisation at the end and no copy of a pi or a v to the host.  The evaluation cache is neither read nor
+ * written; no cache tag, generation or captured graph of any model changes; no az_stats counter but device_ms moves.  Allowed wherever
+ * az_net_predict_states is.  AZ_ERR_BAD_ARGUMENT, with nothing written: n < 1 or n > 2^24; W = 0 or W > 2^24; pis or zs NULL, or states
+ * and boards both NULL; a pi outside [0, 1] or a z outside [-1, 1] (NaN included); a state or plane set az_samples_merge would refuse.
+ * AZ_ERR_NO_MODEL: an id that is not initialised.
+ *
+ * az_samples_holdout: held[i] = (mix64(mix64(seed) ^ k_i) >> 40) < share_e6 * 2^24 / 1000000 (unsigned 64-bit), k_i the key
+ * az_samples_merge forms for tuple i under AZ_MERGE_CANONICAL: a function of the position alone, so a position and its mirror image are
+ * always on one side and a held-out position stays held out in every window split with the same seed.  Share 0 holds nothing, 1000000
+ * everything.  Inputs and validation are az_samples_merge's (states or boards, pis, zs; host or device; n <= 2^24; n = 0 is legal); held
+ * [n] u8, host or device.  Refused while a self-play session is open.
+ *
+ * az_net_train_set_validation: copies the set to the device (16-byte states, about 60 bytes per tuple with weights; validated as
+ * az_net_evaluate validates it) and keeps it until the next call or az_destroy; v = NULL clears it.  Refused while a training session is
+ * open.  With a set registered, az_net_train and az_net_train_samples score it at the end of every epoch: the weights and BatchNorm moving
+ * averages exactly as az_net_train_end would store them at that step (the live weights, not the averaged shadow) go into a model slot no
+ * id names, of the effective class of the destination id (a fresh id: the engine's), and are scored as az_net_evaluate scores.  The
+ * trainer is only read: with both options below at 0 the stored model is bit for bit the one trained without a set.
+ *   "train_keep_best"  0 (default) / 1: store the weights of the epoch with the lowest loss_pi + loss_v (the first such epoch) instead of
+ *                      the last epoch's
+ *   "train_patience"   0 (default: off) or 1 .. 1000: stop behind the first epoch that ends that many consecutive epochs without a new
+ *                      best; az_net_train_history and the validation history then hold the epochs actually run
+ * Either option without a registered set makes az_net_train / az_net_train_samples fail with AZ_ERR_BAD_ARGUMENT before they begin.  The
+ * fine-grained az_net_train_begin / _step / _end never validate.
+ * az_net_train_validation: (loss_pi, loss_v, kl, top1) of each epoch of the last az_net_train / az_net_train_samples: writes
+ * min(epochs, cap_epochs) rows to out (may be NULL), *best_epoch (may be NULL) = the first epoch of the lowest loss_pi + loss_v (-1 with
+ * no rows), and returns the number of rows (0 when no set was registered).
+ * Whether early stopping or keeping the best epoch changes playing strength is unmeasured. */
+#define AZ_SCORE_FIELDS 6
+#define AZ_SCORE_SUMS   5
+az_status az_net_evaluate(az_engine* e, int32_t model_id, const az_samples* s, const uint32_t* weights,
+                          double* score /* [AZ_SCORE_FIELDS] */, uint64_t* sums /* [AZ_SCORE_SUMS], may be NULL */,
+                          float* ce /* [n], may be NULL */, float* se /* [n], may be NULL */, float* kl /* [n], may be NULL */);
+az_status az_samples_holdout(az_engine* e, const az_samples* s, int64_t share_e6, uint64_t seed, uint8_t* held /* [n] */);
+az_status az_net_train_set_validation(az_engine* e, const az_samples* v /* NULL clears */, const uint32_t* weights);
+int32_t az_net_train_validation(const az_engine* e, double* out /* [cap_epochs,4] */, int32_t cap_epochs, int32_t* best_epoch);
+
 /* ---- arena::play_games, src/arena.rs:62-99 + gate, src/coach.rs:377-390 ---- */
 typedef struct az_arena_params {
     int32_t num_games;      /* num/2 per seating, src/arena.rs:83 */

@@ -49,6 +49,12 @@
 #pragma weak az_selfplay_get_search
 #pragma weak az_samples_blend_z
 #pragma weak az_samples_surprise
+// Coach::validation_share / az_host::evaluate / samples_holdout / train_set_validation / train_validation: with validation_share 0 (the
+// default) no Coach calls them.
+#pragma weak az_net_evaluate
+#pragma weak az_samples_holdout
+#pragma weak az_net_train_set_validation
+#pragma weak az_net_train_validation
 
 namespace az_host {
 
@@ -281,6 +287,54 @@ inline TrainDraw train_draw(const Engine& e, int64_t n, const uint32_t* weights,
     d.mirror.assign(d.idx.size(), 0);
     e.check(az_net_train_draw(e.raw(), n, weights, flags, t0, steps, d.idx.data(), d.mirror.data()));
     return d;
+}
+
+// ---- held-out loss, the hold-out rule, per-epoch validation (include/az_engine.h; csrc/az_score.h) --------------------------------------
+inline az_samples tuples_view(int64_t n, const uint64_t* states, const float* boards, const float* pis, const float* zs) {
+    az_samples s{};
+    s.capacity = n; s.count = n;
+    s.states = const_cast<uint64_t*>(states); s.boards = const_cast<float*>(boards);
+    s.pis = const_cast<float*>(pis); s.zs = const_cast<float*>(zs);
+    return s;
+}
+// az_net_evaluate: the loss of a model as self-play runs it over n tuples (states [n,2], or with states nullptr boards [n,2,6,7]; weights
+// u32 [n] or nullptr = all ones), scored on the device in one call.  sums = S_ce, S_kl, S_se, S_hit, W; ce / se / kl [n] may be nullptr
+struct Score { int64_t n = 0; uint64_t weight_sum = 0; double loss_pi = 0, loss_v = 0, kl = 0, top1 = 0; uint64_t sums[AZ_SCORE_SUMS] = {0, 0, 0, 0, 0}; };
+inline Score evaluate(const Engine& e, size_t model_id, int64_t n, const uint64_t* states, const float* boards, const float* pis, const float* zs,
+                      const uint32_t* weights = nullptr, float* ce = nullptr, float* se = nullptr, float* kl = nullptr) {
+    if (!az_net_evaluate) throw Panic("evaluate: the linked engine library has no az_net_evaluate");
+    const az_samples s = tuples_view(n, states, boards, pis, zs);
+    double f[AZ_SCORE_FIELDS] = {0, 0, 0, 0, 0, 0};
+    Score r;
+    e.check(az_net_evaluate(e.raw(), (int32_t)model_id, &s, weights, f, r.sums, ce, se, kl));
+    r.n = (int64_t)f[0]; r.weight_sum = (uint64_t)f[1]; r.loss_pi = f[2]; r.loss_v = f[3]; r.kl = f[4]; r.top1 = f[5];
+    return r;
+}
+// az_samples_holdout: held [n] at `share` (0 .. 1) and seed -- a function of the position alone, the same for a position and its mirror image
+inline std::vector<uint8_t> samples_holdout(const Engine& e, int64_t n, const uint64_t* states, const float* boards, const float* pis, const float* zs,
+                                            double share, uint64_t seed) {
+    if (!az_samples_holdout) throw Panic("samples_holdout: the linked engine library has no az_samples_holdout");
+    const az_samples s = tuples_view(n, states, boards, pis, zs);
+    std::vector<uint8_t> held((size_t)std::max<int64_t>(n, 0), 255);
+    e.check(az_samples_holdout(e.raw(), &s, (int64_t)std::llround(share * 1e6), seed, held.data()));
+    return held;
+}
+// az_net_train_set_validation: registers the set az_net_train / az_net_train_samples score at the end of every epoch; n = 0 clears it
+inline void train_set_validation(const Engine& e, int64_t n = 0, const uint64_t* states = nullptr, const float* boards = nullptr, const float* pis = nullptr,
+                                 const float* zs = nullptr, const uint32_t* weights = nullptr) {
+    if (!az_net_train_set_validation) throw Panic("train_set_validation: the linked engine library has no az_net_train_set_validation");
+    if (n == 0) { e.check(az_net_train_set_validation(e.raw(), nullptr, nullptr)); return; }
+    const az_samples s = tuples_view(n, states, boards, pis, zs);
+    e.check(az_net_train_set_validation(e.raw(), &s, weights));
+}
+// az_net_train_validation: rows [epochs][4] = (loss_pi, loss_v, kl, top1) of the last az_net_train / az_net_train_samples; best_epoch or -1
+struct Validation { std::vector<double> rows; int32_t best_epoch = -1; };
+inline Validation train_validation(const Engine& e) {
+    if (!az_net_train_validation) throw Panic("train_validation: the linked engine library has no az_net_train_validation");
+    Validation v;
+    v.rows.resize(4 * (size_t)az_net_train_validation(e.raw(), nullptr, 0, nullptr));
+    az_net_train_validation(e.raw(), v.rows.data(), (int32_t)(v.rows.size() / 4), &v.best_epoch);
+    return v;
 }
 
 // ---- search statistics as targets (include/az_engine.h; csrc/az_target.h) --------------------------------------------------------------
@@ -574,7 +628,10 @@ class Coach {
     // samples_weight (with merge_weighted): the sum of the multiplicities the batches were drawn by (= samples_raw); 0 with it off
     // quality (with solve_min_stones > 0): [0] the new model's arena moves, [1] the old model's, each {examined, kept, win_to_draw, win_to_loss,
     // draw_to_loss, unknown} (quality_tally above); all zero with the report off
-    struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; size_t samples_raw; uint64_t quality[2][6]; size_t samples_weight; };
+    // val_n, val_loss_pi / val_loss_v / val_top1 (one entry per epoch) and best_epoch (with validation_share > 0): the held-out part of the
+    // window and its score at the end of every epoch; 0, empty and -1 with it off
+    struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; size_t samples_raw; uint64_t quality[2][6]; size_t samples_weight;
+                    size_t val_n; std::vector<double> val_loss_pi, val_loss_v, val_top1; int32_t best_epoch; };
 
     // Coach::setup(checkpoint_directory, + the reference's 14 numeric parameters), src/coach.rs:38-103
     static Coach setup(Engine& e, const std::string& checkpoint_directory, size_t mcts_reserve_size, float update_threshold,
@@ -802,6 +859,27 @@ class Coach {
             ab.reserve(n * 84); ap.reserve(n * 7); av.reserve(n);
             for (auto& h : history) { ab.insert(ab.end(), h.boards.begin(), h.boards.end()); ap.insert(ap.end(), h.pis.begin(), h.pis.end()); av.insert(av.end(), h.vs.begin(), h.vs.end()); }
             const size_t n_raw = n;
+            size_t val_n = 0;
+            if (validation_share > 0) {                               // the split: before merge and shuffle, by the position alone
+                if (!(validation_share < 1.0)) throw Panic("validation_share must be in 0 .. 1 (exclusive)");
+                const std::vector<uint8_t> held = samples_holdout(e_, (int64_t)n, nullptr, ab.data(), ap.data(), av.data(), validation_share, seed);
+                std::vector<float> vb, vp, vv, tb, tp, tv;
+                for (size_t i = 0; i < n; ++i) {
+                    std::vector<float>&b = held[i] ? vb : tb, &p = held[i] ? vp : tp, &v = held[i] ? vv : tv;
+                    b.insert(b.end(), ab.begin() + (std::ptrdiff_t)(i * 84), ab.begin() + (std::ptrdiff_t)((i + 1) * 84));
+                    p.insert(p.end(), ap.begin() + (std::ptrdiff_t)(i * 7), ap.begin() + (std::ptrdiff_t)((i + 1) * 7));
+                    v.push_back(av[i]);
+                }
+                val_n = vv.size();
+                if (val_n == n) throw Panic("validation_share holds the whole window out");
+                if (val_n > 0) {
+                    train_set_validation(e_, (int64_t)val_n, nullptr, vb.data(), vp.data(), vv.data());
+                    ab.swap(tb); ap.swap(tp); av.swap(tv);
+                    n = av.size();
+                }
+            } else if (keep_best || patience) {
+                throw Panic("keep_best and patience need validation_share > 0");
+            }
             if (merge_weighted && !merge_positions) throw Panic("merge_weighted requires merge_positions");
             std::vector<uint64_t> as;                                 // merge_weighted: the merged states (no planes are made)
             std::vector<uint32_t> mult;                               // ... and their multiplicities
@@ -841,6 +919,12 @@ class Coach {
                 ScopedOption optim_guard(weight_decay > 0 || clip_norm > 0 || lr_warmup_steps > 0 || lr_decay != 0 || ema_decay > 0,
                                          [&] { e_.set_train_optim(weight_decay, clip_norm, lr_warmup_steps, lr_decay, lr_floor, ema_decay); },
                                          [&] { e_.set_train_optim(); });
+                // the validation set and its two options hold for this training only
+                ScopedOption validation_guard(val_n > 0,
+                                              [&] { e_.check(az_set_option(e_.raw(), "train_keep_best", keep_best ? 1 : 0));
+                                                    e_.check(az_set_option(e_.raw(), "train_patience", (int64_t)patience)); },
+                                              [&] { az_set_option(e_.raw(), "train_keep_best", 0); az_set_option(e_.raw(), "train_patience", 0);
+                                                    az_net_train_set_validation(e_.raw(), nullptr, nullptr); });
                 if (merge_weighted)       // rows in proportion to the multiplicities, mirrored at random under merge_canonical; an epoch keeps the merged set's cost
                     train_samples(e_, model_id, model_id + 1, (int64_t)n, ss.data(), nullptr, sp.data(), sv.data(), sw.data(), merge_canonical ? AZ_TRAIN_MIRROR : 0);
                 else
@@ -855,6 +939,12 @@ class Coach {
             r.iteration = iteration; r.samples = n; r.samples_raw = n_raw; r.samples_weight = weight_sum; r.model_id = model_id;
             r.losses.resize(2 * (size_t)az_net_train_history(e_.raw(), nullptr, 0));
             az_net_train_history(e_.raw(), r.losses.data(), (int32_t)(r.losses.size() / 2));
+            r.val_n = val_n; r.best_epoch = -1;
+            if (val_n > 0) {
+                const Validation v = train_validation(e_);
+                for (size_t k = 0; k < v.rows.size() / 4; ++k) { r.val_loss_pi.push_back(v.rows[4 * k]); r.val_loss_v.push_back(v.rows[4 * k + 1]); r.val_top1.push_back(v.rows[4 * k + 3]); }
+                r.best_epoch = v.best_epoch;
+            }
             // arena: new (first listed) vs old, both seatings (:333-375)
             az_arena_params a{};
             a.num_games = (int32_t)num_arena_games; a.num_sims = (int32_t)num_sims; a.max_depth = (int32_t)max_depth; a.cpuct = cpuct;
@@ -984,6 +1074,15 @@ class Coach {
     // files, the merge and the trainers see ordinary tuples; merge_positions + merge_weighted turn the duplicates back into draw weights.
     // Both 0 (the default): the engine is never asked
     double value_target_q = 0.0, surprise_share = 0.0;
+    // Held-out validation (az_samples_holdout / az_net_train_set_validation; csrc/az_score.h).  validation_share (0 .. 1): every iteration the
+    // assembled window is split by the hold-out rule BEFORE merge and shuffle, with learn()'s constant seed -- a function of the position
+    // alone, so a position (and its mirror image) is on the same side in every iteration; the rest is trained on, the held-out part is
+    // registered raw and scored at the end of every epoch (Report::val_*, best_epoch).  keep_best stores the best epoch's weights, patience
+    // > 0 stops after that many epochs without a new best.  History and the .examples files keep every tuple.  0 (the default): the engine
+    // is never asked and reports and files are what they were
+    double validation_share = 0.0;
+    bool keep_best = false;
+    size_t patience = 0;
     float update_threshold = 0.f;
     int32_t cpuct = 1;
 

@@ -103,6 +103,12 @@ extern "C" {
     /// the draw alone for global steps t0 .. t0 + steps: idx_out [steps * "train_batch"], mirror_out the same length (may be null)
     pub fn az_net_train_draw(e: *mut az_engine, n: i64, weights: *const u32, flags: i32, t0: u64, steps: i64, idx_out: *mut i64,
                              mirror_out: *mut u8) -> c_int;
+    // held-out loss on the device, the hold-out rule, per-epoch validation inside NNet::train (score: [6], sums: [5] or null)
+    pub fn az_net_evaluate(e: *mut az_engine, model_id: i32, s: *const az_samples, weights: *const u32, score: *mut f64, sums: *mut u64,
+                           ce: *mut f32, se: *mut f32, kl: *mut f32) -> c_int;
+    pub fn az_samples_holdout(e: *mut az_engine, s: *const az_samples, share_e6: i64, seed: u64, held: *mut u8) -> c_int;
+    pub fn az_net_train_set_validation(e: *mut az_engine, v: *const az_samples, weights: *const u32) -> c_int;
+    pub fn az_net_train_validation(e: *const az_engine, out: *mut f64, cap_epochs: i32, best_epoch: *mut i32) -> i32;
     // ---- AsyncMcts, src/async_mcts.rs:14-115
     pub fn az_tree_create(e: *mut az_engine, n_games: i32, reserve: u64, num_sims: i32, num_threads: i32, max_depth: i32,
                           model_id: i32, cpuct: i32, out: *mut *mut az_tree) -> c_int;
