@@ -384,6 +384,7 @@ struct az_engine {
     struct EvalLog { std::vector<int32_t> count; std::vector<uint64_t> states; std::vector<float> pi, v; };
     EvalLog ar_log[2];
     struct SelfplaySession* sp_session = nullptr;      // az_selfplay_begin .. az_selfplay_end
+    int32_t sp_model_id = 0;                           // the open session's model id (meaningful while sp_session is set)
     int ar_log_cap = 0, ar_log_games = 0;
     std::vector<uint8_t> ar_moves;      // [games][AZ_MAX_PLIES] move record of the last az_arena (az_arena_get_moves)
     std::vector<int32_t> ar_len;
@@ -529,6 +530,19 @@ az_status gumbel_refusal(az_engine* e, int T, const char* who) {
     if (e->selfplay_async) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": gumbel_m and selfplay_async exclude each other");
     if (e->forced_playouts_k_e6 > 0) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": gumbel_m and forced_playouts_k_e6 exclude each other (both claim the root's arg-max)");
     return AZ_OK;
+}
+// The call-interleaving contract of an open self-play session (include/az_engine.h, next to az_selfplay_begin): an entry that could change
+// what the session's remaining chunks are -- a tree search (it sizes, clears and retags the evaluation cache), a write to the session's
+// model, an option the session captured at begin or reads while it plays -- is refused on entry, before any work, with a message that
+// names it.  session_refusal: refused whatever the arguments are; session_model_refusal: refused for the session's model id only.
+az_status session_refusal(az_engine* e, const char* entry) {
+    if (!e->sp_session) return AZ_OK;
+    return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(entry) + ": refused while a self-play session is open (az_selfplay_end first)");
+}
+az_status session_model_refusal(az_engine* e, const char* entry, int32_t model_id) {
+    if (!e->sp_session || model_id != e->sp_model_id) return AZ_OK;
+    return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(entry) + ": model " + std::to_string(model_id) +
+                                            " belongs to the open self-play session (az_selfplay_end first)");
 }
 az_status fail_hip(az_engine* e, const HipFail& f) {
     char buf[512];
@@ -1112,6 +1126,12 @@ const char* az_last_error(const az_engine* e) { return e ? e->err.c_str() : "nul
 az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     if (!e || !key) return AZ_ERR_BAD_ARGUMENT;
     auto is = [&](const char* k) { return std::strcmp(key, k) == 0; };
+    // an open self-play session captured these at begin or reads them while it plays (the evaluation cache's shape, which rows go through
+    // it, the driver and its schedule, conv2's rounding): no value of them is taken until az_selfplay_end
+    if (e->sp_session)
+        for (const char* k : {"conv2_table", "eval_dedup", "eval_cache_log2", "eval_cache_persist", "eval_cache_max_stones", "selfplay_async",
+                              "selfplay_async_launches", "selfplay_async_iters"})
+            if (is(k)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_set_option: " + std::string(k) + " cannot change while a self-play session is open");
     // ---- options of the shipped library: every one of them lives in THIS engine ----
     if (is("conv2_table") && (value == 0 || value == 1)) {
         if (value == 0 && e->netopt.net_fp8) return fail(e, AZ_ERR_BAD_ARGUMENT, "conv2_table = 0 is not available while net_fp8 is 1 (the fp8 class takes conv2 from the table kernel)");
@@ -1119,7 +1139,14 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
             for (const auto& kv : e->nets)
                 if (kv.second.kind == AZ_NET_CONV && effective_class(e, kv.second))
                     return fail(e, AZ_ERR_BAD_ARGUMENT, "conv2_table = 0 is not available while model " + std::to_string(kv.first) + " is of the fp8 class (it takes conv2 from the table kernel)");
+        if ((int)value == e->netopt.conv2_table) return AZ_OK;
         e->netopt.conv2_table = (int)value;
+        for (auto& kv : e->nets) {
+            NetModel& m = kv.second;
+            if (m.kind != AZ_NET_CONV) continue;
+            m.cache_tag = 0;                                      // the table set and the GEMM set round differently: a persistent cache never serves the other one's rows
+            m.generation = ++g_model_generation;
+        }
         return AZ_OK;
     }
     if (is("net_fp8") && (value == 0 || value == 1)) {
@@ -1359,6 +1386,7 @@ az_status az_reset_stats(az_engine* e) {
 // ---- NNet ------------------------------------------------------------------------------------
 az_status az_net_set_kind(az_engine* e, int32_t model_id, az_net_kind kind, uint64_t salt) {
     if (!e || (kind != AZ_NET_STUB && kind != AZ_NET_HASH)) return fail(e, AZ_ERR_BAD_ARGUMENT, "kind must be STUB or HASH");
+    if (az_status sr = session_model_refusal(e, "az_net_set_kind", model_id)) return sr;
     NetModel& m = e->nets[model_id];
     m.kind = kind;
     // two hash nets with the same salt but different model ids differ (oracle: HashNet::predict)
@@ -1383,6 +1411,7 @@ az_status az_net_free(az_engine* e, int32_t model_id) {
     if (!e) return AZ_ERR_BAD_ARGUMENT;
     auto it = e->nets.find(model_id);
     if (it == e->nets.end()) return fail(e, AZ_ERR_NO_MODEL, "model id not initialised");
+    if (az_status sr = session_model_refusal(e, "az_net_free", model_id)) return sr;      // the session holds a pointer to it
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream);
     if (it->second.conv) convnet_destroy(it->second.conv);
@@ -1425,6 +1454,7 @@ az_status az_net_get_class(az_engine* e, int32_t model_id, int32_t* stored, int3
 
 az_status az_net_init_random(az_engine* e, int32_t model_id, uint64_t seed) {
     if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (az_status sr = session_model_refusal(e, "az_net_init_random", model_id)) return sr;
     try {
         HIPCHK(hipSetDevice(e->device));
         NetModel* m;
@@ -1442,6 +1472,7 @@ int64_t az_net_param_count(const az_engine* e) { return e ? convnet_param_count(
 
 az_status az_net_set_params(az_engine* e, int32_t model_id, const float* params, int64_t n) {
     if (!e || !params) return AZ_ERR_BAD_ARGUMENT;
+    if (az_status sr = session_model_refusal(e, "az_net_set_params", model_id)) return sr;
     if (n != convnet_param_count(e->cfg.net_channels)) return fail(e, AZ_ERR_BAD_ARGUMENT, "parameter count mismatch");
     try {
         HIPCHK(hipSetDevice(e->device));
@@ -1484,6 +1515,7 @@ az_status az_net_save(az_engine* e, int32_t model_id, const char* path) {
 
 az_status az_net_load(az_engine* e, int32_t model_id, const char* path) {
     if (!e || !path) return AZ_ERR_BAD_ARGUMENT;
+    if (az_status sr = session_model_refusal(e, "az_net_load", model_id)) return sr;
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(e, AZ_ERR_IO, std::string("cannot read ") + path);
     char magic[8];
@@ -1921,6 +1953,7 @@ az_status az_net_train_step(az_engine* e, const float* boards, const float* pis,
 az_status az_net_train_end(az_engine* e, int32_t model_id) {
     if (!e) return AZ_ERR_BAD_ARGUMENT;
     if (!e->train_open) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_end: no open training session");
+    if (az_status sr = session_model_refusal(e, "az_net_train_end", model_id)) return sr;      // the training session stays open
     const int64_t n = az_net_param_count(e);
     std::vector<float> p((size_t)n);
     if (!trainer_get_params(e->trainer, p.data(), n, e->stream)) return fail(e, AZ_ERR_HIP, "trainer_get_params failed");
@@ -1931,6 +1964,8 @@ az_status az_net_train_end(az_engine* e, int32_t model_id) {
 az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id, const float* boards, const float* pis,
                        const float* vs, int64_t n) {
     if (!e || !boards || !pis || !vs || n <= 0) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train: bad argument");
+    if (e->train_open) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train: a training session is open (az_net_train_end first)");
+    if (az_status sr = session_model_refusal(e, "az_net_train", model_id)) return sr;
     if (const char* why = validation_arg_error(e)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_net_train: ") + why).c_str());
     az_status st = az_net_train_begin(e, previous_model_id);
     if (st) return st;
@@ -1952,7 +1987,8 @@ az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id
         e->train_history.clear();
         e->val_history.clear();
         e->val_best = -1;
-        if (!trainer_set_lr_table(t, e->hyper, (int64_t)e->train_epochs * steps, e->stream)) return fail(e, AZ_ERR_HIP, "trainer_set_lr_table failed");
+        // a failure below closes the training session az_net_train_begin opened above: the next az_net_train must not find it open
+        if (!trainer_set_lr_table(t, e->hyper, (int64_t)e->train_epochs * steps, e->stream)) { e->train_open = false; return fail(e, AZ_ERR_HIP, "trainer_set_lr_table failed"); }
         uint64_t gstep = 0;
         for (int epoch = 0; epoch < e->train_epochs; ++epoch) {
             // batches are drawn with replacement (np.random.randint, :130), from the build's counter RNG
@@ -1963,11 +1999,13 @@ az_status az_net_train(az_engine* e, int32_t previous_model_id, int32_t model_id
                 }
             HIPCHK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
             if (!trainer_run_epoch(t, e->hyper, d_boards, d_pis, d_vs, d_idx, steps, b, mix64(e->train_seed ^ 0xD6E8FEB86659FD93ull), gstep,
-                                   e->stream))
+                                   e->stream)) {
+                e->train_open = false;
                 return fail(e, AZ_ERR_HIP, "trainer_run_epoch failed");
+            }
             gstep += (uint64_t)steps;
             double l[2];
-            if (!trainer_read_losses(t, l, true, e->stream)) return fail(e, AZ_ERR_HIP, "trainer_read_losses failed");
+            if (!trainer_read_losses(t, l, true, e->stream)) { e->train_open = false; return fail(e, AZ_ERR_HIP, "trainer_read_losses failed"); }
             e->train_history.push_back((float)(l[0] / (double)steps));
             e->train_history.push_back((float)(l[1] / (double)steps));
             bool stop = false;
@@ -2123,6 +2161,7 @@ az_status az_net_train_samples(az_engine* e, int32_t previous_model_id, int32_t 
 
 az_status az_net_train_ema(az_engine* e, int32_t model_id) {
     if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (az_status sr = session_model_refusal(e, "az_net_train_ema", model_id)) return sr;
     if (!e->trainer || !e->train_ema_session)
         return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_ema: the last az_net_train_begin did not see \"train_ema_decay_e9\" > 0");
     try {
@@ -2271,6 +2310,7 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
                                   float* pi, uint16_t* counts, float* q) {
     if (!t || !states || !pi) return AZ_ERR_BAD_ARGUMENT;
     az_engine* e = t->e;
+    if (az_status sr = session_refusal(e, "az_tree_get_action_prob")) return sr;       // a search sizes, clears and retags the evaluation cache
     if (t->shared) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_tree_get_action_prob on a shared tree batch: use az_tree_slot_get_action_prob");
     NetModel* net;
     az_status st = find_net(e, t->model_id, &net);
@@ -2365,6 +2405,7 @@ az_status az_tree_share(az_tree* t, int32_t window_us) {
         return AZ_OK;
     }
     az_engine* e = t->e;
+    if (az_status sr = session_refusal(e, "az_tree_share")) return sr;
     try {
         HIPCHK(hipSetDevice(e->device));
         const int G = t->th.d.G;
@@ -2404,6 +2445,12 @@ az_status az_tree_slot_get_action_prob(az_tree* t, int32_t slot, const uint64_t*
     SharedTrees& sh = *t->shared;
     if (!state || !pi) {
         if (sh.comb.holds(slot)) set_slot_error(sh, slot, "az_tree_slot_get_action_prob: state and pi are required");
+        return AZ_ERR_BAD_ARGUMENT;
+    }
+    // a batch shared before the session was opened: its searches would run prepare_cache under the session.  No slot call is in flight
+    // while another entry runs on the engine (the header's threading rule), so the session pointer is stable here
+    if (t->e->sp_session) {
+        if (sh.comb.holds(slot)) set_slot_error(sh, slot, "az_tree_slot_get_action_prob: refused while a self-play session is open (az_selfplay_end first)");
         return AZ_ERR_BAD_ARGUMENT;
     }
     SlotCall c{state, temp, seed, game_id, pi, counts, q, AZ_ERR_HIP};
@@ -2760,6 +2807,7 @@ az_status az_selfplay_begin(az_engine* e, const az_selfplay_params* p) {
         std::unique_ptr<SelfplaySession> ss;
         az_status st = selfplay_begin_impl(e, p, ss);
         if (st) return st;
+        e->sp_model_id = p->model_id;
         e->sp_session = ss.release();
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
@@ -2981,7 +3029,10 @@ az_status match_run(az_engine* e, const MatchParams& m, uint64_t* pair_wld, int8
         bool any_dedup = false;
         for (int k = 0; k < K; ++k) { launch_reset_trees(lease[k]->d, nullptr, s); any_dedup = any_dedup || dedup_applies(e, *nets[k]); }
         prepare_cache(e, any_dedup, (uint64_t)PN * AZ_MAX_PLIES * ((uint64_t)m.num_sims + 1), s);
-        for (int k = 0; k < K; ++k) (void)cache_for(e, *nets[k]);      // all tags are fixed before the first fork (retagging may clear the cache)
+        // all tags are fixed before the first fork (retagging may clear the cache).  Two passes: when the 15-bit counter wraps at one of
+        // the models, the models tagged before it lose their tags again, and the second pass hands them new ones (K <= 16: no second wrap)
+        for (int pass = 0; pass < 2; ++pass)
+            for (int k = 0; k < K; ++k) (void)cache_for(e, *nets[k]);
         SearchParams sp{(uint32_t)m.max_depth, (float)m.cpuct};
         az_status result = AZ_OK;
         for (int ply = 0; ply <= AZ_MAX_PLIES; ++ply) {
@@ -3062,6 +3113,7 @@ az_status match_run(az_engine* e, const MatchParams& m, uint64_t* pair_wld, int8
 
 az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], int8_t* results) {
     if (!e || !p || !out_wld) return AZ_ERR_BAD_ARGUMENT;
+    if (az_status sr = session_refusal(e, "az_arena")) return sr;
     if (p->num_games < 0 || p->num_sims <= 0 || p->max_depth < 0 || p->reserve < 8)
         return fail(e, AZ_ERR_BAD_ARGUMENT, "az_arena: bad argument");
     // unsharded: num/2 games per seating (src/arena.rs:83, an odd game is dropped); sharded: this rank's range of an
@@ -3940,6 +3992,14 @@ long long az_diag_fp8_skinny_launches(az_engine* e) {
     long long n = 0;
     for (NetWorkspace* w : e->ws) n += (long long)netws_fp8_skinny_launches(w);
     return n;
+}
+// Diagnostic library only: the 15-bit counter that hands out evaluation-cache tags (retag_model), so that a test can place its wrap.
+// Returns the previous value, or -1 when the value is outside 1 .. 0x8000.
+long long az_diag_set_next_cache_tag(az_engine* e, long long next) {
+    if (!e || next < 1 || next > 0x8000) return -1;
+    const long long was = (long long)e->next_cache_tag;
+    e->next_cache_tag = (uint64_t)next;
+    return was;
 }
 // Diagnostic library only: the trainer's workspace after an az_net_train_step (az_train.h TrainDiagBuf: z, a, mean, invstd of a layer,
 // the heads' logits / dhead / per-sample losses, and -- from steps taken while keep is on -- every layer's d loss / d a and dz).  keep:

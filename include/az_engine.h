@@ -628,7 +628,35 @@ az_status az_selfplay(az_engine* e, const az_selfplay_params* p, az_samples* out
  * the seed and the net alone) -- while the slots they freed already play later episodes.  A host that fetches its episodes in
  * chunks (one training-set shard, one bench step at a time) thereby pays the drain of the last slots once per session, not
  * once per chunk.  az_selfplay_end closes the session (az_destroy does too); one session per engine; the model may not be
- * changed while it is open.  az_selfplay is begin + next(n_games) + end. */
+ * changed while it is open.  az_selfplay is begin + next(n_games) + end.
+ *
+ * THE SESSION CONTRACT (calls interleaved with an open session; tests/session_contract.py lists every export and every option key
+ * with its class, tests/test_session_contract_gpu.py holds each row to it under both drivers, lock-step and "selfplay_async").  An open
+ * session owns its model, its view of the evaluation cache and the options it captured at az_selfplay_begin.  Between az_selfplay_begin
+ * and az_selfplay_end every other call is of exactly one class:
+ *   REFUSED   AZ_ERR_BAD_ARGUMENT on entry, before any work, with an az_last_error that names the entry (the slot call: with
+ *             az_tree_slot_error).  Nothing changes: every option and counter reads as before, the session stays usable and its
+ *             remaining chunks are what they would have been.  These are
+ *               - every entry that runs a tree search (a search sizes, clears and retags the evaluation cache): az_selfplay,
+ *                 az_selfplay_begin, az_arena, az_tournament, az_tree_get_action_prob, az_tree_slot_get_action_prob, az_tree_share;
+ *               - the sample and solver entries that use the engine's workspaces: az_samples_merge, _blend_z, _surprise, _holdout,
+ *                 az_net_train_samples, az_net_train_draw, az_solve, az_move_quality;
+ *               - any change of a conv model's class by az_net_set_class (a call that leaves the stored class as it is returns AZ_OK);
+ *               - the options "net_fp8", "eval_mirror", "conv2_table", "eval_dedup", "eval_cache_log2", "eval_cache_persist",
+ *                 "eval_cache_max_stones", "selfplay_async", "selfplay_async_launches", "selfplay_async_iters", "selfplay_record_search"
+ *                 and the root-move keys (root noise, playout cap, forced playouts, Gumbel).
+ *   BY MODEL  refused, as above, when the call's destination is the session's model id, inert for any other id: az_net_free,
+ *             az_net_set_kind, az_net_init_random, az_net_load, az_net_set_params, az_net_train, az_net_train_end, az_net_train_ema.
+ *             (Should a write reach the session's model all the same, az_selfplay_next notices the changed generation and refuses.)
+ *   INERT     accepted; the session's remaining chunks are bit for bit those of the undisturbed session, and the call returns what it
+ *             returns with no session open: every other entry (the predicts and az_net_evaluate on any model, the session's included;
+ *             the getters; az_tree_create / _reset / _destroy and the tree's logs; az_get_stats / az_reset_stats; the az_comm_* entries
+ *             and the collectives; az_net_train_begin / _step; every other option: the bit-identical kernel and schedule switches, the
+ *             profile and trainer keys, "arena_opening_plies").
+ * az_destroy with a session open closes it first.
+ * A TRAINING session (az_net_train_begin .. az_net_train_end) has a rule of the same kind: while it is open az_net_train,
+ * az_net_train_samples, az_net_train_draw and az_net_train_set_validation are refused; a second az_net_train_begin is a RESTART -- the
+ * open session is dropped without storing anything, and what follows is bit for bit what follows a first az_net_train_begin. */
 az_status az_selfplay_begin(az_engine* e, const az_selfplay_params* p);
 az_status az_selfplay_next(az_engine* e, int32_t n_games, az_samples* out);
 az_status az_selfplay_end(az_engine* e);

@@ -182,6 +182,7 @@ def test_fork_is_bit_identical_at_c512(e512, b):
             e512.train_begin(1)
             out.append(e512.train_step(boards, pis, vs, mask_seed=99, apply=False, want_grads=True))
         assert out[0][0] == out[1][0] and np.array_equal(out[0][1], out[1][1])
+        e512.train_end(3)                         # az_net_train is refused while a step session is open; id 3 is overwritten below
         n = 3 * b
         tb, tp, tv = make_batch(n, seed=7000 + b)
         for key, val in (("train_epochs", 1), ("train_batch", b), ("train_seed", 5)):
@@ -289,6 +290,10 @@ def test_az_net_train_replays_at_the_batch_bounds(e512, batch):
     n, epochs, seed = 2 * batch, 2, 4321
     boards, pis, vs = make_batch(n, seed=77 + batch)
     e512.net_init_random(8, seed=3)
+    # the module's engine is shared: a step session that an earlier test left open (a second az_net_train_begin restarts it) is closed
+    # here, since az_net_train is refused while one is open; id 9 is overwritten below
+    e512.train_begin(8)
+    e512.train_end(9)
     e512.set_option("train_dropout_e6", 300000)
     for key, val in (("train_epochs", epochs), ("train_batch", batch), ("train_seed", seed)):
         e512.set_option(key, val)
