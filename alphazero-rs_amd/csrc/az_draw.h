@@ -88,7 +88,7 @@ void launch_draw_scan(const uint32_t* w, int64_t n, uint64_t* Q, uint64_t* bsum,
 // throughout unless `mirror`).  Q == NULL: all weights 1 and W = n
 void launch_draw_rows(const uint64_t* Q, int64_t n, uint64_t W, uint64_t seed, uint64_t t0, int64_t steps, int b, bool mirror, int64_t* idx,
                       uint8_t* mir, hipStream_t s);
-// *bad |= 1 where a state has overlapping stones or bits outside the 7 x 6 board (k_merge_keys' test)
+// *bad |= sample_state_bits of az_samples.h: a state with overlapping stones or bits outside the 7 x 6 board
 void launch_draw_check_states(const ulonglong2* states, int64_t n, uint32_t* bad, hipStream_t s);
 #endif
 

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "az_game.h"
+#include "az_samples.h"
 
 namespace az {
 
@@ -109,9 +110,9 @@ __global__ __launch_bounds__(256) void k_draw_check_states(const ulonglong2* __r
     uint32_t mine_bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const ulonglong2 s = states[i];
-        if ((s.x & s.y) || ((s.x | s.y) & ~C4_FULL)) mine_bad = 1u;
+        mine_bad |= sample_state_bits(s.x, s.y);
     }
-    if (mine_bad) atomicOr(bad, 1u);
+    if (mine_bad) atomicOr(bad, mine_bad);
 }
 
 inline unsigned draw_grid(int64_t items) { return (unsigned)std::min<int64_t>((items + 255) / 256, 65536); }

@@ -30,6 +30,7 @@
 #include "az_solve.h"
 #include "az_target.h"
 #include "az_rating.h"
+#include "az_samples.h"
 #include "az_train.h"
 #include "az_tree.h"
 #include "az_gumbel.h"
@@ -479,6 +480,11 @@ struct az_engine {
             p = nullptr; cap = 0;
             ++serial;
         }
+        // a workspace sized by the call: given back first when the call needs under a quarter of more than 256 MiB (merge_scratch's rule below)
+        void* fit(size_t bytes, hipStream_t s) {
+            if (cap > ((size_t)1 << 28) && cap / 4 > bytes) release(s);
+            return ensure(bytes, s);
+        }
         ~Scratch() { if (p) (void)hipFree(p); }
     } comm_scratch;
     Scratch score_scratch;          // workspace of az_net_evaluate / az_samples_holdout and of the per-epoch validation; follows merge_scratch's rule
@@ -548,6 +554,30 @@ az_status fail_hip(az_engine* e, const HipFail& f) {
     char buf[512];
     std::snprintf(buf, sizeof buf, "HIP error %d (%s) at %s", (int)f.code, hipGetErrorString(f.code), f.what);
     return fail(e, AZ_ERR_HIP, buf);
+}
+
+// ---- a window of training tuples through the C ABI (csrc/az_samples.h) -------------------------------------------------------------------
+// what a window lacks, for the caller to put its own name and subject in front of; allow_empty: a window of no tuples needs no array
+const char* samples_shape_error(const az_samples* smp, bool allow_empty) {
+    if (allow_empty && smp->count == 0) return nullptr;
+    return (!smp->pis || !smp->zs || (!smp->states && !smp->boards)) ? "pis, zs and states or boards" : nullptr;
+}
+// the window to the device: its states, or without states its boards, to d_in; pis and zs
+SampleWindow stage_window(void* d_in, void* d_pis, void* d_zs, const az_samples* smp, hipStream_t s) {
+    const size_t N = (size_t)smp->count;
+    if (smp->states) HIPCHK(hipMemcpyAsync(d_in, smp->states, N * 16, hipMemcpyDefault, s));
+    else HIPCHK(hipMemcpyAsync(d_in, smp->boards, N * AZ_FEATURES * 4, hipMemcpyDefault, s));
+    HIPCHK(hipMemcpyAsync(d_pis, smp->pis, N * AZ_ACTIONS * 4, hipMemcpyDefault, s));
+    HIPCHK(hipMemcpyAsync(d_zs, smp->zs, N * 4, hipMemcpyDefault, s));
+    return {smp->states ? (const ulonglong2*)d_in : nullptr, smp->states ? nullptr : (const float*)d_in, (const float*)d_pis, (const float*)d_zs};
+}
+// the verdict word of a validating pass, behind one synchronisation of the stream
+uint32_t read_verdict(const uint32_t* d_bad, hipStream_t s) {
+    uint32_t bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return bad;
 }
 
 // The root-move options as the kernels take them, for searches of num_sims simulations at cpuct_f on the trees of th.  Each option that is
@@ -1634,12 +1664,6 @@ void score_enqueue(az_engine* e, const NetModel& m, char* work, const ScoreSet& 
     }
     HIPCHK(hipGetLastError());
 }
-const char* score_bad_text(uint32_t bad) {
-    if (bad & SCORE_BAD_FEATURE) return "a boards feature that is not 0 or 1, or a cell set in both planes";
-    if (bad & SCORE_BAD_STATE) return "a state with overlapping stones or bits outside the 7x6 board";
-    if (bad & SCORE_BAD_VALUE) return "a pi that is NaN or outside [0, 1], or a z that is NaN or outside [-1, 1]";
-    return nullptr;
-}
 const char* score_sum_text(const uint64_t* sums) {
     if (sums[4] == 0) return "the weights sum to 0";
     if (sums[4] > SCORE_MAX_WEIGHT) return "the weights sum to more than 2^24";
@@ -1664,7 +1688,7 @@ az_status az_net_evaluate(az_engine* e, int32_t model_id, const az_samples* smp,
     if (!smp || !score) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_evaluate: the samples and score are required");
     const int64_t n = smp->count;
     if (n < 1 || n > SCORE_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_evaluate: 1 .. 2^24 tuples");
-    if (!smp->pis || !smp->zs || (!smp->states && !smp->boards)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_evaluate: the samples need pis, zs and states or boards");
+    if (const char* why = samples_shape_error(smp, false)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_evaluate: the samples need ") + why);
     NetModel* m;
     az_status st = find_net(e, model_id, &m);
     if (st) return st;
@@ -1674,34 +1698,27 @@ az_status az_net_evaluate(az_engine* e, int32_t model_id, const az_samples* smp,
         hipStream_t s = e->stream;
         const size_t N = (size_t)n;
         const bool from_boards = !smp->states;
-        size_t total = 0;
-        auto need = [&](size_t bytes) { const size_t off = total; total += score_pad(bytes); return off; };
+        Carve c;
         // [hdr: verdict, sums] [inputs] [validated states] [per-tuple outputs] [the forwards' part]
-        const size_t o_hdr = need(256), o_in = need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_st = need(N * 16), o_pi = need(N * 28), o_z = need(N * 4),
-                     o_w = need(weights ? N * 4 : 0), o_ce = need(ce ? N * 4 : 0), o_se = need(se ? N * 4 : 0), o_kl = need(kl ? N * 4 : 0),
-                     o_work = need(score_work_bytes(e));
-        if (e->score_scratch.cap > ((size_t)1 << 28) && e->score_scratch.cap / 4 > total) e->score_scratch.release(s);
-        char* base = (char*)e->score_scratch.ensure(total, s);
+        const size_t o_hdr = c.need(256), o_in = c.need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_st = c.need(N * 16), o_pi = c.need(N * 28),
+                     o_z = c.need(N * 4), o_w = c.need(weights ? N * 4 : 0), o_ce = c.need(ce ? N * 4 : 0), o_se = c.need(se ? N * 4 : 0),
+                     o_kl = c.need(kl ? N * 4 : 0), o_work = c.need(score_work_bytes(e));
+        char* base = (char*)e->score_scratch.fit(c.total, s);
         uint32_t* d_bad = (uint32_t*)(base + o_hdr);
         uint64_t* d_sums = (uint64_t*)(base + o_hdr + 8);
         // the whole window is staged once
         HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
-        HIPCHK(hipMemcpyAsync(base + o_in, from_boards ? (const void*)smp->boards : (const void*)smp->states, from_boards ? N * AZ_FEATURES * 4 : N * 16,
-                              hipMemcpyDefault, s));
-        HIPCHK(hipMemcpyAsync(base + o_pi, smp->pis, N * 28, hipMemcpyDefault, s));
-        HIPCHK(hipMemcpyAsync(base + o_z, smp->zs, N * 4, hipMemcpyDefault, s));
+        const SampleWindow in = stage_window(base + o_in, base + o_pi, base + o_z, smp, s);
         if (weights) HIPCHK(hipMemcpyAsync(base + o_w, weights, N * 4, hipMemcpyDefault, s));
-        launch_score_states(from_boards ? nullptr : (const ulonglong2*)(base + o_in), from_boards ? (const float*)(base + o_in) : nullptr,
-                            (const float*)(base + o_pi), (const float*)(base + o_z), 1, n, (ulonglong2*)(base + o_st), d_bad, s);
-        const ScoreSet w{n, (const ulonglong2*)(base + o_st), (const float*)(base + o_pi), (const float*)(base + o_z),
-                         weights ? (const uint32_t*)(base + o_w) : nullptr};
+        launch_score_states(in, 1, n, (ulonglong2*)(base + o_st), d_bad, s);
+        const ScoreSet w{n, (const ulonglong2*)(base + o_st), in.pis, in.zs, weights ? (const uint32_t*)(base + o_w) : nullptr};
         const ScoreOut o{ce ? (float*)(base + o_ce) : nullptr, se ? (float*)(base + o_se) : nullptr, kl ? (float*)(base + o_kl) : nullptr};
         score_enqueue(e, *m, base + o_work, w, d_sums, o);
         uint64_t hdr[1 + SCORE_SUMS] = {0, 0, 0, 0, 0, 0};
         HIPCHK(hipMemcpyAsync(hdr, base + o_hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));                    // the one synchronisation
         resolve_profile(e);
-        if (const char* why = score_bad_text((uint32_t)hdr[0])) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_evaluate: ") + why);
+        if (const char* why = sample_bad_text((uint32_t)hdr[0], true)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_evaluate: ") + why);
         if (const char* why = score_sum_text(hdr + 1)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_evaluate: ") + why);
         score[0] = (double)n;
         score[1] = (double)hdr[1 + 4];
@@ -1724,35 +1741,25 @@ az_status az_samples_holdout(az_engine* e, const az_samples* smp, int64_t share_
     if (share_e6 < 0 || share_e6 > TARGET_E6) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: share_e6 must be in 0 .. 1000000");
     const int64_t n = smp->count;
     if (n < 0 || n > SCORE_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: 0 .. 2^24 tuples");
+    if (const char* why = samples_shape_error(smp, true)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_samples_holdout: the samples need ") + why);
     if (n == 0) return AZ_OK;
-    if (!smp->pis || !smp->zs || (!smp->states && !smp->boards)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: the samples need pis, zs and states or boards");
     ScopedTimer timer{e};
     try {
         HIPCHK(hipSetDevice(e->device));
         hipStream_t s = e->stream;
         const size_t N = (size_t)n;
         const bool from_boards = !smp->states;
-        size_t total = 0;
-        auto need = [&](size_t bytes) { const size_t off = total; total += score_pad(bytes); return off; };
-        const size_t o_hdr = need(256), o_in = need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_st = need(N * 16), o_pi = need(N * 28), o_z = need(N * 4),
-                     o_held = need(N);
-        if (e->score_scratch.cap > ((size_t)1 << 28) && e->score_scratch.cap / 4 > total) e->score_scratch.release(s);
-        char* base = (char*)e->score_scratch.ensure(total, s);
+        Carve c;
+        const size_t o_hdr = c.need(256), o_in = c.need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_st = c.need(N * 16), o_pi = c.need(N * 28),
+                     o_z = c.need(N * 4), o_held = c.need(N);
+        char* base = (char*)e->score_scratch.fit(c.total, s);
         uint32_t* d_bad = (uint32_t*)(base + o_hdr);
         HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
-        HIPCHK(hipMemcpyAsync(base + o_in, from_boards ? (const void*)smp->boards : (const void*)smp->states, from_boards ? N * AZ_FEATURES * 4 : N * 16,
-                              hipMemcpyDefault, s));
-        HIPCHK(hipMemcpyAsync(base + o_pi, smp->pis, N * 28, hipMemcpyDefault, s));
-        HIPCHK(hipMemcpyAsync(base + o_z, smp->zs, N * 4, hipMemcpyDefault, s));
-        launch_score_states(from_boards ? nullptr : (const ulonglong2*)(base + o_in), from_boards ? (const float*)(base + o_in) : nullptr,
-                            (const float*)(base + o_pi), (const float*)(base + o_z), 0, n, (ulonglong2*)(base + o_st), d_bad, s);
+        launch_score_states(stage_window(base + o_in, base + o_pi, base + o_z, smp, s), 0, n, (ulonglong2*)(base + o_st), d_bad, s);
         launch_score_holdout((const ulonglong2*)(base + o_st), n, seed, score_thresh24((uint64_t)share_e6), (uint8_t*)(base + o_held), s);
-        uint32_t bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipGetLastError());
-        if (bad & SCORE_BAD_VALUE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_holdout: a pi or z that is NaN or outside [-1, 1]");
-        if (const char* why = score_bad_text(bad)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_samples_holdout: ") + why);
+        const uint32_t bad = read_verdict(d_bad, s);
+        // a value fault is reported before a feature or a state fault here
+        if (const char* why = sample_bad_text(bad & SAMPLE_BAD_VALUE ? SAMPLE_BAD_VALUE : bad, false)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_samples_holdout: ") + why);
         HIPCHK(hipMemcpy(held, base + o_held, N, hipMemcpyDefault));
         return AZ_OK;
     } catch (const HipFail& f) { return fail_hip(e, f); }
@@ -1834,7 +1841,7 @@ az_status az_net_train_set_validation(az_engine* e, const az_samples* v, const u
         }
         const int64_t n = v->count;
         if (n < 1 || n > SCORE_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_set_validation: 1 .. 2^24 tuples");
-        if (!v->pis || !v->zs || (!v->states && !v->boards)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_set_validation: the samples need pis, zs and states or boards");
+        if (const char* why = samples_shape_error(v, false)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_train_set_validation: the samples need ") + why);
         const size_t N = (size_t)n;
         uint64_t W = (uint64_t)n;
         if (weights) {
@@ -1856,16 +1863,9 @@ az_status az_net_train_set_validation(az_engine* e, const az_samples* v, const u
             DeviceMem in;
             void* d_in = from_boards ? (void*)in.alloc<float>(N * AZ_FEATURES) : (void*)in.alloc<ulonglong2>(N);
             HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), s));
-            HIPCHK(hipMemcpyAsync(d_in, from_boards ? (const void*)v->boards : (const void*)v->states, from_boards ? N * AZ_FEATURES * 4 : N * 16, hipMemcpyDefault, s));
-            HIPCHK(hipMemcpyAsync(d_pi, v->pis, N * 28, hipMemcpyDefault, s));
-            HIPCHK(hipMemcpyAsync(d_z, v->zs, N * 4, hipMemcpyDefault, s));
             if (d_w) HIPCHK(hipMemcpyAsync(d_w, weights, N * 4, hipMemcpyDefault, s));
-            launch_score_states(from_boards ? nullptr : (const ulonglong2*)d_in, from_boards ? (const float*)d_in : nullptr, d_pi, d_z, 1, n, d_st, d_bad, s);
-            uint32_t bad = 0;
-            HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipGetLastError());
-            if (const char* why = score_bad_text(bad)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_train_set_validation: ") + why);
+            launch_score_states(stage_window(d_in, d_pi, d_z, v, s), 1, n, d_st, d_bad, s);
+            if (const char* why = sample_bad_text(read_verdict(d_bad, s), true)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_train_set_validation: ") + why);
         }
         e->val_mem.release();
         std::swap(e->val_mem.ptrs, mem.ptrs);
@@ -2084,8 +2084,7 @@ az_status az_net_train_samples(az_engine* e, int32_t previous_model_id, int32_t 
     if (!s) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_samples: the samples are required");
     const int64_t n = s->count;
     if (const char* why = draw_arg_error(e, n, flags)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_net_train_samples: ") + why).c_str());
-    if (!s->pis || !s->zs || (!s->states && !s->boards))
-        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_samples: the samples need pis, zs and states or boards");
+    if (const char* why = samples_shape_error(s, false)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_train_samples: the samples need ") + why);
     if (const char* why = validation_arg_error(e)) return fail(e, AZ_ERR_BAD_ARGUMENT, (std::string("az_net_train_samples: ") + why).c_str());
     ScopedTimer timer{e};
     std::vector<float> val_params, best_params;
@@ -2100,10 +2099,7 @@ az_status az_net_train_samples(az_engine* e, int32_t previous_model_id, int32_t 
             HIPCHK(hipMemcpyAsync(d_states, s->states, (size_t)n * 16, hipMemcpyDefault, e->stream));
             HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), e->stream));
             launch_draw_check_states(d_states, n, d_bad, e->stream);
-            uint32_t bad = 0;
-            HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-            if (bad) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_net_train_samples: a state with overlapping stones or bits outside the 7x6 board");
+            if (const char* why = sample_bad_text(read_verdict(d_bad, e->stream), false)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_net_train_samples: ") + why);
             src.states = d_states;
         } else {
             float* d_boards = mem.alloc<float>((size_t)n * 84);
@@ -3276,18 +3272,12 @@ az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, a
     if (n < 0 || n > MERGE_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: 0 .. 2^24 tuples");
     if (!dst->pis || !dst->zs) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: dst needs pis and zs");
     if (dst->capacity < n) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: dst->capacity is below src->count");
-    if (n > 0 && (!src->pis || !src->zs || (!src->states && !src->boards)))
-        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: src needs pis, zs and states or boards");
+    if (const char* why = samples_shape_error(src, true)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_samples_merge: src needs ") + why);
     {   // no dst array may overlap a src array: the inputs are read after the first outputs could have been written
         const size_t N = (size_t)n, C = (size_t)dst->capacity;
-        const std::pair<const void*, size_t> in[4] = {{src->states, N * 16}, {src->boards, N * AZ_FEATURES * 4}, {src->pis, N * AZ_ACTIONS * 4}, {src->zs, N * 4}};
-        const std::pair<const void*, size_t> out[5] = {{dst->states, C * 16}, {dst->boards, C * AZ_FEATURES * 4}, {dst->pis, C * AZ_ACTIONS * 4}, {dst->zs, C * 4}, {counts, C * 4}};
-        for (const auto& a : in)
-            for (const auto& b : out) {
-                if (!a.first || !b.first || !a.second || !b.second) continue;
-                const uintptr_t a0 = (uintptr_t)a.first, b0 = (uintptr_t)b.first;
-                if (a0 < b0 + b.second && b0 < a0 + a.second) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a dst array overlaps a src array");
-            }
+        const SampleSpan in[4] = {{src->states, N * 16}, {src->boards, N * AZ_FEATURES * 4}, {src->pis, N * AZ_ACTIONS * 4}, {src->zs, N * 4}};
+        const SampleSpan out[5] = {{dst->states, C * 16}, {dst->boards, C * AZ_FEATURES * 4}, {dst->pis, C * AZ_ACTIONS * 4}, {dst->zs, C * 4}, {counts, C * 4}};
+        if (sample_arrays_overlap(in, out)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a dst array overlaps a src array");
     }
     if (n == 0) { dst->count = 0; return AZ_OK; }
     ScopedTimer timer{e};
@@ -3299,20 +3289,15 @@ az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, a
         const uint32_t T = std::max<uint32_t>(next_pow2_u32(2 * (uint64_t)N), 64u);
         const size_t nb = (N + 255) / 256;
         // one allocation, carved: [hdr] [inputs] [per tuple] [table] [per group] [outputs]
-        size_t total = 0;
-        auto need = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
-        const size_t o_hdr = need(256), o_in_st = need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_in_pi = need(N * 28), o_in_z = need(N * 4),
-                     o_cst = need(N * 16), o_slot = need(N * 4), o_tkey = need((size_t)T * 8), o_tmin = need((size_t)T * 4),
-                     o_trank = need((size_t)T * 4), o_bsum = need(nb * 4), o_first = need(N * 4), o_sums = need(N * 64), o_cnt = need(N * 4),
-                     o_out_st = need(N * 16), o_out_pi = need(N * 28), o_out_z = need(N * 4), o_out_b = need(dst->boards ? N * AZ_FEATURES * 4 : 0);
-        if (e->merge_scratch.cap > ((size_t)1 << 28) && e->merge_scratch.cap / 4 > total) e->merge_scratch.release(s);      // one huge call does not pin its gigabytes
-        char* base = (char*)e->merge_scratch.ensure(total, s);
+        Carve c;
+        const size_t o_hdr = c.need(256), o_in_st = c.need(from_boards ? N * AZ_FEATURES * 4 : N * 16), o_in_pi = c.need(N * 28), o_in_z = c.need(N * 4),
+                     o_cst = c.need(N * 16), o_slot = c.need(N * 4), o_tkey = c.need((size_t)T * 8), o_tmin = c.need((size_t)T * 4),
+                     o_trank = c.need((size_t)T * 4), o_bsum = c.need(nb * 4), o_first = c.need(N * 4), o_sums = c.need(N * 64), o_cnt = c.need(N * 4),
+                     o_out_st = c.need(N * 16), o_out_pi = c.need(N * 28), o_out_z = c.need(N * 4), o_out_b = c.need(dst->boards ? N * AZ_FEATURES * 4 : 0);
+        char* base = (char*)e->merge_scratch.fit(c.total, s);      // one huge call does not pin its gigabytes
         MergeBufs b{};
         b.n = (uint32_t)N;
-        b.in_states = from_boards ? nullptr : (const ulonglong2*)(base + o_in_st);
-        b.in_boards = from_boards ? (const float*)(base + o_in_st) : nullptr;
-        b.in_pis = (const float*)(base + o_in_pi);
-        b.in_zs = (const float*)(base + o_in_z);
+        b.in = stage_window(base + o_in_st, base + o_in_pi, base + o_in_z, src, s);
         b.cst = (ulonglong2*)(base + o_cst);
         b.slot = (uint32_t*)(base + o_slot);
         b.tkey = (unsigned long long*)(base + o_tkey);
@@ -3328,26 +3313,15 @@ az_status az_samples_merge(az_engine* e, const az_samples* src, int32_t flags, a
         b.o_boards = dst->boards ? (float*)(base + o_out_b) : nullptr;
         b.o_pis = (float*)(base + o_out_pi);
         b.o_zs = (float*)(base + o_out_z);
-        if (from_boards) HIPCHK(hipMemcpyAsync(base + o_in_st, src->boards, N * AZ_FEATURES * 4, hipMemcpyDefault, s));
-        else HIPCHK(hipMemcpyAsync(base + o_in_st, src->states, N * 16, hipMemcpyDefault, s));
-        HIPCHK(hipMemcpyAsync(base + o_in_pi, src->pis, N * 28, hipMemcpyDefault, s));
-        HIPCHK(hipMemcpyAsync(base + o_in_z, src->zs, N * 4, hipMemcpyDefault, s));
         HIPCHK(hipMemsetAsync(b.hdr, 0, 256, s));
         HIPCHK(hipMemsetAsync(b.tkey, 0, (size_t)T * 8, s));
         HIPCHK(hipMemsetAsync(b.tmin, 0xFF, (size_t)T * 4, s));
         // 1. keys: every refusal that depends on the data is found here, before anything is written for the caller
         launch_merge_keys(e->cfg.game, b, (flags & AZ_MERGE_CANONICAL) ? 1 : 0, s);
-        uint32_t hdr[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(hdr, b.hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (hdr[0] & MERGE_BAD_FEATURE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a boards feature that is not 0 or 1, or a cell set in both planes");
-        if (hdr[0] & MERGE_BAD_STATE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a state with overlapping stones or bits outside the 7x6 board");
-        if (hdr[0] & MERGE_BAD_VALUE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_merge: a pi or z that is NaN or outside [-1, 1]");
+        if (const char* why = sample_bad_text(read_verdict(b.hdr, s), false)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_samples_merge: ") + why);
         // 2. output ranks in order of first occurrence; m groups
         launch_merge_scan(b, s);
-        HIPCHK(hipMemcpyAsync(hdr, b.hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        const size_t m = hdr[1];
+        const size_t m = read_verdict(b.hdr + 1, s);
         if (m == 0 || m > N) return fail(e, AZ_ERR_HIP, "az_samples_merge: the scan returned an impossible group count");
         // 3. integer sums per group, 4. means or verbatim copies
         HIPCHK(hipMemsetAsync(b.sums, 0, m * 64, s));
@@ -3378,20 +3352,17 @@ az_status az_samples_blend_z(az_engine* e, int64_t n, const float* zs, const flo
     try {
         HIPCHK(hipSetDevice(e->device));
         hipStream_t s = e->stream;
-        const size_t N = (size_t)n, row = (N * 4 + 255) / 256 * 256;
-        const size_t total = 256 + 3 * row;
-        if (e->target_scratch.cap > ((size_t)1 << 28) && e->target_scratch.cap / 4 > total) e->target_scratch.release(s);
-        char* base = (char*)e->target_scratch.ensure(total, s);
-        uint32_t* d_bad = (uint32_t*)base;
-        float *d_z = (float*)(base + 256), *d_r = (float*)(base + 256 + row), *d_o = (float*)(base + 256 + 2 * row);
+        const size_t N = (size_t)n;
+        Carve c;
+        const size_t o_hdr = c.need(256), o_z = c.need(N * 4), o_r = c.need(N * 4), o_o = c.need(N * 4);
+        char* base = (char*)e->target_scratch.fit(c.total, s);
+        uint32_t* d_bad = (uint32_t*)(base + o_hdr);
+        float *d_z = (float*)(base + o_z), *d_r = (float*)(base + o_r), *d_o = (float*)(base + o_o);
         HIPCHK(hipMemsetAsync(d_bad, 0, 256, s));
         HIPCHK(hipMemcpyAsync(d_z, zs, N * 4, hipMemcpyDefault, s));
         HIPCHK(hipMemcpyAsync(d_r, root_q, N * 4, hipMemcpyDefault, s));
         launch_target_blend(d_z, d_r, n, lambda_e6, d_o, d_bad, s);
-        uint32_t bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (bad) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_blend_z: a z or a root_q that is NaN or outside [-1, 1]");
+        if (read_verdict(d_bad, s)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_blend_z: a z or a root_q that is NaN or outside [-1, 1]");
         HIPCHK(hipMemcpyAsync(zs_out, d_o, N * 4, hipMemcpyDefault, s));
         HIPCHK(hipStreamSynchronize(s));
         return AZ_OK;
@@ -3407,7 +3378,7 @@ az_status az_samples_surprise(az_engine* e, const az_samples* src, const float* 
     if (share_e6 < 0 || share_e6 > TARGET_E6) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: share_e6 must be in 0 .. 1000000");
     const long long n = src->count;
     if (n < 0 || n > TARGET_MAX_TUPLES) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: 0 .. 2^24 tuples");
-    if (n > 0 && (!priors || !src->pis || !src->zs || (!src->states && !src->boards)))
+    if (n > 0 && (!priors || samples_shape_error(src, false)))
         return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: needs priors and src's pis, zs and states or boards");
     if (dst) {
         if (!dst->pis || !dst->zs) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: dst needs pis and zs");
@@ -3416,15 +3387,10 @@ az_status az_samples_surprise(az_engine* e, const az_samples* src, const float* 
             return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: dst asks for an array (states / boards) that src does not have");
         // no dst array may overlap a src array, as in az_samples_merge
         const size_t N = (size_t)n, C = (size_t)dst->capacity;
-        const std::pair<const void*, size_t> in[5] = {{src->states, N * 16}, {src->boards, N * AZ_FEATURES * 4}, {src->pis, N * AZ_ACTIONS * 4}, {src->zs, N * 4},
-                                                      {priors, N * AZ_ACTIONS * 4}};
-        const std::pair<const void*, size_t> out[4] = {{dst->states, C * 16}, {dst->boards, C * AZ_FEATURES * 4}, {dst->pis, C * AZ_ACTIONS * 4}, {dst->zs, C * 4}};
-        for (const auto& a : in)
-            for (const auto& b : out) {
-                if (!a.first || !b.first || !a.second || !b.second) continue;
-                const uintptr_t a0 = (uintptr_t)a.first, b0 = (uintptr_t)b.first;
-                if (a0 < b0 + b.second && b0 < a0 + a.second) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a dst array overlaps a src array");
-            }
+        const SampleSpan in[5] = {{src->states, N * 16}, {src->boards, N * AZ_FEATURES * 4}, {src->pis, N * AZ_ACTIONS * 4}, {src->zs, N * 4},
+                                  {priors, N * AZ_ACTIONS * 4}};
+        const SampleSpan out[4] = {{dst->states, C * 16}, {dst->boards, C * AZ_FEATURES * 4}, {dst->pis, C * AZ_ACTIONS * 4}, {dst->zs, C * 4}};
+        if (sample_arrays_overlap(in, out)) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a dst array overlaps a src array");
     }
     if (n == 0) { if (dst) dst->count = 0; return AZ_OK; }
     ScopedTimer timer{e};
@@ -3435,38 +3401,26 @@ az_status az_samples_surprise(az_engine* e, const az_samples* src, const float* 
         const bool st = src->states != nullptr, bd = src->boards != nullptr;
         const bool o_st = dst && dst->states, o_bd = dst && dst->boards;
         const size_t nb = draw_scan_blocks(n);
-        size_t total = 0;
-        auto need = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
+        Carve c;
         // [hdr: bad, SK, W] [inputs] [per tuple] [outputs, 2n rows]
-        const size_t o_hdr = need(256), o_in_st = need(st ? N * 16 : 0), o_in_b = need(bd ? N * AZ_FEATURES * 4 : 0), o_in_pi = need(N * 28),
-                     o_in_z = need(N * 4), o_in_pr = need(N * 28), o_kl = need(N * 4), o_K = need(N * 8), o_cnt = need(N * 4), o_Q = need(N * 8),
-                     o_bsum = need(nb * 8), o_idx = need(dst ? M * 4 : 0), o_out_st = need(o_st ? M * 16 : 0), o_out_b = need(o_bd ? M * AZ_FEATURES * 4 : 0),
-                     o_out_pi = need(dst ? M * 28 : 0), o_out_z = need(dst ? M * 4 : 0);
-        if (e->target_scratch.cap > ((size_t)1 << 28) && e->target_scratch.cap / 4 > total) e->target_scratch.release(s);
-        char* base = (char*)e->target_scratch.ensure(total, s);
+        const size_t o_hdr = c.need(256), o_in_st = c.need(st ? N * 16 : 0), o_in_b = c.need(bd ? N * AZ_FEATURES * 4 : 0), o_in_pi = c.need(N * 28),
+                     o_in_z = c.need(N * 4), o_in_pr = c.need(N * 28), o_kl = c.need(N * 4), o_K = c.need(N * 8), o_cnt = c.need(N * 4), o_Q = c.need(N * 8),
+                     o_bsum = c.need(nb * 8), o_idx = c.need(dst ? M * 4 : 0), o_out_st = c.need(o_st ? M * 16 : 0),
+                     o_out_b = c.need(o_bd ? M * AZ_FEATURES * 4 : 0), o_out_pi = c.need(dst ? M * 28 : 0), o_out_z = c.need(dst ? M * 4 : 0);
+        char* base = (char*)e->target_scratch.fit(c.total, s);
         uint32_t* d_bad = (uint32_t*)(base + o_hdr);
         uint64_t *d_SK = (uint64_t*)(base + o_hdr + 8), *d_W = (uint64_t*)(base + o_hdr + 16);
-        const ulonglong2* d_st = st ? (const ulonglong2*)(base + o_in_st) : nullptr;
-        const float* d_b = bd ? (const float*)(base + o_in_b) : nullptr;
-        const float *d_pi = (const float*)(base + o_in_pi), *d_z = (const float*)(base + o_in_z), *d_pr = (const float*)(base + o_in_pr);
+        const float *d_b = bd ? (const float*)(base + o_in_b) : nullptr, *d_pr = (const float*)(base + o_in_pr);
         float* d_kl = (float*)(base + o_kl);
         uint64_t *d_K = (uint64_t*)(base + o_K), *d_Q = (uint64_t*)(base + o_Q), *d_bsum = (uint64_t*)(base + o_bsum);
         uint32_t* d_cnt = (uint32_t*)(base + o_cnt);
         HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
-        if (st) HIPCHK(hipMemcpyAsync(base + o_in_st, src->states, N * 16, hipMemcpyDefault, s));
-        if (bd) HIPCHK(hipMemcpyAsync(base + o_in_b, src->boards, N * AZ_FEATURES * 4, hipMemcpyDefault, s));
-        HIPCHK(hipMemcpyAsync(base + o_in_pi, src->pis, N * 28, hipMemcpyDefault, s));
-        HIPCHK(hipMemcpyAsync(base + o_in_z, src->zs, N * 4, hipMemcpyDefault, s));
+        const SampleWindow in = stage_window(base + (st ? o_in_st : o_in_b), base + o_in_pi, base + o_in_z, src, s);
+        if (st && bd) HIPCHK(hipMemcpyAsync(base + o_in_b, src->boards, N * AZ_FEATURES * 4, hipMemcpyDefault, s));      // the gather copies both
         HIPCHK(hipMemcpyAsync(base + o_in_pr, priors, N * 28, hipMemcpyDefault, s));
         // 1. KL, K and their integer sum; every refusal that depends on the data is found here, before anything is written for the caller
-        launch_target_kl(d_st, st ? nullptr : d_b, d_pi, d_z, d_pr, n, d_kl, d_K, d_SK, d_bad, s);
-        uint32_t bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (bad & TARGET_BAD_FEATURE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a boards feature that is not 0 or 1, or a cell set in both planes");
-        if (bad & TARGET_BAD_STATE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a state with overlapping stones or bits outside the 7x6 board");
-        if (bad & TARGET_BAD_VALUE) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a pi or z that is NaN or outside [-1, 1]");
-        if (bad & TARGET_BAD_PRIOR) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_samples_surprise: a prior that is NaN or outside [0, 1]");
+        launch_target_kl(in, d_pr, n, d_kl, d_K, d_SK, d_bad, s);
+        if (const char* why = sample_bad_text(read_verdict(d_bad, s), false)) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string("az_samples_surprise: ") + why);
         // 2. copies, 3. their inclusive prefix
         launch_target_copies(d_K, d_SK, n, share_e6, seed, d_cnt, s);
         launch_draw_scan(d_cnt, n, d_Q, d_bsum, d_W, s);
@@ -3476,7 +3430,7 @@ az_status az_samples_surprise(az_engine* e, const az_samples* src, const float* 
         if (dst) {
             if (W > (uint64_t)M) return fail(e, AZ_ERR_HIP, "az_samples_surprise: the scan returned an impossible row count");
             // 4. the gather
-            launch_target_gather(d_Q, n, (int64_t)W, (uint32_t*)(base + o_idx), d_st, d_b, d_pi, d_z, o_st ? (ulonglong2*)(base + o_out_st) : nullptr,
+            launch_target_gather(d_Q, n, (int64_t)W, (uint32_t*)(base + o_idx), in.states, d_b, in.pis, in.zs, o_st ? (ulonglong2*)(base + o_out_st) : nullptr,
                                  o_bd ? (float*)(base + o_out_b) : nullptr, (float*)(base + o_out_pi), (float*)(base + o_out_z), s);
             if (W) {
                 if (o_st) HIPCHK(hipMemcpyAsync(dst->states, base + o_out_st, (size_t)W * 16, hipMemcpyDefault, s));
@@ -3509,10 +3463,6 @@ const char* solve_param_error(int32_t n, uint32_t max_nodes, int32_t min_stones,
     return nullptr;
 }
 
-void solve_release_outsized(az_engine* e, az_engine::Scratch& sc, size_t need) {
-    if (sc.cap > ((size_t)1 << 28) && sc.cap / 4 > need) sc.release(e->stream);
-}
-
 // The search over b.n positions already on the device (states, active, mv, nodes, values set by the caller): sizes the grid, readies the
 // table, launches.
 void solve_on_device(az_engine* e, SolveBufs b, int32_t max_lanes) {
@@ -3527,8 +3477,7 @@ void solve_on_device(az_engine* e, SolveBufs b, int32_t max_lanes) {
     // fixed places: the counters have room for every lane the device can hold, so a slice never moves with the call's lane count
     const size_t off_gens = 256, off_tt = off_gens + ((size_t)e->solve_device_lanes * 4 + 255) / 256 * 256;
     const size_t total = off_tt + (b.tt_log2 ? (lanes * 8) << b.tt_log2 : 0);
-    solve_release_outsized(e, e->solve_table, total);
-    char* base = (char*)e->solve_table.ensure(total, s);
+    char* base = (char*)e->solve_table.fit(total, s);
     if (e->solve_table.serial != e->solve_table_serial || (int)b.tt_log2 != e->solve_table_log2 || lanes > e->solve_table_lanes) {
         HIPCHK(hipMemsetAsync(base, 0, total, s));         // a new allocation, another slice size, or lanes that have no counter yet
         e->solve_table_serial = e->solve_table.serial;
@@ -3560,11 +3509,9 @@ az_status az_solve(az_engine* e, const uint64_t* states, int32_t n, uint32_t max
         HIPCHK(hipSetDevice(e->device));
         hipStream_t s = e->stream;
         const size_t N = (size_t)n;
-        size_t total = 0;
-        auto need = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
-        const size_t o_hdr = need(256), o_st = need(N * 16), o_mv = need(N * 7), o_val = need(N), o_nodes = need(N * 28);
-        solve_release_outsized(e, e->solve_io, total);
-        char* base = (char*)e->solve_io.ensure(total, s);
+        Carve c;
+        const size_t o_hdr = c.need(256), o_st = c.need(N * 16), o_mv = c.need(N * 7), o_val = c.need(N), o_nodes = c.need(N * 28);
+        char* base = (char*)e->solve_io.fit(c.total, s);
         HIPCHK(hipMemcpyAsync(base + o_st, states, N * 16, hipMemcpyDefault, s));
         HIPCHK(hipMemsetAsync(base + o_hdr, 0, 256, s));
         launch_solve_validate((const ulonglong2*)(base + o_st), (uint32_t)N, (uint32_t*)(base + o_hdr), s);
@@ -3604,12 +3551,10 @@ az_status az_move_quality(az_engine* e, const uint64_t* start_boards, const int3
         HIPCHK(hipSetDevice(e->device));
         hipStream_t s = e->stream;
         const size_t N = (size_t)n, P = N * AZ_MAX_PLIES;
-        size_t total = 0;
-        auto need = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
-        const size_t o_hdr = need(256), o_start = need(N * 16), o_len = need(N * 4), o_moves = need(P), o_st = need(P * 16), o_act = need(P),
-                     o_mv = need(P * 7), o_val = need(P), o_nodes = need(P * 28), o_cls = need(P), o_pv = need(P);
-        solve_release_outsized(e, e->solve_io, total);
-        char* base = (char*)e->solve_io.ensure(total, s);
+        Carve c;
+        const size_t o_hdr = c.need(256), o_start = c.need(N * 16), o_len = c.need(N * 4), o_moves = c.need(P), o_st = c.need(P * 16), o_act = c.need(P),
+                     o_mv = c.need(P * 7), o_val = c.need(P), o_nodes = c.need(P * 28), o_cls = c.need(P), o_pv = c.need(P);
+        char* base = (char*)e->solve_io.fit(c.total, s);
         if (start_boards) HIPCHK(hipMemcpyAsync(base + o_start, start_boards, N * 16, hipMemcpyDefault, s));
         HIPCHK(hipMemcpyAsync(base + o_len, game_len, N * 4, hipMemcpyDefault, s));
         HIPCHK(hipMemcpyAsync(base + o_moves, moves, P, hipMemcpyDefault, s));

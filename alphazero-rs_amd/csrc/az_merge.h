@@ -13,22 +13,17 @@
 //   finalise    one thread per group: a group of one copies its tuple's bits, a larger one divides in double and rounds once to f32
 #pragma once
 #include "az_common.h"
+#include "az_samples.h"
 
 namespace az {
 
 constexpr long long MERGE_MAX_TUPLES = 1ll << 24;       // keeps every int64 sum below 2^62
 constexpr int MERGE_FRAC_BITS = 38;                     // q(x) = llrint((double)x * 2^38)
-// bits of hdr[0], the verdict of the keys pass
-constexpr uint32_t MERGE_BAD_VALUE = 1u, MERGE_BAD_STATE = 2u, MERGE_BAD_FEATURE = 4u;
 constexpr uint32_t MERGE_MIRRORED = 1u << 31;           // bit 31 of slot[i]: the tuple's state is the mirror image of its group's
 
 struct MergeBufs {
     uint32_t n;                     // tuples
-    // inputs on the device: states [n] or (states == nullptr) boards [n][84]; pis [n][7]; zs [n]
-    const ulonglong2* in_states;
-    const float* in_boards;
-    const float* in_pis;
-    const float* in_zs;
+    SampleWindow in;                // the inputs on the device
     // per tuple
     ulonglong2* cst;                // [n] the state the tuple is merged under (canonicalised when asked)
     uint32_t* slot;                 // [n] its table slot | MERGE_MIRRORED
@@ -42,7 +37,7 @@ struct MergeBufs {
     uint32_t* first;                // [m] input index of the group's first occurrence
     unsigned long long* sums;       // [m][8] two's-complement int64 sums of q(pi[0..6]), q(z)
     uint32_t* cnt;                  // [m] multiplicity
-    uint32_t* hdr;                  // [0] verdict bits of the keys pass, [1] m
+    uint32_t* hdr;                  // [0] verdict bits of the keys pass (SAMPLE_BAD_* of az_samples.h), [1] m
     // outputs staged on the device, m rows each (boards may be nullptr)
     ulonglong2* o_states;
     float* o_boards;

@@ -1,7 +1,8 @@
 // az_merge.hip -- the kernels of az_samples_merge (position averaging; csrc/az_merge.h).
 // Templates over the Game policy of az_game.h, as the tree kernels are: they use G::State, G::pack, G::canonical and G::feature.  The one
-// thing that is restated here and not taken from the policy is the inverse of G::feature (a state from its two feature planes); both games
-// play on the same 7 x 6 board with the same planes (connect_four_game.rs:219-237), as k_canonicalise of az_engine.hip relies on too.
+// thing that is not taken from the policy is the inverse of G::feature (a state from its two feature planes), which the window check of
+// az_samples.h holds; both games play on the same 7 x 6 board with the same planes (connect_four_game.rs:219-237), as k_canonicalise of
+// az_engine.hip relies on too.
 #include "az_merge.h"
 
 #include <algorithm>
@@ -9,6 +10,9 @@
 #include "az_game.h"
 
 namespace az {
+
+static_assert(SAMPLE_BOARD == C4_FULL && ConnectFour::ACTIONS == 7 && ConnectFour::FEATURES == 84, "az_samples.h restates az_game.h's board, actions and feature cells");
+
 namespace {
 
 constexpr uint32_t MERGE_BLOCK = 256;
@@ -20,33 +24,8 @@ template <class G>
 __global__ __launch_bounds__(MERGE_BLOCK) void k_merge_keys(MergeBufs b, int canonical) {
     const uint32_t i = blockIdx.x * MERGE_BLOCK + threadIdx.x;
     if (i >= b.n) return;
-    uint32_t bad = 0;
-    uint64_t mine = 0, theirs = 0;
-    if (b.in_states) {
-        const ulonglong2 s = b.in_states[i];
-        mine = s.x;
-        theirs = s.y;
-    } else {
-        const float* f = b.in_boards + (size_t)i * 84;
-        for (int r = 0; r < 6; ++r)
-            for (int c = 0; c < 7; ++c) {
-                const float a = f[r * 7 + c], o = f[42 + r * 7 + c];          // plane 0 = the side to move, row 0 = top
-                const bool a1 = a == 1.0f, o1 = o == 1.0f;
-                if (!((a1 || a == 0.0f) && (o1 || o == 0.0f)) || (a1 && o1)) bad |= MERGE_BAD_FEATURE;
-                const uint64_t bit = 1ull << (c * 7 + (5 - r));
-                if (a1) mine |= bit;
-                if (o1) theirs |= bit;
-            }
-    }
-    if ((mine & theirs) || ((mine | theirs) & ~C4_FULL)) bad |= MERGE_BAD_STATE;
-    for (int a = 0; a < 7; ++a) {
-        const float x = b.in_pis[(size_t)i * 7 + a];
-        if (!(x >= -1.0f && x <= 1.0f)) bad |= MERGE_BAD_VALUE;              // a NaN fails both comparisons
-    }
-    {
-        const float z = b.in_zs[i];
-        if (!(z >= -1.0f && z <= 1.0f)) bad |= MERGE_BAD_VALUE;
-    }
+    uint64_t mine, theirs;
+    const uint32_t bad = sample_check(b.in, i, false, &mine, &theirs);
     if (bad) {                                   // the call is refused: nothing behind this pass runs
         atomicOr(&b.hdr[0], bad);
         return;
@@ -177,8 +156,8 @@ __global__ __launch_bounds__(MERGE_BLOCK) void k_merge_accumulate(MergeBufs b) {
             rank = b.trank[sl & ~MERGE_MIRRORED];
             const bool mir = (sl & MERGE_MIRRORED) != 0u;
 #pragma unroll
-            for (int a = 0; a < 7; ++a) q[mir ? 6 - a : a] = llrint((double)b.in_pis[(size_t)i * 7 + a] * 0x1p38);
-            q[7] = llrint((double)b.in_zs[i] * 0x1p38);
+            for (int a = 0; a < 7; ++a) q[mir ? 6 - a : a] = llrint((double)b.in.pis[(size_t)i * 7 + a] * 0x1p38);
+            q[7] = llrint((double)b.in.zs[i] * 0x1p38);
         }
         // a whole wave on one group: sum across the wave, one lane goes on
         unsigned long long copies = 1ull;
@@ -220,8 +199,8 @@ __global__ __launch_bounds__(MERGE_BLOCK) void k_merge_finalise(MergeBufs b, uin
     b.o_states[j] = b.cst[i];
     if (k == 1u) {                               // verbatim: no arithmetic touches the values
         const bool mir = (b.slot[i] & MERGE_MIRRORED) != 0u;
-        for (int a = 0; a < 7; ++a) b.o_pis[(size_t)j * 7 + (mir ? 6 - a : a)] = b.in_pis[(size_t)i * 7 + a];
-        b.o_zs[j] = b.in_zs[i];
+        for (int a = 0; a < 7; ++a) b.o_pis[(size_t)j * 7 + (mir ? 6 - a : a)] = b.in.pis[(size_t)i * 7 + a];
+        b.o_zs[j] = b.in.zs[i];
         return;
     }
     const double div = (double)((long long)k << MERGE_FRAC_BITS);          // k * 2^38 <= 2^62: exact

@@ -94,12 +94,9 @@ inline bool score_best_stop(const double* hist, int stride, int n, int patience,
 
 #if defined(__HIPCC__)
 // ---- device side (az_score.hip) --------------------------------------------------------------------------------------------------------
-constexpr uint32_t SCORE_BAD_VALUE = 1u, SCORE_BAD_STATE = 2u, SCORE_BAD_FEATURE = 4u;      // verdict bits, as az_merge.h's
-// one thread per tuple: the state (given, or rebuilt from its feature planes), pi and z validated as az_samples_merge validates them
-// (strict = 0: both in [-1, 1]) or as az_samples_blend_z / az_samples_surprise do (strict = 1: target_is_prior(pi), target_in_unit(z));
-// out[i] = the state, or the empty board where the tuple is refused (nothing invalid ever reaches a forward); *bad |= the verdict bits
-void launch_score_states(const ulonglong2* states, const float* boards, const float* pis, const float* zs, int strict, int64_t n, ulonglong2* out,
-                         uint32_t* bad, hipStream_t s);
+// one thread per tuple: sample_check of az_samples.h (strict = its strict_pi); out[i] = the state, or the empty board where the tuple is
+// refused (nothing invalid ever reaches a forward); *bad |= the verdict bits
+void launch_score_states(const SampleWindow& w, int strict, int64_t n, ulonglong2* out, uint32_t* bad, hipStream_t s);
 // one thread per row of a chunk: tuple first + r scores net_pi[r * 8 .. + 7) and net_v[r] (an EvalBatch's rows, read in place) against its
 // target; sums[0 .. 5) += the workgroup's integers (one 64-bit atomic per workgroup and sum); ce / se / kl [n] may be nullptr
 void launch_score(const float* net_pi, const float* net_v, const ulonglong2* states, const float* pis, const float* zs, const uint32_t* weights,

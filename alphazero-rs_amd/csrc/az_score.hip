@@ -17,36 +17,12 @@ constexpr uint32_t SCORE_BLOCK = 256;
 
 inline unsigned score_blocks(int64_t items) { return (unsigned)((items + SCORE_BLOCK - 1) / SCORE_BLOCK); }      // n <= 2^24: at most 65536
 
-__global__ __launch_bounds__(SCORE_BLOCK) void k_score_states(const ulonglong2* __restrict__ states, const float* __restrict__ boards,
-                                                              const float* __restrict__ pis, const float* __restrict__ zs, int strict, int64_t n,
-                                                              ulonglong2* __restrict__ out, uint32_t* __restrict__ bad) {
+__global__ __launch_bounds__(SCORE_BLOCK) void k_score_states(SampleWindow w, int strict, int64_t n, ulonglong2* __restrict__ out,
+                                                              uint32_t* __restrict__ bad) {
     const int64_t i = (int64_t)blockIdx.x * SCORE_BLOCK + threadIdx.x;
     if (i >= n) return;
-    uint32_t b = 0u;
-    uint64_t mine = 0, theirs = 0;
-    if (states) {
-        const ulonglong2 s = states[i];
-        mine = s.x;
-        theirs = s.y;
-    } else {                                     // the inverse of Game::feature, as k_merge_keys restates it
-        const float* f = boards + (size_t)i * 84;
-        for (int r = 0; r < 6; ++r)
-            for (int c = 0; c < 7; ++c) {
-                const float a = f[r * 7 + c], o = f[42 + r * 7 + c];
-                const bool a1 = a == 1.0f, o1 = o == 1.0f;
-                if (!((a1 || a == 0.0f) && (o1 || o == 0.0f)) || (a1 && o1)) b |= SCORE_BAD_FEATURE;
-                const uint64_t bit = 1ull << (c * 7 + (5 - r));
-                if (a1) mine |= bit;
-                if (o1) theirs |= bit;
-            }
-    }
-    if ((mine & theirs) || ((mine | theirs) & ~C4_FULL)) b |= SCORE_BAD_STATE;
-#pragma unroll
-    for (int a = 0; a < TARGET_ACTIONS; ++a) {
-        const float x = pis[(size_t)i * TARGET_ACTIONS + a];
-        if (!(strict ? target_is_prior(x) : target_in_unit(x))) b |= SCORE_BAD_VALUE;
-    }
-    if (!target_in_unit(zs[i])) b |= SCORE_BAD_VALUE;
+    uint64_t mine, theirs;
+    const uint32_t b = sample_check(w, i, strict != 0, &mine, &theirs);
     if (b) atomicOr(bad, b);                     // the call is refused; the forwards behind this pass see an empty board in the tuple's place
     out[i] = b ? make_ulonglong2(0ull, 0ull) : make_ulonglong2(mine, theirs);
 }
@@ -103,10 +79,9 @@ __global__ __launch_bounds__(SCORE_BLOCK) void k_score_holdout(const ulonglong2*
 
 }  // namespace
 
-void launch_score_states(const ulonglong2* states, const float* boards, const float* pis, const float* zs, int strict, int64_t n, ulonglong2* out,
-                         uint32_t* bad, hipStream_t s) {
+void launch_score_states(const SampleWindow& w, int strict, int64_t n, ulonglong2* out, uint32_t* bad, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_score_states, dim3(score_blocks(n)), dim3(SCORE_BLOCK), 0, s, states, boards, pis, zs, strict, n, out, bad);
+    hipLaunchKernelGGL(k_score_states, dim3(score_blocks(n)), dim3(SCORE_BLOCK), 0, s, w, strict, n, out, bad);
 }
 void launch_score(const float* net_pi, const float* net_v, const ulonglong2* states, const float* pis, const float* zs, const uint32_t* weights,
                   int64_t first, int rows, uint64_t* sums, float* ce, float* se, float* kl, hipStream_t s) {

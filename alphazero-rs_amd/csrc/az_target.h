@@ -28,6 +28,7 @@
 #endif
 
 #include "az_noise.h"
+#include "az_samples.h"
 
 namespace az {
 
@@ -85,9 +86,6 @@ AZT_HD float target_blend(int64_t lambda_e6, float z, float R) {
     const float b = azn_div((float)lambda_e6, 1e6f), a = azn_sub(1.0f, b);
     return azn_add(azn_mul(a, z), azn_mul(b, R));
 }
-// what az_samples_blend_z and az_samples_surprise refuse in a pi, a z or an R: a NaN fails both comparisons
-AZT_HD bool target_in_unit(float x) { return x >= -1.0f && x <= 1.0f; }
-AZT_HD bool target_is_prior(float x) { return x >= 0.0f && x <= 1.0f; }
 
 AZT_HD float target_kl(const float* pi, const float* prior) {
     float t = 0.0f;
@@ -114,13 +112,11 @@ AZT_HD uint32_t target_copies(double w, uint64_t seed, uint64_t i) {
 
 #if defined(__HIPCC__)
 // ---- device side (az_target.hip) -----------------------------------------------------------------------------------------------------
-constexpr uint32_t TARGET_BAD_VALUE = 1u, TARGET_BAD_STATE = 2u, TARGET_BAD_FEATURE = 4u, TARGET_BAD_PRIOR = 8u;      // verdict bits
-// out[i] = target_blend(lambda_e6, zs[i], root_q[i]); *bad |= TARGET_BAD_VALUE where either input is NaN or outside [-1, 1]
+// out[i] = target_blend(lambda_e6, zs[i], root_q[i]); *bad |= SAMPLE_BAD_VALUE where either input is NaN or outside [-1, 1]
 void launch_target_blend(const float* zs, const float* root_q, int64_t n, int64_t lambda_e6, float* out, uint32_t* bad, hipStream_t s);
-// pass 1: kl[i], K[i]; *SK += the K of every tuple (one 64-bit integer atomic per workgroup); *bad |= the verdict bits (the validation of
-// az_samples_merge's keys pass, and a prior outside [0, 1]).  states or (states == nullptr) boards
-void launch_target_kl(const ulonglong2* states, const float* boards, const float* pis, const float* zs, const float* priors, int64_t n, float* kl,
-                      uint64_t* K, uint64_t* SK, uint32_t* bad, hipStream_t s);
+// pass 1: kl[i], K[i]; *SK += the K of every tuple (one 64-bit integer atomic per workgroup); *bad |= the verdict bits (sample_check of
+// az_samples.h, and a prior outside [0, 1])
+void launch_target_kl(const SampleWindow& w, const float* priors, int64_t n, float* kl, uint64_t* K, uint64_t* SK, uint32_t* bad, hipStream_t s);
 // pass 2: counts[i] = c_i
 void launch_target_copies(const uint64_t* K, const uint64_t* SK, int64_t n, int64_t share_e6, uint64_t seed, uint32_t* counts, hipStream_t s);
 // pass 4 (behind launch_draw_scan of az_draw.h): output row r is tuple min{ i : Q[i] > r }; every copy bit for bit.  Any output may be nullptr

@@ -26,49 +26,28 @@ __global__ __launch_bounds__(TARGET_BLOCK) void k_target_blend(const float* __re
     uint32_t mine_bad = 0u;
     for (int64_t i = (int64_t)blockIdx.x * TARGET_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * TARGET_BLOCK) {
         const float z = zs[i], r = rq[i];
-        if (!target_in_unit(z) || !target_in_unit(r)) mine_bad = TARGET_BAD_VALUE;
+        if (!sample_in_unit(z) || !sample_in_unit(r)) mine_bad = SAMPLE_BAD_VALUE;
         out[i] = target_blend(lambda_e6, z, r);
     }
     if (mine_bad) atomicOr(bad, mine_bad);
 }
 
 // one thread per tuple; whole workgroups (no early return: the sum below meets in LDS)
-__global__ __launch_bounds__(TARGET_BLOCK) void k_target_kl(const ulonglong2* __restrict__ states, const float* __restrict__ boards,
-                                                            const float* __restrict__ pis, const float* __restrict__ zs, const float* __restrict__ priors,
-                                                            int64_t n, float* __restrict__ kl, u64* __restrict__ K, u64* __restrict__ SK,
-                                                            uint32_t* __restrict__ bad) {
+__global__ __launch_bounds__(TARGET_BLOCK) void k_target_kl(SampleWindow w, const float* __restrict__ priors, int64_t n, float* __restrict__ kl,
+                                                            u64* __restrict__ K, u64* __restrict__ SK, uint32_t* __restrict__ bad) {
     __shared__ u64 s_w[TARGET_BLOCK / 64];
     const int64_t i = (int64_t)blockIdx.x * TARGET_BLOCK + threadIdx.x;
     u64 k = 0ull;
     if (i < n) {
-        uint32_t b = 0u;
-        uint64_t mine = 0, theirs = 0;
-        if (states) {
-            const ulonglong2 s = states[i];
-            mine = s.x;
-            theirs = s.y;
-        } else {                                 // the inverse of Game::feature, as k_merge_keys restates it
-            const float* f = boards + (size_t)i * 84;
-            for (int r = 0; r < 6; ++r)
-                for (int c = 0; c < 7; ++c) {
-                    const float a = f[r * 7 + c], o = f[42 + r * 7 + c];
-                    const bool a1 = a == 1.0f, o1 = o == 1.0f;
-                    if (!((a1 || a == 0.0f) && (o1 || o == 0.0f)) || (a1 && o1)) b |= TARGET_BAD_FEATURE;
-                    const uint64_t bit = 1ull << (c * 7 + (5 - r));
-                    if (a1) mine |= bit;
-                    if (o1) theirs |= bit;
-                }
-        }
-        if ((mine & theirs) || ((mine | theirs) & ~C4_FULL)) b |= TARGET_BAD_STATE;
+        uint64_t mine, theirs;
+        uint32_t b = sample_check(w, i, false, &mine, &theirs);
         float pi[TARGET_ACTIONS], pr[TARGET_ACTIONS];
 #pragma unroll
         for (int a = 0; a < TARGET_ACTIONS; ++a) {
-            pi[a] = pis[(size_t)i * TARGET_ACTIONS + a];
+            pi[a] = w.pis[(size_t)i * TARGET_ACTIONS + a];
             pr[a] = priors[(size_t)i * TARGET_ACTIONS + a];
-            if (!target_in_unit(pi[a])) b |= TARGET_BAD_VALUE;
-            if (!target_is_prior(pr[a])) b |= TARGET_BAD_PRIOR;
+            if (!sample_is_prior(pr[a])) b |= SAMPLE_BAD_PRIOR;
         }
-        if (!target_in_unit(zs[i])) b |= TARGET_BAD_VALUE;
         if (b) atomicOr(bad, b);                 // the call is refused: nothing behind this pass runs
         else {
             const float v = target_kl(pi, pr);
@@ -133,11 +112,10 @@ void launch_target_blend(const float* zs, const float* root_q, int64_t n, int64_
     if (n <= 0) return;
     hipLaunchKernelGGL(k_target_blend, dim3(target_grid(n)), dim3(TARGET_BLOCK), 0, s, zs, root_q, n, lambda_e6, out, bad);
 }
-void launch_target_kl(const ulonglong2* states, const float* boards, const float* pis, const float* zs, const float* priors, int64_t n, float* kl,
-                      uint64_t* K, uint64_t* SK, uint32_t* bad, hipStream_t s) {
+void launch_target_kl(const SampleWindow& w, const float* priors, int64_t n, float* kl, uint64_t* K, uint64_t* SK, uint32_t* bad, hipStream_t s) {
     if (n <= 0) return;
     const unsigned nb = (unsigned)((n + TARGET_BLOCK - 1) / TARGET_BLOCK);          // n <= 2^24: at most 65536 workgroups
-    hipLaunchKernelGGL(k_target_kl, dim3(nb), dim3(TARGET_BLOCK), 0, s, states, boards, pis, zs, priors, n, kl, (u64*)K, (u64*)SK, bad);
+    hipLaunchKernelGGL(k_target_kl, dim3(nb), dim3(TARGET_BLOCK), 0, s, w, priors, n, kl, (u64*)K, (u64*)SK, bad);
 }
 void launch_target_copies(const uint64_t* K, const uint64_t* SK, int64_t n, int64_t share_e6, uint64_t seed, uint32_t* counts, hipStream_t s) {
     if (n <= 0) return;
