@@ -400,13 +400,7 @@ struct az_engine {
     int train_epochs = 10, train_batch = 64;       // connect_four_net.py:13-14
     uint64_t train_seed = 0;
     int train_graph = 1;
-    int train_gemm = 1;
-    int train_gemm3_ring = 1;       // "train_gemm3_ring"
-    int train_fwd_x3 = 1;           // "train_fwd_x3"
-    int train_wgrad_tr = 1;         // "train_wgrad_tr"
-    int train_implicit = 1;         // "train_implicit"
-    int train_fork = 0;             // "train_fork": the wgrad chains of a step on a second stream branch (csrc/az_train.hip)
-    int train_fwd_dma = 1;
+    TrainSwitches train_sw;         // "train_gemm" ... "train_fork": the routes of a step (csrc/az_train_plan.h)
     std::vector<float> train_history;              // (loss_pi, loss_v) mean per epoch of the last az_net_train
     // the opt-in optimiser rules (csrc/az_optim.h), read by az_net_train_begin: "train_weight_decay_e9", "train_clip_norm_e6",
     // "train_lr_warmup_steps", "train_lr_decay", "train_lr_floor_e6", "train_lr_total_steps", "train_ema_decay_e9"
@@ -1263,17 +1257,24 @@ az_status az_set_option(az_engine* e, const char* key, int64_t value) {
     if (is("train_batch") && value >= 2 && value <= TRAIN_MAX_BATCH) { e->train_batch = (int)value; return AZ_OK; }
     if (is("train_seed")) { e->train_seed = (uint64_t)value; return AZ_OK; }
     if (is("train_graph") && (value == 0 || value == 1)) { e->train_graph = (int)value; if (e->trainer) trainer_set_graph(e->trainer, value != 0); return AZ_OK; }
-    if (is("train_gemm3_ring") && (value == 0 || value == 1)) { e->train_gemm3_ring = (int)value; if (e->trainer) trainer_set_gemm3_ring(e->trainer, value != 0); return AZ_OK; }
-    if (is("train_fwd_x3") && (value == 0 || value == 1)) { e->train_fwd_x3 = (int)value; if (e->trainer) trainer_set_fwd_x3(e->trainer, value != 0); return AZ_OK; }
-    if (is("train_wgrad_tr") && (value == 0 || value == 1)) { e->train_wgrad_tr = (int)value; if (e->trainer) trainer_set_wgrad_tr(e->trainer, value != 0); return AZ_OK; }
-    if (is("train_implicit") && (value == 0 || value == 1)) { e->train_implicit = (int)value; if (e->trainer) trainer_set_implicit(e->trainer, value != 0); return AZ_OK; }
-    if (is("train_fork") && (value == 0 || value == 1)) {
-        e->train_fork = (int)value;
-        if (e->trainer) { (void)hipSetDevice(e->device); trainer_set_fork(e->trainer, value != 0); }
+    // the route switches of a step (csrc/az_train_plan.h), each 0 / 1; a live trainer takes the record at once ("train_fork" may create its
+    // second stream: on the engine's device)
+    struct SwitchKey { const char* key; int TrainSwitches::* field; };
+    static const SwitchKey switch_keys[] = {
+        {"train_gemm", &TrainSwitches::gemm},
+        {"train_fwd_dma", &TrainSwitches::fwd_dma},
+        {"train_fwd_x3", &TrainSwitches::fwd_x3},
+        {"train_wgrad_tr", &TrainSwitches::wgrad_tr},
+        {"train_implicit", &TrainSwitches::implicit},
+        {"train_gemm3_ring", &TrainSwitches::gemm3_ring},
+        {"train_fork", &TrainSwitches::fork},
+    };
+    for (const SwitchKey& r : switch_keys) {
+        if (!is(r.key) || (value != 0 && value != 1)) continue;
+        e->train_sw.*r.field = (int)value;
+        if (e->trainer) { (void)hipSetDevice(e->device); trainer_set_switches(e->trainer, e->train_sw); }
         return AZ_OK;
     }
-    if (is("train_gemm") && (value == 0 || value == 1)) { e->train_gemm = (int)value; if (e->trainer) trainer_set_gemm(e->trainer, (int)value); return AZ_OK; }
-    if (is("train_fwd_dma") && (value == 0 || value == 1)) { e->train_fwd_dma = (int)value; if (e->trainer) trainer_set_fwd_dma(e->trainer, value != 0); return AZ_OK; }
     if (is("train_lr_e9") && value > 0) { e->hyper.lr = (float)((double)value * 1e-9); return AZ_OK; }
     if (is("train_dropout_e6") && value >= 0 && value < 1000000) { e->hyper.dropout = (float)((double)value * 1e-6); return AZ_OK; }
     // per-epoch validation (csrc/az_score.h): read when az_net_train / az_net_train_samples begin
@@ -1899,13 +1900,7 @@ az_status az_net_train_begin(az_engine* e, int32_t previous_model_id) {
             e->trainer = trainer_create(e->cfg.net_channels, &err);
             if (!e->trainer) return fail(e, AZ_ERR_HIP, err ? err : "trainer_create failed");
             trainer_set_graph(e->trainer, e->train_graph != 0);
-            trainer_set_gemm(e->trainer, e->train_gemm);
-            trainer_set_fork(e->trainer, e->train_fork != 0);
-            trainer_set_implicit(e->trainer, e->train_implicit != 0);
-            trainer_set_wgrad_tr(e->trainer, e->train_wgrad_tr != 0);
-            trainer_set_fwd_x3(e->trainer, e->train_fwd_x3 != 0);
-            trainer_set_gemm3_ring(e->trainer, e->train_gemm3_ring != 0);
-            trainer_set_fwd_dma(e->trainer, e->train_fwd_dma != 0);
+            trainer_set_switches(e->trainer, e->train_sw);
         }
         const int64_t n = az_net_param_count(e);
         std::vector<float> p((size_t)n);
@@ -3951,8 +3946,13 @@ long long az_diag_set_next_cache_tag(az_engine* e, long long next) {
 // 0, or -1 refused (no training session yet, "train_fork" 1).  read: bytes copied, or -1 and nothing copied.
 int az_diag_train_keep(az_engine* e, int on) {
     if (!e || !e->trainer || hipSetDevice(e->device) != hipSuccess) return -1;
-    if (on && e->train_fork) return -1;
+    if (on && e->train_sw.fork) return -1;
     return trainer_diag_set_keep(e->trainer, on != 0) ? 0 : -1;
+}
+// Diagnostic library only: the plan (csrc/az_train_plan.h train_plan_encode) the trainer would follow for a step of batch b under its
+// current switches -> the int32 count, or -1 (no training session yet, b outside 2 .. 256, cap too small).  Host only, launches nothing.
+int az_diag_train_plan(az_engine* e, int b, int32_t* out, int cap) {
+    return e && e->trainer ? trainer_diag_plan(e->trainer, b, out, cap) : -1;
 }
 long long az_diag_train_read(az_engine* e, int what, int layer, int rows, void* out) {
     if (!e || !e->trainer || !out || hipSetDevice(e->device) != hipSuccess) return -1;

@@ -2,12 +2,15 @@
 //
 // f32 training of the policy+value net on the engine's flat parameter layout (az_net.hip `Layout`, the weights
 // file): forward in BatchNorm training mode, softmax cross-entropy + mean squared error, backward, Adam.
-// Every GEMM (conv layers as im2col x weights, dgrad, wgrad, the FCs) runs on the f32 matrix cores
-// (v_mfma_f32_16x16x4_f32); the column reductions are two-stage and summed in a fixed order, so a step is
-// deterministic run to run.
+// By default conv2..conv4's forward GEMMs run as f16 x 3 on the f16 matrix cores and every backward GEMM above conv1 as bf16 x 3 on the
+// bf16 matrix cores (f32 accumulation), conv1 and the FC forwards on the f32 matrix cores (v_mfma_f32_16x16x4_f32); with "train_gemm" 0
+// every GEMM runs there.  Which kernel chain a layer takes is decided once per step by train_step_plan (az_train_plan.h).  The column
+// reductions are two-stage and every split-K sum is taken in slice order, so a step is deterministic run to run.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "az_train_plan.h"
 
 namespace az {
 
@@ -80,13 +83,9 @@ struct TrainSamples {
 bool trainer_run_epoch_samples(Trainer* t, const TrainHyper& h, const TrainSamples& samples, const int64_t* d_idx, const uint8_t* d_mir,
                                int64_t steps, int b, uint64_t seed_key, uint64_t gstep0, hipStream_t s);
 void trainer_set_graph(Trainer* t, bool on);      // A/B switch: replay a captured graph (default) or launch directly
-void trainer_set_fwd_dma(Trainer* t, bool on);    // 1 (default): forward GEMMs fed by LDS-DMA (k_gemm_f32_dma); 0: register-staged k_gemm_f32
-void trainer_set_fork(Trainer* t, bool on);       // true: a step's wgrad chains on a second stream branch, joined before Adam (default false: no gain)
-void trainer_set_gemm3_ring(Trainer* t, bool on); // true (default): the big bf16 x 3 GEMMs on k_gemm3_ring (one 8-wave workgroup per CU, 3-stage ring)
-void trainer_set_fwd_x3(Trainer* t, bool on);     // true (default): conv2..conv4 forward as f16 x 3 on the f16 matrix cores; false: v_mfma_f32_16x16x4_f32
-void trainer_set_wgrad_tr(Trainer* t, bool on);   // true (default): conv wgrad on k_wgrad3_tr (transposed LDS reads; no transpose kernels)
-void trainer_set_implicit(Trainer* t, bool on);   // true (default): conv2..conv4's GEMMs gather their rows from the activations (no im2col / col2im)
-void trainer_set_gemm(Trainer* t, int mode);      // 1 (default): the GEMMs as bf16 x 3 on the bf16 matrix cores; 0: v_mfma_f32_16x16x4_f32
+// the seven route switches (az_train_plan.h), read by the next step.  The first call with fork on creates the second stream and its events
+// on the current device; where that fails the fork stays off
+void trainer_set_switches(Trainer* t, const TrainSwitches& sw);
 
 // ---- the workspace reader of the per-kernel tests (tests/test_train_layers_gpu.py) ----------------------------------------------------
 // Called by the diagnostic library's az_diag_train_* exports only (az_engine.hip under AZ_DIAG): nothing in the shipped library reaches
@@ -111,5 +110,8 @@ bool trainer_diag_set_keep(Trainer* t, bool on);
 // copied: no such buffer or layer, rows <= 0 or above the last step's batch, no step since trainer_set_params, a kept buffer when the
 // last step kept nothing.
 long long trainer_diag_read(Trainer* t, int what, int layer, int rows, void* out, hipStream_t s);
+// The plan a step of batch b would follow under the trainer's switches, as train_plan_encode writes it -> the int32 count, or -1 (b outside
+// 2 .. TRAIN_MAX_BATCH, cap below TRAIN_PLAN_INTS).  Host only: nothing is launched.
+int trainer_diag_plan(Trainer* t, int b, int32_t* out, int cap);
 
 }  // namespace az

@@ -28,6 +28,7 @@
 #include "az_mirror.h"
 #include "az_net.h"
 #include "az_optim.h"
+#include "az_train_plan.h"
 
 namespace az {
 
@@ -1716,9 +1717,8 @@ struct Trainer {
     float *sums = nullptr, *dhead = nullptr, *sample_loss = nullptr, *logits = nullptr;
     double *partial = nullptr, *loss_totals = nullptr;
     float* splitk = nullptr;           // partial sums of the split-K GEMMs
-    // bf16 x 3 operands of the backward GEMMs (gemm_mode 1): the weights as stored, dz, and the transposed wgrad operands
-    int gemm_mode = 1;
-    bool fwd_dma = true;               // forward GEMMs on k_gemm_f32_dma where its shape constraints hold
+    TrainSwitches sw;                  // the route switches: train_step_plan (az_train_plan.h) turns them and the shape into a step's chains
+    // bf16 x 3 operands of the backward GEMMs (sw.gemm 1): the weights as stored, dz, and the transposed wgrad operands
     uint16_t *w_hi = nullptr, *w_lo = nullptr;                                         // [L.total] each, a matrix at its own offset
     uint16_t *dz_hi = nullptr, *dz_lo = nullptr, *dzt_hi = nullptr, *dzt_lo = nullptr, *at_hi = nullptr, *at_lo = nullptr;
     StepState* step_state = nullptr;
@@ -1727,24 +1727,19 @@ struct Trainer {
     EpochCounters* counters = nullptr;
     bool use_graph = true;
     size_t splitk_floats = 0;
-    // second branch of a step (gemm_mode 1): the weight split and every layer's wgrad chain (transposes, k_gemm3, split-K reduce) run on
+    // second branch of a step (sw.gemm 1 and sw.fork): the weight split and every layer's wgrad chain (transposes, k_gemm3, split-K reduce) run on
     // `side`, forked from / joined to the caller's stream by events, with their own split-K workspace; the caller's stream keeps the
     // chain the next layer waits for (BatchNorm backward, dgrad, col2im).  Same kernels on the same data: bit-identical to fork = false.
-    // forward conv2..conv4 as f16 x 3 (fwd_x3): the im2col matrices and the transposed weights (times 256) as half-precision hi / lo pairs
-    bool fwd_x3 = true;
+    // forward conv2..conv4 as f16 x 3 (sw.fwd_x3): the im2col matrices and the transposed weights (times 256) as half-precision hi / lo pairs
     uint16_t *col_hi[4] = {nullptr}, *col_lo[4] = {nullptr}, *wt_hi[4] = {nullptr}, *wt_lo[4] = {nullptr};
     float* act_scale = nullptr;        // [8]: s_l of a[0..2] at [l], the epilogue's 1 / (256 s_l) at [4 + l] (act_scales_body)
-    // wgrad of conv2..conv4 on k_wgrad3_tr (transposed LDS reads, no k_transpose_split): the im2col matrices as bf16 hi / lo
-    bool wgrad_tr = true;
+    // wgrad of conv2..conv4 on k_wgrad3_tr (sw.wgrad_tr: transposed LDS reads, no k_transpose_split): the im2col matrices as bf16 hi / lo
     uint16_t *col_bhi[4] = {nullptr}, *col_blo[4] = {nullptr};
-    // the three conv GEMMs of conv2..conv4 gather their A rows from the activations (ImplicitA): no im2col matrix, no col2im.  The
-    // activations a[0..2] as half / bf16 pairs, each with one all-zero row behind the largest batch's rows (act_zero_off[l] bytes in)
-    bool implicit = true;
+    // the three conv GEMMs of conv2..conv4 gather their A rows from the activations (sw.implicit, ImplicitA): no im2col matrix, no col2im.
+    // The activations a[0..2] as half / bf16 pairs, each with one all-zero row behind the largest batch's rows (act_zero_off[l] bytes in)
     uint16_t *act_hi[3] = {nullptr}, *act_lo[3] = {nullptr}, *act_bhi[5] = {nullptr}, *act_blo[5] = {nullptr};      // [3], [4]: the FC layers' inputs (their wgrad)
     uint32_t act_zero_off[3] = {0, 0, 0}, dz_zero_off = 0;
-    bool gemm3_ring = true;            // dgrad / wgrad with >= 192 rows on k_gemm3_ring (256 x 128 tiles, 3-stage ring) instead of k_gemm3
-    bool fork = false;                 // measured: no gain as direct launches, 7 % slower inside a hipGraph (profiles/README.md)
-    hipStream_t side = nullptr;
+    hipStream_t side = nullptr;        // sw.fork measured: no gain as direct launches, 7 % slower inside a hipGraph (profiles/README.md)
     hipEvent_t ev_start = nullptr, ev_sw = nullptr, ev_join = nullptr, ev_dz[6] = {nullptr}, ev_tr[6] = {nullptr};
     float* splitk2 = nullptr;
     size_t splitk2_floats = 0;
@@ -1952,21 +1947,20 @@ float* trainer_batch_vs(Trainer* t) { return t->bvs; }
 
 namespace {
 
+static_assert(TBK == PLAN_F32_BK && GD_BK == PLAN_DMA_BK && G3_BM == PLAN_G3_BM && G3R_BM == PLAN_G3R_BM && BN_SMALL_ROWS == PLAN_BN_SMALL_ROWS,
+              "az_train_plan.h restates the kernels' tile and step sizes");
+
 inline dim3 grid1(int64_t n, int block = 256, int cap = 4096) { return dim3((unsigned)std::min<int64_t>((n + block - 1) / block, cap)); }
 
 // split-K plan + launch (ws = workspace of ws_floats floats for the partial sums)
 template <int A_K1, int B_N1>
 void launch_gemm_f32(GemmF32 g, float* ws, size_t ws_floats, hipStream_t s) {
-    // 128 x 128 tiles when K is long and the output still yields >= 64 of them (conv2 / conv3 forward, dgrad, wgrad), else 64 x 64
-    const bool big = g.K >= 256 && ((g.M + 127) / 128) * ((g.N + 127) / 128) >= 64;
+    // 128 x 128 tiles for conv2 / conv3 forward, dgrad, wgrad (gemm_f32_big), else 64 x 64
+    const bool big = gemm_f32_big(g.M, g.N, g.K);
     const int TM = big ? 128 : 64;
-    const int tiles = ((g.M + TM - 1) / TM) * ((g.N + TM - 1) / TM);
-    const int ksteps = (g.K + TBK - 1) / TBK;
-    int splits = std::max(1, std::min((big ? 768 : 1536) / std::max(tiles, 1), ksteps / 8));
-    while (splits > 1 && (size_t)splits * g.M * g.N > ws_floats) --splits;
-    int k_per = ((ksteps + splits - 1) / splits) * TBK;
-    splits = (g.K + k_per - 1) / k_per;
-    g.k_per_split = k_per;
+    const SplitK sk = gemm_splitk(GemmPlan{big ? GK_F32_128 : GK_F32_64, g.M, g.N, g.K, 0}, ws_floats);
+    const int splits = sk.splits;
+    g.k_per_split = sk.steps_per_slice * TBK;
     g.splits = splits;
     float* out = g.C;
     const int64_t ldc = g.ldc;
@@ -1979,18 +1973,15 @@ void launch_gemm_f32(GemmF32 g, float* ws, size_t ws_floats, hipStream_t s) {
         launch_splitk_reduce(ws, splits, g.M, g.N, out, ldc, bias, s);
 }
 
-// C[M][N] = A[M][K] W[K][N] + bias
+// C[M][N] = A[M][K] W[K][N] + bias; dma: on k_gemm_f32_dma (the plan has checked gemm_f32_dma_ok)
 void gemm_nn(const float* A, int64_t lda, const float* W, float* Cm, const float* bias, int M, int N, int K, float* ws, size_t wsn,
-             hipStream_t s, bool dma = false) {
+             hipStream_t s, bool dma) {
     GemmF32 g{A, lda, 1, W, N, 1, Cm, N, bias, M, N, K, 0, 1};
-    if (dma && M >= 128 && K % GD_BK == 0 && K >= 8 * GD_BK && N % 128 == 0 && lda % 4 == 0) {
-        // k_gemm_f32_dma: 128 x 128 tiles, two workgroups per CU (512 slots a round), at least 8 K-steps per slice
-        const int tiles = ((M + 127) / 128) * (N / 128), ksteps = K / GD_BK;
-        int splits = std::max(1, std::min(512 / tiles, ksteps / 8));      // never a second round of a few workgroups
-        while (splits > 1 && (size_t)splits * M * N > wsn) --splits;
-        const int k_per = ((ksteps + splits - 1) / splits) * GD_BK;
-        splits = (K + k_per - 1) / k_per;
-        g.k_per_split = k_per;
+    if (dma) {
+        const int tiles = ((M + 127) / 128) * (N / 128);
+        const SplitK sk = gemm_splitk(GemmPlan{GK_F32_DMA, M, N, K, 0}, wsn);
+        const int splits = sk.splits;
+        g.k_per_split = sk.steps_per_slice * GD_BK;
         g.splits = splits;
         if (splits > 1) { g.C = ws; g.bias = nullptr; }
         hipLaunchKernelGGL(k_gemm_f32_dma, dim3((unsigned)((tiles * splits + 7) / 8 * 8)), dim3(256), 0, s, g);
@@ -2013,22 +2004,15 @@ void gemm_tn(const float* A, int64_t lda, const float* dZ, float* dW, int M, int
 int red_parts(int M) { return std::max(1, std::min(RED_PARTS, (M + 63) / 64)); }
 
 // out[M][N] (row stride ldo) = A W^T (+ bias) as bf16 x 3: A hi / lo [M][lda], W hi / lo [N][ldw], both contiguous along the contraction
-// Kc.  Split-K so that about two workgroups per CU exist (a workgroup walks at least 8 K-steps); the slices are summed in slice order.
+// Kc, on k_gemm3_ring (ring: the plan's gemm3_on_ring; a gathered A exists there only) or k_gemm3.  Split-K by gemm_split_want; the
+// slices are summed in slice order.
 void launch_gemm3(const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* out, int ldo,
-                  const float* bias, int M, int N, int Kc, float* ws, size_t ws_floats, hipStream_t s, bool ring = false, bool f16 = false,
+                  const float* bias, int M, int N, int Kc, float* ws, size_t ws_floats, hipStream_t s, bool ring, bool f16 = false,
                   float out_scale = 1.0f, const ImplicitA* ia = nullptr, const float* out_scale_dev = nullptr) {
-    const int steps = Kc / 32;
-    const int mt_r = (M + G3R_BM - 1) / G3R_BM;
-    // at most a tenth of the row tiles' rows beyond M, and a contraction long enough to fill and drain the ring (conv4's wgrad has 12
-    // K-steps: 14.9 us on k_gemm3, 15.8 on the ring)
-    if (ia || (ring && steps >= 16 && (mt_r * G3R_BM - M) * 10 <= mt_r * G3R_BM)) {      // a gathered A exists on the ring kernel only
-        // k_gemm3_ring: 256 x 128 tiles, ONE workgroup per CU: never more than 256 of them while the tiles fit (a second round of a few
-        // workgroups costs a whole round), at least 6 K-steps per slice (the ring is 3 deep)
-        const int mt = mt_r, NT = N / 128, tiles = mt * NT;
-        int splits = std::max(1, std::min(256 / tiles, steps / 6));
-        while (splits > 1 && (size_t)splits * M * N > ws_floats) --splits;
-        const int sps = (steps + splits - 1) / splits;
-        splits = (steps + sps - 1) / sps;
+    const SplitK sk = gemm_splitk(GemmPlan{ring ? GK_GEMM3_RING : GK_GEMM3, M, N, Kc, 0}, ws_floats);
+    const int sps = sk.steps_per_slice, splits = sk.splits;
+    if (ring) {                 // 256 x 128 tiles, one workgroup per CU
+        const int mt = (M + G3R_BM - 1) / G3R_BM, NT = N / 128, tiles = mt * NT;
         Gemm3 g{a_hi, a_lo, w_hi, w_lo, splits > 1 ? ws : out, bias, M, N, Kc, lda, ldw, ldo, sps, splits, 0, out_scale, ia ? *ia : ImplicitA{},
                 out_scale_dev};
         if (f16) hipLaunchKernelGGL((k_gemm3_ring<true>), dim3((unsigned)((tiles * splits + 7) / 8 * 8)), dim3(512), 0, s, g);
@@ -2037,11 +2021,7 @@ void launch_gemm3(const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uin
             launch_splitk_reduce(ws, splits, M, N, out, (int64_t)ldo, bias, s);
         return;
     }
-    const int mt = (M + G3_BM - 1) / G3_BM, NT = N / 128, tiles = mt * NT;
-    int splits = std::max(1, std::min((512 + tiles / 2) / tiles, steps / 8));
-    while (splits > 1 && (size_t)splits * M * N > ws_floats) --splits;
-    const int sps = (steps + splits - 1) / splits;
-    splits = (steps + sps - 1) / sps;
+    const int mt = (M + G3_BM - 1) / G3_BM, NT = N / 128;
     const int xcd_rows = mt >= 8 ? 1 : 0;
     Gemm3 g{a_hi, a_lo, w_hi, w_lo, splits > 1 ? ws : out, bias, M, N, Kc, lda, ldw, ldo, sps, splits, xcd_rows, out_scale, ImplicitA{}, out_scale_dev};
     const dim3 grid((unsigned)((xcd_rows ? (mt + 7) / 8 * 8 : mt) * NT), (unsigned)splits);
@@ -2050,14 +2030,12 @@ void launch_gemm3(const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uin
     if (splits > 1)
         launch_splitk_reduce(ws, splits, M, N, out, (int64_t)ldo, bias, s);
 }
-// dW [Kin][N] = A^T dz on k_wgrad3_tr; split-K over the 32-row steps so that at most 256 workgroups exist, slices summed in slice order
+// dW [Kin][N] = A^T dz on k_wgrad3_tr; split-K over the 32-row steps (gemm_split_want), slices summed in slice order
 void launch_wgrad3_tr(const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uint16_t* z_hi, const uint16_t* z_lo, int ldz, float* out, int M,
                       int Kin, int N, float* ws, size_t ws_floats, hipStream_t s, const ImplicitA* ia = nullptr) {
-    const int tiles = (Kin / 256) * (N / 128), steps = M / 32;
-    int splits = std::max(1, std::min(256 / tiles, steps / 6));
-    while (splits > 1 && (size_t)splits * Kin * N > ws_floats) --splits;
-    const int sps = (steps + splits - 1) / splits;
-    splits = (steps + sps - 1) / sps;
+    const int tiles = (Kin / 256) * (N / 128);
+    const SplitK sk = gemm_splitk(GemmPlan{GK_WGRAD3_TR, Kin, N, M, 0}, ws_floats);
+    const int sps = sk.steps_per_slice, splits = sk.splits;
     Wgrad3 g{a_hi, a_lo, z_hi, z_lo, splits > 1 ? ws : out, Kin, N, M, lda, ldz, sps, splits, ia ? *ia : ImplicitA{},
              ia ? (65536 + ia->Ht * ia->Wt - 1) / (ia->Ht * ia->Wt) : 0, ia ? (65536 + ia->Wt - 1) / ia->Wt : 0};
     hipLaunchKernelGGL(k_wgrad3_tr, dim3((unsigned)((tiles * splits + 7) / 8 * 8)), dim3(512), 0, s, g);
@@ -2105,13 +2083,13 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
         return d;
     };
     constexpr int APPLY_ROWS = 32;      // rows per block of the apply kernels
-    // ---- forward ----
-    const bool x3 = t->gemm_mode == 1;
-    const bool fork = x3 && t->fork && t->side;
-    // the gathered conv GEMMs need the f16 x 3 forward, k_wgrad3_tr's shapes (42 b, 20 b, 6 b rows in 32s: b % 16 == 0; C % 256 == 0)
-    const bool impl = x3 && t->implicit && t->fwd_x3 && t->wgrad_tr && b % 16 == 0 && b * 20 > BN_SMALL_ROWS && C % 256 == 0;
-    // the FC layers' wgrad on k_wgrad3_tr as well (A = the previous layer's activations as bf16 pairs, two 32-row K-steps at batch 64)
-    auto fc_tr = [&](int l) { return x3 && t->wgrad_tr && l >= 4 && b % 32 == 0 && ld[l].K % 256 == 0 && ld[l].N % 128 == 0; };
+    // every route of the step, decided once (az_train_plan.h): below, a switch per decision and the descriptors
+    const StepPlan plan = train_step_plan(t->sw, t->side != nullptr, b, C);
+    const bool fork = plan.fork != 0;
+    // the branch of the weight split and the wgrad chains: the side stream with its own split-K workspace, or the caller's
+    struct Branch { hipStream_t s; float* ws; size_t ws_floats; };
+    const Branch side = fork ? Branch{t->side, t->splitk2, t->splitk2_floats} : Branch{s, t->splitk, t->splitk_floats};
+    const hipStream_t s2 = side.s;
     const int geo[4][3] = {{6, 7, 1}, {6, 7, 1}, {6, 7, 0}, {4, 5, 0}};      // conv layer l: input H, W, pad
     auto gather = [&](int l, bool dgrad) {      // ImplicitA of conv layer l (1..3): forward / wgrad rows = outputs, dgrad rows = inputs
         const int H = geo[l][0], W = geo[l][1], pad = geo[l][2], Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
@@ -2121,7 +2099,6 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
         else { ia.Ht = H; ia.Wt = W; ia.Hs = Ho; ia.Ws = Wo; ia.sgn = -1; ia.off = pad; ia.zero_off = t->dz_zero_off; }
         return ia;
     };
-    hipStream_t s2 = fork ? t->side : s;
     auto hand = [&](hipEvent_t ev, hipStream_t from, hipStream_t to) {       // `to` continues after everything enqueued on `from` so far
         if (fork) { (void)hipEventRecord(ev, from); (void)hipStreamWaitEvent(to, ev, 0); }
     };
@@ -2129,31 +2106,27 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
         SplitWeights sw{};
         const int64_t offs[5] = {L.conv_w[1], L.conv_w[2], L.conv_w[3], L.fc_w[0], L.fc_w[1]};
         for (int i = 0; i < 5; ++i) { sw.off[i] = offs[i]; sw.count[i] = (int64_t)ld[i + 1].K * ld[i + 1].N; }
-        if (impl) { sw.perm_c[0] = C; sw.perm_n[0] = C; }      // conv2 only: its dgrad is the gathered GEMM
+        if (plan.perm_conv2) { sw.perm_c[0] = C; sw.perm_n[0] = C; }      // conv2 only: its dgrad is the gathered GEMM
         return sw;
     };
     auto split_weights = [&]() {
         const SplitWeights sw = split_desc();
         hipLaunchKernelGGL(k_split_weights, dim3(256, 5), dim3(256), 0, s2, (const float*)P, sw, t->w_hi, t->w_lo);
     };
-    if (fork) {                      // the weight split needs the parameters only: under the forward pass
+    if (plan.split == SPLIT_SIDE_START) {      // the weight split needs the parameters only: under the forward pass
         hand(t->ev_start, s, s2);
         split_weights();
         (void)hipEventRecord(t->ev_sw, s2);
     }
     if (!col1_done) hipLaunchKernelGGL(k_boards_col1, grid1((int64_t)b * 42 * 20, 256, 1 << 20), dim3(256), 0, s, d_boards, t->col[0], b);
-    const bool fx3 = x3 && t->fwd_x3;           // "train_gemm" 0 keeps every GEMM on the f32 matrix cores
-    // k_wgrad3_tr's shape constraints (a batch of 64 meets them at every width that is a multiple of 256 / 9 ... i.e. 9 C % 256 == 0)
-    auto tr_ok = [&](int l) { return x3 && t->wgrad_tr && l >= 1 && l <= 3 && ld[l].M % 32 == 0 && ld[l].K % 256 == 0 && ld[l].N % 128 == 0; };
-    const bool prep_one = fx3 && !fork;      // both weight preparations in one launch, ahead of the forward pass
-    if (fx3) {          // W [9C][C] of conv2..conv4 -> (256 W)^T as half hi / lo [C][9C]; the activations' scales s_l
+    if (plan.prep != PREP_NONE) {      // W [9C][C] of conv2..conv4 -> (256 W)^T as half hi / lo [C][9C]; the activations' scales s_l
         TransposeJob j[3];
         for (int l = 1; l <= 3; ++l) j[l - 1] = TransposeJob{P + ld[l].w, t->wt_hi[l], t->wt_lo[l], C, C / 64, C};
         const int tgx = 3 * (C / 64), tgy = 9 * C / 64;
         ActScaleJob aj{};
         for (int l = 0; l < 3; ++l) { aj.bn[l] = ld[l].bn; aj.sqrt_m1[l] = (float)std::sqrt((double)(rows[l] - 1)); }
         aj.C = C;
-        if (prep_one) {
+        if (plan.prep == PREP_ONE) {      // with the weight split (SPLIT_IN_PREP), in one launch ahead of the forward pass
             const SplitWeights sw = split_desc();
             hipLaunchKernelGGL(k_weight_prep, dim3((unsigned)(tgx * tgy + 256 * 5 + 1)), dim3(256), 0, s, j[0], j[1], j[2], 9 * C, 9 * C, 256.0f, tgx,
                                tgy, (const float*)P, sw, t->w_hi, t->w_lo, 256, aj, t->act_scale);
@@ -2164,37 +2137,39 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
     }
     for (int l = 0; l < 6; ++l) {
         const LayerDef& d = ld[l];
-        if (impl && l >= 1 && l <= 3) {
+        const LayerPlan& lp = plan.layer[l];
+        switch (lp.fwd) {
+        case FWD_X3_GATHER: {
             const ImplicitA ia = gather(l, false);
             launch_gemm3(t->act_hi[l - 1], t->act_lo[l - 1], 0, t->wt_hi[l], t->wt_lo[l], 9 * C, t->z[l], d.N, P + d.bias, d.M, d.N, d.K, t->splitk,
                          t->splitk_floats, s, true, true, 1.0f, &ia, t->act_scale + 4 + (l - 1));
-        } else if (fx3 && l >= 1 && l <= 3)
-            launch_gemm3(t->col_hi[l], t->col_lo[l], 9 * C, t->wt_hi[l], t->wt_lo[l], 9 * C, t->z[l], d.N, P + d.bias, d.M, d.N, d.K, t->splitk,
-                         t->splitk_floats, s, t->gemm3_ring, true, 1.0f, nullptr, t->act_scale + 4 + (l - 1));
-        else
-            gemm_nn(d.A, d.lda, P + d.w, t->z[l], P + d.bias, d.M, d.N, d.K, t->splitk, t->splitk_floats, s, t->fwd_dma);
-        BnLayer bn = bn_desc(l, t->a[l], nullptr);
-        if (impl && l <= 2) {
-            bn.act_hi = t->act_hi[l]; bn.act_lo = t->act_lo[l]; bn.act_bhi = t->act_bhi[l]; bn.act_blo = t->act_blo[l];
-            bn.act_scale = t->act_scale + l;
+            break;
         }
-        if ((l == 3 || l == 4) && fc_tr(l + 1)) { bn.act_bhi = t->act_bhi[l]; bn.act_blo = t->act_blo[l]; }
+        case FWD_X3_COL:
+            launch_gemm3(t->col_hi[l], t->col_lo[l], 9 * C, t->wt_hi[l], t->wt_lo[l], 9 * C, t->z[l], d.N, P + d.bias, d.M, d.N, d.K, t->splitk,
+                         t->splitk_floats, s, lp.fwd_gemm.kernel == GK_GEMM3_RING, true, 1.0f, nullptr, t->act_scale + 4 + (l - 1));
+            break;
+        default:
+            gemm_nn(d.A, d.lda, P + d.w, t->z[l], P + d.bias, d.M, d.N, d.K, t->splitk, t->splitk_floats, s, lp.fwd_gemm.kernel == GK_F32_DMA);
+        }
+        BnLayer bn = bn_desc(l, t->a[l], nullptr);
+        if (lp.bn_extra & BN_OUT_F16) { bn.act_hi = t->act_hi[l]; bn.act_lo = t->act_lo[l]; bn.act_scale = t->act_scale + l; }
+        if (lp.bn_extra & BN_OUT_BF16) { bn.act_bhi = t->act_bhi[l]; bn.act_blo = t->act_blo[l]; }      // the next layer's wgrad operand
         const int parts = red_parts(d.M), rpb = (d.M + parts - 1) / parts;
-        if (d.M <= BN_SMALL_ROWS) {
+        if (lp.bn_small) {
             hipLaunchKernelGGL(k_bn_fwd_small, dim3(d.N / BN_COLS), dim3(256), 0, s, bn, h.bn_eps, h.bn_momentum, P + d.bn + 2 * d.N, P + d.bn + 3 * d.N, st);
         } else {
             hipLaunchKernelGGL((k_colreduce<0>), dim3(d.N / BN_COLS, parts), dim3(256), 0, s, bn, rpb, t->partial, st);
             hipLaunchKernelGGL(k_bn_apply, dim3(d.N / BN_COLS, (d.M + APPLY_ROWS - 1) / APPLY_ROWS), dim3(256), 0, s, bn, t->partial, parts,
                                APPLY_ROWS, h.bn_eps, h.bn_momentum, P + d.bn + 2 * d.N, P + d.bn + 3 * d.N, st);
         }
-        if (l <= 2 && !impl) {
+        if (lp.im2col) {
             const int ln = l + 1;                // the layer this matrix feeds
             Im2colOut io{};
-            if (fx3) { io.col_hi = t->col_hi[ln]; io.col_lo = t->col_lo[ln]; io.hi_scale = t->act_scale + l; }
-            if (tr_ok(ln)) { io.col_bhi = t->col_bhi[ln]; io.col_blo = t->col_blo[ln]; }
-            if (!fx3 || !tr_ok(ln)) io.col = t->col[ln];
-            const int H = l == 2 ? 4 : 6, W = l == 2 ? 5 : 7, pad = l == 0 ? 1 : 0;
-            hipLaunchKernelGGL(k_im2col, grid1((int64_t)ld[ln].M * 9 * C / 4), dim3(256), 0, s, t->a[l], io, b, H, W, C, pad);
+            if (lp.im2col & COL_F16) { io.col_hi = t->col_hi[ln]; io.col_lo = t->col_lo[ln]; io.hi_scale = t->act_scale + l; }
+            if (lp.im2col & COL_BF16) { io.col_bhi = t->col_bhi[ln]; io.col_blo = t->col_blo[ln]; }
+            if (lp.im2col & COL_F32) io.col = t->col[ln];
+            hipLaunchKernelGGL(k_im2col, grid1((int64_t)ld[ln].M * 9 * C / 4), dim3(256), 0, s, t->a[l], io, b, geo[ln][0], geo[ln][1], C, geo[ln][2]);
         }
     }
     hipLaunchKernelGGL(k_heads_loss, dim3(b), dim3(64), 0, s, t->a[5], P + L.pi_w, P + L.pi_b, P + L.v_w, P + L.v_b, d_pis, d_vs, b,
@@ -2202,19 +2177,20 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
     // ---- backward ----
     hipLaunchKernelGGL(k_heads_bwd, grid1(std::max<int64_t>(512 * 8 + 8, (int64_t)b * 512)), dim3(256), 0, s, t->a[5], t->dhead,
                        P + L.pi_w, P + L.v_w, b, G + L.pi_w, G + L.pi_b, G + L.v_w, G + L.v_b, t->dact, t->sample_loss, t->loss_totals);
-    if (x3 && !fork && !prep_one) split_weights();
+    if (plan.split == SPLIT_AFTER_HEADS) split_weights();
     if (fork) (void)hipStreamWaitEvent(s, t->ev_sw, 0);
     for (int l = 5; l >= 0; --l) {
         const LayerDef& d = ld[l];
+        const LayerPlan& lp = plan.layer[l];
         // t->dact holds d loss / d a[l]  ->  dz (through dropout, ReLU and BatchNorm)
         BnLayer bn = bn_desc(l, t->dz, t->dact);
-        const bool g3 = x3 && l >= 1;
+        const bool g3 = lp.wgrad != WGRAD_F32;      // the layer's backward GEMMs as bf16 x 3: dz as bf16 pairs too
         if (g3) { bn.out_hi = t->dz_hi; bn.out_lo = t->dz_lo; }
         const int parts = red_parts(d.M), rpb = (d.M + parts - 1) / parts;
         if (fork && l <= 4) (void)hipStreamWaitEvent(s, t->ev_tr[l + 1], 0);      // dz is rewritten: the layer above has transposed it
         const size_t keep_bytes = (size_t)d.M * d.N * sizeof(float);
         if (keep_bwd) (void)hipMemcpyAsync(t->keep_dact[l], t->dact, keep_bytes, hipMemcpyDeviceToDevice, s);
-        if (d.M <= BN_SMALL_ROWS) {
+        if (lp.bn_small) {
             hipLaunchKernelGGL(k_bn_bwd_small, dim3(d.N / BN_COLS), dim3(256), 0, s, bn, G + d.bn, G + d.bn + d.N, st);
         } else {
             hipLaunchKernelGGL((k_colreduce<1>), dim3(d.N / BN_COLS, parts), dim3(256), 0, s, bn, rpb, t->partial, st);
@@ -2225,54 +2201,63 @@ void enqueue_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
         // The gradient of a bias in front of a BatchNorm is identically zero (the batch mean absorbs it); the kernels
         // leave those slots at 0 instead of the rounding residue a column sum of dz would give, which Adam would
         // turn into a random walk of size lr.
-        if (g3) {
-            // wgrad: dW [K][N] = A^T dz, both operands transposed so that the contraction (the rows) is contiguous
+        // wgrad: dW [K][N] = A^T dz.  On the side branch where the fork is active; ev_tr[l] says that the branch has read dz, which the
+        // caller's stream rewrites in the layer below
+        if (g3) hand(t->ev_dz[l], s, s2);
+        auto dz_read = [&]() { if (fork) (void)hipEventRecord(t->ev_tr[l], s2); };
+        switch (lp.wgrad) {
+        case WGRAD_TR_GATHER: {     // A gathered from the layer's input, dz as stored
+            const ImplicitA ia = gather(l, false);
+            launch_wgrad3_tr(t->act_bhi[l - 1], t->act_blo[l - 1], 0, t->dz_hi, t->dz_lo, d.N, G + d.w, d.M, d.K, d.N, side.ws, side.ws_floats, s2, &ia);
+            dz_read();
+            break;
+        }
+        case WGRAD_TR_ACT:          // A = the previous layer's activations as bf16 pairs (the FC layers)
+            launch_wgrad3_tr(t->act_bhi[l - 1], t->act_blo[l - 1], d.K, t->dz_hi, t->dz_lo, d.N, G + d.w, d.M, d.K, d.N, side.ws, side.ws_floats, s2);
+            dz_read();
+            break;
+        case WGRAD_TR_COL:          // A = the im2col pairs and dz as stored: no transposes
+            launch_wgrad3_tr(t->col_bhi[l], t->col_blo[l], (int)d.lda, t->dz_hi, t->dz_lo, d.N, G + d.w, d.M, d.K, d.N, side.ws, side.ws_floats, s2);
+            dz_read();
+            break;
+        case WGRAD_TRANSPOSE: {     // both operands transposed so that the contraction (the rows) is contiguous
             const int Mp = (d.M + 63) / 64 * 64;
-            hand(t->ev_dz[l], s, s2);
-            if (impl && l <= 3) {     // A gathered from the layer's input, dz as stored
-                const ImplicitA ia = gather(l, false);
-                launch_wgrad3_tr(t->act_bhi[l - 1], t->act_blo[l - 1], 0, t->dz_hi, t->dz_lo, d.N, G + d.w, d.M, d.K, d.N, fork ? t->splitk2 : t->splitk,
-                                 fork ? t->splitk2_floats : t->splitk_floats, s2, &ia);
-                if (fork) (void)hipEventRecord(t->ev_tr[l], s2);
-            } else if (fc_tr(l)) {
-                launch_wgrad3_tr(t->act_bhi[l - 1], t->act_blo[l - 1], d.K, t->dz_hi, t->dz_lo, d.N, G + d.w, d.M, d.K, d.N, fork ? t->splitk2 : t->splitk,
-                                 fork ? t->splitk2_floats : t->splitk_floats, s2);
-                if (fork) (void)hipEventRecord(t->ev_tr[l], s2);
-            } else if (tr_ok(l)) {       // A and dz as stored: no transposes
-                launch_wgrad3_tr(t->col_bhi[l], t->col_blo[l], (int)d.lda, t->dz_hi, t->dz_lo, d.N, G + d.w, d.M, d.K, d.N, fork ? t->splitk2 : t->splitk,
-                                 fork ? t->splitk2_floats : t->splitk_floats, s2);
-                if (fork) (void)hipEventRecord(t->ev_tr[l], s2);
-            } else {
-                const TransposeJob jz{t->dz, t->dzt_hi, t->dzt_lo, d.N, (d.N + 63) / 64, d.N}, ja{d.A, t->at_hi, t->at_lo, d.K, (d.K + 63) / 64, d.lda};
-                launch_transpose_split2(ja, jz, d.M, Mp, s2);         // the big one first
-                if (fork) (void)hipEventRecord(t->ev_tr[l], s2);
-                launch_gemm3(t->at_hi, t->at_lo, Mp, t->dzt_hi, t->dzt_lo, Mp, G + d.w, d.N, nullptr, d.K, d.N, Mp, fork ? t->splitk2 : t->splitk,
-                             fork ? t->splitk2_floats : t->splitk_floats, s2, t->gemm3_ring);
-            }
-            // dgrad: d input [M][K] = dz W^T, W [K][N] as stored
-            float* din = l >= 4 ? t->dact : t->dcol;
+            const TransposeJob jz{t->dz, t->dzt_hi, t->dzt_lo, d.N, (d.N + 63) / 64, d.N}, ja{d.A, t->at_hi, t->at_lo, d.K, (d.K + 63) / 64, d.lda};
+            launch_transpose_split2(ja, jz, d.M, Mp, s2);         // the big one first
+            dz_read();
+            launch_gemm3(t->at_hi, t->at_lo, Mp, t->dzt_hi, t->dzt_lo, Mp, G + d.w, d.N, nullptr, d.K, d.N, Mp, side.ws, side.ws_floats, s2,
+                         lp.wgrad_gemm.kernel == GK_GEMM3_RING);
+            break;
+        }
+        default:
+            gemm_tn(d.A, d.lda, t->dz, G + d.w, d.M, d.N, d.K, t->splitk, t->splitk_floats, s);
+        }
+        // dgrad: d input [M][K] = dz W^T, W [K][N] as stored; the FC layers' is d a[l-1] directly, a conv's goes through dcol and col2im
+        float* din = lp.dgrad_dst == DST_DACT ? t->dact : t->dcol;
+        switch (lp.dgrad) {
+        case DGRAD_F32:
+            gemm_nt(t->dz, P + d.w, din, d.K, d.M, d.N, d.K, t->splitk, t->splitk_floats, s);
+            break;
+        case DGRAD_X3:
+            launch_gemm3(t->dz_hi, t->dz_lo, d.N, t->w_hi + d.w, t->w_lo + d.w, d.N, din, d.K, nullptr, d.M, d.K, d.N, t->splitk, t->splitk_floats, s,
+                         lp.dgrad_gemm.kernel == GK_GEMM3_RING);
+            break;
+        case DGRAD_X3_GATHER: {
             // d input [b Hin Win][C] = the transposed convolution as ONE GEMM over (tap, n): no dcol, no col2im -- for the 'same' convolution
             // (conv2) only: a 'valid' one has fewer output than input positions, and the gathered form multiplies every input position by
             // all nine taps (conv3 2.1 x, conv4 3.3 x the products of dz W^T + col2im; measured 49 vs 41 and 34 vs 24 us)
-            if (impl && l == 1) {
-                const ImplicitA ia = gather(l, true);
-                ImplicitA ig = ia;
-                ig.Cs = d.N;
-                launch_gemm3(t->dz_hi, t->dz_lo, 0, t->w_hi + d.w, t->w_lo + d.w, 9 * d.N, t->dact, C, nullptr, b * ia.Ht * ia.Wt, C, 9 * d.N, t->splitk,
-                             t->splitk_floats, s, true, false, 1.0f, &ig);
-            } else
-            launch_gemm3(t->dz_hi, t->dz_lo, d.N, t->w_hi + d.w, t->w_lo + d.w, d.N, din, d.K, nullptr, d.M, d.K, d.N, t->splitk, t->splitk_floats, s,
-                         t->gemm3_ring);
-        } else {
-            gemm_tn(d.A, d.lda, t->dz, G + d.w, d.M, d.N, d.K, t->splitk, t->splitk_floats, s);
-            if (l == 0) break;
-            if (l >= 4) gemm_nt(t->dz, P + d.w, t->dact, d.K, d.M, d.N, d.K, t->splitk, t->splitk_floats, s);      // FC: d a[l-1] directly
-            else gemm_nt(t->dz, P + d.w, t->dcol, d.K, d.M, d.N, d.K, t->splitk, t->splitk_floats, s);
+            const ImplicitA ia = gather(l, true);
+            ImplicitA ig = ia;
+            ig.Cs = d.N;
+            launch_gemm3(t->dz_hi, t->dz_lo, 0, t->w_hi + d.w, t->w_lo + d.w, 9 * d.N, din, C, nullptr, b * ia.Ht * ia.Wt, C, 9 * d.N, t->splitk,
+                         t->splitk_floats, s, true, false, 1.0f, &ig);
+            break;
         }
-        if (l >= 1 && l <= 3 && !(impl && g3 && l == 1)) {
-            const int H = l == 3 ? 4 : 6, W = l == 3 ? 5 : 7, pad = l == 1 ? 1 : 0;
-            hipLaunchKernelGGL(k_col2im, grid1((int64_t)b * H * W * C / 4), dim3(256), 0, s, t->dcol, t->dact, b, H, W, C, pad);
+        default: break;             // conv1 has no input gradient
         }
+        if (lp.col2im)
+            hipLaunchKernelGGL(k_col2im, grid1((int64_t)b * geo[l][0] * geo[l][1] * C / 4), dim3(256), 0, s, t->dcol, t->dact, b, geo[l][0], geo[l][1], C,
+                               geo[l][2]);
     }
     hand(t->ev_join, s2, s);
     if (t->optim.on()) {
@@ -2308,7 +2293,7 @@ bool trainer_step(Trainer* t, const TrainHyper& h, const float* d_boards, const 
     st.pad_ = 0.0f;
     t->last_lr = st.lr_t;
     if (hipMemcpyAsync(t->step_state, &st, sizeof st, hipMemcpyHostToDevice, s) != hipSuccess) return false;
-    const bool keep = t->keep && !t->fork;      // the diagnostic reader's switch: never on in the shipped library
+    const bool keep = t->keep && !t->sw.fork;      // the diagnostic reader's switch: never on in the shipped library
     enqueue_step(t, h, d_boards, d_pis, d_vs, b, apply, s, false, keep);
     t->last_b = b;
     t->kept_b = keep ? b : 0;
@@ -2375,33 +2360,27 @@ bool trainer_run_epoch_samples(Trainer* t, const TrainHyper& h, const TrainSampl
 }
 
 void trainer_set_graph(Trainer* t, bool on) { if (t) t->use_graph = on; }
-void trainer_set_gemm(Trainer* t, int mode) { if (t) t->gemm_mode = mode; }
-// The branch's stream and events exist only once the option has been switched on: an idle extra stream still takes one of the device's
+// The branch's stream and events exist only once "train_fork" has been switched on: an idle extra stream still takes one of the device's
 // few hardware queues, and the arena's two search streams then share one (measured: az_arena 2755 -> 1860 games/s in a process whose
-// trainer merely owned a second stream).
-void trainer_set_fork(Trainer* t, bool on) {
+// trainer merely owned a second stream).  Where they cannot be made the fork stays off.
+void trainer_set_switches(Trainer* t, const TrainSwitches& sw) {
     if (!t) return;
-    if (on && !t->side) {
+    t->sw = sw;
+    if (sw.fork && !t->side) {
         bool ok = hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking) == hipSuccess;
         for (hipEvent_t* ev : {&t->ev_start, &t->ev_sw, &t->ev_join}) ok = ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
         for (int l = 0; l < 6 && ok; ++l)
             ok = hipEventCreateWithFlags(&t->ev_dz[l], hipEventDisableTiming) == hipSuccess &&
                  hipEventCreateWithFlags(&t->ev_tr[l], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { if (t->side) { (void)hipStreamDestroy(t->side); t->side = nullptr; } on = false; }
+        if (!ok) { if (t->side) { (void)hipStreamDestroy(t->side); t->side = nullptr; } t->sw.fork = 0; }
     }
-    t->fork = on;
 }
-void trainer_set_fwd_x3(Trainer* t, bool on) { if (t) t->fwd_x3 = on; }
-void trainer_set_wgrad_tr(Trainer* t, bool on) { if (t) t->wgrad_tr = on; }
-void trainer_set_implicit(Trainer* t, bool on) { if (t) t->implicit = on; }
-void trainer_set_gemm3_ring(Trainer* t, bool on) { if (t) t->gemm3_ring = on; }
-void trainer_set_fwd_dma(Trainer* t, bool on) { if (t) t->fwd_dma = on; }
 
 // ---- the per-kernel tests' reader (az_train.h) ---------------------------------------------------------------------------------------
 bool trainer_diag_set_keep(Trainer* t, bool on) {
     if (!t) return false;
     if (!on) { t->keep = false; return true; }
-    if (t->fork) return false;
+    if (t->sw.fork) return false;
     const size_t B = TRAIN_MAX_BATCH, C = (size_t)t->C;
     const size_t n[6] = {B * 42 * C, B * 42 * C, B * 20 * C, B * 6 * C, B * 1024, B * 512};
     for (int l = 0; l < 6; ++l)
@@ -2409,6 +2388,11 @@ bool trainer_diag_set_keep(Trainer* t, bool on) {
             if (!*q && !(*q = t->dalloc<float>(n[l]))) return false;
     t->keep = true;
     return true;
+}
+
+int trainer_diag_plan(Trainer* t, int b, int32_t* out, int cap) {
+    if (!t || !out || b <= 1 || b > TRAIN_MAX_BATCH) return -1;
+    return train_plan_encode(train_step_plan(t->sw, t->side != nullptr, b, t->C), out, cap);
 }
 
 long long trainer_diag_read(Trainer* t, int what, int layer, int rows, void* out, hipStream_t s) {

@@ -130,8 +130,8 @@ def run_case(engine_mod, e, C, p, batch, what, gemm_set=R.DEFAULT_SET, switches=
 
 @pytest.mark.parametrize("case", R.TABLE_CASES, ids=R.case_id)
 def test_every_kernel_meets_its_bound(engine_mod, engines, case):
-    """The table of train_layers_ref.TABLE_CASES: C = 128 in all four GEMM sets at batches 2 (one-launch BatchNorm everywhere), 11
-    (conv4's on the large-row kernels), 37 (odd: transposes + k_gemm3, ragged tiles), 65 (the FC BatchNorm large-row), 128 (the FC
+    """The table of train_layers_ref.TABLE_CASES: C = 128 in all four GEMM sets at batches 2 (one-launch BatchNorm from conv3 up), 11
+    (conv4's on the large-row kernels), 37 (odd: transposes + launch_gemm3, ragged tiles), 65 (the FC BatchNorm large-row), 128 (the FC
     forward on k_gemm_f32_dma); C = 256 at 16 / 32 / 48 (the gathered GEMMs, fc_tr, the FC wgrad through the transposes) and at 32 with
     each shipped switch off alone; C = 384 at 37 (9 C % 256 != 0); C = 512 at 32 in the default and the f32 set."""
     C, gemm_set, switches, b = case

@@ -1,7 +1,9 @@
 """NNet::train (csrc/az_train.hip) against float64 autograd over the whole accepted range: every batch in [2, 256] and every width
-C % 128 == 0 reaches a kernel chain of its own in enqueue_step, chosen by row thresholds and divisibility rules (BN_SMALL_ROWS,
-k_wgrad3_tr's 32-row steps, the gathered ImplicitA GEMMs at C % 256 == 0 and b % 16 == 0, k_gemm_f32_dma at >= 128 rows, the split-K
-plans).  The batches below are picked to cross those thresholds; each carries a comment naming the path it takes.  The bars are
+C % 128 == 0 reaches a kernel chain of its own, chosen by the step plan (csrc/az_train_plan.h) from row thresholds and divisibility rules
+(BN_SMALL_ROWS, k_wgrad3_tr's 32-row steps, the gathered ImplicitA GEMMs at C % 256 == 0 and b % 16 == 0, k_gemm_f32_dma at >= 128 rows,
+the split-K plans).  The batches below are picked to cross those thresholds; each states the routes it is here for as data (SWEEP_512,
+SWEEP_512_F32, OTHER_WIDTHS, NEW_ROUTES), and tests/test_train_plan_cpu.py holds the plan to every entry and checks that every route the
+plan can choose is reached by some case that runs on the GPU.  The bars are
 test_gradients_match_autograd's (tests/test_train_gpu.py check_step): losses to 1e-5 relative, every gradient tensor to 1e-3 relative L2,
 pre-BN biases exactly 0, moving averages to 1e-6 / 1e-5.  check_step prints the worst per-tensor error of every case ("[worst]").
 """
@@ -46,22 +48,54 @@ def _restore(e):
 
 # ---- the batch sweep at the shipped width ------------------------------------------------------------------------------------------
 
-SWEEP_512 = [
-    2,      # smallest batch: conv3 (40 rows) and conv4 (12) BatchNorm on k_bn_fwd_small / k_bn_bwd_small, FC on the one-launch kernels
-    3,      # largest batch whose conv3 BatchNorm (60 rows) is on the one-launch kernels
-    8,      # b % 8: conv3's wgrad on k_wgrad3_tr from the stored operands (tr_ok, 160 rows), conv2 / conv4 through the transposes
-    10,     # largest batch whose conv4 BatchNorm (60 rows) is on the one-launch kernels
-    11,     # conv4 BatchNorm on k_colreduce / k_bn_apply (66 rows); odd: no k_wgrad3_tr anywhere
-    16,     # smallest gathered batch (ImplicitA forward / wgrad, conv2 dgrad without col2im), FC wgrad not yet on k_wgrad3_tr
-    24,     # b % 8 but not % 16: tr_ok on conv3 only (480 rows), transposes on conv2 / conv4, no gathered GEMMs
-    37,     # odd: every wgrad through k_transpose_split + k_gemm3, ring waste rule at 1554 rows
-    64,     # the bench shape: gathered GEMMs, FC wgrad on k_wgrad3_tr (fc_tr), FC BatchNorm at BN_SMALL_ROWS exactly
-    65,     # FC BatchNorm on the large-row kernels (k_colreduce, k_bn_apply, k_bn_bwd_apply); odd: no gathered GEMMs
-    96,     # gathered + fc_tr, FC BatchNorm on the large-row kernels, 4032 / 1920 / 576 rows in the split-K plans
-    128,    # FC forward on k_gemm_f32_dma (>= 128 rows), gathered, fc_tr
-    200,    # b % 8 only: tr_ok on conv3, transposes elsewhere, FC on k_gemm_f32_dma without fc_tr (200 % 32 != 0)
-    256,    # the largest batch (TRAIN_MAX_BATCH): 10752 rows in conv1 / conv2, every split-K plan at its maximum M
-]
+# batch -> the routes it is here for, in the words of tests/train_plan_twin.decode: {"gathered": bool} and {field: {layer: value}} with
+# layers 0..5 = conv1..conv4, fc1, fc2.  tests/test_train_plan_cpu.py holds the step plan (csrc/az_train_plan.h) to every entry.
+_TRANSPOSES = {l: "transpose" for l in range(1, 6)}
+_GATHERED = {"gathered": True, "wgrad": {1: "tr_gather", 2: "tr_gather", 3: "tr_gather"}, "dgrad": {1: "x3_gather"}, "col2im": {1: False, 2: True, 3: True}}
+_FC_DMA = {4: "gemm_f32_dma", 5: "gemm_f32_dma"}
+_FC_F32_64 = {4: "gemm_f32_64", 5: "gemm_f32_64"}
+
+SWEEP_512 = {
+    # smallest batch: conv3 (40 rows) and conv4 (12) BatchNorm on k_bn_fwd_small / k_bn_bwd_small, FC on the one-launch kernels
+    2: {"gathered": False, "bn": {0: "large", 1: "large", 2: "small", 3: "small", 4: "small", 5: "small"}, "wgrad": _TRANSPOSES},
+    # largest batch whose conv3 BatchNorm (60 rows) is on the one-launch kernels
+    3: {"bn": {1: "large", 2: "small"}},
+    # b % 8: conv3's wgrad on k_wgrad3_tr from the stored operands (160 rows), conv2 / conv4 through the transposes
+    8: {"gathered": False, "wgrad": {1: "transpose", 2: "tr_col", 3: "transpose"}, "im2col": {0: {"f16", "f32"}, 1: {"f16", "bf16"}, 2: {"f16", "f32"}}},
+    # largest batch whose conv4 BatchNorm (60 rows) is on the one-launch kernels
+    10: {"bn": {2: "large", 3: "small"}},
+    # conv4 BatchNorm on k_colreduce / k_bn_apply (66 rows); odd: no k_wgrad3_tr anywhere
+    11: {"bn": {3: "large", 4: "small"}, "wgrad": _TRANSPOSES},
+    # smallest gathered batch (ImplicitA forward / wgrad, conv2 dgrad without col2im), FC wgrad not yet on k_wgrad3_tr
+    16: {**_GATHERED, "wgrad": {**_GATHERED["wgrad"], 4: "transpose", 5: "transpose"}, "im2col": {0: None, 1: None, 2: None}},
+    # b % 8 but not % 16: k_wgrad3_tr on conv3 only (480 rows), transposes on conv2 / conv4, no gathered GEMMs
+    24: {"gathered": False, "wgrad": {1: "transpose", 2: "tr_col", 3: "transpose", 4: "transpose", 5: "transpose"}},
+    # odd: every wgrad through k_transpose_split + launch_gemm3; the ring's waste rule at 1554 rows keeps conv2's forward and dgrad on k_gemm3
+    37: {"gathered": False, "wgrad": _TRANSPOSES, "fwd_kernel": {1: "gemm3", 2: "gemm3_ring"}, "dgrad_kernel": {1: "gemm3", 2: "gemm3_ring"}},
+    # the bench shape: gathered GEMMs, FC wgrad on k_wgrad3_tr, FC BatchNorm at BN_SMALL_ROWS exactly
+    64: {**_GATHERED, "wgrad": {**_GATHERED["wgrad"], 4: "tr_act", 5: "tr_act"}, "bn": {3: "large", 4: "small", 5: "small"}, "fwd_kernel": _FC_F32_64},
+    # FC BatchNorm on the large-row kernels (k_colreduce, k_bn_apply, k_bn_bwd_apply); odd: no gathered GEMMs
+    65: {"gathered": False, "bn": {4: "large", 5: "large"}, "wgrad": _TRANSPOSES},
+    # gathered + FC wgrad on k_wgrad3_tr, FC BatchNorm on the large-row kernels, 4032 / 1920 / 576 rows in the split-K plans
+    96: {**_GATHERED, "wgrad": {**_GATHERED["wgrad"], 4: "tr_act", 5: "tr_act"}, "bn": {4: "large", 5: "large"}},
+    # FC forward on k_gemm_f32_dma (>= 128 rows), gathered, FC wgrad on k_wgrad3_tr
+    128: {**_GATHERED, "wgrad": {**_GATHERED["wgrad"], 4: "tr_act", 5: "tr_act"}, "fwd_kernel": _FC_DMA},
+    # b % 8 only: k_wgrad3_tr on conv3, transposes elsewhere, FC on k_gemm_f32_dma without k_wgrad3_tr (200 % 32 != 0)
+    200: {"gathered": False, "wgrad": {1: "transpose", 2: "tr_col", 3: "transpose", 4: "transpose", 5: "transpose"}, "fwd_kernel": _FC_DMA},
+    # the largest batch (TRAIN_MAX_BATCH): 10752 rows in conv1 / conv2, every split-K plan at its maximum M
+    256: {**_GATHERED, "wgrad": {**_GATHERED["wgrad"], 4: "tr_act", 5: "tr_act"}, "fwd_kernel": _FC_DMA},
+}
+
+# the same thresholds with every GEMM on the f32 matrix cores ("train_gemm" 0)
+_ALL_F32 = {"gathered": False, "fwd": {l: "f32" for l in range(6)}, "wgrad": {l: "f32" for l in range(6)}, "dgrad": {l: "f32" for l in range(1, 6)}}
+SWEEP_512_F32 = {
+    2: {**_ALL_F32, "bn": {0: "large", 1: "large", 2: "small", 3: "small", 4: "small", 5: "small"}},
+    11: {**_ALL_F32, "bn": {3: "large", 4: "small"}},
+    24: {**_ALL_F32, "fwd_kernel": {1: "gemm_f32_dma", 2: "gemm_f32_dma", 3: "gemm_f32_dma", **_FC_F32_64}},
+    65: {**_ALL_F32, "bn": {4: "large", 5: "large"}, "fwd_kernel": _FC_F32_64},
+    128: {**_ALL_F32, "fwd_kernel": _FC_DMA},
+    256: {**_ALL_F32, "fwd_kernel": _FC_DMA},
+}
 
 
 # batch -> (parameter seed, batch seed); the rest use (1000 + b, 2000 + b).  A ReLU mask flip -- a pre-activation within rounding of
@@ -85,7 +119,7 @@ def test_batch_sweep_default_set_at_c512(e512, b):
     check_step(e512, p, 512, boards, pis, vs, f"C=512 b={b} default")
 
 
-@pytest.mark.parametrize("b", [2, 11, 24, 65, 128, 256])
+@pytest.mark.parametrize("b", SWEEP_512_F32)
 def test_batch_sweep_f32_set_at_c512(e512, b):
     """Every GEMM on the f32 matrix cores ("train_gemm" 0) over the same thresholds: the small / large BatchNorm kernels (2, 11, 65),
     the f32 forward on k_gemm_f32 (< 128 rows: the FC layers up to b = 127) and on k_gemm_f32_dma (128, 256), split-K plans."""
@@ -112,7 +146,10 @@ def _dropout_case(e, C, b, what):
     assert (lp2, lv2) == (lp, lv) and np.array_equal(g2, g), what
 
 
-@pytest.mark.parametrize("b", [65, 128, 256])
+DROPOUT_C128 = [65, 128, 256]
+
+
+@pytest.mark.parametrize("b", DROPOUT_C128)
 def test_dropout_on_the_large_row_kernels_c128(e128, b):
     """Dropout 0.3 with b > BN_SMALL_ROWS: the keep_thresh branches of k_colreduce<1>, k_bn_apply and k_bn_bwd_apply (every other
     dropout test runs the FC BatchNorm on the one-launch kernels).  The reference applies the counter RNG's masks explicitly."""
@@ -133,13 +170,21 @@ def test_dropout_on_the_large_row_kernels_c512(e512):
 
 # ---- other widths ------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("C,b", [
-    (256, 16),   # gathered GEMMs at the smallest width that has them (C % 256 == 0), smallest gathered batch
-    (256, 48),   # gathered, FC wgrad through the transposes (48 % 32 != 0)
-    (256, 64),   # gathered + fc_tr
-    (384, 37),   # 9 C % 256 != 0: no k_wgrad3_tr on the convs, no gathered GEMMs; odd batch
-    (384, 64),   # the same at the default batch (fc_tr on, K = 6 C = 2304)
-])
+OTHER_WIDTHS = {
+    # gathered GEMMs at the smallest width that has them (C % 256 == 0), smallest gathered batch
+    (256, 16): {**_GATHERED, "wgrad": {**_GATHERED["wgrad"], 4: "transpose", 5: "transpose"}},
+    # gathered, FC wgrad through the transposes (48 % 32 != 0)
+    (256, 48): {**_GATHERED, "wgrad": {**_GATHERED["wgrad"], 4: "transpose", 5: "transpose"}},
+    # gathered + FC wgrad on k_wgrad3_tr
+    (256, 64): {**_GATHERED, "wgrad": {**_GATHERED["wgrad"], 4: "tr_act", 5: "tr_act"}},
+    # 9 C % 256 != 0: no k_wgrad3_tr on the convs, no gathered GEMMs; odd batch
+    (384, 37): {"gathered": False, "wgrad": _TRANSPOSES},
+    # the same at the default batch (FC wgrad on k_wgrad3_tr, K = 6 C = 2304)
+    (384, 64): {"gathered": False, "wgrad": {1: "transpose", 2: "transpose", 3: "transpose", 4: "tr_act", 5: "tr_act"}},
+}
+
+
+@pytest.mark.parametrize("C,b", OTHER_WIDTHS)
 def test_other_widths(engine_mod, C, b):
     """Training at C = 256 and 384 (inference is tested at both), default set."""
     e = _engine(engine_mod, C)
@@ -151,10 +196,42 @@ def test_other_widths(engine_mod, C, b):
         e.close()
 
 
+# ---- routes no other GPU case reaches ------------------------------------------------------------------------------------------------
+
+# (C, batch, {option: value}, routes): the smallest case for each per-layer route that the step plan can choose and no other case of this
+# module, of tests/test_train_layers_gpu.py or of tests/test_train_gpu.py takes (tests/test_train_plan_cpu.py
+# test_every_reachable_route_runs_on_the_gpu lists what would be missing without them)
+NEW_ROUTES = [
+    # f32 forward with k_wgrad3_tr on the convs: k_im2col writes the f32 matrix and the bf16 pairs, no half pairs (16: the smallest batch
+    # at which conv2, conv3 and conv4 all have their rows in 32s)
+    (256, 16, {"train_fwd_x3": 0}, {"gathered": False, "fwd": {1: "f32", 2: "f32", 3: "f32"}, "wgrad": {1: "tr_col", 2: "tr_col", 3: "tr_col"},
+                                    "im2col": {0: {"f32", "bf16"}, 1: {"f32", "bf16"}, 2: {"f32", "bf16"}}}),
+    # conv3's register-staged f32 forward in 128 x 128 tiles: 64 of them need 20 b > 31 x 128 rows at two column tiles
+    (256, 199, {"train_gemm": 0, "train_fwd_dma": 0}, {"fwd_kernel": {1: "gemm_f32_128", 2: "gemm_f32_128", 3: "gemm_f32_64"}}),
+]
+
+
+@pytest.mark.parametrize("C,b,switches", [c[:3] for c in NEW_ROUTES], ids=[f"{c[0]}-{c[1]}-" + "-".join(f"{k}{v}" for k, v in c[2].items()) for c in NEW_ROUTES])
+def test_routes_no_other_case_reaches(engine_mod, C, b, switches):
+    e = _engine(engine_mod, C)
+    try:
+        for key, val in switches.items():
+            e.set_option(key, val)
+        p = perturbed_params(e, 1, seed=5500 + b, C=C)
+        boards, pis, vs = make_batch(b, seed=6500 + b)
+        check_step(e, p, C, boards, pis, vs, f"C={C} b={b} {switches}")
+    finally:
+        e.close()
+
+
 # ---- the shipped switches -------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("b", [64, 128])
-@pytest.mark.parametrize("switch", ["train_implicit", "train_wgrad_tr", "train_gemm3_ring"])
+SHIPPED_SWITCHES = ["train_implicit", "train_wgrad_tr", "train_gemm3_ring"]
+SWITCH_BATCHES = [64, 128]
+
+
+@pytest.mark.parametrize("b", SWITCH_BATCHES)
+@pytest.mark.parametrize("switch", SHIPPED_SWITCHES)
 def test_shipped_switches_off_at_c512(e512, switch, b):
     """Each shipped option turned off alone at C = 512: the im2col + col2im conv GEMMs instead of the gathered ones, wgrad through the
     transposes instead of k_wgrad3_tr, every x3 GEMM on k_gemm3 instead of the ring."""
@@ -167,7 +244,7 @@ def test_shipped_switches_off_at_c512(e512, switch, b):
         _restore(e512)
 
 
-@pytest.mark.parametrize("b", [64, 128])
+@pytest.mark.parametrize("b", SWITCH_BATCHES)
 def test_fork_is_bit_identical_at_c512(e512, b):
     """"train_fork" 1 (the wgrad chains on a second stream branch, here around the gathered wgrad: events ev_dz / ev_tr) gives the
     same bits as 0: single steps with dropout, and a short az_net_train with the captured graph and with direct launches."""

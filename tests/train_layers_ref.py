@@ -489,6 +489,42 @@ def case_id(case):
     return f"C{C}-b{b}-set{''.join(map(str, gs))}" + "".join(f"-{k}0" for k in sw)
 
 
+# case id -> the routes the case is in the table for, in the words of tests/train_plan_twin.decode ({"gathered": bool}, {field: {layer:
+# value}}, layers 0..5 = conv1..conv4, fc1, fc2).  tests/test_train_plan_cpu.py holds the step plan (csrc/az_train_plan.h) to every entry.
+def _table_routes():
+    bn = lambda small: {l: "small" if l in small else "large" for l in range(6)}
+    gathered = {"gathered": True, "wgrad": {1: "tr_gather", 2: "tr_gather", 3: "tr_gather"}, "dgrad": {1: "x3_gather"}, "col2im": {1: False, 2: True, 3: True}}
+    fc = lambda route: {4: route, 5: route}
+    out = {}
+    for gs in GEMM_SETS:
+        x3 = gs[0] == 1
+        convs = {l: "transpose" if x3 else "f32" for l in (1, 2, 3)}
+        for b, spec in (
+            (2, {"bn": bn((2, 3, 4, 5))}),                        # conv1 / conv2 have 84 rows: the large-row kernels; one launch for the rest
+            (11, {"bn": bn((4, 5))}),                             # conv4's (66 rows) on the large-row kernels
+            (37, {"gathered": False, "wgrad": {0: "f32", **convs, **fc("transpose" if x3 else "f32")}}),      # odd: transposes + launch_gemm3, ragged tiles
+            (65, {"bn": bn(())}),                                 # the FC BatchNorm on the large-row kernels
+            (128, {"fwd_kernel": fc("gemm_f32_dma" if gs[1] else "gemm_f32_64"), "wgrad": {**convs, **fc("tr_act" if x3 else "f32")}}),
+        ):
+            out[case_id((128, gs, {}, b))] = spec
+    for b, fcw in ((16, "transpose"), (32, "tr_act"), (48, "transpose")):
+        out[case_id((256, DEFAULT_SET, {}, b))] = {**gathered, "wgrad": {**gathered["wgrad"], **fc(fcw)}}
+    out[case_id((256, DEFAULT_SET, {"train_implicit": 0}, 32))] = {
+        "gathered": False, "fwd": {1: "x3_col", 2: "x3_col", 3: "x3_col"}, "wgrad": {1: "tr_col", 2: "tr_col", 3: "tr_col", **fc("tr_act")},
+        "dgrad": {1: "x3", 2: "x3", 3: "x3"}, "col2im": {1: True, 2: True, 3: True}, "im2col": {l: {"f16", "bf16"} for l in range(3)}}
+    out[case_id((256, DEFAULT_SET, {"train_wgrad_tr": 0}, 32))] = {"gathered": False, "wgrad": {l: "transpose" for l in range(1, 6)}}
+    out[case_id((256, DEFAULT_SET, {"train_gemm3_ring": 0}, 32))] = {        # a gathered A exists on the ring kernel only; every other x 3 GEMM on k_gemm3
+        **gathered, "fwd_kernel": {1: "gemm3_ring", 2: "gemm3_ring", 3: "gemm3_ring"}, "dgrad_kernel": {1: "gemm3_ring", 2: "gemm3", 3: "gemm3", 4: "gemm3", 5: "gemm3"}}
+    out[case_id((384, DEFAULT_SET, {}, 37))] = {"gathered": False, "wgrad": {l: "transpose" for l in range(1, 6)}}      # 9 C % 256 != 0
+    out[case_id((512, DEFAULT_SET, {}, 32))] = {**gathered, "wgrad": {**gathered["wgrad"], **fc("tr_act")}}
+    out[case_id((512, (0, 1, 0), {}, 32))] = {"gathered": False, "fwd": {l: "f32" for l in range(6)}, "wgrad": {l: "f32" for l in range(6)},
+                                              "dgrad": {l: "f32" for l in range(1, 6)}}
+    return out
+
+
+TABLE_ROUTES = _table_routes()
+
+
 # ---- the whole step, kernel by kernel -----------------------------------------------------------------------------------
 def check_step(dev, p, C, boards, pis, vs, gemm_set=(1, 1, 1), mask_seed=0, dropout=0.0):
     """Every kernel of one step against its reference.  dev: {"z", "a", "mean", "invstd", "dact", "dz": lists of six arrays as read,
