@@ -116,6 +116,14 @@ class Coach:
         # new best ("train_keep_best", "train_patience").  `history` and the .examples files keep every tuple.  The engine's trainer only.
         # 0 (the default): the engine is never asked and reports and files are what they were
         self.validation_share, self.keep_best, self.patience = 0.0, False, 0
+        # Reanalyse (Engine.reanalyse; include/az_reanalyse.h).  reanalyse_sims > 0: every iteration, once the new
+        # window is appended and the oldest dropped and BEFORE the .examples file is written, the pi of every tuple of every older history
+        # entry is replaced by a fresh search of reanalyse_sims simulations with the current model in its self-play class: temp 1, seed +
+        # iteration, game ids reanalyse_first_game_id(iteration, entry) + tuple, the Coach's forced playouts / Gumbel rule on, root noise off,
+        # the playout cap untouched.  z is kept; with value_target_q > 0 the older entries' z is blended with the fresh root value.  The
+        # file holds what was trained on, so a resumed run is byte-identical.  The report gains t_reanalyse and reanalysed.  Every rank holds
+        # the whole history and runs the same deterministic calls.  0 (the default): the engine is never asked, files are what they were
+        self.reanalyse_sims = 0
         self.history = collections.deque()
         self.start_iteration = 0
         os.makedirs(self.dir, exist_ok=True)
@@ -200,6 +208,28 @@ class Coach:
         return self._scoped(self.arena_opening_plies > 0, lambda: self.engine.set_arena_openings(self.arena_opening_plies),
                             lambda: self.engine.set_arena_openings(0))
 
+    def reanalyse_history(self, model_id, iteration, seed):
+        """Coach.reanalyse_sims: re-search every history entry but the newest (csrc/az_reanalyse.h states the rule; include/az_host.hpp
+        Coach::reanalyse_history is the other host).  Returns the tuples re-searched."""
+        if self.selfplay_class != -1:
+            self.engine.net_set_class(model_id, self.selfplay_class)
+        done = 0
+        with self._selfplay_forced_playouts(), self._selfplay_gumbel():
+            for hi in range(reanalyse_entries(len(self.history))):
+                boards, pis, vs = self.history[hi]
+                if vs.shape[0] == 0:
+                    continue
+                want = {"counts": None, "q": None, "selected": None, "root_prior": None}
+                r = self.engine.reanalyse(self.reanalyse_sims, model_id, boards=boards, temp=1.0, seed=seed + iteration,
+                                          first_game_id=reanalyse_first_game_id(iteration, hi), concurrent=self.num_episode_threads,
+                                          max_depth=self.max_depth, cpuct=self.cpuct, reserve=self.mcts_reserve_size,
+                                          num_sim_threads=self.num_sim_threads, out=want)
+                if self.value_target_q > 0:
+                    vs = self.engine.blend_z(vs, r["root_q"], self.value_target_q)
+                self.history[hi] = (boards, r["pi"], vs)
+                done += int(vs.shape[0])
+        return done
+
     def execute_episodes(self, model_id, iteration, seed):
         """The self-play fan-out of src/coach.rs:241-272: num_eps x execute_episode, sharded by global game id."""
         from . import dist as azdist
@@ -278,6 +308,10 @@ class Coach:
             self.history.append((boards, pis, vs))                      # :282: pushed even when the play was skipped (empty entry)
             if len(self.history) > self.max_history_length:             # :285-288
                 self.history.popleft()
+            if self.reanalyse_sims > 0:                                 # before the save: a resumed run reads what this one trained on
+                t0 = time.perf_counter()
+                reanalysed = self.reanalyse_history(model_id, iteration, seed)
+                t_reanalyse = time.perf_counter() - t0
             if rank == 0:
                 self.save_train_examples(iteration)                     # :291-293
             allb = np.concatenate([h[0] for h in self.history])
@@ -406,6 +440,8 @@ class Coach:
             if self.validation_share > 0:
                 report[-1].update({"val_n": val_n, "val_loss_pi": [r[0] for r in val_rows], "val_loss_v": [r[1] for r in val_rows],
                                    "val_top1": [r[3] for r in val_rows], "best_epoch": val_best})
+            if self.reanalyse_sims > 0:
+                report[-1].update({"reanalysed": reanalysed, "t_reanalyse": t_reanalyse})
             if quality is not None:
                 report[-1]["quality"] = quality
                 report[-1]["seconds"]["quality"] = t_quality
@@ -418,6 +454,16 @@ class Coach:
                 write_state(self.dir, iteration, model_id)
             self.model_id = model_id
         return report
+
+
+def reanalyse_entries(history_len):
+    """csrc/az_reanalyse.h: the history entries [0, reanalyse_entries) are re-searched -- every one but the newest."""
+    return history_len - 1 if history_len > 1 else 0
+
+
+def reanalyse_first_game_id(iteration, history_index):
+    """csrc/az_reanalyse.h: tuple j of history entry `history_index` is re-searched on game id this + j in iteration `iteration`."""
+    return ((1 << 62) + (int(iteration) << 40) + (int(history_index) << 32)) & (2 ** 64 - 1)
 
 
 QUALITY_KEYS = ("examined", "kept", "win_to_draw", "win_to_loss", "draw_to_loss", "unknown")

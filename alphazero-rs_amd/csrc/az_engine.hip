@@ -3,6 +3,7 @@
 //
 // There is NO CPU fallback: every entry point runs the HIP kernels or fails with a status.
 #include "../../include/az_engine.h"
+#include "../../include/az_reanalyse.h"
 
 #include <dlfcn.h>
 #include <unistd.h>
@@ -483,6 +484,7 @@ struct az_engine {
     } comm_scratch;
     Scratch score_scratch;          // workspace of az_net_evaluate / az_samples_holdout and of the per-epoch validation; follows merge_scratch's rule
     Scratch target_scratch;         // workspace of az_samples_blend_z / az_samples_surprise; follows merge_scratch's rule
+    Scratch reanalyse_scratch;      // az_reanalyse's staged window, outputs and chunk arrays; follows merge_scratch's rule
     Scratch merge_scratch;          // workspace of az_samples_merge: sized by the call, kept for later calls of the same or a smaller size, given back
                                     // when a call needs under a quarter of a workspace of more than 256 MiB (a 2^24-tuple call holds over 10 GB)
     // az_solve / az_move_quality: solve_table = [counter][generation per lane, room for the device's lanes][lanes << tt_log2 entries], solve_io =
@@ -2386,6 +2388,121 @@ az_status az_gumbel_values(az_engine* e, int32_t n, uint64_t seed, const uint64_
     return per_root_values(e, "az_gumbel_values", n, game_ids, states, g_out, [&](const uint64_t* d_ids, const ulonglong2* d_states, float* d_g) {
         launch_gumbel_values(e->cfg.game, n, seed, d_ids, d_states, temp_is_zero != 0, d_g, e->stream);
     });
+}
+
+// ---- az_reanalyse (include/az_reanalyse.h) -------------------------------------------------------------------------
+// A window of stored positions through a pool of G trees, chunk after chunk on the engine's stream: arm (roots, reset flags, active bits,
+// streams), reset, the unchanged search, emit (rows [off, off + k) of the staged outputs), harvest.  Every search takes the same number of
+// steps, so no tree is refilled inside a chunk.  The host waits twice: for the check's verdict (a refused window searches nothing) and at
+// the end (the counters, the error words, the outputs).
+az_status az_reanalyse(az_engine* e, const az_reanalyse_params* p, int64_t n, const uint64_t* states, const float* boards, const uint64_t* game_ids,
+                       float* pi, float* root_q, float* root_prior, uint16_t* counts, float* q, int32_t* selected) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (az_status sr = session_refusal(e, "az_reanalyse")) return sr;                 // a search sizes, clears and retags the evaluation cache
+    if (!p) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: the params are required");
+    if (n < 0 || n > REANALYSE_MAX_POSITIONS) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: 0 .. 2^24 positions");
+    if (e->cfg.game != AZ_GAME_CONNECT_FOUR) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: the position check is Connect Four's (az_config.game = 0)");
+    if (p->num_sims < 1 || p->reserve < 8 || p->max_depth < 0 || p->concurrent < 0)
+        return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: num_sims >= 1, reserve >= 8, max_depth >= 0 and concurrent >= 0 are required");
+    if (p->concurrent > 1024 * 64) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: at most 65536 trees per chunk");
+    int T = p->num_sim_threads;
+    if (az_status st = check_threads(e, p->num_sims, &T)) return st;
+    if (az_status st = gumbel_refusal(e, T, "az_reanalyse")) return st;
+    if (e->forced_playouts_k_e6 > 0 && T > 1) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: forced_playouts_k_e6 needs num_sim_threads = 1");
+    if (n == 0) return AZ_OK;
+    if (!pi) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: pi is required");
+    if (!states && !boards) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: states or boards are required");
+    NetModel* net;
+    if (az_status st = find_net(e, p->model_id, &net)) return st;
+    int G = p->concurrent;
+    if (G == 0) {
+        G = REANALYSE_DEFAULT_CONCURRENT;
+        if (net->kind == AZ_NET_CONV) G = std::max(1, std::min(G, e->cfg.max_batch / T));
+    }
+    G = (int)std::min<int64_t>(G, n);
+    if (az_status st = check_batch(e, *net, G * T)) return st;
+    const uint64_t nodes = std::min<uint64_t>(p->reserve, reachable_slots(p->num_sims, AZ_MAX_PLIES));      // az_tree_create's capacity threshold
+    // every tree is built at its position and searched once: the root's two blocks and one per expansion
+    const uint64_t blocks = reachable_blocks(p->num_sims, 1, nodes);
+    if (az_status cs = check_tree_slots(e, blocks)) return cs;
+    ScopedTimer timer{e};
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t N = (size_t)n, Gs = (size_t)G;
+        Carve c;
+        // [hdr: verdict words, the call's readback] [inputs] [validated states] [game ids] [the six outputs] [the chunk's roots, streams, flags]
+        const size_t o_hdr = c.need(512), o_in = c.need(states ? N * 16 : N * AZ_FEATURES * 4), o_st = c.need(N * 16), o_id = c.need(game_ids ? N * 8 : 0),
+                     o_pi = c.need(N * 28), o_rq = c.need(root_q ? N * 4 : 0), o_rp = c.need(root_prior ? N * 28 : 0), o_cn = c.need(counts ? N * 14 : 0),
+                     o_q = c.need(q ? N * 28 : 0), o_sel = c.need(selected ? N * 4 : 0), o_roots = c.need(Gs * 16), o_streams = c.need(Gs * 16),
+                     o_flags = c.need(Gs);
+        char* base = (char*)e->reanalyse_scratch.fit(c.total, s);
+        uint32_t* d_verdict = (uint32_t*)(base + o_hdr);
+        CallReadback* d_rb = (CallReadback*)(base + o_hdr + 256);
+        static_assert(sizeof(CallReadback) <= 256 && RV_COUNT * sizeof(uint32_t) <= 256, "the header holds both");
+        // the whole window is staged once
+        HIPCHK(hipMemsetAsync(d_verdict, 0xFF, 256, s));
+        HIPCHK(hipMemcpyAsync(base + o_in, states ? (const void*)states : (const void*)boards, states ? N * 16 : N * AZ_FEATURES * 4, hipMemcpyDefault, s));
+        const uint64_t* d_ids = nullptr;
+        if (game_ids) {
+            HIPCHK(hipMemcpyAsync(base + o_id, game_ids, N * 8, hipMemcpyDefault, s));
+            d_ids = (const uint64_t*)(base + o_id);
+        }
+        ulonglong2* d_states = (ulonglong2*)(base + o_st);
+        launch_reanalyse_check(states ? (const SampleState*)(base + o_in) : nullptr, states ? nullptr : (const float*)(base + o_in), n, d_states, d_verdict, s);
+        const uint32_t first = read_verdict(d_verdict + RV_FIRST, s);      // the first wait: a refused window searches nothing
+        if (first != 0xFFFFFFFFu)
+            return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: position " + std::to_string(first >> 7) + ": " + reanalyse_bad_text(first & 0x7Fu));
+        TreeLease lease;
+        acquire_trees(e, lease, G, blocks, nodes, hash_entries(p->num_sims, 1), T, s);
+        TreeHost& th = *lease;
+        ulonglong2* d_roots = (ulonglong2*)(base + o_roots);
+        ulonglong2* d_streams = (ulonglong2*)(base + o_streams);
+        uint8_t* d_flags = (uint8_t*)(base + o_flags);
+        const ReanalyseOut out{(float*)(base + o_pi), root_q ? (float*)(base + o_rq) : nullptr, root_prior ? (float*)(base + o_rp) : nullptr,
+                               counts ? (uint16_t*)(base + o_cn) : nullptr, q ? (float*)(base + o_q) : nullptr,
+                               selected ? (int32_t*)(base + o_sel) : nullptr};
+        // the root-move record of az_tree_get_action_prob, each tree on its own (seed, game id)
+        RootMove mv = root_move_for(e, th, p->num_sims, (float)p->cpuct, true);
+        if (uses_root_stream(mv)) mv.stream.stream = d_streams;
+        if (mv.gumbel.m != 0u) mv.gumbel.temp_threshold = p->temp == 0.0f ? INT32_MIN : INT32_MAX;
+        ScopedRootMove armed;
+        armed.install(th, mv);
+        const SearchParams sp{(uint32_t)p->max_depth, (float)p->cpuct};
+        prepare_cache(e, dedup_applies(e, *net), (uint64_t)n * ((uint64_t)p->num_sims + 1), s);
+        // chunks back to back; every chunk's search is sized by the pool (one captured graph serves them all, the short last one included)
+        for (int64_t off = 0; off < n; off += G) {
+            const int k = (int)std::min<int64_t>(G, n - off);
+            launch_reanalyse_arm(th.d, d_states, d_ids, p->seed, p->first_game_id, off, k, d_roots, d_streams, d_flags, s);
+            launch_reset_trees(th.d, d_flags, s, d_roots);
+            run_search(e, th, d_roots, p->num_sims, sp, *net, G);
+            launch_reanalyse_emit(th.d, p->temp, d_streams, off, k, out, d_verdict, s);
+            launch_harvest(th.d, th.d_totals, nullptr, s);
+        }
+        launch_call_readback(th.d_totals, e->cache.stat, th.d.err, d_rb, s);
+        CallReadback rb;
+        uint32_t verdict[RV_COUNT];
+        HIPCHK(hipMemcpyAsync(&rb, d_rb, sizeof rb, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(verdict, d_verdict, sizeof verdict, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(pi, out.pi, N * 28, hipMemcpyDefault, s));
+        if (root_q) HIPCHK(hipMemcpyAsync(root_q, out.root_q, N * 4, hipMemcpyDefault, s));
+        if (root_prior) HIPCHK(hipMemcpyAsync(root_prior, out.root_prior, N * 28, hipMemcpyDefault, s));
+        if (counts) HIPCHK(hipMemcpyAsync(counts, out.counts, N * 14, hipMemcpyDefault, s));
+        if (q) HIPCHK(hipMemcpyAsync(q, out.q, N * 28, hipMemcpyDefault, s));
+        if (selected) HIPCHK(hipMemcpyAsync(selected, out.selected, N * 4, hipMemcpyDefault, s));
+        HIPCHK(hipStreamSynchronize(s));                    // the second wait
+        HIPCHK(hipGetLastError());
+        resolve_profile(e);
+        fold_dedup(e, rb.dd);
+        fold_tree_totals(e, rb.totals, dedup_applies(e, *net));
+        e->stats.moves += (uint64_t)n;
+        if (az_status st = report_tree_errors(e, th, rb.err)) {
+            const std::string where = verdict[RV_FULL] != 0xFFFFFFFFu ? "position " + std::to_string(verdict[RV_FULL])
+                                                                       : "a position of the chunk at " + std::to_string(verdict[RV_CHUNK]);
+            return fail(e, st, "az_reanalyse: " + where + ": " + e->err);
+        }
+        return AZ_OK;
+    } catch (const HipFail& f) { return fail_hip(e, f); }
 }
 
 // ---- shared tree batch: many host threads, one slot (one AsyncMcts) each ---------------------------------------------------

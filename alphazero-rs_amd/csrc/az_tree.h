@@ -21,6 +21,7 @@
 #include "az_playout.h"
 #include "az_forced.h"
 #include "az_opening.h"
+#include "az_reanalyse.h"
 
 namespace az {
 
@@ -345,6 +346,28 @@ void launch_root_noise_eta(int game, int n, uint64_t seed, const uint64_t* game_
 void launch_gumbel_values(int game, int n, uint64_t seed, const uint64_t* game_ids, const ulonglong2* states, bool temp_is_zero, float* g_out, hipStream_t s);
 // get_action_prob's epilogue for each request with its own temperature and RNG stream (root_policy), plus its status word
 void launch_slot_root_policy(const TreeDev& t, const SlotReq* req, int n, SlotOut* out, hipStream_t s);
+// ---- az_reanalyse (include/az_reanalyse.h): a window of stored positions through a pool of trees, chunk by chunk -----------------------------
+// the staged outputs of a call, rows by position (pi is always there; the others may be nullptr)
+struct ReanalyseOut {
+    float* pi;               // [n][7]
+    float* root_q;           // [n]
+    float* root_prior;       // [n][7]
+    uint16_t* counts;        // [n][7]
+    float* q;                // [n][7]
+    int32_t* selected;       // [n]
+};
+// the call's verdict words, all ones before the first kernel: RV_FIRST = (index << 7 | verdict bits) of the first refused position
+// (csrc/az_reanalyse.h); RV_FULL = the first position whose tree ran full; RV_CHUNK = the offset of the first chunk that saw an error word
+enum ReanalyseVerdict { RV_FIRST = 0, RV_FULL = 1, RV_CHUNK = 2, RV_COUNT = 4 };
+// validates the n positions (states, or with states == nullptr boards [n][84]) and writes their states to out [n]
+void launch_reanalyse_check(const SampleState* states, const float* boards, int64_t n, ulonglong2* out, uint32_t* verdict, hipStream_t s);
+// trees [0, k) take positions [off, off + k): roots[g], reset_flags[g] = 1, head.active = 1, streams[g] = (seed, game_ids ? game_ids[off + g] :
+// first_game_id + off + g); trees [k, G) go inactive with reset_flags 0
+void launch_reanalyse_arm(const TreeDev& t, const ulonglong2* states, const uint64_t* game_ids, uint64_t seed, uint64_t first_game_id, int64_t off,
+                          int k, ulonglong2* roots, ulonglong2* streams, uint8_t* reset_flags, hipStream_t s);
+// get_action_prob's epilogue (root_policy on streams[g]) and k_selfplay_record's arithmetic for trees [0, k), into rows [off, off + k) of out
+void launch_reanalyse_emit(const TreeDev& t, float temp, const ulonglong2* streams, int64_t off, int k, const ReanalyseOut& out, uint32_t* verdict,
+                           hipStream_t s);
 // what one get_action_prob call hands back besides pi / counts / q: written into PINNED host memory by k_call_readback
 struct CallReadback {
     unsigned long long totals[ST_TOTALS];

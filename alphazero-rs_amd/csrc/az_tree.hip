@@ -1434,6 +1434,98 @@ __global__ __launch_bounds__(64) void k_selfplay_record(TreeDev t, GamesDev gd, 
     if (sub == 0) rec.root_q[so] = target_root_finish(acc, N);
 }
 
+// ---- az_reanalyse (include/az_reanalyse.h): the three kernels around the unchanged search ---------------------------
+// The check: one thread per position of the whole window.  verdict[RV_FIRST] ends as (index << 7 | verdict bits) of the FIRST position that
+// is refused (atomicMin over a word that starts at all ones); the validated state goes to out[i] (an empty board in a refused one's place).
+__global__ __launch_bounds__(256) void k_reanalyse_check(const SampleState* __restrict__ states, const float* __restrict__ boards, int64_t n,
+                                                         ulonglong2* __restrict__ out, uint32_t* __restrict__ verdict) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint64_t mine, theirs;
+    const uint32_t b = reanalyse_check(states, boards, i, &mine, &theirs);
+    if (b) atomicMin(&verdict[RV_FIRST], ((uint32_t)i << 7) | b);
+    out[i] = b ? make_ulonglong2(0ull, 0ull) : make_ulonglong2(mine, theirs);
+}
+// The arm: tree g < k takes position off + g -- its root, its reset flag, its active bit and its (seed, game id) stream, which is the root
+// noise's and the Gumbel variates' while either is on and the emit's tie-break stream always; the trees of a short last chunk go inactive
+// and keep what they hold.
+__global__ __launch_bounds__(256) void k_reanalyse_arm(TreeDev t, const ulonglong2* __restrict__ states, const uint64_t* __restrict__ game_ids,
+                                                       uint64_t seed, uint64_t first_game_id, int64_t off, int k, ulonglong2* __restrict__ roots,
+                                                       ulonglong2* __restrict__ streams, uint8_t* __restrict__ reset_flags) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= t.G) return;
+    const bool on = g < k;
+    t.head[g].head.active = on ? 1u : 0u;
+    reset_flags[g] = on ? 1 : 0;
+    if (!on) return;
+    const int64_t i = off + g;
+    roots[g] = states[i];
+    streams[g] = make_ulonglong2(seed, game_ids ? game_ids[i] : first_game_id + (uint64_t)i);
+}
+// The emit: k_root_policy's body with the tree's own game id, plus k_selfplay_record's arithmetic on the same finished tree, into row off + g
+// of the six outputs (8 lanes per tree, lane a = action a: a wave writes 8 consecutive rows).  A tree the search left inactive (its arena
+// ran out at the root) or that stands at its capacity while the search raised a capacity error is blamed: the smallest such position ends
+// in verdict[RV_FULL]; the first chunk that sees any error word set leaves its offset in verdict[RV_CHUNK].
+template <class G, int RR>
+__global__ __launch_bounds__(64) void k_reanalyse_emit(TreeDev t, float temp, const ulonglong2* __restrict__ streams, int64_t off, int k,
+                                                       ReanalyseOut out, uint32_t* __restrict__ verdict) {
+    constexpr int GW = G::GROUP;
+    constexpr int NA = G::ACTIONS;
+    static_assert(NA == TARGET_ACTIONS, "az_target.h's rule is stated for 7 actions");
+    const int tid = blockIdx.x * 64 + threadIdx.x;
+    const int g = tid / GW, sub = tid % GW;
+    if (g >= k) return;
+    const uint32_t any_err = t.err[ERR_CAPACITY] | t.err[ERR_HASH_FULL] | t.err[ERR_PATH] | t.err[ERR_TERMINAL_ROOT];
+    if (g == 0 && sub == 0 && any_err) atomicMin(&verdict[RV_CHUNK], (uint32_t)off);
+    const TreeHead h = head_load(t, g);
+    const bool full_err = (t.err[ERR_CAPACITY] | t.err[ERR_HASH_FULL]) != 0u;
+    if (!h.active || (full_err && (h.len + BLOCK_SLOTS > t.R || h.count + BLOCK_SLOTS > t.reserve_nodes))) {
+        if (sub == 0) atomicMin(&verdict[RV_FULL], (uint32_t)(off + g));
+        if (!h.active) return;
+    }
+    const size_t base = (size_t)g * t.R;
+    // R and the stored priors, read as k_selfplay_record reads them
+    const NodeRec pr = node_load(node_ptr(t, base, h.root));
+    const uint32_t nchild = (pr.meta >> META_NCHILD_SHIFT) & 7u, cb = pr.child_base;
+    uint32_t ca = 0, cn = 0;
+    float cq = 0.0f, cp = 0.0f;
+    if ((uint32_t)sub < nchild) {
+        const NodeRec cr = node_load(node_ptr(t, base, cb + sub));
+        const uint64_t cc = cr.link != NONE ? node_ctr(node_ptr(t, base, cr.link)) : cr.ctr;
+        ca = cr.meta & META_A_MASK;
+        cn = ctr_n(cc);
+        cq = ctr_q(cc);
+        cp = __uint_as_float(cr.prior);
+    }
+    uint32_t an = 0u;
+    float aq = 0.0f, ap = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        const uint32_t aj = gshfl<GW>(ca, j), nj = gshfl<GW>(cn, j);
+        const float qj = gshflf<GW>(cq, j), pj = gshflf<GW>(cp, j);
+        if ((uint32_t)j < nchild && aj == (uint32_t)sub) { an = nj; aq = qj; ap = pj; }
+    }
+    float acc = 0.0f;
+    uint32_t N = 0u;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) target_root_term(acc, N, gshfl<GW>(an, a), gshflf<GW>(aq, a));
+    // get_action_prob's epilogue on the tree's own stream
+    const ulonglong2 st = streams[g];
+    const typename G::State s = G::unpack(node_key(t, base, h.root));
+    const RootPolicy rp = root_policy<G, RR>(t, h.root, g, sub, temp, st.x, st.y, (uint64_t)G::stones(s));
+    const size_t row = (size_t)(off + g);
+    if (sub < NA) {
+        out.pi[row * NA + sub] = rp.pi;
+        if (out.counts) out.counts[row * NA + sub] = (uint16_t)rp.count;
+        if (out.q) out.q[row * NA + sub] = rp.q;
+        if (out.root_prior) out.root_prior[row * NA + sub] = ap;
+    }
+    if (sub == 0) {
+        if (out.root_q) out.root_q[row] = target_root_finish(acc, N);
+        if (out.selected) out.selected[row] = rp.sel;
+    }
+}
+
 // ---- FREE-RUNNING self-play: every slot on its own timeline ("selfplay_async") -------------------------------------------------------
 // The lock-step driver runs one simulation per tree per forward, and every tree waits for the move boundary of all: of 8192 trees only
 // ~40 % put a row into a step's batch (the others hit the evaluation cache, a terminal node or a transposition), so the net runs on
@@ -1817,6 +1909,20 @@ void launch_selfplay_move(const TreeDev& t, const GamesDev& gd, SelfplayMovePara
 }
 void launch_selfplay_record(const TreeDev& t, const GamesDev& gd, const SearchRecDev& rec, hipStream_t s) {
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_selfplay_record<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, gd, rec));
+}
+void launch_reanalyse_check(const SampleState* states, const float* boards, int64_t n, ulonglong2* out, uint32_t* verdict, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_reanalyse_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, states, boards, n, out, verdict);
+}
+void launch_reanalyse_arm(const TreeDev& t, const ulonglong2* states, const uint64_t* game_ids, uint64_t seed, uint64_t first_game_id, int64_t off,
+                          int k, ulonglong2* roots, ulonglong2* streams, uint8_t* reset_flags, hipStream_t s) {
+    hipLaunchKernelGGL(k_reanalyse_arm, dim3((t.G + 255) / 256), dim3(256), 0, s, t, states, game_ids, seed, first_game_id, off, k, roots, streams,
+                       reset_flags);
+}
+void launch_reanalyse_emit(const TreeDev& t, float temp, const ulonglong2* streams, int64_t off, int k, const ReanalyseOut& out, uint32_t* verdict,
+                           hipStream_t s) {
+    if (k <= 0) return;
+    AZ_FOR_RR(t, AZ_FOR_GAME(t.game, hipLaunchKernelGGL((k_reanalyse_emit<TG, RR>), dim3(group_blocks(k)), dim3(64), 0, s, t, temp, streams, off, k, out, verdict)));
 }
 void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                        SelfplayMoveParams mp, int num_sims, int first, int max_iters, hipStream_t s) {

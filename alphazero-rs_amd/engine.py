@@ -100,6 +100,21 @@ EXPORTS = [
 COMM_ID_BYTES = 128
 
 
+class az_reanalyse_params(C.Structure):
+    _fields_ = [("concurrent", C.c_int32), ("num_sims", C.c_int32), ("max_depth", C.c_int32), ("cpuct", C.c_int32), ("model_id", C.c_int32),
+                ("num_sim_threads", C.c_int32), ("temp", C.c_float), ("reserve", C.c_uint64), ("seed", C.c_uint64), ("first_game_id", C.c_uint64)]
+
+
+# the symbols of the extension headers (include/az_reanalyse.h): exported by the same library, declared outside include/az_engine.h
+EXT_EXPORTS = ["az_reanalyse"]
+REANALYSE_ID_BASE = 1 << 62
+
+
+def reanalyse_first_game_id(iteration, history_index):
+    """csrc/az_reanalyse.h: the first game id of the Coach's re-search of history entry `history_index` in iteration `iteration`."""
+    return (REANALYSE_ID_BASE + (int(iteration) << 40) + (int(history_index) << 32)) & (2 ** 64 - 1)
+
+
 def load_library(path=LIB_PATH):
     if not os.path.exists(path):
         raise ImportError(
@@ -180,8 +195,12 @@ def load_library(path=LIB_PATH):
         "az_comm_destroy": (i32, [vp]),
         "az_gather_samples": (i32, [vp, C.POINTER(az_samples), i32, C.POINTER(az_samples), vp]),
         "az_allreduce_u64": (i32, [vp, vp, i32]),
+        # include/az_reanalyse.h (EXT_EXPORTS)
+        "az_reanalyse": (i32, [vp, C.POINTER(az_reanalyse_params), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
+        if name in EXT_EXPORTS and not hasattr(lib, name):      # an older build loaded through AZ_ENGINE_LIB (A/B runs): the entry's own method raises
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -576,6 +595,39 @@ class Engine:
     def tree_selected(self, tree):
         """az_tree_get_selected of a TreeBatch (see TreeBatch.selected)."""
         return tree.selected()
+
+    def reanalyse(self, num_sims, model_id, *, states=None, boards=None, game_ids=None, temp=1.0, seed=0, first_game_id=0, concurrent=0,
+                  max_depth=1000, cpuct=1, reserve=1000000, num_sim_threads=1, out=None):
+        """az_reanalyse (include/az_reanalyse.h): a fresh search of each of n stored positions (states [n,2] u64 or boards [n,2,6,7]
+        f32; game_ids u64 [n], None = first_game_id + i) with model_id as it is now.  Row i is bit for bit what a one-tree
+        get_action_prob says after reset(states[i]).  Arrays may be numpy arrays or torch tensors (host or device).  Returns a dict: pi
+        [n,7], root_q [n], root_prior [n,7], counts u16 [n,7], q [n,7], selected i32 [n]; out = a dict of caller arrays or tensors to
+        write into instead (a key that is missing is allocated, a key that is None is not asked for; pi is always returned)."""
+        if not hasattr(self._lib, "az_reanalyse"):
+            raise RuntimeError("the loaded engine library has no az_reanalyse (a build older than include/az_reanalyse.h)")
+        if (states is None) == (boards is None):
+            raise ValueError("states or boards, not both")
+        if states is not None and not hasattr(states, "data_ptr"):
+            states = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, 2)
+        if boards is not None and not hasattr(boards, "data_ptr"):
+            boards = np.ascontiguousarray(boards, dtype=np.float32).reshape(-1, 2, 6, 7)
+        n = int(len(states if states is not None else boards))
+        if game_ids is not None and not hasattr(game_ids, "data_ptr"):
+            game_ids = np.ascontiguousarray(game_ids, dtype=np.uint64).reshape(n)
+        shapes = {"pi": ((n, ACTIONS), np.float32), "root_q": ((n,), np.float32), "root_prior": ((n, ACTIONS), np.float32),
+                  "counts": ((n, ACTIONS), np.uint16), "q": ((n, ACTIONS), np.float32), "selected": ((n,), np.int32)}
+        res = dict(out or {})
+        for k, (shape, dt) in shapes.items():
+            if k not in res:
+                res[k] = np.zeros(shape, dt)
+        if res["pi"] is None:
+            raise ValueError("pi is always returned")
+        p = az_reanalyse_params(concurrent, num_sims, max_depth, cpuct, model_id, num_sim_threads, float(temp), reserve,
+                                int(seed) & (2 ** 64 - 1), int(first_game_id) & (2 ** 64 - 1))
+        self._check(self._lib.az_reanalyse(self._h, C.byref(p), n, _as_ptr(states), _as_ptr(boards), _as_ptr(game_ids), _as_ptr(res["pi"]),
+                                           _as_ptr(res["root_q"]), _as_ptr(res["root_prior"]), _as_ptr(res["counts"]), _as_ptr(res["q"]),
+                                           _as_ptr(res["selected"])))
+        return res
 
     # ---- Coach::execute_episode x many ----
     def selfplay(self, n_games, num_sims, model_id, seed=0, first_game_id=0, concurrent=0, temp_threshold=15,

@@ -1,7 +1,7 @@
 // examples/connect_four.rs (src lines 45-80) on the C++ host: the same Coach::setup parameters, the engine behind it.
 // Build:  g++ -std=c++17 -O2 -I include examples/connect_four.cpp -o connect_four -L alphazero-rs_amd -laz_engine
 //         (and -Wl,-rpath,$PWD/alphazero-rs_amd)
-// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]] [--value-target-q L] [--surprise S] [--validation SHARE[,PATIENCE[,best]]]
+// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]] [--value-target-q L] [--surprise S] [--validation SHARE[,PATIENCE[,best]]] [--reanalyse SIMS]
 //         selfplay_fp8 = 1: the episodes are played in the fp8 class, the arena gate in bf16 (Coach::selfplay_class)
 //         root_noise_eps > 0 (e.g. 0.25, with root_noise_alpha 0.3; default alpha 1): Dirichlet root noise in the episodes (Coach::root_noise_eps)
 //         eval_mirror = 1: mirror-canonical leaf evaluation for the whole loop, episodes and gate (Coach::eval_mirror)
@@ -26,6 +26,8 @@
 //         --validation SHARE[,PATIENCE[,best]] (anywhere on the line, e.g. 0.05 or 0.05,3,best): held-out validation -- a share SHARE of the
 //         window's positions is never trained on and scored at the end of every epoch; PATIENCE > 0 stops after that many epochs without a
 //         new best, best keeps the best epoch's weights (Coach::validation_share / patience / keep_best)
+//         --reanalyse SIMS (anywhere on the line, e.g. 50): every iteration the pi of every tuple of the older history windows is replaced by a
+//         fresh search of SIMS simulations with the current net, before the window is saved and trained on (Coach::reanalyse_sims)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,7 +48,8 @@ int main(int argc, char** argv) {
         }
         return v;
     };
-    const std::string gumbel = take("--gumbel"), value_q = take("--value-target-q"), surprise_s = take("--surprise"), validation = take("--validation");
+    const std::string gumbel = take("--gumbel"), value_q = take("--value-target-q"), surprise_s = take("--surprise"), validation = take("--validation"),
+                      reanalyse_s = take("--reanalyse");
     const std::string dir = argc > 1 ? argv[1] : "./checkpoint";
     const size_t iters = argc > 2 ? std::strtoul(argv[2], nullptr, 10) : 1;       // num_iters, examples/connect_four.rs:65
     const size_t eps = argc > 3 ? std::strtoul(argv[3], nullptr, 10) : 1;         // num_eps, :66
@@ -83,6 +86,7 @@ int main(int argc, char** argv) {
             if (c1 != std::string::npos) coach.patience = (size_t)std::strtoul(validation.c_str() + c1 + 1, nullptr, 10);
             coach.keep_best = c2 != std::string::npos && validation.substr(c2 + 1) == "best";
         }
+        if (!reanalyse_s.empty()) coach.reanalyse_sims = (size_t)std::strtoul(reanalyse_s.c_str(), nullptr, 10);
         if (!gumbel.empty()) {
             coach.gumbel_m = std::strtol(gumbel.c_str(), nullptr, 10);
             const size_t c1 = gumbel.find(','), c2 = c1 == std::string::npos ? c1 : gumbel.find(',', c1 + 1);
@@ -103,6 +107,7 @@ int main(int argc, char** argv) {
             if (coach.validation_share > 0 && !r.val_loss_pi.empty())
                 std::printf("iteration %zu: %zu held out, %zu epochs, best epoch %d with val loss (%.4f, %.4f) top1 %.4f\n", r.iteration, r.val_n, r.val_loss_pi.size(),
                             (int)r.best_epoch, r.val_loss_pi[(size_t)r.best_epoch], r.val_loss_v[(size_t)r.best_epoch], r.val_top1[(size_t)r.best_epoch]);
+            if (coach.reanalyse_sims > 0) std::printf("iteration %zu: %zu older tuples re-searched in %.2f s\n", r.iteration, r.reanalysed, r.t_reanalyse);
             if (coach.merge_weighted) std::printf("iteration %zu: rows drawn by multiplicity, total weight %zu\n", r.iteration, r.samples_weight);
         }
         return 0;

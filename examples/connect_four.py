@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--value-target-q", type=float, default=0.0, metavar="L")   # value target (1 - L) z + L q: the game outcome mixed with the root value of the tuple's own search, e.g. 0.5 (Coach.value_target_q)
     ap.add_argument("--surprise", type=float, default=0.0, metavar="S")   # policy surprise weighting: the iteration's tuples resampled, a share S of the weight in proportion to KL(pi || root prior), e.g. 0.5 (Coach.surprise_share)
     ap.add_argument("--validation", default=None, metavar="SHARE[,PATIENCE[,best]]")   # held-out validation, e.g. 0.05 or 0.05,3,best: a share SHARE of the window's positions is never trained on and scored at the end of every epoch; PATIENCE > 0 stops after that many epochs without a new best, best keeps the best epoch's weights (Coach.validation_share / patience / keep_best)
+    ap.add_argument("--reanalyse", type=int, default=0, metavar="SIMS")   # every iteration the pi of every tuple of the older history windows is replaced by a fresh search of SIMS simulations with the current net, before the window is saved and trained on, e.g. 50 (Coach.reanalyse_sims)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
     ap.add_argument("--eval-mirror", action="store_true")    # mirror-canonical leaf evaluation for the whole loop (Coach.eval_mirror)
     a = ap.parse_args()
@@ -80,6 +81,7 @@ def main():
         coach.gumbel_c_visit, coach.gumbel_c_scale = (float(parts[1]) if len(parts) > 1 else 50.0), (float(parts[2]) if len(parts) > 2 else 1.0)
     coach.arena_opening_plies = a.arena_openings
     coach.value_target_q, coach.surprise_share = a.value_target_q, a.surprise
+    coach.reanalyse_sims = a.reanalyse
     coach.weight_decay, coach.clip_norm, coach.ema_decay = a.weight_decay, a.clip_norm, a.ema
     if a.lr_schedule:
         parts = a.lr_schedule.split(",")
@@ -104,6 +106,8 @@ def main():
         if "val_n" in r:
             print(r["iteration"], "held out", r["val_n"], "val loss_pi", [round(x, 4) for x in r["val_loss_pi"]], "loss_v", [round(x, 4) for x in r["val_loss_v"]],
                   "top1", [round(x, 4) for x in r["val_top1"]], "best epoch", r["best_epoch"])
+        if "reanalysed" in r:
+            print(r["iteration"], "older tuples re-searched", r["reanalysed"], "in", round(r["t_reanalyse"], 2), "s")
         if "quality" in r:
             print(r["iteration"], "move quality from", coach.solve_min_stones, "stones:", r["quality"])
     e.close()

@@ -14,6 +14,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "az_engine.h"
+#include "az_reanalyse.h"
 // Bound weakly, for one reason: the CPU tests link this header against recording doubles of the ABI that define only the entries a
 // Coach used before position averaging (tests/cpp/test_root_noise_host_cpu.cpp and its like), and Coach::learn names az_samples_merge.
 // With a real engine library the symbol resolves as any other; without it Coach::merge_positions panics instead of calling through null.
@@ -55,6 +57,8 @@
 #pragma weak az_samples_holdout
 #pragma weak az_net_train_set_validation
 #pragma weak az_net_train_validation
+// Coach::reanalyse_sims / az_host::reanalyse: with reanalyse_sims 0 (the default) no Coach calls it.
+#pragma weak az_reanalyse
 
 namespace az_host {
 
@@ -374,6 +378,29 @@ inline Surprised surprise(const Engine& e, const std::vector<uint64_t>& states, 
     return r;
 }
 
+// ---- az_reanalyse (include/az_reanalyse.h): a fresh search of each of n stored positions with a model as it is now ------------------------
+// positions as states [n][2] or (states == nullptr) boards [n][84]; game_ids [n] or nullptr (p.first_game_id + i).  Row i of every array is
+// what a one-tree az_tree_get_action_prob says after az_tree_reset(t, &states[i]); want_search = false leaves counts, q and selected empty
+struct Reanalysed { std::vector<float> pi, root_q, root_prior, q; std::vector<uint16_t> counts; std::vector<int32_t> selected; };
+inline Reanalysed reanalyse(const Engine& e, const az_reanalyse_params& p, int64_t n, const uint64_t* states, const float* boards,
+                            const uint64_t* game_ids = nullptr, bool want_search = true) {
+    if (!az_reanalyse) throw Panic("reanalyse: the linked engine library has no az_reanalyse");
+    if (n < 0) throw Panic("reanalyse: n < 0");
+    const size_t N = (size_t)n;
+    Reanalysed r;
+    r.pi.resize(N * 7); r.root_q.resize(N); r.root_prior.resize(N * 7);
+    if (want_search) { r.q.resize(N * 7); r.counts.resize(N * 7); r.selected.resize(N); }
+    e.check(az_reanalyse(e.raw(), &p, n, states, boards, game_ids, r.pi.data(), r.root_q.data(), r.root_prior.data(),
+                         want_search ? r.counts.data() : nullptr, want_search ? r.q.data() : nullptr, want_search ? r.selected.data() : nullptr));
+    return r;
+}
+// The Coaches' rule (csrc/az_reanalyse.h states it; alphazero-rs_amd/coach.py is the other host): in iteration `it`, once the new window is
+// appended and the oldest dropped, every history entry h but the last is re-searched, tuple j of it on game id
+// reanalyse_first_game_id(it, h) + j with seed + it as the call's seed
+constexpr uint64_t REANALYSE_ID_BASE = 1ull << 62;
+inline uint64_t reanalyse_first_game_id(uint64_t iteration, uint64_t history_index) { return REANALYSE_ID_BASE + (iteration << 40) + (history_index << 32); }
+inline size_t reanalyse_entries(size_t history_len) { return history_len > 1 ? history_len - 1 : 0; }
+
 inline Ratings rating_fit(const std::vector<uint64_t>& wld, size_t K, double prior_games = 2.0) {
     if (!az_rating_fit) throw Panic("rating_fit: the linked engine library has no az_rating_fit");
     if (wld.size() != K * K * 3) throw Panic("rating_fit: wld must hold K * K * 3 counts");
@@ -631,7 +658,10 @@ class Coach {
     // val_n, val_loss_pi / val_loss_v / val_top1 (one entry per epoch) and best_epoch (with validation_share > 0): the held-out part of the
     // window and its score at the end of every epoch; 0, empty and -1 with it off
     struct Report { size_t iteration, samples, nwins, pwins, draws, model_id; bool accepted; std::vector<float> losses; size_t samples_raw; uint64_t quality[2][6]; size_t samples_weight;
-                    size_t val_n; std::vector<double> val_loss_pi, val_loss_v, val_top1; int32_t best_epoch; };
+                    size_t val_n; std::vector<double> val_loss_pi, val_loss_v, val_top1; int32_t best_epoch;
+                    // reanalysed (with reanalyse_sims > 0): the tuples of the older history entries whose pi this iteration re-searched, and the
+                    // seconds that took; 0 with it off
+                    size_t reanalysed; double t_reanalyse; };
 
     // Coach::setup(checkpoint_directory, + the reference's 14 numeric parameters), src/coach.rs:38-103
     static Coach setup(Engine& e, const std::string& checkpoint_directory, size_t mcts_reserve_size, float update_threshold,
@@ -813,6 +843,31 @@ class Coach {
         return h;
     }
 
+    // Coach::reanalyse_sims: the pi of every tuple of every history entry but the newest becomes az_reanalyse's under the current model
+    // (in its self-play class), with the Coach's forced playouts / Gumbel rule on, root noise off and the playout cap untouched; z is kept,
+    // or with value_target_q > 0 blended with the fresh root value.  Returns the tuples re-searched.  Every rank holds the whole history and
+    // runs the same deterministic calls: no exchange
+    size_t reanalyse_history(size_t model_id, size_t iteration, uint64_t seed) {
+        if (selfplay_class != AZ_NET_CLASS_ENGINE) e_.net_set_class(model_id, selfplay_class);
+        ScopedOption forced_guard(forced_playouts_k > 0, [&] { e_.set_forced_playouts(forced_playouts_k, policy_prune); },
+                                  [&] { e_.set_forced_playouts(0.0, false); });
+        ScopedOption gumbel_guard(gumbel_m > 0, [&] { e_.set_gumbel(gumbel_m, gumbel_c_visit, gumbel_c_scale); }, [&] { e_.set_gumbel(0); });
+        size_t done = 0;
+        for (size_t hi = 0; hi < reanalyse_entries(history.size()); ++hi) {
+            HistoryEntry& h = history[hi];
+            if (h.len() == 0) continue;
+            az_reanalyse_params p{};
+            p.concurrent = (int32_t)num_episode_threads; p.num_sims = (int32_t)reanalyse_sims; p.max_depth = (int32_t)max_depth; p.cpuct = cpuct;
+            p.model_id = (int32_t)model_id; p.num_sim_threads = (int32_t)num_sim_threads; p.temp = 1.0f; p.reserve = mcts_reserve_size;
+            p.seed = seed + (uint64_t)iteration; p.first_game_id = reanalyse_first_game_id(iteration, hi);
+            Reanalysed r = reanalyse(e_, p, (int64_t)h.len(), nullptr, h.boards.data(), nullptr, false);
+            h.pis.swap(r.pi);
+            if (value_target_q > 0) h.vs = blend_z(e_, h.vs, r.root_q, value_target_q);
+            done += h.len();
+        }
+        return done;
+    }
+
     // Coach::learn(skip_first_play), src/coach.rs:169-396.  Engine model slots: `model_id` is the current net,
     // `model_id + 1` the candidate.
     static constexpr size_t RESUMED = (size_t)-1;     // learn(): continue from the live model of the resumed run (else 0)
@@ -851,6 +906,13 @@ class Coach {
             }
             history.push_back(std::move(h));                                    // :282: pushed even when the play was skipped
             if (history.size() > max_history_length) history.pop_front();      // :285-288
+            size_t reanalysed = 0;
+            double t_reanalyse = 0.0;
+            if (reanalyse_sims > 0) {                                 // before the save: a resumed run reads what this one trained on
+                const auto t0 = std::chrono::steady_clock::now();
+                reanalysed = reanalyse_history(model_id, iteration, seed);
+                t_reanalyse = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            }
             if (rank_ == 0) save_train_examples(iteration);                       // :291-293 (one writer per run)
             size_t n = 0;
             for (auto& h : history) n += h.len();
@@ -940,6 +1002,7 @@ class Coach {
             r.losses.resize(2 * (size_t)az_net_train_history(e_.raw(), nullptr, 0));
             az_net_train_history(e_.raw(), r.losses.data(), (int32_t)(r.losses.size() / 2));
             r.val_n = val_n; r.best_epoch = -1;
+            r.reanalysed = reanalysed; r.t_reanalyse = t_reanalyse;
             if (val_n > 0) {
                 const Validation v = train_validation(e_);
                 for (size_t k = 0; k < v.rows.size() / 4; ++k) { r.val_loss_pi.push_back(v.rows[4 * k]); r.val_loss_v.push_back(v.rows[4 * k + 1]); r.val_top1.push_back(v.rows[4 * k + 3]); }
@@ -1074,6 +1137,12 @@ class Coach {
     // files, the merge and the trainers see ordinary tuples; merge_positions + merge_weighted turn the duplicates back into draw weights.
     // Both 0 (the default): the engine is never asked
     double value_target_q = 0.0, surprise_share = 0.0;
+    // Reanalyse (az_reanalyse; include/az_reanalyse.h).  reanalyse_sims > 0: every iteration, once the new window is
+    // appended and the oldest dropped and BEFORE the .examples file is written, the pi of every tuple of every older history entry is
+    // replaced by a fresh search of reanalyse_sims simulations with the current model (reanalyse_history above; temp 1, seed + iteration,
+    // game ids reanalyse_first_game_id(iteration, entry) + tuple).  The file holds what was trained on, so a resumed run is byte-identical.
+    // Report::reanalysed / t_reanalyse.  0 (the default): the engine is never asked and every file is what it was
+    size_t reanalyse_sims = 0;
     // Held-out validation (az_samples_holdout / az_net_train_set_validation; csrc/az_score.h).  validation_share (0 .. 1): every iteration the
     // assembled window is split by the hold-out rule BEFORE merge and shuffle, with learn()'s constant seed -- a function of the position
     // alone, so a position (and its mirror image) is on the same side in every iteration; the rest is trained on, the held-out part is
