@@ -40,7 +40,7 @@ def _build(LIB, suffix, extra_flags, force, verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     # every header under csrc/ is a dependency of every source: a new one needs no entry here
     hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")))
-    hdrs += [os.path.join(CSRC, "..", "..", "include", h) for h in ("az_engine.h", "az_reanalyse.h")]
+    hdrs += [os.path.join(CSRC, "..", "..", "include", h) for h in ("az_engine.h", "az_reanalyse.h", "az_search_stop.h")]
     # a library newer than every source and header is current even where the object files did not travel with it
     if not force and not _stale(LIB, [os.path.join(CSRC, s) for s in SOURCES] + hdrs):
         return LIB

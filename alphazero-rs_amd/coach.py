@@ -74,6 +74,10 @@ class Coach:
         # "eval_mirror" (Engine.set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
         # run under the mirror-canonical function F, so the gate compares like with like.  False (the default): the engine is never asked
         self.eval_mirror = False
+        # The decided-move stop (Engine.set_search_stop; include/az_search_stop.h): set ONCE at the start of learn()
+        # for the whole loop -- the episodes' temperature-0 moves and every move of the arena gate end once they can no longer change.
+        # False (the default): the engine is never asked
+        self.search_stop = False
         # Position averaging (Engine.merge_samples): every iteration's concatenated window is merged to one tuple per distinct position --
         # mean pi, mean z -- before the shuffle, so the shuffle and NNet::train see the merged set; `history` and the <iter>.examples files
         # stay raw (resume is unaffected, a later iteration may merge differently).  merge_canonical also merges a position with its
@@ -294,6 +298,8 @@ class Coach:
         free = getattr(self.engine, "net_free", None)
         if self.eval_mirror:
             self.engine.set_eval_mirror(True)
+        if self.search_stop:
+            self.engine.set_search_stop(True)
         for iteration in range(self.start_iteration, self.start_iteration + self.num_iters):
             t_play = t_train = t_arena = 0.0
             boards, pis, vs = np.zeros((0, 2, 6, 7), np.float32), np.zeros((0, 7), np.float32), np.zeros(0, np.float32)

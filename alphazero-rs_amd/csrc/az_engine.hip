@@ -4,6 +4,7 @@
 // There is NO CPU fallback: every entry point runs the HIP kernels or fails with a status.
 #include "../../include/az_engine.h"
 #include "../../include/az_reanalyse.h"
+#include "../../include/az_search_stop.h"
 
 #include <dlfcn.h>
 #include <unistd.h>
@@ -361,6 +362,12 @@ struct az_engine {
     // Gumbel root search with sequential halving on the same moves ("gumbel_m" 0 = off, "gumbel_c_visit_e6", "gumbel_c_scale_e6"); never the
     // arena or the slot calls
     int64_t gumbel_m = 0, gumbel_c_visit_e6 = GUMBEL_C_VISIT_E6_DEFAULT, gumbel_c_scale_e6 = GUMBEL_C_SCALE_E6_DEFAULT;
+    // the decided-move stop (include/az_search_stop.h; csrc/az_stop.h): az_search_stop_set's switch, the device counters the count kernel
+    // adds to (allocated when the switch is first set to 1) and their sums, folded once per call
+    int32_t search_stop = 0;
+    DeviceMem stop_mem;
+    unsigned long long* stop_stat = nullptr;
+    uint64_t stop_totals[SS_COUNT] = {0, 0, 0, 0};
     // paired openings of az_arena, never of self-play or the tree calls ("arena_opening_plies" 0 = off; az_arena_set_opening_book)
     int64_t arena_opening_plies = 0;
     std::vector<uint64_t> ar_book;      // [entries][2] {first seat's stones, second seat's stones}; empty = no book
@@ -532,6 +539,24 @@ az_status gumbel_refusal(az_engine* e, int T, const char* who) {
     if (e->selfplay_async) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": gumbel_m and selfplay_async exclude each other");
     if (e->forced_playouts_k_e6 > 0) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": gumbel_m and forced_playouts_k_e6 exclude each other (both claim the root's arg-max)");
     return AZ_OK;
+}
+// what the entries that search refuse while the decided-move stop is on (include/az_search_stop.h).  root_rules: the entry can search by
+// "gumbel_m", "forced_playouts_k_e6" or "selfplay_async" (the arena and the tournament ignore all three)
+az_status stop_refusal(az_engine* e, int T, const char* who, bool root_rules) {
+    if (!e->search_stop) return AZ_OK;
+    if (T > 1) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": search_stop needs num_sim_threads = 1");
+    if (!root_rules) return AZ_OK;
+    if (e->selfplay_async) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": search_stop and selfplay_async exclude each other");
+    if (e->gumbel_m != 0) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": search_stop and gumbel_m exclude each other (the rule is stated for the PUCT root)");
+    if (e->forced_playouts_k_e6 > 0) return fail(e, AZ_ERR_BAD_ARGUMENT, std::string(who) + ": search_stop and forced_playouts_k_e6 exclude each other (the rule is stated for the PUCT root)");
+    return AZ_OK;
+}
+// the record of an entry whose moves have budget num_sims and are eligible when stones + 1 >= temp_threshold (az_tree.h SearchStop)
+SearchStop stop_for(const az_engine* e, int num_sims, int32_t temp_threshold) {
+    SearchStop st{};
+    if (!e->search_stop) return st;
+    st.on = 1u; st.num_sims = (uint32_t)num_sims; st.temp_threshold = temp_threshold; st.stat = e->stop_stat;
+    return st;
 }
 // The call-interleaving contract of an open self-play session (include/az_engine.h, next to az_selfplay_begin): an entry that could change
 // what the session's remaining chunks are -- a tree search (it sizes, clears and retags the evaluation cache), a write to the session's
@@ -915,8 +940,17 @@ void resolve_profile(az_engine* e) {
 
 void fold_tree_totals(az_engine* e, const unsigned long long* h, bool dedup);
 // fold the per-tree counters into the engine stats and clear them (k_harvest sums on the device)
+// fold the decided-move stop's device counters into the engine (after the call's launches; one blocking copy, only while the switch is on)
+void fold_stop(az_engine* e) {
+    if (!e->search_stop || !e->stop_stat) return;
+    unsigned long long h[SS_COUNT];
+    HIPCHK(hipMemcpy(h, e->stop_stat, sizeof h, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(e->stop_stat, 0, sizeof h));
+    for (int i = 0; i < SS_COUNT; ++i) e->stop_totals[i] += h[i];
+}
 void harvest_stats(az_engine* e, TreeHost& th, const NetModel& net) {
     harvest_dedup(e);
+    fold_stop(e);
     const bool dedup = dedup_applies(e, net);
     launch_harvest(th.d, th.d_totals, th.d_counts, e->stream);
     unsigned long long h[ST_TOTALS];
@@ -2312,6 +2346,8 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
     if (st) return st;
     st = gumbel_refusal(e, t->th.d.T, "az_tree_get_action_prob");
     if (st) return st;
+    st = stop_refusal(e, t->th.d.T, "az_tree_get_action_prob", true);
+    if (st) return st;
     ScopedTimer timer{e};
     try {
         HIPCHK(hipSetDevice(e->device));
@@ -2325,8 +2361,9 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
             std::memcpy(t->h_states, states, (size_t)G * 16);
             HIPCHK(hipMemcpyAsync(t->d_root_states, t->h_states, (size_t)G * 16, hipMemcpyHostToDevice, e->stream));
         }
-        launch_set_active(d, 1u, e->stream);
         RootMove mv = root_move_for(e, t->th, t->num_sims, (float)t->cpuct, true);
+        if (temp == 0.0f) mv.stop = stop_for(e, t->num_sims, INT32_MIN);        // (another temperature: no move is eligible, the call runs feature-off)
+        launch_set_active(d, mv.stop.on ? stop_word((uint32_t)t->num_sims, true) : 1u, e->stream);
         t->last_gumbel = mv.gumbel.m != 0u;
         if (uses_root_stream(mv)) {      // tree g's stream: (seed, first_game_id + g), from device memory so the search graph survives the call's seed
             launch_noise_streams(t->d_noise_streams, G, seed, first_game_id, e->stream);
@@ -2339,9 +2376,11 @@ az_status az_tree_get_action_prob(az_tree* t, const uint64_t* states, float temp
         prepare_cache(e, dedup_applies(e, *net), (uint64_t)G * ((uint64_t)t->num_sims + 1), e->stream);
         run_search(e, t->th, t->d_root_states, t->num_sims, sp, *net, G);
         launch_root_policy(d, temp, seed, first_game_id, t->h_pi, t->h_counts, t->h_q, e->stream);
+        launch_stop_count(d, nullptr, e->stream);
         launch_harvest(d, t->th.d_totals, t->th.d_counts, e->stream);
         launch_call_readback(t->th.d_totals, e->cache.stat, d.err, t->h_rb, e->stream);
         HIPCHK(hipStreamSynchronize(e->stream));
+        if (mv.stop.on) fold_stop(e);
         resolve_profile(e);
         fold_dedup(e, t->h_rb->dd);
         fold_tree_totals(e, t->h_rb->totals, dedup_applies(e, *net));
@@ -2409,6 +2448,7 @@ az_status az_reanalyse(az_engine* e, const az_reanalyse_params* p, int64_t n, co
     if (az_status st = check_threads(e, p->num_sims, &T)) return st;
     if (az_status st = gumbel_refusal(e, T, "az_reanalyse")) return st;
     if (e->forced_playouts_k_e6 > 0 && T > 1) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: forced_playouts_k_e6 needs num_sim_threads = 1");
+    if (az_status st = stop_refusal(e, T, "az_reanalyse", true)) return st;
     if (n == 0) return AZ_OK;
     if (!pi) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: pi is required");
     if (!states && !boards) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_reanalyse: states or boards are required");
@@ -2466,6 +2506,7 @@ az_status az_reanalyse(az_engine* e, const az_reanalyse_params* p, int64_t n, co
         RootMove mv = root_move_for(e, th, p->num_sims, (float)p->cpuct, true);
         if (uses_root_stream(mv)) mv.stream.stream = d_streams;
         if (mv.gumbel.m != 0u) mv.gumbel.temp_threshold = p->temp == 0.0f ? INT32_MIN : INT32_MAX;
+        if (p->temp == 0.0f) mv.stop = stop_for(e, p->num_sims, INT32_MIN);      // as the tree call arms it
         ScopedRootMove armed;
         armed.install(th, mv);
         const SearchParams sp{(uint32_t)p->max_depth, (float)p->cpuct};
@@ -2477,6 +2518,7 @@ az_status az_reanalyse(az_engine* e, const az_reanalyse_params* p, int64_t n, co
             launch_reset_trees(th.d, d_flags, s, d_roots);
             run_search(e, th, d_roots, p->num_sims, sp, *net, G);
             launch_reanalyse_emit(th.d, p->temp, d_streams, off, k, out, d_verdict, s);
+            launch_stop_count(th.d, nullptr, s);
             launch_harvest(th.d, th.d_totals, nullptr, s);
         }
         launch_call_readback(th.d_totals, e->cache.stat, th.d.err, d_rb, s);
@@ -2492,6 +2534,7 @@ az_status az_reanalyse(az_engine* e, const az_reanalyse_params* p, int64_t n, co
         if (selected) HIPCHK(hipMemcpyAsync(selected, out.selected, N * 4, hipMemcpyDefault, s));
         HIPCHK(hipStreamSynchronize(s));                    // the second wait
         HIPCHK(hipGetLastError());
+        if (mv.stop.on) fold_stop(e);
         resolve_profile(e);
         fold_dedup(e, rb.dd);
         fold_tree_totals(e, rb.totals, dedup_applies(e, *net));
@@ -2628,6 +2671,8 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     if (st) return st;
     st = gumbel_refusal(e, T, "az_selfplay");
     if (st) return st;
+    st = stop_refusal(e, T, "az_selfplay", true);
+    if (st) return st;
     if (e->selfplay_record_search && e->selfplay_async)
         return fail(e, AZ_ERR_BAD_ARGUMENT, "az_selfplay: selfplay_record_search and selfplay_async exclude each other");
     const int cap_sims = (int)e->playout_cap_sims;
@@ -2688,6 +2733,7 @@ static az_status selfplay_begin_impl(az_engine* e, const az_selfplay_params* p, 
     RootMove mv = root_move_for(e, th, p->num_sims, (float)p->cpuct, true);
     if (uses_root_stream(mv)) mv.stream = RootStream{p->seed, p->first_game_id, gd.gid, nullptr};      // (seed, first_game_id + the slot's episode, ply)
     if (mv.gumbel.m != 0u) mv.gumbel.temp_threshold = p->temp_threshold;
+    mv.stop = stop_for(e, p->num_sims, p->temp_threshold);       // the session captures the switch here
     if (cap_sims > 0) {
         // the slots' first moves (ply 0 of episodes 0 .. C-1) are drawn here; every later one by the move that precedes it (selfplay_move_body)
         PlayoutCap cap{mem.alloc<uint32_t>(C), (uint32_t)p->num_sims, (uint32_t)cap_sims, playout_cap_thresh24((uint64_t)e->playout_cap_full_e6)};
@@ -2788,6 +2834,7 @@ static az_status selfplay_run_until(az_engine* e, SelfplaySession& ss, int hi) {
         // a tree whose own budget is smaller sits the rest of the round out
         run_search(e, th, gd.state, ss.round_sims, ss.sp, *net, ss.active, nullptr, ss.rows_typ, gd.counters + 3);
         if (ss.rec.root_q) launch_selfplay_record(th.d, gd, ss.rec, s);
+        launch_stop_count(th.d, gd.gid, s);
         launch_selfplay_move(th.d, gd, ss.mp, s);
         if (ss.mp.refill) launch_reset_trees(th.d, gd.need_reset, s);
         HIPCHK(hipMemcpyAsync(h_ctr, gd.counters, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -2957,6 +3004,35 @@ az_status az_selfplay(az_engine* e, const az_selfplay_params* p, az_samples* out
         HIPCHK(hipStreamSynchronize(e->stream));
         return st;
     } catch (const HipFail& f) { return fail_hip(e, f); }
+}
+
+// ---- the decided-move stop (include/az_search_stop.h; csrc/az_stop.h) -----------------------------------------------
+az_status az_search_stop_set(az_engine* e, int32_t on) {
+    if (!e) return AZ_ERR_BAD_ARGUMENT;
+    if (on != 0 && on != 1) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_search_stop_set: on must be 0 or 1");
+    if (e->sp_session) return fail(e, AZ_ERR_BAD_ARGUMENT, "az_search_stop_set: search_stop cannot change while a self-play session is open");
+    if (on && !e->stop_stat) {
+        try {
+            HIPCHK(hipSetDevice(e->device));
+            unsigned long long* p = e->stop_mem.alloc<unsigned long long>(8);
+            HIPCHK(hipMemset(p, 0, 8 * sizeof(unsigned long long)));
+            e->stop_stat = p;
+        } catch (const HipFail& f) { return fail_hip(e, f); }
+    }
+    e->search_stop = on;
+    return AZ_OK;
+}
+az_status az_search_stop_get(const az_engine* e, int32_t* on) {
+    if (!e || !on) return AZ_ERR_BAD_ARGUMENT;
+    *on = e->search_stop;
+    return AZ_OK;
+}
+// the counters as the finished calls left them: no device work, so an open session never notices it
+az_status az_search_stop_stats(az_engine* e, uint64_t out[4], int32_t reset) {
+    if (!e || !out) return AZ_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < SS_COUNT; ++i) out[i] = e->stop_totals[i];
+    if (reset) for (int i = 0; i < SS_COUNT; ++i) e->stop_totals[i] = 0;
+    return AZ_OK;
 }
 
 az_status az_selfplay_get_full_plies(az_engine* e, uint64_t* mask) {
@@ -3142,6 +3218,14 @@ az_status match_run(az_engine* e, const MatchParams& m, uint64_t* pair_wld, int8
         for (int pass = 0; pass < 2; ++pass)
             for (int k = 0; k < K; ++k) (void)cache_for(e, *nets[k]);
         SearchParams sp{(uint32_t)m.max_depth, (float)m.cpuct};
+        // the decided-move stop: every move of a match is played at temperature 0 (the only part of the root-move record a match arms)
+        ScopedRootMove armed[MATCH_MAX_MODELS];
+        if (e->search_stop)
+            for (int k = 0; k < K; ++k) {
+                RootMove mv{};
+                mv.stop = stop_for(e, m.num_sims, INT32_MIN);
+                armed[k].install(*lease[k], mv);
+            }
         az_status result = AZ_OK;
         for (int ply = 0; ply <= AZ_MAX_PLIES; ++ply) {
             for (int k = 0; k < K; ++k) launch_match_sync(lease[k]->d, ad, tb[k], s);
@@ -3160,6 +3244,7 @@ az_status match_run(az_engine* e, const MatchParams& m, uint64_t* pair_wld, int8
                 HIPCHK(hipEventRecord(ev.join[i - 1], streams[i]));
                 HIPCHK(hipStreamWaitEvent(s, ev.join[i - 1], 0));
             }
+            for (int k = 0; k < K; ++k) launch_stop_count(lease[k]->d, nullptr, s);
             for (int k = 0; k < K; ++k) launch_match_move(lease[k]->d, ad, tb[k], m.seed, s);
             HIPCHK(hipMemcpyAsync(ctr, ad.counters, sizeof ctr, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
@@ -3273,6 +3358,8 @@ az_status az_arena(az_engine* e, const az_arena_params* p, uint64_t out_wld[3], 
     int T = p->num_sim_threads;
     st = check_threads(e, p->num_sims, &T);
     if (st) return st;
+    st = stop_refusal(e, T, "az_arena", false);
+    if (st) return st;
     st = check_batch(e, *nets[0], G * T);
     if (st) return st;
     st = check_batch(e, *nets[1], G * T);
@@ -3303,6 +3390,7 @@ az_status az_tournament(az_engine* e, const int32_t* model_ids, int32_t num_mode
     }
     int T = num_sim_threads;
     if (az_status st = check_threads(e, num_sims, &T)) return st;
+    if (az_status st = stop_refusal(e, T, "az_tournament", false)) return st;
     for (int k = 0; k < K; ++k)
         if (az_status st = check_batch(e, *nets[k], (K - 1) * n * T)) return st;
     const int P = K * (K - 1) / 2;

@@ -22,6 +22,7 @@
 #include "az_forced.h"
 #include "az_opening.h"
 #include "az_reanalyse.h"
+#include "az_stop.h"
 
 namespace az {
 
@@ -118,15 +119,29 @@ struct Gumbel {
     int32_t* selected;           // [G] out (k_root_policy): the selected action of the tree's last az_tree_get_action_prob
 };
 
+// The decided-move stop (include/az_search_stop.h; the rule: az_stop.h).  on == 0 is OFF: the launchers then pick the kernels' PC_NONE /
+// PC_BUDGET instantiations, which contain none of this.  While it is on every searching tree's TreeHead.active is a stop_word: the entry
+// arms it at the start of each move (k_sync_active, k_match_sync, k_reanalyse_arm, launch_set_active) with the move's budget and whether
+// the move is eligible, k_backup_select / k_search_fixture count it down and take the decision, and launch_stop_count reads what is left
+// where the move is played or emitted.
+struct SearchStop {
+    uint32_t on;                 // 0 = OFF
+    uint32_t num_sims;           // B of a move that has no playout cap word
+    int32_t temp_threshold;      // a move is eligible when stones + 1 >= temp_threshold (the tree call and az_reanalyse: INT32_MIN for temp == 0, INT32_MAX else; the arena: INT32_MIN)
+    uint32_t pad;
+    unsigned long long* stat;    // [SS_COUNT] the engine's counters on the device (az_search_stop_stats)
+};
+
 struct RootMove {
     RootNoise noise;             // (ahead of the stream on purpose: with the stream first k_async_step<NZ> spills 32 .. 64 bytes more)
     RootStream stream;
     PlayoutCap cap;              // a self-play session's own searches only
     ForcedPlayouts forced;
     Gumbel gumbel;               // never set for the slot calls
+    SearchStop stop;             // never set for the slot calls
 };
 static_assert(sizeof(RootStream) == 32 && sizeof(RootNoise) == 8 && sizeof(PlayoutCap) == 24 && sizeof(ForcedPlayouts) == 16 && sizeof(Gumbel) == 48 &&
-              sizeof(RootMove) == 128, "no implicit padding: the record is part of the search graph's key");
+              sizeof(SearchStop) == 24 && sizeof(RootMove) == 152, "no implicit padding: the record is part of the search graph's key");
 
 struct TreeDev {
     int32_t G;               // trees
@@ -288,6 +303,9 @@ struct MatchTable {
 void launch_count_done(const int32_t* g_len, int lo, int hi, uint32_t* counter, hipStream_t s);   // *counter = #{lo <= i < hi : g_len[i] > 0}
 void launch_init_heads(const TreeDev& t, hipStream_t s);                      // zero every TreeHead, active = 1
 void launch_set_active(const TreeDev& t, uint32_t value, hipStream_t s);
+// the decided-move stop: every searching tree whose move was eligible adds its move to t.move.stop.stat (its budget: the playout cap's
+// word, else stop.num_sims; skipped: what its word has left when it was decided).  gid [G] or nullptr: trees with gid[g] < 0 do not count
+void launch_stop_count(const TreeDev& t, const int32_t* gid, hipStream_t s);
 void launch_reset_trees(const TreeDev& t, const uint8_t* flags /*[G] or nullptr = all*/, hipStream_t s,
                         const ulonglong2* roots = nullptr /*[G] root states, nullptr = initial board*/);
 void launch_root_prepare(const TreeDev& t, const EvalBatch& eb, const EvalCache& ec, const ulonglong2* root_states, hipStream_t s);

@@ -18,6 +18,9 @@ static_assert(GUMBEL_PURPOSE == RNG_GUMBEL, "az_gumbel.h restates the purpose wo
 // THE ROOT RULE of a search: one template axis with three values (forced playouts and Gumbel exclude each other, az_engine.hip), so the
 // kernels that carry it exist three times, not four
 enum RootRule : int { RR_NONE = 0, RR_FORCED = 1, RR_GUMBEL = 2 };
+// THE COUNTDOWN of a move in TreeHead.active, the PC axis of k_backup_select and k_search_fixture: none / the playout cap's budget / a budget
+// plus the decided-move stop (az_stop.h).  The kernels that only carry the cap (k_step_mt, k_async_step, k_selfplay_move) keep a bool.
+enum Countdown : int { PC_NONE = 0, PC_BUDGET = 1, PC_STOP = 2 };
 
 // ---- lane-group primitives (GW = Game::GROUP lanes per tree) ------------------------------------------------------
 template <int GW> AZ_D uint32_t gshfl(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src, GW); }
@@ -901,6 +904,30 @@ AZ_D RootPolicy root_policy(const TreeDev& t, uint32_t root, int g, int sub, flo
     return out;
 }
 
+// ---- the decided-move stop (az_stop.h; only the PC_STOP instantiations contain it) ---------------------------------------------------------
+// The decision of one tree's 8 lanes: lane j reads root child j's visit count as root_policy reads it (a link slot resolved to its canonical
+// node, the raw u16), the two largest are taken over the slots by group shuffles.  It reads the root record and its child block, the two
+// lines the selection loads next.  The caller has made the backup's counter stores visible (the wave fence).
+template <class G>
+AZ_D bool stop_root_decided(const TreeDev& t, uint32_t root, int g, int sub, uint32_t left) {
+    constexpr int GW = G::GROUP;
+    const size_t base = (size_t)g * t.R;
+    const NodeRec pr = node_load(node_ptr(t, base, root));
+    const uint32_t nchild = (pr.meta >> META_NCHILD_SHIFT) & 7u, cb = pr.child_base;
+    uint32_t n = 0u;
+    if ((uint32_t)sub < nchild) {
+        const NodeRec cr = node_load(node_ptr(t, base, cb + sub));
+        n = ctr_n(cr.link != NONE ? node_ctr(node_ptr(t, base, cr.link)) : cr.ctr);
+    }
+    uint32_t n1 = 0u, n2 = 0u;
+#pragma unroll
+    for (int j = 0; j < G::ACTIONS; ++j) {
+        const uint32_t nj = gshfl<GW>(n, j);
+        if ((uint32_t)j < nchild) stop_top2(n1, n2, nj);
+    }
+    return stop_decided(n1, n2, left);
+}
+
 // the batch a launch consumes gets its election table cleared (nothing reads the keys any more: the backups read tuniq)
 AZ_D void clear_election_keys(const EvalBatch& eb) {
     if (!eb.dedup) return;
@@ -930,10 +957,14 @@ __global__ __launch_bounds__(64) void k_backup(TreeDev t, EvalBatch eb, EvalCach
 // PC (playout cap): TreeHead.active carries the simulations the tree's move has left (1 | left << 1); a tree with none left selects nothing
 // and requests no leaf for the rest of the round -- its last backup above still runs, and its lanes still go through leaf_request's
 // workgroup-wide row claim as an inactive tree's do.  So a replayed graph chunk in which some trees are done is correct as it is.
+// PC_STOP (the decided-move stop): TreeHead.active is a stop_word (az_stop.h).  Between the backup and the selection an eligible tree that
+// still has simulations left takes the decision; a decided tree keeps its `left`, sets STOP_DECIDED_BIT and from then on is a tree with none
+// left: it selects nothing, requests no leaf and goes through leaf_request's claim as an inactive tree does.
 // RR (the root rule): select_body's forced / Gumbel branch at the root, on the tree's forced / Gumbel moves
-template <class G, bool STAMP, bool NZ, bool MIR, bool PC, int RR>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
+template <class G, bool STAMP, bool NZ, bool MIR, int PC, int RR>     // STAMP: diagnostic build, per-wave s_memtime stamps of the kernel's phases into dbg[wave][8]
 __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_prev, EvalBatch eb_next, EvalCache ec,
                                                        SearchParams sp, unsigned long long* dbg) {
+    static_assert(PC != PC_STOP || RR == RR_NONE, "the decided-move stop is stated for the PUCT root: no such instantiation (RR_OF_PC)");
     constexpr int GW = G::GROUP;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;      // 64 or 256 threads (256 only when every wave of the grid holds trees)
     const int g = tid / GW, sub = tid % GW;
@@ -957,11 +988,17 @@ __global__ __launch_bounds__(256) void k_backup_select(TreeDev t, EvalBatch eb_p
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     AZ_TSTAMP(3);
     bool go = true;
-    if constexpr (PC) go = (h.active >> 1) != 0u;
+    if constexpr (PC == PC_BUDGET) go = (h.active >> 1) != 0u;
+    if constexpr (PC == PC_STOP) {
+        go = (h.active & 1u) != 0u && stop_left(h.active) != 0u && !(h.active & STOP_DECIDED_BIT);
+        if (go && (h.active & STOP_ELIGIBLE_BIT)) {
+            if (stop_root_decided<G>(t, h.root, g, sub, stop_left(h.active))) { h.active |= STOP_DECIDED_BIT; go = false; }
+        }
+    }
     bool forced = true;
     if constexpr (RR != RR_NONE) forced = move_noisy(t, g);
     const typename G::State leaf_s = select_body<G, false, RR>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, go, forced);
-    if constexpr (PC) { if (go) h.active -= 2u; }
+    if constexpr (PC != PC_NONE) { if (go) h.active -= 2u; }
     AZ_TSTAMP(4);
     const uint32_t src = leaf_request<G, MIR>(eb_next, ec, h.leaf_kind == LEAF_EVAL, leaf_s, sub);
     AZ_TSTAMP(5);
@@ -1085,8 +1122,10 @@ AZ_D float fixture_row(typename G::State s, int kind, uint64_t salt, int sub) {
     for (int a = 0; a < G::ACTIONS; ++a) out = sub == a ? pi[a] : out;
     return out;
 }
-// PC (playout cap): tree g runs the budget of its own move, t.move.cap.word[g], instead of num_sims
-template <class G, bool NZ, bool PC, int RR>
+// PC_BUDGET (playout cap): tree g runs the budget of its own move, t.move.cap.word[g], instead of num_sims
+// PC_STOP (the decided-move stop): the budget is the one the tree's stop_word was armed with; an eligible tree takes the decision before every
+// selection and leaves with what it skipped in its word, as k_backup_select does
+template <class G, bool NZ, int PC, int RR>
 __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind,
                                                        uint64_t salt) {
     constexpr int GW = G::GROUP;
@@ -1100,10 +1139,13 @@ __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglon
     constexpr bool GZ = RR == RR_GUMBEL;
     bool noisy = true;
     if constexpr (NZ || GZ) noisy = move_noisy(t, g);
-    if constexpr (PC) num_sims = (int)(t.move.cap.word[g] & ~PLAYOUT_FULL_BIT);
+    if constexpr (PC == PC_BUDGET) num_sims = (int)(t.move.cap.word[g] & ~PLAYOUT_FULL_BIT);
+    bool eligible = false, decided = false;
+    if constexpr (PC == PC_STOP) { num_sims = (int)stop_left(h.active); eligible = (h.active & STOP_ELIGIBLE_BIT) != 0u; }
     bool forced = true;
     if constexpr (RR != RR_NONE) forced = move_noisy(t, g);
     typename G::State ls = root_prepare_body<G, NZ, GZ>(t, h, root_states, g, sub, noisy);
+    if constexpr (PC == PC_STOP) { if (h.active == 0u) eligible = false; }      // a failed root: the tree is out of this search
     for (int i = 0; i <= num_sims; ++i) {
         group_memory_sync();
         // backup of the previous leaf (i == 0: the root's priors only, S1), then the next selection
@@ -1111,8 +1153,16 @@ __global__ __launch_bounds__(64) void k_search_fixture(TreeDev t, const ulonglon
         backup_body<G, true, NZ, false, GZ>(t, h, pth, no_eb, no_ec, g, sub, t.path + (size_t)g * PATH_CAP, pv, noisy);
         if (i == num_sims) break;
         group_memory_sync();
+        if constexpr (PC == PC_STOP) {
+            if (eligible && stop_root_decided<G>(t, h.root, g, sub, (uint32_t)(num_sims - i))) {
+                h.active = stop_word((uint32_t)(num_sims - i), true) | STOP_DECIDED_BIT;
+                decided = true;
+                break;
+            }
+        }
         ls = select_body<G, false, RR>(t, h, pth, sp, g, sub, t.path + (size_t)g * PATH_CAP, nullptr, true, forced);
     }
+    if constexpr (PC == PC_STOP) { if (h.active != 0u && !decided) h.active = stop_word(0u, eligible); }
     h.leaf_kind = LEAF_NONE;
     if (sub == 0) head_store(t, g, h);
 }
@@ -1449,13 +1499,17 @@ __global__ __launch_bounds__(256) void k_reanalyse_check(const SampleState* __re
 // The arm: tree g < k takes position off + g -- its root, its reset flag, its active bit and its (seed, game id) stream, which is the root
 // noise's and the Gumbel variates' while either is on and the emit's tie-break stream always; the trees of a short last chunk go inactive
 // and keep what they hold.
+// SS (the decided-move stop is armed: temp == 0): a searching tree's word is the stop_word of an eligible move of stop.num_sims simulations
+template <bool SS>
 __global__ __launch_bounds__(256) void k_reanalyse_arm(TreeDev t, const ulonglong2* __restrict__ states, const uint64_t* __restrict__ game_ids,
                                                        uint64_t seed, uint64_t first_game_id, int64_t off, int k, ulonglong2* __restrict__ roots,
                                                        ulonglong2* __restrict__ streams, uint8_t* __restrict__ reset_flags) {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= t.G) return;
     const bool on = g < k;
-    t.head[g].head.active = on ? 1u : 0u;
+    uint32_t word = 1u;
+    if constexpr (SS) word = stop_word(t.move.stop.num_sims, stop_eligible(0, t.move.stop.temp_threshold));
+    t.head[g].head.active = on ? word : 0u;
     reset_flags[g] = on ? 1 : 0;
     if (!on) return;
     const int64_t i = off + g;
@@ -1725,6 +1779,9 @@ __device__ __forceinline__ void arena_move_body(const TreeDev& t, const TreeHead
 // Tree g of a model's batch plays the game its table names (MatchTable, az_tree.h).  Which model moves: seat 0 moves when cur_player == +1;
 // the games of a pair below ad.half seat (first listed, second listed), the rest the other way round.  The tree searches this ply when its
 // game is running and its model is to move, and its root state is gathered from the per-game array.
+// SS (the decided-move stop): a searching tree's word is the stop_word of an eligible move of stop.num_sims simulations (every move of a
+// match is played at temperature 0)
+template <bool SS>
 __global__ void k_match_sync(TreeDev t, ArenaDev ad, MatchTable tb) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= t.G) return;
@@ -1734,7 +1791,9 @@ __global__ void k_match_sync(TreeDev t, ArenaDev ad, MatchTable tb) {
     const int second = (int)(w >> 31);                                  // 0: this model is the pair's first listed ("new"), 1: its second ("old")
     const int first_model = ad.first + gi % tb.n < ad.half ? 0 : 1;     // the seating uses the arena's global index, the index inside the pair
     const int mover = ad.player[gi] == 1 ? first_model : 1 - first_model;
-    t.head[g].head.active = (ad.alive[gi] != 0 && mover == second) ? 1u : 0u;
+    uint32_t word = 1u;
+    if constexpr (SS) word = stop_word(t.move.stop.num_sims, true);
+    t.head[g].head.active = (ad.alive[gi] != 0 && mover == second) ? word : 0u;
     tb.roots[g] = ad.state[gi];
 }
 
@@ -1751,12 +1810,47 @@ __global__ __launch_bounds__(64) void k_match_move(TreeDev t, ArenaDev ad, Match
     arena_move_body<G>(t, h, ad, g, gi, (uint64_t)(ad.first + gi % tb.n), sub, seed);
 }
 
+// SS (the decided-move stop): the slot's word is the stop_word of its move -- the budget is the cap's own or stop.num_sims, the move is
+// eligible by selfplay_move_body's temperature test on the slot's ply
+template <bool SS>
 __global__ void k_sync_active(TreeDev t, GamesDev gd) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= t.G) return;
     uint32_t a = gd.gid[g] >= 0 ? 1u : 0u;
-    if (a && t.move.cap.word) a |= (t.move.cap.word[g] & ~PLAYOUT_FULL_BIT) << 1;      // playout cap: the simulations the slot's move has left
+    if constexpr (SS) {
+        if (a) a = stop_word(t.move.cap.word ? (t.move.cap.word[g] & ~PLAYOUT_FULL_BIT) : t.move.stop.num_sims, stop_eligible(gd.ply[g], t.move.stop.temp_threshold));
+    } else {
+        if (a && t.move.cap.word) a |= (t.move.cap.word[g] & ~PLAYOUT_FULL_BIT) << 1;      // playout cap: the simulations the slot's move has left
+    }
     t.head[g].head.active = a;
+}
+
+// ---- the decided-move stop's counters (az_stop.h StopStat): one thread per tree, where the move is played or emitted.  A tree that searched
+// an eligible move adds the move, its budget and -- when it was decided -- the stop and what its word has left; one atomic per counter and wave.
+__global__ __launch_bounds__(256) void k_stop_count(TreeDev t, const int32_t* __restrict__ gid) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long v[SS_COUNT] = {0ull, 0ull, 0ull, 0ull};
+    if (g < t.G && (!gid || gid[g] >= 0)) {
+        const uint32_t w = t.head[g].head.active;
+        if ((w & 1u) && (w & STOP_ELIGIBLE_BIT)) {
+            const bool decided = (w & STOP_DECIDED_BIT) != 0u;
+            v[SS_ELIGIBLE] = 1ull;
+            v[SS_STOPPED] = decided ? 1ull : 0ull;
+            v[SS_BUDGET] = t.move.cap.word ? (t.move.cap.word[g] & ~PLAYOUT_FULL_BIT) : t.move.stop.num_sims;
+            v[SS_SKIPPED] = decided ? stop_left(w) : 0u;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < SS_COUNT; ++k) {
+        uint32_t x = (uint32_t)v[k];                  // 64 lanes x < 2^30 each: the wave's sum is taken in 64 bits
+        unsigned long long sum = x;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(sum >> 32), off, 64), lo = (uint32_t)__shfl_xor((int)(uint32_t)sum, off, 64);
+            sum += ((unsigned long long)hi << 32) | lo;
+        }
+        if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&t.move.stop.stat[k], sum);
+    }
 }
 
 // ---- launchers: one instantiation of every kernel per Game policy, chosen by TreeDev.game ------------------------------
@@ -1789,6 +1883,18 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
         if ((t_).move.cap.word) { constexpr bool PC = true; __VA_ARGS__; }                    \
         else { constexpr bool PC = false; __VA_ARGS__; }                                 \
     } while (0)
+// ... and per countdown (k_backup_select, k_search_fixture): the decided-move stop while the entry point's record has stop.on, else as AZ_FOR_PC
+#define AZ_FOR_PCX(t_, ...)                                                              \
+    do {                                                                                 \
+        if ((t_).move.stop.on) { constexpr int PC = PC_STOP; __VA_ARGS__; }              \
+        else if ((t_).move.cap.word) { constexpr int PC = PC_BUDGET; __VA_ARGS__; }      \
+        else { constexpr int PC = PC_NONE; __VA_ARGS__; }                                \
+    } while (0)
+#define AZ_FOR_SS(t_, ...)                                                               \
+    do {                                                                                 \
+        if ((t_).move.stop.on) { constexpr bool SS = true; __VA_ARGS__; }                \
+        else { constexpr bool SS = false; __VA_ARGS__; }                                 \
+    } while (0)
 // ... and per root rule: Gumbel while the entry point's record has gumbel.m != 0, else forced playouts while forced.k != 0 (the two exclude
 // each other), else today's kernels.  GZ = the baseline capture of a Gumbel move in the kernels that carry no selection; FP = the rule of
 // k_step_mt / k_async_step / k_slot_root_policy, which are never launched with Gumbel on (refused for T > 1 and selfplay_async, zero for
@@ -1804,6 +1910,8 @@ static_assert(game_ok<ConnectFour>() && game_ok<ConnectThree>(),
     (void)RR; (void)GZ; (void)FP;                                                             \
     __VA_ARGS__
 #define RR_OF_FP (FP ? RR_FORCED : RR_NONE)
+// the decided-move stop is stated for the PUCT root (its entries refuse forced playouts and Gumbel): no PC_STOP instantiation carries another rule
+#define RR_OF_PC (PC == PC_STOP ? RR_NONE : RR)
 static inline int group_blocks(int G) { return (G * BLOCK_SLOTS + 63) / 64; }
 #ifdef AZ_DIAG
 // diagnostic library only: the PUCT term of best_child (src/node.rs:352-356) for n (child counter, prior bits, parent N) triples, as the
@@ -1860,11 +1968,11 @@ void launch_backup_select(const TreeDev& t, const EvalBatch& eb_prev, const Eval
     const dim3 grid(four ? (unsigned)(t.G * 8 / 256) : group_blocks(t.G)), block(four ? 256 : 64);
 #ifdef AZ_DIAG
     if (g_tree_dbg && t.G * 8 / 64 <= TREE_DBG_WAVES) {
-        AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR, PC, RR>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg))));
+        AZ_FOR_RR(t, AZ_FOR_PCX(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, true, NZ, MIR, PC, RR_OF_PC>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, g_tree_dbg))));
         return;
     }
 #endif
-    AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR, PC, RR>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr))));
+    AZ_FOR_RR(t, AZ_FOR_PCX(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_backup_select<TG, false, NZ, MIR, PC, RR_OF_PC>), grid, block, 0, s, t, eb_prev, eb_next, ec, sp, nullptr))));
 }
 void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch& eb_next, const EvalCache& ec, SearchParams sp,
                     int first, int last, hipStream_t s) {
@@ -1873,7 +1981,7 @@ void launch_step_mt(const TreeDev& t, const EvalBatch& eb_prev, const EvalBatch&
 }
 void launch_search_fixture(const TreeDev& t, const ulonglong2* root_states, SearchParams sp, int num_sims, int kind, uint64_t salt,
                            hipStream_t s) {
-    AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ, PC, RR>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt))));
+    AZ_FOR_RR(t, AZ_FOR_PCX(t, AZ_FOR_GAME_NZ(t, hipLaunchKernelGGL((k_search_fixture<TG, NZ, PC, RR_OF_PC>), dim3(group_blocks(t.G)), dim3(64), 0, s, t, root_states, sp, num_sims, kind, salt))));
 }
 void launch_root_policy(const TreeDev& t, float temp, uint64_t seed, uint64_t first_game_id, float* pi,
                         uint16_t* counts, float* q, hipStream_t s) {
@@ -1916,8 +2024,8 @@ void launch_reanalyse_check(const SampleState* states, const float* boards, int6
 }
 void launch_reanalyse_arm(const TreeDev& t, const ulonglong2* states, const uint64_t* game_ids, uint64_t seed, uint64_t first_game_id, int64_t off,
                           int k, ulonglong2* roots, ulonglong2* streams, uint8_t* reset_flags, hipStream_t s) {
-    hipLaunchKernelGGL(k_reanalyse_arm, dim3((t.G + 255) / 256), dim3(256), 0, s, t, states, game_ids, seed, first_game_id, off, k, roots, streams,
-                       reset_flags);
+    AZ_FOR_SS(t, hipLaunchKernelGGL(k_reanalyse_arm<SS>, dim3((t.G + 255) / 256), dim3(256), 0, s, t, states, game_ids, seed, first_game_id, off, k, roots,
+                                    streams, reset_flags));
 }
 void launch_reanalyse_emit(const TreeDev& t, float temp, const ulonglong2* streams, int64_t off, int k, const ReanalyseOut& out, uint32_t* verdict,
                            hipStream_t s) {
@@ -1931,14 +2039,18 @@ void launch_async_step(const TreeDev& t, const GamesDev& gd, const EvalBatch& eb
     AZ_FOR_RR(t, AZ_FOR_PC(t, AZ_FOR_GAME_NZ_MIR(t, eb_next, hipLaunchKernelGGL((k_async_step<TG, NZ, MIR, PC, RR_OF_FP>), grid, block, 0, s, t, gd, eb_prev, eb_next, ec, sp, mp, num_sims, first, max_iters))));
 }
 void launch_selfplay_sync_active(const TreeDev& t, const GamesDev& gd, hipStream_t s) {
-    hipLaunchKernelGGL(k_sync_active, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gd);
+    AZ_FOR_SS(t, hipLaunchKernelGGL(k_sync_active<SS>, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gd));
+}
+void launch_stop_count(const TreeDev& t, const int32_t* gid, hipStream_t s) {
+    if (!t.move.stop.on) return;
+    hipLaunchKernelGGL(k_stop_count, dim3((t.G + 255) / 256), dim3(256), 0, s, t, gid);
 }
 static_assert(OPENING_E_NONE == E_NONE && OPENING_E_PLUS1 == E_PLUS1, "az_opening.h restates the ecodes of az_common.h");
 void launch_arena_openings(int game, const ArenaDev& ad, const ArenaOpenings& op, hipStream_t s) {
     AZ_FOR_GAME(game, hipLaunchKernelGGL(k_arena_openings<TG>, dim3((ad.G + 255) / 256), dim3(256), 0, s, ad, op));
 }
 void launch_match_sync(const TreeDev& t, const ArenaDev& ad, const MatchTable& tb, hipStream_t s) {
-    hipLaunchKernelGGL(k_match_sync, dim3((t.G + 255) / 256), dim3(256), 0, s, t, ad, tb);
+    AZ_FOR_SS(t, hipLaunchKernelGGL(k_match_sync<SS>, dim3((t.G + 255) / 256), dim3(256), 0, s, t, ad, tb));
 }
 void launch_match_move(const TreeDev& t, const ArenaDev& ad, const MatchTable& tb, uint64_t seed, hipStream_t s) {
     AZ_FOR_GAME(t.game, hipLaunchKernelGGL(k_match_move<TG>, dim3(group_blocks(t.G)), dim3(64), 0, s, t, ad, tb, seed));

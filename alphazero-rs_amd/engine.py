@@ -108,6 +108,8 @@ class az_reanalyse_params(C.Structure):
 # the symbols of the extension headers (include/az_reanalyse.h): exported by the same library, declared outside include/az_engine.h
 EXT_EXPORTS = ["az_reanalyse"]
 REANALYSE_ID_BASE = 1 << 62
+# the symbols of include/az_search_stop.h (the decided-move stop): a list of their own, bound with the same skip
+SEARCH_STOP_EXPORTS = ["az_search_stop_set", "az_search_stop_get", "az_search_stop_stats"]
 
 
 def reanalyse_first_game_id(iteration, history_index):
@@ -197,9 +199,13 @@ def load_library(path=LIB_PATH):
         "az_allreduce_u64": (i32, [vp, vp, i32]),
         # include/az_reanalyse.h (EXT_EXPORTS)
         "az_reanalyse": (i32, [vp, C.POINTER(az_reanalyse_params), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        # include/az_search_stop.h (SEARCH_STOP_EXPORTS)
+        "az_search_stop_set": (i32, [vp, i32]),
+        "az_search_stop_get": (i32, [vp, C.POINTER(i32)]),
+        "az_search_stop_stats": (i32, [vp, vp, i32]),
     }
     for name, (res, args) in sigs.items():
-        if name in EXT_EXPORTS and not hasattr(lib, name):      # an older build loaded through AZ_ENGINE_LIB (A/B runs): the entry's own method raises
+        if name in EXT_EXPORTS + SEARCH_STOP_EXPORTS and not hasattr(lib, name):      # an older build loaded through AZ_ENGINE_LIB (A/B runs): the entry's own method raises
             continue
         fn = getattr(lib, name)
         fn.restype = res
@@ -465,6 +471,30 @@ class Engine:
         """az_set_option on this engine (keys: include/az_engine.h), e.g. set_option("net_fp8", 1): conv3 and conv4 of this engine's
         conv-net forwards on the FP8 (e4m3) matrix path -- a numerics class of its own, default off."""
         self._check(self._lib.az_set_option(self._h, key.encode(), int(value)))
+
+    def set_search_stop(self, on):
+        """az_search_stop_set (include/az_search_stop.h, default off): a temperature-0 search ends once its most visited root child leads
+        the runner-up by more than the simulations still to come -- the move and pi are the full search's, counts and q those of the search
+        as far as it ran.  Refused while a self-play session is open."""
+        if not hasattr(self._lib, "az_search_stop_set"):
+            raise RuntimeError("the loaded engine library has no az_search_stop_set (a build older than include/az_search_stop.h)")
+        self._check(self._lib.az_search_stop_set(self._h, int(on)))
+
+    def get_search_stop(self):
+        if not hasattr(self._lib, "az_search_stop_get"):
+            return 0
+        v = C.c_int32(0)
+        self._check(self._lib.az_search_stop_get(self._h, C.byref(v)))
+        return int(v.value)
+
+    def search_stop_stats(self, reset=False):
+        """az_search_stop_stats: dict of the four counters over the finished calls (eligible_moves, stopped_moves, budgeted_sims,
+        skipped_sims); reset clears them afterwards."""
+        if not hasattr(self._lib, "az_search_stop_stats"):
+            raise RuntimeError("the loaded engine library has no az_search_stop_stats (a build older than include/az_search_stop.h)")
+        out = np.zeros(4, np.uint64)
+        self._check(self._lib.az_search_stop_stats(self._h, _ptr(out), 1 if reset else 0))
+        return dict(zip(("eligible_moves", "stopped_moves", "budgeted_sims", "skipped_sims"), (int(x) for x in out)))
 
     def set_eval_mirror(self, on):
         """The opt-in "eval_mirror" (include/az_engine.h, default off): every forward of a conv model of this engine is taken on the

@@ -1,7 +1,7 @@
 // examples/connect_four.rs (src lines 45-80) on the C++ host: the same Coach::setup parameters, the engine behind it.
 // Build:  g++ -std=c++17 -O2 -I include examples/connect_four.cpp -o connect_four -L alphazero-rs_amd -laz_engine
 //         (and -Wl,-rpath,$PWD/alphazero-rs_amd)
-// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]] [--value-target-q L] [--surprise S] [--validation SHARE[,PATIENCE[,best]]] [--reanalyse SIMS]
+// Run:    ./connect_four ./checkpoint [num_iters] [num_eps] [num_sims] [num_arena_games] [selfplay_fp8] [root_noise_eps] [root_noise_alpha] [eval_mirror] [playout_cap] [forced_playouts] [arena_openings] [merge_positions] [move_quality] [--gumbel M[,CVISIT,CSCALE]] [--value-target-q L] [--surprise S] [--validation SHARE[,PATIENCE[,best]]] [--reanalyse SIMS] [--search-stop]
 //         selfplay_fp8 = 1: the episodes are played in the fp8 class, the arena gate in bf16 (Coach::selfplay_class)
 //         root_noise_eps > 0 (e.g. 0.25, with root_noise_alpha 0.3; default alpha 1): Dirichlet root noise in the episodes (Coach::root_noise_eps)
 //         eval_mirror = 1: mirror-canonical leaf evaluation for the whole loop, episodes and gate (Coach::eval_mirror)
@@ -28,6 +28,8 @@
 //         new best, best keeps the best epoch's weights (Coach::validation_share / patience / keep_best)
 //         --reanalyse SIMS (anywhere on the line, e.g. 50): every iteration the pi of every tuple of the older history windows is replaced by a
 //         fresh search of SIMS simulations with the current net, before the window is saved and trained on (Coach::reanalyse_sims)
+//         --search-stop (anywhere on the line): the decided-move stop for the whole loop -- a temperature-0 search of the episodes and every
+//         search of the gate ends once its move can no longer change (Coach::search_stop; include/az_search_stop.h)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -48,6 +50,15 @@ int main(int argc, char** argv) {
         }
         return v;
     };
+    // ... and the switch "--search-stop", which has no value
+    bool search_stop = false;
+    for (int i = 1; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--search-stop") != 0) continue;
+        search_stop = true;
+        for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+        argc -= 1;
+        break;
+    }
     const std::string gumbel = take("--gumbel"), value_q = take("--value-target-q"), surprise_s = take("--surprise"), validation = take("--validation"),
                       reanalyse_s = take("--reanalyse");
     const std::string dir = argc > 1 ? argv[1] : "./checkpoint";
@@ -86,6 +97,7 @@ int main(int argc, char** argv) {
             if (c1 != std::string::npos) coach.patience = (size_t)std::strtoul(validation.c_str() + c1 + 1, nullptr, 10);
             coach.keep_best = c2 != std::string::npos && validation.substr(c2 + 1) == "best";
         }
+        coach.search_stop = search_stop;
         if (!reanalyse_s.empty()) coach.reanalyse_sims = (size_t)std::strtoul(reanalyse_s.c_str(), nullptr, 10);
         if (!gumbel.empty()) {
             coach.gumbel_m = std::strtol(gumbel.c_str(), nullptr, 10);

@@ -43,6 +43,7 @@ def main():
     ap.add_argument("--reanalyse", type=int, default=0, metavar="SIMS")   # every iteration the pi of every tuple of the older history windows is replaced by a fresh search of SIMS simulations with the current net, before the window is saved and trained on, e.g. 50 (Coach.reanalyse_sims)
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA")   # Dirichlet root noise of the episodes, e.g. 0.25,0.3 (Coach.root_noise_eps)
     ap.add_argument("--eval-mirror", action="store_true")    # mirror-canonical leaf evaluation for the whole loop (Coach.eval_mirror)
+    ap.add_argument("--search-stop", action="store_true")    # the decided-move stop for the whole loop: a temperature-0 search of the episodes and every search of the gate ends once its move can no longer change (Coach.search_stop)
     a = ap.parse_args()
     e = azeng.Engine(device=0, max_batch=max(a.slots, a.arena, 128), net_channels=a.channels)
     e.net_init_random(0, a.seed)
@@ -66,6 +67,7 @@ def main():
     if a.selfplay_fp8:
         coach.selfplay_class = azeng.NET_CLASS_FP8
     coach.eval_mirror = a.eval_mirror
+    coach.search_stop = a.search_stop
     if a.root_noise:
         eps, _, alpha = a.root_noise.partition(",")
         coach.root_noise_eps, coach.root_noise_alpha = float(eps), float(alpha) if alpha else 1.0

@@ -29,6 +29,7 @@
 
 #include "az_engine.h"
 #include "az_reanalyse.h"
+#include "az_search_stop.h"
 // Bound weakly, for one reason: the CPU tests link this header against recording doubles of the ABI that define only the entries a
 // Coach used before position averaging (tests/cpp/test_root_noise_host_cpu.cpp and its like), and Coach::learn names az_samples_merge.
 // With a real engine library the symbol resolves as any other; without it Coach::merge_positions panics instead of calling through null.
@@ -59,6 +60,10 @@
 #pragma weak az_net_train_validation
 // Coach::reanalyse_sims / az_host::reanalyse: with reanalyse_sims 0 (the default) no Coach calls it.
 #pragma weak az_reanalyse
+// az_host::set_search_stop / search_stop_stats: no default path calls them.
+#pragma weak az_search_stop_set
+#pragma weak az_search_stop_get
+#pragma weak az_search_stop_stats
 
 namespace az_host {
 
@@ -393,6 +398,20 @@ inline Reanalysed reanalyse(const Engine& e, const az_reanalyse_params& p, int64
     e.check(az_reanalyse(e.raw(), &p, n, states, boards, game_ids, r.pi.data(), r.root_q.data(), r.root_prior.data(),
                          want_search ? r.counts.data() : nullptr, want_search ? r.q.data() : nullptr, want_search ? r.selected.data() : nullptr));
     return r;
+}
+// ---- the decided-move stop (include/az_search_stop.h) ---------------------------------------------------------------
+// on: a temperature-0 search ends once its move can no longer change; refused while a self-play session is open
+inline void set_search_stop(const Engine& e, bool on) {
+    if (!az_search_stop_set) throw Panic("set_search_stop: the linked engine library has no az_search_stop_set");
+    e.check(az_search_stop_set(e.raw(), on ? 1 : 0));
+}
+// the four counters over the finished calls; reset clears them afterwards
+struct SearchStopStats { uint64_t eligible_moves = 0, stopped_moves = 0, budgeted_sims = 0, skipped_sims = 0; };
+inline SearchStopStats search_stop_stats(const Engine& e, bool reset = false) {
+    if (!az_search_stop_stats) throw Panic("search_stop_stats: the linked engine library has no az_search_stop_stats");
+    uint64_t v[4] = {0, 0, 0, 0};
+    e.check(az_search_stop_stats(e.raw(), v, reset ? 1 : 0));
+    return SearchStopStats{v[0], v[1], v[2], v[3]};
 }
 // The Coaches' rule (csrc/az_reanalyse.h states it; alphazero-rs_amd/coach.py is the other host): in iteration `it`, once the new window is
 // appended and the oldest dropped, every history entry h but the last is re-searched, tuple j of it on game id
@@ -879,6 +898,7 @@ class Coach {
             if (rank_ == 0 && !std::filesystem::exists(w)) e_.check(az_net_save(e_.raw(), (int32_t)model_id, w.c_str()));
         }
         if (eval_mirror) e_.set_eval_mirror(true);
+        if (search_stop) set_search_stop(e_, true);
         for (size_t iteration = start_iteration; iteration < start_iteration + num_iters; ++iteration) {
             HistoryEntry h;
             if (!skip_first_play || iteration > start_iteration) {
@@ -1103,6 +1123,10 @@ class Coach {
     // "eval_mirror" (Engine::set_eval_mirror): set ONCE at the start of learn() for the whole loop -- the episodes and the arena gate both
     // run under the mirror-canonical function, so the gate compares like with like.  false (the default): the engine is never asked
     bool eval_mirror = false;
+    // The decided-move stop (az_host::set_search_stop; include/az_search_stop.h): set ONCE at the start of learn() for the whole loop -- the
+    // episodes' temperature-0 moves and every move of the arena gate end once they can no longer change.  false (the default): the engine is
+    // never asked
+    bool search_stop = false;
     // Position averaging (az_samples_merge): every iteration's concatenated window is merged to one tuple per distinct position before
     // the shuffle, so the shuffle and NNet::train see the merged set; `history` and the <iter>.examples files stay raw.  merge_canonical
     // also merges a position with its mirror image: the window already holds both orientations (symmetries are expanded before it is merged)
