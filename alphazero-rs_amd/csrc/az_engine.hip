@@ -4110,6 +4110,49 @@ long long az_diag_read_act(az_engine* e, int layer, int rows, void* out) {
     if (!e || !out || rows <= 0 || hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;
     return netws_read_act(e->ws[0], layer, rows, out);
 }
+// Diagnostic library only: ONE forward of a conv model on the engine's first stream with the three numbers a search hands the launchers
+// given apart -- the exact row count n (EvalBatch::n, read on the device), the host's bound rows_hint (the grids) and its estimate rows_typ
+// (the kernel families; 0 = none) -- where az_net_predict_states can only run rows_hint == n, rows_typ == 0.  Rows in the caller's order, no
+// de-duplication, no canonicalisation ("eval_mirror" on: refused).  All rows_hint rows of the device's pi / v are filled with
+// AZ_DIAG_HINTED_SENTINEL before the forward and all of them are copied back to the host (pi [rows_hint][7], v [rows_hint]): a row no
+// kernel wrote still holds it.  The workspace's act2 .. fc2o rows [0, rows_hint) are filled with NaN bytes first (netws_poison_acts), so
+// an element no kernel wrote reads as such and never as an earlier forward's right answer.  The readers above then read this forward's
+// layers.  Bytes copied, or -1 and nothing written.
+constexpr uint32_t AZ_DIAG_HINTED_SENTINEL = 0x7FC5A5A5u;      // a quiet NaN no kernel computes
+long long az_diag_predict_hinted(az_engine* e, int32_t model_id, const uint64_t* states, int n, int rows_hint, int rows_typ, float* pi, float* v) {
+    if (!e || !states || !pi || !v || n < 1 || rows_hint < n || rows_hint > e->cfg.max_batch || rows_typ < 0 || e->eval_mirror != 0) return -1;
+    auto it = e->nets.find(model_id);
+    if (it == e->nets.end() || it->second.kind != AZ_NET_CONV || !it->second.conv) return -1;
+    try {
+        HIPCHK(hipSetDevice(e->device));
+        DeviceMem mem;
+        const size_t rows = (size_t)rows_hint;
+        EvalBatch eb{};
+        eb.cap = rows_hint;
+        eb.n = mem.alloc<uint32_t>(1);
+        eb.state = mem.alloc<ulonglong2>(rows);
+        eb.pi = mem.alloc<float>(rows * 8);
+        eb.v = mem.alloc<float>(rows);
+        const uint32_t nb = (uint32_t)n;
+        std::vector<uint32_t> fill(rows * 8, AZ_DIAG_HINTED_SENTINEL);
+        HIPCHK(hipMemcpyAsync(eb.n, &nb, sizeof nb, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemsetAsync(eb.state, 0, rows * 16, e->stream));                       // rows past n: the empty board
+        HIPCHK(hipMemcpyAsync(eb.state, states, (size_t)n * 16, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(eb.pi, fill.data(), rows * 32, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(eb.v, fill.data(), rows * 4, hipMemcpyHostToDevice, e->stream));
+        if (!netws_poison_acts(workspace_for(e, e->stream), rows_hint, e->stream)) return -1;
+        net_forward(e, it->second, eb, rows_hint, e->stream, rows_typ, false);
+        HIPCHK(hipGetLastError());
+        std::vector<float> hp(rows * 8), hv(rows);
+        HIPCHK(hipMemcpyAsync(hp.data(), eb.pi, rows * 32, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(hv.data(), eb.v, rows * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (size_t i = 0; i < rows; ++i)
+            for (int a = 0; a < 7; ++a) pi[i * 7 + a] = hp[i * 8 + a];
+        std::memcpy(v, hv.data(), rows * 4);
+        return (long long)(rows * 32);
+    } catch (const HipFail&) { return -1; }
+}
 long long az_diag_read_conv_table(az_engine* e, int32_t model_id, int which, int first_row, int n_rows, void* out) {
     if (!e || !out || hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
     auto it = e->nets.find(model_id);

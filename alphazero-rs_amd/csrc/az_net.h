@@ -106,6 +106,8 @@ long long netws_read_conv3_out(NetWorkspace* ws, int rows, void* out);
 // copied or -1.  layer 1 act1 [8][9][C] (-1 if never allocated), 2 act2 [42][C], 3 act3 [20][C], 4 act4 [6][C], 5 fc1o [1024],
 // 6 fc2o [512].  Under net_fp8, act2 and act3 hold e4m3 bytes: these bf16 readers are meaningless there (use the _fp8 readers).
 long long netws_read_act(NetWorkspace* ws, int layer, int rows, void* out);
+// diagnostic library only: rows [0, rows) of act2 .. fc2o filled with 0xFF bytes (NaNs in bf16 and e4m3) on stream s
+bool netws_poison_acts(NetWorkspace* ws, int rows, hipStream_t s);
 // diagnostic library's reader: rows [first_row, first_row + n_rows) of a model's conv1 table t1 (which = 1: [19683] rows of [C] bf16)
 // or conv2 table u2 (which = 2: [19683 + 1] rows of [9][C] f16, the last one the appended zero row); the bytes copied or -1
 long long convnet_read_conv_table(const ConvNet* n, int which, int first_row, int n_rows, void* out);

@@ -2150,6 +2150,18 @@ long long netws_read_act(NetWorkspace* n, int layer, int rows, void* out) {
     return hipMemcpy(out, src[layer - 1], bytes, hipMemcpyDeviceToHost) == hipSuccess ? (long long)bytes : -1;
 }
 
+// Diagnostic library only: rows [0, rows) of act2 .. fc2o set to 0xFF bytes (bf16 and e4m3 NaNs) on stream s, so that what a forward
+// does not write cannot hold an earlier forward's right answer (az_diag_predict_hinted).  act1 keeps its zero halo: not touched.
+bool netws_poison_acts(NetWorkspace* n, int rows, hipStream_t s) {
+    if (!n || rows <= 0 || rows > n->max_batch) return false;
+    uint16_t* dst[5] = {n->act2, n->act3, n->act4, n->fc1o, n->fc2o};
+    const size_t per_row[5] = {42 * (size_t)n->C, 20 * (size_t)n->C, 6 * (size_t)n->C, 1024, 512};
+    bool ok = true;
+    for (int i = 0; i < 5; ++i)
+        if (dst[i]) ok &= hipMemsetAsync(dst[i], 0xFF, (size_t)rows * per_row[i] * sizeof(uint16_t), s) == hipSuccess;
+    return ok;
+}
+
 long long convnet_read_conv_table(const ConvNet* n, int which, int first_row, int n_rows, void* out) {
     if (!n || !out || (which != 1 && which != 2) || first_row < 0 || n_rows <= 0) return -1;
     const int total = which == 1 ? CONV1_PATTERNS : CONV1_PATTERNS + 1;

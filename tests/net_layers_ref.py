@@ -263,12 +263,21 @@ def conv1_rows(states, T):
     return T[patterns_of(states)]
 
 
-def forward_layers(states, folded, dtype=torch.float64, table=None):
+def conv1_from_table(states, table_ref):
+    """conv1_ref's (y, max S) from conv1_table_ref's (T, S): the rows of the states' patterns.  For thousands of states the 19683-row
+    table, computed once, is several times cheaper than conv1_ref on every board; the two are the same sums of the same terms."""
+    T, S = table_ref
+    pat = patterns_of(states)
+    return T[pat], float(S[np.unique(pat)].max())
+
+
+def forward_layers(states, folded, dtype=torch.float64, table=None, conv1=None):
     """The net layer by layer, each layer from the bf16 rounding of the one before (what the device stores):
     -> {"t1": conv1 rows, "conv2" .. "fc2": (y unrounded, S, stored = bf16-rounded y as float64), "S1": max S of conv1}.
-    table = a U_of callable (table_conv2_ref) computes conv2 from the conv2 table instead of the GEMM form."""
-    y1, S1 = conv1_ref(states, folded)
-    out = {"t1": bf16_round64(y1), "S1": float(S1.max())}
+    table = a U_of callable (table_conv2_ref) computes conv2 from the conv2 table instead of the GEMM form.
+    conv1 = conv1_from_table's pair takes the place of conv1_ref on every board."""
+    y1, S1 = conv1_ref(states, folded) if conv1 is None else conv1
+    out = {"t1": bf16_round64(y1), "S1": float(np.max(S1))}
     a = out["t1"]
     for name in LAYERS:
         if name == "conv2" and table is not None:

@@ -226,15 +226,16 @@ def off_nearest(codes, near):
 
 
 # ---- the whole exact forward ----------------------------------------------------------------------------------------
-def forward_exact(states, params, C, sa2, sa3, dtype=torch.float32):
+def forward_exact(states, params, C, sa2, sa3, dtype=torch.float32, conv1=None):
     """exact_params through the fp8 class, every layer from the stored form of the one before -> {"act2", "act3": codes, "act4",
     "fc1", "fc2": bf16 bits, "pi", "v", and what exact_conditions reads}.  conv2 is the GEMM form's sum: on exact data the table
-    entries are exact integers of at most 2048, so the table gather adds the same numbers (net_layers_ref's exact-data conditions)."""
+    entries are exact integers of at most 2048, so the table gather adds the same numbers (net_layers_ref's exact-data conditions).
+    conv1 = net_layers_ref.conv1_from_table's pair takes the place of conv1_ref on every board."""
     folded = L.fold_like_engine(params, C)
     q = quantised(params, C, sa2, sa3)
-    y1, S1 = L.conv1_ref(states, folded)
+    y1, S1 = L.conv1_ref(states, folded) if conv1 is None else conv1
     y2, S2 = L.layer_ref("conv2", L.bf16_round64(y1), folded, dtype)
-    out = {"S1": float(S1.max()), "conv2": (y2, S2), "act2": nearest_codes(y2, sa2), "scaled_max": [float(y2.max() * sa2)], "units": {}}
+    out = {"S1": float(np.max(S1)), "conv2": (y2, S2), "act2": nearest_codes(y2, sa2), "scaled_max": [float(y2.max() * sa2)], "units": {}}
     a = code_values(out["act2"])
     for name in ("conv3", "conv4"):
         y, beta, T = layer8_ref(name, a, q, dtype)

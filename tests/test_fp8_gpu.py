@@ -12,7 +12,8 @@ import pytest
 
 import net_ref_fp8 as r8
 from net_ref import exact_params, forward_ref, layout, random_params
-from test_net_gpu import _check_move_record, _flatten_log, _replay_every_episode, random_states
+from test_net_gpu import (_check_move_record, _flatten_log, _replay_every_episode, assert_every_recorded_row_is_the_net, hold_a_draining_selfplay,
+                          hold_an_arena_and_a_tree_search, random_states)
 
 pytestmark = pytest.mark.gpu
 CH = 512
@@ -192,11 +193,8 @@ def test_fp8_replay_parity_selfplay_with_refill(fp8_engine, oracle):
     logs = fp8_engine.selfplay_get_evals(n, cap)
     assert logs[0].max() <= cap and logs[0].min() > 0
     _replay_every_episode(oracle, got, logs, sims, seed, n)
-    cnt, states, pis, vs = logs
-    for g in (0, 17, n - 1):
-        k = int(min(cnt[g], 256))
-        pi2, v2 = fp8_engine.predict_states(states[g, :k], 24)
-        assert np.array_equal(pi2, pis[g, :k]) and np.array_equal(v2, vs[g, :k]), g
+    cnt, states, pis, vs = logs                      # every row of 256 games spread over the ids (with 0, 17 and the last)
+    assert_every_recorded_row_is_the_net(fp8_engine, 24, cnt, states, pis, vs, games=sorted(set(np.linspace(0, n - 1, 256).astype(int).tolist()) | {17}))
     try:
         fp8_engine.set_option("eval_dedup", 0)
         plain = fp8_engine.selfplay(n_games=n, concurrent=conc, num_sims=sims, model_id=24, seed=seed, want_boards=False)
@@ -276,8 +274,19 @@ def test_fp8_replay_parity_arena_with_two_conv_nets(fp8_engine, oracle):
     assert np.array_equal(ores, res) and owld.tolist() == wld.tolist()
     glen, gmoves = fp8_engine.arena_get_moves(num)
     _check_move_record(oracle, glen, gmoves, res)
-    for w, mid in ((0, 23), (1, 22)):
-        cnt, states, pis, vs = logs[w]
-        k = int(min(cnt[0], 128))
-        pi2, v2 = fp8_engine.predict_states(states[0, :k], mid)
-        assert np.array_equal(pi2, pis[0, :k]) and np.array_equal(v2, vs[0, :k])
+    for w, mid in ((0, 23), (1, 22)):                # every row of every game, under the right model
+        assert_every_recorded_row_is_the_net(fp8_engine, mid, *logs[w])
+
+
+@pytest.mark.parametrize("threads", [1, 2])
+@pytest.mark.parametrize("graph", [0, 8, 20])        # 20: the shipped value (no graph at 16 simulations); 8: two graph replays per move
+@pytest.mark.parametrize("dedup", [0, 1])
+def test_fp8_every_row_of_a_draining_selfplay_is_the_net(fp8_engine, dedup, graph, threads):
+    fp8_engine.net_init_random(25, seed=23)
+    hold_a_draining_selfplay(fp8_engine, 25, dedup, graph, threads)
+
+
+def test_fp8_every_row_of_an_arena_and_a_tree_search_is_the_net(fp8_engine, oracle):
+    fp8_engine.net_init_random(26, seed=24)
+    fp8_engine.net_init_random(27, seed=25)
+    hold_an_arena_and_a_tree_search(fp8_engine, oracle, 26, 27)

@@ -258,9 +258,8 @@ def test_replay_parity_selfplay(conv_engine, oracle):
     assert np.array_equal(got["moves"], ref["moves"]) and np.array_equal(got["game_len"], ref["game_len"])
     assert np.array_equal(got["pis"], ref["pis"]) and np.array_equal(got["zs"], ref["zs"])
     assert np.array_equal(got["boards"].reshape(-1, 84), ref["boards"].reshape(-1, 84))
-    # and the recorded rows are what the net returns for those states (the log is the real net output)
-    pi2, v2 = conv_engine.predict_states(fs[:256], 6)
-    assert np.array_equal(pi2, fp[:256]) and np.array_equal(v2, fv[:256])
+    # and the recorded rows are what the net returns for those states (the log is the real net output): every row of every game
+    assert_every_recorded_row_is_the_net(conv_engine, 6, cnt, states, pis, vs)
 
 
 def test_replay_parity_get_action_prob(conv_engine, oracle):
@@ -359,10 +358,9 @@ def test_bench_scale_replay_parity_with_the_conv_net(engine, oracle):
     cnt, states, pis, vs = engine.selfplay_get_evals(n, cap)
     assert cnt.max() <= cap and cnt.min() > 0
     _replay_every_episode(oracle, got, (cnt, states, pis, vs), sims, seed, n)
-    # and the recorded rows are what NNet::predict returns for those states
-    g = 17
-    pi2, v2 = engine.predict_states(states[g, :256], 21)
-    assert np.array_equal(pi2, pis[g, :256]) and np.array_equal(v2, vs[g, :256])
+    # and the recorded rows are what NNet::predict returns for those states: every row of 256 games spread over the ids (and game 17)
+    games = sorted(set(np.linspace(0, n - 1, 256).astype(int).tolist()) | {17})
+    assert_every_recorded_row_is_the_net(engine, 21, cnt, states, pis, vs, games=games)
 
 
 def test_shipped_kernel_choices_are_bit_identical(engine, oracle):
@@ -399,6 +397,97 @@ def _flatten_log(cnt, states, pis, vs, ids):
     off[1:] = np.cumsum([cnt[g] for g in ids])
     cat = lambda a: np.ascontiguousarray(np.concatenate([a[g, :cnt[g]] for g in ids]))
     return off, cat(states), cat(pis), cat(vs)
+
+
+def assert_every_recorded_row_is_the_net(engine, model_id, cnt, states, pis, vs, games=None):
+    """Replay parity feeds the engine's own recorded (pi, v) rows back to the oracle: a forward that returned stale or wrong rows at some
+    batch sizes replays perfectly.  Here ALL recorded rows of all games (of `games`, if given) are flattened, their distinct states go
+    through predict_states in chunks of 128 -- the size the layer tests hold to float64 -- and every recorded row must be its state's
+    row bit for bit.  A failure names the game, the row within the game and how many rows differ.  -> (rows, distinct states)."""
+    ids = list(range(len(cnt))) if games is None else [int(g) for g in games]
+    off, fs, fp, fv = _flatten_log(cnt, states, pis, vs, ids)
+    fs = fs.reshape(-1, 2)
+    assert len(fs) > 0 and len(fp) == len(fv) == len(fs)
+    uniq, inv = np.unique(fs, axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    npi = np.empty((len(uniq), 7), np.float32)
+    nv = np.empty(len(uniq), np.float32)
+    for o in range(0, len(uniq), 128):
+        npi[o:o + 128], nv[o:o + 128] = engine.predict_states(uniq[o:o + 128], model_id)
+    as_bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    bad = (as_bits(fp).reshape(len(fs), -1) != as_bits(npi[inv])).any(axis=1) | (as_bits(fv).reshape(-1) != as_bits(nv[inv]))
+    if bad.any():
+        rows = np.flatnonzero(bad)
+        k = np.searchsorted(off, rows, side="right") - 1
+        raise AssertionError(("recorded (pi, v) rows that are not the net's", len(rows), "of", len(fs), "in", len(np.unique(k)), "games; first (game, row in game)",
+                              [(ids[int(g)], int(r - off[g])) for g, r in zip(k[:8], rows[:8])], "model", model_id))
+    return len(fs), len(uniq)
+
+
+def hold_a_draining_selfplay(engine, model_id, dedup, graph, threads, games=192, sims=16, seed=61):
+    """One self-play call with as many slots as games: as the games end the leaf batch walks down through every count from `games`
+    (x threads) to 1 while the estimate handed to the launchers lags a move behind -- the regime tests/test_net_routes_gpu.py sweeps
+    forward by forward, here as a search produces it.  Every recorded row must be the net's."""
+    cap = 42 * (sims + 1) + 8
+    try:
+        engine.set_option("eval_dedup", dedup)
+        engine.set_option("search_graph", graph)
+        engine.reset_stats()
+        got = engine.selfplay(n_games=games, concurrent=games, num_sims=sims, model_id=model_id, seed=seed, want_boards=False, record_evals=cap,
+                              num_sim_threads=threads)
+        st = engine.stats()
+        cnt, states, pis, vs = engine.selfplay_get_evals(games, cap)
+    finally:
+        engine.set_option("eval_dedup", 1)
+        engine.set_option("search_graph", 20)
+    assert st["games"] == games and cnt.min() > 0 and cnt.max() <= cap
+    assert st["leaf_rows_executed"] > 0
+    if dedup == 0:
+        assert st["leaf_rows_executed"] == st["leaf_rows_requested"], st
+    rows, distinct = assert_every_recorded_row_is_the_net(engine, model_id, cnt, states, pis, vs)
+    assert rows == int(cnt.sum()) and rows >= sims * int(got["game_len"].min())
+    return got
+
+
+def hold_an_arena_and_a_tree_search(engine, oracle, new_id, old_id, games=192, sims=16):
+    """az_arena with two conv nets (two streams, two workspaces, the shared tagged cache) and a get_action_prob sequence on one tree batch:
+    every recorded row of either is the net's, under the right model."""
+    cap = 22 * (sims + 1) + 8
+    engine.reset_stats()
+    wld, _ = engine.arena(games, sims, new_model_id=new_id, old_model_id=old_id, seed=13, record_evals=cap)
+    assert int(wld.sum()) == games and engine.stats()["leaf_rows_executed"] > 0
+    for which, mid in ((0, new_id), (1, old_id)):
+        cnt, states, pis, vs = engine.arena_get_evals(which, games, cap)
+        assert cnt.min() > 0 and cnt.max() <= cap
+        assert_every_recorded_row_is_the_net(engine, mid, cnt, states, pis, vs)
+    G, moves = 96, 5
+    tb = engine.tree_create(G, reserve=oracle.default_reserve(sims), num_sims=sims, max_depth=1000, model_id=new_id, cpuct=1)
+    try:
+        tb.record_evals(moves * (sims + 1) + 8)
+        states = [(0, 0)] * G
+        rng = np.random.default_rng(6)
+        for _ in range(moves):                                       # (no game of five plies has ended)
+            pi, _, _ = tb.get_action_prob(np.array(states, dtype=np.uint64), 1.0, seed=4)
+            states = [oracle.c4_play(s[0], s[1], int(rng.choice([a for a in range(7) if pi[g][a] > 0]))) for g, s in enumerate(states)]
+        cnt, lstates, lpis, lvs = tb.get_evals()
+        assert cnt.min() >= moves
+        assert_every_recorded_row_is_the_net(engine, new_id, cnt, lstates, lpis, lvs)
+    finally:
+        tb.close()
+
+
+@pytest.mark.parametrize("threads", [1, 2])
+@pytest.mark.parametrize("graph", [0, 8, 20])        # 20: the shipped value (no graph at 16 simulations); 8: two graph replays per move
+@pytest.mark.parametrize("dedup", [0, 1])
+def test_every_row_of_a_draining_selfplay_is_the_net(conv_engine, dedup, graph, threads):
+    conv_engine.net_init_random(9, seed=23)
+    hold_a_draining_selfplay(conv_engine, 9, dedup, graph, threads)
+
+
+def test_every_row_of_an_arena_and_a_tree_search_is_the_net(conv_engine, oracle):
+    conv_engine.net_init_random(10, seed=24)
+    conv_engine.net_init_random(11, seed=25)
+    hold_an_arena_and_a_tree_search(conv_engine, oracle, 10, 11)
 
 
 def _replay_every_episode(oracle, got, logs, sims, seed, n, sim_threads=1, chunk=1024):

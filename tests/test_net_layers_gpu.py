@@ -19,6 +19,11 @@ Largest err / bound seen on the MI355X (information, not the bar -- the bar is 1
   C = 512, conv2_table 0: conv2 0.551  conv3 0.429  conv4 0.370  fc1 0.523  fc2 0.789
   tables, all rows: u2 0.947 / 0.888 / 0.734 at C = 128 / 256 / 512; conv1 x 2^k, k = -12 .. 12: the same figures for every k.
 Exact data: no bit differed, at any width, row count or option set.
+
+The row counts here stop at 150 with max_batch = 256, and predict_states can only run a forward whose bound is its exact count and
+which has no estimate.  Above that -- the image-resident conv3 kernel past one round and its cut tail, the ring's two-per-CU family
+and its 96 .. 192-row tiles, the FCs' family window -- and for every (exact count, bound, estimate) a search can hand the launchers,
+tests/test_net_routes_gpu.py holds the same layers to the same exact reference on a pool of 8192 states (the triples: tests/net_routes.py).
 """
 import ctypes
 
